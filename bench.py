@@ -16,6 +16,9 @@ partials per inner iteration.  Inputs are resident in HBM when the timed region 
 row-sharded over the N ranks (strong scaling: every rank draws the same matrix from the same seed and
 keeps its nnz-balanced row block), 8 MB all-reduce per inner iteration.
 
+--dump-outputs DIR writes the factors W and H of the last timed step as DIR/<name>.npy (float32; a seeded sample of a
+factor over 24 MB): the same arguments give the same inputs, so two builds can be compared output for output.
+
 The JSON line also carries
   roofline      the dominant kernel's algorithmic bytes / its mean launch time (HIP events on the
                 solver's own stream, second pass over the same K steps) against 8 TB/s
@@ -56,9 +59,29 @@ def host_cores() -> int:
     return max(1, n)
 
 
-def als_measure(a, d, mfx, k, steps, warmup) -> dict:
+DUMP_BYTES_PER_FACTOR = 24 << 20  # --dump-outputs: at most 2 x 24 MB (+ sample indices), under the 64 MB cap
+
+
+def dump_outputs(out_dir, factors) -> None:
+    """--dump-outputs: writes each factor of `factors` ({name: (float32 array, entity axis)}) as out_dir/<name>.npy.  A factor
+    larger than DUMP_BYTES_PER_FACTOR keeps a fixed, seeded sample of its entities (users / items, along `axis`, sorted), and
+    out_dir/<name>_index.npy (float64) lists which; the sample depends only on the factor's shape, so runs with the same
+    arguments write the same entries."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, (x, axis) in factors.items():
+        n, per = x.shape[axis], x.nbytes // max(1, x.shape[axis])
+        keep = DUMP_BYTES_PER_FACTOR // (per + 8)
+        if n > keep:
+            idx = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+            x = np.take(x, idx, axis=axis)
+            np.save(os.path.join(out_dir, name + "_index.npy"), idx.astype(np.float64))
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(x, dtype=np.float32))
+
+
+def als_measure(a, d, mfx, k, steps, warmup, dump_dir=None) -> dict:
     """ALS iterations (BASELINE configs[3]) on the device-resident matrix `d`: time per iteration, the two half-sweeps
-    against both of their rooflines, test RMSE."""
+    against both of their rooflines, test RMSE.  dump_dir: write the factors of the last timed iteration there."""
     import time as _t
     import torch
     p = mfx.parameter()
@@ -71,6 +94,9 @@ def als_measure(a, d, mfx, k, steps, warmup) -> dict:
     t0 = _t.perf_counter()
     rep = s.iterate(steps, with_rmse=True)
     el = _t.perf_counter() - t0
+    if dump_dir is not None:
+        W, H = s.get_factors()  # W: rows x k, H: cols x k
+        dump_outputs(dump_dir, {"W": (W, 0), "H": (H, 0)})
     kt = s.kernel_times()
     s.close()
     flops = 2.0 * (Z * k * (k + 1) + 2.0 * Z * k)  # both half-sweeps: symmetric Gramian + rhs
@@ -113,9 +139,10 @@ def als_measure(a, d, mfx, k, steps, warmup) -> dict:
 
 def bench_als(a, d, mfx, gen_s) -> None:
     """Secondary measurement (BASELINE configs[3]): ALS iteration time on the same synthetic matrix, as its own line."""
-    m = als_measure(a, d, mfx, a.k, a.steps, a.warmup)
+    m = als_measure(a, d, mfx, a.k, a.steps, a.warmup, dump_dir=a.dump_outputs)
     print(json.dumps({"metric": "ALS iteration time at k=%d" % a.k, "value": m["ms_per_iteration"], "unit": "ms",
-                      "n_gpus": 1, "steps": a.steps, "warmup": a.warmup, "higher_is_better": False, "dtype": "f32",
+                      "n_gpus": 1, "steps": a.steps, "warmup": a.warmup, "ms_per_step": m["ms_per_iteration"],
+                      "higher_is_better": False, "dtype": "f32",
                       "data": "synthetic", "config": {"workload": m["workload"]},
                       "gramian_tflops": m["gramian_tflops"], "roofline": m["roofline"], "half_sweeps": m["half_sweeps"],
                       "kernels": m["kernels"], "rmse": m["rmse"], "als_src_sha16": m["als_src_sha16"],
@@ -339,9 +366,15 @@ def main() -> None:
                          "config); config5: BASELINE configs[4], one global 10M x 1M x 1e9 matrix at k = 128 "
                          "row-sharded over the ranks (strong scaling); nnz1e9: the north star's target point "
                          "'k = 64, nnz = 1e9' on one GPU -- ten Netflix-sized user blocks, 4801890 x 17770, 990721120 ratings")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what they computed -- the factors W and H of the last timed step (rank 0's "
+                         "W block when N > 1) -- as DIR/<name>.npy, float32; a factor over 24 MB keeps a fixed, seeded sample "
+                         "of its users / items, listed in DIR/<name>_index.npy")
     ap.add_argument("--dry-run", action="store_true", help="launch plumbing only (gloo, no GPU)")
     ap.add_argument("--dry-run-fail-rank", type=int, default=-1, help="(with --dry-run) this rank exits with status 3 before the collective")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     if "WORLD_SIZE" not in os.environ and a.gpus > 1:  # bare `python bench.py --gpus N`: be the launcher
         raise SystemExit(launch_workers(a.gpus, sys.argv[1:]))
     if a.dry_run:
@@ -451,6 +484,9 @@ def main() -> None:
         elapsed = float(te[0])
     ms_per_step = 1e3 * elapsed / a.steps
     value = nnz_global / (elapsed / a.steps)
+    if a.dump_outputs is not None and rank == 0:
+        W, H = solver.get_factors()  # W: k x rows, H: k x cols
+        dump_outputs(a.dump_outputs, {"W": (W, 1), "H": (H, 1)})
 
     # ---------------- roofline: same K steps again, every launch bracketed by HIP events ------------
     ktimes = {}
