@@ -7,6 +7,7 @@
 
 #include "als_solver.hpp"
 #include "ccd_solver.hpp"
+#include "recommend.hpp"
 
 namespace mfx {
 
@@ -412,6 +413,40 @@ int mfx_als_half(int64_t nseg, int64_t nnz, const uint32_t* ptr, const uint32_t*
         MFX_REQUIRE(nseg < (int64_t) 0xFFFFFFFFll && nrows_x < (int64_t) 0xFFFFFFFFll && nnz < (int64_t) 0xFFFF0000ll,
                     "mfx_als_half: sizes exceed the 32-bit index range");
         return als_half_op(nseg, nnz, ptr, idx, val, nrows_x, X, Y, k, lambda, variant, device);
+    });
+}
+
+/* ------------------------------------------------------------------ top-N recommendation */
+int mfx_rec_create(mfx_rec_t* out, const float* W, const float* H, int64_t rows, int64_t cols, int64_t k, int layout,
+                   const mfx_csx* exclude, mfx_memspace space, int device) {
+    return guarded("mfx_rec_create", [&]() -> int {
+        MFX_REQUIRE(out, "mfx_rec_create: out is NULL");
+        *out = nullptr;
+        Recommender* r = nullptr;
+        MFX_TRY(Recommender::create(&r, W, H, rows, cols, k, layout, exclude, space, device));
+        *out = new mfx_rec_s{r};
+        return MFX_OK;
+    });
+}
+int mfx_rec_query(mfx_rec_t r, int64_t nusers, const uint32_t* users, int32_t n_top, uint32_t* items, float* scores,
+                  mfx_memspace space, int item_slices) {
+    return guarded("mfx_rec_query", [&]() -> int {
+        MFX_REQUIRE(r && r->impl, "null recommender");
+        return r->impl->query(nusers, users, n_top, items, scores, space, item_slices);
+    });
+}
+int mfx_rec_destroy(mfx_rec_t r) {
+    return guarded("mfx_rec_destroy", [&]() -> int {
+        if (!r) return MFX_OK;
+        delete r->impl;
+        delete r;
+        return MFX_OK;
+    });
+}
+int mfx_topn_metrics(int64_t nusers, const uint32_t* users, int32_t n_top, const uint32_t* items, const mfx_coo* T,
+                     float min_rating, double out[4], int64_t* users_evaluated) {
+    return guarded("mfx_topn_metrics", [&]() -> int {
+        return topn_metrics(nusers, users, n_top, items, T, min_rating, out, users_evaluated);
     });
 }
 

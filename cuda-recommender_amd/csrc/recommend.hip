@@ -1,0 +1,611 @@
+// recommend.hip -- fused top-N recommendation on gfx950 (mfx_rec_*), plus the host-side ranking metrics.
+//
+// A query never materialises the users x items score matrix.  One workgroup (four waves) owns 128 users of the batch
+// and one slice of the items.  H is repacked at create time into 32-item tiles, [tile][t chunk][2*KC t values][32
+// items], so that one LDS stage is a contiguous copy that every wave of the workgroup shares (double-buffered, one
+// barrier per stage).  Each wave keeps the W rows of its 32 users in registers as the B operand of
+// v_mfma_f32_32x32x2_f32 (lane l: W[user l&31][t = 2s + (l>>5)]) and reads the H tile as the A operand
+// (H[item l&31][t = 2s + (l>>5)]), so the accumulator has the user on the lane (column = lane & 31) and 16 items in
+// the registers (row = (r&3) + 8*(r>>2) + 4*(lane>>5)).  Every score is the fp32 FMA chain over t = 0, 1, 2, ... in
+// ascending order (one MFMA = two chained FMAs), whatever the tile, slice, batch or factor layout; k is padded with
+// zeros to the MFMA step, and k > 128 runs several t chunks into the same accumulator, same order.
+//
+// Selection: each lane holds the running threshold of its user (the N-th best score so far) and compares its 16
+// scores against it -- one VALU compare per score.  Scores that pass are appended to the user's candidate list
+// (L = pow2 >= N + 32 entries in the workspace).  When a list would overflow, the wave filters the new entries
+// against the user's exclusion row (binary search, candidates only), sorts the list (bitonic, in LDS for L <= 256,
+// in place in the workspace otherwise), keeps the best N and raises the threshold.  Items of one slice are visited
+// in ascending order, so admitting ties (score >= threshold) is only ever extra work, never a wrong answer.
+// Total order: score descending, then item ascending; -0 == +0; NaN scores are never admitted.
+//
+// Small batches split the items over `slices` (grid.y); each slice leaves its sorted top N in the workspace and
+// mfx_rec_merge selects the final N from slices * N entries.  The scores are the same numbers, so the result is
+// bitwise the one of the unsplit pass.
+#include <algorithm>
+#include <cmath>
+#include <memory>
+#include <unordered_map>
+
+#include "ccd_kernels.hpp"  // check_index_range
+#include "recommend.hpp"
+
+#define MFX_LAUNCH_CHECK() MFX_HIP(hipGetLastError())
+
+namespace mfx {
+
+namespace {
+
+using f32x16 = __attribute__((ext_vector_type(16))) float;
+
+constexpr int kRecWaves = 4;                 // waves per workgroup
+constexpr int kRecThreads = 64 * kRecWaves;
+constexpr int kRecUsers = 32 * kRecWaves;    // users per workgroup
+constexpr int kTile = 32;                    // items per LDS stage (one 32 x 32 MFMA tile per wave)
+constexpr int kScr = 256;                    // per-wave LDS sort scratch (entries); longer lists sort in the workspace
+constexpr int kMaxMerge = 8192;              // slices * N of one merge (64 KiB of LDS)
+constexpr int kMaxTop = 1024, kMaxK = 1024;
+constexpr uint32_t kPad = 0xFFFFFFFFu;
+constexpr size_t kWorkspaceCap = size_t(1) << 30;  // candidate lists of one launch (users are chunked under this)
+
+struct RecArgs {
+    const float* wp;        // [rows][kt]
+    const float* hp;        // [nblk][nch][2*KC][32]
+    const uint32_t* users;  // NULL: slot q is user q0 + q
+    uint32_t q0, nq;        // first batch slot of this launch, slots in this launch
+    const uint32_t* ex_ptr; // NULL: no exclusion
+    const uint32_t* ex_idx;
+    uint32_t cols;
+    int kt, nch, nblk, bps, n_top, L;
+    float* ls;              // [slices][nq][L] candidate lists
+    uint32_t* li;
+    uint32_t* out_items;    // [q0 + q][n_top], written here when there is one slice
+    float* out_scores;      // may be NULL
+};
+
+__device__ inline bool beats(float as, uint32_t ai, float bs, uint32_t bi) {
+    return as > bs || (as == bs && ai < bi);
+}
+
+// Every lane of the wave sees the memory operations every other lane issued before (LDS and global).
+__device__ inline void wave_sync() {
+    __threadfence_block();
+    __builtin_amdgcn_wave_barrier();
+}
+
+// Bitonic sort of P (power of two) entries, best first, by one wave.  ks / is are flat pointers (LDS or global).
+__device__ void wave_bitonic(float* ks, uint32_t* is, int P, int lane) {
+    for (int k = 2; k <= P; k <<= 1) {
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int x = lane; x < (P >> 1); x += 64) {
+                const int a = ((x & ~(j - 1)) << 1) | (x & (j - 1));
+                const int b = a + j;
+                const float sa = ks[a], sb = ks[b];
+                const uint32_t ia = is[a], ib = is[b];
+                const bool sw = (a & k) == 0 ? beats(sb, ib, sa, ia) : beats(sa, ia, sb, ib);
+                if (sw) {
+                    ks[a] = sb; ks[b] = sa;
+                    is[a] = ib; is[b] = ia;
+                }
+            }
+            wave_sync();
+        }
+    }
+}
+
+__device__ inline bool excluded(const uint32_t* ex, uint32_t lo, uint32_t hi, uint32_t item) {
+    const uint32_t end = hi;
+    while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (ex[mid] < item) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo < end && ex[lo] == item;
+}
+
+__device__ inline int wave_sum(int v) {
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    return v;
+}
+
+// One LDS stage (NF4 float4, contiguous in the packed H) through registers: the loads of stage s+1 are in flight
+// while the MFMAs of stage s run.
+template <int NV, int NF4>
+__device__ inline void load_stage(float4 (&stg)[NV], const float* src, int tid) {
+    const float4* s4 = reinterpret_cast<const float4*>(src);
+#pragma unroll
+    for (int v = 0; v < NV; ++v) {
+        const int e = tid + v * kRecThreads;
+        if (NF4 % kRecThreads == 0 || e < NF4) stg[v] = s4[e];
+    }
+}
+template <int NV, int NF4>
+__device__ inline void store_stage(const float4 (&stg)[NV], float* dst, int tid) {
+    float4* d4 = reinterpret_cast<float4*>(dst);
+#pragma unroll
+    for (int v = 0; v < NV; ++v) {
+        const int e = tid + v * kRecThreads;
+        if (NF4 % kRecThreads == 0 || e < NF4) d4[e] = stg[v];
+    }
+}
+
+template <int KC>
+__global__ __launch_bounds__(kRecThreads) void mfx_rec_topn(RecArgs a) {
+    constexpr int STAGE = 2 * KC * kTile;        // floats per LDS stage
+    constexpr int NF4 = STAGE / 4;
+    constexpr int NV = (NF4 + kRecThreads - 1) / kRecThreads;
+    __shared__ __attribute__((aligned(16))) float hb[2][STAGE];
+    __shared__ float scs[kRecWaves][kScr];
+    __shared__ uint32_t sci[kRecWaves][kScr];
+
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, h = lane >> 5, j = lane & 31;
+    const uint32_t slice = blockIdx.y;
+    const uint32_t qw0 = blockIdx.x * kRecUsers + wave * 32;
+    const uint32_t q = qw0 + j;
+    const bool uvalid = q < a.nq;
+    const uint32_t u = uvalid ? (a.users ? a.users[a.q0 + q] : a.q0 + q) : 0;
+    const int b0 = (int) slice * a.bps;
+    const int b1 = min(a.nblk, b0 + a.bps);
+    const int nst = b1 > b0 ? (b1 - b0) * a.nch : 0;
+    const bool single = gridDim.y == 1;
+    const bool lds_sort = a.L <= kScr;
+
+    float4 stg[NV];
+
+    float thr = -INFINITY;  // score of the user's N-th entry once it has N; admission is score >= thr
+    int cnt = 0;            // entries in the user's list
+    int clean = 0;          // leading entries already checked against the exclusion row (the sorted top)
+
+    // Filters, sorts and truncates the list of user slot qw0 + uj (the whole wave works on it).  fin: write the
+    // final N entries (padded) to the output (one slice) or to the head of the list (merge input).
+    auto flush = [&](int uj, bool fin) __attribute__((always_inline)) {
+        const int c_u = __shfl(cnt, uj), cl_u = __shfl(clean, uj);
+        const uint32_t uid = __shfl(u, uj);
+        const uint32_t qu = qw0 + uj;
+        const size_t base = ((size_t) slice * a.nq + qu) * (size_t) a.L;
+        int P = 1;
+        while (P < c_u) P <<= 1;
+        float* ks = lds_sort ? scs[wave] : a.ls + base;
+        uint32_t* is = lds_sort ? sci[wave] : a.li + base;
+        uint32_t elo = 0, ehi = 0;
+        if (a.ex_ptr) { elo = a.ex_ptr[uid]; ehi = a.ex_ptr[uid + 1]; }
+        wave_sync();
+        int kept = 0;
+        for (int e = lane; e < P; e += 64) {
+            float s = -INFINITY;
+            uint32_t it = kPad;
+            if (e < c_u) {
+                s = a.ls[base + e];
+                it = a.li[base + e];
+                if (e >= cl_u && ehi > elo && excluded(a.ex_idx, elo, ehi, it)) { s = -INFINITY; it = kPad; }
+                else ++kept;
+            }
+            ks[e] = s;
+            is[e] = it;
+        }
+        kept = wave_sum(kept);
+        wave_sync();
+        wave_bitonic(ks, is, P, lane);
+        const int m = min(a.n_top, kept);
+        if (fin) {
+            for (int e = lane; e < a.n_top; e += 64) {
+                float s = -INFINITY;
+                uint32_t it = kPad;
+                if (e < m) { s = ks[e]; it = is[e]; }
+                if (single) {
+                    const size_t o = (size_t) (a.q0 + qu) * a.n_top + e;
+                    a.out_items[o] = it;
+                    if (a.out_scores) a.out_scores[o] = s;
+                } else {
+                    a.ls[base + e] = s;
+                    a.li[base + e] = it;
+                }
+            }
+        } else if (lds_sort) {
+            for (int e = lane; e < m; e += 64) { a.ls[base + e] = ks[e]; a.li[base + e] = is[e]; }
+        }
+        wave_sync();
+        const float nthr = (!fin && m == a.n_top) ? ks[a.n_top - 1] : -INFINITY;
+        if (j == uj) { cnt = m; clean = m; thr = nthr; }
+        wave_sync();
+    };
+
+    float wf[KC];
+    f32x16 acc;
+    if (nst > 0) {
+        load_stage<NV, NF4>(stg, a.hp + (size_t) b0 * a.nch * STAGE, tid);
+        store_stage<NV, NF4>(stg, hb[0], tid);
+    }
+    __syncthreads();
+    for (int st = 0; st < nst; ++st) {
+        const int c = st % a.nch;
+        const int blk = b0 + st / a.nch;
+        if (st + 1 < nst) load_stage<NV, NF4>(stg, a.hp + (size_t) (b0 * a.nch + st + 1) * STAGE, tid);
+        if (a.nch > 1 || st == 0) {
+            const float* wr = a.wp + (size_t) u * a.kt + c * 2 * KC + h;
+#pragma unroll
+            for (int s = 0; s < KC; ++s) wf[s] = uvalid ? wr[2 * s] : 0.f;
+        }
+        if (c == 0) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+        }
+        const float* hbuf = hb[st & 1] + h * kTile + j;
+#pragma unroll
+        for (int s = 0; s < KC; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(hbuf[2 * s * kTile], wf[s], acc, 0, 0, 0);
+
+        if (c == a.nch - 1) {
+            const uint32_t ibase = (uint32_t) blk * kTile + 4 * h;
+            uint32_t mask = 0;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const uint32_t item = ibase + (r & 3) + 8 * (r >> 2);
+                mask |= (uint32_t) (uvalid && item < a.cols && acc[r] >= thr) << r;
+            }
+            if (__ballot(mask != 0)) {
+                const int n = __popc(mask);
+                const int n_o = __shfl_xor(n, 32);
+                const int tot = n + n_o;
+                uint64_t fm = __ballot(uvalid && h == 0 && cnt + tot > a.L);
+                while (fm) {
+                    const int uj = __ffsll((unsigned long long) fm) - 1;
+                    fm &= fm - 1;
+                    flush(uj, false);
+                }
+                if (mask) {
+                    size_t pos = ((size_t) slice * a.nq + q) * (size_t) a.L + cnt + (h ? n_o : 0);
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        if (mask >> r & 1) {
+                            a.ls[pos] = acc[r];
+                            a.li[pos] = ibase + (r & 3) + 8 * (r >> 2);
+                            ++pos;
+                        }
+                    }
+                }
+                cnt += tot;
+            }
+        }
+        if (st + 1 < nst) store_stage<NV, NF4>(stg, hb[(st + 1) & 1], tid);
+        __syncthreads();
+    }
+    uint64_t fm = __ballot(uvalid && h == 0);
+    while (fm) {
+        const int uj = __ffsll((unsigned long long) fm) - 1;
+        fm &= fm - 1;
+        flush(uj, true);
+    }
+}
+
+// Final N of one batch slot from the slices' sorted heads (one wave per slot).
+__global__ __launch_bounds__(64) void mfx_rec_merge(const float* ls, const uint32_t* li, uint32_t q0, uint32_t nq,
+                                                    int slices, int L, int n_top, int P, uint32_t* out_items,
+                                                    float* out_scores) {
+    extern __shared__ float smem[];
+    float* ks = smem;
+    uint32_t* is = reinterpret_cast<uint32_t*>(smem + P);
+    const uint32_t q = blockIdx.x;
+    const int lane = threadIdx.x;
+    const int n_in = slices * n_top;
+    for (int e = lane; e < P; e += 64) {
+        float s = -INFINITY;
+        uint32_t it = kPad;
+        if (e < n_in) {
+            const size_t src = ((size_t) (e / n_top) * nq + q) * (size_t) L + (e % n_top);
+            s = ls[src];
+            it = li[src];
+        }
+        ks[e] = s;
+        is[e] = it;
+    }
+    wave_sync();
+    wave_bitonic(ks, is, P, lane);
+    for (int e = lane; e < n_top; e += 64) {
+        const size_t o = (size_t) (q0 + q) * n_top + e;
+        out_items[o] = is[e];
+        if (out_scores) out_scores[o] = ks[e];
+    }
+}
+
+// hp[b][c][tt][jj] = H[item b*32 + jj][t c*2KC + tt], zero outside cols x k.
+__global__ void mfx_rec_pack_h(const float* H, int layout, uint32_t cols, int k, int kc2, int nch, int nblk, float* hp) {
+    const size_t total = (size_t) nblk * nch * kc2 * kTile;
+    for (size_t x = (size_t) blockIdx.x * blockDim.x + threadIdx.x; x < total; x += (size_t) gridDim.x * blockDim.x) {
+        const uint32_t jj = x % kTile;
+        size_t rest = x / kTile;
+        const int tt = rest % kc2;
+        rest /= kc2;
+        const int c = rest % nch;
+        const size_t b = rest / nch;
+        const size_t item = b * kTile + jj;
+        const int t = c * kc2 + tt;
+        float v = 0.f;
+        if (item < cols && t < k) v = layout == 0 ? H[(size_t) t * cols + item] : H[item * k + t];
+        hp[x] = v;
+    }
+}
+
+// wp[u][t] = W[u][t], zero for t >= k.
+__global__ void mfx_rec_pack_w(const float* W, int layout, uint32_t rows, int k, int kt, float* wp) {
+    const size_t total = (size_t) rows * kt;
+    for (size_t x = (size_t) blockIdx.x * blockDim.x + threadIdx.x; x < total; x += (size_t) gridDim.x * blockDim.x) {
+        const size_t uu = x / kt;
+        const int t = x % kt;
+        float v = 0.f;
+        if (t < k) v = layout == 0 ? W[(size_t) t * rows + uu] : W[uu * k + t];
+        wp[x] = v;
+    }
+}
+
+// bad |= 1: row pointers not a valid prefix sum of nnz; 2: column index >= cols; 4: a row not non-decreasing.
+__global__ void mfx_rec_check_exclude(const uint32_t* rp, const uint32_t* ci, uint32_t rows, uint32_t cols,
+                                      uint64_t nnz, int* bad) {
+    for (uint32_t r = blockIdx.x * blockDim.x + threadIdx.x; r < rows; r += gridDim.x * blockDim.x) {
+        const uint32_t lo = rp[r], hi = rp[r + 1];
+        if (lo > hi || hi > nnz || (r == 0 && lo != 0) || (r == rows - 1 && hi != nnz)) {
+            atomicOr(bad, 1);
+            continue;
+        }
+        uint32_t prev = 0;
+        int f = 0;
+        for (uint32_t p = lo; p < hi; ++p) {
+            const uint32_t c = ci[p];
+            if (c >= cols) f |= 2;
+            if (p > lo && c < prev) f |= 4;
+            prev = c;
+        }
+        if (f) atomicOr(bad, f);
+    }
+}
+
+int grid_for(size_t n) { return (int) std::min<size_t>((n + 255) / 256, 4096); }
+
+template <int KC>
+int launch_topn(const RecArgs& a, int slices, hipStream_t st) {
+    const dim3 grid((a.nq + kRecUsers - 1) / kRecUsers, slices);
+    hipLaunchKernelGGL(mfx_rec_topn<KC>, grid, dim3(kRecThreads), 0, st, a);
+    MFX_LAUNCH_CHECK();
+    return MFX_OK;
+}
+
+}  // namespace
+
+Recommender::~Recommender() {
+    if (st_) {
+        (void) hipSetDevice(device_);
+        (void) hipStreamSynchronize(st_);
+        (void) hipStreamDestroy(st_);
+    }
+}
+
+int Recommender::create(Recommender** out, const float* W, const float* H, int64_t rows, int64_t cols, int64_t k,
+                        int layout, const mfx_csx* ex, mfx_memspace space, int device) {
+    *out = nullptr;
+    MFX_REQUIRE(W && H, "mfx_rec_create: W and H are required");
+    MFX_REQUIRE(rows >= 1 && cols >= 1 && rows < (int64_t) 0xFFFFFFFFll && cols < (int64_t) 0xFFFFFFFFll,
+                "mfx_rec_create: rows / cols out of range (%lld x %lld)", (long long) rows, (long long) cols);
+    MFX_REQUIRE(k >= 1 && k <= kMaxK, "mfx_rec_create: k must be in [1, %d] (got %lld)", kMaxK, (long long) k);
+    MFX_REQUIRE(layout == 0 || layout == 1, "mfx_rec_create: layout must be 0 (CCD++) or 1 (ALS), got %d", layout);
+    MFX_REQUIRE(space == MFX_HOST || space == MFX_DEVICE, "mfx_rec_create: bad memory space");
+    if (ex) {
+        MFX_REQUIRE(ex->rows == rows && ex->cols == cols,
+                    "mfx_rec_create: exclusion matrix is %lld x %lld, the factors are %lld x %lld", (long long) ex->rows,
+                    (long long) ex->cols, (long long) rows, (long long) cols);
+        MFX_REQUIRE(ex->csr_row_ptr && ex->nnz >= 0 && ex->nnz < (int64_t) 0xFFFFFFFFll && (ex->nnz == 0 || ex->csr_col_idx),
+                    "mfx_rec_create: exclusion matrix lacks csr_row_ptr / csr_col_idx");
+    }
+    MFX_TRY(use_device(device));
+    std::unique_ptr<Recommender> r(new Recommender());
+    r->device_ = device;
+    r->rows_ = rows; r->cols_ = cols; r->k_ = k;
+    const int steps = (int) ((k + 1) / 2);
+    int kc = 1;
+    while (kc < steps && kc < 64) kc <<= 1;
+    r->kc_ = kc;
+    r->nch_ = (steps + kc - 1) / kc;
+    r->kt_ = r->nch_ * 2 * kc;
+    r->nblk_ = (int) ((cols + kTile - 1) / kTile);
+    int cus = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0) r->cus_ = cus;
+    MFX_HIP(hipStreamCreateWithFlags(&r->st_, hipStreamNonBlocking));
+    hipStream_t st = r->st_;
+
+    DevBuf<float> tw, th;
+    const float* dW = W;
+    const float* dH = H;
+    if (space == MFX_HOST) {
+        MFX_TRY(tw.alloc((size_t) rows * k)); MFX_TRY(tw.upload(W, (size_t) rows * k, MFX_HOST, st));
+        MFX_TRY(th.alloc((size_t) cols * k)); MFX_TRY(th.upload(H, (size_t) cols * k, MFX_HOST, st));
+        dW = tw.get();
+        dH = th.get();
+    }
+    MFX_TRY(r->wp_.alloc((size_t) rows * r->kt_));
+    MFX_TRY(r->hp_.alloc((size_t) r->nblk_ * kTile * r->kt_));
+    hipLaunchKernelGGL(mfx_rec_pack_w, dim3(grid_for((size_t) rows * r->kt_)), dim3(256), 0, st, dW, layout,
+                       (uint32_t) rows, (int) k, r->kt_, r->wp_.get());
+    MFX_LAUNCH_CHECK();
+    hipLaunchKernelGGL(mfx_rec_pack_h, dim3(grid_for((size_t) r->nblk_ * kTile * r->kt_)), dim3(256), 0, st, dH, layout,
+                       (uint32_t) cols, (int) k, 2 * kc, r->nch_, r->nblk_, r->hp_.get());
+    MFX_LAUNCH_CHECK();
+
+    if (ex) {
+        uint32_t nnz_ptr = 0;
+        MFX_TRY(r->ex_ptr_.alloc((size_t) rows + 1));
+        MFX_TRY(r->ex_ptr_.upload(ex->csr_row_ptr, (size_t) rows + 1, space, st));
+        MFX_HIP(hipMemcpyAsync(&nnz_ptr, r->ex_ptr_.get() + rows, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        MFX_HIP(hipStreamSynchronize(st));
+        MFX_REQUIRE((int64_t) nnz_ptr == ex->nnz, "mfx_rec_create: exclusion csr_row_ptr[rows] = %u but nnz = %lld", nnz_ptr,
+                    (long long) ex->nnz);
+        if (ex->nnz > 0) {
+            MFX_TRY(r->ex_idx_.alloc((size_t) ex->nnz));
+            MFX_TRY(r->ex_idx_.upload(ex->csr_col_idx, (size_t) ex->nnz, space, st));
+        }
+        DevBuf<int> bad;
+        MFX_TRY(bad.alloc_zero(1, st));
+        hipLaunchKernelGGL(mfx_rec_check_exclude, dim3(grid_for((size_t) rows)), dim3(256), 0, st, r->ex_ptr_.get(),
+                           r->ex_idx_.get(), (uint32_t) rows, (uint32_t) cols, (uint64_t) ex->nnz, bad.get());
+        MFX_LAUNCH_CHECK();
+        int hb = 0;
+        MFX_HIP(hipMemcpyAsync(&hb, bad.get(), sizeof(int), hipMemcpyDeviceToHost, st));
+        MFX_HIP(hipStreamSynchronize(st));
+        MFX_REQUIRE(!(hb & 1), "mfx_rec_create: exclusion csr_row_ptr is not a non-decreasing prefix sum from 0 to nnz");
+        MFX_REQUIRE(!(hb & 2), "mfx_rec_create: exclusion column index out of range [0, %lld)", (long long) cols);
+        MFX_REQUIRE(!(hb & 4), "mfx_rec_create: exclusion column indices must be non-decreasing within every row");
+        r->has_ex_ = true;
+    }
+    MFX_HIP(hipStreamSynchronize(st));
+    *out = r.release();
+    return MFX_OK;
+}
+
+int Recommender::query(int64_t nusers, const uint32_t* users, int32_t n_top, uint32_t* items, float* scores,
+                       mfx_memspace space, int item_slices) {
+    MFX_REQUIRE(n_top >= 1 && n_top <= kMaxTop, "mfx_rec_query: n_top must be in [1, %d] (got %d)", kMaxTop, n_top);
+    MFX_REQUIRE(nusers >= 0 && nusers < (int64_t) 0xFFFFFFFFll, "mfx_rec_query: bad nusers %lld", (long long) nusers);
+    MFX_REQUIRE(users || nusers <= rows_, "mfx_rec_query: users = NULL needs nusers <= rows (%lld > %lld)",
+                (long long) nusers, (long long) rows_);
+    MFX_REQUIRE(space == MFX_HOST || space == MFX_DEVICE, "mfx_rec_query: bad memory space");
+    MFX_REQUIRE(item_slices >= 0, "mfx_rec_query: item_slices must be >= 0 (got %d)", item_slices);
+    MFX_REQUIRE(item_slices * (int64_t) n_top <= kMaxMerge, "mfx_rec_query: item_slices * n_top must be <= %d", kMaxMerge);
+    if (nusers == 0) return MFX_OK;
+    MFX_REQUIRE(items, "mfx_rec_query: items is NULL");
+    MFX_TRY(use_device(device_));
+    hipStream_t st = st_;
+
+    int L = 64;
+    while (L < n_top + 32) L <<= 1;
+    const uint32_t nu = (uint32_t) nusers;
+
+    // slices: forced, or enough workgroups for about two per CU
+    int slices = item_slices;
+    const auto per_launch = [&](int s) {
+        size_t qmax = kWorkspaceCap / ((size_t) s * L * 8);
+        qmax = std::max<size_t>(kRecUsers, qmax / kRecUsers * kRecUsers);
+        return (uint32_t) std::min<size_t>(nu, qmax);
+    };
+    if (slices == 0) {
+        const int ublocks = (int) ((per_launch(1) + kRecUsers - 1) / kRecUsers);
+        const int want = 2 * cus_;
+        slices = ublocks >= want ? 1 : (want + ublocks - 1) / ublocks;
+        slices = std::min(slices, std::max(1, nblk_ / 4));
+        slices = std::min(slices, kMaxMerge / n_top);
+        slices = std::max(slices, 1);
+        const int bps = (nblk_ + slices - 1) / slices;
+        slices = (nblk_ + bps - 1) / bps;  // no empty slices
+    }
+    const int bps = (nblk_ + slices - 1) / slices;
+    const uint32_t qc = per_launch(slices);
+
+    DevBuf<uint32_t> d_users, d_items;
+    DevBuf<float> d_scores, ls;
+    DevBuf<uint32_t> li;
+    const uint32_t* du = users;
+    if (users && space == MFX_HOST) {
+        MFX_TRY(d_users.alloc(nu));
+        MFX_TRY(d_users.upload(users, nu, MFX_HOST, st));
+        du = d_users.get();
+    }
+    if (users) MFX_TRY(check_index_range(du, nu, (uint32_t) rows_, "mfx_rec_query: user id", st));
+    uint32_t* oi = items;
+    float* os = scores;
+    if (space == MFX_HOST) {
+        MFX_TRY(d_items.alloc((size_t) nu * n_top));
+        oi = d_items.get();
+        if (scores) {
+            MFX_TRY(d_scores.alloc((size_t) nu * n_top));
+            os = d_scores.get();
+        }
+    }
+    MFX_TRY(ls.alloc((size_t) slices * qc * L));
+    MFX_TRY(li.alloc((size_t) slices * qc * L));
+
+    RecArgs a{};
+    a.wp = wp_.get();
+    a.hp = hp_.get();
+    a.users = du;
+    a.ex_ptr = has_ex_ ? ex_ptr_.get() : nullptr;
+    a.ex_idx = ex_idx_.get();
+    a.cols = (uint32_t) cols_;
+    a.kt = kt_; a.nch = nch_; a.nblk = nblk_; a.bps = bps; a.n_top = n_top; a.L = L;
+    a.ls = ls.get(); a.li = li.get();
+    a.out_items = oi; a.out_scores = os;
+    int P = 1;
+    while (P < slices * n_top) P <<= 1;
+    for (uint32_t q0 = 0; q0 < nu; q0 += qc) {
+        a.q0 = q0;
+        a.nq = std::min(qc, nu - q0);
+        switch (kc_) {
+            case 1: MFX_TRY(launch_topn<1>(a, slices, st)); break;
+            case 2: MFX_TRY(launch_topn<2>(a, slices, st)); break;
+            case 4: MFX_TRY(launch_topn<4>(a, slices, st)); break;
+            case 8: MFX_TRY(launch_topn<8>(a, slices, st)); break;
+            case 16: MFX_TRY(launch_topn<16>(a, slices, st)); break;
+            case 32: MFX_TRY(launch_topn<32>(a, slices, st)); break;
+            default: MFX_TRY(launch_topn<64>(a, slices, st)); break;
+        }
+        if (slices > 1) {
+            hipLaunchKernelGGL(mfx_rec_merge, dim3(a.nq), dim3(64), (size_t) P * 8, st, a.ls, a.li, q0, a.nq, slices, L,
+                               n_top, P, oi, os);
+            MFX_LAUNCH_CHECK();
+        }
+    }
+    if (space == MFX_HOST) {
+        MFX_HIP(hipMemcpyAsync(items, oi, sizeof(uint32_t) * nu * n_top, hipMemcpyDeviceToHost, st));
+        if (scores) MFX_HIP(hipMemcpyAsync(scores, os, sizeof(float) * nu * n_top, hipMemcpyDeviceToHost, st));
+    }
+    MFX_HIP(hipStreamSynchronize(st));
+    return MFX_OK;
+}
+
+int topn_metrics(int64_t nusers, const uint32_t* users, int32_t n_top, const uint32_t* items, const mfx_coo* T,
+                 float min_rating, double out[4], int64_t* users_evaluated) {
+    MFX_REQUIRE(nusers >= 0 && n_top >= 1 && (nusers == 0 || items) && T && out, "mfx_topn_metrics: bad argument");
+    MFX_REQUIRE(T->nnz == 0 || (T->row && T->col && T->val), "mfx_topn_metrics: null test array");
+    MFX_REQUIRE(!std::isnan(min_rating), "mfx_topn_metrics: min_rating is NaN");
+    // R_u of the listed users: distinct test items with value >= min_rating
+    std::unordered_map<uint32_t, std::vector<uint32_t>> rel;
+    rel.reserve((size_t) nusers);
+    for (int64_t s = 0; s < nusers; ++s) rel.emplace(users ? users[s] : (uint32_t) s, std::vector<uint32_t>());
+    for (int64_t p = 0; p < T->nnz; ++p) {
+        if (!(T->val[p] >= min_rating)) continue;
+        auto it = rel.find(T->row[p]);
+        if (it != rel.end()) it->second.push_back(T->col[p]);
+    }
+    for (auto& kv : rel) {
+        std::sort(kv.second.begin(), kv.second.end());
+        kv.second.erase(std::unique(kv.second.begin(), kv.second.end()), kv.second.end());
+    }
+    double hr = 0, prec = 0, rec = 0, ndcg = 0;
+    int64_t kept = 0;
+    std::vector<uint32_t> seen;
+    for (int64_t s = 0; s < nusers; ++s) {
+        const std::vector<uint32_t>& R = rel[users ? users[s] : (uint32_t) s];
+        if (R.empty()) continue;
+        ++kept;
+        seen.clear();
+        double dcg = 0;
+        for (int32_t jj = 0; jj < n_top; ++jj) {
+            const uint32_t it = items[(size_t) s * n_top + jj];
+            if (it == kPad || !std::binary_search(R.begin(), R.end(), it)) continue;
+            if (std::find(seen.begin(), seen.end(), it) != seen.end()) continue;  // a hit counts once
+            seen.push_back(it);
+            dcg += 1.0 / std::log2((double) jj + 2.0);
+        }
+        double idcg = 0;
+        const int64_t ideal = std::min<int64_t>(n_top, (int64_t) R.size());
+        for (int64_t jj = 0; jj < ideal; ++jj) idcg += 1.0 / std::log2((double) jj + 2.0);
+        const double hits = (double) seen.size();
+        hr += hits > 0 ? 1.0 : 0.0;
+        prec += hits / n_top;
+        rec += hits / (double) R.size();
+        ndcg += dcg / idcg;
+    }
+    const double d = kept ? (double) kept : 1.0;
+    out[0] = kept ? hr / d : 0.0;
+    out[1] = kept ? prec / d : 0.0;
+    out[2] = kept ? rec / d : 0.0;
+    out[3] = kept ? ndcg / d : 0.0;
+    if (users_evaluated) *users_evaluated = kept;
+    return MFX_OK;
+}
+
+}  // namespace mfx

@@ -1,0 +1,42 @@
+// recommend.hpp -- resident top-N recommender (mfx_rec_*) and the host-side ranking metrics (mfx_topn_metrics).
+//
+// The query is one fused pass per (user block, item slice): scores come out of v_mfma_f32_32x32x2_f32 tiles (H staged
+// in LDS and shared by the 128 users of a workgroup, W in registers), a running per-user threshold keeps the
+// per-score work to one compare, and only the scores that pass reach a per-user candidate list in the workspace;
+// nothing of the users x items score matrix is ever stored.  See recommend.hip.
+#pragma once
+
+#include "common.hpp"
+
+namespace mfx {
+
+class Recommender {
+public:
+    static int create(Recommender** out, const float* W, const float* H, int64_t rows, int64_t cols, int64_t k,
+                      int layout, const mfx_csx* exclude, mfx_memspace space, int device);
+    int query(int64_t nusers, const uint32_t* users, int32_t n_top, uint32_t* items, float* scores,
+              mfx_memspace space, int item_slices);
+    ~Recommender();
+
+private:
+    int device_ = 0;
+    hipStream_t st_ = nullptr;
+    int64_t rows_ = 0, cols_ = 0, k_ = 0;
+    int kc_ = 0;       // MFMA steps (of two t values) per LDS stage: 1, 2, 4, ..., 64
+    int nch_ = 0;      // t chunks of 2 * kc_ (k > 128 takes several)
+    int kt_ = 0;       // padded k = nch_ * 2 * kc_
+    int nblk_ = 0;     // 32-item tiles
+    int cus_ = 256;    // compute units of the device (automatic slicing)
+    DevBuf<float> wp_, hp_;
+    DevBuf<uint32_t> ex_ptr_, ex_idx_;
+    bool has_ex_ = false;
+};
+
+int topn_metrics(int64_t nusers, const uint32_t* users, int32_t n_top, const uint32_t* items, const mfx_coo* T,
+                 float min_rating, double out[4], int64_t* users_evaluated);
+
+}  // namespace mfx
+
+struct mfx_rec_s {
+    mfx::Recommender* impl;
+};

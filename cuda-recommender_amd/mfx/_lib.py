@@ -107,6 +107,12 @@ SIGNATURES = {
     "mfx_initial_col": (None, [f32p, C.c_int64, C.c_int64]),
     "mfx_partition_rows": (C.c_int, [C.c_int64, u32p, C.c_int, i64p]),
     "mfx_extract_shard": (C.c_int, [C.POINTER(mfx_csx), C.c_int64, C.c_int64, u32p, u32p, f32p, u32p, u32p, f32p]),
+    "mfx_rec_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int,
+                                 C.POINTER(mfx_csx), C.c_int, C.c_int]),
+    "mfx_rec_query": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
+    "mfx_rec_destroy": (C.c_int, [C.c_void_p]),
+    "mfx_topn_metrics": (C.c_int, [C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(mfx_coo), C.c_float, f64p,
+                                   i64p]),
 }
 
 _LIB = None

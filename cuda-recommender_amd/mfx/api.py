@@ -588,3 +588,142 @@ def extract_shard(R: RatingData, row_lo: int, row_hi: int) -> RatingData:
     out.test_col = np.ascontiguousarray(R.test_col[keep])
     out.test_val = np.ascontiguousarray(R.test_val[keep])
     return out
+
+
+# ---------------------------------------------------------------------------------------------
+# top-N recommendation (mfx_rec_*) and ranking metrics (mfx_topn_metrics)
+# ---------------------------------------------------------------------------------------------
+PAD_ITEM = 0xFFFFFFFF  # item id of the slots a list could not fill (score -inf)
+
+
+def _is_dev(a) -> bool:
+    return hasattr(a, "data_ptr") and not isinstance(a, np.ndarray)
+
+
+class Recommender:
+    """Resident top-N recommender over trained factors (mfx_rec_*).
+
+    layout 0: CCD++ factors W [k][rows], H [k][cols]; layout 1: ALS factors W [rows][k], H [cols][k].  W and H are
+    numpy float32 arrays, or float32 tensors exposing `data_ptr()` on the GPU (both the same kind).  `exclude`: a
+    RatingData whose CSR rows name the items each user is never recommended (e.g. the training ratings)."""
+
+    def __init__(self, W, H, layout: int, exclude: Optional[RatingData] = None, device: int = 0):
+        self.handle = C.c_void_p()
+        self.device = device
+        if layout not in (0, 1):
+            raise ValueError("layout must be 0 (CCD++: [k][rows]) or 1 (ALS: [rows][k])")
+        dev = _is_dev(W)
+        if dev != _is_dev(H):
+            raise ValueError("W and H must both be host arrays or both device tensors")
+        shW, shH = tuple(W.shape), tuple(H.shape)
+        if len(shW) != 2 or len(shH) != 2:
+            raise ValueError("W and H must be 2-D")
+        if layout == 0:
+            (k, rows), (k2, cols) = shW, shH
+        else:
+            (rows, k), (cols, k2) = shW, shH
+        if k != k2:
+            raise ValueError(f"W and H disagree on k ({k} vs {k2})")
+        self.rows, self.cols, self.k, self.layout = int(rows), int(cols), int(k), layout
+        self._keep = []
+        ex = None
+        if dev:
+            import torch
+            for t in (W, H):
+                assert t.dtype == torch.float32 and t.is_contiguous(), "need contiguous float32 tensors"
+            pw, ph, space = C.c_void_p(int(W.data_ptr())), C.c_void_p(int(H.data_ptr())), L.MFX_DEVICE
+            if exclude is not None:
+                rp = torch.from_numpy(exclude.csr_row_ptr.view(np.int32)).to(W.device)
+                ci = torch.from_numpy(exclude.csr_col_idx.view(np.int32)).to(W.device)
+                self._keep += [rp, ci]
+                ex = L.mfx_csx(exclude.rows, exclude.cols, int(exclude.csr_col_idx.shape[0]), None, None, None,
+                               C.c_void_p(int(rp.data_ptr())), C.c_void_p(int(ci.data_ptr())) if ci.numel() else None, None)
+        else:
+            _f32c(W); _f32c(H)
+            pw, ph, space = _vp(W), _vp(H), L.MFX_HOST
+            if exclude is not None:
+                exclude.check_types()
+                ex = L.mfx_csx(exclude.rows, exclude.cols, int(exclude.csr_col_idx.shape[0]), None, None, None,
+                               _vp(exclude.csr_row_ptr), _vp(exclude.csr_col_idx), None)
+        L.check(L.lib().mfx_rec_create(C.byref(self.handle), pw, ph, self.rows, self.cols, self.k, layout,
+                                       C.byref(ex) if ex is not None else None, space, device))
+
+    def query(self, n_top: int, users=None, item_slices: int = 0, on_device: bool = False):
+        """Top-n_top items of `users` (None: all users in order) -> (items uint32 [U, n_top], scores float32
+        [U, n_top]).  Padding slots: item PAD_ITEM, score -inf.  A `users` tensor on the GPU (int32 / uint32 bits) or
+        on_device=True keeps everything on the device: the results are then int32 / float32 tensors on it (the items'
+        bits are the uint32 ids)."""
+        if _is_dev(users) or on_device:
+            import torch
+            dev = torch.device("cuda", self.device)
+            if users is not None:
+                assert users.is_contiguous() and users.element_size() == 4, "users: contiguous 32-bit tensor"
+                n = int(users.numel())
+                pu = C.c_void_p(int(users.data_ptr())) if n else None
+            else:
+                n, pu = self.rows, None
+            items = torch.empty((n, n_top), dtype=torch.int32, device=dev)
+            scores = torch.empty((n, n_top), dtype=torch.float32, device=dev)
+            if n:
+                L.check(L.lib().mfx_rec_query(self.handle, n, pu, n_top, C.c_void_p(int(items.data_ptr())),
+                                              C.c_void_p(int(scores.data_ptr())), L.MFX_DEVICE, item_slices))
+            return items, scores
+        if users is None:
+            n, pu, keep = self.rows, None, None
+        else:
+            keep = np.ascontiguousarray(np.asarray(users), dtype=np.int64)
+            if keep.ndim != 1 or (keep.size and (keep.min() < 0 or keep.max() >= 2 ** 32)):
+                raise ValueError("users must be a 1-D array of non-negative 32-bit ids")
+            keep = keep.astype(np.uint32)
+            n, pu = int(keep.size), _vp(keep)
+        items = np.empty((n, n_top), np.uint32)
+        scores = np.empty((n, n_top), np.float32)
+        L.check(L.lib().mfx_rec_query(self.handle, n, pu, n_top, _vp(items), _vp(scores), L.MFX_HOST, item_slices))
+        return items, scores
+
+    def close(self):
+        if self.handle:
+            L.lib().mfx_rec_destroy(self.handle)
+            self.handle = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def recommend(W, H, layout: int, n_top: int, users=None, exclude: Optional[RatingData] = None, device: int = 0,
+              item_slices: int = 0):
+    """One-shot Recommender(W, H, layout, exclude, device).query(n_top, users, item_slices)."""
+    with Recommender(W, H, layout, exclude=exclude, device=device) as r:
+        return r.query(n_top, users=users, item_slices=item_slices)
+
+
+def topn_metrics(items, T, users=None, min_rating: float = float("-inf")) -> dict:
+    """Ranking metrics of top-N lists `items` [U, N] (uint32; PAD_ITEM slots never count) against the test set T
+    (TestData or RatingData): {"hr", "precision", "recall", "ndcg", "users"}.  users: the user of each list (None:
+    list u is user u).  Only test entries with value >= min_rating count; users left with none are skipped."""
+    items = np.ascontiguousarray(np.asarray(items), dtype=np.uint32)
+    if items.ndim != 2 or items.shape[1] < 1:
+        raise ValueError("items must be [users, n_top] with n_top >= 1")
+    n, n_top = items.shape
+    pu = None
+    if users is not None:
+        users = np.ascontiguousarray(np.asarray(users), dtype=np.uint32)
+        if users.shape != (n,):
+            raise ValueError("users must have one entry per list")
+        pu = _vp(users)
+    if not isinstance(T, TestData):
+        T = test_data_of(T)
+    coo = _coo(T)
+    out = (C.c_double * 4)()
+    kept = C.c_int64(0)
+    L.check(L.lib().mfx_topn_metrics(n, pu, n_top, _vp(items), C.byref(coo), float(min_rating), out, C.byref(kept)))
+    return {"hr": out[0], "precision": out[1], "recall": out[2], "ndcg": out[3], "users": int(kept.value)}

@@ -223,6 +223,31 @@ int mfx_als_kernel_times(mfx_als_t s, int cap, const char** names, double* secon
 int mfx_als_destroy(mfx_als_t s);
 
 /* ------------------------------------------------------------------------------------
+ * Top-N recommendation: a resident handle over trained factors that returns, for each
+ * requested user, the n_top highest-scoring items the user must not be excluded from.
+ * Score of (u, i) = the fp32 sum over t of W[u,t]*H[i,t], accumulated in ascending t
+ * (bitwise the same whatever the batch, its order, item_slices or layout).  Order: score
+ * descending, then item ascending (-0 == +0); NaN scores are never returned.  Slots left
+ * when fewer than n_top items are eligible hold item 0xFFFFFFFF and score -INFINITY.
+ * Range: 1 <= n_top <= 1024, 1 <= k <= 1024; anything else is MFX_ERR_INVALID.
+ * ---------------------------------------------------------------------------------- */
+typedef struct mfx_rec_s* mfx_rec_t;
+/* layout 0: CCD++ factors, W [k][rows], H [k][cols]; layout 1: ALS factors, W [rows][k], H [cols][k].
+ * Copies (and repacks) W and H into library-owned device memory.
+ * exclude: NULL, or a rating matrix of the same rows x cols; only csr_row_ptr / csr_col_idx are read:
+ * the items each user is never recommended.  Column indices must be non-decreasing within every row
+ * (checked on the device; MFX_ERR_INVALID otherwise).  `space` applies to W, H and exclude. */
+int mfx_rec_create(mfx_rec_t* out, const float* W, const float* H, int64_t rows, int64_t cols, int64_t k,
+                   int layout, const mfx_csx* exclude, mfx_memspace space, int device);
+/* Top-n_top items of each of nusers users.  users: NULL means 0 .. nusers-1; any order, duplicates
+ * allowed.  items [nusers][n_top], scores [nusers][n_top] or NULL; `space` applies to all three.
+ * item_slices: 0 = automatic; > 0 forces the item dimension to be split over that many slices
+ * (a test hook; item_slices * n_top must not exceed 8192). */
+int mfx_rec_query(mfx_rec_t r, int64_t nusers, const uint32_t* users, int32_t n_top, uint32_t* items,
+                  float* scores, mfx_memspace space, int item_slices);
+int mfx_rec_destroy(mfx_rec_t r);
+
+/* ------------------------------------------------------------------------------------
  * Single operators (host pointers in, host pointers out): one call per reference
  * function on the path, used by the parity tests.
  * ---------------------------------------------------------------------------------- */
@@ -308,6 +333,14 @@ int mfx_partition_rows(int64_t rows, const uint32_t* csr_row_ptr, int nshards, i
 int mfx_extract_shard(const mfx_csx* R, int64_t row_lo, int64_t row_hi, uint32_t* l_csr_row_ptr,
                       uint32_t* l_csr_col_idx, float* l_csr_val, uint32_t* l_csc_col_ptr,
                       uint32_t* l_csc_row_idx, float* l_csc_val);
+/* Ranking metrics of top-N lists (host pointers) against a test set.  For listed user u, R_u = the
+ * distinct test items of u with value >= min_rating (-INFINITY: all); users with an empty R_u are
+ * skipped and *users_evaluated (may be NULL) is the number kept.  Padding items (0xFFFFFFFF) never
+ * count; a repeated item counts once.  out = {HR, precision, recall, NDCG}, means over the kept
+ * users of [hits > 0], hits / n_top, hits / |R_u| and DCG / IDCG with gain 1 / log2(rank + 2)
+ * (rank 0-based, IDCG over min(n_top, |R_u|) ranks); fp64 throughout. */
+int mfx_topn_metrics(int64_t nusers, const uint32_t* users, int32_t n_top, const uint32_t* items,
+                     const mfx_coo* T, float min_rating, double out[4], int64_t* users_evaluated);
 
 #ifdef __cplusplus
 }
