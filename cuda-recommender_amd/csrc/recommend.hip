@@ -7,8 +7,9 @@
 // v_mfma_f32_32x32x2_f32 (lane l: W[user l&31][t = 2s + (l>>5)]) and reads the H tile as the A operand
 // (H[item l&31][t = 2s + (l>>5)]), so the accumulator has the user on the lane (column = lane & 31) and 16 items in
 // the registers (row = (r&3) + 8*(r>>2) + 4*(lane>>5)).  Every score is the fp32 FMA chain over t = 0, 1, 2, ... in
-// ascending order (one MFMA = two chained FMAs), whatever the tile, slice, batch or factor layout; k is padded with
-// zeros to the MFMA step, and k > 128 runs several t chunks into the same accumulator, same order.
+// ascending order (one MFMA = two chained FMAs), whatever the tile, slice, batch or factor layout; k is padded to
+// the MFMA step with steps that leave the accumulator bitwise unchanged (W +0, H -0; see mfx_rec_pack_h), and k > 128
+// runs several t chunks into the same accumulator, same order.
 //
 // Selection: each lane holds the running threshold of its user (the N-th best score so far) and compares its 16
 // scores against it -- one VALU compare per score.  Scores that pass are appended to the user's candidate list
@@ -306,7 +307,9 @@ __global__ __launch_bounds__(64) void mfx_rec_merge(const float* ls, const uint3
     }
 }
 
-// hp[b][c][tt][jj] = H[item b*32 + jj][t c*2KC + tt], zero outside cols x k.
+// hp[b][c][tt][jj] = H[item b*32 + jj][t c*2KC + tt], zero outside cols x k.  The padding t >= k is -0: with the
+// +0 padding of W its products are -0, and fma(+0, -0, acc) == acc for every acc, a -0 score included (a +0 product
+// would turn an underflowed -0 score into +0).
 __global__ void mfx_rec_pack_h(const float* H, int layout, uint32_t cols, int k, int kc2, int nch, int nblk, float* hp) {
     const size_t total = (size_t) nblk * nch * kc2 * kTile;
     for (size_t x = (size_t) blockIdx.x * blockDim.x + threadIdx.x; x < total; x += (size_t) gridDim.x * blockDim.x) {
@@ -318,7 +321,7 @@ __global__ void mfx_rec_pack_h(const float* H, int layout, uint32_t cols, int k,
         const size_t b = rest / nch;
         const size_t item = b * kTile + jj;
         const int t = c * kc2 + tt;
-        float v = 0.f;
+        float v = t < k ? 0.f : -0.f;
         if (item < cols && t < k) v = layout == 0 ? H[(size_t) t * cols + item] : H[item * k + t];
         hp[x] = v;
     }

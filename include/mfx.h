@@ -225,7 +225,8 @@ int mfx_als_destroy(mfx_als_t s);
 /* ------------------------------------------------------------------------------------
  * Top-N recommendation: a resident handle over trained factors that returns, for each
  * requested user, the n_top highest-scoring items the user must not be excluded from.
- * Score of (u, i) = the fp32 sum over t of W[u,t]*H[i,t], accumulated in ascending t
+ * Score of (u, i) = the fp32 fused multiply-add chain in ascending t: acc = +0, then
+ * acc = fmaf(W[u,t], H[i,t], acc) for t = 0 .. k-1, one rounding per step, subnormals kept
  * (bitwise the same whatever the batch, its order, item_slices or layout).  Order: score
  * descending, then item ascending (-0 == +0); NaN scores are never returned.  Slots left
  * when fewer than n_top items are eligible hold item 0xFFFFFFFF and score -INFINITY.

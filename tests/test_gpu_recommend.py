@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT, load_golden
+from rec_exact import chain_scores, eligible_mask, expected_topn
 
 pytestmark = pytest.mark.gpu
 
@@ -84,10 +85,16 @@ def test_golden_factors_with_training_exclusion(mfx, case, solver):
     W, H = g[solver + "__W"], g[solver + "__H"]
     layout = 1 if solver == "als" else 0
     Wr, Hr = rows_major(W, H, layout)
+    users = np.arange(d.rows)
+    S = chain_scores(Wr, Hr, users)
+    elig = eligible_mask(d, users, d.cols)
     with mfx.Recommender(np.ascontiguousarray(W), np.ascontiguousarray(H), layout, exclude=d) as r:
         for n_top in (1, 5, d.cols, d.cols + 3):
             items, scores = r.query(n_top)
-            check_lists(Wr, Hr, np.arange(d.rows), n_top, items, scores, ex=d)
+            check_lists(Wr, Hr, users, n_top, items, scores, ex=d)
+            want_i, want_s = expected_topn(S, elig, n_top)
+            assert np.array_equal(items, want_i), n_top
+            assert np.array_equal(scores.view(np.uint32), want_s.view(np.uint32)), n_top
 
 
 # ------------------------------------------------------------------------------------------------ synthetic shapes
