@@ -26,8 +26,21 @@
 
 #include "ccd_kernels.hpp"
 
+// MFX_ALS_IMPLICIT = 1 (ials_half.hip): the same kernels as the implicit-feedback k_ials_* instantiations.  A translation
+// unit of their own, so that the k_als_* kernels of this one compile to exactly the code they had without them.
+#ifndef MFX_ALS_IMPLICIT
+#define MFX_ALS_IMPLICIT 0
+#endif
+#if MFX_ALS_IMPLICIT
+#define ALS_KERNEL(name) k_ials_##name
+#else
+#define ALS_KERNEL(name) k_als_##name
+#endif
+
 namespace mfx {
 namespace {
+
+constexpr bool kImplicit = MFX_ALS_IMPLICIT != 0;
 
 // unfused multiply / subtract (HIP's __fmul_rn is a plain `*` and would be contracted into v_fma)
 __device__ __forceinline__ float mul_rn(float a, float b) {
@@ -77,6 +90,9 @@ struct AlsArgs {
     float* gram_out;  // != nullptr: dump the k x k Gramian (no lambda) of item 0 and stop
     unsigned long long* phases;  // != nullptr (MFX_ALS_PHASES=1): s_memtime clocks per phase, summed over the waves:
                                  // [0] Gramian loop, [1] staging into LDS, [2] factorisation, [3] triangular solves, [4] systems
+    // implicit-feedback kernels (k_ials_*) only; appended so that the fields above keep their kernel-argument offsets
+    float alpha;       // confidence weight of a gathered entry: w = fp32(alpha * r)
+    const float* G;    // [k][k] base Gramian X^T X + lambda I (ials_base_gramian), the start of every unsplit / reduced system
 };
 constexpr uint32_t kPhaseCopies = 1024;
 __device__ __forceinline__ void phase_mark(const AlsArgs& a, int slot, unsigned long long& t) {
@@ -548,12 +564,71 @@ __device__ void factor_solve(float* lds, const AlsArgs& a, uint32_t seg, unsigne
 
 
 
+// ---- Implicit feedback (Hu, Koren, Volinsky 2008) --------------------------------------------------------------
+// The k_ials_* kernels (kImplicit, ials_half.hip) are the kernels below: every gathered entry r carries the Gramian weight
+// w = fp32(alpha r) and the rhs weight 1 + w (0 when r = 0: an explicit zero is no entry), and an unsplit system / a
+// reducer starts its accumulators from the base Gramian G = X^T X + lambda I instead of zero (the launches pass
+// lambda = 0, so factor_solve adds nothing more to the diagonal).  A system is then
+//   (X^T X + lambda I + sum_j w_j x_j x_j^T) y = sum_{j, r_j > 0} (1 + w_j) x_j.
+// How the weight reaches the MFMA (the same register is the A and the B operand of the unweighted Gramian):
+// MFX_IALS_SQRT = 0 feeds a scaled copy w x as the A operand, 1 scales the row IN PLACE by sqrt(w) after its rhs update
+// (no register more, one rounding more).  Measured at the Netflix shape (tools/ials_bench.py, one MI355X, same box and
+// call, profiles/r06_ials_bench*.json): copy 13.22 / 66.4 ms per iteration at k = 64 / 128, sqrt 14.02 / 70.4 ms -- the
+// copy costs no spills where it matters (k_ials_gram16: 128 VGPRs, 20-24 bytes of scratch in both forms) and saves the
+// v_sqrt and the multiplies that wait on it.
+// (copy form: a diagonal tile holds sum fl(w x_i) x_j and sum fl(w x_j) x_i, equal up to rounding; the staging keeps one.)
+#ifndef MFX_IALS_SQRT
+#define MFX_IALS_SQRT 0
+#endif
+constexpr bool kIalsSqrt = MFX_IALS_SQRT != 0;
+
+// r -> (rhs weight, Gramian operand scale): (1 + w or 0, sqrt(w)) in the sqrt form, (1 + w or 0, w) in the copy form
+__device__ __forceinline__ void ials_weights(float r, float alpha, float& rhs, float& scale) {
+    const float w = mul_rn(alpha, r);
+    rhs = r > 0.f ? add_rn(1.0f, w) : 0.f;
+    scale = kIalsSqrt ? __builtin_sqrtf(w) : w;
+}
+
+// G into the 32x32x2 accumulators of k_als_gram<NT>: tile (I, J), register r of lane (c31, h) is G[32 I + (r & 3) + 8 (r >> 2) + 4 h][32 J + c31]
+template <int NT>
+__device__ __forceinline__ void ials_base32(f32x16 (&acc)[Tiles<NT>::kCount], const float* __restrict__ G, uint32_t k, uint32_t c31, uint32_t h) {
+    int ti = 0;
+#pragma unroll
+    for (int I = 0; I < NT; ++I)
+#pragma unroll
+        for (int J = I; J < NT; ++J, ++ti)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const uint32_t row = 32 * I + (r & 3) + 8 * (r >> 2) + 4 * h, col = 32 * J + c31;
+                acc[ti][r] = row < k && col < k ? G[row * k + col] : 0.f;
+            }
+}
+// One gathered row pair of k_als_gram<NT>, implicit form: rhs from the unscaled row, then the weighted MFMAs
+template <int NT>
+__device__ __forceinline__ void ials_rows(float (&av)[NT], float rv, float alpha, float (&bacc)[NT], f32x16 (&acc)[Tiles<NT>::kCount]) {
+    float rw, sw;
+    ials_weights(rv, alpha, rw, sw);
+    float xa[NT];
+#pragma unroll
+    for (int I = 0; I < NT; ++I) {
+        bacc[I] += rw * av[I];
+        if constexpr (kIalsSqrt) { av[I] *= sw; xa[I] = av[I]; }
+        else xa[I] = av[I] * sw;
+    }
+    int ti = 0;
+#pragma unroll
+    for (int I = 0; I < NT; ++I)
+#pragma unroll
+        for (int J = I; J < NT; ++J, ++ti)
+            acc[ti] = __builtin_amdgcn_mfma_f32_32x32x2f32(xa[I], av[J], acc[ti], 0, 0, 0);
+}
+
 // Waves per SIMD the LDS image allows anyway (k = 128: 34 KB per system -> one wave per SIMD; k = 96: two), stated
 // so that the register allocator does not trade the Gramian loop's pipelining for an occupancy it cannot get.
 constexpr int als_waves(int NT) { return NT >= 4 ? 1 : NT == 3 ? 2 : NT == 2 ? 3 : 6; }
 
 template <int NT>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(als_waves(NT), als_waves(NT)))) void k_als_gram(AlsArgs a) {
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(als_waves(NT), als_waves(NT)))) void ALS_KERNEL(gram)(AlsArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const uint32_t lane = threadIdx.x & 63, c31 = lane & 31, h = lane >> 5;
     const uint32_t item = blockIdx.x;
@@ -571,6 +646,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(als_waves(NT
     for (int t = 0; t < Tiles<NT>::kCount; ++t)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
+    if constexpr (kImplicit)
+        if (it.slot < 0) ials_base32<NT>(acc, a.G, k, c31, h);  // chunk partials start from zero: the reducer adds G
 #pragma unroll
     for (int I = 0; I < NT; ++I) bacc[I] = 0.f;
 
@@ -615,6 +692,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(als_waves(NT
             constexpr int s = decltype(S)::value;
     #pragma unroll
             for (int u = 0; u < U; ++u) {
+                if constexpr (kImplicit) {
+                    ials_rows<NT>(av[s][u], rv[s][u], a.alpha, bacc, acc);
+                    continue;
+                }
                 int ti = 0;
     #pragma unroll
                 for (int I = 0; I < NT; ++I) {
@@ -697,6 +778,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(als_waves(NT
             load_idx(q0 + 4 * U);
     #pragma unroll
             for (int u = 0; u < U; ++u) {
+                if constexpr (kImplicit) {
+                    ials_rows<NT>(av[u], rv[u], a.alpha, bacc, acc);
+                    continue;
+                }
                 int ti = 0;
     #pragma unroll
                 for (int I = 0; I < NT; ++I) {
@@ -725,7 +810,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(als_waves(NT
 }
 
 template <int NT>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(als_waves(NT), als_waves(NT)))) void k_als_reduce(AlsArgs a) {
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(als_waves(NT), als_waves(NT)))) void ALS_KERNEL(reduce)(AlsArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const uint32_t lane = threadIdx.x & 63;
     if (blockIdx.x >= a.count) return;
@@ -736,6 +821,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(als_waves(NT
     for (int t = 0; t < Tiles<NT>::kCount; ++t)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
+    if constexpr (kImplicit) ials_base32<NT>(acc, a.G, a.k, lane & 31, lane >> 5);
 #pragma unroll
     for (int I = 0; I < NT; ++I) bacc[I] = 0.f;
     for (uint32_t s = 0; s < rd.nslots; ++s) {  // chunk order: deterministic
@@ -760,6 +846,20 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(als_waves(NT
 // permutation that stage_tiles16 undoes on the way to LDS.  10 of 16 tiles (upper triangle of the
 // 4 x 4 set grid) = 320 MFMA cycles per 4 rows, against 384 for 3 of 4 32x32 tiles.
 constexpr int kSets = 4, kTiles16 = kSets * (kSets + 1) / 2;
+
+// G [k][k] into the 16x16x4 accumulators of k_als_gram16: tile (e, f), register q of lane (c, g) is G[4 (4 g + q) + e][4 c + f]
+__device__ __forceinline__ void ials_base16(f32x4 (&acc)[kTiles16], const float* __restrict__ G, uint32_t k, uint32_t c, uint32_t g) {
+    int ti = 0;
+#pragma unroll
+    for (int e = 0; e < kSets; ++e)
+#pragma unroll
+        for (int f = e; f < kSets; ++f, ++ti)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const uint32_t row = 4 * (4 * g + q) + e, col = 4 * c + f;
+                acc[ti][q] = row < k && col < k ? G[row * k + col] : 0.f;
+            }
+}
 
 __device__ __forceinline__ void stage_tiles16(f32x4 (&acc)[kTiles16], float (&bacc)[kSets], float* lds) {
     const uint32_t lane = threadIdx.x & 63, c = lane & 15, g = lane >> 4;
@@ -862,9 +962,27 @@ __device__ __forceinline__ void g16_load_rows(Gram16Regs<D>& r, const char* __re
     }
 }
 template <int D, int S>
-__device__ __forceinline__ void g16_mfma(Gram16Regs<D>& r) {
+__device__ __forceinline__ void g16_mfma(Gram16Regs<D>& r, float alpha) {
 #pragma unroll
     for (int u = 0; u < kU16; ++u) {
+        if constexpr (kImplicit) {  // the same with the weights of ials_weights: rhs from the unscaled row, then the MFMAs
+            float rw, sw;
+            ials_weights(r.rv[S][u], alpha, rw, sw);
+            const float hi = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, rw), 0xE4, 0xF, 0xF, false));
+            const f32x2 rr = {rw, hi};
+            r.bacc[0] = fma2(rr, r.av[S][u].lo, r.bacc[0]);
+            r.bacc[1] = fma2(rr, r.av[S][u].hi, r.bacc[1]);
+            f32x4 xa;  // A operand
+            if constexpr (kIalsSqrt) { r.av[S][u] *= sw; xa = r.av[S][u]; }
+            else xa = r.av[S][u] * sw;
+            int ti = 0;
+#pragma unroll
+            for (int e = 0; e < kSets; ++e)
+#pragma unroll
+                for (int f = e; f < kSets; ++f, ++ti)
+                    r.acc[ti] = __builtin_amdgcn_mfma_f32_16x16x4f32(xa[e], r.av[S][u][f], r.acc[ti], 0, 0, 0);
+            continue;
+        }
         // rhs: two v_pk_fma_f32 with the rating duplicated into a register pair BY HAND.  The compiler's own form reads
         // the rating through op_sel from (rating, whatever sits in the odd partner register) -- which the allocator
         // fills with a destination of the loads just issued, and the waitcnt pass then drains every load in flight
@@ -886,6 +1004,7 @@ struct Gram16Ctx {  // loop-invariant operands of the stages
     const uint32_t* ibase; const float* vbase; const char* Xb;
     uint32_t g, len, rowbytes, lane_off, zero_off;
     bool col_ok;
+    float alpha;  // (k_ials_gram16 only)
 };
 // Steps s, s + 1, ... on sets U, U + 1, ... D - 1: MFMAs of step s on set U, the factor rows of step s + D - 1 into the
 // set the previous step has just released, the indices of step s + D into this step's own (already consumed) slots.
@@ -897,7 +1016,7 @@ __device__ __forceinline__ bool g16_steps(Gram16Regs<D>& r, const Gram16Ctx& c, 
         g16_load_rows<D, (U + D - 1) % D>(r, c.Xb, c.vbase, s + D - 1, c.g, c.len, c.col_ok, c.rowbytes, c.lane_off, c.zero_off);
         g16_load_idx<D, U>(r, c.ibase, s + D, c.g);
         __builtin_amdgcn_sched_barrier(0);
-        g16_mfma<D, U>(r);
+        g16_mfma<D, U>(r, c.alpha);
         __builtin_amdgcn_sched_barrier(0);
         if (++s * kRows16 >= c.len) return true;
         return g16_steps<D, U + 1>(r, c, s);
@@ -926,7 +1045,7 @@ __device__ __forceinline__ void g16_prologue(Gram16Regs<D>& r, const Gram16Ctx& 
 // entries per system) wants the latency hiding of three or four (7.9 ms; 9.2 ms at two; r4: four, see kU16).  Three = 168 VGPRs, no
 // spills; four = 128 VGPRs + 18 spilled dwords, same time.
 template <int WAVES, int D, bool FULL>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES))) void k_als_gram16(AlsArgs a) {
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES))) void ALS_KERNEL(gram16)(AlsArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const uint32_t lane = threadIdx.x & 63, c = lane & 15, g = lane >> 4;
     const uint32_t item = blockIdx.x;
@@ -941,6 +1060,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES
     unsigned long long tmark = a.phases ? __builtin_readcyclecounter() : 0ull;
 #pragma unroll
     for (int t = 0; t < kTiles16; ++t) r.acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+    if constexpr (kImplicit)
+        if (it.slot < 0) ials_base16(r.acc, a.G, k, c, g);  // chunk partials start from zero: the reducer adds G
     r.bacc[0] = r.bacc[1] = f32x2{0.f, 0.f};
 
     Gram16Ctx cx;
@@ -953,6 +1074,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES
     cx.lane_off = 16 * c;
     cx.zero_off = a.x_rows * cx.rowbytes;
     cx.g = g;
+    if constexpr (kImplicit) cx.alpha = a.alpha;
     g16_prologue<D, 0>(r, cx);
     for (uint32_t s = 0;;)
         if (g16_steps<D, 0>(r, cx, s)) break;
@@ -974,7 +1096,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES
     factor_solve<2, FULL>(lds, a, it.seg, tmark);
 }
 
-__global__ __launch_bounds__(64) void k_als_reduce16(AlsArgs a) {
+__global__ __launch_bounds__(64) void ALS_KERNEL(reduce16)(AlsArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const uint32_t lane = threadIdx.x & 63;
     if (blockIdx.x >= a.count) return;
@@ -983,6 +1105,7 @@ __global__ __launch_bounds__(64) void k_als_reduce16(AlsArgs a) {
     float bacc[kSets];
 #pragma unroll
     for (int t = 0; t < kTiles16; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+    if constexpr (kImplicit) ials_base16(acc, a.G, a.k, lane & 15, lane >> 4);
 #pragma unroll
     for (int e = 0; e < kSets; ++e) bacc[e] = 0.f;
     for (uint32_t s = 0; s < rd.nslots; ++s) {  // chunk order: deterministic
@@ -1014,15 +1137,15 @@ int launch_half_16(const AlsArgs& base, uint32_t nitems, uint32_t nreduces, uint
         a.count = nitems;
         // mean entries per work item: long items -> two waves per SIMD, tail-dominated launches -> three
         const bool longs = nnz / nitems >= 1024, full = a.k == 64;
-        if (longs && full) hipLaunchKernelGGL((k_als_gram16<MFX_G16_WL, MFX_G16_DL, true>), dim3(nitems), dim3(64), lds_bytes, st, a);
-        else if (longs) hipLaunchKernelGGL((k_als_gram16<MFX_G16_WL, MFX_G16_DL, false>), dim3(nitems), dim3(64), lds_bytes, st, a);
-        else if (full) hipLaunchKernelGGL((k_als_gram16<MFX_G16_WS, MFX_G16_DS, true>), dim3(nitems), dim3(64), lds_bytes, st, a);
-        else hipLaunchKernelGGL((k_als_gram16<MFX_G16_WS, MFX_G16_DS, false>), dim3(nitems), dim3(64), lds_bytes, st, a);
+        if (longs && full) hipLaunchKernelGGL((ALS_KERNEL(gram16)<MFX_G16_WL, MFX_G16_DL, true>), dim3(nitems), dim3(64), lds_bytes, st, a);
+        else if (longs) hipLaunchKernelGGL((ALS_KERNEL(gram16)<MFX_G16_WL, MFX_G16_DL, false>), dim3(nitems), dim3(64), lds_bytes, st, a);
+        else if (full) hipLaunchKernelGGL((ALS_KERNEL(gram16)<MFX_G16_WS, MFX_G16_DS, true>), dim3(nitems), dim3(64), lds_bytes, st, a);
+        else hipLaunchKernelGGL((ALS_KERNEL(gram16)<MFX_G16_WS, MFX_G16_DS, false>), dim3(nitems), dim3(64), lds_bytes, st, a);
         MFX_HIP(hipGetLastError());
     }
     if (nreduces) {
         a.count = nreduces;
-        hipLaunchKernelGGL(k_als_reduce16, dim3(nreduces), dim3(64), lds_bytes, st, a);
+        hipLaunchKernelGGL(ALS_KERNEL(reduce16), dim3(nreduces), dim3(64), lds_bytes, st, a);
         MFX_HIP(hipGetLastError());
     }
     return MFX_OK;
@@ -1034,20 +1157,20 @@ int launch_half_nt(const AlsArgs& base, uint32_t nitems, uint32_t nreduces, hipS
     // packed lower triangle (rows rounded up to 4 floats) + rhs: see solve_tail
     const size_t lds_bytes = ((size_t) 4 * (KP / 4 + 1) * (2 * (KP / 4)) + KP) * sizeof(float);
     if (lds_bytes > 48 * 1024) {  // a per-device attribute; setting it again is cheap next to a half-sweep
-        MFX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_als_gram<NT>),
+        MFX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ALS_KERNEL(gram)<NT>),
                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds_bytes));
-        MFX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_als_reduce<NT>),
+        MFX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ALS_KERNEL(reduce)<NT>),
                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds_bytes));
     }
     AlsArgs a = base;
     if (nitems) {
         a.count = nitems;
-        hipLaunchKernelGGL(k_als_gram<NT>, dim3(nitems), dim3(64), lds_bytes, st, a);
+        hipLaunchKernelGGL(ALS_KERNEL(gram)<NT>, dim3(nitems), dim3(64), lds_bytes, st, a);
         MFX_HIP(hipGetLastError());
     }
     if (nreduces) {
         a.count = nreduces;
-        hipLaunchKernelGGL(k_als_reduce<NT>, dim3(nreduces), dim3(64), lds_bytes, st, a);
+        hipLaunchKernelGGL(ALS_KERNEL(reduce)<NT>, dim3(nreduces), dim3(64), lds_bytes, st, a);
         MFX_HIP(hipGetLastError());
     }
     return MFX_OK;
@@ -1074,6 +1197,18 @@ constexpr uint32_t kAlsPad = 128;     // entries behind the index / value arrays
 static_assert(kAlsPad >= 16 * ((MFX_G16_DL > MFX_G16_DS ? MFX_G16_DL : MFX_G16_DS) + 2), "index / value padding too short for the pipeline depth");
 
 }  // namespace
+
+#if MFX_ALS_IMPLICIT
+int ials_half_launch(const AlsHalf& h, const float* X, uint32_t x_rows, float* Y, uint32_t k, const float* G, float alpha,
+                     float* ws, uint32_t* spd_fail, hipStream_t st) {
+    AlsArgs a{};
+    a.items = h.items.get(); a.reduces = h.reduces.get(); a.idx = h.idx.get(); a.val = h.val.get();
+    a.X = X; a.x_rows = x_rows; a.sentinel = (uint32_t) h.nnz; a.Y = Y; a.k = k; a.ws = ws; a.spd_fail = spd_fail;
+    a.lambda = 0.f;  // lambda is on G's diagonal already
+    a.alpha = alpha; a.G = G;
+    return launch_half(a, h.nitems, h.nreduces, h.nnz, st);
+}
+#else
 
 size_t als_ws_floats(uint32_t nslots, uint32_t k) {
     const size_t nt = (k + 31) / 32;
@@ -1141,6 +1276,19 @@ int AlsSolver::create(AlsSolver** out, const mfx_csx* R, const mfx_coo* T, const
     MFX_REQUIRE(out && R && p, "mfx_als_create: null argument");
     std::unique_ptr<AlsSolver> s(new AlsSolver());
     MFX_TRY(s->init(R, T, p, space, shard));
+    *out = s.release();
+    return MFX_OK;
+}
+
+int AlsSolver::create_implicit(AlsSolver** out, const mfx_csx* R, const mfx_params* p, float alpha, mfx_memspace space) {
+    MFX_REQUIRE(out && R && p, "mfx_ials_create: null argument");
+    MFX_REQUIRE(std::isfinite(alpha) && alpha >= 0.f, "mfx_ials_create: alpha = %g (finite and >= 0 required)", (double) alpha);
+    MFX_REQUIRE(p->k >= 1 && p->k <= 128, "implicit ALS: rank k = %u not supported (1 <= k <= 128)", p->k);
+    MFX_REQUIRE(p->schedule == 1, "implicit ALS: schedule must be 1 (there is no as-written mode)");
+    std::unique_ptr<AlsSolver> s(new AlsSolver());
+    s->implicit_ = true;
+    s->alpha_ = alpha;
+    MFX_TRY(s->init(R, nullptr, p, space, nullptr));
     *out = s.release();
     return MFX_OK;
 }
@@ -1225,9 +1373,18 @@ int AlsSolver::init(const mfx_csx* R, const mfx_coo* T, const mfx_params* p, mfx
     }
     MFX_TRY(rmse_partials_.alloc_zero(kRmseBlocks, st_));
     MFX_TRY(rmse_sum_.alloc_zero(1, st_));
+    if (implicit_) {
+        MFX_TRY(ials_check_values(rows_.val.get(), rows_.nnz, alpha_, "implicit ALS: R (CSR) value", st_));
+        MFX_TRY(ials_check_values(cols_.val.get(), cols_.nnz, alpha_, "implicit ALS: R (CSC) value", st_));
+        MFX_TRY(G_.alloc((size_t) k_ * k_));
+        MFX_TRY(gpart_.alloc(ials_base_ws_floats(std::max(m_, n_), k_)));
+        MFX_TRY(loss_ws_.alloc(ials_loss_ws_doubles(k_)));
+        MFX_TRY(loss_.alloc_zero(1, st_));
+    }
     MFX_HIP(hipStreamSynchronize(st_));
     return MFX_OK;
 }
+
 
 // After a half-sweep every rank holds only its own block of the factor it just solved: ONE grouped exchange
 // (every owner broadcasts its block inside a single ncclGroupStart / End) makes the replica whole again.
@@ -1291,7 +1448,11 @@ int AlsSolver::iterate(int n_iter, int with_rmse, mfx_iter_report* reports) {
     for (int it = 0; it < n_iter; ++it) {
         MFX_HIP(hipMemsetAsync(spd_fail_.get(), 0, sizeof(uint32_t), st_));
         MFX_HIP(hipEventRecord(ev_[0], st_));
-        if (p_.schedule == 0)  // as written: the reference's arithmetic, bit for bit (als_exact.hip)
+        if (implicit_) {  // (ev_[4]: the base Gramian of H is done)
+            MFX_TRY(ials_base_gramian(H_.get(), n_, k_, p_.lambda, gpart_.get(), G_.get(), st_));
+            MFX_HIP(hipEventRecord(ev_[4], st_));
+            MFX_TRY(ials_half_launch(rows_, H_.get(), n_, W_.get(), k_, G_.get(), alpha_, ws_.get(), spd_fail_.get(), st_));
+        } else if (p_.schedule == 0)  // as written: the reference's arithmetic, bit for bit (als_exact.hip)
             MFX_TRY(als_half_exact_launch(rows_, H_.get(), W_.get() + (size_t) row_lo_ * k_, k_, p_.lambda, spd_fail_.get(), st_));
         else
             MFX_TRY(als_half_launch(rows_, H_.get(), n_, W_.get() + (size_t) row_lo_ * k_, k_, p_.lambda, ws_.get(),
@@ -1299,7 +1460,11 @@ int AlsSolver::iterate(int n_iter, int with_rmse, mfx_iter_report* reports) {
         if (comm_) MFX_TRY(exchange(W_.get(), row_bounds_));
         MFX_HIP(hipEventRecord(ev_[1], st_));
         if (phases_.size()) MFX_TRY(print_phases("user half (W over H)"));
-        if (p_.schedule == 0)
+        if (implicit_) {  // (ev_[5]: the base Gramian of W is done)
+            MFX_TRY(ials_base_gramian(W_.get(), m_, k_, p_.lambda, gpart_.get(), G_.get(), st_));
+            MFX_HIP(hipEventRecord(ev_[5], st_));
+            MFX_TRY(ials_half_launch(cols_, W_.get(), m_, H_.get(), k_, G_.get(), alpha_, ws_.get(), spd_fail_.get(), st_));
+        } else if (p_.schedule == 0)
             MFX_TRY(als_half_exact_launch(cols_, W_.get(), H_.get() + (size_t) col_lo_ * k_, k_, p_.lambda, spd_fail_.get(), st_));
         else
             MFX_TRY(als_half_launch(cols_, W_.get(), m_, H_.get() + (size_t) col_lo_ * k_, k_, p_.lambda, ws_.get(),
@@ -1322,14 +1487,22 @@ int AlsSolver::iterate(int n_iter, int with_rmse, mfx_iter_report* reports) {
         MFX_HIP(hipMemcpyAsync(&bad, spd_fail_.get(), sizeof(uint32_t), hipMemcpyDeviceToHost, st_));
         MFX_HIP(hipStreamSynchronize(st_));
         if (with_rmse && global_test_nnz_ > 0) rmse = std::sqrt(sum / (double) global_test_nnz_);
-        float ms_w = 0.f, ms_h = 0.f, ms_r = 0.f;
-        MFX_HIP(hipEventElapsedTime(&ms_w, ev_[0], ev_[1]));
-        MFX_HIP(hipEventElapsedTime(&ms_h, ev_[1], ev_[2]));
+        float ms_w = 0.f, ms_h = 0.f, ms_r = 0.f, ms_gh = 0.f, ms_gw = 0.f;
+        if (implicit_) {
+            MFX_HIP(hipEventElapsedTime(&ms_gh, ev_[0], ev_[4]));
+            MFX_HIP(hipEventElapsedTime(&ms_w, ev_[4], ev_[1]));
+            MFX_HIP(hipEventElapsedTime(&ms_gw, ev_[1], ev_[5]));
+            MFX_HIP(hipEventElapsedTime(&ms_h, ev_[5], ev_[2]));
+            t_half_[2] += ms_gh * 1e-3; t_half_[3] += ms_gw * 1e-3; n_half_[2]++; n_half_[3]++;
+        } else {
+            MFX_HIP(hipEventElapsedTime(&ms_w, ev_[0], ev_[1]));
+            MFX_HIP(hipEventElapsedTime(&ms_h, ev_[1], ev_[2]));
+        }
         MFX_HIP(hipEventElapsedTime(&ms_r, ev_[2], ev_[3]));
         t_half_[0] += ms_w * 1e-3; t_half_[1] += ms_h * 1e-3; n_half_[0]++; n_half_[1]++;
         mfx_iter_report rep;
         rep.rank_time = 0.0;
-        rep.update_time = (ms_w + ms_h) * 1e-3;
+        rep.update_time = (ms_gh + ms_w + ms_gw + ms_h) * 1e-3;
         rep.rmse = rmse;
         rep.rmse_time = ms_r * 1e-3;
         update_acc_ += rep.update_time;
@@ -1358,16 +1531,27 @@ int AlsSolver::get_factors(float* W, float* H, mfx_memspace space) {
 
 int AlsSolver::kernel_times(int cap, const char** names, double* seconds, int64_t* launches) {
     static const char* nm[2] = {"als_half_rows(W over H)", "als_half_cols(H over W)"};
+    static const char* nm_impl[4] = {"ials_half_rows(W over H)", "ials_half_cols(H over W)", "ials_base_gram(H)", "ials_base_gram(W)"};
     int n = 0;
-    for (int i = 0; i < 2 && n < cap; ++i) {
+    for (int i = 0; i < 4 && n < cap; ++i) {
         if (!n_half_[i]) continue;
-        if (names) names[n] = nm[i];
+        if (names) names[n] = implicit_ ? nm_impl[i] : nm[i];
         if (seconds) seconds[n] = t_half_[i];
         if (launches) launches[n] = n_half_[i];
         ++n;
     }
-    t_half_[0] = t_half_[1] = 0; n_half_[0] = n_half_[1] = 0;
+    for (int i = 0; i < 4; ++i) { t_half_[i] = 0; n_half_[i] = 0; }
     return n;
+}
+
+int AlsSolver::loss(double* out) {
+    MFX_REQUIRE(implicit_, "mfx_ials_loss: not an implicit-feedback ALS handle (mfx_ials_create)");
+    MFX_REQUIRE(factors_set_, "mfx_ials_loss: call mfx_als_set_factors first");
+    MFX_TRY(use_device(device_));
+    MFX_TRY(ials_loss_launch(rows_, W_.get(), m_, H_.get(), n_, k_, p_.lambda, alpha_, loss_ws_.get(), loss_.get(), st_));
+    MFX_HIP(hipMemcpyAsync(out, loss_.get(), sizeof(double), hipMemcpyDeviceToHost, st_));
+    MFX_HIP(hipStreamSynchronize(st_));
+    return MFX_OK;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1424,5 +1608,29 @@ int als_half_op(int64_t nseg, int64_t nnz, const uint32_t* ptr, const uint32_t* 
     MFX_HIP(hipStreamSynchronize(os.st));
     return MFX_OK;
 }
+
+int ials_half_op(int64_t nseg, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val,
+                 int64_t nrows_x, const float* X, float* Y, int64_t k, float lambda, float alpha, int device) {
+    MFX_TRY(use_device(device));
+    OpStream os;
+    MFX_HIP(hipStreamCreateWithFlags(&os.st, hipStreamNonBlocking));
+    AlsHalf h;
+    MFX_TRY(h.build((uint32_t) nseg, (uint64_t) nnz, (uint32_t) nrows_x, ptr, idx, val, MFX_HOST, kAlsChunk, os.st));
+    MFX_TRY(ials_check_values(h.val.get(), h.nnz, alpha, "mfx_ials_half: value", os.st));
+    DevBuf<float> dX, dY, ws, G, part; DevBuf<uint32_t> fail_cnt;
+    MFX_TRY(dX.alloc_zero(((size_t) nrows_x + 1) * k, os.st)); MFX_TRY(dX.upload(X, (size_t) nrows_x * k, MFX_HOST, os.st));
+    MFX_TRY(dY.alloc_zero((size_t) nseg * k, os.st));
+    MFX_TRY(ws.alloc(std::max<size_t>(1, als_ws_floats(h.nslots, (uint32_t) k))));
+    MFX_TRY(G.alloc((size_t) k * k));
+    MFX_TRY(part.alloc(ials_base_ws_floats((uint32_t) nrows_x, (uint32_t) k)));
+    MFX_TRY(fail_cnt.alloc_zero(1, os.st));
+    MFX_TRY(ials_base_gramian(dX.get(), (uint32_t) nrows_x, (uint32_t) k, lambda, part.get(), G.get(), os.st));
+    MFX_TRY(ials_half_launch(h, dX.get(), (uint32_t) nrows_x, dY.get(), (uint32_t) k, G.get(), alpha, ws.get(), fail_cnt.get(), os.st));
+    MFX_HIP(hipMemcpyAsync(Y, dY.get(), sizeof(float) * (size_t) nseg * k, hipMemcpyDeviceToHost, os.st));
+    MFX_HIP(hipStreamSynchronize(os.st));
+    return MFX_OK;
+}
+
+#endif  // MFX_ALS_IMPLICIT
 
 }  // namespace mfx

@@ -39,6 +39,10 @@ class AlsSolver {
 public:
     static int create(AlsSolver** out, const mfx_csx* R, const mfx_coo* T, const mfx_params* p,
                       mfx_memspace space, const mfx_als_shard* shard = nullptr);
+    // implicit feedback (mfx_ials_create): R holds interaction strengths r >= 0, confidence 1 + alpha r
+    static int create_implicit(AlsSolver** out, const mfx_csx* R, const mfx_params* p, float alpha, mfx_memspace space);
+    bool implicit() const { return implicit_; }
+    int loss(double* out);  // implicit only: the objective at the current factors (ials.hip)
     ~AlsSolver();
     int set_factors(const float* W, const float* H, mfx_memspace space);
     int iterate(int n_iter, int with_rmse, mfx_iter_report* reports);
@@ -73,14 +77,32 @@ private:
     double update_acc_ = 0;
     bool factors_set_ = false;
     hipEvent_t ev_[6] = {};
-    double t_half_[2] = {0, 0};
-    int64_t n_half_[2] = {0, 0};
+    double t_half_[4] = {0, 0, 0, 0};  // [0], [1]: the two half-sweeps; implicit: [2], [3] the base Gramians of H and W
+    int64_t n_half_[4] = {0, 0, 0, 0};
+    // implicit feedback
+    bool implicit_ = false;
+    float alpha_ = 0.f;
+    DevBuf<float> G_, gpart_;        // base Gramian [k][k] of the fixed side, its per-partition partials
+    DevBuf<double> loss_ws_, loss_;  // fp64 Gramians + entry partials of the objective, the objective
 };
 
 // Launches one half-sweep: Y[seg] = argmin over segment `seg` given factor rows X[x_rows + 1][k],
 // whose last row must be all zeros.
 int als_half_launch(const AlsHalf& h, const float* X, uint32_t x_rows, float* Y, uint32_t k, float lambda, float* ws,
                     uint32_t* spd_fail, hipStream_t st, unsigned long long* phases = nullptr);
+// Implicit half-sweep (k_ials_*): G = the base Gramian X^T X + lambda I of all x_rows rows (ials_base_gramian)
+int ials_half_launch(const AlsHalf& h, const float* X, uint32_t x_rows, float* Y, uint32_t k, const float* G, float alpha,
+                     float* ws, uint32_t* spd_fail, hipStream_t st);
+// ials.hip: G = X^T X + lambda I over X [rows][k] (MFMA partials `part`, summed in a fixed order)
+uint32_t ials_base_parts(uint32_t rows);
+size_t ials_base_ws_floats(uint32_t rows, uint32_t k);
+int ials_base_gramian(const float* X, uint32_t rows, uint32_t k, float lambda, float* part, float* G, hipStream_t st);
+// MFX_ERR_INVALID unless every value is finite, >= 0 and alpha * value is finite (device-side check)
+int ials_check_values(const float* d_val, uint64_t n, float alpha, const char* what, hipStream_t st);
+// the implicit objective over the training rows (CSR orientation) into *out (device, fp64)
+size_t ials_loss_ws_doubles(uint32_t k);
+int ials_loss_launch(const AlsHalf& rows, const float* W, uint32_t m, const float* H, uint32_t n, uint32_t k, float lambda, float alpha,
+                     double* ws, double* out, hipStream_t st);
 // floats of workspace needed for `nslots` partial slots at rank k
 size_t als_ws_floats(uint32_t nslots, uint32_t k);
 
@@ -93,6 +115,8 @@ int als_gramian_op(int64_t cnt, const uint32_t* idx, int64_t nrows_x, const floa
                    int device);
 int als_half_op(int64_t nseg, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val,
                 int64_t nrows_x, const float* X, float* Y, int64_t k, float lambda, int variant, int device);
+int ials_half_op(int64_t nseg, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val,
+                 int64_t nrows_x, const float* X, float* Y, int64_t k, float lambda, float alpha, int device);
 
 }  // namespace mfx
 

@@ -240,6 +240,36 @@ int mfx_als_destroy(mfx_als_t s) {
         return MFX_OK;
     });
 }
+/* ------------------------------------------------------------------ implicit-feedback ALS */
+int mfx_ials_create(mfx_als_t* out, const mfx_csx* R, const mfx_params* p, float alpha, mfx_memspace space) {
+    return guarded("mfx_ials_create", [&]() -> int {
+        MFX_REQUIRE(out, "mfx_ials_create: out is NULL");
+        *out = nullptr;
+        AlsSolver* s = nullptr;
+        MFX_TRY(AlsSolver::create_implicit(&s, R, p, alpha, space));  // (argument checks before the device is touched)
+        *out = new mfx_als_s{s};
+        return MFX_OK;
+    });
+}
+int mfx_ials_loss(mfx_als_t s, double* loss) {
+    return guarded("mfx_ials_loss", [&]() -> int {
+        MFX_REQUIRE(s && s->impl && loss, "mfx_ials_loss: null argument");
+        return s->impl->loss(loss);
+    });
+}
+int mfx_ials_half(int64_t nseg, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val,
+                  int64_t nrows_x, const float* X, float* Y, int64_t k, float lambda, float alpha, int device) {
+    return guarded("mfx_ials_half", [&]() -> int {
+        MFX_REQUIRE(nseg > 0 && nnz >= 0 && ptr && X && Y && nrows_x > 0, "mfx_ials_half: bad argument");
+        MFX_REQUIRE(nnz == 0 || (idx && val), "mfx_ials_half: null idx / val with nnz > 0");
+        MFX_REQUIRE(k >= 1 && k <= 128, "implicit ALS: rank k = %lld not supported (1 <= k <= 128)", (long long) k);
+        MFX_REQUIRE(std::isfinite(alpha) && alpha >= 0.f, "mfx_ials_half: alpha = %g (finite and >= 0 required)", (double) alpha);
+        MFX_REQUIRE(nseg < (int64_t) 0xFFFFFFFFll && nrows_x < (int64_t) 0xFFFFFFFFll && nnz < (int64_t) 0xFFFF0000ll,
+                    "mfx_ials_half: sizes exceed the 32-bit index range");
+        return ials_half_op(nseg, nnz, ptr, idx, val, nrows_x, X, Y, k, lambda, alpha, device);
+    });
+}
+
 int mfx_als_run(const mfx_csx* R, const mfx_coo* T, float* W, float* H, const mfx_params* p,
                 mfx_iter_report* reports) {
     return guarded("mfx_als_run", [&]() -> int {

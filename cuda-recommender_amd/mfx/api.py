@@ -499,6 +499,65 @@ class AlsSolver:
             pass
 
 
+class ImplicitAlsSolver:
+    """Resident implicit-feedback ALS (mfx_ials_create): R holds interaction strengths r >= 0, every (user, item)
+    pair is in the loss with preference p = (r > 0) and confidence 1 + alpha r.  Factors use the ALS layout,
+    W [rows][k] and H [cols][k].  device_arrays: the matrix as a dict of device tensors (mfx.synth_torch)."""
+
+    def __init__(self, R: Optional[RatingData], parameters: parameter, alpha: float, device_arrays: Optional[dict] = None):
+        self.handle = C.c_void_p()
+        cp = parameters.to_c()
+        if device_arrays is not None:
+            d = device_arrays
+            ptr = lambda t: C.c_void_p(int(t.data_ptr())) if t is not None and t.numel() else None
+            self.rows, self.cols, self.k = int(d["rows"]), int(d["cols"]), int(parameters.k)
+            csx = L.mfx_csx(self.rows, self.cols, int(d["csr_val"].numel()), ptr(d["csc_col_ptr"]), ptr(d["csc_row_idx"]),
+                            ptr(d["csc_val"]), ptr(d["csr_row_ptr"]), ptr(d["csr_col_idx"]), ptr(d["csr_val"]))
+            space = L.MFX_DEVICE
+        else:
+            self.rows, self.cols, self.k = R.rows, R.cols, int(parameters.k)
+            csx, space = _csx(R), L.MFX_HOST
+        L.check(L.lib().mfx_ials_create(C.byref(self.handle), C.byref(csx), C.byref(cp), float(alpha), space))
+
+    def set_factors(self, H, W=None):
+        _f32c(H, (self.cols, self.k))
+        if W is not None:
+            _f32c(W, (self.rows, self.k))
+        L.check(L.lib().mfx_als_set_factors(self.handle, _vp(W) if W is not None else None, _vp(H), L.MFX_HOST))
+
+    def iterate(self, n_iter: int):
+        """n_iter (W-half, H-half) sweeps; the reports carry update_time (rmse stays 0)."""
+        reports = (L.mfx_iter_report * max(1, n_iter))()
+        L.check(L.lib().mfx_als_iterate(self.handle, n_iter, 0, reports))
+        return list(reports)[:n_iter]
+
+    def get_factors(self):
+        W = np.empty((self.rows, self.k), np.float32)
+        H = np.empty((self.cols, self.k), np.float32)
+        L.check(L.lib().mfx_als_get_factors(self.handle, _vp(W), _vp(H), L.MFX_HOST))
+        return W, H
+
+    def loss(self) -> float:
+        """The implicit objective at the current factors (fp64, include/mfx.h mfx_ials_loss)."""
+        out = C.c_double(0.0)
+        L.check(L.lib().mfx_ials_loss(self.handle, C.byref(out)))
+        return float(out.value)
+
+    def kernel_times(self):
+        return _kernel_times(L.lib().mfx_als_kernel_times, self.handle)
+
+    def close(self):
+        if self.handle:
+            L.lib().mfx_als_destroy(self.handle)
+            self.handle = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 # ---------------------------------------------------------------------------------------------
 # single operators (one per reference function on the path)
 # ---------------------------------------------------------------------------------------------
@@ -549,6 +608,15 @@ def als_half(ptr, idx, val, X, k: int, lam: float, device: int = 0, variant: int
     Y = np.empty((nseg, k), np.float32)
     L.check(L.lib().mfx_als_half(nseg, idx.shape[0], _u32(ptr), _u32(idx), _f32(val), X.shape[0], _f32(X), _f32(Y),
                                  k, lam, variant, device))
+    return Y
+
+
+def ials_half(ptr, idx, val, X, k: int, lam: float, alpha: float, device: int = 0) -> np.ndarray:
+    """One implicit-feedback half-sweep (mfx_ials_half): Y [nseg][k] over all rows of X [nrows][k]."""
+    nseg = ptr.shape[0] - 1
+    Y = np.empty((nseg, k), np.float32)
+    L.check(L.lib().mfx_ials_half(nseg, idx.shape[0], _u32(ptr), _u32(idx), _f32(val), X.shape[0], _f32(X), _f32(Y),
+                                  k, lam, alpha, device))
     return Y
 
 

@@ -222,6 +222,26 @@ int mfx_als_kernel_times(mfx_als_t s, int cap, const char** names, double* secon
                          int64_t* launches);
 int mfx_als_destroy(mfx_als_t s);
 
+/* Implicit-feedback ALS (Hu, Koren, Volinsky 2008) on the ALS factor layout.  R holds interaction strengths r >= 0;
+ * every (user, item) pair is in the loss with preference p = (r > 0) and confidence c = 1 + w, w = fp32(alpha * r).
+ * A half-sweep solves, for every segment s over the fixed other factor X (all its rows),
+ *     (X^T X + lambda I + sum_{j in s} w_j x_j x_j^T) y_s = sum_{j in s, r_j > 0} (1 + w_j) x_j
+ * (an empty segment gives y = 0; an explicit zero is no entry).  Returns an mfx_als_t: mfx_als_set_factors / _iterate /
+ * _get_factors / _kernel_times / _destroy work on it unchanged (iterate fills update_time, rmse stays 0).  Reads k,
+ * lambda, device, profile, verbose of *p; schedule must be 1 (no as-written mode exists for this method).  R: both
+ * orientations, values finite and >= 0 with alpha * r finite (checked on the device).  Single GPU.
+ * MFX_ERR_INVALID without touching the device: alpha < 0 / NaN / Inf, k outside 1..128, schedule != 1, a null argument. */
+int mfx_ials_create(mfx_als_t* out, const mfx_csx* R, const mfx_params* p, float alpha, mfx_memspace space);
+/* The objective at the current factors, in fp64:
+ *     L = sum_{(u,i) in R} [c_ui (p_ui - s_ui)^2 - s_ui^2] + <W^T W, H^T H>_F + lambda (|W|^2 + |H|^2)
+ * (= the sum over all rows x cols pairs of c (p - s)^2, plus the regulariser), s_ui the fp32 fused multiply-add chain
+ * in ascending t.  MFX_ERR_INVALID on an explicit-ALS handle. */
+int mfx_ials_loss(mfx_als_t s, double* loss);
+/* Single operator for tests: one implicit half-sweep over host arrays (the counterpart of mfx_als_half):
+ * Y [nseg][k] from X [nrows_x][k] and the segments ptr / idx / val. */
+int mfx_ials_half(int64_t nseg, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val,
+                  int64_t nrows_x, const float* X, float* Y, int64_t k, float lambda, float alpha, int device);
+
 /* ------------------------------------------------------------------------------------
  * Top-N recommendation: a resident handle over trained factors that returns, for each
  * requested user, the n_top highest-scoring items the user must not be excluded from.

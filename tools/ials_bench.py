@@ -1,0 +1,82 @@
+"""Implicit-feedback ALS at the Netflix shape: time per iteration against explicit ALS on the same matrix.
+
+Builds the Netflix-shaped synthetic matrix on the GPU (mfx.synth_torch, as bench.py does; the ratings 1..5 are taken
+as interaction strengths) and prints ONE JSON line with, for every k: ms per implicit iteration and per half-sweep,
+the two base Gramians (X^T X + lambda I), explicit ALS ms per iteration on the same matrix in the same run, the flop
+of an iteration and its fraction of the 157.3 TF fp32 MFMA peak, and the objective (mfx_ials_loss) after each
+iteration.
+
+    python tools/ials_bench.py [--ks 64,128] [--iters 5] [--alpha 1.0] [--lam 0.05]
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "cuda-recommender_amd"))
+
+PEAK_TF = 157.3
+ROWS, COLS, NNZ = 480189, 17770, 99_072_112
+
+
+def flop_per_iteration(rows, cols, nnz, k):
+    """Flop of one iteration in bench.py's ALS convention (both halves: symmetric Gramian k (k + 1) and rhs 2 k per
+    gathered entry) plus the two base Gramians (k (k + 1) per row of each factor)."""
+    return 2.0 * (nnz * k * (k + 1) + 2.0 * nnz * k) + (rows + cols) * k * (k + 1)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--ks", default="64,128")
+    ap.add_argument("--iters", type=int, default=5)
+    ap.add_argument("--alpha", type=float, default=1.0)
+    ap.add_argument("--lam", type=float, default=0.05)
+    ap.add_argument("--seed", type=int, default=1234)
+    a = ap.parse_args()
+    import torch
+    import mfx
+    from mfx import synth_torch
+    d = synth_torch.synth_ratings_device(ROWS, COLS, NNZ, seed=a.seed, device="cuda:0")
+    rows, cols, nnz = int(d["rows"]), int(d["cols"]), int(d["csr_val"].numel())
+    out = {"workload": f"{rows}x{cols} nnz={nnz}", "alpha": a.alpha, "lambda": a.lam, "iters": a.iters,
+           "library": os.path.relpath(mfx.LIB_PATH, ROOT), "runs": []}
+    for k in [int(x) for x in a.ks.split(",")]:
+        p = mfx.parameter()
+        p.k, p.lambda_ = k, a.lam
+        H0 = mfx.initial_col(cols, k)
+        s = mfx.ImplicitAlsSolver(None, p, a.alpha, device_arrays=d)
+        s.set_factors(H0)
+        s.iterate(1)  # warmup
+        s.kernel_times()
+        ms, losses = [], []
+        for _ in range(a.iters):
+            ms.append(s.iterate(1)[0].update_time * 1e3)
+            losses.append(s.loss())
+        kt = s.kernel_times()
+        s.close()
+        per = {name: t * 1e3 / n for name, (t, n) in kt.items()}
+        e = mfx.AlsSolver(None, None, p, device_arrays=d)
+        e.set_factors(H0)
+        e.iterate(1, with_rmse=False)
+        ems = [r.update_time * 1e3 for r in e.iterate(a.iters, with_rmse=False)]
+        e.close()
+        med = float(np.median(ms))
+        fl = flop_per_iteration(rows, cols, nnz, k)
+        out["runs"].append({
+            "k": k, "ms_per_iteration": round(med, 3), "ms_min": round(min(ms), 3), "ms_max": round(max(ms), 3),
+            "ms_user_half": round(per["ials_half_rows(W over H)"], 3), "ms_item_half": round(per["ials_half_cols(H over W)"], 3),
+            "ms_base_gram_H": round(per["ials_base_gram(H)"], 3), "ms_base_gram_W": round(per["ials_base_gram(W)"], 3),
+            "explicit_als_ms_per_iteration": round(float(np.median(ems)), 3),
+            "ratio_to_explicit": round(med / float(np.median(ems)), 3),
+            "flop_per_iteration": fl, "fraction_of_fp32_mfma_peak": round(fl / (med * 1e-3) / (PEAK_TF * 1e12), 4),
+            "loss_per_iteration": losses,
+        })
+        torch.cuda.synchronize()
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
