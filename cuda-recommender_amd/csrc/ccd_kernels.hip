@@ -181,6 +181,7 @@ struct FlatArgs {
     float2* pack2;
     const float* next_vec;
     float4* pack4;
+    const float* gather_aux;  // kAux modes: the second gathered operand
 };
 
 // G: element of the gathered operand in global memory; S: the same inside the LDS slice (the fused CSR pass keeps
@@ -190,19 +191,25 @@ template <typename S, typename G> __device__ __forceinline__ S to_slice(const G&
 template <> __device__ __forceinline__ F3 to_slice<F3, float4>(const float4& g) { return F3{g.x, g.y, g.z}; }
 template <typename G, typename S> __device__ __forceinline__ G from_slice(const S& s) { return s; }
 template <> __device__ __forceinline__ float4 from_slice<float4, F3>(const F3& s) { return make_float4(s.x, s.y, s.z, 0.f); }
+// kAux: a second, 4-byte gathered operand staged as its own float slice behind the first (FM_FCSR2: a 16-byte entry
+// plus a 4-byte one keeps every ds_read aligned, where one 20-byte entry would not)
 template <int MODE> struct ModeTraits;
-template <> struct ModeTraits<FM_SWEEP> { using G = float;  using S = float;  using P = float;  static constexpr bool kPerSeg = false, kWrite = false, kDot = true; };
-template <> struct ModeTraits<FM_RESID> { using G = float;  using S = float;  using P = float;  static constexpr bool kPerSeg = true,  kWrite = true,  kDot = false; };
-template <> struct ModeTraits<FM_FCSC>  { using G = float2; using S = float2; using P = float2; static constexpr bool kPerSeg = true,  kWrite = true,  kDot = true; };
-template <> struct ModeTraits<FM_FCSR>  { using G = float4; using S = F3;     using P = float2; static constexpr bool kPerSeg = true,  kWrite = true,  kDot = true; };
+template <> struct ModeTraits<FM_SWEEP> { using G = float;  using S = float;  using P = float;  static constexpr bool kPerSeg = false, kWrite = false, kDot = true, kAux = false; };
+template <> struct ModeTraits<FM_RESID> { using G = float;  using S = float;  using P = float;  static constexpr bool kPerSeg = true,  kWrite = true,  kDot = false, kAux = false; };
+template <> struct ModeTraits<FM_FCSC>  { using G = float2; using S = float2; using P = float2; static constexpr bool kPerSeg = true,  kWrite = true,  kDot = true, kAux = false; };
+template <> struct ModeTraits<FM_FCSR>  { using G = float4; using S = F3;     using P = float2; static constexpr bool kPerSeg = true,  kWrite = true,  kDot = true, kAux = false; };
+template <> struct ModeTraits<FM_FCSC_RO> { using G = float2; using S = float2; using P = float2; static constexpr bool kPerSeg = true, kWrite = false, kDot = true, kAux = false; };
+template <> struct ModeTraits<FM_FCSR_RO> { using G = float4; using S = F3;     using P = float2; static constexpr bool kPerSeg = true, kWrite = false, kDot = true, kAux = false; };
+template <> struct ModeTraits<FM_FCSC2> { using G = float4; using S = float4; using P = float4; static constexpr bool kPerSeg = true,  kWrite = true,  kDot = true, kAux = false; };
+template <> struct ModeTraits<FM_FCSR2> { using G = float4; using S = float4; using P = float4; static constexpr bool kPerSeg = true,  kWrite = true,  kDot = true, kAux = true; };
 
 __device__ __forceinline__ float zero_of(float) { return 0.f; }
 __device__ __forceinline__ float2 zero_of(float2) { return make_float2(0.f, 0.f); }
 __device__ __forceinline__ float4 zero_of(float4) { return make_float4(0.f, 0.f, 0.f, 0.f); }
 
-// One element: new residual value and its (g, h) contribution.
+// One element: new residual value and its (g, h) contribution.  aux: the kAux operand (else unused).
 template <int MODE>
-__device__ __forceinline__ void element_op(float v, const typename ModeTraits<MODE>::G& ga,
+__device__ __forceinline__ void element_op(float v, const typename ModeTraits<MODE>::G& ga, float aux,
                                            const typename ModeTraits<MODE>::P& ps, int add,
                                            float& v_out, float& gc, float& hc) {
     if constexpr (MODE == FM_SWEEP) {
@@ -214,14 +221,21 @@ __device__ __forceinline__ void element_op(float v, const typename ModeTraits<MO
         v_out = add ? add_rn(v, prod) : sub_rn(v, prod);
         gc = 0.f;
         hc = 0.f;
-    } else if constexpr (MODE == FM_FCSC) {
+    } else if constexpr (MODE == FM_FCSC || MODE == FM_FCSC_RO) {
         v_out = add_rn(sub_rn(v, mul_rn(ga.x, ps.x)), mul_rn(ga.y, ps.y));
         gc = ga.y * v_out;
         hc = ga.y * ga.y;
-    } else {
+    } else if constexpr (MODE == FM_FCSR || MODE == FM_FCSR_RO) {
         v_out = add_rn(sub_rn(v, mul_rn(ga.x, ps.x)), mul_rn(ga.y, ps.y));
         gc = ga.z * v_out;
         hc = ga.z * ga.z;
+    } else {
+        // catch-up: the previous rank's update exactly as its read-only pass computed it, then this rank's
+        const float r = add_rn(sub_rn(v, mul_rn(ga.x, ps.x)), mul_rn(ga.y, ps.y));
+        v_out = add_rn(sub_rn(r, mul_rn(ga.z, ps.z)), mul_rn(ga.w, ps.w));
+        const float d = MODE == FM_FCSC2 ? ga.w : aux;
+        gc = d * v_out;
+        hc = d * d;
     }
 }
 
@@ -247,8 +261,12 @@ __device__ __forceinline__ float2 load_partial_sc1(const float2* p) {
     return make_float2(__builtin_bit_cast(float, (uint32_t) bits), __builtin_bit_cast(float, (uint32_t) (bits >> 32)));
 }
 
+// The read-only passes of rank_pair hold as much LDS as FM_FCSC / FM_FCSR, so a CU takes two of their workgroups -- if they
+// stay at 64 VGPRs (FM_FCSR_RO takes 66, hence 7 waves per SIMD and one workgroup, when left to the allocator)
+template <int MODE> constexpr int flat_min_waves(int block) { return MODE == FM_FCSC_RO || MODE == FM_FCSR_RO ? block / 128 : 1; }
+
 template <int MODE, bool LDS, int BLOCK, bool PSCHK, bool FUSE = false>
-__global__ __launch_bounds__(BLOCK) void k_flat(FlatArgs a) {
+__global__ __launch_bounds__(BLOCK, flat_min_waves<MODE>(BLOCK)) void k_flat(FlatArgs a) {
     static_assert(!FUSE || ModeTraits<MODE>::kDot, "fused finalize: passes that produce sums");
     using TR = ModeTraits<MODE>;
     // FUSE: dispatch slot -> chunk through wg_order (ascending first segment, so that the chunks of one segment
@@ -259,6 +277,8 @@ __global__ __launch_bounds__(BLOCK) void k_flat(FlatArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     using S = typename TR::S;
     S* __restrict__ slice = reinterpret_cast<S*>(lds_raw);
+    constexpr size_t kSliceEntry = sizeof(S) + (TR::kAux ? sizeof(float) : 0);  // LDS bytes per gathered index
+    float* __restrict__ aux_slice = reinterpret_cast<float*>(lds_raw + ((size_t) a.panel_rows + 1) * sizeof(S));
     const uint32_t lane = threadIdx.x & 63;
     const uint32_t span = __builtin_amdgcn_readfirstlane(chunk * (BLOCK / 64) + (threadIdx.x >> 6));
     const G* __restrict__ gather = static_cast<const G*>(a.gather);
@@ -290,10 +310,14 @@ __global__ __launch_bounds__(BLOCK) void k_flat(FlatArgs a) {
         const uint32_t cnt = a.gather_len - gbase < a.panel_rows ? a.gather_len - gbase : a.panel_rows;
         for (uint32_t i = threadIdx.x; i < cnt; i += BLOCK) slice[i] = to_slice<S, G>(gather[gbase + i]);
         if (threadIdx.x == 0) slice[a.panel_rows] = S{};
+        if constexpr (TR::kAux) {
+            for (uint32_t i = threadIdx.x; i < cnt; i += BLOCK) aux_slice[i] = a.gather_aux[gbase + i];
+            if (threadIdx.x == 0) aux_slice[a.panel_rows] = 0.f;
+        }
     }
     // The workgroup touches a contiguous window of ranks; stage their per-segment operands next to
     // the slice so that segmented tiles read LDS instead of chasing seg_of_rank -> perseg through L2.
-    P* __restrict__ ps_lds = reinterpret_cast<P*>(lds_raw + (((size_t) a.panel_rows + 1) * sizeof(S) + 15) / 16 * 16);
+    P* __restrict__ ps_lds = reinterpret_cast<P*>(lds_raw + (((size_t) a.panel_rows + 1) * kSliceEntry + 15) / 16 * 16);
     uint32_t win_base = 0;
     if constexpr (LDS && TR::kPerSeg) {
         const uint32_t first = chunk * (BLOCK / 64);
@@ -368,10 +392,12 @@ __global__ __launch_bounds__(BLOCK) void k_flat(FlatArgs a) {
         const uint32_t ids[4] = {(uint32_t) id.x, (uint32_t) id.y, (uint32_t) id.z, (uint32_t) id.w};
         const float vs[4] = {v.x, v.y, v.z, v.w};
         G ga[4];
+        float gx[4] = {};
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             if constexpr (LDS) ga[e] = from_slice<G, S>(slice[ids[e]]);
             else ga[e] = ids[e] < a.gather_len ? gather[ids[e]] : zero_of(G{});  // cache panels pad with index G
+            if constexpr (LDS && TR::kAux) gx[e] = aux_slice[ids[e]];
         }
         float vo[4], gc[4], hc[4];
 
@@ -379,7 +405,7 @@ __global__ __launch_bounds__(BLOCK) void k_flat(FlatArgs a) {
             // ---- no segment starts in this tile: everything belongs to the open segment ----
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                element_op<MODE>(vs[e], ga[e], pcur, a.add, vo[e], gc[e], hc[e]);
+                element_op<MODE>(vs[e], ga[e], gx[e], pcur, a.add, vo[e], gc[e], hc[e]);
                 if (partial && e0 + e >= a.nnz) { gc[e] = 0.f; hc[e] = 0.f; }
                 if constexpr (TR::kDot) { og += gc[e]; oh += hc[e]; }
             }
@@ -398,7 +424,7 @@ __global__ __launch_bounds__(BLOCK) void k_flat(FlatArgs a) {
                     const uint32_t re1 = r1 + (uint32_t) __popc(nib & ((2u << e) - 1u));
                     ps = fetch_ps(re1 - 1);
                 }
-                element_op<MODE>(vs[e], ga[e], ps, a.add, vo[e], gc[e], hc[e]);
+                element_op<MODE>(vs[e], ga[e], gx[e], ps, a.add, vo[e], gc[e], hc[e]);
                 if (partial && e0 + e >= a.nnz) { gc[e] = 0.f; hc[e] = 0.f; }
             }
             if constexpr (TR::kDot) {
@@ -597,7 +623,7 @@ __global__ __launch_bounds__(kSegBlock) void k_seg_owner(SegOwnerArgs a) {
                     const bool live = pos >= lo && pos < hi;
                     all_live &= live;
                     float vo, gc, hc;
-                    element_op<MODE>(v4[u][e], ga[u][e], ps, 0, vo, gc, hc);
+                    element_op<MODE>(v4[u][e], ga[u][e], 0.f, ps, 0, vo, gc, hc);
                     o[e] = vo;
                     g += live ? gc : 0.f; h += live ? hc : 0.f;
                 }
@@ -765,6 +791,7 @@ struct FinKernelArgs {
     bool pack4_as3;
     bool nmf;
     double* fundec_seg;
+    float4* quad;
 };
 
 template <int PL>
@@ -836,7 +863,9 @@ __global__ __launch_bounds__(kBlock) void k_finalize(FinKernelArgs a) {
             }
         }
         // k = 1: the "next" rank is this one, so its old value is the x just written (out_vec aliases next_vec)
-        a.pack2[c] = make_float2(x, a.next_vec == a.out_vec ? x : next);
+        const float next_old = a.next_vec == a.out_vec ? x : next;
+        if (a.quad) a.quad[c] = make_float4(old.x, old.y, x, next_old);  // the next rank's catch-up pass (FM_FCSC2 / FM_FCSR2)
+        a.pack2[c] = make_float2(x, next_old);
     }
 }
 
@@ -1136,7 +1165,8 @@ template <int MODE>
 int launch_flat_mode(const SegStreamDev& s, const FlatArgs& a, hipStream_t st) {
     if (!s.lds_panels)
         return launch_flat_t<MODE, false, kBlock, false>(a, (s.nspans + (kBlock / 64) - 1) / (kBlock / 64), 0, st);
-    size_t lds_bytes = (((size_t) s.panel_rows + 1) * sizeof(typename ModeTraits<MODE>::S) + 15) / 16 * 16;
+    const size_t entry = sizeof(typename ModeTraits<MODE>::S) + (ModeTraits<MODE>::kAux ? sizeof(float) : 0);
+    size_t lds_bytes = (((size_t) s.panel_rows + 1) * entry + 15) / 16 * 16;
     if (ModeTraits<MODE>::kPerSeg) lds_bytes += (size_t) kPerSegLdsCap * sizeof(typename ModeTraits<MODE>::P);
     const uint32_t grid = s.nspans / s.spans_per_wg;
     switch (s.spans_per_wg) {
@@ -1179,7 +1209,7 @@ int launch_flat_fused_mode(const SegStreamDev& s, const FlatArgs& a, hipStream_t
 int launch_flat_fused(FlatMode mode, const SegStreamDev& s, const void* gather, const void* perseg, const FinalizeArgs& f, hipStream_t st) {
     MFX_REQUIRE(((s.lds_panels && s.spans_per_wg == 16) || !s.panel_rows) && s.fz_order && s.fz_g0 && s.fz_g1 && s.fz_expected && s.fz_arrived,
                 "launch_flat_fused: the layout carries no fused-finalize tables");
-    MFX_REQUIRE(!f.gh_dense && !f.cnt_override && !f.pack4_as3 && !f.nmf && !f.fundec_seg, "launch_flat_fused: dense / overridden / extended finalize inputs are not fused");
+    MFX_REQUIRE(!f.gh_dense && !f.cnt_override && !f.pack4_as3 && !f.nmf && !f.fundec_seg && !f.quad, "launch_flat_fused: dense / overridden / extended finalize inputs are not fused");
     MFX_REQUIRE(mode == FM_FCSC || mode == FM_FCSR || mode == FM_SWEEP, "launch_flat_fused: bad mode %d", (int) mode);
     FlatArgs a = flat_args_of(s, gather, perseg, 0);
     a.wg_order = s.fz_order; a.wg_g0 = s.fz_g0; a.wg_g1 = s.fz_g1; a.expected = s.fz_expected; a.arrived = s.fz_arrived;
@@ -1193,14 +1223,37 @@ int launch_flat_fused(FlatMode mode, const SegStreamDev& s, const void* gather, 
     return mode == FM_FCSC ? launch_flat_fused_mode<FM_FCSC>(s, a, st) : launch_flat_fused_mode<FM_FCSR>(s, a, st);
 }
 
+// The deferred-write modes exist for LDS panels only (launch_flat_mode<...> instantiates them with the LDS slice)
+template <int MODE>
+int launch_flat_lds_only(const SegStreamDev& s, const FlatArgs& a, hipStream_t st) {
+    MFX_REQUIRE(s.lds_panels && !s.scatter, "launch_flat: mode %d needs the LDS-panel layout", MODE);
+    const size_t entry = sizeof(typename ModeTraits<MODE>::S) + (ModeTraits<MODE>::kAux ? sizeof(float) : 0);
+    size_t lds_bytes = (((size_t) s.panel_rows + 1) * entry + 15) / 16 * 16 + (size_t) kPerSegLdsCap * sizeof(typename ModeTraits<MODE>::P);
+    MFX_REQUIRE(lds_bytes <= 160 * 1024, "launch_flat: mode %d needs %zu bytes of LDS at %u panel rows", MODE, lds_bytes, s.panel_rows);
+    const uint32_t grid = s.nspans / s.spans_per_wg;
+    switch (s.spans_per_wg) {
+        case 4: return launch_flat_lds<MODE, 256>(s, a, grid, lds_bytes, st);
+        case 8: return launch_flat_lds<MODE, 512>(s, a, grid, lds_bytes, st);
+        case 16: return launch_flat_lds<MODE, 1024>(s, a, grid, lds_bytes, st);
+        default: return fail(MFX_ERR_INVALID, "panel layout: spans_per_wg must be 4, 8 or 16 (got %u)", s.spans_per_wg);
+    }
+}
+
 int launch_flat(FlatMode mode, const SegStreamDev& s, const void* gather, const void* perseg, int add,
-                hipStream_t st) {
-    const FlatArgs a = flat_args_of(s, gather, perseg, add);
+                hipStream_t st, const float* gather_aux) {
+    FlatArgs a = flat_args_of(s, gather, perseg, add);
+    a.gather_aux = gather_aux;
     switch (mode) {
         case FM_SWEEP: return launch_flat_mode<FM_SWEEP>(s, a, st);
         case FM_RESID: return launch_flat_mode<FM_RESID>(s, a, st);
         case FM_FCSC: return launch_flat_mode<FM_FCSC>(s, a, st);
         case FM_FCSR: return launch_flat_mode<FM_FCSR>(s, a, st);
+        case FM_FCSC_RO: return launch_flat_lds_only<FM_FCSC_RO>(s, a, st);
+        case FM_FCSR_RO: return launch_flat_lds_only<FM_FCSR_RO>(s, a, st);
+        case FM_FCSC2: return launch_flat_lds_only<FM_FCSC2>(s, a, st);
+        case FM_FCSR2:
+            MFX_REQUIRE(gather_aux, "launch_flat: FM_FCSR2 needs its fifth operand");
+            return launch_flat_lds_only<FM_FCSR2>(s, a, st);
         default: return fail(MFX_ERR_INVALID, "launch_flat: bad mode %d", (int) mode);
     }
 }
@@ -1283,7 +1336,7 @@ int launch_finalize(const SegStreamDev& s, const FinalizeArgs& f, hipStream_t st
         a.slab_acc = f.slab_src->wgacc; a.slab_lo = f.slab_src->slab_lo; a.slab_bad = f.slab_src->scat_slab_bad; a.slab_pr = f.slab_src->panel_rows;
     }
     MFX_REQUIRE(!f.gh_len || ((f.gh_dense || f.slab_src) && (uint64_t) f.seg_base + f.gh_len <= s.nseg), "launch_finalize: bad segment range %u + %u of %u", f.seg_base, f.gh_len, s.nseg);
-    a.lambda = f.lambda; a.out_vec = f.out_vec; a.pack2 = f.pack2; a.next_vec = f.next_vec; a.pack4 = f.pack4; a.pack4_as3 = f.pack4_as3; a.nmf = f.nmf; a.fundec_seg = f.fundec_seg;
+    a.lambda = f.lambda; a.out_vec = f.out_vec; a.pack2 = f.pack2; a.next_vec = f.next_vec; a.pack4 = f.pack4; a.quad = f.quad; a.pack4_as3 = f.pack4_as3; a.nmf = f.nmf; a.fundec_seg = f.fundec_seg;
     const bool dense = f.gh_dense || f.slab_src;
     const int pl = dense ? 1 : panel_lanes(s);
     const uint32_t nfin = dense ? a.gh_len : s.nseg;
@@ -1356,7 +1409,7 @@ int launch_test_r1(int64_t nnz_test, const uint32_t* row, const uint32_t* col, f
 
 int launch_seg_owner(FlatMode mode, const SegStreamDev& s, const void* gather, const void* perseg, const FinalizeArgs& f, hipStream_t st) {
     MFX_REQUIRE(s.panel_rows == 0 && !s.scatter && s.ptr && s.idx && s.own_short && s.own_long, "launch_seg_owner: needs the plain layout with its owner lists");
-    MFX_REQUIRE(!f.gh_dense && !f.cnt_override && !f.pack4_as3 && !f.nmf && !f.fundec_seg, "launch_seg_owner: dense / overridden / extended finalize inputs are not supported");
+    MFX_REQUIRE(!f.gh_dense && !f.cnt_override && !f.pack4_as3 && !f.nmf && !f.fundec_seg && !f.quad, "launch_seg_owner: dense / overridden / extended finalize inputs are not supported");
     MFX_REQUIRE(mode == FM_SWEEP || ((mode == FM_FCSC || mode == FM_FCSR) && f.pack2 && f.next_vec && f.pack2 == perseg), "launch_seg_owner: bad mode / packs");
     if (s.nseg == 0) return MFX_OK;
     SegOwnerArgs a;

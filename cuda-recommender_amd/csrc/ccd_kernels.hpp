@@ -87,11 +87,21 @@ enum FlatMode : int {
                    //   val = (val - A.x*B.x) + A.y*B.y ; g += A.y*val ; h += A.y^2
     FM_FCSR = 3,   // float4 C = gather[idx], float2 D = perseg[seg]:
                    //   val = (val - C.x*D.x) + C.y*D.y ; g += C.z*val ; h += C.z^2
+    // Deferred residual writes (LDS panels only; CcdSolver::rank_pair): rank t streams its copy without
+    // storing it, rank t + 1 redoes rank t's update in registers (same operands, same order: same bits)
+    // before its own, and stores.
+    FM_FCSC_RO = 4,  // FM_FCSC, val not written
+    FM_FCSR_RO = 5,  // FM_FCSR, val not written
+    FM_FCSC2 = 6,  // float4 A = gather[idx], float4 B = perseg[seg]:
+                   //   r = (val - A.x*B.x) + A.y*B.y ; val = (r - A.z*B.z) + A.w*B.w ; g += A.w*val ; h += A.w^2
+    FM_FCSR2 = 7,  // float4 C = gather[idx], float c5 = gather_aux[idx], float4 D = perseg[seg]:
+                   //   r = (val - C.x*D.x) + C.y*D.y ; val = (r - C.z*D.z) + C.w*D.w ; g += c5*val ; h += c5^2
 };
 
-// Flat-stream pass over `s`.  gather/perseg element types depend on `mode` (see FlatMode).
+// Flat-stream pass over `s`.  gather/perseg element types depend on `mode` (see FlatMode);
+// gather_aux: FM_FCSR2's fifth gathered operand.
 int launch_flat(FlatMode mode, const SegStreamDev& s, const void* gather, const void* perseg,
-                int add, hipStream_t st);
+                int add, hipStream_t st, const float* gather_aux = nullptr);
 
 // Scatter passes (ccd_scatter.hip).  `s` is the store of the orientation being STREAMED; results are per
 // index of its gathered ("local") dimension.  slice_src: operands of the local dimension; global_op:
@@ -143,6 +153,7 @@ struct FinalizeArgs {
     float2* pack2 = nullptr;            // in: (prev_new, cur_old); out: (cur_new, next_old)
     const float* next_vec = nullptr;    // W[t+1] / H[t+1] slice (old values)
     float4* pack4 = nullptr;            // out: (prev_new, cur_old, cur_new, 0), may be nullptr
+    float4* quad = nullptr;             // out: (prev_new, cur_old, cur_new, next_old), may be nullptr (k_finalize only)
     // Opt-in extensions (mfx_params.do_nmf / eps; the reference parses these flags and ignores them):
     bool nmf = false;                   // clamp the new value at 0
     double* fundec_seg = nullptr;       // [nseg] scratch: per-segment function decrease h (old - new)^2 (clamped: -2 g old + h old^2)

@@ -812,6 +812,17 @@ int CcdSolver::init(const mfx_csx* R, const mfx_coo* T, const mfx_params* p, mfx
         MFX_TRY(r1_sum_.alloc_zero(1, st_));
         for (hipEvent_t& e : ev_rank_) MFX_HIP(hipEventCreate(&e));
     }
+    {   // deferred residual writes (rank_pair): the plain fused schedule on LDS panels, one inner iteration, nothing opt-in.
+        // MFX_DEFER_RESID=0 keeps one stored pass per copy and rank (A/B).
+        const char* e = std::getenv("MFX_DEFER_RESID");
+        auto fits = [](const SegStreamDev& v, size_t entry) {  // the catch-up pass's slice + float4 operand window in one CU's LDS
+            return ((size_t) v.panel_rows + 1) * entry + 15 + 1024 * sizeof(float4) <= 160 * 1024;
+        };
+        defer_resid_ = !(e && std::atoi(e) == 0) && p->schedule == 1 && p->maxinneriter == 1 && p->kernel_variant == 1 && !scatter_ &&
+                       !owner_mode_ && !ref_order_ && !comm_ && fuse_finalize_ == 0 && !ext_on_ && csc_.view.lds_panels && csr_.view.lds_panels &&
+                       fits(csc_.view, sizeof(float4)) && fits(csr_.view, sizeof(float4) + sizeof(float)) && k_ >= 2;
+        if (defer_resid_) MFX_TRY(packD_.alloc_zero(m_, st_));
+    }
     MFX_TRY(rmse_sum_.alloc_zero(1, st_));
     MFX_HIP(hipStreamSynchronize(st_));
     return MFX_OK;
@@ -1187,6 +1198,40 @@ int CcdSolver::rank_fused(uint32_t t) {
     return MFX_OK;
 }
 
+// Ranks t and t + 1 with ONE stored pass per copy (defer_resid_).  A fused pass applies one elementwise update to its copy
+// and stores it; the stored value is only a cache of that fixed sequence of roundings.  So rank t streams both copies
+// read-only (FM_FCSC_RO / FM_FCSR_RO: today's sums, 6.25 instead of 10.25 bytes per rating), and rank t + 1's passes
+// (FM_FCSC2 / FM_FCSR2) start from the older stored value, redo rank t's update in registers with the same operands in the
+// same order -- the same bits -- then apply their own and store.  Every sum runs over the same stored order with the same
+// operands, so W, H and the stored residual are bit-identical to two calls of rank_fused.  The operands rank t + 1 needs
+// that rank t's packs no longer hold come from rank t's finalizes: quads (x_{t-1}, x_t old, x_t, x_{t+1} old) of both
+// sides (packC for the columns, packD_ for the rows); the CSR catch-up's fifth operand v_{t+1} is H[t + 1] itself.
+int CcdSolver::rank_pair(uint32_t t) {
+    const uint32_t t1 = t + 1, next1 = (t1 + 1) % k_;
+    // invariant on entry, as in rank_fused: packA = (u_prev_new | 0, W[t] old), packB = (v_prev_new | 0, H[t] old)
+    // ---- rank t: read-only passes; the finalizes also leave the quads (packC: columns, packD_: rows) ----
+    FinalizeArgs fv = fin_base();
+    fv.out_vec = Ht(t); fv.pack2 = packB_.get(); fv.next_vec = Ht(t1); fv.quad = packC_.get();  // (its first three = the pack4 of rank_fused)
+    PROF(KernelProfiler::K_SWEEP, launch_flat(FM_FCSC_RO, csc_.view, packA_.get(), packB_.get(), 0, st_));
+    PROF(KernelProfiler::K_FINALIZE, launch_finalize(csc_.view, fv, st_));
+    FinalizeArgs fu = fin_base();
+    fu.out_vec = Wt(t); fu.pack2 = packA_.get(); fu.next_vec = Wt(t1); fu.quad = packD_.get();
+    PROF(KernelProfiler::K_SWEEP, launch_flat(FM_FCSR_RO, csr_.view, packC_.get(), packA_.get(), 0, st_));
+    PROF(KernelProfiler::K_FINALIZE, launch_finalize(csr_.view, fu, st_));
+    // ---- rank t + 1: catch-up passes (rank t's update, then its own), stored ----
+    // packA = (u_t, W[t+1] old), packB = (v_t, H[t+1] old); packC / packD_ = the quads of rank t
+    FinalizeArgs fv1 = fin_base();
+    fv1.out_vec = Ht(t1); fv1.pack2 = packB_.get(); fv1.next_vec = Ht(next1);  // (no pack4: packC stays the column quads)
+    PROF(KernelProfiler::K_FCSC, launch_flat(FM_FCSC2, csc_.view, packD_.get(), packC_.get(), 0, st_));
+    PROF(KernelProfiler::K_FINALIZE, launch_finalize(csc_.view, fv1, st_));
+    FinalizeArgs fu1 = fin_base();
+    fu1.out_vec = Wt(t1); fu1.pack2 = packA_.get(); fu1.next_vec = Wt(next1);
+    PROF(KernelProfiler::K_FCSR, launch_flat(FM_FCSR2, csr_.view, packC_.get(), packD_.get(), 0, st_, Ht(t1)));
+    PROF(KernelProfiler::K_FINALIZE, launch_finalize(csr_.view, fu1, st_));
+    pending_sub_ = (int32_t) t1;
+    return MFX_OK;
+}
+
 int CcdSolver::flush_pending() {
     if (pending_sub_ < 0) return MFX_OK;
     const uint32_t t = (uint32_t) pending_sub_, next = (t + 1) % k_;
@@ -1335,6 +1380,12 @@ int CcdSolver::enqueue_outer_iteration(int64_t oiter) {
     early_stop_ = 0;
     uint32_t done = 0;
     for (uint32_t t = 0; t < k_ && rc == MFX_OK; ++t) {
+        if (defer_resid_ && t + 1 < k_) {  // (with odd k the last rank is an ordinary fused one)
+            rc = rank_pair(t);
+            ++t;
+            done += 2;
+            continue;
+        }
         if (p_.eps > 0.f && early_stop_ >= 5) break;  // LIBPMF: five ranks stopped in their first inner iteration
         if (p_.rank_trace) rc = trace_begin(t);
         if (rc == MFX_OK) rc = p_.schedule == 0 ? rank_as_written(t, oiter > 1) : rank_fused(t);

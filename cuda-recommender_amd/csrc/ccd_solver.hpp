@@ -135,6 +135,10 @@ private:
     int fuse_finalize_ = 0;
     bool use_fused(const SegStreamStore& s) const { return fuse_finalize_ == 1 && !ext_on_ && s.can_fuse_finalize(); }
     int rank_fused(uint32_t t);
+    // ranks t, t + 1 with one stored pass per copy (read-only passes, then catch-up passes); MFX_DEFER_RESID=0 turns it off
+    bool defer_resid_ = false;
+    DevBuf<float4> packD_;             // [m] row quads (u_{t-1}, u_t old, u_t, u_{t+1} old) of the pair's first rank
+    int rank_pair(uint32_t t);
     int rank_fused_owner(uint32_t t);  // (r4) small matrices: k_seg_owner, two launches per rank
     bool owner_mode_ = false;
     int rank_as_written(uint32_t t, bool add_back);

@@ -78,13 +78,16 @@ def mean_counter(path, kern, ctr):
         return None
     s = n = 0
     for r in csv.DictReader(open(f)):
-        if kern in r["Kernel_Name"] and r["Counter_Name"] == ctr:
+        if any(x in r["Kernel_Name"] for x in kern) and r["Counter_Name"] == ctr:
             s += float(r["Counter_Value"]); n += 1
     return s / n if n else None
 
 
-# bench kernel name -> substring of the device kernel's name
-KERNELS = {"ccd_fused_csc_pass": "k_flat<2", "ccd_fused_csr_pass": "k_flat<3", "ccd_scatter_v_pass": "k_scatter<0", "ccd_scatter_u_pass": "k_scatter<1"}
+# bench kernel name -> substrings of the device kernels booked under it.  Deferred residual writes (CcdSolver::rank_pair):
+# the catch-up passes k_flat<6 / <7 are booked as the fused passes, the read-only passes k_flat<4 / <5 as ccd_flat_sweep.
+KERNELS = {"ccd_fused_csc_pass": ("k_flat<2", "k_flat<6"), "ccd_fused_csr_pass": ("k_flat<3", "k_flat<7"),
+           "ccd_flat_sweep": ("k_flat<0", "k_flat<4", "k_flat<5"),
+           "ccd_scatter_v_pass": ("k_scatter<0",), "ccd_scatter_u_pass": ("k_scatter<1",)}
 traffic = {}
 tpath = os.path.join(dst, "traffic.json")
 if os.path.exists(tpath):
