@@ -31,8 +31,16 @@
 #ifndef MFX_ALS_IMPLICIT
 #define MFX_ALS_IMPLICIT 0
 #endif
+// MFX_ALS_NREG = 1 (als_nreg.hip): the explicit kernels with fp32(lambda * n) on the diagonal of a segment of n entries
+// (the k_alsn_* instantiations: the row minimiser of the CCD++ objective); a translation unit of their own for the same
+// reason.
+#ifndef MFX_ALS_NREG
+#define MFX_ALS_NREG 0
+#endif
 #if MFX_ALS_IMPLICIT
 #define ALS_KERNEL(name) k_ials_##name
+#elif MFX_ALS_NREG
+#define ALS_KERNEL(name) k_alsn_##name
 #else
 #define ALS_KERNEL(name) k_als_##name
 #endif
@@ -93,6 +101,9 @@ struct AlsArgs {
     // implicit-feedback kernels (k_ials_*) only; appended so that the fields above keep their kernel-argument offsets
     float alpha;       // confidence weight of a gathered entry: w = fp32(alpha * r)
     const float* G;    // [k][k] base Gramian X^T X + lambda I (ials_base_gramian), the start of every unsplit / reduced system
+#if MFX_ALS_NREG
+    const uint32_t* seg_ptr;  // (k_alsn_* only) segment pointers [nseg + 1]: segment s has seg_ptr[s + 1] - seg_ptr[s] entries
+#endif
 };
 constexpr uint32_t kPhaseCopies = 1024;
 __device__ __forceinline__ void phase_mark(const AlsArgs& a, int slot, unsigned long long& t) {
@@ -389,7 +400,11 @@ __device__ void factor_solve(float* lds, const AlsArgs& a, uint32_t seg, unsigne
         }
         return;
     }
-    for (int i = (int) lane; i < KP; i += 64) L[roff(i) + i] = i < k ? add_rn(L[roff(i) + i], a.lambda) : 1.0f;  // rows k.. : identity
+    float lam = a.lambda;  // k_alsn_*: fp32(lambda * n) for a segment of n entries, one rounding; from here on the plain path
+#if MFX_ALS_NREG
+    lam = mul_rn(a.lambda, (float) (a.seg_ptr[seg + 1] - a.seg_ptr[seg]));
+#endif
+    for (int i = (int) lane; i < KP; i += 64) L[roff(i) + i] = i < k ? add_rn(L[roff(i) + i], lam) : 1.0f;  // rows k.. : identity
     __syncthreads();
 
     // Left-looking Cholesky on the lower triangle, row i at a time (the reference's choldc1 loop,
@@ -1190,8 +1205,7 @@ int launch_half(const AlsArgs& a, uint32_t nitems, uint32_t nreduces, uint64_t n
     }
 }
 
-constexpr uint32_t kAlsChunk = 2048;  // gathered rows per wavefront before a segment is split
-constexpr uint32_t kAlsPad = 128;     // entries behind the index / value arrays (see AlsHalf::build)
+constexpr uint32_t kAlsPad = 128;    // entries behind the index / value arrays (see AlsHalf::build)
 // k_als_gram16 at pipeline depth D loads the indices of step s + D while it works on step s: at most 16 (D + 1) + 15
 // entries past an item's end
 static_assert(kAlsPad >= 16 * ((MFX_G16_DL > MFX_G16_DS ? MFX_G16_DL : MFX_G16_DS) + 2), "index / value padding too short for the pipeline depth");
@@ -1206,6 +1220,15 @@ int ials_half_launch(const AlsHalf& h, const float* X, uint32_t x_rows, float* Y
     a.X = X; a.x_rows = x_rows; a.sentinel = (uint32_t) h.nnz; a.Y = Y; a.k = k; a.ws = ws; a.spd_fail = spd_fail;
     a.lambda = 0.f;  // lambda is on G's diagonal already
     a.alpha = alpha; a.G = G;
+    return launch_half(a, h.nitems, h.nreduces, h.nnz, st);
+}
+#elif MFX_ALS_NREG
+int als_half_nreg_launch(const AlsHalf& h, const float* X, uint32_t x_rows, float* Y, uint32_t k, float lambda, float* ws,
+                         uint32_t* spd_fail, hipStream_t st) {
+    AlsArgs a{};
+    a.items = h.items.get(); a.reduces = h.reduces.get(); a.idx = h.idx.get(); a.val = h.val.get();
+    a.X = X; a.x_rows = x_rows; a.sentinel = (uint32_t) h.nnz; a.Y = Y; a.k = k; a.lambda = lambda; a.ws = ws; a.spd_fail = spd_fail;
+    a.seg_ptr = h.ptr.get();
     return launch_half(a, h.nitems, h.nreduces, h.nnz, st);
 }
 #else

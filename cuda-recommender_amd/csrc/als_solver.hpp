@@ -21,6 +21,8 @@ struct AlsReduce {    // a segment whose Gramian was split over `nslots` consecu
     uint32_t seg, slot0, nslots;
 };
 
+constexpr uint32_t kAlsChunk = 2048;  // gathered rows per wavefront before a segment is split (AlsHalf::build's `chunk`)
+
 // One orientation (rows over H, or columns over W).
 struct AlsHalf {
     uint32_t nseg = 0;
@@ -90,6 +92,10 @@ private:
 // whose last row must be all zeros.
 int als_half_launch(const AlsHalf& h, const float* X, uint32_t x_rows, float* Y, uint32_t k, float lambda, float* ws,
                     uint32_t* spd_fail, hipStream_t st, unsigned long long* phases = nullptr);
+// The same with fp32(lambda * n) on the diagonal of a segment of n entries (k_alsn_*, als_nreg.hip): the exact minimiser of the
+// CCD++ objective over one segment, X fixed
+int als_half_nreg_launch(const AlsHalf& h, const float* X, uint32_t x_rows, float* Y, uint32_t k, float lambda, float* ws,
+                         uint32_t* spd_fail, hipStream_t st);
 // Implicit half-sweep (k_ials_*): G = the base Gramian X^T X + lambda I of all x_rows rows (ials_base_gramian)
 int ials_half_launch(const AlsHalf& h, const float* X, uint32_t x_rows, float* Y, uint32_t k, const float* G, float alpha,
                      float* ws, uint32_t* spd_fail, hipStream_t st);

@@ -465,6 +465,26 @@ int mfx_rec_query(mfx_rec_t r, int64_t nusers, const uint32_t* users, int32_t n_
         return r->impl->query(nusers, users, n_top, items, scores, space, item_slices);
     });
 }
+int mfx_rec_fold_in_setup(mfx_rec_t r, int model, float lambda, float alpha) {
+    return guarded("mfx_rec_fold_in_setup", [&]() -> int {
+        MFX_REQUIRE(r && r->impl, "null recommender");
+        return r->impl->fold_in_setup(model, lambda, alpha);
+    });
+}
+int mfx_rec_fold_in(mfx_rec_t r, int64_t nusers, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val,
+                    float* W_out, int32_t n_top, uint32_t* items, float* scores, mfx_memspace space) {
+    return guarded("mfx_rec_fold_in", [&]() -> int {
+        MFX_REQUIRE(r && r->impl, "null recommender");
+        return r->impl->fold_in(nusers, nnz, ptr, idx, val, W_out, n_top, items, scores, space);
+    });
+}
+int mfx_rec_fold_in_times(mfx_rec_t r, double seconds[3]) {
+    return guarded("mfx_rec_fold_in_times", [&]() -> int {
+        MFX_REQUIRE(r && r->impl && seconds, "null recommender or seconds");
+        r->impl->fold_in_times(seconds);
+        return MFX_OK;
+    });
+}
 int mfx_rec_destroy(mfx_rec_t r) {
     return guarded("mfx_rec_destroy", [&]() -> int {
         if (!r) return MFX_OK;

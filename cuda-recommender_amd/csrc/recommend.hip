@@ -22,11 +22,17 @@
 // Small batches split the items over `slices` (grid.y); each slice leaves its sorted top N in the workspace and
 // mfx_rec_merge selects the final N from slices * N entries.  The scores are the same numbers, so the result is
 // bitwise the one of the unsplit pass.
+//
+// Fold-in (mfx_rec_fold_in) solves the query rows with the ALS half-sweep launchers against H unpacked from the tiles
+// (the same bits the scores use), packs the solved rows like W and runs the same top-N pass with the query's own rows
+// as the exclusion.
 #include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <memory>
 #include <unordered_map>
 
+#include "als_solver.hpp"   // AlsHalf and the half-sweep launchers (fold-in)
 #include "ccd_kernels.hpp"  // check_index_range
 #include "recommend.hpp"
 
@@ -339,6 +345,19 @@ __global__ void mfx_rec_pack_w(const float* W, int layout, uint32_t rows, int k,
     }
 }
 
+// hx[item][t] = H[item][t] read back from the tiles of mfx_rec_pack_h (t < k only: the padding never leaks in), row
+// `cols` all zeros: the gather target of the half-sweep kernels past a segment's end.
+__global__ void mfx_rec_unpack_h(const float* hp, uint32_t cols, int k, int kc2, int nch, float* hx) {
+    const size_t total = ((size_t) cols + 1) * k;
+    for (size_t x = (size_t) blockIdx.x * blockDim.x + threadIdx.x; x < total; x += (size_t) gridDim.x * blockDim.x) {
+        const size_t item = x / k;
+        const int t = x % k;
+        float v = 0.f;
+        if (item < cols) v = hp[(((item / kTile) * nch + t / kc2) * kc2 + t % kc2) * kTile + item % kTile];
+        hx[x] = v;
+    }
+}
+
 // bad |= 1: row pointers not a valid prefix sum of nnz; 2: column index >= cols; 4: a row not non-decreasing.
 __global__ void mfx_rec_check_exclude(const uint32_t* rp, const uint32_t* ci, uint32_t rows, uint32_t cols,
                                       uint64_t nnz, int* bad) {
@@ -472,11 +491,23 @@ int Recommender::query(int64_t nusers, const uint32_t* users, int32_t n_top, uin
     if (nusers == 0) return MFX_OK;
     MFX_REQUIRE(items, "mfx_rec_query: items is NULL");
     MFX_TRY(use_device(device_));
-    hipStream_t st = st_;
+    const uint32_t nu = (uint32_t) nusers;
+    DevBuf<uint32_t> d_users;
+    const uint32_t* du = users;
+    if (users && space == MFX_HOST) {
+        MFX_TRY(d_users.alloc(nu));
+        MFX_TRY(d_users.upload(users, nu, MFX_HOST, st_));
+        du = d_users.get();
+    }
+    if (users) MFX_TRY(check_index_range(du, nu, (uint32_t) rows_, "mfx_rec_query: user id", st_));
+    return topn(wp_.get(), nu, du, has_ex_ ? ex_ptr_.get() : nullptr, ex_idx_.get(), n_top, items, scores, space, item_slices);
+}
 
+int Recommender::topn(const float* wp, uint32_t nu, const uint32_t* du, const uint32_t* ex_ptr, const uint32_t* ex_idx,
+                      int32_t n_top, uint32_t* items, float* scores, mfx_memspace space, int item_slices) {
+    hipStream_t st = st_;
     int L = 64;
     while (L < n_top + 32) L <<= 1;
-    const uint32_t nu = (uint32_t) nusers;
 
     // slices: forced, or enough workgroups for about two per CU
     int slices = item_slices;
@@ -498,16 +529,9 @@ int Recommender::query(int64_t nusers, const uint32_t* users, int32_t n_top, uin
     const int bps = (nblk_ + slices - 1) / slices;
     const uint32_t qc = per_launch(slices);
 
-    DevBuf<uint32_t> d_users, d_items;
+    DevBuf<uint32_t> d_items;
     DevBuf<float> d_scores, ls;
     DevBuf<uint32_t> li;
-    const uint32_t* du = users;
-    if (users && space == MFX_HOST) {
-        MFX_TRY(d_users.alloc(nu));
-        MFX_TRY(d_users.upload(users, nu, MFX_HOST, st));
-        du = d_users.get();
-    }
-    if (users) MFX_TRY(check_index_range(du, nu, (uint32_t) rows_, "mfx_rec_query: user id", st));
     uint32_t* oi = items;
     float* os = scores;
     if (space == MFX_HOST) {
@@ -522,11 +546,11 @@ int Recommender::query(int64_t nusers, const uint32_t* users, int32_t n_top, uin
     MFX_TRY(li.alloc((size_t) slices * qc * L));
 
     RecArgs a{};
-    a.wp = wp_.get();
+    a.wp = wp;
     a.hp = hp_.get();
     a.users = du;
-    a.ex_ptr = has_ex_ ? ex_ptr_.get() : nullptr;
-    a.ex_idx = ex_idx_.get();
+    a.ex_ptr = ex_ptr;
+    a.ex_idx = ex_idx;
     a.cols = (uint32_t) cols_;
     a.kt = kt_; a.nch = nch_; a.nblk = nblk_; a.bps = bps; a.n_top = n_top; a.L = L;
     a.ls = ls.get(); a.li = li.get();
@@ -556,6 +580,108 @@ int Recommender::query(int64_t nusers, const uint32_t* users, int32_t n_top, uin
         if (scores) MFX_HIP(hipMemcpyAsync(scores, os, sizeof(float) * nu * n_top, hipMemcpyDeviceToHost, st));
     }
     MFX_HIP(hipStreamSynchronize(st));
+    return MFX_OK;
+}
+
+int Recommender::fold_in_setup(int model, float lambda, float alpha) {
+    MFX_REQUIRE(model == MFX_FOLD_ALS || model == MFX_FOLD_ALS_EXACT || model == MFX_FOLD_CCD || model == MFX_FOLD_IMPLICIT,
+                "mfx_rec_fold_in_setup: unknown model %d", model);
+    MFX_REQUIRE(k_ <= 128, "mfx_rec_fold_in_setup: fold-in solves ranks k <= 128 (the handle has k = %lld)", (long long) k_);
+    MFX_REQUIRE(std::isfinite(lambda) && lambda > 0.f, "mfx_rec_fold_in_setup: lambda = %g (finite and > 0 required)", (double) lambda);
+    MFX_REQUIRE(std::isfinite(alpha) && alpha >= 0.f, "mfx_rec_fold_in_setup: alpha = %g (finite and >= 0 required)", (double) alpha);
+    MFX_TRY(use_device(device_));
+    hipStream_t st = st_;
+    fold_model_ = -1;  // (until this setup is through)
+    const size_t nh = ((size_t) cols_ + 1) * k_;
+    if (!hx_.get()) MFX_TRY(hx_.alloc(nh));
+    hipLaunchKernelGGL(mfx_rec_unpack_h, dim3(grid_for(nh)), dim3(256), 0, st, hp_.get(), (uint32_t) cols_, (int) k_, 2 * kc_,
+                       nch_, hx_.get());
+    MFX_LAUNCH_CHECK();
+    DevBuf<float> part;
+    if (model == MFX_FOLD_IMPLICIT) {  // the base Gramian of the implicit system, as the trainer's ials_base_gramian builds it
+        MFX_TRY(part.alloc(ials_base_ws_floats((uint32_t) cols_, (uint32_t) k_)));
+        MFX_TRY(fold_g_.alloc((size_t) k_ * k_));
+        MFX_TRY(ials_base_gramian(hx_.get(), (uint32_t) cols_, (uint32_t) k_, lambda, part.get(), fold_g_.get(), st));
+    }
+    MFX_HIP(hipStreamSynchronize(st));
+    fold_model_ = model;
+    fold_lambda_ = lambda;
+    fold_alpha_ = alpha;
+    return MFX_OK;
+}
+
+int Recommender::fold_in(int64_t nusers, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val, float* W_out,
+                         int32_t n_top, uint32_t* items, float* scores, mfx_memspace space) {
+    MFX_REQUIRE(fold_model_ >= 0, "mfx_rec_fold_in: call mfx_rec_fold_in_setup first");
+    MFX_REQUIRE(nusers >= 0 && nusers < (int64_t) 0xFFFFFFFFll, "mfx_rec_fold_in: bad nusers %lld", (long long) nusers);
+    MFX_REQUIRE(nnz >= 0 && nnz < (int64_t) 0xFFFF0000ll, "mfx_rec_fold_in: bad nnz %lld", (long long) nnz);
+    MFX_REQUIRE(n_top >= 0 && n_top <= kMaxTop, "mfx_rec_fold_in: n_top must be in [0, %d] (got %d)", kMaxTop, n_top);
+    MFX_REQUIRE(space == MFX_HOST || space == MFX_DEVICE, "mfx_rec_fold_in: bad memory space");
+    fold_s_[0] = fold_s_[1] = fold_s_[2] = 0.0;
+    if (nusers == 0) return MFX_OK;
+    MFX_REQUIRE(ptr && (nnz == 0 || (idx && val)), "mfx_rec_fold_in: null ptr / idx / val");
+    MFX_REQUIRE(n_top == 0 || items, "mfx_rec_fold_in: items is NULL");
+    MFX_TRY(use_device(device_));
+    hipStream_t st = st_;
+    using clk = std::chrono::steady_clock;
+    const auto t0 = clk::now();
+    const uint32_t nu = (uint32_t) nusers, k = (uint32_t) k_;
+    // the query rows as one half-sweep over H, with the chunking of training: build() checks the pointers on the host
+    // and every index < cols on the device; then the exclusion check of mfx_rec_create (ids non-decreasing in a row)
+    AlsHalf h;
+    MFX_TRY(h.build(nu, (uint64_t) nnz, (uint32_t) cols_, ptr, idx, val, space, kAlsChunk, st));
+    DevBuf<int> bad;
+    MFX_TRY(bad.alloc_zero(1, st));
+    hipLaunchKernelGGL(mfx_rec_check_exclude, dim3(grid_for(nu)), dim3(256), 0, st, h.ptr.get(), h.idx.get(), nu,
+                       (uint32_t) cols_, (uint64_t) nnz, bad.get());
+    MFX_LAUNCH_CHECK();
+    int hb = 0;
+    MFX_HIP(hipMemcpyAsync(&hb, bad.get(), sizeof(int), hipMemcpyDeviceToHost, st));
+    MFX_HIP(hipStreamSynchronize(st));
+    MFX_REQUIRE(!(hb & 1), "mfx_rec_fold_in: ptr is not a non-decreasing prefix sum from 0 to nnz");
+    MFX_REQUIRE(!(hb & 2), "mfx_rec_fold_in: column index out of range [0, %lld)", (long long) cols_);
+    MFX_REQUIRE(!(hb & 4), "mfx_rec_fold_in: column indices must be non-decreasing within every row");
+    if (fold_model_ == MFX_FOLD_IMPLICIT) MFX_TRY(ials_check_values(h.val.get(), h.nnz, fold_alpha_, "mfx_rec_fold_in: value", st));
+    const auto t1 = clk::now();
+
+    DevBuf<float> Y, ws, wq;
+    DevBuf<uint32_t> spd_fail;
+    MFX_TRY(Y.alloc_zero((size_t) nu * k, st));
+    MFX_TRY(spd_fail.alloc_zero(1, st));
+    if (fold_model_ != MFX_FOLD_ALS_EXACT) MFX_TRY(ws.alloc(std::max<size_t>(1, als_ws_floats(h.nslots, k))));
+    const uint32_t x_rows = (uint32_t) cols_;
+    switch (fold_model_) {
+        case MFX_FOLD_ALS:
+            MFX_TRY(als_half_launch(h, hx_.get(), x_rows, Y.get(), k, fold_lambda_, ws.get(), spd_fail.get(), st));
+            break;
+        case MFX_FOLD_ALS_EXACT:
+            MFX_TRY(als_half_exact_launch(h, hx_.get(), Y.get(), k, fold_lambda_, spd_fail.get(), st));
+            break;
+        case MFX_FOLD_CCD:
+            MFX_TRY(als_half_nreg_launch(h, hx_.get(), x_rows, Y.get(), k, fold_lambda_, ws.get(), spd_fail.get(), st));
+            break;
+        default:
+            MFX_TRY(ials_half_launch(h, hx_.get(), x_rows, Y.get(), k, fold_g_.get(), fold_alpha_, ws.get(), spd_fail.get(), st));
+            break;
+    }
+    MFX_HIP(hipStreamSynchronize(st));
+    const auto t2 = clk::now();
+
+    if (W_out)
+        MFX_HIP(hipMemcpyAsync(W_out, Y.get(), sizeof(float) * (size_t) nu * k,
+                               space == MFX_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, st));
+    if (n_top > 0) {
+        MFX_TRY(wq.alloc((size_t) nu * kt_));
+        hipLaunchKernelGGL(mfx_rec_pack_w, dim3(grid_for((size_t) nu * kt_)), dim3(256), 0, st, Y.get(), 1, nu, (int) k, kt_,
+                           wq.get());
+        MFX_LAUNCH_CHECK();
+        MFX_TRY(topn(wq.get(), nu, nullptr, h.ptr.get(), h.idx.get(), n_top, items, scores, space, 0));
+    }
+    MFX_HIP(hipStreamSynchronize(st));
+    const auto t3 = clk::now();
+    fold_s_[0] = std::chrono::duration<double>(t1 - t0).count();
+    fold_s_[1] = std::chrono::duration<double>(t2 - t1).count();
+    fold_s_[2] = std::chrono::duration<double>(t3 - t2).count();
     return MFX_OK;
 }
 

@@ -16,9 +16,19 @@ public:
                       int layout, const mfx_csx* exclude, mfx_memspace space, int device);
     int query(int64_t nusers, const uint32_t* users, int32_t n_top, uint32_t* items, float* scores,
               mfx_memspace space, int item_slices);
+    // fold-in (mfx_rec_fold_in_setup / mfx_rec_fold_in): solve query rows against H, then score them
+    int fold_in_setup(int model, float lambda, float alpha);
+    int fold_in(int64_t nusers, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val, float* W_out,
+                int32_t n_top, uint32_t* items, float* scores, mfx_memspace space);
+    void fold_in_times(double out[3]) const { for (int i = 0; i < 3; ++i) out[i] = fold_s_[i]; }
     ~Recommender();
 
 private:
+    // The top-N pass over nu batch slots: slot q scores packed row users[q] (q when users is NULL) of wp [.][kt_] and
+    // excludes the items of row users[q] (q) of ex_ptr / ex_idx (ex_ptr NULL: none).  Device pointers except items /
+    // scores, which live in `space`.
+    int topn(const float* wp, uint32_t nu, const uint32_t* users, const uint32_t* ex_ptr, const uint32_t* ex_idx,
+             int32_t n_top, uint32_t* items, float* scores, mfx_memspace space, int item_slices);
     int device_ = 0;
     hipStream_t st_ = nullptr;
     int64_t rows_ = 0, cols_ = 0, k_ = 0;
@@ -30,6 +40,11 @@ private:
     DevBuf<float> wp_, hp_;
     DevBuf<uint32_t> ex_ptr_, ex_idx_;
     bool has_ex_ = false;
+    // fold-in: model (-1 = not set up), H row-major [cols_ + 1][k_] with a zero last row, base Gramian [k_][k_] (implicit)
+    int fold_model_ = -1;
+    float fold_lambda_ = 0.f, fold_alpha_ = 0.f;
+    DevBuf<float> hx_, fold_g_;
+    double fold_s_[3] = {0, 0, 0};  // host build / solve / score seconds of the last fold-in
 };
 
 int topn_metrics(int64_t nusers, const uint32_t* users, int32_t n_top, const uint32_t* items, const mfx_coo* T,

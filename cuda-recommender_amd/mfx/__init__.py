@@ -7,3 +7,4 @@ from .api import (AlsSolver, CcdSolver, Comm, TestData, UsageError, als_gramian,
 from .api import Recommender, recommend, topn_metrics  # noqa: F401
 from .api import ImplicitAlsSolver, ials_half  # noqa: F401
 from ._lib import LIB_PATH, MfxError, lib  # noqa: F401
+from ._lib import MFX_FOLD_ALS, MFX_FOLD_ALS_EXACT, MFX_FOLD_CCD, MFX_FOLD_IMPLICIT  # noqa: F401

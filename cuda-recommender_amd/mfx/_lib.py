@@ -12,6 +12,7 @@ LIB_PATH = os.environ.get("MFX_LIB_PATH") or os.path.join(_PKG, "libmfx.so")  # 
 MFX_HOST, MFX_DEVICE = 0, 1
 MFX_COMM_ID_BYTES = 128
 MFX_VERSION = 2  # include/mfx.h
+MFX_FOLD_ALS, MFX_FOLD_ALS_EXACT, MFX_FOLD_CCD, MFX_FOLD_IMPLICIT = 0, 1, 2, 3  # include/mfx.h mfx_fold_model
 
 u32p = C.POINTER(C.c_uint32)
 f32p = C.POINTER(C.c_float)
@@ -114,6 +115,10 @@ SIGNATURES = {
     "mfx_rec_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int,
                                  C.POINTER(mfx_csx), C.c_int, C.c_int]),
     "mfx_rec_query": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
+    "mfx_rec_fold_in_setup": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_float]),
+    "mfx_rec_fold_in": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                  C.c_void_p, C.c_void_p, C.c_int]),
+    "mfx_rec_fold_in_times": (C.c_int, [C.c_void_p, f64p]),
     "mfx_rec_destroy": (C.c_int, [C.c_void_p]),
     "mfx_topn_metrics": (C.c_int, [C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(mfx_coo), C.c_float, f64p,
                                    i64p]),

@@ -749,6 +749,54 @@ class Recommender:
         L.check(L.lib().mfx_rec_query(self.handle, n, pu, n_top, _vp(items), _vp(scores), L.MFX_HOST, item_slices))
         return items, scores
 
+    def fold_in_setup(self, model: int, lam: float, alpha: float = 0.0):
+        """Prepares fold-in (mfx_rec_fold_in_setup): model MFX_FOLD_ALS / MFX_FOLD_ALS_EXACT / MFX_FOLD_CCD /
+        MFX_FOLD_IMPLICIT, regularisation lam, confidence scale alpha (implicit model).  k <= 128."""
+        L.check(L.lib().mfx_rec_fold_in_setup(self.handle, int(model), float(lam), float(alpha)))
+
+    def fold_in(self, rows, n_top: int = 0, on_device: bool = False):
+        """Solves one factor row per query user against this handle's H and recommends from it (mfx_rec_fold_in).
+        rows: a RatingData-like CSR (csr_row_ptr / csr_col_idx / csr_val) or a (ptr, idx, val) triple of numpy arrays
+        or GPU tensors (32-bit ids, float32 values).  Returns (items [U, n_top], scores [U, n_top], W [U, k]), the lists
+        with each row's own items excluded (None, None when n_top = 0).  Tensors in, or on_device=True: everything
+        stays on the device and the results are tensors (items as int32 holding the uint32 ids)."""
+        ptr, idx, val = (rows.csr_row_ptr, rows.csr_col_idx, rows.csr_val) if hasattr(rows, "csr_row_ptr") else rows
+        if len(ptr.shape) != 1 or ptr.shape[0] < 1 or idx.shape != val.shape:
+            raise ValueError("rows: ptr [U + 1], idx [nnz], val [nnz]")
+        n, nnz, n_top = int(ptr.shape[0]) - 1, int(idx.shape[0]), int(n_top)
+        if any(_is_dev(a) for a in (ptr, idx, val)) or on_device:
+            import torch
+            dev = torch.device("cuda", self.device)
+
+            def put(a, dt):
+                if not _is_dev(a):
+                    a = np.ascontiguousarray(a, dt)
+                    a = torch.from_numpy(a.view(np.int32) if dt == np.uint32 else a).to(dev)
+                assert a.is_contiguous() and a.element_size() == 4, "query tensors: contiguous 32-bit"
+                return a
+            keep = [put(ptr, np.uint32), put(idx, np.uint32), put(val, np.float32)]
+            W = torch.empty((n, self.k), dtype=torch.float32, device=dev)
+            items = torch.empty((n, n_top), dtype=torch.int32, device=dev) if n_top else None
+            scores = torch.empty((n, n_top), dtype=torch.float32, device=dev) if n_top else None
+            p = lambda t: C.c_void_p(int(t.data_ptr())) if t is not None and t.numel() else None
+            L.check(L.lib().mfx_rec_fold_in(self.handle, n, nnz, p(keep[0]), p(keep[1]), p(keep[2]), p(W), n_top, p(items),
+                                            p(scores), L.MFX_DEVICE))
+            return items, scores, W
+        ptr, idx = np.ascontiguousarray(ptr, np.uint32), np.ascontiguousarray(idx, np.uint32)
+        val = np.ascontiguousarray(val, np.float32)
+        W = np.empty((n, self.k), np.float32)
+        items = np.empty((n, n_top), np.uint32) if n_top else None
+        scores = np.empty((n, n_top), np.float32) if n_top else None
+        L.check(L.lib().mfx_rec_fold_in(self.handle, n, nnz, _vp(ptr), _vp(idx), _vp(val), _vp(W), n_top, _vp(items),
+                                        _vp(scores), L.MFX_HOST))
+        return items, scores, W
+
+    def fold_in_times(self) -> dict:
+        """Seconds of the last fold_in call by phase (mfx_rec_fold_in_times): {"build", "solve", "score"}."""
+        out = (C.c_double * 3)()
+        L.check(L.lib().mfx_rec_fold_in_times(self.handle, out))
+        return {"build": out[0], "solve": out[1], "score": out[2]}
+
     def close(self):
         if self.handle:
             L.lib().mfx_rec_destroy(self.handle)

@@ -266,6 +266,35 @@ int mfx_rec_create(mfx_rec_t* out, const float* W, const float* H, int64_t rows,
  * (a test hook; item_slices * n_top must not exceed 8192). */
 int mfx_rec_query(mfx_rec_t r, int64_t nusers, const uint32_t* users, int32_t n_top, uint32_t* items,
                   float* scores, mfx_memspace space, int item_slices);
+/* Fold-in: users given by their interactions (users who arrived after training, or whose history changed) rather
+ * than by a row of W.  With the handle's H fixed, one factor row per query user is solved from the user's entries and
+ * then scored like mfx_rec_query.  H_O: the rows of H the user's entries name, r: their values. */
+typedef enum mfx_fold_model {
+    MFX_FOLD_ALS = 0,       /* (H_O^T H_O + lambda I) w = H_O^T r                  == mfx_als_half variant 1, bit for bit */
+    MFX_FOLD_ALS_EXACT = 1, /* the same system in the reference's operation order == mfx_als_half variant 0, bit for bit */
+    MFX_FOLD_CCD = 2,       /* (H_O^T H_O + fp32(lambda * n_u) I) w = H_O^T r, n_u = stored entries of the row: the exact
+                               minimiser of the CCD++ objective (denominator lambda |Omega| + sum v^2, mfx_rank_one_sweep)
+                               over the row, H fixed */
+    MFX_FOLD_IMPLICIT = 3   /* (H^T H + lambda I + sum_j w_j h_j h_j^T) w = sum_{r_j > 0} (1 + w_j) h_j, w_j = fp32(alpha r_j)
+                                                                                   == mfx_ials_half, bit for bit */
+} mfx_fold_model;
+/* Prepares fold-in on r: keeps H row-major (unpacked from the handle's own copy: the very bits it scores with, for
+ * either layout) with one all-zero row behind it, and for MFX_FOLD_IMPLICIT the base Gramian H^T H + lambda I.  May be
+ * called again with another model, lambda or alpha.  MFX_ERR_INVALID: k > 128, lambda <= 0 or not finite, alpha < 0
+ * or not finite, an unknown model. */
+int mfx_rec_fold_in_setup(mfx_rec_t r, int model, float lambda, float alpha);
+/* Solves one factor row per query user from the CSR rows ptr [nusers+1] / idx [nnz] / val [nnz] (column ids < cols,
+ * non-decreasing within a row, as for the exclude matrix of mfx_rec_create; checked on the device, as are the values
+ * of MFX_FOLD_IMPLICIT: finite, >= 0, alpha * r finite), then returns the n_top best items of each row with the row's
+ * own items excluded, ranked as mfx_rec_query ranks.  A row without entries gets w = 0 under every model.
+ * W_out [nusers][k] or NULL.  n_top = 0: solve only (items / scores ignored); else 1 <= n_top <= 1024, items
+ * [nusers][n_top], scores [nusers][n_top] or NULL.  `space` applies to every array.  MFX_ERR_INVALID before the first
+ * successful mfx_rec_fold_in_setup; a refused query leaves the handle usable. */
+int mfx_rec_fold_in(mfx_rec_t r, int64_t nusers, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val,
+                    float* W_out, int32_t n_top, uint32_t* items, float* scores, mfx_memspace space);
+/* Wall-clock seconds of the last mfx_rec_fold_in on r, each phase ending in a stream synchronisation: [0] host build
+ * (query upload, checks, the host-side split into work items), [1] solve, [2] score (packing, top-N, copies out). */
+int mfx_rec_fold_in_times(mfx_rec_t r, double seconds[3]);
 int mfx_rec_destroy(mfx_rec_t r);
 
 /* ------------------------------------------------------------------------------------

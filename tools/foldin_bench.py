@@ -1,0 +1,88 @@
+"""Fold-in recommendation at the Netflix shape: ms per batch of query users, split into host build / solve / score.
+
+Builds the Netflix-shaped synthetic matrix on the GPU (mfx.synth_torch, as tools/ials_bench.py does) and a random H
+(k = 64) in a recommender handle.  The query rows are training rows of that matrix, so every batch is one the trainers
+themselves solve: 1, 64 and 1 024 seeded random users, and all 480 189 rows in order.  Query arrays are device tensors.
+For models ALS and IMPLICIT at N = 10 it prints ONE JSON line: per (model, batch) the median / min / max ms per
+mfx_rec_fold_in call over --reps (host clock around the call, which ends in a stream synchronisation) and the split of
+the median call into host build (query copies, checks, the host-side split into work items), solve and score, as
+mfx_rec_fold_in_times reports it.
+
+    python tools/foldin_bench.py [--reps 5] [--k 64] [--n-top 10]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "cuda-recommender_amd"))
+
+ROWS, COLS, NNZ = 480189, 17770, 99_072_112
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--k", type=int, default=64)
+    ap.add_argument("--n-top", type=int, default=10)
+    ap.add_argument("--lam", type=float, default=0.05)
+    ap.add_argument("--alpha", type=float, default=1.0)
+    ap.add_argument("--seed", type=int, default=1234)
+    a = ap.parse_args()
+    import torch
+    import mfx
+    from mfx import synth_torch
+    dev = torch.device("cuda:0")
+    d = synth_torch.synth_ratings_device(ROWS, COLS, NNZ, seed=a.seed, device="cuda:0")
+    rows, cols = int(d["rows"]), int(d["cols"])
+    rp, ci, cv = d["csr_row_ptr"], d["csr_col_idx"], d["csr_val"]
+    rp_h = rp.cpu().numpy().astype(np.int64)
+    nnz = int(rp_h[-1])
+    g = torch.Generator(device=dev)
+    g.manual_seed(a.k)
+    H = (torch.randn(cols, a.k, generator=g, device=dev) * 0.3).contiguous()
+    W = torch.zeros(1, a.k, device=dev)
+
+    def batch(users):
+        """Device CSR of the given training rows."""
+        lo, hi = rp_h[users], rp_h[users + 1]
+        ptr = np.zeros(len(users) + 1, np.int64)
+        ptr[1:] = np.cumsum(hi - lo)
+        pos = torch.from_numpy(np.concatenate([np.arange(x, y) for x, y in zip(lo, hi)])).to(dev)
+        return torch.from_numpy(ptr.astype(np.int32)).to(dev), ci[pos].contiguous(), cv[pos].contiguous()
+
+    batches = {str(n): batch(np.sort(np.random.default_rng(n).choice(rows, n, replace=False))) for n in (1, 64, 1024)}
+    batches["all"] = (rp, ci, cv)
+    out = {"tool": "foldin_bench", "workload": f"{rows}x{cols} nnz={nnz}", "k": a.k, "n_top": a.n_top, "lambda": a.lam,
+           "alpha": a.alpha, "reps": a.reps, "query_arrays": "device", "runs": []}
+    with mfx.Recommender(W, H, 1) as r:
+        for name, model in (("ALS", mfx.MFX_FOLD_ALS), ("IMPLICIT", mfx.MFX_FOLD_IMPLICIT)):
+            t0 = time.perf_counter()
+            r.fold_in_setup(model, a.lam, a.alpha)
+            setup_ms = (time.perf_counter() - t0) * 1e3
+            for bname, q in batches.items():
+                r.fold_in(q, a.n_top)  # warm-up
+                torch.cuda.synchronize()
+                ms, split = [], []
+                for _ in range(a.reps):
+                    t0 = time.perf_counter()
+                    r.fold_in(q, a.n_top)
+                    torch.cuda.synchronize()
+                    ms.append((time.perf_counter() - t0) * 1e3)
+                    split.append(r.fold_in_times())
+                med = int(np.argsort(ms)[len(ms) // 2])
+                run = {"model": name, "batch": bname, "users": int(q[0].numel()) - 1, "nnz": int(q[1].numel()),
+                       "setup_ms": round(setup_ms, 3), "ms_median": round(float(np.median(ms)), 3),
+                       "ms_min": round(min(ms), 3), "ms_max": round(max(ms), 3)}
+                run.update({f"{key}_ms": round(v * 1e3, 3) for key, v in split[med].items()})
+                out["runs"].append(run)
+                print(json.dumps(run), file=sys.stderr, flush=True)
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
