@@ -265,13 +265,30 @@ __device__ __forceinline__ float2 load_partial_sc1(const float2* p) {
 // stay at 64 VGPRs (FM_FCSR_RO takes 66, hence 7 waves per SIMD and one workgroup, when left to the allocator)
 template <int MODE> constexpr int flat_min_waves(int block) { return MODE == FM_FCSC_RO || MODE == FM_FCSR_RO ? block / 128 : 1; }
 
-template <int MODE, bool LDS, int BLOCK, bool PSCHK, bool FUSE = false>
+// PERSIST (LDS panels, no in-pass finalize): workgroup w of G walks the contiguous chunks [w n / G, (w + 1) n / G) instead of
+// one.  The gathered slice is staged when the workgroup starts and again only where wg_panel changes inside its range
+// (3023 stagings per launch become about G + panels at the Netflix shape); the per-segment window still belongs to a chunk,
+// so there are two, used alternately: while chunk i reads window i & 1, a wave that has finished its span first sends the
+// first tile of its span in chunk i + 1, then fills its share of that chunk's window into the other one.  One barrier per
+// chunk orders both: past it every wave is done with chunk i - 1, so window i & 1 is complete and the other one is free.
+// Per span nothing differs from the one-chunk form: same start, same metadata words, same owner rule for part / carry, the
+// same sums in the same order.  (Tried and dropped, DESIGN.md section 10.0: the window's loads issued during the span and
+// held in registers; streams two tiles ahead.)
+template <int MODE, bool LDS, int BLOCK, bool PSCHK, bool FUSE = false, bool PERSIST = false>
 __global__ __launch_bounds__(BLOCK, flat_min_waves<MODE>(BLOCK)) void k_flat(FlatArgs a) {
     static_assert(!FUSE || ModeTraits<MODE>::kDot, "fused finalize: passes that produce sums");
+    static_assert(!PERSIST || (LDS && !FUSE), "persistent form: LDS panels without the in-pass finalize");
     using TR = ModeTraits<MODE>;
     // FUSE: dispatch slot -> chunk through wg_order (ascending first segment, so that the chunks of one segment
     // group run at about the same time and groups complete all along the pass, not at its end)
-    const uint32_t chunk = FUSE ? a.wg_order[blockIdx.x] : blockIdx.x;
+    uint32_t chunk = FUSE ? a.wg_order[blockIdx.x] : blockIdx.x;
+    uint32_t chunk_end = chunk + 1;  // PERSIST: end of this workgroup's range
+    const uint32_t nchunks = a.nspans / (BLOCK / 64);  // (LDS panels: whole chunks only)
+    if constexpr (PERSIST) {
+        chunk = (uint32_t) ((uint64_t) blockIdx.x * nchunks / gridDim.x);
+        chunk_end = (uint32_t) ((uint64_t) (blockIdx.x + 1) * nchunks / gridDim.x);
+        if (chunk >= chunk_end) return;  // (more workgroups than chunks: the launcher never asks for that)
+    }
     using G = typename TR::G;
     using P = typename TR::P;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
@@ -280,11 +297,11 @@ __global__ __launch_bounds__(BLOCK, flat_min_waves<MODE>(BLOCK)) void k_flat(Fla
     constexpr size_t kSliceEntry = sizeof(S) + (TR::kAux ? sizeof(float) : 0);  // LDS bytes per gathered index
     float* __restrict__ aux_slice = reinterpret_cast<float*>(lds_raw + ((size_t) a.panel_rows + 1) * sizeof(S));
     const uint32_t lane = threadIdx.x & 63;
-    const uint32_t span = __builtin_amdgcn_readfirstlane(chunk * (BLOCK / 64) + (threadIdx.x >> 6));
+    uint32_t span = __builtin_amdgcn_readfirstlane(chunk * (BLOCK / 64) + (threadIdx.x >> 6));
     const G* __restrict__ gather = static_cast<const G*>(a.gather);
     const P* __restrict__ perseg = static_cast<const P*>(a.perseg);
     const uint32_t span_words = a.tiles_per_span * (kTileElems / 32);
-    const uint64_t start = (uint64_t) span * a.tiles_per_span * kTileElems;
+    uint64_t start = (uint64_t) span * a.tiles_per_span * kTileElems;
     // panel-local indices are 16-bit: 2 B/nnz instead of 4 (10 B/nnz per fused pass instead of 12)
     using IdxVec = typename std::conditional<LDS, u16x4, u32x4>::type;
     using IdxElem = typename std::conditional<LDS, uint16_t, uint32_t>::type;
@@ -297,15 +314,10 @@ __global__ __launch_bounds__(BLOCK, flat_min_waves<MODE>(BLOCK)) void k_flat(Fla
     IdxVec id_n;
     f32x4 v_n;
     uint32_t fl_n, hp_n, hp_nn;
-    if constexpr (LDS) {
-        // The first tile's streams go out BEFORE the slice is staged: a CU holds two of these workgroups, and while
-        // one of them stages (two to three dependent round trips before its barrier) half the CU would otherwise
-        // have nothing in flight.  (LDS panels: every chunk holds BLOCK / 64 whole spans, so the span exists.)
-        id_n = __builtin_nontemporal_load(idx4);
-        v_n = __builtin_nontemporal_load(val4);
-        fl_n = flw[0]; hp_n = hpw[0]; hp_nn = hpw[8];
-        // stage this workgroup's panel slice; slot panel_rows is the zero entry padding points at
-        const uint32_t panel = a.wg_panel[chunk];
+    // PERSIST: from a wave's span to its span in the next chunk, in index / value quads and in metadata words
+    const size_t span_step_q = (size_t) (BLOCK / 64) * a.tiles_per_span * 64, span_step_w = (size_t) (BLOCK / 64) * span_words;
+    // stage a panel's slice; slot panel_rows is the zero entry padding points at
+    auto stage_slice = [&](uint32_t panel) {
         const uint32_t gbase = panel * a.panel_rows;
         const uint32_t cnt = a.gather_len - gbase < a.panel_rows ? a.gather_len - gbase : a.panel_rows;
         for (uint32_t i = threadIdx.x; i < cnt; i += BLOCK) slice[i] = to_slice<S, G>(gather[gbase + i]);
@@ -314,21 +326,54 @@ __global__ __launch_bounds__(BLOCK, flat_min_waves<MODE>(BLOCK)) void k_flat(Fla
             for (uint32_t i = threadIdx.x; i < cnt; i += BLOCK) aux_slice[i] = a.gather_aux[gbase + i];
             if (threadIdx.x == 0) aux_slice[a.panel_rows] = 0.f;
         }
+    };
+    uint32_t panel = 0, panel_next = 0;  // PERSIST: of this chunk / of the next one (fetched a chunk ahead)
+    if constexpr (LDS) {
+        // The first tile's streams go out BEFORE the slice is staged: a CU holds two of these workgroups, and while
+        // one of them stages (two to three dependent round trips before its barrier) half the CU would otherwise
+        // have nothing in flight.  (LDS panels: every chunk holds BLOCK / 64 whole spans, so the span exists.)
+        id_n = __builtin_nontemporal_load(idx4);
+        v_n = __builtin_nontemporal_load(val4);
+        fl_n = flw[0]; hp_n = hpw[0]; hp_nn = hpw[8];
+        panel = a.wg_panel[chunk];
+        stage_slice(panel);
     }
     // The workgroup touches a contiguous window of ranks; stage their per-segment operands next to
     // the slice so that segmented tiles read LDS instead of chasing seg_of_rank -> perseg through L2.
     P* __restrict__ ps_lds = reinterpret_cast<P*>(lds_raw + (((size_t) a.panel_rows + 1) * kSliceEntry + 15) / 16 * 16);
     uint32_t win_base = 0;
+    // heads before chunk c (c <= nchunks: the metadata's spare words hold the total); a chunk's window is
+    // [max(heads before it, 1) - 1, heads before the next chunk), cut at kPerSegLdsCap entries
+    auto heads_before = [&](uint32_t c) { return a.hpre[(size_t) c * (BLOCK / 64) * span_words]; };
+    uint32_t hb1 = 0, hb2 = 0;  // PERSIST: heads before chunk + 1, chunk + 2 (the next window's bounds, fetched a chunk ahead)
     if constexpr (LDS && TR::kPerSeg) {
-        const uint32_t first = chunk * (BLOCK / 64);
-        const uint32_t rb0 = a.hpre[(size_t) first * span_words];
+        const uint32_t rb0 = heads_before(chunk);
         win_base = rb0 > 0 ? rb0 - 1 : 0;
-        const uint32_t win_end = a.hpre[(size_t) (first + BLOCK / 64) * span_words];  // heads before the next chunk
+        const uint32_t win_end = heads_before(chunk + 1);  // heads before the next chunk
+        if constexpr (PERSIST) { hb1 = win_end; hb2 = heads_before(chunk + 2 < nchunks ? chunk + 2 : nchunks); }
         uint32_t cnt = win_end - win_base;
         if (cnt > kPerSegLdsCap) cnt = kPerSegLdsCap;
         for (uint32_t j = threadIdx.x; j < cnt; j += BLOCK) ps_lds[j] = perseg[a.seg_of_rank[win_base + j]];
     }
-    if constexpr (LDS) __syncthreads();
+    if constexpr (LDS && !PERSIST) __syncthreads();
+    for (uint32_t visit = 0;; ++visit) {  // one chunk per round; only PERSIST comes round again
+    const bool more = PERSIST && chunk + 1 < chunk_end;
+    uint32_t win_base_n = 0, win_cnt_n = 0;  // PERSIST: the next chunk's window
+    if constexpr (PERSIST) {
+        if (visit && panel_next != panel) {  // workgroup-uniform: every wave is done with the old slice before it is replaced
+            __syncthreads();
+            panel = panel_next;
+            stage_slice(panel);
+        }
+        __syncthreads();
+        if constexpr (TR::kPerSeg) {
+            if (more) {
+                win_base_n = hb1 > 0 ? hb1 - 1 : 0;
+                win_cnt_n = hb2 - win_base_n < kPerSegLdsCap ? hb2 - win_base_n : kPerSegLdsCap;
+            }
+        }
+    }
+    P* __restrict__ ps_cur = PERSIST ? ps_lds + (visit & 1u) * kPerSegLdsCap : ps_lds;  // this chunk's window
     // a wave without work (plain layout: a span beyond the last one, or one that holds only padding) skips the stream loop;
     // with the fused finalize it still joins the epilogue's barriers
     bool live = span < a.nspans;  // (LDS panels: always true, every chunk holds BLOCK / 64 spans)
@@ -336,8 +381,8 @@ __global__ __launch_bounds__(BLOCK, flat_min_waves<MODE>(BLOCK)) void k_flat(Fla
     auto fetch_ps = [&](uint32_t r) -> P {  // r: rank, always valid where this is called
         if constexpr (LDS) {
             const uint32_t rl = r - win_base;
-            if constexpr (!PSCHK) return ps_lds[rl];
-            else if (rl < kPerSegLdsCap) return ps_lds[rl];
+            if constexpr (!PSCHK) return ps_cur[rl];
+            else if (rl < kPerSegLdsCap) return ps_cur[rl];
         }
         return perseg[a.seg_of_rank[r]];
     };
@@ -377,12 +422,25 @@ __global__ __launch_bounds__(BLOCK, flat_min_waves<MODE>(BLOCK)) void k_flat(Fla
         // reading two tiles past the last span stays in bounds (and yields heads_total).
         const uint32_t cur1_next = __builtin_amdgcn_readfirstlane(hp_nn);
         hp_n = hp_nn;
-        if (tile + 1 < ntiles) {
+        if constexpr (!PERSIST) {
+            if (tile + 1 < ntiles) {
+                id_n = __builtin_nontemporal_load(idx4 + (tile + 1) * 64);
+                v_n = __builtin_nontemporal_load(val4 + (tile + 1) * 64);
+            }
+            fl_n = flw[(tile + 1) * 8];
+            hp_nn = hpw[(tile + 2) * 8];
+        } else if (tile + 1 < ntiles) {
             id_n = __builtin_nontemporal_load(idx4 + (tile + 1) * 64);
             v_n = __builtin_nontemporal_load(val4 + (tile + 1) * 64);
+            fl_n = flw[(tile + 1) * 8];
+            hp_nn = hpw[(tile + 2) * 8];
+        } else if (more) {  // the first tile of this wave's span in the next chunk, and what that chunk's round needs
+            id_n = __builtin_nontemporal_load(idx4 + span_step_q);
+            v_n = __builtin_nontemporal_load(val4 + span_step_q);
+            fl_n = flw[span_step_w]; hp_n = hpw[span_step_w]; hp_nn = hpw[span_step_w + 8];
+            panel_next = a.wg_panel[chunk + 1];
+            if constexpr (TR::kPerSeg) { hb1 = hb2; hb2 = heads_before(chunk + 3 < nchunks ? chunk + 3 : nchunks); }
         }
-        fl_n = flw[(tile + 1) * 8];
-        hp_nn = hpw[(tile + 2) * 8];
         const uint64_t base = start + (uint64_t) tile * kTileElems;
         // plain layout only: the tile that straddles nnz needs its padding masked; with LDS panels
         // padding gathers the zero slot and contributes exact zeros
@@ -505,6 +563,22 @@ __builtin_nontemporal_store(f32x4{vo[0], vo[1], vo[2], vo[3]}, val4 + tile * 64)
         }
     }
     }  // live
+    if constexpr (!PERSIST) break;
+    if (!more) break;
+    if constexpr (TR::kPerSeg) {  // this thread's share of the next chunk's window, into the window nobody reads any more
+        P* __restrict__ ps_nxt = ps_lds + ((visit + 1) & 1u) * kPerSegLdsCap;
+        for (uint32_t j = threadIdx.x; j < win_cnt_n; j += BLOCK) ps_nxt[j] = perseg[a.seg_of_rank[win_base_n + j]];
+        win_base = win_base_n;
+    }
+    // on to the same wave slot of the next chunk (addresses re-derived from the wave-uniform span, as at the start)
+    ++chunk;
+    span += BLOCK / 64;
+    start = (uint64_t) span * a.tiles_per_span * kTileElems;
+    idx4 = reinterpret_cast<const IdxVec*>(static_cast<const IdxElem*>(a.idx) + start) + lane;
+    val4 = reinterpret_cast<f32x4*>(a.val + start) + lane;
+    flw = a.flags32 + (size_t) span * span_words + (lane >> 3);
+    hpw = a.hpre + (size_t) span * span_words + (lane >> 3);
+    }  // chunk rounds
     if constexpr (FUSE) fused_finalize<BLOCK>(a, chunk, lds_raw);
 }
 
@@ -1143,15 +1217,54 @@ int ensure_dynamic_lds(const void* kernel, LdsAttrCache& c, size_t lds_bytes) {
 }
 }  // namespace
 
-template <int MODE, bool LDS, int BLOCK, bool PSCHK, bool FUSE = false>
+template <int MODE, bool LDS, int BLOCK, bool PSCHK, bool FUSE = false, bool PERSIST = false>
 int launch_flat_t(const FlatArgs& a, uint32_t grid, size_t lds_bytes, hipStream_t st) {
     if (lds_bytes > 48 * 1024) {
         static LdsAttrCache cache;  // per instantiation
-        MFX_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(k_flat<MODE, LDS, BLOCK, PSCHK, FUSE>), cache, lds_bytes));
+        MFX_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(k_flat<MODE, LDS, BLOCK, PSCHK, FUSE, PERSIST>), cache, lds_bytes));
     }
-    hipLaunchKernelGGL((k_flat<MODE, LDS, BLOCK, PSCHK, FUSE>), dim3(grid), dim3(BLOCK), lds_bytes, st, a);
+    hipLaunchKernelGGL((k_flat<MODE, LDS, BLOCK, PSCHK, FUSE, PERSIST>), dim3(grid), dim3(BLOCK), lds_bytes, st, a);
     MFX_LAUNCH_CHECK();
     return MFX_OK;
+}
+
+// Workgroups of k_flat<MODE, true, BLOCK, PSCHK, false, true> that one CU holds at `lds_bytes` each: what its registers and
+// launch bound allow (asked of the runtime once per instantiation and device), cut by the LDS.
+template <int MODE, int BLOCK, bool PSCHK>
+uint32_t flat_persist_per_cu(size_t lds_bytes) {
+    static std::mutex m;
+    static int by_regs[64] = {};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
+    std::lock_guard<std::mutex> lk(m);
+    if (by_regs[dev] == 0) {
+        int n = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, reinterpret_cast<const void*>(k_flat<MODE, true, BLOCK, PSCHK, false, true>), BLOCK, 0) != hipSuccess || n < 1) {
+            (void) hipGetLastError();
+            n = 1;
+        }
+        by_regs[dev] = n;
+    }
+    const size_t by_lds = lds_bytes ? (size_t) 160 * 1024 / lds_bytes : 1;
+    return (uint32_t) std::max<size_t>(1, std::min<size_t>((size_t) by_regs[dev], by_lds));
+}
+
+// Persistent launch (k_flat, PERSIST) where the view asks for it and there are more chunks than resident workgroups;
+// today's one-chunk launch otherwise.  lds_bytes: of the one-chunk form (the persistent one adds the second window).
+template <int MODE, int BLOCK, bool PSCHK>
+int launch_flat_persist(const SegStreamDev& s, const FlatArgs& a, uint32_t grid, size_t lds_bytes, hipStream_t st) {
+    if ((s.flat_persist_modes >> MODE) & 1u) {
+        const size_t lds2 = lds_bytes + (size_t) kPerSegLdsCap * sizeof(typename ModeTraits<MODE>::P);
+        if (lds2 <= 160 * 1024) {
+            // resident workgroups, if every one of them walks two chunks at least: with fewer there is next to no staging to
+            // save, and the one-chunk launch is the faster one (ML-10M shape, 310 chunks on 256 CUs: 29.7 / 30.3 us against
+            // 30.1 / 31.1 us per catch-up pass).  A pinned count (tests) is taken as it is, up to one chunk per workgroup.
+            const uint32_t resident = s.flat_cus * flat_persist_per_cu<MODE, BLOCK, PSCHK>(lds2);
+            const uint32_t g = s.flat_persist_wgs ? s.flat_persist_wgs : (grid / 2 >= resident ? resident : grid);
+            if (g >= 1 && g < grid) return launch_flat_t<MODE, true, BLOCK, PSCHK, false, true>(a, g, lds2, st);
+        }
+    }
+    return launch_flat_t<MODE, true, BLOCK, PSCHK>(a, grid, lds_bytes, st);
 }
 
 template <int MODE, int BLOCK>
@@ -1231,11 +1344,23 @@ int launch_flat_lds_only(const SegStreamDev& s, const FlatArgs& a, hipStream_t s
     size_t lds_bytes = (((size_t) s.panel_rows + 1) * entry + 15) / 16 * 16 + (size_t) kPerSegLdsCap * sizeof(typename ModeTraits<MODE>::P);
     MFX_REQUIRE(lds_bytes <= 160 * 1024, "launch_flat: mode %d needs %zu bytes of LDS at %u panel rows", MODE, lds_bytes, s.panel_rows);
     const uint32_t grid = s.nspans / s.spans_per_wg;
-    switch (s.spans_per_wg) {
-        case 4: return launch_flat_lds<MODE, 256>(s, a, grid, lds_bytes, st);
-        case 8: return launch_flat_lds<MODE, 512>(s, a, grid, lds_bytes, st);
-        case 16: return launch_flat_lds<MODE, 1024>(s, a, grid, lds_bytes, st);
-        default: return fail(MFX_ERR_INVALID, "panel layout: spans_per_wg must be 4, 8 or 16 (got %u)", s.spans_per_wg);
+    // The read-only passes keep the one-chunk form: they must stay at 64 VGPRs for their second workgroup per CU, and the
+    // persistent form of them takes 72 to 85 when left to the allocator (9 to 21 spilled VGPRs at the bound); DESIGN.md section 10.0.
+    if constexpr (!ModeTraits<MODE>::kWrite) {
+        switch (s.spans_per_wg) {
+            case 4: return launch_flat_lds<MODE, 256>(s, a, grid, lds_bytes, st);
+            case 8: return launch_flat_lds<MODE, 512>(s, a, grid, lds_bytes, st);
+            case 16: return launch_flat_lds<MODE, 1024>(s, a, grid, lds_bytes, st);
+            default: return fail(MFX_ERR_INVALID, "panel layout: spans_per_wg must be 4, 8 or 16 (got %u)", s.spans_per_wg);
+        }
+    } else {
+        const bool pschk = s.max_wg_ranks > kPerSegLdsCap;
+        switch (s.spans_per_wg) {
+            case 4: return pschk ? launch_flat_persist<MODE, 256, true>(s, a, grid, lds_bytes, st) : launch_flat_persist<MODE, 256, false>(s, a, grid, lds_bytes, st);
+            case 8: return pschk ? launch_flat_persist<MODE, 512, true>(s, a, grid, lds_bytes, st) : launch_flat_persist<MODE, 512, false>(s, a, grid, lds_bytes, st);
+            case 16: return pschk ? launch_flat_persist<MODE, 1024, true>(s, a, grid, lds_bytes, st) : launch_flat_persist<MODE, 1024, false>(s, a, grid, lds_bytes, st);
+            default: return fail(MFX_ERR_INVALID, "panel layout: spans_per_wg must be 4, 8 or 16 (got %u)", s.spans_per_wg);
+        }
     }
 }
 

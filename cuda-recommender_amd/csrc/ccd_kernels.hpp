@@ -75,6 +75,10 @@ struct SegStreamDev {
     const uint32_t* own_short = nullptr;       // [own_nshort][4] all other segments, longest first: one wavefront each
     uint32_t own_nlong = 0, own_nshort = 0;
     uint32_t own_max_len = 0;                  // the longest segment (the owner form gives balance up: the solver declines it beyond 65536 entries)
+    // persistent flat passes (k_flat's PERSIST form; set by the solver, 0 = one chunk per workgroup as ever)
+    uint32_t flat_persist_modes = 0;           // bit m: FlatMode m walks contiguous chunk ranges with resident workgroups only
+    uint32_t flat_cus = 0;                     // compute units of the device: the grid is flat_cus x workgroups a CU holds ...
+    uint32_t flat_persist_wgs = 0;             // ... unless pinned (MFX_FLAT_WGS: tests); never more than there are chunks
     // reduction scratch written by the flat kernels
     float2* part = nullptr;    // [nne] (g, h) per non-empty virtual segment
     float2* carry = nullptr;   // [nspans] (g, h) of a span's leading run

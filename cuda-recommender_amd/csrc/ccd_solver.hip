@@ -823,6 +823,23 @@ int CcdSolver::init(const mfx_csx* R, const mfx_coo* T, const mfx_params* p, mfx
                        fits(csc_.view, sizeof(float4)) && fits(csr_.view, sizeof(float4) + sizeof(float)) && k_ >= 2;
         if (defer_resid_) MFX_TRY(packD_.alloc_zero(m_, st_));
     }
+    {   // persistent flat passes (k_flat's PERSIST form): resident workgroups walk contiguous chunk ranges, so a panel's slice is
+        // staged once per workgroup and panel instead of once per chunk.  On for the catch-up passes of rank_pair, whose slices
+        // fill a CU's LDS; its read-only passes have no persistent form (section 10.0).  MFX_FLAT_PERSIST=0: one chunk per workgroup as before (A/B, the tests' reference); a value
+        // above 1 is a bit mask over FlatMode (A/B per pass).  MFX_FLAT_WGS pins the workgroup count (tests).
+        uint32_t modes = (1u << FM_FCSC2) | (1u << FM_FCSR2);
+        if (const char* e = std::getenv("MFX_FLAT_PERSIST")) { const long v = std::strtol(e, nullptr, 0); if (v == 0) modes = 0; else if (v > 1) modes &= (uint32_t) v; }
+        uint32_t wgs = 0;
+        if (const char* e = std::getenv("MFX_FLAT_WGS")) { const int v = std::atoi(e); if (v > 0) wgs = (uint32_t) v; }
+        int dev = 0, cus = 0;
+        MFX_HIP(hipGetDevice(&dev));
+        MFX_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+        for (SegStreamDev* v : {&csc_.view, &csr_.view}) {
+            v->flat_persist_modes = defer_resid_ && cus > 0 ? modes : 0u;
+            v->flat_cus = cus > 0 ? (uint32_t) cus : 0u;
+            v->flat_persist_wgs = wgs;
+        }
+    }
     MFX_TRY(rmse_sum_.alloc_zero(1, st_));
     MFX_HIP(hipStreamSynchronize(st_));
     return MFX_OK;
