@@ -26,6 +26,16 @@
 
 #include "ccd_kernels.hpp"
 
+// MFX_ALS_BLOCK = 1 (ials_block_step.hip): the implicit kernels once more as the k_ialsb_* instantiations, one block step of
+// the block subspace sweeps (ials_block.hip): the system of one block of d <= 128 coordinates.  a.k is d, a.X the block's
+// column slice of X, a.G the diagonal block of the base Gramian; the rhs weight of an entry is (1 + w) - w s with its
+// stored score s, the rhs starts from -P[seg] (P = G[block, :] y), and the solution written to Y is the step z = -Delta.
+#ifndef MFX_ALS_BLOCK
+#define MFX_ALS_BLOCK 0
+#endif
+#if MFX_ALS_BLOCK
+#define MFX_ALS_IMPLICIT 1
+#endif
 // MFX_ALS_IMPLICIT = 1 (ials_half.hip): the same kernels as the implicit-feedback k_ials_* instantiations.  A translation
 // unit of their own, so that the k_als_* kernels of this one compile to exactly the code they had without them.
 #ifndef MFX_ALS_IMPLICIT
@@ -37,7 +47,9 @@
 #ifndef MFX_ALS_NREG
 #define MFX_ALS_NREG 0
 #endif
-#if MFX_ALS_IMPLICIT
+#if MFX_ALS_BLOCK
+#define ALS_KERNEL(name) k_ialsb_##name
+#elif MFX_ALS_IMPLICIT
 #define ALS_KERNEL(name) k_ials_##name
 #elif MFX_ALS_NREG
 #define ALS_KERNEL(name) k_alsn_##name
@@ -103,6 +115,10 @@ struct AlsArgs {
     const float* G;    // [k][k] base Gramian X^T X + lambda I (ials_base_gramian), the start of every unsplit / reduced system
 #if MFX_ALS_NREG
     const uint32_t* seg_ptr;  // (k_alsn_* only) segment pointers [nseg + 1]: segment s has seg_ptr[s + 1] - seg_ptr[s] entries
+#endif
+#if MFX_ALS_BLOCK
+    const float* score;  // (k_ialsb_* only) [nnz + pad]: the score <x_j, y> of every stored pair, parallel to val
+    const float* P;      // (k_ialsb_* only) [nseg][k]: G[block, :] y of every segment
 #endif
 };
 constexpr uint32_t kPhaseCopies = 1024;
@@ -405,6 +421,10 @@ __device__ void factor_solve(float* lds, const AlsArgs& a, uint32_t seg, unsigne
     lam = mul_rn(a.lambda, (float) (a.seg_ptr[seg + 1] - a.seg_ptr[seg]));
 #endif
     for (int i = (int) lane; i < KP; i += 64) L[roff(i) + i] = i < k ? add_rn(L[roff(i) + i], lam) : 1.0f;  // rows k.. : identity
+#if MFX_ALS_BLOCK
+    // rhs = sum_j ((1 + w_j) - w_j s_j) x_j - P[seg]; FULL: position i of the permuted image is column 4 (i & 15) + (i >> 4)
+    for (int i = (int) lane; i < k; i += 64) bv[i] = sub_rn(bv[i], a.P[(size_t) seg * k + (FULL ? 4 * (i & 15) + (i >> 4) : i)]);
+#endif
     __syncthreads();
 
     // Left-looking Cholesky on the lower triangle, row i at a time (the reference's choldc1 loop,
@@ -598,9 +618,13 @@ __device__ void factor_solve(float* lds, const AlsArgs& a, uint32_t seg, unsigne
 constexpr bool kIalsSqrt = MFX_IALS_SQRT != 0;
 
 // r -> (rhs weight, Gramian operand scale): (1 + w or 0, sqrt(w)) in the sqrt form, (1 + w or 0, w) in the copy form
-__device__ __forceinline__ void ials_weights(float r, float alpha, float& rhs, float& scale) {
+__device__ __forceinline__ void ials_weights(float r, float alpha, float& rhs, float& scale, float sv = 0.f) {
     const float w = mul_rn(alpha, r);
+#if MFX_ALS_BLOCK
+    rhs = r > 0.f ? sub_rn(add_rn(1.0f, w), mul_rn(w, sv)) : 0.f;  // (1 + w) - w s: minus half the gradient's weight at score s
+#else
     rhs = r > 0.f ? add_rn(1.0f, w) : 0.f;
+#endif
     scale = kIalsSqrt ? __builtin_sqrtf(w) : w;
 }
 
@@ -620,9 +644,10 @@ __device__ __forceinline__ void ials_base32(f32x16 (&acc)[Tiles<NT>::kCount], co
 }
 // One gathered row pair of k_als_gram<NT>, implicit form: rhs from the unscaled row, then the weighted MFMAs
 template <int NT>
-__device__ __forceinline__ void ials_rows(float (&av)[NT], float rv, float alpha, float (&bacc)[NT], f32x16 (&acc)[Tiles<NT>::kCount]) {
+__device__ __forceinline__ void ials_rows(float (&av)[NT], float rv, float alpha, float (&bacc)[NT], f32x16 (&acc)[Tiles<NT>::kCount],
+                                          float sv = 0.f) {
     float rw, sw;
-    ials_weights(rv, alpha, rw, sw);
+    ials_weights(rv, alpha, rw, sw, sv);
     float xa[NT];
 #pragma unroll
     for (int I = 0; I < NT; ++I) {
@@ -678,6 +703,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(als_waves(NT
         const uint32_t zrow = (uint32_t) __builtin_amdgcn_readfirstlane((int) a.x_rows);
         uint32_t ix[2][U];
         float rv[2][U];
+#if MFX_ALS_BLOCK
+        float sv[2][U];
+#endif
         float av[2][U][NT];
         auto load_idx = [&](auto S, uint32_t q0) {
             constexpr int s = decltype(S)::value;
@@ -695,6 +723,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(als_waves(NT
                 asm volatile("" : "+v"(row));  // opaque use: keeps the index load where it was issued (see g16_load_rows)
                 const uint32_t q = q0 + 2 * u + h;
                 rv[s][u] = a.val[q < it.hi ? q : a.sentinel];
+#if MFX_ALS_BLOCK
+                sv[s][u] = a.score[q < it.hi ? q : a.sentinel];
+#endif
     #pragma unroll
                 for (int I = 0; I < NT; ++I) {
                     const uint32_t col = I * 32 + c31;
@@ -708,7 +739,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(als_waves(NT
     #pragma unroll
             for (int u = 0; u < U; ++u) {
                 if constexpr (kImplicit) {
+#if MFX_ALS_BLOCK
+                    ials_rows<NT>(av[s][u], rv[s][u], a.alpha, bacc, acc, sv[s][u]);
+#else
                     ials_rows<NT>(av[s][u], rv[s][u], a.alpha, bacc, acc);
+#endif
                     continue;
                 }
                 int ti = 0;
@@ -756,6 +791,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(als_waves(NT
         const uint32_t zrow = (uint32_t) __builtin_amdgcn_readfirstlane((int) a.x_rows);
         uint32_t row_n[U];
         float rv_n[U], rv_c[U];
+#if MFX_ALS_BLOCK
+        float sv_n[U], sv_c[U];
+#endif
         float av_n[U][NT];
         auto load_idx = [&](uint32_t q0) {
     #pragma unroll
@@ -764,6 +802,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(als_waves(NT
                 const uint32_t qe = q < it.hi ? q : a.sentinel;
                 row_n[u] = a.idx[qe];
                 rv_n[u] = a.val[qe];
+#if MFX_ALS_BLOCK
+                sv_n[u] = a.score[qe];
+#endif
             }
         };
         auto load_rows = [&]() {
@@ -776,6 +817,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(als_waves(NT
                     av_n[u][I] = a.X[(size_t) (in ? row_n[u] : zrow) * k + (in ? col : 0u)];
                 }
                 rv_c[u] = rv_n[u];
+#if MFX_ALS_BLOCK
+                sv_c[u] = sv_n[u];
+#endif
             }
         };
         load_idx(it.lo);
@@ -783,6 +827,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(als_waves(NT
         load_idx(it.lo + 2 * U);
         for (uint32_t q0 = it.lo; q0 < it.hi; q0 += 2 * U) {
             float av[U][NT], rv[U];
+#if MFX_ALS_BLOCK
+            float sv[U];
+    #pragma unroll
+            for (int u = 0; u < U; ++u) sv[u] = sv_c[u];
+#endif
     #pragma unroll
             for (int u = 0; u < U; ++u) {
                 rv[u] = rv_c[u];
@@ -794,7 +843,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(als_waves(NT
     #pragma unroll
             for (int u = 0; u < U; ++u) {
                 if constexpr (kImplicit) {
+#if MFX_ALS_BLOCK
+                    ials_rows<NT>(av[u], rv[u], a.alpha, bacc, acc, sv[u]);
+#else
                     ials_rows<NT>(av[u], rv[u], a.alpha, bacc, acc);
+#endif
                     continue;
                 }
                 int ti = 0;
@@ -945,6 +998,9 @@ struct Gram16Regs {
     uint32_t ix[D][kU16];  // gathered row indices           (stage 0: loaded D steps ahead of their MFMAs)
     f32x4 av[D][kU16];     // gathered factor-row quarters   (stage 1: D - 1 steps ahead)
     float rv[D][kU16];     // ratings                        (stage 1)
+#if MFX_ALS_BLOCK
+    float sv[D][kU16];     // scores of the stored pairs     (stage 1)
+#endif
     f32x4 acc[kTiles16];
     f32x2 bacc[2];         // rhs partial sums of column sets (0, 1) and (2, 3)
 };
@@ -963,7 +1019,7 @@ __device__ __forceinline__ void g16_load_idx(Gram16Regs<D>& r, const uint32_t* _
 template <int D, int S>
 __device__ __forceinline__ void g16_load_rows(Gram16Regs<D>& r, const char* __restrict__ Xb, const float* __restrict__ vbase,
                                               uint32_t s, uint32_t g, uint32_t len, bool col_ok, uint32_t rowbytes,
-                                              uint32_t lane_off, uint32_t zero_off) {
+                                              uint32_t lane_off, uint32_t zero_off, const float* __restrict__ sbase = nullptr) {
 #pragma unroll
     for (int u = 0; u < kU16; ++u) {
         const bool ok = col_ok && s * kRows16 + 4 * u + g < len;
@@ -974,6 +1030,9 @@ __device__ __forceinline__ void g16_load_rows(Gram16Regs<D>& r, const char* __re
         const uint32_t off = ok ? __umul24(ix, rowbytes) + lane_off : zero_off;  // x_rows < 2^24, table < 4 GB (launch_half)
         r.av[S][u] = *reinterpret_cast<const f32x4*>(Xb + off);
         r.rv[S][u] = vbase[s * kRows16 + 4 * u + g];
+#if MFX_ALS_BLOCK
+        r.sv[S][u] = sbase[s * kRows16 + 4 * u + g];
+#endif
     }
 }
 template <int D, int S>
@@ -982,7 +1041,11 @@ __device__ __forceinline__ void g16_mfma(Gram16Regs<D>& r, float alpha) {
     for (int u = 0; u < kU16; ++u) {
         if constexpr (kImplicit) {  // the same with the weights of ials_weights: rhs from the unscaled row, then the MFMAs
             float rw, sw;
+#if MFX_ALS_BLOCK
+            ials_weights(r.rv[S][u], alpha, rw, sw, r.sv[S][u]);
+#else
             ials_weights(r.rv[S][u], alpha, rw, sw);
+#endif
             const float hi = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, rw), 0xE4, 0xF, 0xF, false));
             const f32x2 rr = {rw, hi};
             r.bacc[0] = fma2(rr, r.av[S][u].lo, r.bacc[0]);
@@ -1020,6 +1083,9 @@ struct Gram16Ctx {  // loop-invariant operands of the stages
     uint32_t g, len, rowbytes, lane_off, zero_off;
     bool col_ok;
     float alpha;  // (k_ials_gram16 only)
+#if MFX_ALS_BLOCK
+    const float* sbase;
+#endif
 };
 // Steps s, s + 1, ... on sets U, U + 1, ... D - 1: MFMAs of step s on set U, the factor rows of step s + D - 1 into the
 // set the previous step has just released, the indices of step s + D into this step's own (already consumed) slots.
@@ -1028,7 +1094,11 @@ struct Gram16Ctx {  // loop-invariant operands of the stages
 template <int D, int U>
 __device__ __forceinline__ bool g16_steps(Gram16Regs<D>& r, const Gram16Ctx& c, uint32_t& s) {
     if constexpr (U < D) {
+#if MFX_ALS_BLOCK
+        g16_load_rows<D, (U + D - 1) % D>(r, c.Xb, c.vbase, s + D - 1, c.g, c.len, c.col_ok, c.rowbytes, c.lane_off, c.zero_off, c.sbase);
+#else
         g16_load_rows<D, (U + D - 1) % D>(r, c.Xb, c.vbase, s + D - 1, c.g, c.len, c.col_ok, c.rowbytes, c.lane_off, c.zero_off);
+#endif
         g16_load_idx<D, U>(r, c.ibase, s + D, c.g);
         __builtin_amdgcn_sched_barrier(0);
         g16_mfma<D, U>(r, c.alpha);
@@ -1045,7 +1115,11 @@ __device__ __forceinline__ void g16_prologue(Gram16Regs<D>& r, const Gram16Ctx& 
         g16_load_idx<D, U>(r, c.ibase, U, c.g);
         g16_prologue<D, U + 1>(r, c);
         if constexpr (U + 1 < D)  // (after ALL index loads are in flight)
+#if MFX_ALS_BLOCK
+            g16_load_rows<D, U>(r, c.Xb, c.vbase, U, c.g, c.len, c.col_ok, c.rowbytes, c.lane_off, c.zero_off, c.sbase);
+#else
             g16_load_rows<D, U>(r, c.Xb, c.vbase, U, c.g, c.len, c.col_ok, c.rowbytes, c.lane_off, c.zero_off);
+#endif
     }
 }
 
@@ -1083,6 +1157,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES
     cx.len = it.hi - it.lo;
     cx.ibase = a.idx + it.lo;
     cx.vbase = a.val + it.lo;
+#if MFX_ALS_BLOCK
+    cx.sbase = a.score + it.lo;
+#endif
     cx.Xb = reinterpret_cast<const char*>(a.X);
     cx.rowbytes = 4 * k;
     cx.col_ok = 4 * c < k;                 // lanes past column k gather the zero row
@@ -1212,7 +1289,19 @@ static_assert(kAlsPad >= 16 * ((MFX_G16_DL > MFX_G16_DS ? MFX_G16_DL : MFX_G16_D
 
 }  // namespace
 
-#if MFX_ALS_IMPLICIT
+static_assert(kAlsPad == kAlsEntryPad, "als_solver.hpp states the padding of the entry arrays");
+
+#if MFX_ALS_BLOCK
+int ialsb_step_launch(const AlsHalf& h, const float* Xb, uint32_t x_rows, float* Z, uint32_t d, const float* Gbb, float alpha,
+                      const float* score, const float* P, float* ws, uint32_t* spd_fail, hipStream_t st) {
+    AlsArgs a{};
+    a.items = h.items.get(); a.reduces = h.reduces.get(); a.idx = h.idx.get(); a.val = h.val.get();
+    a.X = Xb; a.x_rows = x_rows; a.sentinel = (uint32_t) h.nnz; a.Y = Z; a.k = d; a.ws = ws; a.spd_fail = spd_fail;
+    a.lambda = 0.f;  // lambda is on G's diagonal already
+    a.alpha = alpha; a.G = Gbb; a.score = score; a.P = P;
+    return launch_half(a, h.nitems, h.nreduces, h.nnz, st);
+}
+#elif MFX_ALS_IMPLICIT
 int ials_half_launch(const AlsHalf& h, const float* X, uint32_t x_rows, float* Y, uint32_t k, const float* G, float alpha,
                      float* ws, uint32_t* spd_fail, hipStream_t st) {
     AlsArgs a{};
@@ -1316,6 +1405,23 @@ int AlsSolver::create_implicit(AlsSolver** out, const mfx_csx* R, const mfx_para
     return MFX_OK;
 }
 
+int AlsSolver::create_block(AlsSolver** out, const mfx_csx* R, const mfx_params* p, float alpha, int32_t block, mfx_memspace space) {
+    MFX_REQUIRE(out && R && p, "mfx_ials_block_create: null argument");
+    MFX_REQUIRE(std::isfinite(alpha) && alpha >= 0.f, "mfx_ials_block_create: alpha = %g (finite and >= 0 required)", (double) alpha);
+    MFX_REQUIRE(p->k >= 1 && p->k <= kIalsBlockMaxRank, "implicit ALS by block sweeps: rank k = %u not supported (1 <= k <= %u)", p->k,
+                kIalsBlockMaxRank);
+    MFX_REQUIRE(block >= 0 && block <= (int32_t) kIalsBlockMaxBlock, "implicit ALS by block sweeps: block = %d (0 = chosen from k, else 1 <= block <= %u)",
+                block, kIalsBlockMaxBlock);
+    MFX_REQUIRE(p->schedule == 1, "implicit ALS by block sweeps: schedule must be 1 (there is no as-written mode)");
+    std::unique_ptr<AlsSolver> s(new AlsSolver());
+    s->implicit_ = true;
+    s->alpha_ = alpha;
+    s->block_ = std::min<uint32_t>(block ? (uint32_t) block : ialsb_default_block(p->k), p->k);
+    MFX_TRY(s->init(R, nullptr, p, space, nullptr));
+    *out = s.release();
+    return MFX_OK;
+}
+
 AlsSolver::~AlsSolver() {
     (void) hipSetDevice(device_);
     for (hipEvent_t& e : ev_)
@@ -1350,7 +1456,7 @@ int AlsSolver::init(const mfx_csx* R, const mfx_coo* T, const mfx_params* p, mfx
     MFX_REQUIRE(R->rows > 0 && R->cols > 0 && R->nnz >= 0, "bad matrix shape");
     MFX_REQUIRE(R->rows < (int64_t) 0xFFFFFFFFll && R->cols < (int64_t) 0xFFFFFFFFll &&
                     R->nnz < (int64_t) 0xFFFF0000ll, "matrix exceeds 32-bit index range");
-    MFX_REQUIRE(p->k >= 1 && p->k <= 128, "ALS: rank k = %u not supported (1 <= k <= 128)", p->k);
+    MFX_REQUIRE(p->k >= 1 && p->k <= (block_ ? kIalsBlockMaxRank : 128u), "ALS: rank k = %u not supported (1 <= k <= 128)", p->k);
     MFX_REQUIRE(R->csc_col_ptr && R->csr_row_ptr, "null CSR/CSC pointer array");
     p_ = *p;
     device_ = p->device;
@@ -1381,7 +1487,7 @@ int AlsSolver::init(const mfx_csx* R, const mfx_coo* T, const mfx_params* p, mfx
     // one extra, all-zero row each: the Gramian kernel gathers it for positions past a segment's end
     MFX_TRY(W_.alloc_zero(((size_t) m_ + 1) * k_, st_));
     MFX_TRY(H_.alloc_zero(((size_t) n_ + 1) * k_, st_));
-    MFX_TRY(ws_.alloc(std::max<size_t>(1, als_ws_floats(std::max(rows_.nslots, cols_.nslots), k_))));
+    MFX_TRY(ws_.alloc(block_ ? 1 : std::max<size_t>(1, als_ws_floats(std::max(rows_.nslots, cols_.nslots), k_))));
     MFX_TRY(spd_fail_.alloc_zero(1, st_));
     if (std::getenv("MFX_ALS_PHASES")) { MFX_TRY(phases_.alloc_zero((size_t) kPhaseCopies * 8, st_)); }
     nnz_test_ = T ? T->nnz : 0;
@@ -1399,9 +1505,15 @@ int AlsSolver::init(const mfx_csx* R, const mfx_coo* T, const mfx_params* p, mfx
     if (implicit_) {
         MFX_TRY(ials_check_values(rows_.val.get(), rows_.nnz, alpha_, "implicit ALS: R (CSR) value", st_));
         MFX_TRY(ials_check_values(cols_.val.get(), cols_.nnz, alpha_, "implicit ALS: R (CSC) value", st_));
-        MFX_TRY(G_.alloc((size_t) k_ * k_));
-        MFX_TRY(gpart_.alloc(ials_base_ws_floats(std::max(m_, n_), k_)));
-        MFX_TRY(loss_ws_.alloc(ials_loss_ws_doubles(k_)));
+        if (block_) {
+            MFX_REQUIRE(rows_.nnz == cols_.nnz, "implicit ALS by block sweeps: the two orientations hold %llu and %llu entries",
+                        (unsigned long long) rows_.nnz, (unsigned long long) cols_.nnz);
+            MFX_TRY(bs_.alloc(k_, block_, std::max(m_, n_), std::max(m_, n_), rows_.nnz, std::max(rows_.nslots, cols_.nslots), st_));
+        } else {
+            MFX_TRY(G_.alloc((size_t) k_ * k_));
+            MFX_TRY(gpart_.alloc(ials_base_ws_floats(std::max(m_, n_), k_)));
+            MFX_TRY(loss_ws_.alloc(ials_loss_ws_doubles(k_)));  // (block sweeps: on the first loss(), up to 1 GB at k = 1024)
+        }
         MFX_TRY(loss_.alloc_zero(1, st_));
     }
     MFX_HIP(hipStreamSynchronize(st_));
@@ -1457,6 +1569,7 @@ int AlsSolver::set_factors(const float* W, const float* H, mfx_memspace space) {
     MFX_REQUIRE(H, "mfx_als_set_factors: H is required");
     MFX_TRY(use_device(device_));
     if (W) MFX_TRY(W_.upload(W, (size_t) m_ * k_, space, st_));
+    else if (block_) MFX_HIP(hipMemsetAsync(W_.get(), 0, sizeof(float) * (size_t) m_ * k_, st_));  // W is the warm start of the first W-half
     MFX_TRY(H_.upload(H, (size_t) n_ * k_, space, st_));
     MFX_HIP(hipStreamSynchronize(st_));
     factors_set_ = true;
@@ -1471,7 +1584,11 @@ int AlsSolver::iterate(int n_iter, int with_rmse, mfx_iter_report* reports) {
     for (int it = 0; it < n_iter; ++it) {
         MFX_HIP(hipMemsetAsync(spd_fail_.get(), 0, sizeof(uint32_t), st_));
         MFX_HIP(hipEventRecord(ev_[0], st_));
-        if (implicit_) {  // (ev_[4]: the base Gramian of H is done)
+        if (block_) {
+            MFX_TRY(ialsb_gramian(bs_, H_.get(), n_, p_.lambda, st_));
+            MFX_HIP(hipEventRecord(ev_[4], st_));
+            MFX_TRY(ialsb_half_launch(bs_, rows_, H_.get(), n_, W_.get(), alpha_, spd_fail_.get(), st_));
+        } else if (implicit_) {  // (ev_[4]: the base Gramian of H is done)
             MFX_TRY(ials_base_gramian(H_.get(), n_, k_, p_.lambda, gpart_.get(), G_.get(), st_));
             MFX_HIP(hipEventRecord(ev_[4], st_));
             MFX_TRY(ials_half_launch(rows_, H_.get(), n_, W_.get(), k_, G_.get(), alpha_, ws_.get(), spd_fail_.get(), st_));
@@ -1483,7 +1600,11 @@ int AlsSolver::iterate(int n_iter, int with_rmse, mfx_iter_report* reports) {
         if (comm_) MFX_TRY(exchange(W_.get(), row_bounds_));
         MFX_HIP(hipEventRecord(ev_[1], st_));
         if (phases_.size()) MFX_TRY(print_phases("user half (W over H)"));
-        if (implicit_) {  // (ev_[5]: the base Gramian of W is done)
+        if (block_) {
+            MFX_TRY(ialsb_gramian(bs_, W_.get(), m_, p_.lambda, st_));
+            MFX_HIP(hipEventRecord(ev_[5], st_));
+            MFX_TRY(ialsb_half_launch(bs_, cols_, W_.get(), m_, H_.get(), alpha_, spd_fail_.get(), st_));
+        } else if (implicit_) {  // (ev_[5]: the base Gramian of W is done)
             MFX_TRY(ials_base_gramian(W_.get(), m_, k_, p_.lambda, gpart_.get(), G_.get(), st_));
             MFX_HIP(hipEventRecord(ev_[5], st_));
             MFX_TRY(ials_half_launch(cols_, W_.get(), m_, H_.get(), k_, G_.get(), alpha_, ws_.get(), spd_fail_.get(), st_));
@@ -1555,10 +1676,11 @@ int AlsSolver::get_factors(float* W, float* H, mfx_memspace space) {
 int AlsSolver::kernel_times(int cap, const char** names, double* seconds, int64_t* launches) {
     static const char* nm[2] = {"als_half_rows(W over H)", "als_half_cols(H over W)"};
     static const char* nm_impl[4] = {"ials_half_rows(W over H)", "ials_half_cols(H over W)", "ials_base_gram(H)", "ials_base_gram(W)"};
+    static const char* nm_block[4] = {"ialsb_half_rows(W over H)", "ialsb_half_cols(H over W)", "ialsb_base_gram(H)", "ialsb_base_gram(W)"};
     int n = 0;
     for (int i = 0; i < 4 && n < cap; ++i) {
         if (!n_half_[i]) continue;
-        if (names) names[n] = implicit_ ? nm_impl[i] : nm[i];
+        if (names) names[n] = block_ ? nm_block[i] : implicit_ ? nm_impl[i] : nm[i];
         if (seconds) seconds[n] = t_half_[i];
         if (launches) launches[n] = n_half_[i];
         ++n;
@@ -1571,6 +1693,7 @@ int AlsSolver::loss(double* out) {
     MFX_REQUIRE(implicit_, "mfx_ials_loss: not an implicit-feedback ALS handle (mfx_ials_create)");
     MFX_REQUIRE(factors_set_, "mfx_ials_loss: call mfx_als_set_factors first");
     MFX_TRY(use_device(device_));
+    if (!loss_ws_.size()) MFX_TRY(loss_ws_.alloc(ials_loss_ws_doubles(k_)));
     MFX_TRY(ials_loss_launch(rows_, W_.get(), m_, H_.get(), n_, k_, p_.lambda, alpha_, loss_ws_.get(), loss_.get(), st_));
     MFX_HIP(hipMemcpyAsync(out, loss_.get(), sizeof(double), hipMemcpyDeviceToHost, st_));
     MFX_HIP(hipStreamSynchronize(st_));

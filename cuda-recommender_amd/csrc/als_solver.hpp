@@ -22,6 +22,7 @@ struct AlsReduce {    // a segment whose Gramian was split over `nslots` consecu
 };
 
 constexpr uint32_t kAlsChunk = 2048;  // gathered rows per wavefront before a segment is split (AlsHalf::build's `chunk`)
+constexpr uint32_t kAlsEntryPad = 128;  // entries behind AlsHalf::idx / val that the Gramian kernels may read (and ignore)
 
 // One orientation (rows over H, or columns over W).
 struct AlsHalf {
@@ -37,12 +38,41 @@ struct AlsHalf {
               mfx_memspace space, uint32_t chunk, hipStream_t st);
 };
 
+// Implicit ALS by block subspace sweeps (ials_block.hip): what one half-sweep at rank k <= 1024 with blocks of d <= 128
+// coordinates keeps on the device besides the factors.  One set serves both orientations.
+struct IalsBlock {
+    uint32_t k = 0, d = 0;
+    DevBuf<float> G, gpart;  // base Gramian [k][k] of the fixed side, its per-partition tile partials
+    DevBuf<float> Xb;        // the fixed side block-major: block b is [rows + 1][width of b], the last row all zeros
+    DevBuf<float> Gbb;       // the diagonal blocks of G, block b contiguous [width][width] at b d d
+    DevBuf<float> P, Z;      // [nseg][width]: G[block, :] y and the step of the current block
+    DevBuf<float> score;     // [nnz + kAlsEntryPad]: <x_j, y> of every stored pair in the orientation of the half
+    DevBuf<float> ws;        // partial slots of split segments (als_ws_floats at rank d)
+    int alloc(uint32_t k, uint32_t d, uint32_t max_rows_x, uint32_t max_seg, uint64_t nnz, uint32_t nslots, hipStream_t st);
+};
+constexpr uint32_t kIalsBlockMaxRank = 1024, kIalsBlockMaxBlock = 128;
+inline uint32_t ialsb_default_block(uint32_t k) { return k < 64 ? k : 64; }  // mfx_ials_block_create, block = 0
+// G = X^T X + lambda I into b.G, any k <= 1024 (32 x 32 MFMA tiles over row partitions, summed in partition order)
+int ialsb_gramian(IalsBlock& b, const float* X, uint32_t rows, float lambda, hipStream_t st);
+// One half-sweep in place on Y [h.nseg][k] (the warm start) over X [x_rows][k] with b.G = X^T X + lambda I: the scores,
+// then for every block in ascending order G[block, :] y, the block systems (k_ialsb_*: ialsb_step_launch) and the update
+// of y and of the scores
+int ialsb_half_launch(IalsBlock& b, const AlsHalf& h, const float* X, uint32_t x_rows, float* Y, float alpha, uint32_t* spd_fail,
+                      hipStream_t st);
+// ials_block_step.hip (als_solver.hip compiled with MFX_ALS_BLOCK): the systems of one block, Z [nseg][d] = the steps
+int ialsb_step_launch(const AlsHalf& h, const float* Xb, uint32_t x_rows, float* Z, uint32_t d, const float* Gbb, float alpha,
+                      const float* score, const float* P, float* ws, uint32_t* spd_fail, hipStream_t st);
+int ials_block_half_op(int64_t nseg, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val, int64_t nrows_x,
+                       const float* X, const float* Y_in, float* Y_out, int64_t k, int32_t block, float lambda, float alpha, int device);
+
 class AlsSolver {
 public:
     static int create(AlsSolver** out, const mfx_csx* R, const mfx_coo* T, const mfx_params* p,
                       mfx_memspace space, const mfx_als_shard* shard = nullptr);
     // implicit feedback (mfx_ials_create): R holds interaction strengths r >= 0, confidence 1 + alpha r
     static int create_implicit(AlsSolver** out, const mfx_csx* R, const mfx_params* p, float alpha, mfx_memspace space);
+    // implicit feedback by block subspace sweeps (mfx_ials_block_create): k <= 1024, block = 0 or 1..128
+    static int create_block(AlsSolver** out, const mfx_csx* R, const mfx_params* p, float alpha, int32_t block, mfx_memspace space);
     bool implicit() const { return implicit_; }
     int loss(double* out);  // implicit only: the objective at the current factors (ials.hip)
     ~AlsSolver();
@@ -86,6 +116,8 @@ private:
     float alpha_ = 0.f;
     DevBuf<float> G_, gpart_;        // base Gramian [k][k] of the fixed side, its per-partition partials
     DevBuf<double> loss_ws_, loss_;  // fp64 Gramians + entry partials of the objective, the objective
+    uint32_t block_ = 0;             // > 0: block subspace sweeps with blocks of block_ coordinates
+    IalsBlock bs_;
 };
 
 // Launches one half-sweep: Y[seg] = argmin over segment `seg` given factor rows X[x_rows + 1][k],

@@ -251,6 +251,32 @@ int mfx_ials_create(mfx_als_t* out, const mfx_csx* R, const mfx_params* p, float
         return MFX_OK;
     });
 }
+int mfx_ials_block_create(mfx_als_t* out, const mfx_csx* R, const mfx_params* p, float alpha, int32_t block, mfx_memspace space) {
+    return guarded("mfx_ials_block_create", [&]() -> int {
+        MFX_REQUIRE(out, "mfx_ials_block_create: out is NULL");
+        *out = nullptr;
+        AlsSolver* s = nullptr;
+        MFX_TRY(AlsSolver::create_block(&s, R, p, alpha, block, space));  // (argument checks before the device is touched)
+        *out = new mfx_als_s{s};
+        return MFX_OK;
+    });
+}
+int mfx_ials_block_half(int64_t nseg, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val,
+                        int64_t nrows_x, const float* X, const float* Y_in, float* Y_out, int64_t k, int32_t block,
+                        float lambda, float alpha, int device) {
+    return guarded("mfx_ials_block_half", [&]() -> int {
+        MFX_REQUIRE(nseg > 0 && nnz >= 0 && ptr && X && Y_out && nrows_x > 0, "mfx_ials_block_half: bad argument");
+        MFX_REQUIRE(nnz == 0 || (idx && val), "mfx_ials_block_half: null idx / val with nnz > 0");
+        MFX_REQUIRE(k >= 1 && k <= (int64_t) kIalsBlockMaxRank, "implicit ALS by block sweeps: rank k = %lld not supported (1 <= k <= %u)",
+                    (long long) k, kIalsBlockMaxRank);
+        MFX_REQUIRE(block >= 0 && block <= (int32_t) kIalsBlockMaxBlock,
+                    "implicit ALS by block sweeps: block = %d (0 = chosen from k, else 1 <= block <= %u)", block, kIalsBlockMaxBlock);
+        MFX_REQUIRE(std::isfinite(alpha) && alpha >= 0.f, "mfx_ials_block_half: alpha = %g (finite and >= 0 required)", (double) alpha);
+        MFX_REQUIRE(nseg < (int64_t) 0xFFFFFFFFll && nrows_x < (int64_t) 0xFFFFFFFFll && nnz < (int64_t) 0xFFFF0000ll,
+                    "mfx_ials_block_half: sizes exceed the 32-bit index range");
+        return ials_block_half_op(nseg, nnz, ptr, idx, val, nrows_x, X, Y_in, Y_out, k, block, lambda, alpha, device);
+    });
+}
 int mfx_ials_loss(mfx_als_t s, double* loss) {
     return guarded("mfx_ials_loss", [&]() -> int {
         MFX_REQUIRE(s && s->impl && loss, "mfx_ials_loss: null argument");

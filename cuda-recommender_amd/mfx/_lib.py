@@ -101,6 +101,10 @@ SIGNATURES = {
     "mfx_ials_loss": (C.c_int, [C.c_void_p, f64p]),
     "mfx_ials_half": (C.c_int, [C.c_int64, C.c_int64, u32p, u32p, f32p, C.c_int64, f32p, f32p, C.c_int64,
                                 C.c_float, C.c_float, C.c_int]),
+    "mfx_ials_block_create": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(mfx_csx), C.POINTER(mfx_params), C.c_float, C.c_int32,
+                                        C.c_int]),
+    "mfx_ials_block_half": (C.c_int, [C.c_int64, C.c_int64, u32p, u32p, f32p, C.c_int64, f32p, f32p, f32p, C.c_int64, C.c_int32,
+                                      C.c_float, C.c_float, C.c_int]),
     "mfx_comm_unique_id": (C.c_int, [C.c_void_p]),
     "mfx_comm_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "mfx_comm_create_local": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int]),

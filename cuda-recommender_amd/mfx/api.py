@@ -502,9 +502,13 @@ class AlsSolver:
 class ImplicitAlsSolver:
     """Resident implicit-feedback ALS (mfx_ials_create): R holds interaction strengths r >= 0, every (user, item)
     pair is in the loss with preference p = (r > 0) and confidence 1 + alpha r.  Factors use the ALS layout,
-    W [rows][k] and H [cols][k].  device_arrays: the matrix as a dict of device tensors (mfx.synth_torch)."""
+    W [rows][k] and H [cols][k].  device_arrays: the matrix as a dict of device tensors (mfx.synth_torch).
+    block=None: the exact solver (k <= 128).  block=d (0 = chosen from k): block subspace sweeps over d coordinates at
+    a time (mfx_ials_block_create, k <= 1024) -- a different method; there W, when given to set_factors, is the warm
+    start of the first half-sweep."""
 
-    def __init__(self, R: Optional[RatingData], parameters: parameter, alpha: float, device_arrays: Optional[dict] = None):
+    def __init__(self, R: Optional[RatingData], parameters: parameter, alpha: float, device_arrays: Optional[dict] = None,
+                 block: Optional[int] = None):
         self.handle = C.c_void_p()
         cp = parameters.to_c()
         if device_arrays is not None:
@@ -517,7 +521,10 @@ class ImplicitAlsSolver:
         else:
             self.rows, self.cols, self.k = R.rows, R.cols, int(parameters.k)
             csx, space = _csx(R), L.MFX_HOST
-        L.check(L.lib().mfx_ials_create(C.byref(self.handle), C.byref(csx), C.byref(cp), float(alpha), space))
+        if block is None:
+            L.check(L.lib().mfx_ials_create(C.byref(self.handle), C.byref(csx), C.byref(cp), float(alpha), space))
+        else:
+            L.check(L.lib().mfx_ials_block_create(C.byref(self.handle), C.byref(csx), C.byref(cp), float(alpha), int(block), space))
 
     def set_factors(self, H, W=None):
         _f32c(H, (self.cols, self.k))
@@ -617,6 +624,17 @@ def ials_half(ptr, idx, val, X, k: int, lam: float, alpha: float, device: int = 
     Y = np.empty((nseg, k), np.float32)
     L.check(L.lib().mfx_ials_half(nseg, idx.shape[0], _u32(ptr), _u32(idx), _f32(val), X.shape[0], _f32(X), _f32(Y),
                                   k, lam, alpha, device))
+    return Y
+
+
+def ials_block_half(ptr, idx, val, X, k: int, lam: float, alpha: float, block: int, Y_in=None, device: int = 0) -> np.ndarray:
+    """One half-sweep of implicit ALS by block subspace sweeps (mfx_ials_block_half) from Y_in [nseg][k] (None = zeros)."""
+    nseg = ptr.shape[0] - 1
+    Y = np.empty((nseg, k), np.float32)
+    if Y_in is not None:
+        _f32c(Y_in, (nseg, k))
+    L.check(L.lib().mfx_ials_block_half(nseg, idx.shape[0], _u32(ptr), _u32(idx), _f32(val), X.shape[0], _f32(X),
+                                        _f32(Y_in) if Y_in is not None else None, _f32(Y), k, int(block), lam, alpha, device))
     return Y
 
 

@@ -242,6 +242,30 @@ int mfx_ials_loss(mfx_als_t s, double* loss);
 int mfx_ials_half(int64_t nseg, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val,
                   int64_t nrows_x, const float* X, float* Y, int64_t k, float lambda, float alpha, int device);
 
+/* Implicit ALS by block subspace sweeps ("iALS++", Rendle et al. 2021): the same objective at ranks k up to 1024 (the
+ * range mfx_rec_query scores).  The solver keeps the score s_j = <x_j, y> of every stored pair and a half-sweep makes,
+ * for every segment from its CURRENT row y (warm start), one pass over the blocks pi_b = [b d, min(k, (b + 1) d)),
+ * b = 0, 1, ... of d = `block` coordinates; one step is the exact minimiser of the segment's objective over y_pi:
+ *     g = sum_{r_j > 0} (w_j s_j - (1 + w_j)) x_jpi + G[pi, :] y,     A = sum_{r_j > 0} w_j x_jpi x_jpi^T + G[pi, pi],
+ *     Delta = A^-1 g,     y_pi <- y_pi - Delta,     s_j <- s_j - <x_jpi, Delta>          (G = X^T X + lambda I)
+ * (an empty segment gives y = 0; an explicit zero is no entry).  With a single block (d >= k) from y = 0 a half-sweep
+ * solves the system of mfx_ials_half; otherwise it is a different method with different iterates, whose loss still
+ * falls monotonically.  Cost per stored pair k d instead of k^2.
+ * block: 0 = chosen from k as min(k, 64), else 1 <= block <= 128 (values above k act as k).  Returns an mfx_als_t:
+ * mfx_als_set_factors / _iterate / _get_factors / _kernel_times / _destroy and mfx_ials_loss work on it.
+ * mfx_als_set_factors: H required; W NULL = zeros (W is the warm start of the first W-half -- unlike the exact solvers
+ * it IS read).  One iterate step = W-half over H, then H-half over the new W.  Memory on the device besides the matrix
+ * and the factors: one float per stored pair, a block-major copy of the larger factor, k^2 floats.  Fold-in
+ * (mfx_rec_fold_in_setup, k <= 128) does not cover models of k > 128 trained here.  Single GPU.
+ * MFX_ERR_INVALID without touching the device: k outside 1..1024 ("rank"), block outside 0..128 ("block"), alpha < 0 /
+ * NaN / Inf ("alpha"), schedule != 1 ("schedule"), a null argument. */
+int mfx_ials_block_create(mfx_als_t* out, const mfx_csx* R, const mfx_params* p, float alpha, int32_t block,
+                          mfx_memspace space);
+/* Single operator for tests: one half-sweep from Y_in [nseg][k] (NULL = zeros) to Y_out [nseg][k], host pointers. */
+int mfx_ials_block_half(int64_t nseg, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val,
+                        int64_t nrows_x, const float* X, const float* Y_in, float* Y_out, int64_t k, int32_t block,
+                        float lambda, float alpha, int device);
+
 /* ------------------------------------------------------------------------------------
  * Top-N recommendation: a resident handle over trained factors that returns, for each
  * requested user, the n_top highest-scoring items the user must not be excluded from.

@@ -6,7 +6,13 @@ the two base Gramians (X^T X + lambda I), explicit ALS ms per iteration on the s
 of an iteration and its fraction of the 157.3 TF fp32 MFMA peak, and the objective (mfx_ials_loss) after each
 iteration.
 
-    python tools/ials_bench.py [--ks 64,128] [--iters 5] [--alpha 1.0] [--lam 0.05]
+--block k:d,k:d,... adds runs of the block subspace sweeps (mfx_ials_block_create: rank k in blocks of d coordinates,
+the only implicit solver above k = 128) after the exact ones, from the same H0 (W = 0) on the same matrix in the same
+process: ms per iteration, the loss after every iteration (a different method: read loss against time, not time
+alone), the flop and the gathered bytes of an iteration from the shapes.  --again repeats the exact runs at the end
+(the spread of the yardstick inside the job).
+
+    python tools/ials_bench.py [--ks 64,128] [--block 128:64,256:64] [--again] [--iters 5] [--alpha 1.0] [--lam 0.05]
 """
 import argparse
 import json
@@ -28,9 +34,47 @@ def flop_per_iteration(rows, cols, nnz, k):
     return 2.0 * (nnz * k * (k + 1) + 2.0 * nnz * k) + (rows + cols) * k * (k + 1)
 
 
+def block_counts(rows, cols, nnz, k, d):
+    """(flop, gathered bytes) of one block-sweep iteration from the shapes: per stored pair and half the symmetric
+    block Gramians k (d + 1), the rhs 2 k, the score update 2 k and the scores 2 k; G[block, :] y for every segment
+    2 k^2; the two base Gramians.  Gathered: per stored pair and half three passes over a full row (scores, block
+    systems, score updates) of k floats."""
+    flop = 2.0 * nnz * (k * (d + 1) + 6.0 * k) + (rows + cols) * (2.0 * k * k + k * (k + 1))
+    return flop, 2.0 * 3.0 * nnz * k * 4.0
+
+
+def run_block(mfx, d_arrays, rows, cols, nnz, k, block, a):
+    p = mfx.parameter()
+    p.k, p.lambda_, p.log = k, a.lam, 1 if a.verbose else 0  # (log: the solver reports failed pivots on stdout)
+    H0 = mfx.initial_col(cols, k)
+    s = mfx.ImplicitAlsSolver(None, p, a.alpha, device_arrays=d_arrays, block=block)
+    s.set_factors(H0)
+    losses = []
+    for _ in range(a.iters):  # the loss curve from H0 (these iterations also warm up)
+        s.iterate(1)
+        losses.append(s.loss())
+    s.kernel_times()
+    s.set_factors(H0)  # the same five iterations again, warmed up: the times
+    ms = [r.update_time * 1e3 for r in s.iterate(a.iters)]
+    kt = s.kernel_times()
+    s.close()
+    per = {name: t * 1e3 / n for name, (t, n) in kt.items()}
+    med = float(np.median(ms))
+    fl, by = block_counts(rows, cols, nnz, k, block)
+    return {"k": k, "block": block, "ms_per_iteration": round(med, 3), "ms_min": round(min(ms), 3), "ms_max": round(max(ms), 3),
+            "ms_user_half": round(per["ialsb_half_rows(W over H)"], 3), "ms_item_half": round(per["ialsb_half_cols(H over W)"], 3),
+            "ms_base_gram_H": round(per["ialsb_base_gram(H)"], 3), "ms_base_gram_W": round(per["ialsb_base_gram(W)"], 3),
+            "flop_per_iteration": fl, "fraction_of_fp32_mfma_peak": round(fl / (med * 1e-3) / (PEAK_TF * 1e12), 4),
+            "gathered_bytes_per_iteration": by, "gathered_tb_per_s": round(by / (med * 1e-3) / 1e12, 3),
+            "loss_per_iteration": losses}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--ks", default="64,128")
+    ap.add_argument("--block", default="", help="k:d,k:d,... runs of the block subspace sweeps")
+    ap.add_argument("--again", action="store_true", help="repeat the exact runs after the block runs")
+    ap.add_argument("--verbose", action="store_true", help="block runs: the solver's own log lines (failed pivots) before the JSON line")
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--alpha", type=float, default=1.0)
     ap.add_argument("--lam", type=float, default=0.05)
@@ -43,7 +87,14 @@ def main():
     rows, cols, nnz = int(d["rows"]), int(d["cols"]), int(d["csr_val"].numel())
     out = {"workload": f"{rows}x{cols} nnz={nnz}", "alpha": a.alpha, "lambda": a.lam, "iters": a.iters,
            "library": os.path.relpath(mfx.LIB_PATH, ROOT), "runs": []}
-    for k in [int(x) for x in a.ks.split(",")]:
+    ks = [int(x) for x in a.ks.split(",") if x]
+    blocks = [tuple(int(v) for v in x.split(":")) for x in a.block.split(",") if x]
+    plan = [("exact", k, None) for k in ks] + [("block", k, b) for k, b in blocks] + ([("exact", k, None) for k in ks] if a.again else [])
+    for kind, k, block in plan:
+        if kind == "block":
+            out["runs"].append(run_block(mfx, d, rows, cols, nnz, k, block, a))
+            torch.cuda.synchronize()
+            continue
         p = mfx.parameter()
         p.k, p.lambda_ = k, a.lam
         H0 = mfx.initial_col(cols, k)
