@@ -274,11 +274,24 @@ template <int MODE> constexpr int flat_min_waves(int block) { return MODE == FM_
 // Per span nothing differs from the one-chunk form: same start, same metadata words, same owner rule for part / carry, the
 // same sums in the same order.  (Tried and dropped, DESIGN.md section 10.0: the window's loads issued during the span and
 // held in registers; streams two tiles ahead.)
+// The read-only passes (ROP below) walk their range differently, because they must stay at 64 VGPRs for their second
+// workgroup per CU and the two-window form keeps its look-ahead in registers across the tile loop (25 / 35 spilled VGPRs,
+// reloaded inside the loop).  They keep ONE window and look no further ahead than the first tile of the wave's span in the
+// next chunk: after its span a wave sends that tile, then barrier, the slice again only where wg_panel changes, the next
+// window, barrier (form A).  Streams, head bits and head counts are addressed as a wave-uniform base plus a 32-bit lane
+// offset (three VGPRs where the four per-lane pointers take eight): no scratch access inside the tile loop.
+// MFX_RO_PERSIST_FORM=2 is form B, measured slower: the tile goes out during the span's last tile,
+// from the loop's one load site, its offset chosen by a wave-uniform select.
+#ifndef MFX_RO_PERSIST_FORM
+#define MFX_RO_PERSIST_FORM 1
+#endif
 template <int MODE, bool LDS, int BLOCK, bool PSCHK, bool FUSE = false, bool PERSIST = false>
 __global__ __launch_bounds__(BLOCK, flat_min_waves<MODE>(BLOCK)) void k_flat(FlatArgs a) {
     static_assert(!FUSE || ModeTraits<MODE>::kDot, "fused finalize: passes that produce sums");
     static_assert(!PERSIST || (LDS && !FUSE), "persistent form: LDS panels without the in-pass finalize");
     using TR = ModeTraits<MODE>;
+    constexpr bool ROP = PERSIST && !TR::kWrite;   // persistent read-only pass: one window, see above
+    constexpr bool PERSIST2 = PERSIST && TR::kWrite;  // persistent storing pass: two windows
     // FUSE: dispatch slot -> chunk through wg_order (ascending first segment, so that the chunks of one segment
     // group run at about the same time and groups complete all along the pass, not at its end)
     uint32_t chunk = FUSE ? a.wg_order[blockIdx.x] : blockIdx.x;
@@ -316,6 +329,24 @@ __global__ __launch_bounds__(BLOCK, flat_min_waves<MODE>(BLOCK)) void k_flat(Fla
     uint32_t fl_n, hp_n, hp_nn;
     // PERSIST: from a wave's span to its span in the next chunk, in index / value quads and in metadata words
     const size_t span_step_q = (size_t) (BLOCK / 64) * a.tiles_per_span * 64, span_step_w = (size_t) (BLOCK / 64) * span_words;
+    // ROP: quad q / metadata word w of this wave's span, from its wave-uniform start (sq quads, sw words) plus the lane's bytes
+    uint64_t sq = ROP ? (uint64_t) span * a.tiles_per_span * 64 : 0, sw = ROP ? (uint64_t) span * span_words : 0;
+    struct LaneOff { uint32_t i, v, w; };  // the lane's bytes into an index quad row, a value quad row, a row of metadata words
+    // (the empty asm keeps each 32-bit offset, and its zero extension, in the block of the loads that use it: hoisted out of
+    // the tile loop the extension is a 64-bit per-lane value again, and the loads lose their scalar-base form)
+    auto lane_off = [](uint32_t lane) { LaneOff o{lane * (uint32_t) sizeof(IdxVec), lane * 16u, (lane >> 3) * 4u}; asm volatile("" : "+v"(o.i), "+v"(o.v), "+v"(o.w)); return o; };
+    // (the readfirstlane keeps the wave-uniform address apart from the lane's offset: folded together, and hoisted, they are the per-lane pointers again)
+    using gchar = __attribute__((address_space(1))) const char;
+    auto ubase = [](const void* p) {
+        const uint64_t u = reinterpret_cast<uint64_t>(p);
+        return reinterpret_cast<gchar*>((uint64_t) (uint32_t) __builtin_amdgcn_readfirstlane((int) (u >> 32)) << 32 | (uint32_t) __builtin_amdgcn_readfirstlane((int) u));
+    };
+    using GIdxVec = __attribute__((address_space(1))) const IdxVec;
+    using GF32x4 = __attribute__((address_space(1))) const f32x4;
+    auto ld_idx = [&](uint64_t q, uint32_t lane_ib) { return __builtin_nontemporal_load(reinterpret_cast<GIdxVec*>(ubase(static_cast<const IdxVec*>(a.idx) + (sq + q)) + lane_ib)); };
+    auto ld_val = [&](uint64_t q, uint32_t lane_vb) { return __builtin_nontemporal_load(reinterpret_cast<GF32x4*>(ubase(reinterpret_cast<const f32x4*>(a.val) + (sq + q)) + lane_vb)); };
+    auto ld_fl = [&](uint64_t w, uint32_t lane_wb) { return *reinterpret_cast<const gu32*>(ubase(a.flags32 + (sw + w)) + lane_wb); };
+    auto ld_hp = [&](uint64_t w, uint32_t lane_wb) { return *reinterpret_cast<const gu32*>(ubase(a.hpre + (sw + w)) + lane_wb); };
     // stage a panel's slice; slot panel_rows is the zero entry padding points at
     auto stage_slice = [&](uint32_t panel) {
         const uint32_t gbase = panel * a.panel_rows;
@@ -350,7 +381,7 @@ __global__ __launch_bounds__(BLOCK, flat_min_waves<MODE>(BLOCK)) void k_flat(Fla
         const uint32_t rb0 = heads_before(chunk);
         win_base = rb0 > 0 ? rb0 - 1 : 0;
         const uint32_t win_end = heads_before(chunk + 1);  // heads before the next chunk
-        if constexpr (PERSIST) { hb1 = win_end; hb2 = heads_before(chunk + 2 < nchunks ? chunk + 2 : nchunks); }
+        if constexpr (PERSIST2) { hb1 = win_end; hb2 = heads_before(chunk + 2 < nchunks ? chunk + 2 : nchunks); }
         uint32_t cnt = win_end - win_base;
         if (cnt > kPerSegLdsCap) cnt = kPerSegLdsCap;
         for (uint32_t j = threadIdx.x; j < cnt; j += BLOCK) ps_lds[j] = perseg[a.seg_of_rank[win_base + j]];
@@ -359,7 +390,8 @@ __global__ __launch_bounds__(BLOCK, flat_min_waves<MODE>(BLOCK)) void k_flat(Fla
     for (uint32_t visit = 0;; ++visit) {  // one chunk per round; only PERSIST comes round again
     const bool more = PERSIST && chunk + 1 < chunk_end;
     uint32_t win_base_n = 0, win_cnt_n = 0;  // PERSIST: the next chunk's window
-    if constexpr (PERSIST) {
+    if constexpr (ROP) __syncthreads();  // this chunk's slice and window are staged
+    if constexpr (PERSIST2) {
         if (visit && panel_next != panel) {  // workgroup-uniform: every wave is done with the old slice before it is replaced
             __syncthreads();
             panel = panel_next;
@@ -373,7 +405,7 @@ __global__ __launch_bounds__(BLOCK, flat_min_waves<MODE>(BLOCK)) void k_flat(Fla
             }
         }
     }
-    P* __restrict__ ps_cur = PERSIST ? ps_lds + (visit & 1u) * kPerSegLdsCap : ps_lds;  // this chunk's window
+    P* __restrict__ ps_cur = PERSIST2 ? ps_lds + (visit & 1u) * kPerSegLdsCap : ps_lds;  // this chunk's window
     // a wave without work (plain layout: a span beyond the last one, or one that holds only padding) skips the stream loop;
     // with the fused finalize it still joins the epilogue's barriers
     bool live = span < a.nspans;  // (LDS panels: always true, every chunk holds BLOCK / 64 spans)
@@ -422,7 +454,20 @@ __global__ __launch_bounds__(BLOCK, flat_min_waves<MODE>(BLOCK)) void k_flat(Fla
         // reading two tiles past the last span stays in bounds (and yields heads_total).
         const uint32_t cur1_next = __builtin_amdgcn_readfirstlane(hp_nn);
         hp_n = hp_nn;
-        if constexpr (!PERSIST) {
+        if constexpr (ROP) {
+            // one load site for the span's next tile and, from the last tile (form B), for the first tile of the span in the
+            // next chunk; the head bits and counts are read in any case, as in the one-chunk form (spare words)
+            const bool hop = MFX_RO_PERSIST_FORM == 2 && more && tile + 1 == ntiles;
+            const uint64_t q = hop ? (uint64_t) span_step_q : (uint64_t) (tile + 1) * 64;
+            const uint64_t w = hop ? (uint64_t) span_step_w : (uint64_t) (tile + 1) * 8;
+            const LaneOff lo = lane_off(lane);
+            if (hop || tile + 1 < ntiles) {
+                id_n = ld_idx(q, lo.i);
+                v_n = ld_val(q, lo.v);
+            }
+            fl_n = ld_fl(w, lo.w);
+            hp_nn = ld_hp(w + 8, lo.w);
+        } else if constexpr (!PERSIST) {
             if (tile + 1 < ntiles) {
                 id_n = __builtin_nontemporal_load(idx4 + (tile + 1) * 64);
                 v_n = __builtin_nontemporal_load(val4 + (tile + 1) * 64);
@@ -565,6 +610,31 @@ __builtin_nontemporal_store(f32x4{vo[0], vo[1], vo[2], vo[3]}, val4 + tile * 64)
     }  // live
     if constexpr (!PERSIST) break;
     if (!more) break;
+    if constexpr (ROP) {
+        // on to the same wave slot of the next chunk; what the restaging needs is fetched before the barrier
+        ++chunk;
+        span += BLOCK / 64;
+        sq += span_step_q;
+        sw += span_step_w;
+        const LaneOff lo = lane_off(lane);
+        if (MFX_RO_PERSIST_FORM != 2) {  // form A: the first tile goes out here, ahead of the barriers, as in the one-chunk form
+            id_n = ld_idx(0, lo.i);
+            v_n = ld_val(0, lo.v);
+            fl_n = ld_fl(0, lo.w); hp_nn = ld_hp(8, lo.w);
+        }
+        hp_n = ld_hp(0, lo.w);  // (form B: the one word of the first tile that the span's last tile could not fetch in place)
+        panel_next = a.wg_panel[chunk];
+        const uint32_t rb0 = heads_before(chunk), win_end = heads_before(chunk + 1);
+        __syncthreads();  // every wave is done with the last chunk's window, and with the slice
+        if (panel_next != panel) {  // workgroup-uniform
+            panel = panel_next;
+            stage_slice(panel);
+        }
+        win_base = rb0 > 0 ? rb0 - 1 : 0;
+        const uint32_t cnt = win_end - win_base < kPerSegLdsCap ? win_end - win_base : kPerSegLdsCap;
+        for (uint32_t j = threadIdx.x; j < cnt; j += BLOCK) ps_lds[j] = perseg[a.seg_of_rank[win_base + j]];
+        continue;
+    }
     if constexpr (TR::kPerSeg) {  // this thread's share of the next chunk's window, into the window nobody reads any more
         P* __restrict__ ps_nxt = ps_lds + ((visit + 1) & 1u) * kPerSegLdsCap;
         for (uint32_t j = threadIdx.x; j < win_cnt_n; j += BLOCK) ps_nxt[j] = perseg[a.seg_of_rank[win_base_n + j]];
@@ -1250,15 +1320,16 @@ uint32_t flat_persist_per_cu(size_t lds_bytes) {
 }
 
 // Persistent launch (k_flat, PERSIST) where the view asks for it and there are more chunks than resident workgroups;
-// today's one-chunk launch otherwise.  lds_bytes: of the one-chunk form (the persistent one adds the second window).
+// today's one-chunk launch otherwise.  lds_bytes: of the one-chunk form (the persistent storing passes add the second
+// window; the read-only passes keep one, and with it two workgroups per CU).
 template <int MODE, int BLOCK, bool PSCHK>
 int launch_flat_persist(const SegStreamDev& s, const FlatArgs& a, uint32_t grid, size_t lds_bytes, hipStream_t st) {
     if ((s.flat_persist_modes >> MODE) & 1u) {
-        const size_t lds2 = lds_bytes + (size_t) kPerSegLdsCap * sizeof(typename ModeTraits<MODE>::P);
+        const size_t lds2 = lds_bytes + (ModeTraits<MODE>::kWrite ? (size_t) kPerSegLdsCap * sizeof(typename ModeTraits<MODE>::P) : 0);
         if (lds2 <= 160 * 1024) {
             // resident workgroups, if every one of them walks two chunks at least: with fewer there is next to no staging to
             // save, and the one-chunk launch is the faster one (ML-10M shape, 310 chunks on 256 CUs: 29.7 / 30.3 us against
-            // 30.1 / 31.1 us per catch-up pass).  A pinned count (tests) is taken as it is, up to one chunk per workgroup.
+            // 30.1 / 31.1 us per catch-up pass).  The read-only passes: 2 workgroups per CU.  A pinned count (tests) is taken as it is, up to one chunk per workgroup.
             const uint32_t resident = s.flat_cus * flat_persist_per_cu<MODE, BLOCK, PSCHK>(lds2);
             const uint32_t g = s.flat_persist_wgs ? s.flat_persist_wgs : (grid / 2 >= resident ? resident : grid);
             if (g >= 1 && g < grid) return launch_flat_t<MODE, true, BLOCK, PSCHK, false, true>(a, g, lds2, st);
@@ -1344,23 +1415,14 @@ int launch_flat_lds_only(const SegStreamDev& s, const FlatArgs& a, hipStream_t s
     size_t lds_bytes = (((size_t) s.panel_rows + 1) * entry + 15) / 16 * 16 + (size_t) kPerSegLdsCap * sizeof(typename ModeTraits<MODE>::P);
     MFX_REQUIRE(lds_bytes <= 160 * 1024, "launch_flat: mode %d needs %zu bytes of LDS at %u panel rows", MODE, lds_bytes, s.panel_rows);
     const uint32_t grid = s.nspans / s.spans_per_wg;
-    // The read-only passes keep the one-chunk form: they must stay at 64 VGPRs for their second workgroup per CU, and the
-    // persistent form of them takes 72 to 85 when left to the allocator (9 to 21 spilled VGPRs at the bound); DESIGN.md section 10.0.
-    if constexpr (!ModeTraits<MODE>::kWrite) {
-        switch (s.spans_per_wg) {
-            case 4: return launch_flat_lds<MODE, 256>(s, a, grid, lds_bytes, st);
-            case 8: return launch_flat_lds<MODE, 512>(s, a, grid, lds_bytes, st);
-            case 16: return launch_flat_lds<MODE, 1024>(s, a, grid, lds_bytes, st);
-            default: return fail(MFX_ERR_INVALID, "panel layout: spans_per_wg must be 4, 8 or 16 (got %u)", s.spans_per_wg);
-        }
-    } else {
-        const bool pschk = s.max_wg_ranks > kPerSegLdsCap;
-        switch (s.spans_per_wg) {
-            case 4: return pschk ? launch_flat_persist<MODE, 256, true>(s, a, grid, lds_bytes, st) : launch_flat_persist<MODE, 256, false>(s, a, grid, lds_bytes, st);
-            case 8: return pschk ? launch_flat_persist<MODE, 512, true>(s, a, grid, lds_bytes, st) : launch_flat_persist<MODE, 512, false>(s, a, grid, lds_bytes, st);
-            case 16: return pschk ? launch_flat_persist<MODE, 1024, true>(s, a, grid, lds_bytes, st) : launch_flat_persist<MODE, 1024, false>(s, a, grid, lds_bytes, st);
-            default: return fail(MFX_ERR_INVALID, "panel layout: spans_per_wg must be 4, 8 or 16 (got %u)", s.spans_per_wg);
-        }
+    // All four walk chunk ranges with resident workgroups where the view asks for it (launch_flat_persist): the catch-up passes
+    // with two windows and one workgroup per CU, the read-only passes with one window, at 64 VGPRs, two per CU.
+    const bool pschk = s.max_wg_ranks > kPerSegLdsCap;
+    switch (s.spans_per_wg) {
+        case 4: return pschk ? launch_flat_persist<MODE, 256, true>(s, a, grid, lds_bytes, st) : launch_flat_persist<MODE, 256, false>(s, a, grid, lds_bytes, st);
+        case 8: return pschk ? launch_flat_persist<MODE, 512, true>(s, a, grid, lds_bytes, st) : launch_flat_persist<MODE, 512, false>(s, a, grid, lds_bytes, st);
+        case 16: return pschk ? launch_flat_persist<MODE, 1024, true>(s, a, grid, lds_bytes, st) : launch_flat_persist<MODE, 1024, false>(s, a, grid, lds_bytes, st);
+        default: return fail(MFX_ERR_INVALID, "panel layout: spans_per_wg must be 4, 8 or 16 (got %u)", s.spans_per_wg);
     }
 }
 

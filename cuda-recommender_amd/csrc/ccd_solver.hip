@@ -824,10 +824,11 @@ int CcdSolver::init(const mfx_csx* R, const mfx_coo* T, const mfx_params* p, mfx
         if (defer_resid_) MFX_TRY(packD_.alloc_zero(m_, st_));
     }
     {   // persistent flat passes (k_flat's PERSIST form): resident workgroups walk contiguous chunk ranges, so a panel's slice is
-        // staged once per workgroup and panel instead of once per chunk.  On for the catch-up passes of rank_pair, whose slices
-        // fill a CU's LDS; its read-only passes have no persistent form (section 10.0).  MFX_FLAT_PERSIST=0: one chunk per workgroup as before (A/B, the tests' reference); a value
-        // above 1 is a bit mask over FlatMode (A/B per pass).  MFX_FLAT_WGS pins the workgroup count (tests).
-        uint32_t modes = (1u << FM_FCSC2) | (1u << FM_FCSR2);
+        // staged once per workgroup and panel instead of once per chunk.  On for all four passes of rank_pair: the catch-up passes,
+        // whose slices fill a CU's LDS (one workgroup per CU, two windows), and the read-only passes (two per CU at 64 VGPRs, one
+        // window; DESIGN.md sections 4 and 10.0).  MFX_FLAT_PERSIST=0: one chunk per workgroup as before (A/B, the tests' reference); a value
+        // above 1 is a bit mask over FlatMode (A/B per pass: 0x30 the read-only passes, 0xC0 the catch-up passes).  MFX_FLAT_WGS pins the workgroup count of every persistent pass (tests).
+        uint32_t modes = (1u << FM_FCSC_RO) | (1u << FM_FCSR_RO) | (1u << FM_FCSC2) | (1u << FM_FCSR2);
         if (const char* e = std::getenv("MFX_FLAT_PERSIST")) { const long v = std::strtol(e, nullptr, 0); if (v == 0) modes = 0; else if (v > 1) modes &= (uint32_t) v; }
         uint32_t wgs = 0;
         if (const char* e = std::getenv("MFX_FLAT_WGS")) { const int v = std::atoi(e); if (v > 0) wgs = (uint32_t) v; }
