@@ -49,16 +49,28 @@ struct IalsBlock {
     DevBuf<float> score;     // [nnz + kAlsEntryPad]: <x_j, y> of every stored pair in the orientation of the half
     DevBuf<float> ws;        // partial slots of split segments (als_ws_floats at rank d)
     int alloc(uint32_t k, uint32_t d, uint32_t max_rows_x, uint32_t max_seg, uint64_t nnz, uint32_t nslots, hipStream_t st);
+    // P, Z, score and ws alone, for another set of segments over the same fixed side (fold-in: once per query)
+    int alloc_half(uint32_t max_seg, uint64_t nnz, uint32_t nslots, hipStream_t st);
 };
 constexpr uint32_t kIalsBlockMaxRank = 1024, kIalsBlockMaxBlock = 128;
 inline uint32_t ialsb_default_block(uint32_t k) { return k < 64 ? k : 64; }  // mfx_ials_block_create, block = 0
 // G = X^T X + lambda I into b.G, any k <= 1024 (32 x 32 MFMA tiles over row partitions, summed in partition order)
 int ialsb_gramian(IalsBlock& b, const float* X, uint32_t rows, float lambda, hipStream_t st);
-// One half-sweep in place on Y [h.nseg][k] (the warm start) over X [x_rows][k] with b.G = X^T X + lambda I: the scores,
-// then for every block in ascending order G[block, :] y, the block systems (k_ialsb_*: ialsb_step_launch) and the update
-// of y and of the scores
+// One half-sweep in place on Y [h.nseg][k] (the warm start) over X [x_rows][k] with b.G = X^T X + lambda I: the packing
+// (ialsb_pack_launch: X block-major into b.Xb, the diagonal blocks of b.G into b.Gbb), then the sweep (ialsb_sweep_launch:
+// the scores, then for every block in ascending order G[block, :] y, the block systems (k_ialsb_*: ialsb_step_launch) and
+// the update of y and of the scores)
+int ialsb_pack_launch(IalsBlock& b, const float* X, uint32_t x_rows, hipStream_t st);
+int ialsb_sweep_launch(IalsBlock& b, const AlsHalf& h, const float* X, uint32_t x_rows, float* Y, float alpha, uint32_t* spd_fail,
+                       hipStream_t st);
 int ialsb_half_launch(IalsBlock& b, const AlsHalf& h, const float* X, uint32_t x_rows, float* Y, float alpha, uint32_t* spd_fail,
                       hipStream_t st);
+// Fold-in: up to `sweeps` sweeps in place on Y over a side packed before (ialsb_pack_launch).  An empty row is zero and counts
+// 0 sweeps.  tol = 0: every other row gets `sweeps`, nothing is read back.  tol > 0: after each sweep a row is frozen once
+// max |y_new - y_old| <= tol max |y_new| (its bits never change again), and the host reads the number of rows still moving
+// to stop early.  counts: device [h.nseg] (sweeps applied to each row) or NULL.
+int ialsb_fold_launch(IalsBlock& b, const AlsHalf& h, const float* X, uint32_t x_rows, float* Y, float alpha, int32_t sweeps, float tol,
+                      int32_t* counts, uint32_t* spd_fail, hipStream_t st);
 // ials_block_step.hip (als_solver.hip compiled with MFX_ALS_BLOCK): the systems of one block, Z [nseg][d] = the steps
 int ialsb_step_launch(const AlsHalf& h, const float* Xb, uint32_t x_rows, float* Z, uint32_t d, const float* Gbb, float alpha,
                       const float* score, const float* P, float* ws, uint32_t* spd_fail, hipStream_t st);

@@ -504,6 +504,20 @@ int mfx_rec_fold_in(mfx_rec_t r, int64_t nusers, int64_t nnz, const uint32_t* pt
         return r->impl->fold_in(nusers, nnz, ptr, idx, val, W_out, n_top, items, scores, space);
     });
 }
+int mfx_rec_fold_in_block_setup(mfx_rec_t r, float lambda, float alpha, int32_t block, int32_t sweeps, float tol) {
+    return guarded("mfx_rec_fold_in_block_setup", [&]() -> int {
+        MFX_REQUIRE(r && r->impl, "null recommender");
+        return r->impl->fold_in_block_setup(lambda, alpha, block, sweeps, tol);
+    });
+}
+int mfx_rec_fold_in_warm(mfx_rec_t r, int64_t nusers, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val,
+                         const float* W_init, float* W_out, int32_t* sweeps_done, int32_t n_top, uint32_t* items, float* scores,
+                         mfx_memspace space) {
+    return guarded("mfx_rec_fold_in_warm", [&]() -> int {
+        MFX_REQUIRE(r && r->impl, "null recommender");
+        return r->impl->fold_in_warm(nusers, nnz, ptr, idx, val, W_init, W_out, sweeps_done, n_top, items, scores, space);
+    });
+}
 int mfx_rec_fold_in_times(mfx_rec_t r, double seconds[3]) {
     return guarded("mfx_rec_fold_in_times", [&]() -> int {
         MFX_REQUIRE(r && r->impl && seconds, "null recommender or seconds");

@@ -12,6 +12,9 @@
 //   k_ialsb_gy<ND>                P = Y G[:, pi] for every segment: 32 segments x width per wavefront on the MFMA
 //   (k_ialsb_gram / gram16 / reduce: the block systems, als_solver.hip compiled as ials_block_step.hip)
 //   k_ialsb_update                y_pi += z and s_j += <x_jpi, z> (one wavefront per work item)
+// Fold-in (ialsb_fold_launch) repeats the sweep part over query rows against a side packed once, with a stop per row:
+//   k_ialsb_fold_init / _freeze   the empty rows zeroed and frozen from the start; after a sweep a row frozen earlier gets its
+//                                 bits back, any other row counts the sweep and freezes once it moved by <= tol of its size
 // No float atomics; every sum has a fixed order: results are bitwise reproducible.
 #include <algorithm>
 #include <cmath>
@@ -259,6 +262,56 @@ __global__ __launch_bounds__(64) void k_ialsb_update(const AlsItem* __restrict__
     }
 }
 
+__device__ __forceinline__ float wave_max(float v) {  // maximum over the 64 lanes (no order to fix: max is exact)
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+    return v;
+}
+
+// Before the first sweep of a fold-in, one wavefront per row: an empty row is zeroed (whatever the start row held), frozen and
+// counts 0 sweeps; any other row counts `count` (0 when k_ialsb_freeze does the counting).  frozen may be NULL (no stop rule).
+__global__ __launch_bounds__(256) void k_ialsb_fold_init(const uint32_t* __restrict__ ptr, uint32_t nseg, uint32_t k, float* __restrict__ Y,
+                                                         uint32_t* __restrict__ frozen, int32_t* __restrict__ sweeps, int32_t count) {
+    const uint32_t lane = threadIdx.x & 63, seg = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (seg >= nseg) return;
+    const bool empty = ptr[seg + 1] == ptr[seg];
+    if (empty)
+        for (uint32_t c = lane; c < k; c += 64) Y[(size_t) seg * k + c] = 0.f;
+    if (lane == 0) {
+        if (frozen) frozen[seg] = empty;
+        if (sweeps) sweeps[seg] = empty ? 0 : count;
+    }
+}
+
+// After a sweep, one wavefront per row, lane l the columns l + 64 i of Y and of `snap`, the copy of Y taken before the sweep.
+// A row frozen earlier: the sweep is undone (its bits never change again).  Any other row: the sweep counts, and the row is
+// frozen from now on if max_c |y[c] - snap[c]| <= tol max_c |y[c]| (fp32, maxima only: no order); the rows that stay active
+// are counted into *active (one vector atomic per row, an integer: the sum has no order either).
+__global__ __launch_bounds__(256) void k_ialsb_freeze(float* __restrict__ Y, const float* __restrict__ snap, uint32_t nseg, uint32_t k, float tol,
+                                                      uint32_t* __restrict__ frozen, int32_t* __restrict__ sweeps, uint32_t* __restrict__ active) {
+    const uint32_t lane = threadIdx.x & 63, seg = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (seg >= nseg) return;
+    float* y = Y + (size_t) seg * k;
+    const float* s = snap + (size_t) seg * k;
+    if (frozen[seg]) {  // wave-uniform
+        for (uint32_t c = lane; c < k; c += 64) y[c] = s[c];
+        return;
+    }
+    float dmax = 0.f, ymax = 0.f;
+    for (uint32_t c = lane; c < k; c += 64) {
+        const float v = y[c];
+        dmax = fmaxf(dmax, fabsf(v - s[c]));
+        ymax = fmaxf(ymax, fabsf(v));
+    }
+    dmax = wave_max(dmax);
+    ymax = wave_max(ymax);
+    if (lane == 0) {
+        sweeps[seg] += 1;
+        if (dmax <= tol * ymax) frozen[seg] = 1;
+        else atomicAdd(active, 1u);
+    }
+}
+
 template <int ND>
 void launch_gy(const float* Y, uint32_t nseg, uint32_t k, const float* G, uint32_t b0, uint32_t width, float* P, hipStream_t st) {
     hipLaunchKernelGGL(k_ialsb_gy<ND>, dim3((nseg + 127) / 128), dim3(256), 0, st, Y, nseg, k, G, b0, width, P);
@@ -278,6 +331,10 @@ int IalsBlock::alloc(uint32_t k_, uint32_t d_, uint32_t max_rows_x, uint32_t max
     MFX_TRY(gpart.alloc((size_t) gram_parts(max_rows_x, k) * gram_tiles(k) * 1024));
     MFX_TRY(Xb.alloc(xb_offset(max_rows_x, d, nblocks)));
     MFX_TRY(Gbb.alloc((size_t) nblocks * d * d));
+    return alloc_half(max_seg, nnz, nslots, st);
+}
+
+int IalsBlock::alloc_half(uint32_t max_seg, uint64_t nnz, uint32_t nslots, hipStream_t st) {
     MFX_TRY(P.alloc(std::max<size_t>(1, (size_t) max_seg * d)));
     MFX_TRY(Z.alloc(std::max<size_t>(1, (size_t) max_seg * d)));
     MFX_TRY(score.alloc_zero(nnz + kAlsEntryPad, st));  // (the padding stays zero: what the Gramian kernels read past the end is finite)
@@ -296,16 +353,24 @@ int ialsb_gramian(IalsBlock& b, const float* X, uint32_t rows, float lambda, hip
     return MFX_OK;
 }
 
-int ialsb_half_launch(IalsBlock& b, const AlsHalf& h, const float* X, uint32_t x_rows, float* Y, float alpha, uint32_t* spd_fail,
-                      hipStream_t st) {
+int ialsb_pack_launch(IalsBlock& b, const float* X, uint32_t x_rows, hipStream_t st) {
     const uint32_t k = b.k, d = b.d;
-    MFX_REQUIRE(xb_offset(x_rows, d, (k + d - 1) / d) <= b.Xb.size() && (size_t) h.nseg * d <= std::max<size_t>(1, b.P.size()) &&
-                    h.nnz + kAlsEntryPad <= b.score.size(), "implicit ALS by block sweeps: workspace too small for this half");
-    if (h.nseg == 0) return MFX_OK;
+    MFX_REQUIRE(xb_offset(x_rows, d, (k + d - 1) / d) <= b.Xb.size(), "implicit ALS by block sweeps: workspace too small for %u fixed rows", x_rows);
     hipLaunchKernelGGL(k_ialsb_pack, dim3(x_rows / 4 + 1), dim3(256), 0, st, X, x_rows, k, d, b.Xb.get());
     MFX_HIP(hipGetLastError());
     hipLaunchKernelGGL(k_ialsb_pack_g, dim3((k * d + 255) / 256), dim3(256), 0, st, b.G.get(), k, d, b.Gbb.get());
     MFX_HIP(hipGetLastError());
+    return MFX_OK;
+}
+
+int ialsb_sweep_launch(IalsBlock& b, const AlsHalf& h, const float* X, uint32_t x_rows, float* Y, float alpha, uint32_t* spd_fail,
+                       hipStream_t st) {
+    const uint32_t k = b.k, d = b.d;
+    MFX_REQUIRE(xb_offset(x_rows, d, (k + d - 1) / d) <= b.Xb.size() && (size_t) h.nseg * d <= std::max<size_t>(1, b.P.size()) &&
+                    (size_t) h.nseg * d <= std::max<size_t>(1, b.Z.size()) && h.nnz + kAlsEntryPad <= b.score.size() &&
+                    als_ws_floats(h.nslots, d) <= std::max<size_t>(1, b.ws.size()),
+                "implicit ALS by block sweeps: workspace too small for this half");
+    if (h.nseg == 0) return MFX_OK;
     hipLaunchKernelGGL(k_ialsb_scores, dim3(h.nitems), dim3(64), 0, st, h.items.get(), h.nitems, h.idx.get(), X, Y, k, b.score.get());
     MFX_HIP(hipGetLastError());
     for (uint32_t b0 = 0, blk = 0; b0 < k; b0 += d, ++blk) {
@@ -323,6 +388,49 @@ int ialsb_half_launch(IalsBlock& b, const AlsHalf& h, const float* X, uint32_t x
         hipLaunchKernelGGL(k_ialsb_update, dim3(h.nitems), dim3(64), 0, st, h.items.get(), h.nitems, h.ptr.get(), h.idx.get(), Xblk, x_rows,
                            b.Z.get(), width, Y, k, b0, b.score.get());
         MFX_HIP(hipGetLastError());
+    }
+    return MFX_OK;
+}
+
+int ialsb_half_launch(IalsBlock& b, const AlsHalf& h, const float* X, uint32_t x_rows, float* Y, float alpha, uint32_t* spd_fail,
+                      hipStream_t st) {
+    if (h.nseg == 0) return MFX_OK;
+    MFX_TRY(ialsb_pack_launch(b, X, x_rows, st));
+    return ialsb_sweep_launch(b, h, X, x_rows, Y, alpha, spd_fail, st);
+}
+
+int ialsb_fold_launch(IalsBlock& b, const AlsHalf& h, const float* X, uint32_t x_rows, float* Y, float alpha, int32_t sweeps, float tol,
+                      int32_t* counts, uint32_t* spd_fail, hipStream_t st) {
+    const uint32_t k = b.k, nseg = h.nseg;
+    if (nseg == 0) return MFX_OK;
+    const dim3 grid((nseg + 3) / 4), block(256);
+    if (!(tol > 0.f)) {  // every non-empty row gets `sweeps`: no snapshot, no flags, nothing read back
+        hipLaunchKernelGGL(k_ialsb_fold_init, grid, block, 0, st, h.ptr.get(), nseg, k, Y, (uint32_t*) nullptr, counts, sweeps);
+        MFX_HIP(hipGetLastError());
+        for (int32_t s = 0; s < sweeps; ++s) MFX_TRY(ialsb_sweep_launch(b, h, X, x_rows, Y, alpha, spd_fail, st));
+        return MFX_OK;
+    }
+    DevBuf<float> snap;
+    DevBuf<uint32_t> frozen, active;  // active [sweeps]: the rows still moving after each sweep
+    DevBuf<int32_t> own_counts;
+    MFX_TRY(snap.alloc((size_t) nseg * k));
+    MFX_TRY(frozen.alloc(nseg));
+    MFX_TRY(active.alloc_zero((size_t) sweeps, st));
+    if (!counts) {
+        MFX_TRY(own_counts.alloc(nseg));
+        counts = own_counts.get();
+    }
+    hipLaunchKernelGGL(k_ialsb_fold_init, grid, block, 0, st, h.ptr.get(), nseg, k, Y, frozen.get(), counts, 0);
+    MFX_HIP(hipGetLastError());
+    for (int32_t s = 0; s < sweeps; ++s) {
+        MFX_HIP(hipMemcpyAsync(snap.get(), Y, sizeof(float) * (size_t) nseg * k, hipMemcpyDeviceToDevice, st));
+        MFX_TRY(ialsb_sweep_launch(b, h, X, x_rows, Y, alpha, spd_fail, st));
+        hipLaunchKernelGGL(k_ialsb_freeze, grid, block, 0, st, Y, snap.get(), nseg, k, tol, frozen.get(), counts, active.get() + s);
+        MFX_HIP(hipGetLastError());
+        uint32_t left = 0;
+        MFX_HIP(hipMemcpyAsync(&left, active.get() + s, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        MFX_HIP(hipStreamSynchronize(st));
+        if (left == 0) break;
     }
     return MFX_OK;
 }

@@ -25,7 +25,8 @@
 //
 // Fold-in (mfx_rec_fold_in) solves the query rows with the ALS half-sweep launchers against H unpacked from the tiles
 // (the same bits the scores use), packs the solved rows like W and runs the same top-N pass with the query's own rows
-// as the exclusion.
+// as the exclusion.  Above rank 128 (mfx_rec_fold_in_block_setup) the rows are solved by the block subspace sweeps of
+// ials_block.hip instead, repeated up to a sweep count with a stop per row (ialsb_fold_launch).
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -592,6 +593,7 @@ int Recommender::fold_in_setup(int model, float lambda, float alpha) {
     MFX_TRY(use_device(device_));
     hipStream_t st = st_;
     fold_model_ = -1;  // (until this setup is through)
+    fold_b_ = IalsBlock();  // (what a block setup kept)
     const size_t nh = ((size_t) cols_ + 1) * k_;
     if (!hx_.get()) MFX_TRY(hx_.alloc(nh));
     hipLaunchKernelGGL(mfx_rec_unpack_h, dim3(grid_for(nh)), dim3(256), 0, st, hp_.get(), (uint32_t) cols_, (int) k_, 2 * kc_,
@@ -610,9 +612,53 @@ int Recommender::fold_in_setup(int model, float lambda, float alpha) {
     return MFX_OK;
 }
 
+int Recommender::fold_in_block_setup(float lambda, float alpha, int32_t block, int32_t sweeps, float tol) {
+    MFX_REQUIRE(k_ <= (int64_t) kIalsBlockMaxRank, "mfx_rec_fold_in_block_setup: block sweeps solve ranks k <= %u (the handle has k = %lld)",
+                kIalsBlockMaxRank, (long long) k_);
+    MFX_REQUIRE(std::isfinite(lambda) && lambda > 0.f, "mfx_rec_fold_in_block_setup: lambda = %g (finite and > 0 required)", (double) lambda);
+    MFX_REQUIRE(std::isfinite(alpha) && alpha >= 0.f, "mfx_rec_fold_in_block_setup: alpha = %g (finite and >= 0 required)", (double) alpha);
+    MFX_REQUIRE(block >= 0 && block <= (int32_t) kIalsBlockMaxBlock,
+                "mfx_rec_fold_in_block_setup: block = %d (0 = chosen from k, else 1 <= block <= %u)", block, kIalsBlockMaxBlock);
+    MFX_REQUIRE(sweeps >= 1 && sweeps <= 1024, "mfx_rec_fold_in_block_setup: sweeps = %d (1 <= sweeps <= 1024)", sweeps);
+    MFX_REQUIRE(std::isfinite(tol) && tol >= 0.f, "mfx_rec_fold_in_block_setup: tol = %g (finite and >= 0 required)", (double) tol);
+    MFX_TRY(use_device(device_));
+    hipStream_t st = st_;
+    fold_model_ = -1;  // (until this setup is through)
+    fold_g_.release();  // (what a direct setup kept)
+    const size_t nh = ((size_t) cols_ + 1) * k_;
+    if (!hx_.get()) MFX_TRY(hx_.alloc(nh));
+    hipLaunchKernelGGL(mfx_rec_unpack_h, dim3(grid_for(nh)), dim3(256), 0, st, hp_.get(), (uint32_t) cols_, (int) k_, 2 * kc_,
+                       nch_, hx_.get());
+    MFX_LAUNCH_CHECK();
+    // the Gramian as the block trainer and mfx_ials_block_half build it (ialsb_gramian), and what they pack once per half
+    const uint32_t k = (uint32_t) k_, d = std::min<uint32_t>(block ? (uint32_t) block : ialsb_default_block(k), k);
+    MFX_TRY(fold_b_.alloc(k, d, (uint32_t) cols_, 0, 0, 0, st));
+    MFX_TRY(ialsb_gramian(fold_b_, hx_.get(), (uint32_t) cols_, lambda, st));
+    MFX_TRY(ialsb_pack_launch(fold_b_, hx_.get(), (uint32_t) cols_, st));
+    MFX_HIP(hipStreamSynchronize(st));
+    fold_b_.gpart.release();
+    fold_model_ = kFoldBlock;
+    fold_lambda_ = lambda;
+    fold_alpha_ = alpha;
+    fold_sweeps_ = sweeps;
+    fold_tol_ = tol;
+    return MFX_OK;
+}
+
 int Recommender::fold_in(int64_t nusers, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val, float* W_out,
                          int32_t n_top, uint32_t* items, float* scores, mfx_memspace space) {
-    MFX_REQUIRE(fold_model_ >= 0, "mfx_rec_fold_in: call mfx_rec_fold_in_setup first");
+    return fold_solve(nusers, nnz, ptr, idx, val, nullptr, W_out, nullptr, n_top, items, scores, space);
+}
+
+int Recommender::fold_in_warm(int64_t nusers, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val, const float* W_init,
+                              float* W_out, int32_t* sweeps_done, int32_t n_top, uint32_t* items, float* scores, mfx_memspace space) {
+    MFX_REQUIRE(fold_model_ == kFoldBlock, "mfx_rec_fold_in_warm: call mfx_rec_fold_in_block_setup first");
+    return fold_solve(nusers, nnz, ptr, idx, val, W_init, W_out, sweeps_done, n_top, items, scores, space);
+}
+
+int Recommender::fold_solve(int64_t nusers, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val, const float* W_init,
+                            float* W_out, int32_t* sweeps_done, int32_t n_top, uint32_t* items, float* scores, mfx_memspace space) {
+    MFX_REQUIRE(fold_model_ >= 0, "mfx_rec_fold_in: call mfx_rec_fold_in_setup or mfx_rec_fold_in_block_setup first");
     MFX_REQUIRE(nusers >= 0 && nusers < (int64_t) 0xFFFFFFFFll, "mfx_rec_fold_in: bad nusers %lld", (long long) nusers);
     MFX_REQUIRE(nnz >= 0 && nnz < (int64_t) 0xFFFF0000ll, "mfx_rec_fold_in: bad nnz %lld", (long long) nnz);
     MFX_REQUIRE(n_top >= 0 && n_top <= kMaxTop, "mfx_rec_fold_in: n_top must be in [0, %d] (got %d)", kMaxTop, n_top);
@@ -641,16 +687,30 @@ int Recommender::fold_in(int64_t nusers, int64_t nnz, const uint32_t* ptr, const
     MFX_REQUIRE(!(hb & 1), "mfx_rec_fold_in: ptr is not a non-decreasing prefix sum from 0 to nnz");
     MFX_REQUIRE(!(hb & 2), "mfx_rec_fold_in: column index out of range [0, %lld)", (long long) cols_);
     MFX_REQUIRE(!(hb & 4), "mfx_rec_fold_in: column indices must be non-decreasing within every row");
-    if (fold_model_ == MFX_FOLD_IMPLICIT) MFX_TRY(ials_check_values(h.val.get(), h.nnz, fold_alpha_, "mfx_rec_fold_in: value", st));
+    const bool by_blocks = fold_model_ == kFoldBlock;
+    if (fold_model_ == MFX_FOLD_IMPLICIT || by_blocks)
+        MFX_TRY(ials_check_values(h.val.get(), h.nnz, fold_alpha_, "mfx_rec_fold_in: value", st));
     const auto t1 = clk::now();
 
     DevBuf<float> Y, ws, wq;
     DevBuf<uint32_t> spd_fail;
+    DevBuf<int32_t> counts;
     MFX_TRY(Y.alloc_zero((size_t) nu * k, st));
     MFX_TRY(spd_fail.alloc_zero(1, st));
-    if (fold_model_ != MFX_FOLD_ALS_EXACT) MFX_TRY(ws.alloc(std::max<size_t>(1, als_ws_floats(h.nslots, k))));
+    if (fold_model_ != MFX_FOLD_ALS_EXACT && !by_blocks) MFX_TRY(ws.alloc(std::max<size_t>(1, als_ws_floats(h.nslots, k))));
     const uint32_t x_rows = (uint32_t) cols_;
+    struct QueryWs {  // the per-query part of fold_b_ goes when the call returns
+        IalsBlock& b;
+        ~QueryWs() { b.P.release(); b.Z.release(); b.score.release(); b.ws.release(); }
+    } query_ws{fold_b_};
     switch (fold_model_) {
+        case kFoldBlock:
+            if (W_init) MFX_TRY(Y.upload(W_init, (size_t) nu * k, space, st));
+            if (sweeps_done) MFX_TRY(counts.alloc(nu));
+            MFX_TRY(fold_b_.alloc_half(nu, h.nnz, h.nslots, st));
+            MFX_TRY(ialsb_fold_launch(fold_b_, h, hx_.get(), x_rows, Y.get(), fold_alpha_, fold_sweeps_, fold_tol_, counts.get(),
+                                      spd_fail.get(), st));
+            break;
         case MFX_FOLD_ALS:
             MFX_TRY(als_half_launch(h, hx_.get(), x_rows, Y.get(), k, fold_lambda_, ws.get(), spd_fail.get(), st));
             break;
@@ -669,6 +729,9 @@ int Recommender::fold_in(int64_t nusers, int64_t nnz, const uint32_t* ptr, const
 
     if (W_out)
         MFX_HIP(hipMemcpyAsync(W_out, Y.get(), sizeof(float) * (size_t) nu * k,
+                               space == MFX_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, st));
+    if (sweeps_done)
+        MFX_HIP(hipMemcpyAsync(sweeps_done, counts.get(), sizeof(int32_t) * (size_t) nu,
                                space == MFX_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, st));
     if (n_top > 0) {
         MFX_TRY(wq.alloc((size_t) nu * kt_));

@@ -6,6 +6,7 @@
 // nothing of the users x items score matrix is ever stored.  See recommend.hip.
 #pragma once
 
+#include "als_solver.hpp"  // IalsBlock (fold-in by block sweeps)
 #include "common.hpp"
 
 namespace mfx {
@@ -18,8 +19,13 @@ public:
               mfx_memspace space, int item_slices);
     // fold-in (mfx_rec_fold_in_setup / mfx_rec_fold_in): solve query rows against H, then score them
     int fold_in_setup(int model, float lambda, float alpha);
+    // the same by block subspace sweeps (mfx_rec_fold_in_block_setup): any k, up to `sweeps` sweeps per row
+    int fold_in_block_setup(float lambda, float alpha, int32_t block, int32_t sweeps, float tol);
     int fold_in(int64_t nusers, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val, float* W_out,
                 int32_t n_top, uint32_t* items, float* scores, mfx_memspace space);
+    // mfx_rec_fold_in_warm: after a block setup only; W_init [nusers][k] / sweeps_done [nusers] in `space`, or NULL
+    int fold_in_warm(int64_t nusers, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val, const float* W_init,
+                     float* W_out, int32_t* sweeps_done, int32_t n_top, uint32_t* items, float* scores, mfx_memspace space);
     void fold_in_times(double out[3]) const { for (int i = 0; i < 3; ++i) out[i] = fold_s_[i]; }
     ~Recommender();
 
@@ -29,6 +35,8 @@ private:
     // scores, which live in `space`.
     int topn(const float* wp, uint32_t nu, const uint32_t* users, const uint32_t* ex_ptr, const uint32_t* ex_idx,
              int32_t n_top, uint32_t* items, float* scores, mfx_memspace space, int item_slices);
+    int fold_solve(int64_t nusers, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val, const float* W_init,
+                   float* W_out, int32_t* sweeps_done, int32_t n_top, uint32_t* items, float* scores, mfx_memspace space);
     int device_ = 0;
     hipStream_t st_ = nullptr;
     int64_t rows_ = 0, cols_ = 0, k_ = 0;
@@ -40,10 +48,16 @@ private:
     DevBuf<float> wp_, hp_;
     DevBuf<uint32_t> ex_ptr_, ex_idx_;
     bool has_ex_ = false;
-    // fold-in: model (-1 = not set up), H row-major [cols_ + 1][k_] with a zero last row, base Gramian [k_][k_] (implicit)
+    // fold-in: model (-1 = not set up, kFoldBlock = block sweeps), H row-major [cols_ + 1][k_] with a zero last row, base Gramian [k_][k_] (implicit)
     int fold_model_ = -1;
     float fold_lambda_ = 0.f, fold_alpha_ = 0.f;
     DevBuf<float> hx_, fold_g_;
+    // fold-in by block sweeps: G = H^T H + lambda I, H block-major and the diagonal blocks of G, all packed at setup; P, Z,
+    // the scores and the split-segment slots live for one query
+    static constexpr int kFoldBlock = 100;
+    IalsBlock fold_b_;
+    int32_t fold_sweeps_ = 0;
+    float fold_tol_ = 0.f;
     double fold_s_[3] = {0, 0, 0};  // host build / solve / score seconds of the last fold-in
 };
 

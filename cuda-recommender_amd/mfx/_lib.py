@@ -122,6 +122,9 @@ SIGNATURES = {
     "mfx_rec_fold_in_setup": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_float]),
     "mfx_rec_fold_in": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                   C.c_void_p, C.c_void_p, C.c_int]),
+    "mfx_rec_fold_in_block_setup": (C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_int32, C.c_int32, C.c_float]),
+    "mfx_rec_fold_in_warm": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int]),
     "mfx_rec_fold_in_times": (C.c_int, [C.c_void_p, f64p]),
     "mfx_rec_destroy": (C.c_int, [C.c_void_p]),
     "mfx_topn_metrics": (C.c_int, [C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(mfx_coo), C.c_float, f64p,

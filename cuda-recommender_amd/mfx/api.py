@@ -772,17 +772,29 @@ class Recommender:
         MFX_FOLD_IMPLICIT, regularisation lam, confidence scale alpha (implicit model).  k <= 128."""
         L.check(L.lib().mfx_rec_fold_in_setup(self.handle, int(model), float(lam), float(alpha)))
 
-    def fold_in(self, rows, n_top: int = 0, on_device: bool = False):
+    def fold_in_block_setup(self, lam: float, alpha: float, block: int = 0, sweeps: int = 8, tol: float = 0.0):
+        """Prepares fold-in by block subspace sweeps (mfx_rec_fold_in_block_setup), the method of ImplicitAlsSolver(block=...):
+        any k <= 1024.  block 0 = chosen from k, else 1..128; a row gets at most `sweeps` sweeps (1..1024), exactly `sweeps`
+        with tol = 0, else it stops once a sweep moves it by at most tol of its largest entry.  A cold start at large alpha
+        converges slowly for short rows: choose sweeps / tol for the data, or pass W_init to fold_in."""
+        L.check(L.lib().mfx_rec_fold_in_block_setup(self.handle, float(lam), float(alpha), int(block), int(sweeps), float(tol)))
+
+    def fold_in(self, rows, n_top: int = 0, on_device: bool = False, W_init=None, return_sweeps: bool = False):
         """Solves one factor row per query user against this handle's H and recommends from it (mfx_rec_fold_in).
         rows: a RatingData-like CSR (csr_row_ptr / csr_col_idx / csr_val) or a (ptr, idx, val) triple of numpy arrays
         or GPU tensors (32-bit ids, float32 values).  Returns (items [U, n_top], scores [U, n_top], W [U, k]), the lists
         with each row's own items excluded (None, None when n_top = 0).  Tensors in, or on_device=True: everything
-        stays on the device and the results are tensors (items as int32 holding the uint32 ids)."""
+        stays on the device and the results are tensors (items as int32 holding the uint32 ids).
+        After fold_in_block_setup only (mfx_rec_fold_in_warm): W_init [U, k], numpy or a GPU tensor like the rows, is the
+        start row of every user (None: zeros), and return_sweeps=True appends the int32 sweep counts [U] to the result."""
         ptr, idx, val = (rows.csr_row_ptr, rows.csr_col_idx, rows.csr_val) if hasattr(rows, "csr_row_ptr") else rows
         if len(ptr.shape) != 1 or ptr.shape[0] < 1 or idx.shape != val.shape:
             raise ValueError("rows: ptr [U + 1], idx [nnz], val [nnz]")
         n, nnz, n_top = int(ptr.shape[0]) - 1, int(idx.shape[0]), int(n_top)
-        if any(_is_dev(a) for a in (ptr, idx, val)) or on_device:
+        warm = W_init is not None or return_sweeps
+        if W_init is not None and tuple(W_init.shape) != (n, self.k):
+            raise ValueError(f"W_init must be [{n}, {self.k}]")
+        if any(_is_dev(a) for a in (ptr, idx, val, W_init)) or on_device:
             import torch
             dev = torch.device("cuda", self.device)
 
@@ -793,21 +805,33 @@ class Recommender:
                 assert a.is_contiguous() and a.element_size() == 4, "query tensors: contiguous 32-bit"
                 return a
             keep = [put(ptr, np.uint32), put(idx, np.uint32), put(val, np.float32)]
+            w0 = put(W_init, np.float32) if W_init is not None else None
             W = torch.empty((n, self.k), dtype=torch.float32, device=dev)
             items = torch.empty((n, n_top), dtype=torch.int32, device=dev) if n_top else None
             scores = torch.empty((n, n_top), dtype=torch.float32, device=dev) if n_top else None
+            done = torch.zeros((n,), dtype=torch.int32, device=dev) if return_sweeps else None
             p = lambda t: C.c_void_p(int(t.data_ptr())) if t is not None and t.numel() else None
-            L.check(L.lib().mfx_rec_fold_in(self.handle, n, nnz, p(keep[0]), p(keep[1]), p(keep[2]), p(W), n_top, p(items),
-                                            p(scores), L.MFX_DEVICE))
-            return items, scores, W
+            if warm:
+                L.check(L.lib().mfx_rec_fold_in_warm(self.handle, n, nnz, p(keep[0]), p(keep[1]), p(keep[2]), p(w0), p(W),
+                                                     p(done), n_top, p(items), p(scores), L.MFX_DEVICE))
+            else:
+                L.check(L.lib().mfx_rec_fold_in(self.handle, n, nnz, p(keep[0]), p(keep[1]), p(keep[2]), p(W), n_top, p(items),
+                                                p(scores), L.MFX_DEVICE))
+            return (items, scores, W, done) if return_sweeps else (items, scores, W)
         ptr, idx = np.ascontiguousarray(ptr, np.uint32), np.ascontiguousarray(idx, np.uint32)
         val = np.ascontiguousarray(val, np.float32)
+        w0 = np.ascontiguousarray(W_init, np.float32) if W_init is not None else None
         W = np.empty((n, self.k), np.float32)
         items = np.empty((n, n_top), np.uint32) if n_top else None
         scores = np.empty((n, n_top), np.float32) if n_top else None
-        L.check(L.lib().mfx_rec_fold_in(self.handle, n, nnz, _vp(ptr), _vp(idx), _vp(val), _vp(W), n_top, _vp(items),
-                                        _vp(scores), L.MFX_HOST))
-        return items, scores, W
+        done = np.zeros(n, np.int32) if return_sweeps else None
+        if warm:
+            L.check(L.lib().mfx_rec_fold_in_warm(self.handle, n, nnz, _vp(ptr), _vp(idx), _vp(val), _vp(w0), _vp(W), _vp(done),
+                                                 n_top, _vp(items), _vp(scores), L.MFX_HOST))
+        else:
+            L.check(L.lib().mfx_rec_fold_in(self.handle, n, nnz, _vp(ptr), _vp(idx), _vp(val), _vp(W), n_top, _vp(items),
+                                            _vp(scores), L.MFX_HOST))
+        return (items, scores, W, done) if return_sweeps else (items, scores, W)
 
     def fold_in_times(self) -> dict:
         """Seconds of the last fold_in call by phase (mfx_rec_fold_in_times): {"build", "solve", "score"}."""

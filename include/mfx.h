@@ -256,7 +256,7 @@ int mfx_ials_half(int64_t nseg, int64_t nnz, const uint32_t* ptr, const uint32_t
  * mfx_als_set_factors: H required; W NULL = zeros (W is the warm start of the first W-half -- unlike the exact solvers
  * it IS read).  One iterate step = W-half over H, then H-half over the new W.  Memory on the device besides the matrix
  * and the factors: one float per stored pair, a block-major copy of the larger factor, k^2 floats.  Fold-in
- * (mfx_rec_fold_in_setup, k <= 128) does not cover models of k > 128 trained here.  Single GPU.
+ * for models trained here: mfx_rec_fold_in_block_setup (mfx_rec_fold_in_setup solves k <= 128 only).  Single GPU.
  * MFX_ERR_INVALID without touching the device: k outside 1..1024 ("rank"), block outside 0..128 ("block"), alpha < 0 /
  * NaN / Inf ("alpha"), schedule != 1 ("schedule"), a null argument. */
 int mfx_ials_block_create(mfx_als_t* out, const mfx_csx* R, const mfx_params* p, float alpha, int32_t block,
@@ -316,7 +316,30 @@ int mfx_rec_fold_in_setup(mfx_rec_t r, int model, float lambda, float alpha);
  * successful mfx_rec_fold_in_setup; a refused query leaves the handle usable. */
 int mfx_rec_fold_in(mfx_rec_t r, int64_t nusers, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val,
                     float* W_out, int32_t n_top, uint32_t* items, float* scores, mfx_memspace space);
-/* Wall-clock seconds of the last mfx_rec_fold_in on r, each phase ending in a stream synchronisation: [0] host build
+/* Fold-in by block subspace sweeps, the method of mfx_ials_block_create: any 1 <= k <= 1024.
+ * block: 0 = ialsb_default_block(k) (k below 64, else 64), else 1..128 (clamped to k as mfx_ials_block_half does).
+ * sweeps: 1..1024, the most sweeps a row gets.  tol >= 0, finite: 0 = every non-empty row gets exactly `sweeps`.
+ * Keeps H row-major as mfx_rec_fold_in_setup does, G = H^T H + lambda I as mfx_ials_block_half builds it, H block-major
+ * and the diagonal blocks of G (one more copy of H on the device).  One sweep over the query rows is one
+ * mfx_ials_block_half from the rows' current values: with tol = 0, S sweeps equal S chained calls bit for bit.
+ * tol > 0: after each sweep a row is frozen once max_c |y_new[c] - y_old[c]| <= tol * max_c |y_new[c]| (fp32); a frozen
+ * row's bits never change again, and the loop ends when every row is frozen or `sweeps` is reached (the host reads one
+ * counter per sweep).  A row's bits and its sweep count do not depend on the other rows of the batch.
+ * A sweep is not a solve: from w = 0 the distance to the minimiser shrinks by a factor per sweep that depends on the row,
+ * and at large alpha short rows are the slow ones (DESIGN.md has the table): choose sweeps / tol for the data, or pass
+ * the row's previous factors as W_init.
+ * The last successful setup of either kind decides what mfx_rec_fold_in does; after this one it is mfx_rec_fold_in_warm
+ * with W_init = NULL and sweeps_done = NULL.  MFX_ERR_INVALID: block outside 0..128, sweeps outside 1..1024, tol < 0 or
+ * not finite, lambda <= 0 or not finite, alpha < 0 or not finite. */
+int mfx_rec_fold_in_block_setup(mfx_rec_t r, float lambda, float alpha, int32_t block, int32_t sweeps, float tol);
+/* mfx_rec_fold_in with a start row per user and the sweep counts.  W_init [nusers][k] or NULL (start from 0);
+ * sweeps_done [nusers] or NULL: the sweeps applied to each row.  An empty row gives w = 0 and 0 sweeps whatever W_init
+ * holds.  The query checks are those of MFX_FOLD_IMPLICIT.  Valid only after mfx_rec_fold_in_block_setup: MFX_ERR_INVALID
+ * after mfx_rec_fold_in_setup or no setup, and the handle stays usable. */
+int mfx_rec_fold_in_warm(mfx_rec_t r, int64_t nusers, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val,
+                         const float* W_init, float* W_out, int32_t* sweeps_done, int32_t n_top, uint32_t* items,
+                         float* scores, mfx_memspace space);
+/* Wall-clock seconds of the last mfx_rec_fold_in / mfx_rec_fold_in_warm on r, each phase ending in a stream synchronisation: [0] host build
  * (query upload, checks, the host-side split into work items), [1] solve, [2] score (packing, top-N, copies out). */
 int mfx_rec_fold_in_times(mfx_rec_t r, double seconds[3]);
 int mfx_rec_destroy(mfx_rec_t r);

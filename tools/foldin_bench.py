@@ -8,7 +8,12 @@ mfx_rec_fold_in call over --reps (host clock around the call, which ends in a st
 the median call into host build (query copies, checks, the host-side split into work items), solve and score, as
 mfx_rec_fold_in_times reports it.
 
-    python tools/foldin_bench.py [--reps 5] [--k 64] [--n-top 10]
+With --block D the model is fold-in by block subspace sweeps instead (mfx_rec_fold_in_block_setup, any k <= 1024, D = 0: the
+default block): at most --sweeps sweeps per row from w = 0, stopped per row by --tol when it is > 0.  Each run then also
+reports the sweeps the slowest row took, the mean over the non-empty rows, and the share of row-sweeps that were spent
+on rows already frozen (every sweep runs over the whole batch).
+
+    python tools/foldin_bench.py [--reps 5] [--k 64] [--n-top 10] [--block D --sweeps S --tol T]
 """
 import argparse
 import json
@@ -32,6 +37,9 @@ def main():
     ap.add_argument("--lam", type=float, default=0.05)
     ap.add_argument("--alpha", type=float, default=1.0)
     ap.add_argument("--seed", type=int, default=1234)
+    ap.add_argument("--block", type=int, default=None, help="fold-in by block sweeps with blocks of D coordinates (0: default)")
+    ap.add_argument("--sweeps", type=int, default=8)
+    ap.add_argument("--tol", type=float, default=0.0)
     a = ap.parse_args()
     import torch
     import mfx
@@ -59,10 +67,17 @@ def main():
     batches["all"] = (rp, ci, cv)
     out = {"tool": "foldin_bench", "workload": f"{rows}x{cols} nnz={nnz}", "k": a.k, "n_top": a.n_top, "lambda": a.lam,
            "alpha": a.alpha, "reps": a.reps, "query_arrays": "device", "runs": []}
+    by_blocks = a.block is not None
+    if by_blocks:
+        out.update({"block": a.block, "sweeps": a.sweeps, "tol": a.tol})
+    models = (("BLOCK", None),) if by_blocks else (("ALS", mfx.MFX_FOLD_ALS), ("IMPLICIT", mfx.MFX_FOLD_IMPLICIT))
     with mfx.Recommender(W, H, 1) as r:
-        for name, model in (("ALS", mfx.MFX_FOLD_ALS), ("IMPLICIT", mfx.MFX_FOLD_IMPLICIT)):
+        for name, model in models:
             t0 = time.perf_counter()
-            r.fold_in_setup(model, a.lam, a.alpha)
+            if by_blocks:
+                r.fold_in_block_setup(a.lam, a.alpha, block=a.block, sweeps=a.sweeps, tol=a.tol)
+            else:
+                r.fold_in_setup(model, a.lam, a.alpha)
             setup_ms = (time.perf_counter() - t0) * 1e3
             for bname, q in batches.items():
                 r.fold_in(q, a.n_top)  # warm-up
@@ -79,6 +94,12 @@ def main():
                        "setup_ms": round(setup_ms, 3), "ms_median": round(float(np.median(ms)), 3),
                        "ms_min": round(min(ms), 3), "ms_max": round(max(ms), 3)}
                 run.update({f"{key}_ms": round(v * 1e3, 3) for key, v in split[med].items()})
+                if by_blocks:
+                    done = r.fold_in(q, 0, return_sweeps=True)[3].cpu().numpy()
+                    live = done[done > 0]
+                    longest = int(done.max()) if done.size else 0
+                    run.update({"sweeps_max": longest, "sweeps_mean": round(float(live.mean()), 3) if live.size else 0.0,
+                                "frozen_row_sweeps_share": round(1.0 - float(live.sum()) / (longest * live.size), 4) if live.size else 0.0})
                 out["runs"].append(run)
                 print(json.dumps(run), file=sys.stderr, flush=True)
     print(json.dumps(out))
