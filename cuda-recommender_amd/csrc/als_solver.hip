@@ -33,7 +33,11 @@
 #ifndef MFX_ALS_BLOCK
 #define MFX_ALS_BLOCK 0
 #endif
-#if MFX_ALS_BLOCK
+// MFX_ALS_BLOCK = 2 (als_block_step.hip): the EXPLICIT kernels as the k_alsb_* instantiations, one block step of explicit
+// ALS by block subspace sweeps (ials_block.hip, alsb_*): unweighted MFMAs, no base Gramian; a.k, a.X, a.P and the step
+// written to Y as above, the rhs weight of an entry is r - s with its stored score s, and the diagonal gets a.lambda
+// (a.seg_ptr NULL) or fp32(a.lambda * n) for a segment of n entries (a.seg_ptr, as MFX_ALS_NREG); P = rho y_pi.
+#if MFX_ALS_BLOCK == 1
 #define MFX_ALS_IMPLICIT 1
 #endif
 // MFX_ALS_IMPLICIT = 1 (ials_half.hip): the same kernels as the implicit-feedback k_ials_* instantiations.  A translation
@@ -47,7 +51,9 @@
 #ifndef MFX_ALS_NREG
 #define MFX_ALS_NREG 0
 #endif
-#if MFX_ALS_BLOCK
+#if MFX_ALS_BLOCK == 2
+#define ALS_KERNEL(name) k_alsb_##name
+#elif MFX_ALS_BLOCK
 #define ALS_KERNEL(name) k_ialsb_##name
 #elif MFX_ALS_IMPLICIT
 #define ALS_KERNEL(name) k_ials_##name
@@ -93,6 +99,13 @@ __device__ __forceinline__ float rcp_nr(float x) {
 #endif
 constexpr bool kBlockedCholesky = MFX_ALS_BLOCKED != 0;
 
+// rhs weight of a gathered entry in the explicit kernels: its value r, or r - s at its stored score s in a block step
+#if MFX_ALS_BLOCK
+#define ALS_RHS(r, s) sub_rn(r, s)
+#else
+#define ALS_RHS(r, s) (r)
+#endif
+
 struct AlsArgs {
     const AlsItem* items;
     const AlsReduce* reduces;
@@ -113,12 +126,12 @@ struct AlsArgs {
     // implicit-feedback kernels (k_ials_*) only; appended so that the fields above keep their kernel-argument offsets
     float alpha;       // confidence weight of a gathered entry: w = fp32(alpha * r)
     const float* G;    // [k][k] base Gramian X^T X + lambda I (ials_base_gramian), the start of every unsplit / reduced system
-#if MFX_ALS_NREG
-    const uint32_t* seg_ptr;  // (k_alsn_* only) segment pointers [nseg + 1]: segment s has seg_ptr[s + 1] - seg_ptr[s] entries
+#if MFX_ALS_NREG || MFX_ALS_BLOCK == 2
+    const uint32_t* seg_ptr;  // (k_alsn_*, k_alsb_* only) segment pointers [nseg + 1]: segment s has seg_ptr[s + 1] - seg_ptr[s] entries
 #endif
 #if MFX_ALS_BLOCK
-    const float* score;  // (k_ialsb_* only) [nnz + pad]: the score <x_j, y> of every stored pair, parallel to val
-    const float* P;      // (k_ialsb_* only) [nseg][k]: G[block, :] y of every segment
+    const float* score;  // (k_ialsb_*, k_alsb_* only) [nnz + pad]: the score <x_j, y> of every stored pair, parallel to val
+    const float* P;      // (k_ialsb_*, k_alsb_* only) [nseg][k]: G[block, :] y of every segment (k_alsb_*: rho y_block)
 #endif
 };
 constexpr uint32_t kPhaseCopies = 1024;
@@ -419,6 +432,8 @@ __device__ void factor_solve(float* lds, const AlsArgs& a, uint32_t seg, unsigne
     float lam = a.lambda;  // k_alsn_*: fp32(lambda * n) for a segment of n entries, one rounding; from here on the plain path
 #if MFX_ALS_NREG
     lam = mul_rn(a.lambda, (float) (a.seg_ptr[seg + 1] - a.seg_ptr[seg]));
+#elif MFX_ALS_BLOCK == 2
+    if (a.seg_ptr) lam = mul_rn(a.lambda, (float) (a.seg_ptr[seg + 1] - a.seg_ptr[seg]));  // (wave-uniform)
 #endif
     for (int i = (int) lane; i < KP; i += 64) L[roff(i) + i] = i < k ? add_rn(L[roff(i) + i], lam) : 1.0f;  // rows k.. : identity
 #if MFX_ALS_BLOCK
@@ -749,7 +764,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(als_waves(NT
                 int ti = 0;
     #pragma unroll
                 for (int I = 0; I < NT; ++I) {
-                    bacc[I] += rv[s][u] * av[s][u][I];
+                    bacc[I] += ALS_RHS(rv[s][u], sv[s][u]) * av[s][u][I];
     #pragma unroll
                     for (int J = I; J < NT; ++J, ++ti)
                         acc[ti] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[s][u][I], av[s][u][J], acc[ti], 0, 0, 0);
@@ -853,7 +868,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(als_waves(NT
                 int ti = 0;
     #pragma unroll
                 for (int I = 0; I < NT; ++I) {
-                    bacc[I] += rv[u] * av[u][I];
+                    bacc[I] += ALS_RHS(rv[u], sv[u]) * av[u][I];
     #pragma unroll
                     for (int J = I; J < NT; ++J, ++ti)
                         acc[ti] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u][I], av[u][J], acc[ti], 0, 0, 0);
@@ -1065,9 +1080,10 @@ __device__ __forceinline__ void g16_mfma(Gram16Regs<D>& r, float alpha) {
         // the rating through op_sel from (rating, whatever sits in the odd partner register) -- which the allocator
         // fills with a destination of the loads just issued, and the waitcnt pass then drains every load in flight
         // (s_waitcnt vmcnt(0)) in front of the MFMA block of every second step.
+        const float rw = ALS_RHS(r.rv[S][u], r.sv[S][u]);
         const float hi = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(
-            0, __builtin_bit_cast(int, r.rv[S][u]), 0xE4 /* quad_perm [0,1,2,3]: a plain copy the optimiser cannot fold */, 0xF, 0xF, false));
-        const f32x2 rr = {r.rv[S][u], hi};
+            0, __builtin_bit_cast(int, rw), 0xE4 /* quad_perm [0,1,2,3]: a plain copy the optimiser cannot fold */, 0xF, 0xF, false));
+        const f32x2 rr = {rw, hi};
         r.bacc[0] = fma2(rr, r.av[S][u].lo, r.bacc[0]);
         r.bacc[1] = fma2(rr, r.av[S][u].hi, r.bacc[1]);
         int ti = 0;
@@ -1291,7 +1307,17 @@ static_assert(kAlsPad >= 16 * ((MFX_G16_DL > MFX_G16_DS ? MFX_G16_DL : MFX_G16_D
 
 static_assert(kAlsPad == kAlsEntryPad, "als_solver.hpp states the padding of the entry arrays");
 
-#if MFX_ALS_BLOCK
+#if MFX_ALS_BLOCK == 2
+int alsb_step_launch(const AlsHalf& h, const float* Xb, uint32_t x_rows, float* Z, uint32_t d, float lambda, int32_t reg,
+                     const float* score, const float* P, float* ws, uint32_t* spd_fail, hipStream_t st) {
+    AlsArgs a{};
+    a.items = h.items.get(); a.reduces = h.reduces.get(); a.idx = h.idx.get(); a.val = h.val.get();
+    a.X = Xb; a.x_rows = x_rows; a.sentinel = (uint32_t) h.nnz; a.Y = Z; a.k = d; a.lambda = lambda; a.ws = ws; a.spd_fail = spd_fail;
+    a.seg_ptr = reg ? h.ptr.get() : nullptr;
+    a.score = score; a.P = P;
+    return launch_half(a, h.nitems, h.nreduces, h.nnz, st);
+}
+#elif MFX_ALS_BLOCK
 int ialsb_step_launch(const AlsHalf& h, const float* Xb, uint32_t x_rows, float* Z, uint32_t d, const float* Gbb, float alpha,
                       const float* score, const float* P, float* ws, uint32_t* spd_fail, hipStream_t st) {
     AlsArgs a{};
@@ -1422,6 +1448,24 @@ int AlsSolver::create_block(AlsSolver** out, const mfx_csx* R, const mfx_params*
     return MFX_OK;
 }
 
+int AlsSolver::create_block_explicit(AlsSolver** out, const mfx_csx* R, const mfx_coo* T, const mfx_params* p, int32_t block, int32_t reg,
+                                     mfx_memspace space) {
+    MFX_REQUIRE(out && R && p, "mfx_als_block_create: null argument");
+    MFX_REQUIRE(p->k >= 1 && p->k <= kIalsBlockMaxRank, "explicit ALS by block sweeps: rank k = %u not supported (1 <= k <= %u)", p->k,
+                kIalsBlockMaxRank);
+    MFX_REQUIRE(block >= 0 && block <= (int32_t) kIalsBlockMaxBlock, "explicit ALS by block sweeps: block = %d (0 = chosen from k, else 1 <= block <= %u)",
+                block, kIalsBlockMaxBlock);
+    MFX_REQUIRE(reg == 0 || reg == 1, "explicit ALS by block sweeps: reg = %d (0 = lambda, 1 = lambda * entries of the segment)", reg);
+    MFX_REQUIRE(std::isfinite(p->lambda) && p->lambda > 0.f, "explicit ALS by block sweeps: lambda = %g (finite and > 0 required)", (double) p->lambda);
+    MFX_REQUIRE(p->schedule == 1, "explicit ALS by block sweeps: schedule must be 1 (there is no as-written mode)");
+    std::unique_ptr<AlsSolver> s(new AlsSolver());
+    s->block_ = std::min<uint32_t>(block ? (uint32_t) block : ialsb_default_block(p->k), p->k);
+    s->reg_ = reg;
+    MFX_TRY(s->init(R, T, p, space, nullptr));
+    *out = s.release();
+    return MFX_OK;
+}
+
 AlsSolver::~AlsSolver() {
     (void) hipSetDevice(device_);
     for (hipEvent_t& e : ev_)
@@ -1515,6 +1559,12 @@ int AlsSolver::init(const mfx_csx* R, const mfx_coo* T, const mfx_params* p, mfx
             MFX_TRY(loss_ws_.alloc(ials_loss_ws_doubles(k_)));  // (block sweeps: on the first loss(), up to 1 GB at k = 1024)
         }
         MFX_TRY(loss_.alloc_zero(1, st_));
+    } else if (block_) {
+        MFX_TRY(als_check_finite(rows_.val.get(), rows_.nnz, "explicit ALS by block sweeps: R (CSR) value", st_));
+        MFX_TRY(als_check_finite(cols_.val.get(), cols_.nnz, "explicit ALS by block sweeps: R (CSC) value", st_));
+        MFX_REQUIRE(rows_.nnz == cols_.nnz, "explicit ALS by block sweeps: the two orientations hold %llu and %llu entries",
+                    (unsigned long long) rows_.nnz, (unsigned long long) cols_.nnz);
+        MFX_TRY(bs_.alloc_explicit(k_, block_, std::max(m_, n_), std::max(m_, n_), rows_.nnz, std::max(rows_.nslots, cols_.nslots), st_));
     }
     MFX_HIP(hipStreamSynchronize(st_));
     return MFX_OK;
@@ -1584,7 +1634,9 @@ int AlsSolver::iterate(int n_iter, int with_rmse, mfx_iter_report* reports) {
     for (int it = 0; it < n_iter; ++it) {
         MFX_HIP(hipMemsetAsync(spd_fail_.get(), 0, sizeof(uint32_t), st_));
         MFX_HIP(hipEventRecord(ev_[0], st_));
-        if (block_) {
+        if (block_ && !implicit_) {
+            MFX_TRY(alsb_half_launch(bs_, rows_, H_.get(), n_, W_.get(), p_.lambda, reg_, spd_fail_.get(), st_));
+        } else if (block_) {
             MFX_TRY(ialsb_gramian(bs_, H_.get(), n_, p_.lambda, st_));
             MFX_HIP(hipEventRecord(ev_[4], st_));
             MFX_TRY(ialsb_half_launch(bs_, rows_, H_.get(), n_, W_.get(), alpha_, spd_fail_.get(), st_));
@@ -1600,7 +1652,9 @@ int AlsSolver::iterate(int n_iter, int with_rmse, mfx_iter_report* reports) {
         if (comm_) MFX_TRY(exchange(W_.get(), row_bounds_));
         MFX_HIP(hipEventRecord(ev_[1], st_));
         if (phases_.size()) MFX_TRY(print_phases("user half (W over H)"));
-        if (block_) {
+        if (block_ && !implicit_) {
+            MFX_TRY(alsb_half_launch(bs_, cols_, W_.get(), m_, H_.get(), p_.lambda, reg_, spd_fail_.get(), st_));
+        } else if (block_) {
             MFX_TRY(ialsb_gramian(bs_, W_.get(), m_, p_.lambda, st_));
             MFX_HIP(hipEventRecord(ev_[5], st_));
             MFX_TRY(ialsb_half_launch(bs_, cols_, W_.get(), m_, H_.get(), alpha_, spd_fail_.get(), st_));
@@ -1677,10 +1731,11 @@ int AlsSolver::kernel_times(int cap, const char** names, double* seconds, int64_
     static const char* nm[2] = {"als_half_rows(W over H)", "als_half_cols(H over W)"};
     static const char* nm_impl[4] = {"ials_half_rows(W over H)", "ials_half_cols(H over W)", "ials_base_gram(H)", "ials_base_gram(W)"};
     static const char* nm_block[4] = {"ialsb_half_rows(W over H)", "ialsb_half_cols(H over W)", "ialsb_base_gram(H)", "ialsb_base_gram(W)"};
+    static const char* nm_eblock[2] = {"alsb_half_rows(W over H)", "alsb_half_cols(H over W)"};
     int n = 0;
     for (int i = 0; i < 4 && n < cap; ++i) {
         if (!n_half_[i]) continue;
-        if (names) names[n] = block_ ? nm_block[i] : implicit_ ? nm_impl[i] : nm[i];
+        if (names) names[n] = block_ && !implicit_ ? nm_eblock[i] : block_ ? nm_block[i] : implicit_ ? nm_impl[i] : nm[i];
         if (seconds) seconds[n] = t_half_[i];
         if (launches) launches[n] = n_half_[i];
         ++n;

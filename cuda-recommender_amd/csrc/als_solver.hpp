@@ -51,6 +51,8 @@ struct IalsBlock {
     int alloc(uint32_t k, uint32_t d, uint32_t max_rows_x, uint32_t max_seg, uint64_t nnz, uint32_t nslots, hipStream_t st);
     // P, Z, score and ws alone, for another set of segments over the same fixed side (fold-in: once per query)
     int alloc_half(uint32_t max_seg, uint64_t nnz, uint32_t nslots, hipStream_t st);
+    // explicit ALS by block sweeps (alsb_*): Xb and the per-half part, no G, gpart, Gbb
+    int alloc_explicit(uint32_t k, uint32_t d, uint32_t max_rows_x, uint32_t max_seg, uint64_t nnz, uint32_t nslots, hipStream_t st);
 };
 constexpr uint32_t kIalsBlockMaxRank = 1024, kIalsBlockMaxBlock = 128;
 inline uint32_t ialsb_default_block(uint32_t k) { return k < 64 ? k : 64; }  // mfx_ials_block_create, block = 0
@@ -77,6 +79,28 @@ int ialsb_step_launch(const AlsHalf& h, const float* Xb, uint32_t x_rows, float*
 int ials_block_half_op(int64_t nseg, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val, int64_t nrows_x,
                        const float* X, const float* Y_in, float* Y_out, int64_t k, int32_t block, float lambda, float alpha, int device);
 
+// Explicit ALS by block subspace sweeps (mfx_als_block_create; the explicit part of ials_block.hip): the objective
+// sum_j (r_j - <x_j, y>)^2 + rho |y|^2 of a segment, rho = lambda (reg 0) or fp32(lambda * n) for n stored entries (reg 1),
+// minimised block by block from the segment's current row.  No base Gramian: b.G, b.gpart, b.Gbb stay empty
+// (IalsBlock::alloc_explicit).  The same three launches as above: the packing (X block-major), one sweep in place on Y (the
+// scores, then for every block P = rho y_block, the block systems (k_alsb_*: alsb_step_launch) and the update), and both.
+int alsb_pack_launch(IalsBlock& b, const float* X, uint32_t x_rows, hipStream_t st);
+int alsb_sweep_launch(IalsBlock& b, const AlsHalf& h, const float* X, uint32_t x_rows, float* Y, float lambda, int32_t reg,
+                      uint32_t* spd_fail, hipStream_t st);
+int alsb_half_launch(IalsBlock& b, const AlsHalf& h, const float* X, uint32_t x_rows, float* Y, float lambda, int32_t reg,
+                     uint32_t* spd_fail, hipStream_t st);
+// Fold-in with the stop rule of ialsb_fold_launch, over a side packed before (alsb_pack_launch)
+int alsb_fold_launch(IalsBlock& b, const AlsHalf& h, const float* X, uint32_t x_rows, float* Y, float lambda, int32_t reg, int32_t sweeps,
+                     float tol, int32_t* counts, uint32_t* spd_fail, hipStream_t st);
+// als_block_step.hip (als_solver.hip compiled with MFX_ALS_BLOCK = 2): the systems of one block, Z [nseg][d] = the steps;
+// P [nseg][d] = rho y_block
+int alsb_step_launch(const AlsHalf& h, const float* Xb, uint32_t x_rows, float* Z, uint32_t d, float lambda, int32_t reg,
+                     const float* score, const float* P, float* ws, uint32_t* spd_fail, hipStream_t st);
+// MFX_ERR_INVALID unless every value is finite (device-side check)
+int als_check_finite(const float* d_val, uint64_t n, const char* what, hipStream_t st);
+int als_block_half_op(int64_t nseg, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val, int64_t nrows_x,
+                      const float* X, const float* Y_in, float* Y_out, int64_t k, int32_t block, float lambda, int32_t reg, int device);
+
 class AlsSolver {
 public:
     static int create(AlsSolver** out, const mfx_csx* R, const mfx_coo* T, const mfx_params* p,
@@ -85,6 +109,9 @@ public:
     static int create_implicit(AlsSolver** out, const mfx_csx* R, const mfx_params* p, float alpha, mfx_memspace space);
     // implicit feedback by block subspace sweeps (mfx_ials_block_create): k <= 1024, block = 0 or 1..128
     static int create_block(AlsSolver** out, const mfx_csx* R, const mfx_params* p, float alpha, int32_t block, mfx_memspace space);
+    // explicit feedback by block subspace sweeps (mfx_als_block_create): k <= 1024, block = 0 or 1..128, reg 0 / 1
+    static int create_block_explicit(AlsSolver** out, const mfx_csx* R, const mfx_coo* T, const mfx_params* p, int32_t block, int32_t reg,
+                                     mfx_memspace space);
     bool implicit() const { return implicit_; }
     int loss(double* out);  // implicit only: the objective at the current factors (ials.hip)
     ~AlsSolver();
@@ -130,6 +157,7 @@ private:
     DevBuf<double> loss_ws_, loss_;  // fp64 Gramians + entry partials of the objective, the objective
     uint32_t block_ = 0;             // > 0: block subspace sweeps with blocks of block_ coordinates
     IalsBlock bs_;
+    int32_t reg_ = 0;                // explicit block sweeps: 1 = fp32(lambda * n) on the diagonal of a segment of n entries
 };
 
 // Launches one half-sweep: Y[seg] = argmin over segment `seg` given factor rows X[x_rows + 1][k],

@@ -277,6 +277,34 @@ int mfx_ials_block_half(int64_t nseg, int64_t nnz, const uint32_t* ptr, const ui
         return ials_block_half_op(nseg, nnz, ptr, idx, val, nrows_x, X, Y_in, Y_out, k, block, lambda, alpha, device);
     });
 }
+/* ------------------------------------------------------------------ explicit ALS by block subspace sweeps */
+int mfx_als_block_create(mfx_als_t* out, const mfx_csx* R, const mfx_coo* T, const mfx_params* p, int32_t block, int32_t reg,
+                         mfx_memspace space) {
+    return guarded("mfx_als_block_create", [&]() -> int {
+        MFX_REQUIRE(out, "mfx_als_block_create: out is NULL");
+        *out = nullptr;
+        AlsSolver* s = nullptr;
+        MFX_TRY(AlsSolver::create_block_explicit(&s, R, T, p, block, reg, space));  // (argument checks before the device is touched)
+        *out = new mfx_als_s{s};
+        return MFX_OK;
+    });
+}
+int mfx_als_block_half(int64_t nseg, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val, int64_t nrows_x,
+                       const float* X, const float* Y_in, float* Y_out, int64_t k, int32_t block, float lambda, int32_t reg, int device) {
+    return guarded("mfx_als_block_half", [&]() -> int {
+        MFX_REQUIRE(nseg > 0 && nnz >= 0 && ptr && X && Y_out && nrows_x > 0, "mfx_als_block_half: bad argument");
+        MFX_REQUIRE(nnz == 0 || (idx && val), "mfx_als_block_half: null idx / val with nnz > 0");
+        MFX_REQUIRE(k >= 1 && k <= (int64_t) kIalsBlockMaxRank, "explicit ALS by block sweeps: rank k = %lld not supported (1 <= k <= %u)",
+                    (long long) k, kIalsBlockMaxRank);
+        MFX_REQUIRE(block >= 0 && block <= (int32_t) kIalsBlockMaxBlock,
+                    "explicit ALS by block sweeps: block = %d (0 = chosen from k, else 1 <= block <= %u)", block, kIalsBlockMaxBlock);
+        MFX_REQUIRE(reg == 0 || reg == 1, "mfx_als_block_half: reg = %d (0 = lambda, 1 = lambda * entries of the segment)", reg);
+        MFX_REQUIRE(std::isfinite(lambda) && lambda > 0.f, "mfx_als_block_half: lambda = %g (finite and > 0 required)", (double) lambda);
+        MFX_REQUIRE(nseg < (int64_t) 0xFFFFFFFFll && nrows_x < (int64_t) 0xFFFFFFFFll && nnz < (int64_t) 0xFFFF0000ll,
+                    "mfx_als_block_half: sizes exceed the 32-bit index range");
+        return als_block_half_op(nseg, nnz, ptr, idx, val, nrows_x, X, Y_in, Y_out, k, block, lambda, reg, device);
+    });
+}
 int mfx_ials_loss(mfx_als_t s, double* loss) {
     return guarded("mfx_ials_loss", [&]() -> int {
         MFX_REQUIRE(s && s->impl && loss, "mfx_ials_loss: null argument");
@@ -508,6 +536,12 @@ int mfx_rec_fold_in_block_setup(mfx_rec_t r, float lambda, float alpha, int32_t 
     return guarded("mfx_rec_fold_in_block_setup", [&]() -> int {
         MFX_REQUIRE(r && r->impl, "null recommender");
         return r->impl->fold_in_block_setup(lambda, alpha, block, sweeps, tol);
+    });
+}
+int mfx_rec_fold_in_block_setup_als(mfx_rec_t r, float lambda, int32_t reg, int32_t block, int32_t sweeps, float tol) {
+    return guarded("mfx_rec_fold_in_block_setup_als", [&]() -> int {
+        MFX_REQUIRE(r && r->impl, "null recommender");
+        return r->impl->fold_in_block_setup_als(lambda, reg, block, sweeps, tol);
     });
 }
 int mfx_rec_fold_in_warm(mfx_rec_t r, int64_t nusers, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val,

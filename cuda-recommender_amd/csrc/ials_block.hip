@@ -16,6 +16,12 @@
 //   k_ialsb_fold_init / _freeze   the empty rows zeroed and frozen from the start; after a sweep a row frozen earlier gets its
 //                                 bits back, any other row counts the sweep and freezes once it moved by <= tol of its size
 // No float atomics; every sum has a fixed order: results are bitwise reproducible.
+//
+// Explicit feedback (alsb_*, the last part of this file) runs the same sweep on the objective sum_j (r_j - <x_j, y>)^2 +
+// rho |y|^2 of a segment: no base Gramian, so no k_ialsb_gram_tile, _pack_g or _gy; in their place
+//   k_alsb_p                      P = rho y_pi, rho = lambda or fp32(lambda * n) for a segment of n entries
+//   (k_alsb_gram / gram16 / reduce: the block systems, als_solver.hip compiled as als_block_step.hip)
+// and k_ialsb_pack, _scores, _update, _fold_init and _freeze as they are.
 #include <algorithm>
 #include <cmath>
 
@@ -312,9 +318,65 @@ __global__ __launch_bounds__(256) void k_ialsb_freeze(float* __restrict__ Y, con
     }
 }
 
+// Explicit feedback: P[seg][c] = rho y[b0 + c] for the block at b0, rho = lambda or fp32(lambda * n) for a segment of n
+// entries (one rounding, as k_alsn_* form it); one thread per (segment, column of the block)
+__global__ __launch_bounds__(256) void k_alsb_p(const float* __restrict__ Y, const uint32_t* __restrict__ ptr, uint32_t nseg, uint32_t k, uint32_t b0,
+                                                uint32_t width, float lambda, int32_t reg, float* __restrict__ P) {
+    const size_t e = (size_t) blockIdx.x * 256 + threadIdx.x;
+    if (e >= (size_t) nseg * width) return;
+    const uint32_t seg = (uint32_t) (e / width), c = (uint32_t) (e % width);
+    const float rho = reg ? lambda * (float) (ptr[seg + 1] - ptr[seg]) : lambda;
+    P[e] = rho * Y[(size_t) seg * k + b0 + c];
+}
+
+// the first position whose value is not finite into *first_bad (grid-stride, one atomic per thread that found one)
+__global__ __launch_bounds__(256) void k_alsb_check(uint64_t n, const float* __restrict__ val, unsigned long long* __restrict__ first_bad) {
+    unsigned long long bad = ~0ull;
+    for (uint64_t q = (uint64_t) blockIdx.x * 256 + threadIdx.x; q < n; q += (uint64_t) gridDim.x * 256)
+        if (!(fabsf(val[q]) <= 3.402823466e38f) && q < bad) bad = q;  // (NaN fails the compare)
+    if (bad != ~0ull) atomicMin(first_bad, bad);
+}
+
 template <int ND>
 void launch_gy(const float* Y, uint32_t nseg, uint32_t k, const float* G, uint32_t b0, uint32_t width, float* P, hipStream_t st) {
     hipLaunchKernelGGL(k_ialsb_gy<ND>, dim3((nseg + 127) / 128), dim3(256), 0, st, Y, nseg, k, G, b0, width, P);
+}
+
+// The sweeps of a fold-in with the stop per row; sweep() launches one sweep in place on Y
+template <class Sweep>
+int fold_loop(const AlsHalf& h, uint32_t k, float* Y, int32_t sweeps, float tol, int32_t* counts, hipStream_t st, Sweep&& sweep) {
+    const uint32_t nseg = h.nseg;
+    if (nseg == 0) return MFX_OK;
+    const dim3 grid((nseg + 3) / 4), block(256);
+    if (!(tol > 0.f)) {  // every non-empty row gets `sweeps`: no snapshot, no flags, nothing read back
+        hipLaunchKernelGGL(k_ialsb_fold_init, grid, block, 0, st, h.ptr.get(), nseg, k, Y, (uint32_t*) nullptr, counts, sweeps);
+        MFX_HIP(hipGetLastError());
+        for (int32_t s = 0; s < sweeps; ++s) MFX_TRY(sweep());
+        return MFX_OK;
+    }
+    DevBuf<float> snap;
+    DevBuf<uint32_t> frozen, active;  // active [sweeps]: the rows still moving after each sweep
+    DevBuf<int32_t> own_counts;
+    MFX_TRY(snap.alloc((size_t) nseg * k));
+    MFX_TRY(frozen.alloc(nseg));
+    MFX_TRY(active.alloc_zero((size_t) sweeps, st));
+    if (!counts) {
+        MFX_TRY(own_counts.alloc(nseg));
+        counts = own_counts.get();
+    }
+    hipLaunchKernelGGL(k_ialsb_fold_init, grid, block, 0, st, h.ptr.get(), nseg, k, Y, frozen.get(), counts, 0);
+    MFX_HIP(hipGetLastError());
+    for (int32_t s = 0; s < sweeps; ++s) {
+        MFX_HIP(hipMemcpyAsync(snap.get(), Y, sizeof(float) * (size_t) nseg * k, hipMemcpyDeviceToDevice, st));
+        MFX_TRY(sweep());
+        hipLaunchKernelGGL(k_ialsb_freeze, grid, block, 0, st, Y, snap.get(), nseg, k, tol, frozen.get(), counts, active.get() + s);
+        MFX_HIP(hipGetLastError());
+        uint32_t left = 0;
+        MFX_HIP(hipMemcpyAsync(&left, active.get() + s, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        MFX_HIP(hipStreamSynchronize(st));
+        if (left == 0) break;
+    }
+    return MFX_OK;
 }
 
 struct OpStream {
@@ -401,38 +463,7 @@ int ialsb_half_launch(IalsBlock& b, const AlsHalf& h, const float* X, uint32_t x
 
 int ialsb_fold_launch(IalsBlock& b, const AlsHalf& h, const float* X, uint32_t x_rows, float* Y, float alpha, int32_t sweeps, float tol,
                       int32_t* counts, uint32_t* spd_fail, hipStream_t st) {
-    const uint32_t k = b.k, nseg = h.nseg;
-    if (nseg == 0) return MFX_OK;
-    const dim3 grid((nseg + 3) / 4), block(256);
-    if (!(tol > 0.f)) {  // every non-empty row gets `sweeps`: no snapshot, no flags, nothing read back
-        hipLaunchKernelGGL(k_ialsb_fold_init, grid, block, 0, st, h.ptr.get(), nseg, k, Y, (uint32_t*) nullptr, counts, sweeps);
-        MFX_HIP(hipGetLastError());
-        for (int32_t s = 0; s < sweeps; ++s) MFX_TRY(ialsb_sweep_launch(b, h, X, x_rows, Y, alpha, spd_fail, st));
-        return MFX_OK;
-    }
-    DevBuf<float> snap;
-    DevBuf<uint32_t> frozen, active;  // active [sweeps]: the rows still moving after each sweep
-    DevBuf<int32_t> own_counts;
-    MFX_TRY(snap.alloc((size_t) nseg * k));
-    MFX_TRY(frozen.alloc(nseg));
-    MFX_TRY(active.alloc_zero((size_t) sweeps, st));
-    if (!counts) {
-        MFX_TRY(own_counts.alloc(nseg));
-        counts = own_counts.get();
-    }
-    hipLaunchKernelGGL(k_ialsb_fold_init, grid, block, 0, st, h.ptr.get(), nseg, k, Y, frozen.get(), counts, 0);
-    MFX_HIP(hipGetLastError());
-    for (int32_t s = 0; s < sweeps; ++s) {
-        MFX_HIP(hipMemcpyAsync(snap.get(), Y, sizeof(float) * (size_t) nseg * k, hipMemcpyDeviceToDevice, st));
-        MFX_TRY(ialsb_sweep_launch(b, h, X, x_rows, Y, alpha, spd_fail, st));
-        hipLaunchKernelGGL(k_ialsb_freeze, grid, block, 0, st, Y, snap.get(), nseg, k, tol, frozen.get(), counts, active.get() + s);
-        MFX_HIP(hipGetLastError());
-        uint32_t left = 0;
-        MFX_HIP(hipMemcpyAsync(&left, active.get() + s, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        MFX_HIP(hipStreamSynchronize(st));
-        if (left == 0) break;
-    }
-    return MFX_OK;
+    return fold_loop(h, b.k, Y, sweeps, tol, counts, st, [&]() { return ialsb_sweep_launch(b, h, X, x_rows, Y, alpha, spd_fail, st); });
 }
 
 int ials_block_half_op(int64_t nseg, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val, int64_t nrows_x,
@@ -454,6 +485,97 @@ int ials_block_half_op(int64_t nseg, int64_t nnz, const uint32_t* ptr, const uin
     MFX_TRY(fail_cnt.alloc_zero(1, os.st));
     MFX_TRY(ialsb_gramian(b, dX.get(), (uint32_t) nrows_x, lambda, os.st));
     MFX_TRY(ialsb_half_launch(b, h, dX.get(), (uint32_t) nrows_x, dY.get(), alpha, fail_cnt.get(), os.st));
+    MFX_HIP(hipMemcpyAsync(Y_out, dY.get(), sizeof(float) * (size_t) nseg * k, hipMemcpyDeviceToHost, os.st));
+    MFX_HIP(hipStreamSynchronize(os.st));
+    return MFX_OK;
+}
+
+// ---- Explicit feedback ------------------------------------------------------------------------------------------
+int IalsBlock::alloc_explicit(uint32_t k_, uint32_t d_, uint32_t max_rows_x, uint32_t max_seg, uint64_t nnz, uint32_t nslots, hipStream_t st) {
+    k = k_; d = d_;
+    MFX_TRY(Xb.alloc(xb_offset(max_rows_x, d, (k + d - 1) / d)));
+    return alloc_half(max_seg, nnz, nslots, st);
+}
+
+int als_check_finite(const float* d_val, uint64_t n, const char* what, hipStream_t st) {
+    if (n == 0) return MFX_OK;
+    DevBuf<unsigned long long> flag;
+    MFX_TRY(flag.alloc(1));
+    MFX_HIP(hipMemsetAsync(flag.get(), 0xFF, sizeof(unsigned long long), st));
+    const uint32_t grid = (uint32_t) std::min<uint64_t>((n + 255) / 256, 2048);
+    hipLaunchKernelGGL(k_alsb_check, dim3(grid), dim3(256), 0, st, n, d_val, flag.get());
+    MFX_HIP(hipGetLastError());
+    unsigned long long bad = ~0ull;
+    MFX_HIP(hipMemcpyAsync(&bad, flag.get(), sizeof(bad), hipMemcpyDeviceToHost, st));
+    MFX_HIP(hipStreamSynchronize(st));
+    if (bad == ~0ull) return MFX_OK;
+    float v = 0.f;
+    MFX_HIP(hipMemcpy(&v, d_val + bad, sizeof(v), hipMemcpyDeviceToHost));
+    return fail(MFX_ERR_INVALID, "%s %g at position %llu: finite values required", what, (double) v, bad);
+}
+
+int alsb_pack_launch(IalsBlock& b, const float* X, uint32_t x_rows, hipStream_t st) {
+    const uint32_t k = b.k, d = b.d;
+    MFX_REQUIRE(xb_offset(x_rows, d, (k + d - 1) / d) <= b.Xb.size(), "explicit ALS by block sweeps: workspace too small for %u fixed rows", x_rows);
+    hipLaunchKernelGGL(k_ialsb_pack, dim3(x_rows / 4 + 1), dim3(256), 0, st, X, x_rows, k, d, b.Xb.get());
+    MFX_HIP(hipGetLastError());
+    return MFX_OK;
+}
+
+int alsb_sweep_launch(IalsBlock& b, const AlsHalf& h, const float* X, uint32_t x_rows, float* Y, float lambda, int32_t reg,
+                      uint32_t* spd_fail, hipStream_t st) {
+    const uint32_t k = b.k, d = b.d;
+    MFX_REQUIRE(xb_offset(x_rows, d, (k + d - 1) / d) <= b.Xb.size() && (size_t) h.nseg * d <= std::max<size_t>(1, b.P.size()) &&
+                    (size_t) h.nseg * d <= std::max<size_t>(1, b.Z.size()) && h.nnz + kAlsEntryPad <= b.score.size() &&
+                    als_ws_floats(h.nslots, d) <= std::max<size_t>(1, b.ws.size()),
+                "explicit ALS by block sweeps: workspace too small for this half");
+    if (h.nseg == 0) return MFX_OK;
+    hipLaunchKernelGGL(k_ialsb_scores, dim3(h.nitems), dim3(64), 0, st, h.items.get(), h.nitems, h.idx.get(), X, Y, k, b.score.get());
+    MFX_HIP(hipGetLastError());
+    for (uint32_t b0 = 0, blk = 0; b0 < k; b0 += d, ++blk) {
+        const uint32_t width = std::min(d, k - b0);
+        hipLaunchKernelGGL(k_alsb_p, dim3((uint32_t) (((size_t) h.nseg * width + 255) / 256)), dim3(256), 0, st, Y, h.ptr.get(), h.nseg, k, b0,
+                           width, lambda, reg, b.P.get());
+        MFX_HIP(hipGetLastError());
+        const float* Xblk = b.Xb.get() + xb_offset(x_rows, d, blk);
+        MFX_TRY(alsb_step_launch(h, Xblk, x_rows, b.Z.get(), width, lambda, reg, b.score.get(), b.P.get(), b.ws.get(), spd_fail, st));
+        hipLaunchKernelGGL(k_ialsb_update, dim3(h.nitems), dim3(64), 0, st, h.items.get(), h.nitems, h.ptr.get(), h.idx.get(), Xblk, x_rows,
+                           b.Z.get(), width, Y, k, b0, b.score.get());
+        MFX_HIP(hipGetLastError());
+    }
+    return MFX_OK;
+}
+
+int alsb_half_launch(IalsBlock& b, const AlsHalf& h, const float* X, uint32_t x_rows, float* Y, float lambda, int32_t reg,
+                     uint32_t* spd_fail, hipStream_t st) {
+    if (h.nseg == 0) return MFX_OK;
+    MFX_TRY(alsb_pack_launch(b, X, x_rows, st));
+    return alsb_sweep_launch(b, h, X, x_rows, Y, lambda, reg, spd_fail, st);
+}
+
+int alsb_fold_launch(IalsBlock& b, const AlsHalf& h, const float* X, uint32_t x_rows, float* Y, float lambda, int32_t reg, int32_t sweeps,
+                     float tol, int32_t* counts, uint32_t* spd_fail, hipStream_t st) {
+    return fold_loop(h, b.k, Y, sweeps, tol, counts, st, [&]() { return alsb_sweep_launch(b, h, X, x_rows, Y, lambda, reg, spd_fail, st); });
+}
+
+int als_block_half_op(int64_t nseg, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val, int64_t nrows_x,
+                      const float* X, const float* Y_in, float* Y_out, int64_t k, int32_t block, float lambda, int32_t reg, int device) {
+    MFX_TRY(use_device(device));
+    OpStream os;
+    MFX_HIP(hipStreamCreateWithFlags(&os.st, hipStreamNonBlocking));
+    AlsHalf h;
+    MFX_TRY(h.build((uint32_t) nseg, (uint64_t) nnz, (uint32_t) nrows_x, ptr, idx, val, MFX_HOST, kAlsChunk, os.st));
+    MFX_TRY(als_check_finite(h.val.get(), h.nnz, "mfx_als_block_half: value", os.st));
+    const uint32_t d = std::min<uint32_t>(block ? (uint32_t) block : ialsb_default_block((uint32_t) k), (uint32_t) k);
+    IalsBlock b;
+    MFX_TRY(b.alloc_explicit((uint32_t) k, d, (uint32_t) nrows_x, (uint32_t) nseg, (uint64_t) nnz, h.nslots, os.st));
+    DevBuf<float> dX, dY;
+    DevBuf<uint32_t> fail_cnt;
+    MFX_TRY(dX.alloc((size_t) nrows_x * k)); MFX_TRY(dX.upload(X, (size_t) nrows_x * k, MFX_HOST, os.st));
+    MFX_TRY(dY.alloc_zero((size_t) nseg * k, os.st));
+    if (Y_in) MFX_TRY(dY.upload(Y_in, (size_t) nseg * k, MFX_HOST, os.st));
+    MFX_TRY(fail_cnt.alloc_zero(1, os.st));
+    MFX_TRY(alsb_half_launch(b, h, dX.get(), (uint32_t) nrows_x, dY.get(), lambda, reg, fail_cnt.get(), os.st));
     MFX_HIP(hipMemcpyAsync(Y_out, dY.get(), sizeof(float) * (size_t) nseg * k, hipMemcpyDeviceToHost, os.st));
     MFX_HIP(hipStreamSynchronize(os.st));
     return MFX_OK;

@@ -26,7 +26,8 @@
 // Fold-in (mfx_rec_fold_in) solves the query rows with the ALS half-sweep launchers against H unpacked from the tiles
 // (the same bits the scores use), packs the solved rows like W and runs the same top-N pass with the query's own rows
 // as the exclusion.  Above rank 128 (mfx_rec_fold_in_block_setup) the rows are solved by the block subspace sweeps of
-// ials_block.hip instead, repeated up to a sweep count with a stop per row (ialsb_fold_launch).
+// ials_block.hip instead, repeated up to a sweep count with a stop per row (ialsb_fold_launch); the explicit objectives of
+// MFX_FOLD_ALS / MFX_FOLD_CCD the same way after mfx_rec_fold_in_block_setup_als (alsb_fold_launch).
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -645,6 +646,38 @@ int Recommender::fold_in_block_setup(float lambda, float alpha, int32_t block, i
     return MFX_OK;
 }
 
+int Recommender::fold_in_block_setup_als(float lambda, int32_t reg, int32_t block, int32_t sweeps, float tol) {
+    MFX_REQUIRE(k_ <= (int64_t) kIalsBlockMaxRank, "mfx_rec_fold_in_block_setup_als: block sweeps solve ranks k <= %u (the handle has k = %lld)",
+                kIalsBlockMaxRank, (long long) k_);
+    MFX_REQUIRE(std::isfinite(lambda) && lambda > 0.f, "mfx_rec_fold_in_block_setup_als: lambda = %g (finite and > 0 required)", (double) lambda);
+    MFX_REQUIRE(reg == 0 || reg == 1, "mfx_rec_fold_in_block_setup_als: reg = %d (0 = lambda, 1 = lambda * entries of the row)", reg);
+    MFX_REQUIRE(block >= 0 && block <= (int32_t) kIalsBlockMaxBlock,
+                "mfx_rec_fold_in_block_setup_als: block = %d (0 = chosen from k, else 1 <= block <= %u)", block, kIalsBlockMaxBlock);
+    MFX_REQUIRE(sweeps >= 1 && sweeps <= 1024, "mfx_rec_fold_in_block_setup_als: sweeps = %d (1 <= sweeps <= 1024)", sweeps);
+    MFX_REQUIRE(std::isfinite(tol) && tol >= 0.f, "mfx_rec_fold_in_block_setup_als: tol = %g (finite and >= 0 required)", (double) tol);
+    MFX_TRY(use_device(device_));
+    hipStream_t st = st_;
+    fold_model_ = -1;  // (until this setup is through)
+    fold_g_.release();  // (what a direct setup kept)
+    fold_b_ = IalsBlock();  // (what an implicit block setup kept)
+    const size_t nh = ((size_t) cols_ + 1) * k_;
+    if (!hx_.get()) MFX_TRY(hx_.alloc(nh));
+    hipLaunchKernelGGL(mfx_rec_unpack_h, dim3(grid_for(nh)), dim3(256), 0, st, hp_.get(), (uint32_t) cols_, (int) k_, 2 * kc_,
+                       nch_, hx_.get());
+    MFX_LAUNCH_CHECK();
+    const uint32_t k = (uint32_t) k_, d = std::min<uint32_t>(block ? (uint32_t) block : ialsb_default_block(k), k);
+    MFX_TRY(fold_b_.alloc_explicit(k, d, (uint32_t) cols_, 0, 0, 0, st));
+    MFX_TRY(alsb_pack_launch(fold_b_, hx_.get(), (uint32_t) cols_, st));
+    MFX_HIP(hipStreamSynchronize(st));
+    fold_model_ = kFoldBlockAls;
+    fold_lambda_ = lambda;
+    fold_alpha_ = 0.f;
+    fold_reg_ = reg;
+    fold_sweeps_ = sweeps;
+    fold_tol_ = tol;
+    return MFX_OK;
+}
+
 int Recommender::fold_in(int64_t nusers, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val, float* W_out,
                          int32_t n_top, uint32_t* items, float* scores, mfx_memspace space) {
     return fold_solve(nusers, nnz, ptr, idx, val, nullptr, W_out, nullptr, n_top, items, scores, space);
@@ -652,13 +685,14 @@ int Recommender::fold_in(int64_t nusers, int64_t nnz, const uint32_t* ptr, const
 
 int Recommender::fold_in_warm(int64_t nusers, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val, const float* W_init,
                               float* W_out, int32_t* sweeps_done, int32_t n_top, uint32_t* items, float* scores, mfx_memspace space) {
-    MFX_REQUIRE(fold_model_ == kFoldBlock, "mfx_rec_fold_in_warm: call mfx_rec_fold_in_block_setup first");
+    MFX_REQUIRE(fold_model_ == kFoldBlock || fold_model_ == kFoldBlockAls,
+                "mfx_rec_fold_in_warm: call mfx_rec_fold_in_block_setup or mfx_rec_fold_in_block_setup_als first");
     return fold_solve(nusers, nnz, ptr, idx, val, W_init, W_out, sweeps_done, n_top, items, scores, space);
 }
 
 int Recommender::fold_solve(int64_t nusers, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val, const float* W_init,
                             float* W_out, int32_t* sweeps_done, int32_t n_top, uint32_t* items, float* scores, mfx_memspace space) {
-    MFX_REQUIRE(fold_model_ >= 0, "mfx_rec_fold_in: call mfx_rec_fold_in_setup or mfx_rec_fold_in_block_setup first");
+    MFX_REQUIRE(fold_model_ >= 0, "mfx_rec_fold_in: call mfx_rec_fold_in_setup, mfx_rec_fold_in_block_setup or mfx_rec_fold_in_block_setup_als first");
     MFX_REQUIRE(nusers >= 0 && nusers < (int64_t) 0xFFFFFFFFll, "mfx_rec_fold_in: bad nusers %lld", (long long) nusers);
     MFX_REQUIRE(nnz >= 0 && nnz < (int64_t) 0xFFFF0000ll, "mfx_rec_fold_in: bad nnz %lld", (long long) nnz);
     MFX_REQUIRE(n_top >= 0 && n_top <= kMaxTop, "mfx_rec_fold_in: n_top must be in [0, %d] (got %d)", kMaxTop, n_top);
@@ -687,9 +721,11 @@ int Recommender::fold_solve(int64_t nusers, int64_t nnz, const uint32_t* ptr, co
     MFX_REQUIRE(!(hb & 1), "mfx_rec_fold_in: ptr is not a non-decreasing prefix sum from 0 to nnz");
     MFX_REQUIRE(!(hb & 2), "mfx_rec_fold_in: column index out of range [0, %lld)", (long long) cols_);
     MFX_REQUIRE(!(hb & 4), "mfx_rec_fold_in: column indices must be non-decreasing within every row");
-    const bool by_blocks = fold_model_ == kFoldBlock;
-    if (fold_model_ == MFX_FOLD_IMPLICIT || by_blocks)
+    const bool by_blocks = fold_model_ == kFoldBlock || fold_model_ == kFoldBlockAls;
+    if (fold_model_ == MFX_FOLD_IMPLICIT || fold_model_ == kFoldBlock)
         MFX_TRY(ials_check_values(h.val.get(), h.nnz, fold_alpha_, "mfx_rec_fold_in: value", st));
+    else if (fold_model_ == kFoldBlockAls)
+        MFX_TRY(als_check_finite(h.val.get(), h.nnz, "mfx_rec_fold_in: value", st));
     const auto t1 = clk::now();
 
     DevBuf<float> Y, ws, wq;
@@ -710,6 +746,13 @@ int Recommender::fold_solve(int64_t nusers, int64_t nnz, const uint32_t* ptr, co
             MFX_TRY(fold_b_.alloc_half(nu, h.nnz, h.nslots, st));
             MFX_TRY(ialsb_fold_launch(fold_b_, h, hx_.get(), x_rows, Y.get(), fold_alpha_, fold_sweeps_, fold_tol_, counts.get(),
                                       spd_fail.get(), st));
+            break;
+        case kFoldBlockAls:
+            if (W_init) MFX_TRY(Y.upload(W_init, (size_t) nu * k, space, st));
+            if (sweeps_done) MFX_TRY(counts.alloc(nu));
+            MFX_TRY(fold_b_.alloc_half(nu, h.nnz, h.nslots, st));
+            MFX_TRY(alsb_fold_launch(fold_b_, h, hx_.get(), x_rows, Y.get(), fold_lambda_, fold_reg_, fold_sweeps_, fold_tol_, counts.get(),
+                                     spd_fail.get(), st));
             break;
         case MFX_FOLD_ALS:
             MFX_TRY(als_half_launch(h, hx_.get(), x_rows, Y.get(), k, fold_lambda_, ws.get(), spd_fail.get(), st));

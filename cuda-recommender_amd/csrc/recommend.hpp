@@ -21,6 +21,8 @@ public:
     int fold_in_setup(int model, float lambda, float alpha);
     // the same by block subspace sweeps (mfx_rec_fold_in_block_setup): any k, up to `sweeps` sweeps per row
     int fold_in_block_setup(float lambda, float alpha, int32_t block, int32_t sweeps, float tol);
+    // block sweeps on the explicit objective (mfx_rec_fold_in_block_setup_als): reg 0 = lambda, 1 = lambda * entries of the row
+    int fold_in_block_setup_als(float lambda, int32_t reg, int32_t block, int32_t sweeps, float tol);
     int fold_in(int64_t nusers, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val, float* W_out,
                 int32_t n_top, uint32_t* items, float* scores, mfx_memspace space);
     // mfx_rec_fold_in_warm: after a block setup only; W_init [nusers][k] / sweeps_done [nusers] in `space`, or NULL
@@ -54,7 +56,9 @@ private:
     DevBuf<float> hx_, fold_g_;
     // fold-in by block sweeps: G = H^T H + lambda I, H block-major and the diagonal blocks of G, all packed at setup; P, Z,
     // the scores and the split-segment slots live for one query
-    static constexpr int kFoldBlock = 100;
+    // (kFoldBlockAls: the explicit objective -- no G, only H block-major)
+    static constexpr int kFoldBlock = 100, kFoldBlockAls = 101;
+    int32_t fold_reg_ = 0;
     IalsBlock fold_b_;
     int32_t fold_sweeps_ = 0;
     float fold_tol_ = 0.f;

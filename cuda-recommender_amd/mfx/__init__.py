@@ -6,5 +6,6 @@ from .api import (AlsSolver, CcdSolver, Comm, TestData, UsageError, als_gramian,
                   partition_cols, partition_rows, rank_one_sweep, solvertype, test_data_of, test_rmse, update_rating)
 from .api import Recommender, recommend, topn_metrics  # noqa: F401
 from .api import ImplicitAlsSolver, ials_half, ials_block_half  # noqa: F401
+from .api import als_block_half  # noqa: F401
 from ._lib import LIB_PATH, MfxError, lib  # noqa: F401
 from ._lib import MFX_FOLD_ALS, MFX_FOLD_ALS_EXACT, MFX_FOLD_CCD, MFX_FOLD_IMPLICIT  # noqa: F401

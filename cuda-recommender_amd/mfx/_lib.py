@@ -105,6 +105,10 @@ SIGNATURES = {
                                         C.c_int]),
     "mfx_ials_block_half": (C.c_int, [C.c_int64, C.c_int64, u32p, u32p, f32p, C.c_int64, f32p, f32p, f32p, C.c_int64, C.c_int32,
                                       C.c_float, C.c_float, C.c_int]),
+    "mfx_als_block_create": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(mfx_csx), C.POINTER(mfx_coo), C.POINTER(mfx_params), C.c_int32,
+                                       C.c_int32, C.c_int]),
+    "mfx_als_block_half": (C.c_int, [C.c_int64, C.c_int64, u32p, u32p, f32p, C.c_int64, f32p, f32p, f32p, C.c_int64, C.c_int32,
+                                     C.c_float, C.c_int32, C.c_int]),
     "mfx_comm_unique_id": (C.c_int, [C.c_void_p]),
     "mfx_comm_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "mfx_comm_create_local": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int]),
@@ -123,6 +127,7 @@ SIGNATURES = {
     "mfx_rec_fold_in": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                   C.c_void_p, C.c_void_p, C.c_int]),
     "mfx_rec_fold_in_block_setup": (C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_int32, C.c_int32, C.c_float]),
+    "mfx_rec_fold_in_block_setup_als": (C.c_int, [C.c_void_p, C.c_float, C.c_int32, C.c_int32, C.c_int32, C.c_float]),
     "mfx_rec_fold_in_warm": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int]),
     "mfx_rec_fold_in_times": (C.c_int, [C.c_void_p, f64p]),

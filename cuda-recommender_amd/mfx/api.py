@@ -429,12 +429,37 @@ class AlsSolver:
     """Resident ALS (mfx_als_*)."""
 
     def __init__(self, R: RatingData, T, parameters: parameter, comm: Optional[Comm] = None,
-                 row_range=None, col_range=None, device_arrays: Optional[dict] = None):
+                 row_range=None, col_range=None, device_arrays: Optional[dict] = None, block: Optional[int] = None,
+                 count_reg: bool = False):
         """With `comm`: rank-local ALS shard of the GLOBAL matrix R -- this rank solves user rows
         row_range for the W-half and item columns col_range for the H-half (mfx_als_create_sharded).
-        device_arrays: the matrix as a dict of device tensors (mfx.synth_torch), single GPU only."""
+        device_arrays: the matrix as a dict of device tensors (mfx.synth_torch), single GPU only.
+        block=None: the exact solver (k <= 128).  block=d (0 = chosen from k): block subspace sweeps over d coordinates
+        at a time (mfx_als_block_create, k <= 1024, single GPU) -- a different method above one block; there W, when
+        given to set_factors, is the warm start of the first half-sweep.  count_reg (block sweeps only): lambda times
+        the entries of the segment on the diagonal (the CCD++ objective) instead of lambda."""
         self.handle = C.c_void_p()
         cp = parameters.to_c()
+        if block is None and count_reg:
+            raise ValueError("count_reg needs block sweeps (block=...)")
+        if block is not None:
+            if comm is not None:
+                raise ValueError("ALS by block sweeps is single GPU: comm must be None")
+            reg = 1 if count_reg else 0
+            if device_arrays is not None:
+                d = device_arrays
+                ptr = lambda t: C.c_void_p(int(t.data_ptr())) if t is not None and t.numel() else None
+                self.rows, self.cols, self.k = int(d["rows"]), int(d["cols"]), int(parameters.k)
+                csx = L.mfx_csx(self.rows, self.cols, int(d["csr_val"].numel()), ptr(d["csc_col_ptr"]), ptr(d["csc_row_idx"]),
+                                ptr(d["csc_val"]), ptr(d["csr_row_ptr"]), ptr(d["csr_col_idx"]), ptr(d["csr_val"]))
+                tv = d.get("test_val")
+                coo = L.mfx_coo(int(tv.numel()) if tv is not None else 0, ptr(d.get("test_row")), ptr(d.get("test_col")), ptr(tv))
+                space = L.MFX_DEVICE
+            else:
+                self.rows, self.cols, self.k = R.rows, R.cols, int(parameters.k)
+                csx, coo, space = _csx(R), _coo(T), L.MFX_HOST
+            L.check(L.lib().mfx_als_block_create(C.byref(self.handle), C.byref(csx), C.byref(coo), C.byref(cp), int(block), reg, space))
+            return
         if device_arrays is not None:
             assert comm is None, "device-resident inputs: single-GPU ALS only"
             d = device_arrays
@@ -471,6 +496,8 @@ class AlsSolver:
 
     def set_factors(self, H, W=None):
         _f32c(H, (self.cols, self.k))
+        if W is not None:
+            _f32c(W, (self.rows, self.k))
         L.check(L.lib().mfx_als_set_factors(self.handle, _vp(W) if W is not None else None, _vp(H), L.MFX_HOST))
 
     def iterate(self, n_iter: int, with_rmse: bool = True):
@@ -638,6 +665,18 @@ def ials_block_half(ptr, idx, val, X, k: int, lam: float, alpha: float, block: i
     return Y
 
 
+def als_block_half(ptr, idx, val, X, k: int, lam: float, block: int, Y_in=None, count_reg: bool = False, device: int = 0) -> np.ndarray:
+    """One half-sweep of explicit ALS by block subspace sweeps (mfx_als_block_half) from Y_in [nseg][k] (None = zeros);
+    count_reg: lambda times the entries of the segment on the diagonal instead of lambda."""
+    nseg = ptr.shape[0] - 1
+    Y = np.empty((nseg, k), np.float32)
+    if Y_in is not None:
+        _f32c(Y_in, (nseg, k))
+    L.check(L.lib().mfx_als_block_half(nseg, idx.shape[0], _u32(ptr), _u32(idx), _f32(val), X.shape[0], _f32(X),
+                                       _f32(Y_in) if Y_in is not None else None, _f32(Y), k, int(block), lam, 1 if count_reg else 0, device))
+    return Y
+
+
 def als_inverse(A, device: int = 0) -> np.ndarray:
     """inverseMatrix_CholeskyMethod (src/ALS.cpp:41-64) on one matrix, the reference's operation order."""
     A = np.ascontiguousarray(A, np.float32)
@@ -779,13 +818,20 @@ class Recommender:
         converges slowly for short rows: choose sweeps / tol for the data, or pass W_init to fold_in."""
         L.check(L.lib().mfx_rec_fold_in_block_setup(self.handle, float(lam), float(alpha), int(block), int(sweeps), float(tol)))
 
+    def fold_in_block_setup_als(self, lam: float, block: int = 0, sweeps: int = 8, tol: float = 0.0, count_reg: bool = False):
+        """Prepares fold-in by block subspace sweeps on the explicit objective (mfx_rec_fold_in_block_setup_als), the method
+        of AlsSolver(block=...): any k <= 1024, the objective of MFX_FOLD_ALS, or with count_reg of MFX_FOLD_CCD.  block,
+        sweeps and tol as in fold_in_block_setup.  A sweep is not a solve: with more than one block choose sweeps / tol
+        for the data, or pass W_init to fold_in."""
+        L.check(L.lib().mfx_rec_fold_in_block_setup_als(self.handle, float(lam), 1 if count_reg else 0, int(block), int(sweeps), float(tol)))
+
     def fold_in(self, rows, n_top: int = 0, on_device: bool = False, W_init=None, return_sweeps: bool = False):
         """Solves one factor row per query user against this handle's H and recommends from it (mfx_rec_fold_in).
         rows: a RatingData-like CSR (csr_row_ptr / csr_col_idx / csr_val) or a (ptr, idx, val) triple of numpy arrays
         or GPU tensors (32-bit ids, float32 values).  Returns (items [U, n_top], scores [U, n_top], W [U, k]), the lists
         with each row's own items excluded (None, None when n_top = 0).  Tensors in, or on_device=True: everything
         stays on the device and the results are tensors (items as int32 holding the uint32 ids).
-        After fold_in_block_setup only (mfx_rec_fold_in_warm): W_init [U, k], numpy or a GPU tensor like the rows, is the
+        After fold_in_block_setup / fold_in_block_setup_als only (mfx_rec_fold_in_warm): W_init [U, k], numpy or a GPU tensor like the rows, is the
         start row of every user (None: zeros), and return_sweeps=True appends the int32 sweep counts [U] to the result."""
         ptr, idx, val = (rows.csr_row_ptr, rows.csr_col_idx, rows.csr_val) if hasattr(rows, "csr_row_ptr") else rows
         if len(ptr.shape) != 1 or ptr.shape[0] < 1 or idx.shape != val.shape:

@@ -266,6 +266,37 @@ int mfx_ials_block_half(int64_t nseg, int64_t nnz, const uint32_t* ptr, const ui
                         int64_t nrows_x, const float* X, const float* Y_in, float* Y_out, int64_t k, int32_t block,
                         float lambda, float alpha, int device);
 
+/* Explicit ALS by block subspace sweeps: the objective of mfx_als_create at ranks k up to 1024 (the range mfx_rec_query
+ * scores), by the sweeps of mfx_ials_block_create.  For one segment (a user row or an item column), X the fixed other
+ * factor and r_j the segment's stored values, the objective is
+ *     f(y) = sum_j (r_j - <x_j, y>)^2 + rho |y|^2
+ * with rho = lambda (reg 0: the reference's ALS, src/ALS.cpp) or rho = fp32(lambda * n), n the number of stored entries of
+ * the segment (reg 1: the CCD++ objective, the one MFX_FOLD_CCD minimises at k <= 128).  The solver keeps the score
+ * s_j = <x_j, y> of every stored pair and a half-sweep makes, for every segment from its CURRENT row y, one pass over the
+ * blocks pi_b = [b d, min(k, (b + 1) d)), b = 0, 1, ... of d = `block` coordinates; one step is
+ *     A = sum_j x_jpi x_jpi^T + rho I,     A z = sum_j (r_j - s_j) x_jpi - rho y_pi,     y_pi += z,     s_j += <x_jpi, z>
+ * Every stored entry counts, explicit zeros and negative values included (the "r > 0" rule of the implicit code does not
+ * apply); an empty segment gives y = 0 (src/ALS.cpp:151-157).  With a single block (d >= k) a step from any start is the
+ * exact minimiser: it solves the system of mfx_als_half.  With more than one block this is a different method with
+ * different iterates -- a sweep is not a solve -- whose training objective never increases.  Cost per stored pair k d
+ * instead of k^2.  No float atomics, every sum has a fixed order: results are bitwise reproducible.
+ * block: 0 = chosen from k as min(k, 64), else 1 <= block <= 128 (values above k act as k).  reg: 0 or 1.  T: the test set
+ * of mfx_als_create (or NULL); iterate reports the test RMSE as the exact solver does.  Returns an mfx_als_t:
+ * mfx_als_set_factors / _iterate / _get_factors / _kernel_times / _destroy work on it.  mfx_als_set_factors: H required;
+ * W NULL = zeros (W is the warm start of the first W-half: it IS read).  One iterate step = W-half over H, then H-half
+ * over the new W; kernel-time names alsb_half_rows(W over H), alsb_half_cols(H over W).  Reads k, lambda, device, verbose
+ * of *p; schedule must be 1.  R: both orientations, values finite (checked on the device).  Single GPU.  Memory on the
+ * device besides the matrix and the factors: one float per stored pair and a block-major copy of the larger factor.
+ * Fold-in for models of rank above 128: mfx_rec_fold_in_block_setup_als.  mfx_als_create and mfx_als_half keep k <= 128.
+ * MFX_ERR_INVALID without touching the device: k outside 1..1024 ("rank"), block outside 0..128 ("block"), reg not 0 / 1
+ * ("reg"), lambda <= 0 / NaN / Inf ("lambda"), schedule != 1 ("schedule"), a null argument. */
+int mfx_als_block_create(mfx_als_t* out, const mfx_csx* R, const mfx_coo* T, const mfx_params* p, int32_t block, int32_t reg,
+                         mfx_memspace space);
+/* Single operator for tests: one half-sweep from Y_in [nseg][k] (NULL = zeros) to Y_out [nseg][k], host pointers. */
+int mfx_als_block_half(int64_t nseg, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val,
+                       int64_t nrows_x, const float* X, const float* Y_in, float* Y_out, int64_t k, int32_t block,
+                       float lambda, int32_t reg, int device);
+
 /* ------------------------------------------------------------------------------------
  * Top-N recommendation: a resident handle over trained factors that returns, for each
  * requested user, the n_top highest-scoring items the user must not be excluded from.
@@ -328,14 +359,27 @@ int mfx_rec_fold_in(mfx_rec_t r, int64_t nusers, int64_t nnz, const uint32_t* pt
  * A sweep is not a solve: from w = 0 the distance to the minimiser shrinks by a factor per sweep that depends on the row,
  * and at large alpha short rows are the slow ones (DESIGN.md has the table): choose sweeps / tol for the data, or pass
  * the row's previous factors as W_init.
- * The last successful setup of either kind decides what mfx_rec_fold_in does; after this one it is mfx_rec_fold_in_warm
+ * The last successful setup of any kind decides what mfx_rec_fold_in does; after this one it is mfx_rec_fold_in_warm
  * with W_init = NULL and sweeps_done = NULL.  MFX_ERR_INVALID: block outside 0..128, sweeps outside 1..1024, tol < 0 or
  * not finite, lambda <= 0 or not finite, alpha < 0 or not finite. */
 int mfx_rec_fold_in_block_setup(mfx_rec_t r, float lambda, float alpha, int32_t block, int32_t sweeps, float tol);
+/* The same for the explicit objectives, the method of mfx_als_block_create: reg 0 minimises what MFX_FOLD_ALS solves, reg 1
+ * what MFX_FOLD_CCD solves (fp32(lambda * n_u) on the diagonal), at any 1 <= k <= 1024.  block, sweeps and tol as above.
+ * Keeps H row-major and block-major (no Gramian).  One sweep over the query rows is one mfx_als_block_half from the
+ * rows' current values: with tol = 0, S sweeps equal S chained calls bit for bit; tol > 0 freezes rows by the rule above.
+ * With a single block (block >= k) one sweep is the exact solve; with more blocks a sweep is not a solve: from w = 0 the
+ * distance to the minimiser shrinks by a factor per sweep that depends on the row (DESIGN.md has the sweep counts):
+ * choose sweeps / tol for the data, or pass the row's previous factors as W_init.  Values: finite (checked on the device);
+ * zeros and negative values are entries like any other.
+ * The last successful setup of the three kinds decides what mfx_rec_fold_in does; after this one it is
+ * mfx_rec_fold_in_warm with W_init = NULL and sweeps_done = NULL.  MFX_ERR_INVALID: reg not 0 / 1, block outside 0..128,
+ * sweeps outside 1..1024, tol < 0 or not finite, lambda <= 0 or not finite. */
+int mfx_rec_fold_in_block_setup_als(mfx_rec_t r, float lambda, int32_t reg, int32_t block, int32_t sweeps, float tol);
 /* mfx_rec_fold_in with a start row per user and the sweep counts.  W_init [nusers][k] or NULL (start from 0);
  * sweeps_done [nusers] or NULL: the sweeps applied to each row.  An empty row gives w = 0 and 0 sweeps whatever W_init
- * holds.  The query checks are those of MFX_FOLD_IMPLICIT.  Valid only after mfx_rec_fold_in_block_setup: MFX_ERR_INVALID
- * after mfx_rec_fold_in_setup or no setup, and the handle stays usable. */
+ * holds.  The query checks are those of MFX_FOLD_IMPLICIT (after mfx_rec_fold_in_block_setup_als: finite values).  Valid
+ * only after mfx_rec_fold_in_block_setup or mfx_rec_fold_in_block_setup_als: MFX_ERR_INVALID after mfx_rec_fold_in_setup
+ * or no setup, and the handle stays usable. */
 int mfx_rec_fold_in_warm(mfx_rec_t r, int64_t nusers, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val,
                          const float* W_init, float* W_out, int32_t* sweeps_done, int32_t n_top, uint32_t* items,
                          float* scores, mfx_memspace space);

@@ -13,7 +13,9 @@ default block): at most --sweeps sweeps per row from w = 0, stopped per row by -
 reports the sweeps the slowest row took, the mean over the non-empty rows, and the share of row-sweeps that were spent
 on rows already frozen (every sweep runs over the whole batch).
 
-    python tools/foldin_bench.py [--reps 5] [--k 64] [--n-top 10] [--block D --sweeps S --tol T]
+--explicit (with --block) runs the sweeps on the explicit objective (mfx_rec_fold_in_block_setup_als, --reg 0 / 1).
+
+    python tools/foldin_bench.py [--reps 5] [--k 64] [--n-top 10] [--block D --sweeps S --tol T [--explicit [--reg R]]]
 """
 import argparse
 import json
@@ -40,7 +42,11 @@ def main():
     ap.add_argument("--block", type=int, default=None, help="fold-in by block sweeps with blocks of D coordinates (0: default)")
     ap.add_argument("--sweeps", type=int, default=8)
     ap.add_argument("--tol", type=float, default=0.0)
+    ap.add_argument("--explicit", action="store_true", help="with --block: the explicit objective (mfx_rec_fold_in_block_setup_als)")
+    ap.add_argument("--reg", type=int, default=0, help="with --explicit: 0 = lambda, 1 = lambda * entries of the row")
     a = ap.parse_args()
+    if a.explicit and a.block is None:
+        ap.error("--explicit needs --block")
     import torch
     import mfx
     from mfx import synth_torch
@@ -70,11 +76,15 @@ def main():
     by_blocks = a.block is not None
     if by_blocks:
         out.update({"block": a.block, "sweeps": a.sweeps, "tol": a.tol})
-    models = (("BLOCK", None),) if by_blocks else (("ALS", mfx.MFX_FOLD_ALS), ("IMPLICIT", mfx.MFX_FOLD_IMPLICIT))
+        if a.explicit:
+            out.update({"explicit": True, "reg": a.reg})
+    models = (("BLOCK_ALS" if a.explicit else "BLOCK", None),) if by_blocks else (("ALS", mfx.MFX_FOLD_ALS), ("IMPLICIT", mfx.MFX_FOLD_IMPLICIT))
     with mfx.Recommender(W, H, 1) as r:
         for name, model in models:
             t0 = time.perf_counter()
-            if by_blocks:
+            if by_blocks and a.explicit:
+                r.fold_in_block_setup_als(a.lam, block=a.block, sweeps=a.sweeps, tol=a.tol, count_reg=bool(a.reg))
+            elif by_blocks:
                 r.fold_in_block_setup(a.lam, a.alpha, block=a.block, sweeps=a.sweeps, tol=a.tol)
             else:
                 r.fold_in_setup(model, a.lam, a.alpha)

@@ -12,7 +12,12 @@ process: ms per iteration, the loss after every iteration (a different method: r
 alone), the flop and the gathered bytes of an iteration from the shapes.  --again repeats the exact runs at the end
 (the spread of the yardstick inside the job).
 
-    python tools/ials_bench.py [--ks 64,128] [--block 128:64,256:64] [--again] [--iters 5] [--alpha 1.0] [--lam 0.05]
+--explicit-block k:d,k:d,... adds runs of EXPLICIT ALS by block subspace sweeps (mfx_als_block_create, --reg 0 / 1) on
+the same matrix, the ratings taken as ratings: ms per iteration and per half-sweep, the test RMSE after every iteration,
+flop and gathered bytes from the shapes (no base Gramian, no G y product).
+
+    python tools/ials_bench.py [--ks 64,128] [--block 128:64,256:64] [--explicit-block 256:64] [--reg 0] [--again] [--iters 5]
+                               [--alpha 1.0] [--lam 0.05]
 """
 import argparse
 import json
@@ -41,6 +46,33 @@ def block_counts(rows, cols, nnz, k, d):
     systems, score updates) of k floats."""
     flop = 2.0 * nnz * (k * (d + 1) + 6.0 * k) + (rows + cols) * (2.0 * k * k + k * (k + 1))
     return flop, 2.0 * 3.0 * nnz * k * 4.0
+
+
+def explicit_block_counts(nnz, k, d):
+    """(flop, gathered bytes) of one explicit block-sweep iteration: block_counts without the terms of the base Gramian."""
+    return 2.0 * nnz * (k * (d + 1) + 6.0 * k), 2.0 * 3.0 * nnz * k * 4.0
+
+
+def run_explicit_block(mfx, d_arrays, rows, cols, nnz, k, block, a):
+    p = mfx.parameter()
+    p.k, p.lambda_, p.log = k, a.lam, 1 if a.verbose else 0
+    H0 = mfx.initial_col(cols, k)
+    s = mfx.AlsSolver(None, None, p, device_arrays=d_arrays, block=block, count_reg=bool(a.reg))
+    s.set_factors(H0)
+    rmse = [r.rmse for r in s.iterate(a.iters)]  # the RMSE curve from H0 (these iterations also warm up)
+    s.kernel_times()
+    s.set_factors(H0)  # the same iterations again, warmed up: the times
+    ms = [r.update_time * 1e3 for r in s.iterate(a.iters, with_rmse=False)]
+    kt = s.kernel_times()
+    s.close()
+    per = {name: t * 1e3 / n for name, (t, n) in kt.items()}
+    med = float(np.median(ms))
+    fl, by = explicit_block_counts(nnz, k, block)
+    return {"kind": "explicit_block", "k": k, "block": block, "reg": a.reg, "ms_per_iteration": round(med, 3), "ms_min": round(min(ms), 3),
+            "ms_max": round(max(ms), 3), "ms_user_half": round(per["alsb_half_rows(W over H)"], 3),
+            "ms_item_half": round(per["alsb_half_cols(H over W)"], 3), "flop_per_iteration": fl,
+            "fraction_of_fp32_mfma_peak": round(fl / (med * 1e-3) / (PEAK_TF * 1e12), 4), "gathered_bytes_per_iteration": by,
+            "gathered_tb_per_s": round(by / (med * 1e-3) / 1e12, 3), "test_rmse_per_iteration": rmse}
 
 
 def run_block(mfx, d_arrays, rows, cols, nnz, k, block, a):
@@ -73,6 +105,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--ks", default="64,128")
     ap.add_argument("--block", default="", help="k:d,k:d,... runs of the block subspace sweeps")
+    ap.add_argument("--explicit-block", default="", help="k:d,k:d,... runs of explicit ALS by block subspace sweeps")
+    ap.add_argument("--reg", type=int, default=0, help="explicit block runs: 0 = lambda, 1 = lambda * entries of the segment")
     ap.add_argument("--again", action="store_true", help="repeat the exact runs after the block runs")
     ap.add_argument("--verbose", action="store_true", help="block runs: the solver's own log lines (failed pivots) before the JSON line")
     ap.add_argument("--iters", type=int, default=5)
@@ -89,8 +123,14 @@ def main():
            "library": os.path.relpath(mfx.LIB_PATH, ROOT), "runs": []}
     ks = [int(x) for x in a.ks.split(",") if x]
     blocks = [tuple(int(v) for v in x.split(":")) for x in a.block.split(",") if x]
-    plan = [("exact", k, None) for k in ks] + [("block", k, b) for k, b in blocks] + ([("exact", k, None) for k in ks] if a.again else [])
+    eblocks = [tuple(int(v) for v in x.split(":")) for x in a.explicit_block.split(",") if x]
+    plan = ([("exact", k, None) for k in ks] + [("block", k, b) for k, b in blocks] + [("explicit_block", k, b) for k, b in eblocks] +
+            ([("exact", k, None) for k in ks] if a.again else []))
     for kind, k, block in plan:
+        if kind == "explicit_block":
+            out["runs"].append(run_explicit_block(mfx, d, rows, cols, nnz, k, block, a))
+            torch.cuda.synchronize()
+            continue
         if kind == "block":
             out["runs"].append(run_block(mfx, d, rows, cols, nnz, k, block, a))
             torch.cuda.synchronize()
