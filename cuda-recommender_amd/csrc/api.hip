@@ -559,6 +559,31 @@ int mfx_rec_fold_in_times(mfx_rec_t r, double seconds[3]) {
         return MFX_OK;
     });
 }
+int mfx_rec_set_item_filter(mfx_rec_t r, const uint8_t* keep, mfx_memspace space) {
+    return guarded("mfx_rec_set_item_filter", [&]() -> int {
+        MFX_REQUIRE(r && r->impl, "null recommender");
+        return r->impl->set_item_filter(keep, space);
+    });
+}
+int mfx_rec_similar_setup(mfx_rec_t r) {
+    return guarded("mfx_rec_similar_setup", [&]() -> int {
+        MFX_REQUIRE(r && r->impl, "null recommender");
+        return r->impl->similar_setup();
+    });
+}
+int mfx_rec_item_norms(mfx_rec_t r, float* n2, float* c, mfx_memspace space) {
+    return guarded("mfx_rec_item_norms", [&]() -> int {
+        MFX_REQUIRE(r && r->impl, "null recommender");
+        return r->impl->item_norms(n2, c, space);
+    });
+}
+int mfx_rec_similar(mfx_rec_t r, int64_t nq, const uint32_t* query_items, int metric, int exclude_self, int32_t n_top,
+                    uint32_t* items, float* scores, mfx_memspace space, int item_slices) {
+    return guarded("mfx_rec_similar", [&]() -> int {
+        MFX_REQUIRE(r && r->impl, "null recommender");
+        return r->impl->similar(nq, query_items, metric, exclude_self, n_top, items, scores, space, item_slices);
+    });
+}
 int mfx_rec_destroy(mfx_rec_t r) {
     return guarded("mfx_rec_destroy", [&]() -> int {
         if (!r) return MFX_OK;

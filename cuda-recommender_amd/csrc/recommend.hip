@@ -28,6 +28,12 @@
 // as the exclusion.  Above rank 128 (mfx_rec_fold_in_block_setup) the rows are solved by the block subspace sweeps of
 // ials_block.hip instead, repeated up to a sweep count with a stop per row (ialsb_fold_launch); the explicit objectives of
 // MFX_FOLD_ALS / MFX_FOLD_CCD the same way after mfx_rec_fold_in_block_setup_als (alsb_fold_launch).
+//
+// Item-to-item similarity (mfx_rec_similar) and the item filter (mfx_rec_set_item_filter) are one per-item fp32 factor on
+// the accumulator before the compare (mfx_rec_topn<KC, true>): an inverse norm for the cosine, 1 / NaN for kept / dropped
+// items.  The query operand is H itself packed like W, self-exclusion an identity exclusion CSR, and the cosine's second
+// factor c[q] is applied once per output slot where the final N are written (flush or mfx_rec_merge), so the order is
+// the keys'.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -69,6 +75,8 @@ struct RecArgs {
     uint32_t* li;
     uint32_t* out_items;    // [q0 + q][n_top], written here when there is one slice
     float* out_scores;      // may be NULL
+    const float* fac;       // FAC only: [nblk * 32] per-item factor of the ranking key (NaN: the item is never returned)
+    const float* qfac;      // NULL, or [query id]: factor of a slot's returned scores, applied where its final N leave
 };
 
 __device__ inline bool beats(float as, uint32_t ai, float bs, uint32_t bi) {
@@ -137,8 +145,12 @@ __device__ inline void store_stage(const float4 (&stg)[NV], float* dst, int tid)
     }
 }
 
-template <int KC>
-__global__ __launch_bounds__(kRecThreads) void mfx_rec_topn(RecArgs a) {
+// FAC: the ranking key of (slot, item) is fp32(score * a.fac[item]) instead of the score (cosine keys, item filter).
+// Without FAC the kernels are the ones without the switch.  With it the factors cost KC = 8 and 16 the fourth wave per SIMD
+// (114 and 122 VGPRs + 16 AGPRs) unless the allocator is asked for four; every other instantiation gets the default.
+template <int KC, bool FAC>
+__global__ __launch_bounds__(kRecThreads) __attribute__((amdgpu_waves_per_eu((FAC && KC <= 16) ? 4 : 1)))
+void mfx_rec_topn(RecArgs a) {
     constexpr int STAGE = 2 * KC * kTile;        // floats per LDS stage
     constexpr int NF4 = STAGE / 4;
     constexpr int NV = (NF4 + kRecThreads - 1) / kRecThreads;
@@ -202,6 +214,7 @@ __global__ __launch_bounds__(kRecThreads) void mfx_rec_topn(RecArgs a) {
                 if (e < m) { s = ks[e]; it = is[e]; }
                 if (single) {
                     const size_t o = (size_t) (a.q0 + qu) * a.n_top + e;
+                    if (FAC && a.qfac && e < m) s *= a.qfac[uid];
                     a.out_items[o] = it;
                     if (a.out_scores) a.out_scores[o] = s;
                 } else {
@@ -244,6 +257,14 @@ __global__ __launch_bounds__(kRecThreads) void mfx_rec_topn(RecArgs a) {
 
         if (c == a.nch - 1) {
             const uint32_t ibase = (uint32_t) blk * kTile + 4 * h;
+            if (FAC) {  // a lane's 16 items are four runs of four ids: one 16-byte load of the factors per run
+                const float4* f4 = reinterpret_cast<const float4*>(a.fac + ibase);  // (ibase < 2^32: cols < 2^32 - 1)
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    const float4 f = f4[2 * g];
+                    acc[4 * g] *= f.x; acc[4 * g + 1] *= f.y; acc[4 * g + 2] *= f.z; acc[4 * g + 3] *= f.w;
+                }
+            }
             uint32_t mask = 0;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
@@ -286,9 +307,10 @@ __global__ __launch_bounds__(kRecThreads) void mfx_rec_topn(RecArgs a) {
 }
 
 // Final N of one batch slot from the slices' sorted heads (one wave per slot).
+// qfac (NULL: none) scales the scores on the way out, indexed by the slot's query id; the order is the keys'.
 __global__ __launch_bounds__(64) void mfx_rec_merge(const float* ls, const uint32_t* li, uint32_t q0, uint32_t nq,
                                                     int slices, int L, int n_top, int P, uint32_t* out_items,
-                                                    float* out_scores) {
+                                                    float* out_scores, const uint32_t* users, const float* qfac) {
     extern __shared__ float smem[];
     float* ks = smem;
     uint32_t* is = reinterpret_cast<uint32_t*>(smem + P);
@@ -308,10 +330,11 @@ __global__ __launch_bounds__(64) void mfx_rec_merge(const float* ls, const uint3
     }
     wave_sync();
     wave_bitonic(ks, is, P, lane);
+    const float qf = qfac ? qfac[users ? users[q0 + q] : q0 + q] : 1.f;
     for (int e = lane; e < n_top; e += 64) {
         const size_t o = (size_t) (q0 + q) * n_top + e;
         out_items[o] = is[e];
-        if (out_scores) out_scores[o] = ks[e];
+        if (out_scores) out_scores[o] = (qfac && is[e] != kPad) ? ks[e] * qf : ks[e];
     }
 }
 
@@ -360,6 +383,41 @@ __global__ void mfx_rec_unpack_h(const float* hp, uint32_t cols, int k, int kc2,
     }
 }
 
+// hq[item][t] = H[item][t] from the tiles, +0 for t >= k: the rows of H as a query operand, laid out as mfx_rec_pack_w lays W.
+__global__ void mfx_rec_pack_hq(const float* hp, uint32_t cols, int k, int kc2, int nch, int kt, float* hq) {
+    const size_t total = (size_t) cols * kt;
+    for (size_t x = (size_t) blockIdx.x * blockDim.x + threadIdx.x; x < total; x += (size_t) gridDim.x * blockDim.x) {
+        const size_t item = x / kt;
+        const int t = x % kt;
+        float v = 0.f;
+        if (t < k) v = hp[(((item / kTile) * nch + t / kc2) * kc2 + t % kc2) * kTile + item % kTile];
+        hq[x] = v;
+    }
+}
+
+// n2[i] = the score chain of (H[i], H[i]); c[i] = fp32(1 / sqrt(n2[i])) through fp64, +0 where n2 is 0 or not finite.
+// id[i] = i for i <= cols: row pointers and column indices of the identity exclusion (an item is not its own neighbour).
+__global__ void mfx_rec_item_norms(const float* hq, uint32_t cols, int k, int kt, float* n2, float* c, uint32_t* id) {
+    for (size_t i = (size_t) blockIdx.x * blockDim.x + threadIdx.x; i <= cols; i += (size_t) gridDim.x * blockDim.x) {
+        id[i] = (uint32_t) i;
+        if (i == cols) continue;
+        const float* h = hq + i * kt;
+        float acc = 0.f;
+        for (int t = 0; t < k; ++t) acc = __builtin_fmaf(h[t], h[t], acc);
+        n2[i] = acc;
+        c[i] = (acc > 0.f && acc < INFINITY) ? (float) (1.0 / sqrt((double) acc)) : 0.f;
+    }
+}
+
+// fac[i] = (c ? c[i] : 1) for the items that may be returned, NaN for the others and for the padding past cols.
+__global__ void mfx_rec_build_fac(const uint8_t* keep, const float* c, uint32_t cols, size_t npad, float* fac) {
+    for (size_t i = (size_t) blockIdx.x * blockDim.x + threadIdx.x; i < npad; i += (size_t) gridDim.x * blockDim.x) {
+        float v = __builtin_nanf("");
+        if (i < cols && (!keep || keep[i])) v = c ? c[i] : 1.f;
+        fac[i] = v;
+    }
+}
+
 // bad |= 1: row pointers not a valid prefix sum of nnz; 2: column index >= cols; 4: a row not non-decreasing.
 __global__ void mfx_rec_check_exclude(const uint32_t* rp, const uint32_t* ci, uint32_t rows, uint32_t cols,
                                       uint64_t nnz, int* bad) {
@@ -386,7 +444,8 @@ int grid_for(size_t n) { return (int) std::min<size_t>((n + 255) / 256, 4096); }
 template <int KC>
 int launch_topn(const RecArgs& a, int slices, hipStream_t st) {
     const dim3 grid((a.nq + kRecUsers - 1) / kRecUsers, slices);
-    hipLaunchKernelGGL(mfx_rec_topn<KC>, grid, dim3(kRecThreads), 0, st, a);
+    if (a.fac) hipLaunchKernelGGL((mfx_rec_topn<KC, true>), grid, dim3(kRecThreads), 0, st, a);
+    else hipLaunchKernelGGL((mfx_rec_topn<KC, false>), grid, dim3(kRecThreads), 0, st, a);
     MFX_LAUNCH_CHECK();
     return MFX_OK;
 }
@@ -502,11 +561,109 @@ int Recommender::query(int64_t nusers, const uint32_t* users, int32_t n_top, uin
         du = d_users.get();
     }
     if (users) MFX_TRY(check_index_range(du, nu, (uint32_t) rows_, "mfx_rec_query: user id", st_));
-    return topn(wp_.get(), nu, du, has_ex_ ? ex_ptr_.get() : nullptr, ex_idx_.get(), n_top, items, scores, space, item_slices);
+    return topn(wp_.get(), nu, du, has_ex_ ? ex_ptr_.get() : nullptr, ex_idx_.get(), n_top, items, scores, space, item_slices,
+                fac_keep_.get(), nullptr);
+}
+
+int Recommender::build_facs(const uint8_t* keep) {
+    const size_t npad = (size_t) nblk_ * kTile;
+    if (keep) {
+        if (!fac_keep_.get()) MFX_TRY(fac_keep_.alloc(npad));
+        hipLaunchKernelGGL(mfx_rec_build_fac, dim3(grid_for(npad)), dim3(256), 0, st_, keep, (const float*) nullptr, (uint32_t) cols_,
+                           npad, fac_keep_.get());
+        MFX_LAUNCH_CHECK();
+    }
+    if (sim_c_.get()) {
+        if (!fac_cos_.get()) MFX_TRY(fac_cos_.alloc(npad));
+        hipLaunchKernelGGL(mfx_rec_build_fac, dim3(grid_for(npad)), dim3(256), 0, st_, keep, (const float*) sim_c_.get(),
+                           (uint32_t) cols_, npad, fac_cos_.get());
+        MFX_LAUNCH_CHECK();
+    }
+    MFX_HIP(hipStreamSynchronize(st_));
+    return MFX_OK;
+}
+
+int Recommender::set_item_filter(const uint8_t* keep, mfx_memspace space) {
+    MFX_REQUIRE(space == MFX_HOST || space == MFX_DEVICE, "mfx_rec_set_item_filter: bad memory space");
+    MFX_TRY(use_device(device_));
+    if (!keep) {
+        keep_.release();
+        fac_keep_.release();
+        return build_facs(nullptr);
+    }
+    DevBuf<uint8_t> nk;  // (the handle keeps its filter if this one cannot be taken)
+    MFX_TRY(nk.alloc((size_t) cols_));
+    MFX_TRY(nk.upload(keep, (size_t) cols_, space, st_));
+    MFX_TRY(build_facs(nk.get()));
+    keep_ = std::move(nk);
+    return MFX_OK;
+}
+
+int Recommender::similar_setup() {
+    if (sim_c_.get()) return MFX_OK;
+    MFX_TRY(use_device(device_));
+    DevBuf<float> hq, n2, c;
+    DevBuf<uint32_t> id;
+    MFX_TRY(hq.alloc((size_t) cols_ * kt_));
+    MFX_TRY(n2.alloc((size_t) cols_));
+    MFX_TRY(c.alloc((size_t) cols_));
+    MFX_TRY(id.alloc((size_t) cols_ + 1));
+    hipLaunchKernelGGL(mfx_rec_pack_hq, dim3(grid_for((size_t) cols_ * kt_)), dim3(256), 0, st_, hp_.get(), (uint32_t) cols_, (int) k_,
+                       2 * kc_, nch_, kt_, hq.get());
+    MFX_LAUNCH_CHECK();
+    hipLaunchKernelGGL(mfx_rec_item_norms, dim3(grid_for((size_t) cols_ + 1)), dim3(256), 0, st_, hq.get(), (uint32_t) cols_, (int) k_,
+                       kt_, n2.get(), c.get(), id.get());
+    MFX_LAUNCH_CHECK();
+    MFX_HIP(hipStreamSynchronize(st_));
+    hq_ = std::move(hq); sim_n2_ = std::move(n2); sim_id_ = std::move(id);
+    sim_c_ = std::move(c);
+    const int rc = build_facs(keep_.get());
+    if (rc != MFX_OK) sim_c_.release();  // (not set up)
+    return rc;
+}
+
+int Recommender::item_norms(float* n2, float* c, mfx_memspace space) {
+    MFX_REQUIRE(space == MFX_HOST || space == MFX_DEVICE, "mfx_rec_item_norms: bad memory space");
+    MFX_REQUIRE(sim_c_.get(), "mfx_rec_item_norms: call mfx_rec_similar_setup first");
+    MFX_TRY(use_device(device_));
+    const hipMemcpyKind kind = space == MFX_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+    if (n2) MFX_HIP(hipMemcpyAsync(n2, sim_n2_.get(), sizeof(float) * (size_t) cols_, kind, st_));
+    if (c) MFX_HIP(hipMemcpyAsync(c, sim_c_.get(), sizeof(float) * (size_t) cols_, kind, st_));
+    MFX_HIP(hipStreamSynchronize(st_));
+    return MFX_OK;
+}
+
+int Recommender::similar(int64_t nq, const uint32_t* query_items, int metric, int exclude_self, int32_t n_top, uint32_t* items,
+                         float* scores, mfx_memspace space, int item_slices) {
+    MFX_REQUIRE(sim_c_.get(), "mfx_rec_similar: call mfx_rec_similar_setup first");
+    MFX_REQUIRE(metric == MFX_SIM_DOT || metric == MFX_SIM_COSINE, "mfx_rec_similar: unknown metric %d", metric);
+    MFX_REQUIRE(n_top >= 1 && n_top <= kMaxTop, "mfx_rec_similar: n_top must be in [1, %d] (got %d)", kMaxTop, n_top);
+    MFX_REQUIRE(nq >= 0 && nq < (int64_t) 0xFFFFFFFFll, "mfx_rec_similar: bad nq %lld", (long long) nq);
+    MFX_REQUIRE(query_items || nq <= cols_, "mfx_rec_similar: query_items = NULL needs nq <= cols (%lld > %lld)", (long long) nq,
+                (long long) cols_);
+    MFX_REQUIRE(space == MFX_HOST || space == MFX_DEVICE, "mfx_rec_similar: bad memory space");
+    MFX_REQUIRE(item_slices >= 0, "mfx_rec_similar: item_slices must be >= 0 (got %d)", item_slices);
+    MFX_REQUIRE(item_slices * (int64_t) n_top <= kMaxMerge, "mfx_rec_similar: item_slices * n_top must be <= %d", kMaxMerge);
+    if (nq == 0) return MFX_OK;
+    MFX_REQUIRE(items, "mfx_rec_similar: items is NULL");
+    MFX_TRY(use_device(device_));
+    const uint32_t nu = (uint32_t) nq;
+    DevBuf<uint32_t> d_q;
+    const uint32_t* dq = query_items;
+    if (query_items && space == MFX_HOST) {
+        MFX_TRY(d_q.alloc(nu));
+        MFX_TRY(d_q.upload(query_items, nu, MFX_HOST, st_));
+        dq = d_q.get();
+    }
+    if (query_items) MFX_TRY(check_index_range(dq, nu, (uint32_t) cols_, "mfx_rec_similar: query item", st_));
+    const bool cosine = metric == MFX_SIM_COSINE;
+    return topn(hq_.get(), nu, dq, exclude_self ? sim_id_.get() : nullptr, sim_id_.get(), n_top, items, scores, space, item_slices,
+                cosine ? fac_cos_.get() : fac_keep_.get(), cosine ? sim_c_.get() : nullptr);
 }
 
 int Recommender::topn(const float* wp, uint32_t nu, const uint32_t* du, const uint32_t* ex_ptr, const uint32_t* ex_idx,
-                      int32_t n_top, uint32_t* items, float* scores, mfx_memspace space, int item_slices) {
+                      int32_t n_top, uint32_t* items, float* scores, mfx_memspace space, int item_slices, const float* fac,
+                      const float* qfac) {
     hipStream_t st = st_;
     int L = 64;
     while (L < n_top + 32) L <<= 1;
@@ -557,6 +714,7 @@ int Recommender::topn(const float* wp, uint32_t nu, const uint32_t* du, const ui
     a.kt = kt_; a.nch = nch_; a.nblk = nblk_; a.bps = bps; a.n_top = n_top; a.L = L;
     a.ls = ls.get(); a.li = li.get();
     a.out_items = oi; a.out_scores = os;
+    a.fac = fac; a.qfac = qfac;
     int P = 1;
     while (P < slices * n_top) P <<= 1;
     for (uint32_t q0 = 0; q0 < nu; q0 += qc) {
@@ -573,7 +731,7 @@ int Recommender::topn(const float* wp, uint32_t nu, const uint32_t* du, const ui
         }
         if (slices > 1) {
             hipLaunchKernelGGL(mfx_rec_merge, dim3(a.nq), dim3(64), (size_t) P * 8, st, a.ls, a.li, q0, a.nq, slices, L,
-                               n_top, P, oi, os);
+                               n_top, P, oi, os, du, qfac);
             MFX_LAUNCH_CHECK();
         }
     }
@@ -781,7 +939,7 @@ int Recommender::fold_solve(int64_t nusers, int64_t nnz, const uint32_t* ptr, co
         hipLaunchKernelGGL(mfx_rec_pack_w, dim3(grid_for((size_t) nu * kt_)), dim3(256), 0, st, Y.get(), 1, nu, (int) k, kt_,
                            wq.get());
         MFX_LAUNCH_CHECK();
-        MFX_TRY(topn(wq.get(), nu, nullptr, h.ptr.get(), h.idx.get(), n_top, items, scores, space, 0));
+        MFX_TRY(topn(wq.get(), nu, nullptr, h.ptr.get(), h.idx.get(), n_top, items, scores, space, 0, fac_keep_.get(), nullptr));
     }
     MFX_HIP(hipStreamSynchronize(st));
     const auto t3 = clk::now();

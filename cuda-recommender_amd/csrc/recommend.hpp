@@ -28,15 +28,25 @@ public:
     // mfx_rec_fold_in_warm: after a block setup only; W_init [nusers][k] / sweeps_done [nusers] in `space`, or NULL
     int fold_in_warm(int64_t nusers, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val, const float* W_init,
                      float* W_out, int32_t* sweeps_done, int32_t n_top, uint32_t* items, float* scores, mfx_memspace space);
+    // mfx_rec_set_item_filter / mfx_rec_similar_setup / mfx_rec_item_norms / mfx_rec_similar
+    int set_item_filter(const uint8_t* keep, mfx_memspace space);
+    int similar_setup();
+    int item_norms(float* n2, float* c, mfx_memspace space);
+    int similar(int64_t nq, const uint32_t* query_items, int metric, int exclude_self, int32_t n_top, uint32_t* items, float* scores,
+                mfx_memspace space, int item_slices);
     void fold_in_times(double out[3]) const { for (int i = 0; i < 3; ++i) out[i] = fold_s_[i]; }
     ~Recommender();
 
 private:
     // The top-N pass over nu batch slots: slot q scores packed row users[q] (q when users is NULL) of wp [.][kt_] and
     // excludes the items of row users[q] (q) of ex_ptr / ex_idx (ex_ptr NULL: none).  Device pointers except items /
-    // scores, which live in `space`.
+    // scores, which live in `space`.  fac (NULL: none) [nblk_ * 32]: the ranking key of an item is fp32(score * fac[item]);
+    // qfac (NULL: none, needs fac) [query id]: a slot's returned scores are fp32(key * qfac[users[q]]), the order the keys'.
     int topn(const float* wp, uint32_t nu, const uint32_t* users, const uint32_t* ex_ptr, const uint32_t* ex_idx,
-             int32_t n_top, uint32_t* items, float* scores, mfx_memspace space, int item_slices);
+             int32_t n_top, uint32_t* items, float* scores, mfx_memspace space, int item_slices, const float* fac,
+             const float* qfac);
+    // fac_keep_ (when keep is set) and fac_cos_ (after similar_setup) from the device filter bytes keep (NULL: no filter)
+    int build_facs(const uint8_t* keep);
     int fold_solve(int64_t nusers, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val, const float* W_init,
                    float* W_out, int32_t* sweeps_done, int32_t n_top, uint32_t* items, float* scores, mfx_memspace space);
     int device_ = 0;
@@ -50,6 +60,13 @@ private:
     DevBuf<float> wp_, hp_;
     DevBuf<uint32_t> ex_ptr_, ex_idx_;
     bool has_ex_ = false;
+    // item filter (set_item_filter): the bytes, and 1 / NaN per item [nblk_ * 32] (null without a filter)
+    DevBuf<uint8_t> keep_;
+    DevBuf<float> fac_keep_;
+    // item-to-item (similar_setup): H as a query operand [cols_][kt_], squared norms and inverse norms [cols_], 0 .. cols_
+    // (row pointers and indices of the identity exclusion), inverse norms with NaN at the filtered items [nblk_ * 32]
+    DevBuf<float> hq_, sim_n2_, sim_c_, fac_cos_;
+    DevBuf<uint32_t> sim_id_;
     // fold-in: model (-1 = not set up, kFoldBlock = block sweeps), H row-major [cols_ + 1][k_] with a zero last row, base Gramian [k_][k_] (implicit)
     int fold_model_ = -1;
     float fold_lambda_ = 0.f, fold_alpha_ = 0.f;

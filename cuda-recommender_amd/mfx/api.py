@@ -751,6 +751,7 @@ class Recommender:
             raise ValueError(f"W and H disagree on k ({k} vs {k2})")
         self.rows, self.cols, self.k, self.layout = int(rows), int(cols), int(k), layout
         self._keep = []
+        self._similar = False  # similar_setup() done
         ex = None
         if dev:
             import torch
@@ -878,6 +879,77 @@ class Recommender:
             L.check(L.lib().mfx_rec_fold_in(self.handle, n, nnz, _vp(ptr), _vp(idx), _vp(val), _vp(W), n_top, _vp(items),
                                             _vp(scores), L.MFX_HOST))
         return (items, scores, W, done) if return_sweeps else (items, scores, W)
+
+    def set_item_filter(self, keep):
+        """Only the items with a non-zero keep[i] are returned by every later query, fold_in and similar_items
+        (mfx_rec_set_item_filter).  keep: bool / uint8 numpy array or GPU tensor of length cols (copied), or None to
+        remove the filter."""
+        if keep is None:
+            L.check(L.lib().mfx_rec_set_item_filter(self.handle, None, L.MFX_HOST))
+            return
+        if tuple(keep.shape) != (self.cols,):
+            raise ValueError(f"keep must have one entry per item ({self.cols})")
+        if _is_dev(keep):
+            assert keep.is_contiguous() and keep.element_size() == 1, "keep: contiguous bool / uint8 tensor"
+            L.check(L.lib().mfx_rec_set_item_filter(self.handle, C.c_void_p(int(keep.data_ptr())), L.MFX_DEVICE))
+            return
+        keep = np.asarray(keep)
+        if keep.dtype != np.bool_ and keep.dtype != np.uint8:
+            raise ValueError("keep must be bool or uint8")
+        keep = np.ascontiguousarray(keep).view(np.uint8)
+        L.check(L.lib().mfx_rec_set_item_filter(self.handle, _vp(keep), L.MFX_HOST))
+
+    def similar_setup(self):
+        """Prepares item-to-item queries (mfx_rec_similar_setup): one more copy of H on the device, and the item norms."""
+        L.check(L.lib().mfx_rec_similar_setup(self.handle))
+        self._similar = True
+
+    def item_norms(self):
+        """(n2, c) float32 [cols]: the squared norm of every row of H as the score chain gives it, and the 1 / sqrt(n2) that
+        the cosine of similar_items multiplies with (0 where n2 is 0 or not finite), bit for bit (mfx_rec_item_norms)."""
+        n2, c = np.empty(self.cols, np.float32), np.empty(self.cols, np.float32)
+        L.check(L.lib().mfx_rec_item_norms(self.handle, _vp(n2), _vp(c), L.MFX_HOST))
+        return n2, c
+
+    def similar_items(self, n_top: int, items=None, metric: int = L.MFX_SIM_COSINE, exclude_self: bool = True,
+                      item_slices: int = 0, on_device: bool = False):
+        """The n_top items most similar to each of `items` (None: all items in order) by MFX_SIM_COSINE or MFX_SIM_DOT ->
+        (items uint32 [Q, n_top], scores float32 [Q, n_top]), padded like query (mfx_rec_similar).  exclude_self: an item
+        is not its own neighbour.  The item filter applies, the exclude matrix does not.  An `items` tensor on the GPU
+        or on_device=True keeps everything on the device, as in query."""
+        if not self._similar:
+            self.similar_setup()
+        if _is_dev(items) or on_device:
+            import torch
+            dev = torch.device("cuda", self.device)
+            if items is not None:
+                if not _is_dev(items):
+                    items = torch.from_numpy(np.ascontiguousarray(items, np.uint32).view(np.int32)).to(dev)
+                assert items.is_contiguous() and items.element_size() == 4, "items: contiguous 32-bit tensor"
+                n = int(items.numel())
+                pq = C.c_void_p(int(items.data_ptr())) if n else None
+            else:
+                n, pq = self.cols, None
+            out = torch.empty((n, n_top), dtype=torch.int32, device=dev)
+            scores = torch.empty((n, n_top), dtype=torch.float32, device=dev)
+            if n:
+                L.check(L.lib().mfx_rec_similar(self.handle, n, pq, int(metric), int(bool(exclude_self)), n_top,
+                                                C.c_void_p(int(out.data_ptr())), C.c_void_p(int(scores.data_ptr())), L.MFX_DEVICE,
+                                                item_slices))
+            return out, scores
+        if items is None:
+            n, pq, keep = self.cols, None, None
+        else:
+            keep = np.ascontiguousarray(np.asarray(items), dtype=np.int64)
+            if keep.ndim != 1 or (keep.size and (keep.min() < 0 or keep.max() >= 2 ** 32)):
+                raise ValueError("items must be a 1-D array of non-negative 32-bit ids")
+            keep = keep.astype(np.uint32)
+            n, pq = int(keep.size), _vp(keep)
+        out = np.empty((n, n_top), np.uint32)
+        scores = np.empty((n, n_top), np.float32)
+        L.check(L.lib().mfx_rec_similar(self.handle, n, pq, int(metric), int(bool(exclude_self)), n_top, _vp(out), _vp(scores),
+                                        L.MFX_HOST, item_slices))
+        return out, scores
 
     def fold_in_times(self) -> dict:
         """Seconds of the last fold_in call by phase (mfx_rec_fold_in_times): {"build", "solve", "score"}."""

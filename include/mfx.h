@@ -386,6 +386,37 @@ int mfx_rec_fold_in_warm(mfx_rec_t r, int64_t nusers, int64_t nnz, const uint32_
 /* Wall-clock seconds of the last mfx_rec_fold_in / mfx_rec_fold_in_warm on r, each phase ending in a stream synchronisation: [0] host build
  * (query upload, checks, the host-side split into work items), [1] solve, [2] score (packing, top-N, copies out). */
 int mfx_rec_fold_in_times(mfx_rec_t r, double seconds[3]);
+/* Item filter: keep [cols] bytes in `space`, non-zero = the item may be returned; NULL removes the filter.  Copied.
+ * Applies to every later mfx_rec_query, mfx_rec_fold_in, mfx_rec_fold_in_warm and mfx_rec_similar on r until replaced:
+ * the result is the unfiltered ranking with the filtered items removed and the list refilled, score bits unchanged
+ * (the fold-in solve still sees all of the user's entries).  It works beside the exclude matrix of mfx_rec_create, not
+ * instead of it.  MFX_ERR_INVALID: a bad memory space; the handle keeps the filter it had. */
+int mfx_rec_set_item_filter(mfx_rec_t r, const uint8_t* keep, mfx_memspace space);
+/* Item-to-item similarity: the n_top rows of H nearest to row q of H.  s(q, i) is the score chain of mfx_rec_query with
+ * H[q] in the place of W[u]; n2[i] = s(i, i), the same chain; c[i] = an fp32 approximation of 1 / sqrt(n2[i]) within 2 ulp
+ * of the fp64 value rounded to fp32, +0 where n2[i] is 0 or not finite. */
+typedef enum mfx_rec_metric {
+    MFX_SIM_DOT = 0,    /* ranking key and returned score: s(q, i) */
+    MFX_SIM_COSINE = 1  /* ranking key: key = fp32(s(q, i) * c[i]), one rounding, subnormals kept; returned score:
+                           fp32(key * c[q]).  A returned cosine may exceed 1 by an ulp or two; it is not clamped. */
+} mfx_rec_metric;
+/* Prepares item-to-item queries on r: the rows of H as a query operand (from the handle's own packed copy: the bits it
+ * scores with, either layout; one more copy of H on the device) and the per-item n2 and c.  Idempotent. */
+int mfx_rec_similar_setup(mfx_rec_t r);
+/* The n2 [cols] and c [cols] that mfx_rec_similar uses, bit for bit; either may be NULL.  MFX_ERR_INVALID before
+ * mfx_rec_similar_setup or with a bad memory space. */
+int mfx_rec_item_norms(mfx_rec_t r, float* n2, float* c, mfx_memspace space);
+/* The n_top items most similar to each of nq query items.  query_items: NULL means 0 .. nq-1; any order, duplicates
+ * allowed.  items [nq][n_top], scores [nq][n_top] or NULL; `space` applies to all three; item_slices as in mfx_rec_query.
+ * Order: key descending, then item ascending (-0 == +0); NaN keys are never returned; two different keys that round to
+ * the same returned score stay in key order.  Padding as in mfx_rec_query.  exclude_self != 0: item q is not returned for
+ * query q (other items with the same row are).  The exclude matrix of mfx_rec_create plays no part; the item filter
+ * does, and a filtered-out item can still be a query.  The result does not depend on the batch, its order,
+ * item_slices, the factor layout or host / device pointers.
+ * MFX_ERR_INVALID, the handle left usable: before mfx_rec_similar_setup, an unknown metric, n_top outside 1..1024,
+ * item_slices * n_top > 8192, a query item >= cols (checked on the device), a bad memory space. */
+int mfx_rec_similar(mfx_rec_t r, int64_t nq, const uint32_t* query_items, int metric, int exclude_self, int32_t n_top,
+                    uint32_t* items, float* scores, mfx_memspace space, int item_slices);
 int mfx_rec_destroy(mfx_rec_t r);
 
 /* ------------------------------------------------------------------------------------
