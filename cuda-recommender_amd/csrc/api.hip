@@ -584,6 +584,27 @@ int mfx_rec_similar(mfx_rec_t r, int64_t nq, const uint32_t* query_items, int me
         return r->impl->similar(nq, query_items, metric, exclude_self, n_top, items, scores, space, item_slices);
     });
 }
+int mfx_rec_rank(mfx_rec_t r, int64_t npairs, const uint32_t* users, const uint32_t* items, uint32_t* ranks, float* scores,
+                 uint32_t* n_eligible, mfx_memspace space, int item_slices) {
+    return guarded("mfx_rec_rank", [&]() -> int {
+        MFX_REQUIRE(r && r->impl, "null recommender");
+        return r->impl->rank(npairs, users, items, ranks, scores, n_eligible, space, item_slices);
+    });
+}
+int mfx_rec_rank_times(mfx_rec_t r, double seconds[3]) {
+    return guarded("mfx_rec_rank_times", [&]() -> int {
+        MFX_REQUIRE(r && r->impl && seconds, "null recommender or seconds");
+        r->impl->rank_times(seconds);
+        return MFX_OK;
+    });
+}
+int mfx_rec_evaluate(mfx_rec_t r, const mfx_coo* T, float min_rating, int32_t n_cut, const int32_t* cutoffs, double* out,
+                     double* mrr, double* auc, int64_t* users_evaluated, int64_t* auc_users, mfx_memspace space) {
+    return guarded("mfx_rec_evaluate", [&]() -> int {
+        MFX_REQUIRE(r && r->impl, "null recommender");
+        return r->impl->evaluate(T, min_rating, n_cut, cutoffs, out, mrr, auc, users_evaluated, auc_users, space);
+    });
+}
 int mfx_rec_destroy(mfx_rec_t r) {
     return guarded("mfx_rec_destroy", [&]() -> int {
         if (!r) return MFX_OK;

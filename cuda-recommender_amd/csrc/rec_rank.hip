@@ -1,0 +1,399 @@
+// rec_rank.hip -- exact catalogue ranks of given (user, item) pairs (mfx_rec_rank) and full-rank evaluation
+// (mfx_rec_evaluate) on gfx950.
+//
+// The rank of pair (u, i) is the number of items eligible for u that order before i in the total order of mfx_rec_query
+// (key descending, then item ascending; -0 == +0; NaN keys are never eligible), so it is the position at which a query
+// for u returns i.  Three kernels, no list, no sort:
+//
+//   mfx_rec_target_keys   one thread per pair: the score of (u, i) as the explicit fp32 FMA chain over t ascending from
+//                         the packed W and the rows of H read back from the tiles (the bits the MFMA chain gives, as
+//                         mfx_rec_item_norms relies on), times the item's factor when a filter is set: the pair's key.
+//   mfx_rec_count         the pass of mfx_rec_topn with the selection taken out: same workgroup (128 slots x one item
+//                         slice), same double-buffered LDS stages of packed H, same W-in-registers MFMA loop and chunks
+//                         for k > 128.  A slot is a pair; its lane carries the target's key and id and two counters, and
+//                         every score costs a NaN test and the order compare: how many items with a non-NaN key, how
+//                         many of them before the target.  Item slices add into the pair's counters with integer
+//                         atomics, which no order can change.
+//   mfx_rec_rank_fix      one wave per pair walks the user's exclusion row: every distinct id with a non-NaN key leaves
+//                         the eligible count, every one that orders before the target leaves the rank, and the target
+//                         found in the row, or a NaN target key, makes the pair ineligible (rank 0xFFFFFFFF).
+//
+// A slot per pair rather than per user with several targets in registers: the pass is then independent of how the
+// batch groups its users, and the per-score work stays two compares; a user with t targets costs t slots.
+//
+// mfx_rec_evaluate builds the distinct (user, item) pairs of the held-out set on the host, ranks them in one
+// mfx_rec_rank, and forms every metric in fp64 on the host from the ranks and eligible counts alone.
+#include <algorithm>
+#include <cmath>
+#include <vector>
+
+#include "ccd_kernels.hpp"  // check_index_range
+#include "rec_tiles.hpp"
+#include "recommend.hpp"
+
+namespace mfx {
+
+namespace {
+
+struct RankArgs {
+    const float* wp;         // [rows][kt]
+    const float* hp;         // [nblk][nch][2*KC][32]
+    const uint32_t* users;   // [np]
+    const uint32_t* items;   // [np]
+    const float* tkey;       // [np] key of the pair's target
+    uint32_t np, cols;
+    int kt, nch, nblk, bps;
+    uint32_t* cnt;           // [np][2]: items with a non-NaN key, items ordered before the target (zeroed; slices add)
+    const float* fac;        // FAC only: [nblk * 32] per-item factor of the ranking key
+};
+
+// The score chain of a packed W row and a row of H read back from the tiles (hq: [cols][kt], the bits of the tiles): fma over
+// t = 0 .. k-1 ascending from +0.  A row is contiguous, so a lane's gather is k / 4 16-byte loads from two or three cache
+// lines rather than k lines of the tile layout.
+__device__ inline float chain_score(const float* wr, const float* hr, int k, int kt) {
+    float acc = 0.f;
+    int t = 0;
+    if ((kt & 3) == 0) {  // (rows are 16-byte aligned)
+        for (; t + 4 <= k; t += 4) {
+            const float4 h = *reinterpret_cast<const float4*>(hr + t);
+            acc = __builtin_fmaf(h.x, wr[t], acc);
+            acc = __builtin_fmaf(h.y, wr[t + 1], acc);
+            acc = __builtin_fmaf(h.z, wr[t + 2], acc);
+            acc = __builtin_fmaf(h.w, wr[t + 3], acc);
+        }
+    }
+    for (; t < k; ++t) acc = __builtin_fmaf(hr[t], wr[t], acc);
+    return acc;
+}
+
+__global__ void mfx_rec_target_keys(const float* wp, const float* hq, const uint32_t* users, const uint32_t* items, uint32_t np,
+                                    int k, int kt, const float* fac, float* tkey, float* scores) {
+    for (size_t p = (size_t) blockIdx.x * blockDim.x + threadIdx.x; p < np; p += (size_t) gridDim.x * blockDim.x) {
+        const uint32_t item = items[p];
+        const float s = chain_score(wp + (size_t) users[p] * kt, hq + (size_t) item * kt, k, kt);
+        if (scores) scores[p] = s;
+        tkey[p] = fac ? s * fac[item] : s;
+    }
+}
+
+// One LDS stage (NF4 16-byte vectors, contiguous in the packed H) through registers, as in mfx_rec_topn: the loads of stage
+// s+1 are in flight while the MFMAs of stage s run.  The registers are a plain vector type: as float4 the compiler keeps
+// stg[] of KC = 32 / 64 in scratch (32 / 64 bytes per lane stored and reloaded every stage), which costs the pass 3 % at
+// k = 64 and 10 % at k = 128.
+using f32x4 = __attribute__((ext_vector_type(4))) float;
+template <int NV, int NF4>
+__device__ inline void load_stage(f32x4 (&stg)[NV], const float* src, int tid) {
+    const f32x4* s4 = reinterpret_cast<const f32x4*>(src);
+#pragma unroll
+    for (int v = 0; v < NV; ++v) {
+        const int e = tid + v * kRecThreads;
+        if (NF4 % kRecThreads == 0 || e < NF4) stg[v] = s4[e];
+    }
+}
+template <int NV, int NF4>
+__device__ inline void store_stage(const f32x4 (&stg)[NV], float* dst, int tid) {
+    f32x4* d4 = reinterpret_cast<f32x4*>(dst);
+#pragma unroll
+    for (int v = 0; v < NV; ++v) {
+        const int e = tid + v * kRecThreads;
+        if (NF4 % kRecThreads == 0 || e < NF4) d4[e] = stg[v];
+    }
+}
+
+template <int KC, bool FAC>
+__global__ __launch_bounds__(kRecThreads) void mfx_rec_count(RankArgs a) {
+    constexpr int STAGE = 2 * KC * kTile;        // floats per LDS stage
+    constexpr int NF4 = STAGE / 4;
+    constexpr int NV = (NF4 + kRecThreads - 1) / kRecThreads;
+    __shared__ __attribute__((aligned(16))) float hb[2][STAGE];
+
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, h = lane >> 5, j = lane & 31;
+    const uint32_t q = blockIdx.x * kRecUsers + wave * 32 + j;
+    const bool valid = q < a.np;
+    const uint32_t u = valid ? a.users[q] : 0;
+    const uint32_t ti = valid ? a.items[q] : 0;
+    const float tk = valid ? a.tkey[q] : 0.f;
+    const int b0 = (int) blockIdx.y * a.bps;
+    const int b1 = min(a.nblk, b0 + a.bps);
+    const int nst = b1 > b0 ? (b1 - b0) * a.nch : 0;
+
+    f32x4 stg[NV];
+    uint32_t elig = 0, before = 0;
+    float wf[KC];
+    f32x16 acc;
+    if (nst > 0) {
+        load_stage<NV, NF4>(stg, a.hp + (size_t) b0 * a.nch * STAGE, tid);
+        store_stage<NV, NF4>(stg, hb[0], tid);
+    }
+    __syncthreads();
+    for (int st = 0; st < nst; ++st) {
+        const int c = st % a.nch;
+        const int blk = b0 + st / a.nch;
+        if (st + 1 < nst) load_stage<NV, NF4>(stg, a.hp + (size_t) (b0 * a.nch + st + 1) * STAGE, tid);
+        if (a.nch > 1 || st == 0) {
+            const float* wr = a.wp + (size_t) u * a.kt + c * 2 * KC + h;
+#pragma unroll
+            for (int s = 0; s < KC; ++s) wf[s] = valid ? wr[2 * s] : 0.f;
+        }
+        if (c == 0) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+        }
+        const float* hbuf = hb[st & 1] + h * kTile + j;
+#pragma unroll
+        for (int s = 0; s < KC; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(hbuf[2 * s * kTile], wf[s], acc, 0, 0, 0);
+
+        if (c == a.nch - 1) {
+            const uint32_t ibase = (uint32_t) blk * kTile + 4 * h;
+            if (FAC) {  // a lane's 16 items are four runs of four ids: one 16-byte load of the factors per run
+                const float4* f4 = reinterpret_cast<const float4*>(a.fac + ibase);
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    const float4 f = f4[2 * g];
+                    acc[4 * g] *= f.x; acc[4 * g + 1] *= f.y; acc[4 * g + 2] *= f.z; acc[4 * g + 3] *= f.w;
+                }
+            }
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const uint32_t item = ibase + (r & 3) + 8 * (r >> 2);
+                const float key = acc[r];
+                const bool in = item < a.cols;  // (the packed padding past cols scores 0, not NaN)
+                elig += (uint32_t) (in && key == key);
+                before += (uint32_t) (in && beats(key, item, tk, ti));
+            }
+        }
+        if (st + 1 < nst) store_stage<NV, NF4>(stg, hb[(st + 1) & 1], tid);
+        __syncthreads();
+    }
+    elig += __shfl_xor(elig, 32);
+    before += __shfl_xor(before, 32);
+    if (valid && h == 0) {
+        atomicAdd(a.cnt + 2 * (size_t) q, elig);
+        atomicAdd(a.cnt + 2 * (size_t) q + 1, before);
+    }
+}
+
+// One wave per pair: the exclusion row of the pair's user comes off the counts, and the pair's results are written.
+__global__ __launch_bounds__(kRecThreads) void mfx_rec_rank_fix(const float* wp, const float* hq, const uint32_t* users,
+                                                                const uint32_t* items, const float* tkey, const uint32_t* cnt,
+                                                                uint32_t np, int k, int kt, const uint32_t* ex_ptr,
+                                                                const uint32_t* ex_idx, const float* fac, uint32_t* ranks,
+                                                                uint32_t* n_eligible) {
+    const int lane = threadIdx.x & 63;
+    const size_t p = (size_t) blockIdx.x * kRecWaves + (threadIdx.x >> 6);
+    if (p >= np) return;
+    const uint32_t u = __builtin_amdgcn_readfirstlane(users[p]), ti = items[p];  // (one pair per wave: the W row is a scalar operand)
+    const float tk = tkey[p];
+    int de = 0, db = 0, hit = 0;
+    if (ex_ptr) {
+        const uint32_t lo = ex_ptr[u], hi = ex_ptr[u + 1];
+        const float* wr = wp + (size_t) u * kt;
+        for (uint32_t x = lo + lane; x < hi; x += 64) {
+            const uint32_t e = ex_idx[x];
+            if (x > lo && ex_idx[x - 1] == e) continue;  // (ids are non-decreasing within a row: a repeated id counts once)
+            float key = chain_score(wr, hq + (size_t) e * kt, k, kt);
+            if (fac) key *= fac[e];
+            de += key == key;
+            db += beats(key, e, tk, ti);
+            hit |= e == ti;
+        }
+    }
+    de = wave_sum(de);
+    db = wave_sum(db);
+    hit = wave_sum(hit);
+    if (lane == 0) {
+        ranks[p] = (hit || tk != tk) ? kPad : cnt[2 * p + 1] - (uint32_t) db;
+        if (n_eligible) n_eligible[p] = cnt[2 * p] - (uint32_t) de;
+    }
+}
+
+template <int KC>
+int launch_count(const RankArgs& a, int slices, hipStream_t st) {
+    const dim3 grid((a.np + kRecUsers - 1) / kRecUsers, slices);
+    if (a.fac) hipLaunchKernelGGL((mfx_rec_count<KC, true>), grid, dim3(kRecThreads), 0, st, a);
+    else hipLaunchKernelGGL((mfx_rec_count<KC, false>), grid, dim3(kRecThreads), 0, st, a);
+    MFX_LAUNCH_CHECK();
+    return MFX_OK;
+}
+
+struct Events {  // four stream events around the three phases
+    hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
+    int create() {
+        for (auto& x : e) MFX_HIP(hipEventCreate(&x));
+        return MFX_OK;
+    }
+    ~Events() {
+        for (auto x : e)
+            if (x) (void) hipEventDestroy(x);
+    }
+};
+
+}  // namespace
+
+int Recommender::rank(int64_t npairs, const uint32_t* users, const uint32_t* items, uint32_t* ranks, float* scores,
+                      uint32_t* n_eligible, mfx_memspace space, int item_slices) {
+    MFX_REQUIRE(npairs >= 0 && npairs < (int64_t) 0xFFFFFFFFll, "mfx_rec_rank: bad npairs %lld", (long long) npairs);
+    MFX_REQUIRE(space == MFX_HOST || space == MFX_DEVICE, "mfx_rec_rank: bad memory space");
+    MFX_REQUIRE(item_slices >= 0, "mfx_rec_rank: item_slices must be >= 0 (got %d)", item_slices);
+    if (npairs == 0) return MFX_OK;
+    MFX_REQUIRE(users && items, "mfx_rec_rank: users or items is NULL");
+    MFX_REQUIRE(ranks, "mfx_rec_rank: ranks is NULL");
+    MFX_TRY(use_device(device_));
+    hipStream_t st = st_;
+    const uint32_t np = (uint32_t) npairs;
+    const bool host = space == MFX_HOST;
+
+    DevBuf<uint32_t> d_users, d_items, d_ranks, d_nel, cnt;
+    DevBuf<float> d_scores, tkey;
+    const uint32_t* du = users;
+    const uint32_t* di = items;
+    if (host) {
+        MFX_TRY(d_users.alloc(np)); MFX_TRY(d_users.upload(users, np, MFX_HOST, st));
+        MFX_TRY(d_items.alloc(np)); MFX_TRY(d_items.upload(items, np, MFX_HOST, st));
+        du = d_users.get();
+        di = d_items.get();
+    }
+    MFX_TRY(check_index_range(du, np, (uint32_t) rows_, "mfx_rec_rank: user id", st));
+    MFX_TRY(check_index_range(di, np, (uint32_t) cols_, "mfx_rec_rank: item id", st));
+    uint32_t* orank = ranks;
+    float* oscore = scores;
+    uint32_t* onel = n_eligible;
+    if (host) {
+        MFX_TRY(d_ranks.alloc(np));
+        orank = d_ranks.get();
+        if (scores) { MFX_TRY(d_scores.alloc(np)); oscore = d_scores.get(); }
+        if (n_eligible) { MFX_TRY(d_nel.alloc(np)); onel = d_nel.get(); }
+    }
+    MFX_TRY(ensure_hq());
+    MFX_TRY(tkey.alloc(np));
+    MFX_TRY(cnt.alloc_zero((size_t) np * 2, st));
+    Events ev;
+    MFX_TRY(ev.create());
+
+    // slices: forced, or enough workgroups for about two per CU
+    int slices = item_slices;
+    if (slices == 0) {
+        const int64_t pblocks = ((int64_t) np + kRecUsers - 1) / kRecUsers;
+        const int64_t want = 2 * cus_;
+        slices = pblocks >= want ? 1 : (int) ((want + pblocks - 1) / pblocks);
+        slices = std::max(1, std::min(slices, std::max(1, nblk_ / 4)));
+    }
+    slices = std::min(slices, 65535);  // (grid.y)
+    const int bps = (nblk_ + slices - 1) / slices;
+    slices = (nblk_ + bps - 1) / bps;  // no empty slices
+    const float* fac = fac_keep_.get();
+
+    MFX_HIP(hipEventRecord(ev.e[0], st));
+    hipLaunchKernelGGL(mfx_rec_target_keys, dim3(grid_for(np)), dim3(256), 0, st, wp_.get(), hq_.get(), du, di, np, (int) k_, kt_, fac,
+                       tkey.get(), oscore);
+    MFX_LAUNCH_CHECK();
+    MFX_HIP(hipEventRecord(ev.e[1], st));
+    RankArgs a{};
+    a.wp = wp_.get(); a.hp = hp_.get();
+    a.users = du; a.items = di; a.tkey = tkey.get();
+    a.np = np; a.cols = (uint32_t) cols_;
+    a.kt = kt_; a.nch = nch_; a.nblk = nblk_; a.bps = bps;
+    a.cnt = cnt.get();
+    a.fac = fac;
+    switch (kc_) {
+        case 1: MFX_TRY(launch_count<1>(a, slices, st)); break;
+        case 2: MFX_TRY(launch_count<2>(a, slices, st)); break;
+        case 4: MFX_TRY(launch_count<4>(a, slices, st)); break;
+        case 8: MFX_TRY(launch_count<8>(a, slices, st)); break;
+        case 16: MFX_TRY(launch_count<16>(a, slices, st)); break;
+        case 32: MFX_TRY(launch_count<32>(a, slices, st)); break;
+        default: MFX_TRY(launch_count<64>(a, slices, st)); break;
+    }
+    MFX_HIP(hipEventRecord(ev.e[2], st));
+    hipLaunchKernelGGL(mfx_rec_rank_fix, dim3((np + kRecWaves - 1) / kRecWaves), dim3(kRecThreads), 0, st, wp_.get(), hq_.get(), du, di,
+                       tkey.get(), cnt.get(), np, (int) k_, kt_, has_ex_ ? ex_ptr_.get() : nullptr, ex_idx_.get(), fac,
+                       orank, onel);
+    MFX_LAUNCH_CHECK();
+    MFX_HIP(hipEventRecord(ev.e[3], st));
+    if (host) {
+        MFX_HIP(hipMemcpyAsync(ranks, orank, sizeof(uint32_t) * np, hipMemcpyDeviceToHost, st));
+        if (scores) MFX_HIP(hipMemcpyAsync(scores, oscore, sizeof(float) * np, hipMemcpyDeviceToHost, st));
+        if (n_eligible) MFX_HIP(hipMemcpyAsync(n_eligible, onel, sizeof(uint32_t) * np, hipMemcpyDeviceToHost, st));
+    }
+    MFX_HIP(hipStreamSynchronize(st));
+    for (int i = 0; i < 3; ++i) {
+        float ms = 0.f;
+        MFX_HIP(hipEventElapsedTime(&ms, ev.e[i], ev.e[i + 1]));
+        rank_s_[i] = 1e-3 * ms;
+    }
+    return MFX_OK;
+}
+
+int Recommender::evaluate(const mfx_coo* T, float min_rating, int32_t n_cut, const int32_t* cutoffs, double* out, double* mrr,
+                          double* auc, int64_t* users_evaluated, int64_t* auc_users, mfx_memspace space) {
+    MFX_REQUIRE(T && T->nnz >= 0 && T->nnz < (int64_t) 0xFFFFFFFFll, "mfx_rec_evaluate: bad test set");
+    MFX_REQUIRE(T->nnz == 0 || (T->row && T->col && T->val), "mfx_rec_evaluate: null test array");
+    MFX_REQUIRE(!std::isnan(min_rating), "mfx_rec_evaluate: min_rating is NaN");
+    MFX_REQUIRE(n_cut >= 0 && (n_cut == 0 || (cutoffs && out)), "mfx_rec_evaluate: n_cut = %d needs cutoffs and out", n_cut);
+    for (int32_t c = 0; c < n_cut; ++c) MFX_REQUIRE(cutoffs[c] >= 1, "mfx_rec_evaluate: cutoff %d is %d (>= 1 required)", c, cutoffs[c]);
+    MFX_REQUIRE(space == MFX_HOST || space == MFX_DEVICE, "mfx_rec_evaluate: bad memory space");
+    MFX_TRY(use_device(device_));
+    const size_t nnz = (size_t) T->nnz;
+    std::vector<uint32_t> hr, hc;
+    std::vector<float> hv;
+    const uint32_t* row = T->row;
+    const uint32_t* col = T->col;
+    const float* val = T->val;
+    if (space == MFX_DEVICE && nnz) {
+        hr.resize(nnz); hc.resize(nnz); hv.resize(nnz);
+        MFX_HIP(hipMemcpyAsync(hr.data(), T->row, sizeof(uint32_t) * nnz, hipMemcpyDeviceToHost, st_));
+        MFX_HIP(hipMemcpyAsync(hc.data(), T->col, sizeof(uint32_t) * nnz, hipMemcpyDeviceToHost, st_));
+        MFX_HIP(hipMemcpyAsync(hv.data(), T->val, sizeof(float) * nnz, hipMemcpyDeviceToHost, st_));
+        MFX_HIP(hipStreamSynchronize(st_));
+        row = hr.data(); col = hc.data(); val = hv.data();
+    }
+    // the distinct (user, item) pairs with value >= min_rating, by user: R_u is one run
+    std::vector<uint64_t> pairs;
+    pairs.reserve(nnz);
+    for (size_t p = 0; p < nnz; ++p)
+        if (val[p] >= min_rating) pairs.push_back((uint64_t) row[p] << 32 | col[p]);
+    std::sort(pairs.begin(), pairs.end());
+    pairs.erase(std::unique(pairs.begin(), pairs.end()), pairs.end());
+    const size_t np = pairs.size();
+    std::vector<uint32_t> pu(np), pi(np), ranks(np), nel(np);
+    for (size_t p = 0; p < np; ++p) { pu[p] = (uint32_t) (pairs[p] >> 32); pi[p] = (uint32_t) pairs[p]; }
+    MFX_TRY(rank((int64_t) np, pu.data(), pi.data(), ranks.data(), nullptr, nel.data(), MFX_HOST, 0));
+
+    std::vector<TopnAcc> acc((size_t) n_cut);
+    double mrr_sum = 0, auc_sum = 0;
+    int64_t kept = 0, auc_kept = 0;
+    std::vector<uint32_t> rk;
+    for (size_t lo = 0; lo < np;) {
+        size_t hi = lo + 1;
+        while (hi < np && pu[hi] == pu[lo]) ++hi;
+        const size_t nrel = hi - lo;
+        rk.clear();
+        for (size_t p = lo; p < hi; ++p)
+            if (ranks[p] != kPad) rk.push_back(ranks[p]);
+        std::sort(rk.begin(), rk.end());  // the eligible targets in ranking order: a_p is the index
+        ++kept;
+        for (int32_t c = 0; c < n_cut; ++c) {
+            const size_t nh = std::lower_bound(rk.begin(), rk.end(), (uint32_t) cutoffs[c]) - rk.begin();
+            acc[c].add(rk.data(), nh, nrel, cutoffs[c]);
+        }
+        if (!rk.empty()) {
+            mrr_sum += 1.0 / (1.0 + (double) rk[0]);
+            const double neg = (double) nel[lo] - (double) rk.size();
+            if (neg > 0) {
+                double s = 0;
+                for (size_t x = 0; x < rk.size(); ++x) s += (neg - ((double) rk[x] - (double) x)) / neg;
+                auc_sum += s / (double) rk.size();
+                ++auc_kept;
+            }
+        }
+        lo = hi;
+    }
+    for (int32_t c = 0; c < n_cut; ++c) acc[c].mean(out + 4 * (size_t) c);
+    if (mrr) *mrr = kept ? mrr_sum / (double) kept : 0.0;
+    if (auc) *auc = auc_kept ? auc_sum / (double) auc_kept : 0.0;
+    if (users_evaluated) *users_evaluated = kept;
+    if (auc_users) *auc_users = auc_kept;
+    return MFX_OK;
+}
+
+}  // namespace mfx

@@ -42,24 +42,16 @@
 
 #include "als_solver.hpp"   // AlsHalf and the half-sweep launchers (fold-in)
 #include "ccd_kernels.hpp"  // check_index_range
+#include "rec_tiles.hpp"   // the workgroup shape, the total order
 #include "recommend.hpp"
-
-#define MFX_LAUNCH_CHECK() MFX_HIP(hipGetLastError())
 
 namespace mfx {
 
 namespace {
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-
-constexpr int kRecWaves = 4;                 // waves per workgroup
-constexpr int kRecThreads = 64 * kRecWaves;
-constexpr int kRecUsers = 32 * kRecWaves;    // users per workgroup
-constexpr int kTile = 32;                    // items per LDS stage (one 32 x 32 MFMA tile per wave)
 constexpr int kScr = 256;                    // per-wave LDS sort scratch (entries); longer lists sort in the workspace
 constexpr int kMaxMerge = 8192;              // slices * N of one merge (64 KiB of LDS)
 constexpr int kMaxTop = 1024, kMaxK = 1024;
-constexpr uint32_t kPad = 0xFFFFFFFFu;
 constexpr size_t kWorkspaceCap = size_t(1) << 30;  // candidate lists of one launch (users are chunked under this)
 
 struct RecArgs {
@@ -78,10 +70,6 @@ struct RecArgs {
     const float* fac;       // FAC only: [nblk * 32] per-item factor of the ranking key (NaN: the item is never returned)
     const float* qfac;      // NULL, or [query id]: factor of a slot's returned scores, applied where its final N leave
 };
-
-__device__ inline bool beats(float as, uint32_t ai, float bs, uint32_t bi) {
-    return as > bs || (as == bs && ai < bi);
-}
 
 // Every lane of the wave sees the memory operations every other lane issued before (LDS and global).
 __device__ inline void wave_sync() {
@@ -117,11 +105,6 @@ __device__ inline bool excluded(const uint32_t* ex, uint32_t lo, uint32_t hi, ui
         else hi = mid;
     }
     return lo < end && ex[lo] == item;
-}
-
-__device__ inline int wave_sum(int v) {
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
 }
 
 // One LDS stage (NF4 float4, contiguous in the packed H) through registers: the loads of stage s+1 are in flight
@@ -439,8 +422,6 @@ __global__ void mfx_rec_check_exclude(const uint32_t* rp, const uint32_t* ci, ui
     }
 }
 
-int grid_for(size_t n) { return (int) std::min<size_t>((n + 255) / 256, 4096); }
-
 template <int KC>
 int launch_topn(const RecArgs& a, int slices, hipStream_t st) {
     const dim3 grid((a.nq + kRecUsers - 1) / kRecUsers, slices);
@@ -620,6 +601,17 @@ int Recommender::similar_setup() {
     const int rc = build_facs(keep_.get());
     if (rc != MFX_OK) sim_c_.release();  // (not set up)
     return rc;
+}
+
+int Recommender::ensure_hq() {
+    if (hq_.get()) return MFX_OK;
+    DevBuf<float> hq;
+    MFX_TRY(hq.alloc((size_t) cols_ * kt_));
+    hipLaunchKernelGGL(mfx_rec_pack_hq, dim3(grid_for((size_t) cols_ * kt_)), dim3(256), 0, st_, hp_.get(), (uint32_t) cols_, (int) k_,
+                       2 * kc_, nch_, kt_, hq.get());
+    MFX_LAUNCH_CHECK();
+    hq_ = std::move(hq);
+    return MFX_OK;
 }
 
 int Recommender::item_norms(float* n2, float* c, mfx_memspace space) {
@@ -949,6 +941,28 @@ int Recommender::fold_solve(int64_t nusers, int64_t nnz, const uint32_t* ptr, co
     return MFX_OK;
 }
 
+void TopnAcc::add(const uint32_t* pos, size_t nhits, size_t nrel, int64_t n_top) {
+    ++kept;
+    double dcg = 0;
+    for (size_t x = 0; x < nhits; ++x) dcg += 1.0 / std::log2((double) pos[x] + 2.0);
+    double idcg = 0;
+    const int64_t ideal = std::min<int64_t>(n_top, (int64_t) nrel);
+    for (int64_t jj = 0; jj < ideal; ++jj) idcg += 1.0 / std::log2((double) jj + 2.0);
+    const double hits = (double) nhits;
+    hr += hits > 0 ? 1.0 : 0.0;
+    prec += hits / n_top;
+    rec += hits / (double) nrel;
+    ndcg += dcg / idcg;
+}
+
+void TopnAcc::mean(double out[4]) const {
+    const double d = kept ? (double) kept : 1.0;
+    out[0] = kept ? hr / d : 0.0;
+    out[1] = kept ? prec / d : 0.0;
+    out[2] = kept ? rec / d : 0.0;
+    out[3] = kept ? ndcg / d : 0.0;
+}
+
 int topn_metrics(int64_t nusers, const uint32_t* users, int32_t n_top, const uint32_t* items, const mfx_coo* T,
                  float min_rating, double out[4], int64_t* users_evaluated) {
     MFX_REQUIRE(nusers >= 0 && n_top >= 1 && (nusers == 0 || items) && T && out, "mfx_topn_metrics: bad argument");
@@ -967,36 +981,24 @@ int topn_metrics(int64_t nusers, const uint32_t* users, int32_t n_top, const uin
         std::sort(kv.second.begin(), kv.second.end());
         kv.second.erase(std::unique(kv.second.begin(), kv.second.end()), kv.second.end());
     }
-    double hr = 0, prec = 0, rec = 0, ndcg = 0;
-    int64_t kept = 0;
-    std::vector<uint32_t> seen;
+    TopnAcc acc;
+    std::vector<uint32_t> seen, pos;
     for (int64_t s = 0; s < nusers; ++s) {
         const std::vector<uint32_t>& R = rel[users ? users[s] : (uint32_t) s];
         if (R.empty()) continue;
-        ++kept;
         seen.clear();
-        double dcg = 0;
+        pos.clear();
         for (int32_t jj = 0; jj < n_top; ++jj) {
             const uint32_t it = items[(size_t) s * n_top + jj];
             if (it == kPad || !std::binary_search(R.begin(), R.end(), it)) continue;
             if (std::find(seen.begin(), seen.end(), it) != seen.end()) continue;  // a hit counts once
             seen.push_back(it);
-            dcg += 1.0 / std::log2((double) jj + 2.0);
+            pos.push_back((uint32_t) jj);
         }
-        double idcg = 0;
-        const int64_t ideal = std::min<int64_t>(n_top, (int64_t) R.size());
-        for (int64_t jj = 0; jj < ideal; ++jj) idcg += 1.0 / std::log2((double) jj + 2.0);
-        const double hits = (double) seen.size();
-        hr += hits > 0 ? 1.0 : 0.0;
-        prec += hits / n_top;
-        rec += hits / (double) R.size();
-        ndcg += dcg / idcg;
+        acc.add(pos.data(), pos.size(), R.size(), n_top);
     }
-    const double d = kept ? (double) kept : 1.0;
-    out[0] = kept ? hr / d : 0.0;
-    out[1] = kept ? prec / d : 0.0;
-    out[2] = kept ? rec / d : 0.0;
-    out[3] = kept ? ndcg / d : 0.0;
+    acc.mean(out);
+    const int64_t kept = acc.kept;
     if (users_evaluated) *users_evaluated = kept;
     return MFX_OK;
 }

@@ -35,6 +35,12 @@ public:
     int similar(int64_t nq, const uint32_t* query_items, int metric, int exclude_self, int32_t n_top, uint32_t* items, float* scores,
                 mfx_memspace space, int item_slices);
     void fold_in_times(double out[3]) const { for (int i = 0; i < 3; ++i) out[i] = fold_s_[i]; }
+    // mfx_rec_rank / mfx_rec_evaluate / mfx_rec_rank_times (rec_rank.hip)
+    int rank(int64_t npairs, const uint32_t* users, const uint32_t* items, uint32_t* ranks, float* scores, uint32_t* n_eligible,
+             mfx_memspace space, int item_slices);
+    int evaluate(const mfx_coo* T, float min_rating, int32_t n_cut, const int32_t* cutoffs, double* out, double* mrr, double* auc,
+                 int64_t* users_evaluated, int64_t* auc_users, mfx_memspace space);
+    void rank_times(double out[3]) const { for (int i = 0; i < 3; ++i) out[i] = rank_s_[i]; }
     ~Recommender();
 
 private:
@@ -47,6 +53,8 @@ private:
              const float* qfac);
     // fac_keep_ (when keep is set) and fac_cos_ (after similar_setup) from the device filter bytes keep (NULL: no filter)
     int build_facs(const uint8_t* keep);
+    // hq_ from the tiles unless it is there already (similar_setup builds it too): the rows of H that rank() gathers
+    int ensure_hq();
     int fold_solve(int64_t nusers, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val, const float* W_init,
                    float* W_out, int32_t* sweeps_done, int32_t n_top, uint32_t* items, float* scores, mfx_memspace space);
     int device_ = 0;
@@ -80,6 +88,17 @@ private:
     int32_t fold_sweeps_ = 0;
     float fold_tol_ = 0.f;
     double fold_s_[3] = {0, 0, 0};  // host build / solve / score seconds of the last fold-in
+    double rank_s_[3] = {0, 0, 0};  // device seconds of the last rank: target keys / counting pass / exclusion correction
+};
+
+// The sums behind {HR, precision, recall, NDCG} at one cutoff, shared by mfx_topn_metrics (positions read off a list) and
+// mfx_rec_evaluate (positions are ranks).  add(): one kept user, the 0-based positions below n_top of its distinct hits in
+// ascending order, and |R_u|.
+struct TopnAcc {
+    double hr = 0, prec = 0, rec = 0, ndcg = 0;
+    int64_t kept = 0;
+    void add(const uint32_t* pos, size_t nhits, size_t nrel, int64_t n_top);
+    void mean(double out[4]) const;
 };
 
 int topn_metrics(int64_t nusers, const uint32_t* users, int32_t n_top, const uint32_t* items, const mfx_coo* T,

@@ -137,6 +137,10 @@ SIGNATURES = {
     "mfx_rec_item_norms": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "mfx_rec_similar": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_int32, C.c_void_p, C.c_void_p, C.c_int,
                                   C.c_int]),
+    "mfx_rec_rank": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
+    "mfx_rec_rank_times": (C.c_int, [C.c_void_p, f64p]),
+    "mfx_rec_evaluate": (C.c_int, [C.c_void_p, C.POINTER(mfx_coo), C.c_float, C.c_int32, C.c_void_p, f64p, f64p, f64p, i64p, i64p,
+                                   C.c_int]),
     "mfx_rec_destroy": (C.c_int, [C.c_void_p]),
     "mfx_topn_metrics": (C.c_int, [C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(mfx_coo), C.c_float, f64p,
                                    i64p]),

@@ -719,6 +719,7 @@ def extract_shard(R: RatingData, row_lo: int, row_hi: int) -> RatingData:
 # top-N recommendation (mfx_rec_*) and ranking metrics (mfx_topn_metrics)
 # ---------------------------------------------------------------------------------------------
 PAD_ITEM = 0xFFFFFFFF  # item id of the slots a list could not fill (score -inf)
+PAD_RANK = 0xFFFFFFFF  # rank of a pair whose item is not eligible for its user (rank_of)
 
 
 def _is_dev(a) -> bool:
@@ -950,6 +951,73 @@ class Recommender:
         L.check(L.lib().mfx_rec_similar(self.handle, n, pq, int(metric), int(bool(exclude_self)), n_top, _vp(out), _vp(scores),
                                         L.MFX_HOST, item_slices))
         return out, scores
+
+    def rank_of(self, users, items, item_slices: int = 0, on_device: bool = False):
+        """Exact catalogue rank of each pair (users[p], items[p]) -> (ranks, scores float32, n_eligible), each [P]
+        (mfx_rec_rank).  ranks[p] is the position at which query returns the item for the user -- the number of eligible
+        items ordered before it -- or PAD_RANK when the item is excluded, filtered out or has a NaN key; scores[p] is the
+        score chain of the pair either way; n_eligible[p] counts the items eligible for the user.  numpy in: uint32
+        ranks and counts.  GPU tensors in (32-bit ids) or on_device=True: everything stays on the device and they are
+        int32 tensors holding the uint32 bits, as in query."""
+        if _is_dev(users) or _is_dev(items) or on_device:
+            import torch
+            dev = torch.device("cuda", self.device)
+
+            def put(a):
+                if not _is_dev(a):
+                    a = torch.from_numpy(np.ascontiguousarray(a, np.uint32).view(np.int32)).to(dev)
+                assert a.dim() == 1 and a.is_contiguous() and a.element_size() == 4, "pairs: contiguous 1-D 32-bit tensors"
+                return a
+            tu, ti = put(users), put(items)
+            if tu.numel() != ti.numel():
+                raise ValueError("users and items must have one entry per pair")
+            n = int(tu.numel())
+            ranks = torch.empty((n,), dtype=torch.int32, device=dev)
+            scores = torch.empty((n,), dtype=torch.float32, device=dev)
+            nel = torch.empty((n,), dtype=torch.int32, device=dev)
+            if n:
+                p = lambda t: C.c_void_p(int(t.data_ptr()))
+                L.check(L.lib().mfx_rec_rank(self.handle, n, p(tu), p(ti), p(ranks), p(scores), p(nel), L.MFX_DEVICE, item_slices))
+            return ranks, scores, nel
+        pu, pi = (np.ascontiguousarray(np.asarray(a), dtype=np.int64) for a in (users, items))
+        for a in (pu, pi):
+            if a.ndim != 1 or (a.size and (a.min() < 0 or a.max() >= 2 ** 32)):
+                raise ValueError("users and items must be 1-D arrays of non-negative 32-bit ids")
+        if pu.shape != pi.shape:
+            raise ValueError("users and items must have one entry per pair")
+        pu, pi = pu.astype(np.uint32), pi.astype(np.uint32)
+        n = int(pu.size)
+        ranks, scores, nel = np.empty(n, np.uint32), np.empty(n, np.float32), np.empty(n, np.uint32)
+        L.check(L.lib().mfx_rec_rank(self.handle, n, _vp(pu), _vp(pi), _vp(ranks), _vp(scores), _vp(nel), L.MFX_HOST, item_slices))
+        return ranks, scores, nel
+
+    def rank_times(self) -> dict:
+        """Device seconds of the last rank_of / evaluate by phase (mfx_rec_rank_times): {"keys", "count", "exclude"}."""
+        out = (C.c_double * 3)()
+        L.check(L.lib().mfx_rec_rank_times(self.handle, out))
+        return {"keys": out[0], "count": out[1], "exclude": out[2]}
+
+    def evaluate(self, T, cutoffs=(10,), min_rating: float = float("-inf")) -> dict:
+        """Ranking metrics of this model on the held-out set T (TestData or RatingData) from exact ranks
+        (mfx_rec_evaluate): {"cutoffs", "hr", "precision", "recall", "ndcg" (a list with one value per cutoff each), "mrr",
+        "auc", "users", "auc_users"}.  Cutoffs are not limited to 1024.  Only test entries with value >= min_rating count;
+        users left with none are skipped, as in topn_metrics."""
+        if not isinstance(T, TestData):
+            T = test_data_of(T)
+        cuts = [int(c) for c in cutoffs]
+        if any(c < 1 or c >= 2 ** 31 for c in cuts):
+            raise ValueError("cutoffs must be >= 1")
+        coo = _coo(T)
+        n = len(cuts)
+        ca = np.asarray(cuts, np.int32)
+        out = (C.c_double * (4 * max(n, 1)))()
+        mrr, auc = C.c_double(0), C.c_double(0)
+        kept, auc_kept = C.c_int64(0), C.c_int64(0)
+        L.check(L.lib().mfx_rec_evaluate(self.handle, C.byref(coo), float(min_rating), n, _vp(ca), out, C.byref(mrr), C.byref(auc),
+                                         C.byref(kept), C.byref(auc_kept), L.MFX_HOST))
+        col = lambda j: [out[4 * c + j] for c in range(n)]
+        return {"cutoffs": cuts, "hr": col(0), "precision": col(1), "recall": col(2), "ndcg": col(3), "mrr": mrr.value,
+                "auc": auc.value, "users": int(kept.value), "auc_users": int(auc_kept.value)}
 
     def fold_in_times(self) -> dict:
         """Seconds of the last fold_in call by phase (mfx_rec_fold_in_times): {"build", "solve", "score"}."""

@@ -417,6 +417,43 @@ int mfx_rec_item_norms(mfx_rec_t r, float* n2, float* c, mfx_memspace space);
  * item_slices * n_top > 8192, a query item >= cols (checked on the device), a bad memory space. */
 int mfx_rec_similar(mfx_rec_t r, int64_t nq, const uint32_t* query_items, int metric, int exclude_self, int32_t n_top,
                     uint32_t* items, float* scores, mfx_memspace space, int item_slices);
+/* Exact catalogue ranks of given (user, item) pairs: where does item i stand for user u?
+ * Item j is eligible for u when j < cols, j is not in u's row of the exclude matrix of mfx_rec_create, the item filter
+ * (if one is set) keeps j, and j's ranking key is not NaN.  The key is the score chain of mfx_rec_query; with a filter set
+ * it is fp32(score * the handle's per-item factor), as the top-N pass forms it.
+ * ranks[p]: the number of items j != i eligible for u that order before i (key(u,j) > key(u,i), or equal keys and j < i;
+ *   -0 == +0, +-inf ordinary values); 0xFFFFFFFF when i itself is not eligible for u.  So ranks[p] = r < 0xFFFFFFFF if and
+ *   only if mfx_rec_query for u returns i at position r for every n_top > r, and 0xFFFFFFFF if and only if no query
+ *   ever returns i for u.
+ * scores[p] (may be NULL): the score chain of (u, i), bit for bit, eligible or not.
+ * n_eligible[p] (may be NULL): the number of items eligible for u, the target included if it is; a column id repeated in
+ *   an exclusion row counts once.
+ * Pairs in any order, duplicates allowed; `space` applies to all five arrays; item_slices as in mfx_rec_query (0 =
+ * automatic, > 0 forces the split: a test hook).  A pair's results do not depend on the batch, its order, item_slices,
+ * the factor layout or the memory space.  Nothing of size users x items is stored: 12 bytes per pair during the call, and
+ * from the first call on one more copy of H in the handle (cols x k, row-major, the one mfx_rec_similar_setup keeps).
+ * MFX_ERR_INVALID, the handle left usable: ranks, users or items NULL with npairs > 0, a user >= rows or an item >= cols
+ * (checked on the device), item_slices < 0, a bad memory space.  npairs == 0 is MFX_OK and touches nothing. */
+int mfx_rec_rank(mfx_rec_t r, int64_t npairs, const uint32_t* users, const uint32_t* items, uint32_t* ranks, float* scores,
+                 uint32_t* n_eligible, mfx_memspace space, int item_slices);
+/* Device seconds of the last mfx_rec_rank (or mfx_rec_evaluate) on r by phase: [0] target keys, [1] counting pass,
+ * [2] exclusion correction. */
+int mfx_rec_rank_times(mfx_rec_t r, double seconds[3]);
+/* Ranking metrics of the handle's model on a held-out set T (`space` applies to its arrays) from exact ranks, so no cutoff
+ * limit and no list.  Users as in mfx_topn_metrics: R_u = the distinct test items of u with value >= min_rating, users
+ * with an empty R_u are skipped, *users_evaluated is the number kept.  One mfx_rec_rank of all kept pairs runs on the
+ * device; every sum below is fp64 on the host.
+ * out[c] = {HR, precision, recall, NDCG} at cutoff N = cutoffs[c] >= 1 (not limited to 1024), the definitions of
+ *   mfx_topn_metrics with "hit" meaning rank < N: for N <= 1024 the metrics of the lists of mfx_rec_query(n_top = N).
+ * *mrr: mean over the kept users of 1 / (1 + smallest rank in R_u), 0 for a user whose targets are all ineligible.
+ * *auc: for user u, P_u = its eligible targets, neg = n_eligible - |P_u|, AUC_u = mean over p in P_u of
+ *   (neg - (rank_p - a_p)) / neg with a_p = the number of other targets of u ranked before p; the mean of AUC_u over the
+ *   users with P_u not empty and neg > 0, whose number is *auc_users.
+ * mrr, auc, users_evaluated, auc_users may be NULL; n_cut == 0 is allowed (cutoffs and out are then not read).
+ * MFX_ERR_INVALID: NaN min_rating, a cutoff < 1, a test row >= rows or column >= cols, a bad memory space. */
+int mfx_rec_evaluate(mfx_rec_t r, const mfx_coo* T, float min_rating, int32_t n_cut, const int32_t* cutoffs,
+                     double* out /* [n_cut][4] */, double* mrr, double* auc, int64_t* users_evaluated, int64_t* auc_users,
+                     mfx_memspace space);
 int mfx_rec_destroy(mfx_rec_t r);
 
 /* ------------------------------------------------------------------------------------
