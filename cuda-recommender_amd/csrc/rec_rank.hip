@@ -8,12 +8,11 @@
 //   mfx_rec_target_keys   one thread per pair: the score of (u, i) as the explicit fp32 FMA chain over t ascending from
 //                         the packed W and the rows of H read back from the tiles (the bits the MFMA chain gives, as
 //                         mfx_rec_item_norms relies on), times the item's factor when a filter is set: the pair's key.
-//   mfx_rec_count         the pass of mfx_rec_topn with the selection taken out: same workgroup (128 slots x one item
-//                         slice), same double-buffered LDS stages of packed H, same W-in-registers MFMA loop and chunks
-//                         for k > 128.  A slot is a pair; its lane carries the target's key and id and two counters, and
-//                         every score costs a NaN test and the order compare: how many items with a non-NaN key, how
-//                         many of them before the target.  Item slices add into the pair's counters with integer
-//                         atomics, which no order can change.
+//   mfx_rec_count         the tile pass of rec_tiles.hpp that mfx_rec_topn runs (128 slots x one item slice per
+//                         workgroup), with a count in the place of the selection.  A slot is a pair; its lane carries
+//                         the target's key and id and two counters, and every score costs a NaN test and the order
+//                         compare: how many items with a non-NaN key, how many of them before the target.  Item slices
+//                         add into the pair's counters with integer atomics, which no order can change.
 //   mfx_rec_rank_fix      one wave per pair walks the user's exclusion row: every distinct id with a non-NaN key leaves
 //                         the eligible count, every one that orders before the target leaves the rank, and the target
 //                         found in the row, or a NaN target key, makes the pair ineligible (rank 0xFFFFFFFF).
@@ -27,7 +26,6 @@
 #include <cmath>
 #include <vector>
 
-#include "ccd_kernels.hpp"  // check_index_range
 #include "rec_tiles.hpp"
 #include "recommend.hpp"
 
@@ -35,16 +33,12 @@ namespace mfx {
 
 namespace {
 
-struct RankArgs {
-    const float* wp;         // [rows][kt]
-    const float* hp;         // [nblk][nch][2*KC][32]
+struct RankArgs : TileArgs {
     const uint32_t* users;   // [np]
     const uint32_t* items;   // [np]
     const float* tkey;       // [np] key of the pair's target
-    uint32_t np, cols;
-    int kt, nch, nblk, bps;
+    uint32_t np;
     uint32_t* cnt;           // [np][2]: items with a non-NaN key, items ordered before the target (zeroed; slices add)
-    const float* fac;        // FAC only: [nblk * 32] per-item factor of the ranking key
 };
 
 // The score chain of a packed W row and a row of H read back from the tiles (hq: [cols][kt], the bits of the tiles): fma over
@@ -76,95 +70,25 @@ __global__ void mfx_rec_target_keys(const float* wp, const float* hq, const uint
     }
 }
 
-// One LDS stage (NF4 16-byte vectors, contiguous in the packed H) through registers, as in mfx_rec_topn: the loads of stage
-// s+1 are in flight while the MFMAs of stage s run.  The registers are a plain vector type: as float4 the compiler keeps
-// stg[] of KC = 32 / 64 in scratch (32 / 64 bytes per lane stored and reloaded every stage), which costs the pass 3 % at
-// k = 64 and 10 % at k = 128.
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-template <int NV, int NF4>
-__device__ inline void load_stage(f32x4 (&stg)[NV], const float* src, int tid) {
-    const f32x4* s4 = reinterpret_cast<const f32x4*>(src);
-#pragma unroll
-    for (int v = 0; v < NV; ++v) {
-        const int e = tid + v * kRecThreads;
-        if (NF4 % kRecThreads == 0 || e < NF4) stg[v] = s4[e];
-    }
-}
-template <int NV, int NF4>
-__device__ inline void store_stage(const f32x4 (&stg)[NV], float* dst, int tid) {
-    f32x4* d4 = reinterpret_cast<f32x4*>(dst);
-#pragma unroll
-    for (int v = 0; v < NV; ++v) {
-        const int e = tid + v * kRecThreads;
-        if (NF4 % kRecThreads == 0 || e < NF4) d4[e] = stg[v];
-    }
-}
-
 template <int KC, bool FAC>
 __global__ __launch_bounds__(kRecThreads) void mfx_rec_count(RankArgs a) {
-    constexpr int STAGE = 2 * KC * kTile;        // floats per LDS stage
-    constexpr int NF4 = STAGE / 4;
-    constexpr int NV = (NF4 + kRecThreads - 1) / kRecThreads;
-    __shared__ __attribute__((aligned(16))) float hb[2][STAGE];
-
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, h = lane >> 5, j = lane & 31;
     const uint32_t q = blockIdx.x * kRecUsers + wave * 32 + j;
     const bool valid = q < a.np;
     const uint32_t u = valid ? a.users[q] : 0;
     const uint32_t ti = valid ? a.items[q] : 0;
     const float tk = valid ? a.tkey[q] : 0.f;
-    const int b0 = (int) blockIdx.y * a.bps;
-    const int b1 = min(a.nblk, b0 + a.bps);
-    const int nst = b1 > b0 ? (b1 - b0) * a.nch : 0;
-
-    f32x4 stg[NV];
     uint32_t elig = 0, before = 0;
-    float wf[KC];
-    f32x16 acc;
-    if (nst > 0) {
-        load_stage<NV, NF4>(stg, a.hp + (size_t) b0 * a.nch * STAGE, tid);
-        store_stage<NV, NF4>(stg, hb[0], tid);
-    }
-    __syncthreads();
-    for (int st = 0; st < nst; ++st) {
-        const int c = st % a.nch;
-        const int blk = b0 + st / a.nch;
-        if (st + 1 < nst) load_stage<NV, NF4>(stg, a.hp + (size_t) (b0 * a.nch + st + 1) * STAGE, tid);
-        if (a.nch > 1 || st == 0) {
-            const float* wr = a.wp + (size_t) u * a.kt + c * 2 * KC + h;
+    rec_tile_pass<KC, FAC>(a, (int) blockIdx.y, u, valid, [&](uint32_t ibase, const f32x16& acc) __attribute__((always_inline)) {
 #pragma unroll
-            for (int s = 0; s < KC; ++s) wf[s] = valid ? wr[2 * s] : 0.f;
+        for (int r = 0; r < 16; ++r) {
+            const uint32_t item = acc_item(ibase, r);
+            const float key = acc[r];
+            const bool in = item < a.cols;  // (the packed padding past cols scores 0, not NaN)
+            elig += (uint32_t) (in & (key == key));  // (&: no branch per entry)
+            before += (uint32_t) (in & beats(key, item, tk, ti));
         }
-        if (c == 0) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-        }
-        const float* hbuf = hb[st & 1] + h * kTile + j;
-#pragma unroll
-        for (int s = 0; s < KC; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(hbuf[2 * s * kTile], wf[s], acc, 0, 0, 0);
-
-        if (c == a.nch - 1) {
-            const uint32_t ibase = (uint32_t) blk * kTile + 4 * h;
-            if (FAC) {  // a lane's 16 items are four runs of four ids: one 16-byte load of the factors per run
-                const float4* f4 = reinterpret_cast<const float4*>(a.fac + ibase);
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const float4 f = f4[2 * g];
-                    acc[4 * g] *= f.x; acc[4 * g + 1] *= f.y; acc[4 * g + 2] *= f.z; acc[4 * g + 3] *= f.w;
-                }
-            }
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const uint32_t item = ibase + (r & 3) + 8 * (r >> 2);
-                const float key = acc[r];
-                const bool in = item < a.cols;  // (the packed padding past cols scores 0, not NaN)
-                elig += (uint32_t) (in && key == key);
-                before += (uint32_t) (in && beats(key, item, tk, ti));
-            }
-        }
-        if (st + 1 < nst) store_stage<NV, NF4>(stg, hb[(st + 1) & 1], tid);
-        __syncthreads();
-    }
+    });
     elig += __shfl_xor(elig, 32);
     before += __shfl_xor(before, 32);
     if (valid && h == 0) {
@@ -207,15 +131,6 @@ __global__ __launch_bounds__(kRecThreads) void mfx_rec_rank_fix(const float* wp,
     }
 }
 
-template <int KC>
-int launch_count(const RankArgs& a, int slices, hipStream_t st) {
-    const dim3 grid((a.np + kRecUsers - 1) / kRecUsers, slices);
-    if (a.fac) hipLaunchKernelGGL((mfx_rec_count<KC, true>), grid, dim3(kRecThreads), 0, st, a);
-    else hipLaunchKernelGGL((mfx_rec_count<KC, false>), grid, dim3(kRecThreads), 0, st, a);
-    MFX_LAUNCH_CHECK();
-    return MFX_OK;
-}
-
 struct Events {  // four stream events around the three phases
     hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
     int create() {
@@ -245,16 +160,10 @@ int Recommender::rank(int64_t npairs, const uint32_t* users, const uint32_t* ite
 
     DevBuf<uint32_t> d_users, d_items, d_ranks, d_nel, cnt;
     DevBuf<float> d_scores, tkey;
-    const uint32_t* du = users;
-    const uint32_t* di = items;
-    if (host) {
-        MFX_TRY(d_users.alloc(np)); MFX_TRY(d_users.upload(users, np, MFX_HOST, st));
-        MFX_TRY(d_items.alloc(np)); MFX_TRY(d_items.upload(items, np, MFX_HOST, st));
-        du = d_users.get();
-        di = d_items.get();
-    }
-    MFX_TRY(check_index_range(du, np, (uint32_t) rows_, "mfx_rec_rank: user id", st));
-    MFX_TRY(check_index_range(di, np, (uint32_t) cols_, "mfx_rec_rank: item id", st));
+    const uint32_t* du = nullptr;
+    const uint32_t* di = nullptr;
+    MFX_TRY(stage_ids(users, np, space, (uint32_t) rows_, "mfx_rec_rank: user id", d_users, &du));
+    MFX_TRY(stage_ids(items, np, space, (uint32_t) cols_, "mfx_rec_rank: item id", d_items, &di));
     uint32_t* orank = ranks;
     float* oscore = scores;
     uint32_t* onel = n_eligible;
@@ -270,17 +179,8 @@ int Recommender::rank(int64_t npairs, const uint32_t* users, const uint32_t* ite
     Events ev;
     MFX_TRY(ev.create());
 
-    // slices: forced, or enough workgroups for about two per CU
-    int slices = item_slices;
-    if (slices == 0) {
-        const int64_t pblocks = ((int64_t) np + kRecUsers - 1) / kRecUsers;
-        const int64_t want = 2 * cus_;
-        slices = pblocks >= want ? 1 : (int) ((want + pblocks - 1) / pblocks);
-        slices = std::max(1, std::min(slices, std::max(1, nblk_ / 4)));
-    }
-    slices = std::min(slices, 65535);  // (grid.y)
+    const int slices = pick_slices(item_slices, ((int64_t) np + kRecUsers - 1) / kRecUsers, 65535);  // (grid.y)
     const int bps = (nblk_ + slices - 1) / slices;
-    slices = (nblk_ + bps - 1) / bps;  // no empty slices
     const float* fac = fac_keep_.get();
 
     MFX_HIP(hipEventRecord(ev.e[0], st));
@@ -295,15 +195,13 @@ int Recommender::rank(int64_t npairs, const uint32_t* users, const uint32_t* ite
     a.kt = kt_; a.nch = nch_; a.nblk = nblk_; a.bps = bps;
     a.cnt = cnt.get();
     a.fac = fac;
-    switch (kc_) {
-        case 1: MFX_TRY(launch_count<1>(a, slices, st)); break;
-        case 2: MFX_TRY(launch_count<2>(a, slices, st)); break;
-        case 4: MFX_TRY(launch_count<4>(a, slices, st)); break;
-        case 8: MFX_TRY(launch_count<8>(a, slices, st)); break;
-        case 16: MFX_TRY(launch_count<16>(a, slices, st)); break;
-        case 32: MFX_TRY(launch_count<32>(a, slices, st)); break;
-        default: MFX_TRY(launch_count<64>(a, slices, st)); break;
-    }
+    MFX_TRY(dispatch_kc(kc_, [&](auto kc) {
+        const dim3 grid((np + kRecUsers - 1) / kRecUsers, slices);
+        if (fac) hipLaunchKernelGGL((mfx_rec_count<decltype(kc)::value, true>), grid, dim3(kRecThreads), 0, st, a);
+        else hipLaunchKernelGGL((mfx_rec_count<decltype(kc)::value, false>), grid, dim3(kRecThreads), 0, st, a);
+        MFX_LAUNCH_CHECK();
+        return (int) MFX_OK;
+    }));
     MFX_HIP(hipEventRecord(ev.e[2], st));
     hipLaunchKernelGGL(mfx_rec_rank_fix, dim3((np + kRecWaves - 1) / kRecWaves), dim3(kRecThreads), 0, st, wp_.get(), hq_.get(), du, di,
                        tkey.get(), cnt.get(), np, (int) k_, kt_, has_ex_ ? ex_ptr_.get() : nullptr, ex_idx_.get(), fac,

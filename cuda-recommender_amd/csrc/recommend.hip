@@ -9,7 +9,8 @@
 // the registers (row = (r&3) + 8*(r>>2) + 4*(lane>>5)).  Every score is the fp32 FMA chain over t = 0, 1, 2, ... in
 // ascending order (one MFMA = two chained FMAs), whatever the tile, slice, batch or factor layout; k is padded to
 // the MFMA step with steps that leave the accumulator bitwise unchanged (W +0, H -0; see mfx_rec_pack_h), and k > 128
-// runs several t chunks into the same accumulator, same order.
+// runs several t chunks into the same accumulator, same order.  That pass is rec_tile_pass of rec_tiles.hpp, which the
+// rank count of rec_rank.hip runs too; mfx_rec_topn adds the selection as its per-tile callback.
 //
 // Selection: each lane holds the running threshold of its user (the N-th best score so far) and compares its 16
 // scores against it -- one VALU compare per score.  Scores that pass are appended to the user's candidate list
@@ -42,7 +43,7 @@
 
 #include "als_solver.hpp"   // AlsHalf and the half-sweep launchers (fold-in)
 #include "ccd_kernels.hpp"  // check_index_range
-#include "rec_tiles.hpp"   // the workgroup shape, the total order
+#include "rec_tiles.hpp"   // the tile pass, the workgroup shape, the total order
 #include "recommend.hpp"
 
 namespace mfx {
@@ -54,20 +55,16 @@ constexpr int kMaxMerge = 8192;              // slices * N of one merge (64 KiB 
 constexpr int kMaxTop = 1024, kMaxK = 1024;
 constexpr size_t kWorkspaceCap = size_t(1) << 30;  // candidate lists of one launch (users are chunked under this)
 
-struct RecArgs {
-    const float* wp;        // [rows][kt]
-    const float* hp;        // [nblk][nch][2*KC][32]
+struct RecArgs : TileArgs {
     const uint32_t* users;  // NULL: slot q is user q0 + q
     uint32_t q0, nq;        // first batch slot of this launch, slots in this launch
     const uint32_t* ex_ptr; // NULL: no exclusion
     const uint32_t* ex_idx;
-    uint32_t cols;
-    int kt, nch, nblk, bps, n_top, L;
+    int n_top, L;
     float* ls;              // [slices][nq][L] candidate lists
     uint32_t* li;
     uint32_t* out_items;    // [q0 + q][n_top], written here when there is one slice
     float* out_scores;      // may be NULL
-    const float* fac;       // FAC only: [nblk * 32] per-item factor of the ranking key (NaN: the item is never returned)
     const float* qfac;      // NULL, or [query id]: factor of a slot's returned scores, applied where its final N leave
 };
 
@@ -107,37 +104,16 @@ __device__ inline bool excluded(const uint32_t* ex, uint32_t lo, uint32_t hi, ui
     return lo < end && ex[lo] == item;
 }
 
-// One LDS stage (NF4 float4, contiguous in the packed H) through registers: the loads of stage s+1 are in flight
-// while the MFMAs of stage s run.
-template <int NV, int NF4>
-__device__ inline void load_stage(float4 (&stg)[NV], const float* src, int tid) {
-    const float4* s4 = reinterpret_cast<const float4*>(src);
-#pragma unroll
-    for (int v = 0; v < NV; ++v) {
-        const int e = tid + v * kRecThreads;
-        if (NF4 % kRecThreads == 0 || e < NF4) stg[v] = s4[e];
-    }
-}
-template <int NV, int NF4>
-__device__ inline void store_stage(const float4 (&stg)[NV], float* dst, int tid) {
-    float4* d4 = reinterpret_cast<float4*>(dst);
-#pragma unroll
-    for (int v = 0; v < NV; ++v) {
-        const int e = tid + v * kRecThreads;
-        if (NF4 % kRecThreads == 0 || e < NF4) d4[e] = stg[v];
-    }
-}
-
 // FAC: the ranking key of (slot, item) is fp32(score * a.fac[item]) instead of the score (cosine keys, item filter).
-// Without FAC the kernels are the ones without the switch.  With it the factors cost KC = 8 and 16 the fourth wave per SIMD
-// (114 and 122 VGPRs + 16 AGPRs) unless the allocator is asked for four; every other instantiation gets the default.
+// KC <= 16 fits four waves per SIMD (109 to 125 VGPRs), but only when the allocator is asked for four: left to itself it
+// adds 16 AGPRs, which costs KC = 16 (and KC = 8 with the factors) the fourth wave.  KC = 32 / 64 get the default (3 / 2).
+// KC = 16 is three registers from the 128 at which the request turns into spills: whoever adds per-lane state to the
+// callback or to flush checks -Rpass-analysis=kernel-resource-usage for scratch (DESIGN 5.4 has the table).
+//
+// The kernel is the slot's list state, flush, and the tile pass of rec_tiles.hpp with the admission as its callback.
 template <int KC, bool FAC>
-__global__ __launch_bounds__(kRecThreads) __attribute__((amdgpu_waves_per_eu((FAC && KC <= 16) ? 4 : 1)))
+__global__ __launch_bounds__(kRecThreads) __attribute__((amdgpu_waves_per_eu(KC <= 16 ? 4 : 1)))
 void mfx_rec_topn(RecArgs a) {
-    constexpr int STAGE = 2 * KC * kTile;        // floats per LDS stage
-    constexpr int NF4 = STAGE / 4;
-    constexpr int NV = (NF4 + kRecThreads - 1) / kRecThreads;
-    __shared__ __attribute__((aligned(16))) float hb[2][STAGE];
     __shared__ float scs[kRecWaves][kScr];
     __shared__ uint32_t sci[kRecWaves][kScr];
 
@@ -147,13 +123,8 @@ void mfx_rec_topn(RecArgs a) {
     const uint32_t q = qw0 + j;
     const bool uvalid = q < a.nq;
     const uint32_t u = uvalid ? (a.users ? a.users[a.q0 + q] : a.q0 + q) : 0;
-    const int b0 = (int) slice * a.bps;
-    const int b1 = min(a.nblk, b0 + a.bps);
-    const int nst = b1 > b0 ? (b1 - b0) * a.nch : 0;
     const bool single = gridDim.y == 1;
     const bool lds_sort = a.L <= kScr;
-
-    float4 stg[NV];
 
     float thr = -INFINITY;  // score of the user's N-th entry once it has N; admission is score >= thr
     int cnt = 0;            // entries in the user's list
@@ -214,73 +185,34 @@ void mfx_rec_topn(RecArgs a) {
         wave_sync();
     };
 
-    float wf[KC];
-    f32x16 acc;
-    if (nst > 0) {
-        load_stage<NV, NF4>(stg, a.hp + (size_t) b0 * a.nch * STAGE, tid);
-        store_stage<NV, NF4>(stg, hb[0], tid);
-    }
-    __syncthreads();
-    for (int st = 0; st < nst; ++st) {
-        const int c = st % a.nch;
-        const int blk = b0 + st / a.nch;
-        if (st + 1 < nst) load_stage<NV, NF4>(stg, a.hp + (size_t) (b0 * a.nch + st + 1) * STAGE, tid);
-        if (a.nch > 1 || st == 0) {
-            const float* wr = a.wp + (size_t) u * a.kt + c * 2 * KC + h;
+    rec_tile_pass<KC, FAC>(a, (int) slice, u, uvalid, [&](uint32_t ibase, const f32x16& acc) __attribute__((always_inline)) {
+        uint32_t mask = 0;
 #pragma unroll
-            for (int s = 0; s < KC; ++s) wf[s] = uvalid ? wr[2 * s] : 0.f;
-        }
-        if (c == 0) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-        }
-        const float* hbuf = hb[st & 1] + h * kTile + j;
-#pragma unroll
-        for (int s = 0; s < KC; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(hbuf[2 * s * kTile], wf[s], acc, 0, 0, 0);
-
-        if (c == a.nch - 1) {
-            const uint32_t ibase = (uint32_t) blk * kTile + 4 * h;
-            if (FAC) {  // a lane's 16 items are four runs of four ids: one 16-byte load of the factors per run
-                const float4* f4 = reinterpret_cast<const float4*>(a.fac + ibase);  // (ibase < 2^32: cols < 2^32 - 1)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const float4 f = f4[2 * g];
-                    acc[4 * g] *= f.x; acc[4 * g + 1] *= f.y; acc[4 * g + 2] *= f.z; acc[4 * g + 3] *= f.w;
-                }
+        for (int r = 0; r < 16; ++r) mask |= (uint32_t) (uvalid && acc_item(ibase, r) < a.cols && acc[r] >= thr) << r;
+        if (__ballot(mask != 0)) {
+            const int n = __popc(mask);
+            const int n_o = __shfl_xor(n, 32);
+            const int tot = n + n_o;
+            uint64_t fm = __ballot(uvalid && h == 0 && cnt + tot > a.L);
+            while (fm) {
+                const int uj = __ffsll((unsigned long long) fm) - 1;
+                fm &= fm - 1;
+                flush(uj, false);
             }
-            uint32_t mask = 0;
+            if (mask) {
+                size_t pos = ((size_t) slice * a.nq + q) * (size_t) a.L + cnt + (h ? n_o : 0);
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const uint32_t item = ibase + (r & 3) + 8 * (r >> 2);
-                mask |= (uint32_t) (uvalid && item < a.cols && acc[r] >= thr) << r;
-            }
-            if (__ballot(mask != 0)) {
-                const int n = __popc(mask);
-                const int n_o = __shfl_xor(n, 32);
-                const int tot = n + n_o;
-                uint64_t fm = __ballot(uvalid && h == 0 && cnt + tot > a.L);
-                while (fm) {
-                    const int uj = __ffsll((unsigned long long) fm) - 1;
-                    fm &= fm - 1;
-                    flush(uj, false);
-                }
-                if (mask) {
-                    size_t pos = ((size_t) slice * a.nq + q) * (size_t) a.L + cnt + (h ? n_o : 0);
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        if (mask >> r & 1) {
-                            a.ls[pos] = acc[r];
-                            a.li[pos] = ibase + (r & 3) + 8 * (r >> 2);
-                            ++pos;
-                        }
+                for (int r = 0; r < 16; ++r) {
+                    if (mask >> r & 1) {
+                        a.ls[pos] = acc[r];
+                        a.li[pos] = acc_item(ibase, r);
+                        ++pos;
                     }
                 }
-                cnt += tot;
             }
+            cnt += tot;
         }
-        if (st + 1 < nst) store_stage<NV, NF4>(stg, hb[(st + 1) & 1], tid);
-        __syncthreads();
-    }
+    });
     uint64_t fm = __ballot(uvalid && h == 0);
     while (fm) {
         const int uj = __ffsll((unsigned long long) fm) - 1;
@@ -422,12 +354,48 @@ __global__ void mfx_rec_check_exclude(const uint32_t* rp, const uint32_t* ci, ui
     }
 }
 
-template <int KC>
-int launch_topn(const RecArgs& a, int slices, hipStream_t st) {
-    const dim3 grid((a.nq + kRecUsers - 1) / kRecUsers, slices);
-    if (a.fac) hipLaunchKernelGGL((mfx_rec_topn<KC, true>), grid, dim3(kRecThreads), 0, st, a);
-    else hipLaunchKernelGGL((mfx_rec_topn<KC, false>), grid, dim3(kRecThreads), 0, st, a);
+// mfx_rec_check_exclude over a CSR on the device and its three refusals.  `who` opens every message ("mfx_rec_create:
+// exclusion "), `ptr` is what the caller calls the row pointers.
+int check_csr(const uint32_t* rp, const uint32_t* ci, uint32_t rows, uint32_t cols, uint64_t nnz, const char* who, const char* ptr,
+              hipStream_t st) {
+    DevBuf<int> bad;
+    MFX_TRY(bad.alloc_zero(1, st));
+    hipLaunchKernelGGL(mfx_rec_check_exclude, dim3(grid_for((size_t) rows)), dim3(256), 0, st, rp, ci, rows, cols, nnz, bad.get());
     MFX_LAUNCH_CHECK();
+    int hb = 0;
+    MFX_HIP(hipMemcpyAsync(&hb, bad.get(), sizeof(int), hipMemcpyDeviceToHost, st));
+    MFX_HIP(hipStreamSynchronize(st));
+    MFX_REQUIRE(!(hb & 1), "%s%s is not a non-decreasing prefix sum from 0 to nnz", who, ptr);
+    MFX_REQUIRE(!(hb & 2), "%scolumn index out of range [0, %lld)", who, (long long) cols);
+    MFX_REQUIRE(!(hb & 4), "%scolumn indices must be non-decreasing within every row", who);
+    return MFX_OK;
+}
+
+// What mfx_rec_query and mfx_rec_similar check alike: fn is the entry point, ids / n / bound its names for the batch's
+// ids, their number and what bounds a batch without ids.
+int check_batch(const char* fn, const char* ids_name, const char* n_name, const char* bound_name, int64_t n, const uint32_t* ids,
+                int64_t bound, int32_t n_top, mfx_memspace space, int item_slices) {
+    MFX_REQUIRE(n_top >= 1 && n_top <= kMaxTop, "%s: n_top must be in [1, %d] (got %d)", fn, kMaxTop, n_top);
+    MFX_REQUIRE(n >= 0 && n < (int64_t) 0xFFFFFFFFll, "%s: bad %s %lld", fn, n_name, (long long) n);
+    MFX_REQUIRE(ids || n <= bound, "%s: %s = NULL needs %s <= %s (%lld > %lld)", fn, ids_name, n_name, bound_name, (long long) n,
+                (long long) bound);
+    MFX_REQUIRE(space == MFX_HOST || space == MFX_DEVICE, "%s: bad memory space", fn);
+    MFX_REQUIRE(item_slices >= 0, "%s: item_slices must be >= 0 (got %d)", fn, item_slices);
+    MFX_REQUIRE(item_slices * (int64_t) n_top <= kMaxMerge, "%s: item_slices * n_top must be <= %d", fn, kMaxMerge);
+    return MFX_OK;
+}
+
+// The argument checks the fold-in setups share, in two halves: every setup checks lambda, then its own alpha or reg, and
+// the block setups then check block / sweeps / tol.  fn is the entry point's name.
+int check_fold_lambda(const char* fn, float lambda) {
+    MFX_REQUIRE(std::isfinite(lambda) && lambda > 0.f, "%s: lambda = %g (finite and > 0 required)", fn, (double) lambda);
+    return MFX_OK;
+}
+int check_fold_sweeps(const char* fn, int32_t block, int32_t sweeps, float tol) {
+    MFX_REQUIRE(block >= 0 && block <= (int32_t) kIalsBlockMaxBlock, "%s: block = %d (0 = chosen from k, else 1 <= block <= %u)", fn,
+                block, kIalsBlockMaxBlock);
+    MFX_REQUIRE(sweeps >= 1 && sweeps <= 1024, "%s: sweeps = %d (1 <= sweeps <= 1024)", fn, sweeps);
+    MFX_REQUIRE(std::isfinite(tol) && tol >= 0.f, "%s: tol = %g (finite and >= 0 required)", fn, (double) tol);
     return MFX_OK;
 }
 
@@ -503,17 +471,8 @@ int Recommender::create(Recommender** out, const float* W, const float* H, int64
             MFX_TRY(r->ex_idx_.alloc((size_t) ex->nnz));
             MFX_TRY(r->ex_idx_.upload(ex->csr_col_idx, (size_t) ex->nnz, space, st));
         }
-        DevBuf<int> bad;
-        MFX_TRY(bad.alloc_zero(1, st));
-        hipLaunchKernelGGL(mfx_rec_check_exclude, dim3(grid_for((size_t) rows)), dim3(256), 0, st, r->ex_ptr_.get(),
-                           r->ex_idx_.get(), (uint32_t) rows, (uint32_t) cols, (uint64_t) ex->nnz, bad.get());
-        MFX_LAUNCH_CHECK();
-        int hb = 0;
-        MFX_HIP(hipMemcpyAsync(&hb, bad.get(), sizeof(int), hipMemcpyDeviceToHost, st));
-        MFX_HIP(hipStreamSynchronize(st));
-        MFX_REQUIRE(!(hb & 1), "mfx_rec_create: exclusion csr_row_ptr is not a non-decreasing prefix sum from 0 to nnz");
-        MFX_REQUIRE(!(hb & 2), "mfx_rec_create: exclusion column index out of range [0, %lld)", (long long) cols);
-        MFX_REQUIRE(!(hb & 4), "mfx_rec_create: exclusion column indices must be non-decreasing within every row");
+        MFX_TRY(check_csr(r->ex_ptr_.get(), r->ex_idx_.get(), (uint32_t) rows, (uint32_t) cols, (uint64_t) ex->nnz,
+                          "mfx_rec_create: exclusion ", "csr_row_ptr", st));
         r->has_ex_ = true;
     }
     MFX_HIP(hipStreamSynchronize(st));
@@ -523,27 +482,40 @@ int Recommender::create(Recommender** out, const float* W, const float* H, int64
 
 int Recommender::query(int64_t nusers, const uint32_t* users, int32_t n_top, uint32_t* items, float* scores,
                        mfx_memspace space, int item_slices) {
-    MFX_REQUIRE(n_top >= 1 && n_top <= kMaxTop, "mfx_rec_query: n_top must be in [1, %d] (got %d)", kMaxTop, n_top);
-    MFX_REQUIRE(nusers >= 0 && nusers < (int64_t) 0xFFFFFFFFll, "mfx_rec_query: bad nusers %lld", (long long) nusers);
-    MFX_REQUIRE(users || nusers <= rows_, "mfx_rec_query: users = NULL needs nusers <= rows (%lld > %lld)",
-                (long long) nusers, (long long) rows_);
-    MFX_REQUIRE(space == MFX_HOST || space == MFX_DEVICE, "mfx_rec_query: bad memory space");
-    MFX_REQUIRE(item_slices >= 0, "mfx_rec_query: item_slices must be >= 0 (got %d)", item_slices);
-    MFX_REQUIRE(item_slices * (int64_t) n_top <= kMaxMerge, "mfx_rec_query: item_slices * n_top must be <= %d", kMaxMerge);
+    MFX_TRY(check_batch("mfx_rec_query", "users", "nusers", "rows", nusers, users, rows_, n_top, space, item_slices));
     if (nusers == 0) return MFX_OK;
     MFX_REQUIRE(items, "mfx_rec_query: items is NULL");
     MFX_TRY(use_device(device_));
     const uint32_t nu = (uint32_t) nusers;
     DevBuf<uint32_t> d_users;
-    const uint32_t* du = users;
-    if (users && space == MFX_HOST) {
-        MFX_TRY(d_users.alloc(nu));
-        MFX_TRY(d_users.upload(users, nu, MFX_HOST, st_));
-        du = d_users.get();
-    }
-    if (users) MFX_TRY(check_index_range(du, nu, (uint32_t) rows_, "mfx_rec_query: user id", st_));
+    const uint32_t* du = nullptr;
+    MFX_TRY(stage_ids(users, nu, space, (uint32_t) rows_, "mfx_rec_query: user id", d_users, &du));
     return topn(wp_.get(), nu, du, has_ex_ ? ex_ptr_.get() : nullptr, ex_idx_.get(), n_top, items, scores, space, item_slices,
                 fac_keep_.get(), nullptr);
+}
+
+int Recommender::stage_ids(const uint32_t* ids, uint32_t n, mfx_memspace space, uint32_t bound, const char* what, DevBuf<uint32_t>& buf,
+                           const uint32_t** dev) {
+    *dev = ids;
+    if (!ids) return MFX_OK;
+    if (space == MFX_HOST) {
+        MFX_TRY(buf.alloc(n));
+        MFX_TRY(buf.upload(ids, n, MFX_HOST, st_));
+        *dev = buf.get();
+    }
+    return check_index_range(*dev, n, bound, what, st_);
+}
+
+int Recommender::pick_slices(int forced, int64_t blocks, int cap) const {
+    int slices = forced;
+    if (slices == 0) {  // enough workgroups for about two per CU
+        const int64_t want = 2 * cus_;
+        slices = blocks >= want ? 1 : (int) ((want + blocks - 1) / blocks);
+        slices = std::max(1, std::min(slices, std::max(1, nblk_ / 4)));
+    }
+    slices = std::min(slices, cap);
+    const int bps = (nblk_ + slices - 1) / slices;
+    return (nblk_ + bps - 1) / bps;  // no empty slices
 }
 
 int Recommender::build_facs(const uint8_t* keep) {
@@ -583,20 +555,17 @@ int Recommender::set_item_filter(const uint8_t* keep, mfx_memspace space) {
 int Recommender::similar_setup() {
     if (sim_c_.get()) return MFX_OK;
     MFX_TRY(use_device(device_));
-    DevBuf<float> hq, n2, c;
+    MFX_TRY(ensure_hq());
+    DevBuf<float> n2, c;
     DevBuf<uint32_t> id;
-    MFX_TRY(hq.alloc((size_t) cols_ * kt_));
     MFX_TRY(n2.alloc((size_t) cols_));
     MFX_TRY(c.alloc((size_t) cols_));
     MFX_TRY(id.alloc((size_t) cols_ + 1));
-    hipLaunchKernelGGL(mfx_rec_pack_hq, dim3(grid_for((size_t) cols_ * kt_)), dim3(256), 0, st_, hp_.get(), (uint32_t) cols_, (int) k_,
-                       2 * kc_, nch_, kt_, hq.get());
-    MFX_LAUNCH_CHECK();
-    hipLaunchKernelGGL(mfx_rec_item_norms, dim3(grid_for((size_t) cols_ + 1)), dim3(256), 0, st_, hq.get(), (uint32_t) cols_, (int) k_,
+    hipLaunchKernelGGL(mfx_rec_item_norms, dim3(grid_for((size_t) cols_ + 1)), dim3(256), 0, st_, hq_.get(), (uint32_t) cols_, (int) k_,
                        kt_, n2.get(), c.get(), id.get());
     MFX_LAUNCH_CHECK();
     MFX_HIP(hipStreamSynchronize(st_));
-    hq_ = std::move(hq); sim_n2_ = std::move(n2); sim_id_ = std::move(id);
+    sim_n2_ = std::move(n2); sim_id_ = std::move(id);
     sim_c_ = std::move(c);
     const int rc = build_facs(keep_.get());
     if (rc != MFX_OK) sim_c_.release();  // (not set up)
@@ -629,25 +598,14 @@ int Recommender::similar(int64_t nq, const uint32_t* query_items, int metric, in
                          float* scores, mfx_memspace space, int item_slices) {
     MFX_REQUIRE(sim_c_.get(), "mfx_rec_similar: call mfx_rec_similar_setup first");
     MFX_REQUIRE(metric == MFX_SIM_DOT || metric == MFX_SIM_COSINE, "mfx_rec_similar: unknown metric %d", metric);
-    MFX_REQUIRE(n_top >= 1 && n_top <= kMaxTop, "mfx_rec_similar: n_top must be in [1, %d] (got %d)", kMaxTop, n_top);
-    MFX_REQUIRE(nq >= 0 && nq < (int64_t) 0xFFFFFFFFll, "mfx_rec_similar: bad nq %lld", (long long) nq);
-    MFX_REQUIRE(query_items || nq <= cols_, "mfx_rec_similar: query_items = NULL needs nq <= cols (%lld > %lld)", (long long) nq,
-                (long long) cols_);
-    MFX_REQUIRE(space == MFX_HOST || space == MFX_DEVICE, "mfx_rec_similar: bad memory space");
-    MFX_REQUIRE(item_slices >= 0, "mfx_rec_similar: item_slices must be >= 0 (got %d)", item_slices);
-    MFX_REQUIRE(item_slices * (int64_t) n_top <= kMaxMerge, "mfx_rec_similar: item_slices * n_top must be <= %d", kMaxMerge);
+    MFX_TRY(check_batch("mfx_rec_similar", "query_items", "nq", "cols", nq, query_items, cols_, n_top, space, item_slices));
     if (nq == 0) return MFX_OK;
     MFX_REQUIRE(items, "mfx_rec_similar: items is NULL");
     MFX_TRY(use_device(device_));
     const uint32_t nu = (uint32_t) nq;
     DevBuf<uint32_t> d_q;
-    const uint32_t* dq = query_items;
-    if (query_items && space == MFX_HOST) {
-        MFX_TRY(d_q.alloc(nu));
-        MFX_TRY(d_q.upload(query_items, nu, MFX_HOST, st_));
-        dq = d_q.get();
-    }
-    if (query_items) MFX_TRY(check_index_range(dq, nu, (uint32_t) cols_, "mfx_rec_similar: query item", st_));
+    const uint32_t* dq = nullptr;
+    MFX_TRY(stage_ids(query_items, nu, space, (uint32_t) cols_, "mfx_rec_similar: query item", d_q, &dq));
     const bool cosine = metric == MFX_SIM_COSINE;
     return topn(hq_.get(), nu, dq, exclude_self ? sim_id_.get() : nullptr, sim_id_.get(), n_top, items, scores, space, item_slices,
                 cosine ? fac_cos_.get() : fac_keep_.get(), cosine ? sim_c_.get() : nullptr);
@@ -660,23 +618,13 @@ int Recommender::topn(const float* wp, uint32_t nu, const uint32_t* du, const ui
     int L = 64;
     while (L < n_top + 32) L <<= 1;
 
-    // slices: forced, or enough workgroups for about two per CU
-    int slices = item_slices;
     const auto per_launch = [&](int s) {
         size_t qmax = kWorkspaceCap / ((size_t) s * L * 8);
         qmax = std::max<size_t>(kRecUsers, qmax / kRecUsers * kRecUsers);
         return (uint32_t) std::min<size_t>(nu, qmax);
     };
-    if (slices == 0) {
-        const int ublocks = (int) ((per_launch(1) + kRecUsers - 1) / kRecUsers);
-        const int want = 2 * cus_;
-        slices = ublocks >= want ? 1 : (want + ublocks - 1) / ublocks;
-        slices = std::min(slices, std::max(1, nblk_ / 4));
-        slices = std::min(slices, kMaxMerge / n_top);
-        slices = std::max(slices, 1);
-        const int bps = (nblk_ + slices - 1) / slices;
-        slices = (nblk_ + bps - 1) / bps;  // no empty slices
-    }
+    // slices: as forced, or chosen for the user blocks of one launch, at most what one merge takes
+    const int slices = item_slices ? item_slices : pick_slices(0, (per_launch(1) + kRecUsers - 1) / kRecUsers, kMaxMerge / n_top);
     const int bps = (nblk_ + slices - 1) / slices;
     const uint32_t qc = per_launch(slices);
 
@@ -712,15 +660,14 @@ int Recommender::topn(const float* wp, uint32_t nu, const uint32_t* du, const ui
     for (uint32_t q0 = 0; q0 < nu; q0 += qc) {
         a.q0 = q0;
         a.nq = std::min(qc, nu - q0);
-        switch (kc_) {
-            case 1: MFX_TRY(launch_topn<1>(a, slices, st)); break;
-            case 2: MFX_TRY(launch_topn<2>(a, slices, st)); break;
-            case 4: MFX_TRY(launch_topn<4>(a, slices, st)); break;
-            case 8: MFX_TRY(launch_topn<8>(a, slices, st)); break;
-            case 16: MFX_TRY(launch_topn<16>(a, slices, st)); break;
-            case 32: MFX_TRY(launch_topn<32>(a, slices, st)); break;
-            default: MFX_TRY(launch_topn<64>(a, slices, st)); break;
-        }
+        MFX_TRY(dispatch_kc(kc_, [&](auto kc) {
+            constexpr int KC = decltype(kc)::value;
+            const dim3 grid((a.nq + kRecUsers - 1) / kRecUsers, slices);
+            if (a.fac) hipLaunchKernelGGL((mfx_rec_topn<KC, true>), grid, dim3(kRecThreads), 0, st, a);
+            else hipLaunchKernelGGL((mfx_rec_topn<KC, false>), grid, dim3(kRecThreads), 0, st, a);
+            MFX_LAUNCH_CHECK();
+            return (int) MFX_OK;
+        }));
         if (slices > 1) {
             hipLaunchKernelGGL(mfx_rec_merge, dim3(a.nq), dim3(64), (size_t) P * 8, st, a.ls, a.li, q0, a.nq, slices, L,
                                n_top, P, oi, os, du, qfac);
@@ -735,21 +682,27 @@ int Recommender::topn(const float* wp, uint32_t nu, const uint32_t* du, const ui
     return MFX_OK;
 }
 
+int Recommender::fold_setup_begin(bool drop_g, bool drop_b) {
+    MFX_TRY(use_device(device_));
+    fold_model_ = -1;  // (until the setup is through)
+    if (drop_g) fold_g_.release();     // (what a direct setup kept)
+    if (drop_b) fold_b_ = IalsBlock();  // (what a block setup kept)
+    const size_t nh = ((size_t) cols_ + 1) * k_;
+    if (!hx_.get()) MFX_TRY(hx_.alloc(nh));
+    hipLaunchKernelGGL(mfx_rec_unpack_h, dim3(grid_for(nh)), dim3(256), 0, st_, hp_.get(), (uint32_t) cols_, (int) k_, 2 * kc_, nch_,
+                       hx_.get());
+    MFX_LAUNCH_CHECK();
+    return MFX_OK;
+}
+
 int Recommender::fold_in_setup(int model, float lambda, float alpha) {
     MFX_REQUIRE(model == MFX_FOLD_ALS || model == MFX_FOLD_ALS_EXACT || model == MFX_FOLD_CCD || model == MFX_FOLD_IMPLICIT,
                 "mfx_rec_fold_in_setup: unknown model %d", model);
     MFX_REQUIRE(k_ <= 128, "mfx_rec_fold_in_setup: fold-in solves ranks k <= 128 (the handle has k = %lld)", (long long) k_);
-    MFX_REQUIRE(std::isfinite(lambda) && lambda > 0.f, "mfx_rec_fold_in_setup: lambda = %g (finite and > 0 required)", (double) lambda);
+    MFX_TRY(check_fold_lambda("mfx_rec_fold_in_setup", lambda));
     MFX_REQUIRE(std::isfinite(alpha) && alpha >= 0.f, "mfx_rec_fold_in_setup: alpha = %g (finite and >= 0 required)", (double) alpha);
-    MFX_TRY(use_device(device_));
+    MFX_TRY(fold_setup_begin(false, true));
     hipStream_t st = st_;
-    fold_model_ = -1;  // (until this setup is through)
-    fold_b_ = IalsBlock();  // (what a block setup kept)
-    const size_t nh = ((size_t) cols_ + 1) * k_;
-    if (!hx_.get()) MFX_TRY(hx_.alloc(nh));
-    hipLaunchKernelGGL(mfx_rec_unpack_h, dim3(grid_for(nh)), dim3(256), 0, st, hp_.get(), (uint32_t) cols_, (int) k_, 2 * kc_,
-                       nch_, hx_.get());
-    MFX_LAUNCH_CHECK();
     DevBuf<float> part;
     if (model == MFX_FOLD_IMPLICIT) {  // the base Gramian of the implicit system, as the trainer's ials_base_gramian builds it
         MFX_TRY(part.alloc(ials_base_ws_floats((uint32_t) cols_, (uint32_t) k_)));
@@ -766,21 +719,11 @@ int Recommender::fold_in_setup(int model, float lambda, float alpha) {
 int Recommender::fold_in_block_setup(float lambda, float alpha, int32_t block, int32_t sweeps, float tol) {
     MFX_REQUIRE(k_ <= (int64_t) kIalsBlockMaxRank, "mfx_rec_fold_in_block_setup: block sweeps solve ranks k <= %u (the handle has k = %lld)",
                 kIalsBlockMaxRank, (long long) k_);
-    MFX_REQUIRE(std::isfinite(lambda) && lambda > 0.f, "mfx_rec_fold_in_block_setup: lambda = %g (finite and > 0 required)", (double) lambda);
+    MFX_TRY(check_fold_lambda("mfx_rec_fold_in_block_setup", lambda));
     MFX_REQUIRE(std::isfinite(alpha) && alpha >= 0.f, "mfx_rec_fold_in_block_setup: alpha = %g (finite and >= 0 required)", (double) alpha);
-    MFX_REQUIRE(block >= 0 && block <= (int32_t) kIalsBlockMaxBlock,
-                "mfx_rec_fold_in_block_setup: block = %d (0 = chosen from k, else 1 <= block <= %u)", block, kIalsBlockMaxBlock);
-    MFX_REQUIRE(sweeps >= 1 && sweeps <= 1024, "mfx_rec_fold_in_block_setup: sweeps = %d (1 <= sweeps <= 1024)", sweeps);
-    MFX_REQUIRE(std::isfinite(tol) && tol >= 0.f, "mfx_rec_fold_in_block_setup: tol = %g (finite and >= 0 required)", (double) tol);
-    MFX_TRY(use_device(device_));
+    MFX_TRY(check_fold_sweeps("mfx_rec_fold_in_block_setup", block, sweeps, tol));
+    MFX_TRY(fold_setup_begin(true, false));
     hipStream_t st = st_;
-    fold_model_ = -1;  // (until this setup is through)
-    fold_g_.release();  // (what a direct setup kept)
-    const size_t nh = ((size_t) cols_ + 1) * k_;
-    if (!hx_.get()) MFX_TRY(hx_.alloc(nh));
-    hipLaunchKernelGGL(mfx_rec_unpack_h, dim3(grid_for(nh)), dim3(256), 0, st, hp_.get(), (uint32_t) cols_, (int) k_, 2 * kc_,
-                       nch_, hx_.get());
-    MFX_LAUNCH_CHECK();
     // the Gramian as the block trainer and mfx_ials_block_half build it (ialsb_gramian), and what they pack once per half
     const uint32_t k = (uint32_t) k_, d = std::min<uint32_t>(block ? (uint32_t) block : ialsb_default_block(k), k);
     MFX_TRY(fold_b_.alloc(k, d, (uint32_t) cols_, 0, 0, 0, st));
@@ -799,22 +742,11 @@ int Recommender::fold_in_block_setup(float lambda, float alpha, int32_t block, i
 int Recommender::fold_in_block_setup_als(float lambda, int32_t reg, int32_t block, int32_t sweeps, float tol) {
     MFX_REQUIRE(k_ <= (int64_t) kIalsBlockMaxRank, "mfx_rec_fold_in_block_setup_als: block sweeps solve ranks k <= %u (the handle has k = %lld)",
                 kIalsBlockMaxRank, (long long) k_);
-    MFX_REQUIRE(std::isfinite(lambda) && lambda > 0.f, "mfx_rec_fold_in_block_setup_als: lambda = %g (finite and > 0 required)", (double) lambda);
+    MFX_TRY(check_fold_lambda("mfx_rec_fold_in_block_setup_als", lambda));
     MFX_REQUIRE(reg == 0 || reg == 1, "mfx_rec_fold_in_block_setup_als: reg = %d (0 = lambda, 1 = lambda * entries of the row)", reg);
-    MFX_REQUIRE(block >= 0 && block <= (int32_t) kIalsBlockMaxBlock,
-                "mfx_rec_fold_in_block_setup_als: block = %d (0 = chosen from k, else 1 <= block <= %u)", block, kIalsBlockMaxBlock);
-    MFX_REQUIRE(sweeps >= 1 && sweeps <= 1024, "mfx_rec_fold_in_block_setup_als: sweeps = %d (1 <= sweeps <= 1024)", sweeps);
-    MFX_REQUIRE(std::isfinite(tol) && tol >= 0.f, "mfx_rec_fold_in_block_setup_als: tol = %g (finite and >= 0 required)", (double) tol);
-    MFX_TRY(use_device(device_));
+    MFX_TRY(check_fold_sweeps("mfx_rec_fold_in_block_setup_als", block, sweeps, tol));
+    MFX_TRY(fold_setup_begin(true, true));
     hipStream_t st = st_;
-    fold_model_ = -1;  // (until this setup is through)
-    fold_g_.release();  // (what a direct setup kept)
-    fold_b_ = IalsBlock();  // (what an implicit block setup kept)
-    const size_t nh = ((size_t) cols_ + 1) * k_;
-    if (!hx_.get()) MFX_TRY(hx_.alloc(nh));
-    hipLaunchKernelGGL(mfx_rec_unpack_h, dim3(grid_for(nh)), dim3(256), 0, st, hp_.get(), (uint32_t) cols_, (int) k_, 2 * kc_,
-                       nch_, hx_.get());
-    MFX_LAUNCH_CHECK();
     const uint32_t k = (uint32_t) k_, d = std::min<uint32_t>(block ? (uint32_t) block : ialsb_default_block(k), k);
     MFX_TRY(fold_b_.alloc_explicit(k, d, (uint32_t) cols_, 0, 0, 0, st));
     MFX_TRY(alsb_pack_launch(fold_b_, hx_.get(), (uint32_t) cols_, st));
@@ -860,17 +792,7 @@ int Recommender::fold_solve(int64_t nusers, int64_t nnz, const uint32_t* ptr, co
     // and every index < cols on the device; then the exclusion check of mfx_rec_create (ids non-decreasing in a row)
     AlsHalf h;
     MFX_TRY(h.build(nu, (uint64_t) nnz, (uint32_t) cols_, ptr, idx, val, space, kAlsChunk, st));
-    DevBuf<int> bad;
-    MFX_TRY(bad.alloc_zero(1, st));
-    hipLaunchKernelGGL(mfx_rec_check_exclude, dim3(grid_for(nu)), dim3(256), 0, st, h.ptr.get(), h.idx.get(), nu,
-                       (uint32_t) cols_, (uint64_t) nnz, bad.get());
-    MFX_LAUNCH_CHECK();
-    int hb = 0;
-    MFX_HIP(hipMemcpyAsync(&hb, bad.get(), sizeof(int), hipMemcpyDeviceToHost, st));
-    MFX_HIP(hipStreamSynchronize(st));
-    MFX_REQUIRE(!(hb & 1), "mfx_rec_fold_in: ptr is not a non-decreasing prefix sum from 0 to nnz");
-    MFX_REQUIRE(!(hb & 2), "mfx_rec_fold_in: column index out of range [0, %lld)", (long long) cols_);
-    MFX_REQUIRE(!(hb & 4), "mfx_rec_fold_in: column indices must be non-decreasing within every row");
+    MFX_TRY(check_csr(h.ptr.get(), h.idx.get(), nu, (uint32_t) cols_, (uint64_t) nnz, "mfx_rec_fold_in: ", "ptr", st));
     const bool by_blocks = fold_model_ == kFoldBlock || fold_model_ == kFoldBlockAls;
     if (fold_model_ == MFX_FOLD_IMPLICIT || fold_model_ == kFoldBlock)
         MFX_TRY(ials_check_values(h.val.get(), h.nnz, fold_alpha_, "mfx_rec_fold_in: value", st));
@@ -891,18 +813,16 @@ int Recommender::fold_solve(int64_t nusers, int64_t nnz, const uint32_t* ptr, co
     } query_ws{fold_b_};
     switch (fold_model_) {
         case kFoldBlock:
-            if (W_init) MFX_TRY(Y.upload(W_init, (size_t) nu * k, space, st));
-            if (sweeps_done) MFX_TRY(counts.alloc(nu));
-            MFX_TRY(fold_b_.alloc_half(nu, h.nnz, h.nslots, st));
-            MFX_TRY(ialsb_fold_launch(fold_b_, h, hx_.get(), x_rows, Y.get(), fold_alpha_, fold_sweeps_, fold_tol_, counts.get(),
-                                      spd_fail.get(), st));
-            break;
         case kFoldBlockAls:
             if (W_init) MFX_TRY(Y.upload(W_init, (size_t) nu * k, space, st));
             if (sweeps_done) MFX_TRY(counts.alloc(nu));
             MFX_TRY(fold_b_.alloc_half(nu, h.nnz, h.nslots, st));
-            MFX_TRY(alsb_fold_launch(fold_b_, h, hx_.get(), x_rows, Y.get(), fold_lambda_, fold_reg_, fold_sweeps_, fold_tol_, counts.get(),
-                                     spd_fail.get(), st));
+            if (fold_model_ == kFoldBlock)
+                MFX_TRY(ialsb_fold_launch(fold_b_, h, hx_.get(), x_rows, Y.get(), fold_alpha_, fold_sweeps_, fold_tol_, counts.get(),
+                                          spd_fail.get(), st));
+            else
+                MFX_TRY(alsb_fold_launch(fold_b_, h, hx_.get(), x_rows, Y.get(), fold_lambda_, fold_reg_, fold_sweeps_, fold_tol_,
+                                         counts.get(), spd_fail.get(), st));
             break;
         case MFX_FOLD_ALS:
             MFX_TRY(als_half_launch(h, hx_.get(), x_rows, Y.get(), k, fold_lambda_, ws.get(), spd_fail.get(), st));

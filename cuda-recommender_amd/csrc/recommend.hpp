@@ -3,7 +3,8 @@
 // The query is one fused pass per (user block, item slice): scores come out of v_mfma_f32_32x32x2_f32 tiles (H staged
 // in LDS and shared by the 128 users of a workgroup, W in registers), a running per-user threshold keeps the
 // per-score work to one compare, and only the scores that pass reach a per-user candidate list in the workspace;
-// nothing of the users x items score matrix is ever stored.  See recommend.hip.
+// nothing of the users x items score matrix is ever stored.  See recommend.hip; the pass over the tiles of H, which the
+// rank count of rec_rank.hip runs too, is in rec_tiles.hpp.
 #pragma once
 
 #include "als_solver.hpp"  // IalsBlock (fold-in by block sweeps)
@@ -51,6 +52,17 @@ private:
     int topn(const float* wp, uint32_t nu, const uint32_t* users, const uint32_t* ex_ptr, const uint32_t* ex_idx,
              int32_t n_top, uint32_t* items, float* scores, mfx_memspace space, int item_slices, const float* fac,
              const float* qfac);
+    // The ids of a batch [n] from `space` onto the device (buf holds the copy) with every id < bound checked; *dev is where
+    // they are, NULL for ids = NULL.  `what` opens the refusal ("mfx_rec_query: user id").
+    int stage_ids(const uint32_t* ids, uint32_t n, mfx_memspace space, uint32_t bound, const char* what, DevBuf<uint32_t>& buf,
+                  const uint32_t** dev);
+    // Item slices (grid.y) of a tile pass over `blocks` workgroups of slots: `forced`, or for 0 enough for about two workgroups
+    // per CU; at most cap, and none empty.  rank() passes its item_slices; topn() calls this for item_slices = 0 only and
+    // takes a forced count as given (empty slices included: they merge as padding), as it always did.
+    int pick_slices(int forced, int64_t blocks, int cap) const;
+    // What every fold-in setup starts with: the device, fold_model_ = -1 until the setup is through, what another kind of
+    // setup kept (fold_g_ / fold_b_) dropped as asked, hx_ from the tiles.
+    int fold_setup_begin(bool drop_g, bool drop_b);
     // fac_keep_ (when keep is set) and fac_cos_ (after similar_setup) from the device filter bytes keep (NULL: no filter)
     int build_facs(const uint8_t* keep);
     // hq_ from the tiles unless it is there already (similar_setup builds it too): the rows of H that rank() gathers
