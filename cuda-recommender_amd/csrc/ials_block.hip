@@ -379,6 +379,14 @@ int fold_loop(const AlsHalf& h, uint32_t k, float* Y, int32_t sweeps, float tol,
     return MFX_OK;
 }
 
+// One block (d >= k): the step is the solve itself, whatever the start.  The step forms the residual of the start in fp32,
+// so a start adds rounding of the size of |y0|: next to an answer 58 times smaller (implicit model, k = 1 over 8000 rows,
+// y0 ~ 0.1) that alone is a backward error of 6e-5.  A one-block sweep therefore starts every row from zero.
+int one_block_start(float* Y, uint32_t nseg, uint32_t k, uint32_t d, hipStream_t st) {
+    if (d >= k) MFX_HIP(hipMemsetAsync(Y, 0, sizeof(float) * (size_t) nseg * k, st));
+    return MFX_OK;
+}
+
 struct OpStream {
     hipStream_t st = nullptr;
     ~OpStream() { if (st) { (void) hipStreamSynchronize(st); (void) hipStreamDestroy(st); } }
@@ -433,6 +441,7 @@ int ialsb_sweep_launch(IalsBlock& b, const AlsHalf& h, const float* X, uint32_t 
                     als_ws_floats(h.nslots, d) <= std::max<size_t>(1, b.ws.size()),
                 "implicit ALS by block sweeps: workspace too small for this half");
     if (h.nseg == 0) return MFX_OK;
+    MFX_TRY(one_block_start(Y, h.nseg, k, d, st));
     hipLaunchKernelGGL(k_ialsb_scores, dim3(h.nitems), dim3(64), 0, st, h.items.get(), h.nitems, h.idx.get(), X, Y, k, b.score.get());
     MFX_HIP(hipGetLastError());
     for (uint32_t b0 = 0, blk = 0; b0 < k; b0 += d, ++blk) {
@@ -530,6 +539,7 @@ int alsb_sweep_launch(IalsBlock& b, const AlsHalf& h, const float* X, uint32_t x
                     als_ws_floats(h.nslots, d) <= std::max<size_t>(1, b.ws.size()),
                 "explicit ALS by block sweeps: workspace too small for this half");
     if (h.nseg == 0) return MFX_OK;
+    MFX_TRY(one_block_start(Y, h.nseg, k, d, st));
     hipLaunchKernelGGL(k_ialsb_scores, dim3(h.nitems), dim3(64), 0, st, h.items.get(), h.nitems, h.idx.get(), X, Y, k, b.score.get());
     MFX_HIP(hipGetLastError());
     for (uint32_t b0 = 0, blk = 0; b0 < k; b0 += d, ++blk) {

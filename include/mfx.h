@@ -248,9 +248,10 @@ int mfx_ials_half(int64_t nseg, int64_t nnz, const uint32_t* ptr, const uint32_t
  * b = 0, 1, ... of d = `block` coordinates; one step is the exact minimiser of the segment's objective over y_pi:
  *     g = sum_{r_j > 0} (w_j s_j - (1 + w_j)) x_jpi + G[pi, :] y,     A = sum_{r_j > 0} w_j x_jpi x_jpi^T + G[pi, pi],
  *     Delta = A^-1 g,     y_pi <- y_pi - Delta,     s_j <- s_j - <x_jpi, Delta>          (G = X^T X + lambda I)
- * (an empty segment gives y = 0; an explicit zero is no entry).  With a single block (d >= k) from y = 0 a half-sweep
- * solves the system of mfx_ials_half; otherwise it is a different method with different iterates, whose loss still
- * falls monotonically.  Cost per stored pair k d instead of k^2.
+ * (an empty segment gives y = 0; an explicit zero is no entry).  With a single block (d >= k) a half-sweep solves the
+ * system of mfx_ials_half and does not read its start (the residual of a start is formed in fp32, so a start far from the
+ * answer would only add its rounding: the rows start from zero); otherwise it is a different method with different
+ * iterates, whose loss still falls monotonically.  Cost per stored pair k d instead of k^2.
  * block: 0 = chosen from k as min(k, 64), else 1 <= block <= 128 (values above k act as k).  Returns an mfx_als_t:
  * mfx_als_set_factors / _iterate / _get_factors / _kernel_times / _destroy and mfx_ials_loss work on it.
  * mfx_als_set_factors: H required; W NULL = zeros (W is the warm start of the first W-half -- unlike the exact solvers
@@ -277,7 +278,8 @@ int mfx_ials_block_half(int64_t nseg, int64_t nnz, const uint32_t* ptr, const ui
  *     A = sum_j x_jpi x_jpi^T + rho I,     A z = sum_j (r_j - s_j) x_jpi - rho y_pi,     y_pi += z,     s_j += <x_jpi, z>
  * Every stored entry counts, explicit zeros and negative values included (the "r > 0" rule of the implicit code does not
  * apply); an empty segment gives y = 0 (src/ALS.cpp:151-157).  With a single block (d >= k) a step from any start is the
- * exact minimiser: it solves the system of mfx_als_half.  With more than one block this is a different method with
+ * exact minimiser: it solves the system of mfx_als_half, and the start is not read (as in mfx_ials_block_create, the rows
+ * start from zero).  With more than one block this is a different method with
  * different iterates -- a sweep is not a solve -- whose training objective never increases.  Cost per stored pair k d
  * instead of k^2.  No float atomics, every sum has a fixed order: results are bitwise reproducible.
  * block: 0 = chosen from k as min(k, 64), else 1 <= block <= 128 (values above k act as k).  reg: 0 or 1.  T: the test set

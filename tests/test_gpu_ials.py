@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import ials_ref
+from solve_sweep import segments as _segments  # (test_gpu_alsb.py and test_gpu_ialsb.py import it from here)
 
 pytestmark = pytest.mark.gpu
 
@@ -21,17 +22,6 @@ def mfx():
     import mfx as m
     assert m.device_count() >= 1
     return m
-
-
-def _segments(seed, nrows_x, sizes, zero_frac=0.15):
-    """CSR-like segments of the given sizes over distinct rows of X, strengths 1..5 with explicit zeros."""
-    rng = np.random.default_rng(seed)
-    ptr = np.zeros(len(sizes) + 1, np.uint32)
-    ptr[1:] = np.cumsum(sizes)
-    idx = np.concatenate([np.sort(rng.choice(nrows_x, n, replace=False)) for n in sizes]).astype(np.uint32)
-    val = rng.integers(1, 6, idx.size).astype(np.float32)
-    val[rng.random(idx.size) < zero_frac] = 0.0
-    return ptr, idx, val
 
 
 SIZES = [0, 1, 3, 0, 17, 250, 2048, 2049, 2100, 5000, 1]  # 0, 1, 2 and 3 chunks of 2048 entries
