@@ -51,8 +51,24 @@
 #ifndef MFX_ALS_NREG
 #define MFX_ALS_NREG 0
 #endif
+// MFX_ALS_REG = 1 (ials_reg_half.hip with MFX_ALS_IMPLICIT, ials_reg_block_step.hip with MFX_ALS_BLOCK = 1): the implicit
+// kernels with an unobserved weight alpha0 and a regulariser rho_s per segment, the k_ialsr_* / k_ialsrb_* instantiations.
+// a.G is G0 = fp32(alpha0 X^T X) without lambda; an unsplit system / a reducer starts the diagonal of its accumulators from
+// add_rn(G0[c][c], rho[seg]) (rho[seg]: one scalar load per work item) and the rhs weight of an entry is alpha0 + w
+// (block step: (alpha0 + w) - w s).  At alpha0 = 1 and rho = lambda every operation has the operands and the order of
+// k_ials_*.  Translation units of their own for the reason above.
+#ifndef MFX_ALS_REG
+#define MFX_ALS_REG 0
+#endif
+#if MFX_ALS_REG && !MFX_ALS_IMPLICIT
+#error "MFX_ALS_REG needs MFX_ALS_IMPLICIT or MFX_ALS_BLOCK = 1"
+#endif
 #if MFX_ALS_BLOCK == 2
 #define ALS_KERNEL(name) k_alsb_##name
+#elif MFX_ALS_BLOCK && MFX_ALS_REG
+#define ALS_KERNEL(name) k_ialsrb_##name
+#elif MFX_ALS_REG
+#define ALS_KERNEL(name) k_ialsr_##name
 #elif MFX_ALS_BLOCK
 #define ALS_KERNEL(name) k_ialsb_##name
 #elif MFX_ALS_IMPLICIT
@@ -133,7 +149,15 @@ struct AlsArgs {
     const float* score;  // (k_ialsb_*, k_alsb_* only) [nnz + pad]: the score <x_j, y> of every stored pair, parallel to val
     const float* P;      // (k_ialsb_*, k_alsb_* only) [nseg][k]: G[block, :] y of every segment (k_alsb_*: rho y_block)
 #endif
+#if MFX_ALS_REG
+    float alpha0;      // (k_ialsr_*, k_ialsrb_* only) weight of the all-pairs term; G is fp32(alpha0 X^T X)
+    const float* rho;  // (k_ialsr_*, k_ialsrb_* only) [nseg]: the regulariser of every segment (ialsr_rho_launch)
+#endif
 };
+#if MFX_ALS_REG
+// rho of a work item's segment: the segment is the same in every lane, so one scalar load
+__device__ __forceinline__ float ials_rho(const AlsArgs& a, uint32_t seg) { return a.rho[__builtin_amdgcn_readfirstlane((int) seg)]; }
+#endif
 constexpr uint32_t kPhaseCopies = 1024;
 __device__ __forceinline__ void phase_mark(const AlsArgs& a, int slot, unsigned long long& t) {
     if (a.phases && t) {  // (t == 0: a caller that does not take part, e.g. the reducers of split segments)
@@ -633,19 +657,22 @@ __device__ void factor_solve(float* lds, const AlsArgs& a, uint32_t seg, unsigne
 constexpr bool kIalsSqrt = MFX_IALS_SQRT != 0;
 
 // r -> (rhs weight, Gramian operand scale): (1 + w or 0, sqrt(w)) in the sqrt form, (1 + w or 0, w) in the copy form
-__device__ __forceinline__ void ials_weights(float r, float alpha, float& rhs, float& scale, float sv = 0.f) {
+// (k_ialsr_*, k_ialsrb_*: a0 = alpha0 in the place of the 1)
+__device__ __forceinline__ void ials_weights(float r, float alpha, float& rhs, float& scale, float sv = 0.f, float a0 = 1.0f) {
     const float w = mul_rn(alpha, r);
 #if MFX_ALS_BLOCK
-    rhs = r > 0.f ? sub_rn(add_rn(1.0f, w), mul_rn(w, sv)) : 0.f;  // (1 + w) - w s: minus half the gradient's weight at score s
+    rhs = r > 0.f ? sub_rn(add_rn(a0, w), mul_rn(w, sv)) : 0.f;  // (1 + w) - w s: minus half the gradient's weight at score s
 #else
-    rhs = r > 0.f ? add_rn(1.0f, w) : 0.f;
+    rhs = r > 0.f ? add_rn(a0, w) : 0.f;
 #endif
     scale = kIalsSqrt ? __builtin_sqrtf(w) : w;
 }
 
 // G into the 32x32x2 accumulators of k_als_gram<NT>: tile (I, J), register r of lane (c31, h) is G[32 I + (r & 3) + 8 (r >> 2) + 4 h][32 J + c31]
+// (k_ialsr_*, k_ialsrb_*: rho, the segment's regulariser, goes on the diagonal -- one fp32 add on top of G0)
 template <int NT>
-__device__ __forceinline__ void ials_base32(f32x16 (&acc)[Tiles<NT>::kCount], const float* __restrict__ G, uint32_t k, uint32_t c31, uint32_t h) {
+__device__ __forceinline__ void ials_base32(f32x16 (&acc)[Tiles<NT>::kCount], const float* __restrict__ G, uint32_t k, uint32_t c31, uint32_t h,
+                                            float rho = 0.f) {
     int ti = 0;
 #pragma unroll
     for (int I = 0; I < NT; ++I)
@@ -655,14 +682,17 @@ __device__ __forceinline__ void ials_base32(f32x16 (&acc)[Tiles<NT>::kCount], co
             for (int r = 0; r < 16; ++r) {
                 const uint32_t row = 32 * I + (r & 3) + 8 * (r >> 2) + 4 * h, col = 32 * J + c31;
                 acc[ti][r] = row < k && col < k ? G[row * k + col] : 0.f;
+#if MFX_ALS_REG
+                if (I == J && row == col && row < k) acc[ti][r] = add_rn(acc[ti][r], rho);
+#endif
             }
 }
 // One gathered row pair of k_als_gram<NT>, implicit form: rhs from the unscaled row, then the weighted MFMAs
 template <int NT>
 __device__ __forceinline__ void ials_rows(float (&av)[NT], float rv, float alpha, float (&bacc)[NT], f32x16 (&acc)[Tiles<NT>::kCount],
-                                          float sv = 0.f) {
+                                          float sv = 0.f, float a0 = 1.0f) {
     float rw, sw;
-    ials_weights(rv, alpha, rw, sw, sv);
+    ials_weights(rv, alpha, rw, sw, sv, a0);
     float xa[NT];
 #pragma unroll
     for (int I = 0; I < NT; ++I) {
@@ -702,7 +732,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(als_waves(NT
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
     if constexpr (kImplicit)
+#if MFX_ALS_REG
+        if (it.slot < 0) ials_base32<NT>(acc, a.G, k, c31, h, ials_rho(a, it.seg));
+#else
         if (it.slot < 0) ials_base32<NT>(acc, a.G, k, c31, h);  // chunk partials start from zero: the reducer adds G
+#endif
 #pragma unroll
     for (int I = 0; I < NT; ++I) bacc[I] = 0.f;
 
@@ -754,7 +788,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(als_waves(NT
     #pragma unroll
             for (int u = 0; u < U; ++u) {
                 if constexpr (kImplicit) {
-#if MFX_ALS_BLOCK
+#if MFX_ALS_BLOCK && MFX_ALS_REG
+                    ials_rows<NT>(av[s][u], rv[s][u], a.alpha, bacc, acc, sv[s][u], a.alpha0);
+#elif MFX_ALS_REG
+                    ials_rows<NT>(av[s][u], rv[s][u], a.alpha, bacc, acc, 0.f, a.alpha0);
+#elif MFX_ALS_BLOCK
                     ials_rows<NT>(av[s][u], rv[s][u], a.alpha, bacc, acc, sv[s][u]);
 #else
                     ials_rows<NT>(av[s][u], rv[s][u], a.alpha, bacc, acc);
@@ -858,7 +896,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(als_waves(NT
     #pragma unroll
             for (int u = 0; u < U; ++u) {
                 if constexpr (kImplicit) {
-#if MFX_ALS_BLOCK
+#if MFX_ALS_BLOCK && MFX_ALS_REG
+                    ials_rows<NT>(av[u], rv[u], a.alpha, bacc, acc, sv[u], a.alpha0);
+#elif MFX_ALS_REG
+                    ials_rows<NT>(av[u], rv[u], a.alpha, bacc, acc, 0.f, a.alpha0);
+#elif MFX_ALS_BLOCK
                     ials_rows<NT>(av[u], rv[u], a.alpha, bacc, acc, sv[u]);
 #else
                     ials_rows<NT>(av[u], rv[u], a.alpha, bacc, acc);
@@ -904,7 +946,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(als_waves(NT
     for (int t = 0; t < Tiles<NT>::kCount; ++t)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
+#if MFX_ALS_REG
+    ials_base32<NT>(acc, a.G, a.k, lane & 31, lane >> 5, ials_rho(a, rd.seg));
+#else
     if constexpr (kImplicit) ials_base32<NT>(acc, a.G, a.k, lane & 31, lane >> 5);
+#endif
 #pragma unroll
     for (int I = 0; I < NT; ++I) bacc[I] = 0.f;
     for (uint32_t s = 0; s < rd.nslots; ++s) {  // chunk order: deterministic
@@ -931,7 +977,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(als_waves(NT
 constexpr int kSets = 4, kTiles16 = kSets * (kSets + 1) / 2;
 
 // G [k][k] into the 16x16x4 accumulators of k_als_gram16: tile (e, f), register q of lane (c, g) is G[4 (4 g + q) + e][4 c + f]
-__device__ __forceinline__ void ials_base16(f32x4 (&acc)[kTiles16], const float* __restrict__ G, uint32_t k, uint32_t c, uint32_t g) {
+// (k_ialsr_*, k_ialsrb_*: rho on the diagonal, as in ials_base32)
+__device__ __forceinline__ void ials_base16(f32x4 (&acc)[kTiles16], const float* __restrict__ G, uint32_t k, uint32_t c, uint32_t g,
+                                            float rho = 0.f) {
     int ti = 0;
 #pragma unroll
     for (int e = 0; e < kSets; ++e)
@@ -941,6 +989,9 @@ __device__ __forceinline__ void ials_base16(f32x4 (&acc)[kTiles16], const float*
             for (int q = 0; q < 4; ++q) {
                 const uint32_t row = 4 * (4 * g + q) + e, col = 4 * c + f;
                 acc[ti][q] = row < k && col < k ? G[row * k + col] : 0.f;
+#if MFX_ALS_REG
+                if (e == f && row == col && row < k) acc[ti][q] = add_rn(acc[ti][q], rho);
+#endif
             }
 }
 
@@ -1051,12 +1102,16 @@ __device__ __forceinline__ void g16_load_rows(Gram16Regs<D>& r, const char* __re
     }
 }
 template <int D, int S>
-__device__ __forceinline__ void g16_mfma(Gram16Regs<D>& r, float alpha) {
+__device__ __forceinline__ void g16_mfma(Gram16Regs<D>& r, float alpha, float a0 = 1.0f) {
 #pragma unroll
     for (int u = 0; u < kU16; ++u) {
         if constexpr (kImplicit) {  // the same with the weights of ials_weights: rhs from the unscaled row, then the MFMAs
             float rw, sw;
-#if MFX_ALS_BLOCK
+#if MFX_ALS_BLOCK && MFX_ALS_REG
+            ials_weights(r.rv[S][u], alpha, rw, sw, r.sv[S][u], a0);
+#elif MFX_ALS_REG
+            ials_weights(r.rv[S][u], alpha, rw, sw, 0.f, a0);
+#elif MFX_ALS_BLOCK
             ials_weights(r.rv[S][u], alpha, rw, sw, r.sv[S][u]);
 #else
             ials_weights(r.rv[S][u], alpha, rw, sw);
@@ -1102,6 +1157,9 @@ struct Gram16Ctx {  // loop-invariant operands of the stages
 #if MFX_ALS_BLOCK
     const float* sbase;
 #endif
+#if MFX_ALS_REG
+    float alpha0;
+#endif
 };
 // Steps s, s + 1, ... on sets U, U + 1, ... D - 1: MFMAs of step s on set U, the factor rows of step s + D - 1 into the
 // set the previous step has just released, the indices of step s + D into this step's own (already consumed) slots.
@@ -1117,7 +1175,11 @@ __device__ __forceinline__ bool g16_steps(Gram16Regs<D>& r, const Gram16Ctx& c, 
 #endif
         g16_load_idx<D, U>(r, c.ibase, s + D, c.g);
         __builtin_amdgcn_sched_barrier(0);
+#if MFX_ALS_REG
+        g16_mfma<D, U>(r, c.alpha, c.alpha0);
+#else
         g16_mfma<D, U>(r, c.alpha);
+#endif
         __builtin_amdgcn_sched_barrier(0);
         if (++s * kRows16 >= c.len) return true;
         return g16_steps<D, U + 1>(r, c, s);
@@ -1166,7 +1228,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES
 #pragma unroll
     for (int t = 0; t < kTiles16; ++t) r.acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
     if constexpr (kImplicit)
+#if MFX_ALS_REG
+        if (it.slot < 0) ials_base16(r.acc, a.G, k, c, g, ials_rho(a, it.seg));
+#else
         if (it.slot < 0) ials_base16(r.acc, a.G, k, c, g);  // chunk partials start from zero: the reducer adds G
+#endif
     r.bacc[0] = r.bacc[1] = f32x2{0.f, 0.f};
 
     Gram16Ctx cx;
@@ -1183,6 +1249,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES
     cx.zero_off = a.x_rows * cx.rowbytes;
     cx.g = g;
     if constexpr (kImplicit) cx.alpha = a.alpha;
+#if MFX_ALS_REG
+    cx.alpha0 = a.alpha0;
+#endif
     g16_prologue<D, 0>(r, cx);
     for (uint32_t s = 0;;)
         if (g16_steps<D, 0>(r, cx, s)) break;
@@ -1213,7 +1282,11 @@ __global__ __launch_bounds__(64) void ALS_KERNEL(reduce16)(AlsArgs a) {
     float bacc[kSets];
 #pragma unroll
     for (int t = 0; t < kTiles16; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+#if MFX_ALS_REG
+    ials_base16(acc, a.G, a.k, lane & 15, lane >> 4, ials_rho(a, rd.seg));
+#else
     if constexpr (kImplicit) ials_base16(acc, a.G, a.k, lane & 15, lane >> 4);
+#endif
 #pragma unroll
     for (int e = 0; e < kSets; ++e) bacc[e] = 0.f;
     for (uint32_t s = 0; s < rd.nslots; ++s) {  // chunk order: deterministic
@@ -1315,6 +1388,26 @@ int alsb_step_launch(const AlsHalf& h, const float* Xb, uint32_t x_rows, float* 
     a.X = Xb; a.x_rows = x_rows; a.sentinel = (uint32_t) h.nnz; a.Y = Z; a.k = d; a.lambda = lambda; a.ws = ws; a.spd_fail = spd_fail;
     a.seg_ptr = reg ? h.ptr.get() : nullptr;
     a.score = score; a.P = P;
+    return launch_half(a, h.nitems, h.nreduces, h.nnz, st);
+}
+#elif MFX_ALS_BLOCK && MFX_ALS_REG
+int ialsrb_step_launch(const AlsHalf& h, const float* Xb, uint32_t x_rows, float* Z, uint32_t d, const float* Gbb, float alpha, float alpha0,
+                       const float* rho, const float* score, const float* P, float* ws, uint32_t* spd_fail, hipStream_t st) {
+    AlsArgs a{};
+    a.items = h.items.get(); a.reduces = h.reduces.get(); a.idx = h.idx.get(); a.val = h.val.get();
+    a.X = Xb; a.x_rows = x_rows; a.sentinel = (uint32_t) h.nnz; a.Y = Z; a.k = d; a.ws = ws; a.spd_fail = spd_fail;
+    a.lambda = 0.f;  // rho goes on the diagonal with the start of the accumulators
+    a.alpha = alpha; a.G = Gbb; a.score = score; a.P = P; a.alpha0 = alpha0; a.rho = rho;
+    return launch_half(a, h.nitems, h.nreduces, h.nnz, st);
+}
+#elif MFX_ALS_REG
+int ialsr_half_launch(const AlsHalf& h, const float* X, uint32_t x_rows, float* Y, uint32_t k, const float* G0, float alpha, float alpha0,
+                      const float* rho, float* ws, uint32_t* spd_fail, hipStream_t st) {
+    AlsArgs a{};
+    a.items = h.items.get(); a.reduces = h.reduces.get(); a.idx = h.idx.get(); a.val = h.val.get();
+    a.X = X; a.x_rows = x_rows; a.sentinel = (uint32_t) h.nnz; a.Y = Y; a.k = k; a.ws = ws; a.spd_fail = spd_fail;
+    a.lambda = 0.f;  // rho goes on the diagonal with the start of the accumulators
+    a.alpha = alpha; a.G = G0; a.alpha0 = alpha0; a.rho = rho;
     return launch_half(a, h.nitems, h.nreduces, h.nnz, st);
 }
 #elif MFX_ALS_BLOCK
@@ -1448,6 +1541,35 @@ int AlsSolver::create_block(AlsSolver** out, const mfx_csx* R, const mfx_params*
     return MFX_OK;
 }
 
+int AlsSolver::create_implicit_reg(AlsSolver** out, const mfx_csx* R, const mfx_params* p, float alpha, float alpha0, float nu, int32_t block,
+                                   mfx_memspace space) {
+    const bool blk = block >= 0;
+    const char* fn = blk ? "mfx_ials_block_create_reg" : "mfx_ials_create_reg";
+    MFX_REQUIRE(out && R && p, "%s: null argument", fn);
+    MFX_REQUIRE(space == MFX_HOST || space == MFX_DEVICE, "%s: bad memory space", fn);
+    MFX_REQUIRE(std::isfinite(alpha) && alpha >= 0.f, "%s: alpha = %g (finite and >= 0 required)", fn, (double) alpha);
+    if (blk) {
+        MFX_REQUIRE(p->k >= 1 && p->k <= kIalsBlockMaxRank, "implicit ALS by block sweeps: rank k = %u not supported (1 <= k <= %u)", p->k,
+                    kIalsBlockMaxRank);
+        MFX_REQUIRE(block <= (int32_t) kIalsBlockMaxBlock, "implicit ALS by block sweeps: block = %d (0 = chosen from k, else 1 <= block <= %u)",
+                    block, kIalsBlockMaxBlock);
+    } else {
+        MFX_REQUIRE(p->k >= 1 && p->k <= 128, "implicit ALS: rank k = %u not supported (1 <= k <= 128)", p->k);
+    }
+    MFX_REQUIRE(p->schedule == 1, "%s: schedule must be 1 (there is no as-written mode)", fn);
+    MFX_TRY(ialsr_check_params(fn, p->lambda, alpha0, nu, R->rows, R->cols));
+    std::unique_ptr<AlsSolver> s(new AlsSolver());
+    s->implicit_ = true;
+    s->alpha_ = alpha;
+    s->robj_ = true;
+    s->alpha0_ = alpha0;
+    s->nu_ = nu;
+    if (blk) s->block_ = std::min<uint32_t>(block ? (uint32_t) block : ialsb_default_block(p->k), p->k);
+    MFX_TRY(s->init(R, nullptr, p, space, nullptr));
+    *out = s.release();
+    return MFX_OK;
+}
+
 int AlsSolver::create_block_explicit(AlsSolver** out, const mfx_csx* R, const mfx_coo* T, const mfx_params* p, int32_t block, int32_t reg,
                                      mfx_memspace space) {
     MFX_REQUIRE(out && R && p, "mfx_als_block_create: null argument");
@@ -1556,9 +1678,14 @@ int AlsSolver::init(const mfx_csx* R, const mfx_coo* T, const mfx_params* p, mfx
         } else {
             MFX_TRY(G_.alloc((size_t) k_ * k_));
             MFX_TRY(gpart_.alloc(ials_base_ws_floats(std::max(m_, n_), k_)));
-            MFX_TRY(loss_ws_.alloc(ials_loss_ws_doubles(k_)));  // (block sweeps: on the first loss(), up to 1 GB at k = 1024)
+            MFX_TRY(loss_ws_.alloc(robj_ ? ialsr_loss_ws_doubles(k_) : ials_loss_ws_doubles(k_)));  // (block sweeps: on the first loss(), up to 1 GB at k = 1024)
         }
         MFX_TRY(loss_.alloc_zero(1, st_));
+        if (robj_) {  // rho of every row over the n_ items and of every column over the m_ users
+            MFX_TRY(rho_rows_.alloc(m_)); MFX_TRY(rho_cols_.alloc(n_));
+            MFX_TRY(ialsr_rho_launch(rows_, n_, p_.lambda, alpha0_, nu_, rho_rows_.get(), st_));
+            MFX_TRY(ialsr_rho_launch(cols_, m_, p_.lambda, alpha0_, nu_, rho_cols_.get(), st_));
+        }
     } else if (block_) {
         MFX_TRY(als_check_finite(rows_.val.get(), rows_.nnz, "explicit ALS by block sweeps: R (CSR) value", st_));
         MFX_TRY(als_check_finite(cols_.val.get(), cols_.nnz, "explicit ALS by block sweeps: R (CSC) value", st_));
@@ -1636,10 +1763,18 @@ int AlsSolver::iterate(int n_iter, int with_rmse, mfx_iter_report* reports) {
         MFX_HIP(hipEventRecord(ev_[0], st_));
         if (block_ && !implicit_) {
             MFX_TRY(alsb_half_launch(bs_, rows_, H_.get(), n_, W_.get(), p_.lambda, reg_, spd_fail_.get(), st_));
+        } else if (block_ && robj_) {
+            MFX_TRY(ialsrb_gramian(bs_, H_.get(), n_, alpha0_, st_));
+            MFX_HIP(hipEventRecord(ev_[4], st_));
+            MFX_TRY(ialsb_half_launch(bs_, rows_, H_.get(), n_, W_.get(), alpha_, spd_fail_.get(), st_, alpha0_, rho_rows_.get()));
         } else if (block_) {
             MFX_TRY(ialsb_gramian(bs_, H_.get(), n_, p_.lambda, st_));
             MFX_HIP(hipEventRecord(ev_[4], st_));
             MFX_TRY(ialsb_half_launch(bs_, rows_, H_.get(), n_, W_.get(), alpha_, spd_fail_.get(), st_));
+        } else if (robj_) {
+            MFX_TRY(ialsr_base_gramian(H_.get(), n_, k_, alpha0_, gpart_.get(), G_.get(), st_));
+            MFX_HIP(hipEventRecord(ev_[4], st_));
+            MFX_TRY(ialsr_half_launch(rows_, H_.get(), n_, W_.get(), k_, G_.get(), alpha_, alpha0_, rho_rows_.get(), ws_.get(), spd_fail_.get(), st_));
         } else if (implicit_) {  // (ev_[4]: the base Gramian of H is done)
             MFX_TRY(ials_base_gramian(H_.get(), n_, k_, p_.lambda, gpart_.get(), G_.get(), st_));
             MFX_HIP(hipEventRecord(ev_[4], st_));
@@ -1654,10 +1789,18 @@ int AlsSolver::iterate(int n_iter, int with_rmse, mfx_iter_report* reports) {
         if (phases_.size()) MFX_TRY(print_phases("user half (W over H)"));
         if (block_ && !implicit_) {
             MFX_TRY(alsb_half_launch(bs_, cols_, W_.get(), m_, H_.get(), p_.lambda, reg_, spd_fail_.get(), st_));
+        } else if (block_ && robj_) {
+            MFX_TRY(ialsrb_gramian(bs_, W_.get(), m_, alpha0_, st_));
+            MFX_HIP(hipEventRecord(ev_[5], st_));
+            MFX_TRY(ialsb_half_launch(bs_, cols_, W_.get(), m_, H_.get(), alpha_, spd_fail_.get(), st_, alpha0_, rho_cols_.get()));
         } else if (block_) {
             MFX_TRY(ialsb_gramian(bs_, W_.get(), m_, p_.lambda, st_));
             MFX_HIP(hipEventRecord(ev_[5], st_));
             MFX_TRY(ialsb_half_launch(bs_, cols_, W_.get(), m_, H_.get(), alpha_, spd_fail_.get(), st_));
+        } else if (robj_) {
+            MFX_TRY(ialsr_base_gramian(W_.get(), m_, k_, alpha0_, gpart_.get(), G_.get(), st_));
+            MFX_HIP(hipEventRecord(ev_[5], st_));
+            MFX_TRY(ialsr_half_launch(cols_, W_.get(), m_, H_.get(), k_, G_.get(), alpha_, alpha0_, rho_cols_.get(), ws_.get(), spd_fail_.get(), st_));
         } else if (implicit_) {  // (ev_[5]: the base Gramian of W is done)
             MFX_TRY(ials_base_gramian(W_.get(), m_, k_, p_.lambda, gpart_.get(), G_.get(), st_));
             MFX_HIP(hipEventRecord(ev_[5], st_));
@@ -1748,8 +1891,12 @@ int AlsSolver::loss(double* out) {
     MFX_REQUIRE(implicit_, "mfx_ials_loss: not an implicit-feedback ALS handle (mfx_ials_create)");
     MFX_REQUIRE(factors_set_, "mfx_ials_loss: call mfx_als_set_factors first");
     MFX_TRY(use_device(device_));
-    if (!loss_ws_.size()) MFX_TRY(loss_ws_.alloc(ials_loss_ws_doubles(k_)));
-    MFX_TRY(ials_loss_launch(rows_, W_.get(), m_, H_.get(), n_, k_, p_.lambda, alpha_, loss_ws_.get(), loss_.get(), st_));
+    if (!loss_ws_.size()) MFX_TRY(loss_ws_.alloc(robj_ ? ialsr_loss_ws_doubles(k_) : ials_loss_ws_doubles(k_)));
+    if (robj_)
+        MFX_TRY(ialsr_loss_launch(rows_, W_.get(), m_, H_.get(), n_, k_, p_.lambda, alpha_, alpha0_, nu_, rho_rows_.get(), rho_cols_.get(),
+                                  loss_ws_.get(), loss_.get(), st_));
+    else
+        MFX_TRY(ials_loss_launch(rows_, W_.get(), m_, H_.get(), n_, k_, p_.lambda, alpha_, loss_ws_.get(), loss_.get(), st_));
     MFX_HIP(hipMemcpyAsync(out, loss_.get(), sizeof(double), hipMemcpyDeviceToHost, st_));
     MFX_HIP(hipStreamSynchronize(st_));
     return MFX_OK;
@@ -1827,6 +1974,31 @@ int ials_half_op(int64_t nseg, int64_t nnz, const uint32_t* ptr, const uint32_t*
     MFX_TRY(fail_cnt.alloc_zero(1, os.st));
     MFX_TRY(ials_base_gramian(dX.get(), (uint32_t) nrows_x, (uint32_t) k, lambda, part.get(), G.get(), os.st));
     MFX_TRY(ials_half_launch(h, dX.get(), (uint32_t) nrows_x, dY.get(), (uint32_t) k, G.get(), alpha, ws.get(), fail_cnt.get(), os.st));
+    MFX_HIP(hipMemcpyAsync(Y, dY.get(), sizeof(float) * (size_t) nseg * k, hipMemcpyDeviceToHost, os.st));
+    MFX_HIP(hipStreamSynchronize(os.st));
+    return MFX_OK;
+}
+
+int ials_half_reg_op(int64_t nseg, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val, int64_t nrows_x, const float* X,
+                     float* Y, int64_t k, float lambda, float alpha, float alpha0, float nu, int device) {
+    MFX_TRY(use_device(device));
+    OpStream os;
+    MFX_HIP(hipStreamCreateWithFlags(&os.st, hipStreamNonBlocking));
+    AlsHalf h;
+    MFX_TRY(h.build((uint32_t) nseg, (uint64_t) nnz, (uint32_t) nrows_x, ptr, idx, val, MFX_HOST, kAlsChunk, os.st));
+    MFX_TRY(ials_check_values(h.val.get(), h.nnz, alpha, "mfx_ials_half_reg: value", os.st));
+    DevBuf<float> dX, dY, ws, G, part, rho; DevBuf<uint32_t> fail_cnt;
+    MFX_TRY(dX.alloc_zero(((size_t) nrows_x + 1) * k, os.st)); MFX_TRY(dX.upload(X, (size_t) nrows_x * k, MFX_HOST, os.st));
+    MFX_TRY(dY.alloc_zero((size_t) nseg * k, os.st));
+    MFX_TRY(ws.alloc(std::max<size_t>(1, als_ws_floats(h.nslots, (uint32_t) k))));
+    MFX_TRY(G.alloc((size_t) k * k));
+    MFX_TRY(part.alloc(ials_base_ws_floats((uint32_t) nrows_x, (uint32_t) k)));
+    MFX_TRY(rho.alloc((size_t) nseg));
+    MFX_TRY(fail_cnt.alloc_zero(1, os.st));
+    MFX_TRY(ialsr_rho_launch(h, (uint32_t) nrows_x, lambda, alpha0, nu, rho.get(), os.st));
+    MFX_TRY(ialsr_base_gramian(dX.get(), (uint32_t) nrows_x, (uint32_t) k, alpha0, part.get(), G.get(), os.st));
+    MFX_TRY(ialsr_half_launch(h, dX.get(), (uint32_t) nrows_x, dY.get(), (uint32_t) k, G.get(), alpha, alpha0, rho.get(), ws.get(),
+                              fail_cnt.get(), os.st));
     MFX_HIP(hipMemcpyAsync(Y, dY.get(), sizeof(float) * (size_t) nseg * k, hipMemcpyDeviceToHost, os.st));
     MFX_HIP(hipStreamSynchronize(os.st));
     return MFX_OK;

@@ -63,21 +63,50 @@ int ialsb_gramian(IalsBlock& b, const float* X, uint32_t rows, float lambda, hip
 // the scores, then for every block in ascending order G[block, :] y, the block systems (k_ialsb_*: ialsb_step_launch) and
 // the update of y and of the scores)
 int ialsb_pack_launch(IalsBlock& b, const float* X, uint32_t x_rows, hipStream_t st);
+// rho != NULL (mfx_ials_block_create_reg): b.G holds G0 = fp32(alpha0 X^T X) (ialsrb_gramian), rho [h.nseg] the regulariser of
+// every segment (ialsr_rho_launch); P gets fmaf(rho, y_block, .) on top of Y G0[:, block] and the systems are the k_ialsrb_* ones
 int ialsb_sweep_launch(IalsBlock& b, const AlsHalf& h, const float* X, uint32_t x_rows, float* Y, float alpha, uint32_t* spd_fail,
-                       hipStream_t st);
+                       hipStream_t st, float alpha0 = 1.f, const float* rho = nullptr);
 int ialsb_half_launch(IalsBlock& b, const AlsHalf& h, const float* X, uint32_t x_rows, float* Y, float alpha, uint32_t* spd_fail,
-                      hipStream_t st);
+                      hipStream_t st, float alpha0 = 1.f, const float* rho = nullptr);
 // Fold-in: up to `sweeps` sweeps in place on Y over a side packed before (ialsb_pack_launch).  An empty row is zero and counts
 // 0 sweeps.  tol = 0: every other row gets `sweeps`, nothing is read back.  tol > 0: after each sweep a row is frozen once
 // max |y_new - y_old| <= tol max |y_new| (its bits never change again), and the host reads the number of rows still moving
 // to stop early.  counts: device [h.nseg] (sweeps applied to each row) or NULL.
 int ialsb_fold_launch(IalsBlock& b, const AlsHalf& h, const float* X, uint32_t x_rows, float* Y, float alpha, int32_t sweeps, float tol,
-                      int32_t* counts, uint32_t* spd_fail, hipStream_t st);
+                      int32_t* counts, uint32_t* spd_fail, hipStream_t st, float alpha0 = 1.f, const float* rho = nullptr);
 // ials_block_step.hip (als_solver.hip compiled with MFX_ALS_BLOCK): the systems of one block, Z [nseg][d] = the steps
 int ialsb_step_launch(const AlsHalf& h, const float* Xb, uint32_t x_rows, float* Z, uint32_t d, const float* Gbb, float alpha,
                       const float* score, const float* P, float* ws, uint32_t* spd_fail, hipStream_t st);
 int ials_block_half_op(int64_t nseg, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val, int64_t nrows_x,
                        const float* X, const float* Y_in, float* Y_out, int64_t k, int32_t block, float lambda, float alpha, int device);
+
+// Implicit ALS with an unobserved weight alpha0 and a regulariser per segment rho_s = fp32(lambda (n_s + alpha0 N)^nu), n_s the
+// segment's entries with r > 0 and N the rows of the fixed side (mfx_ials_create_reg, mfx_ials_block_create_reg).
+// MFX_ERR_INVALID naming "alpha0", "nu" or "regulariser"; touches no device
+int ialsr_check_params(const char* fn, float lambda, float alpha0, float nu, int64_t rows, int64_t cols);
+// rho [h.nseg] of the segments of h over a fixed side of N rows (ials.hip; fp64 on the device)
+int ialsr_rho_launch(const AlsHalf& h, uint32_t N, float lambda, float alpha0, float nu, float* rho, hipStream_t st);
+// G[i] = fp32(alpha0 G[i]) over n floats; G0 = fp32(alpha0 X^T X) for k <= 128 (ials_base_gramian with lambda = 0, then the
+// scale) and for any k <= 1024 into b.G (ialsb_gramian likewise)
+int ialsr_scale_launch(float* G, size_t n, float alpha0, hipStream_t st);
+int ialsr_base_gramian(const float* X, uint32_t rows, uint32_t k, float alpha0, float* part, float* G0, hipStream_t st);
+int ialsrb_gramian(IalsBlock& b, const float* X, uint32_t rows, float alpha0, hipStream_t st);
+// ials_reg_half.hip (als_solver.hip compiled with MFX_ALS_IMPLICIT and MFX_ALS_REG): the half-sweep, k <= 128
+int ialsr_half_launch(const AlsHalf& h, const float* X, uint32_t x_rows, float* Y, uint32_t k, const float* G0, float alpha, float alpha0,
+                      const float* rho, float* ws, uint32_t* spd_fail, hipStream_t st);
+// ials_reg_block_step.hip (MFX_ALS_BLOCK = 1 and MFX_ALS_REG): the systems of one block
+int ialsrb_step_launch(const AlsHalf& h, const float* Xb, uint32_t x_rows, float* Z, uint32_t d, const float* Gbb, float alpha, float alpha0,
+                       const float* rho, const float* score, const float* P, float* ws, uint32_t* spd_fail, hipStream_t st);
+// the objective of these handles (generalises ials_loss_launch; nu = 0 takes the regulariser from the Gramians' traces)
+size_t ialsr_loss_ws_doubles(uint32_t k);
+int ialsr_loss_launch(const AlsHalf& rows, const float* W, uint32_t m, const float* H, uint32_t n, uint32_t k, float lambda, float alpha,
+                      float alpha0, float nu, const float* rho_rows, const float* rho_cols, double* ws, double* out, hipStream_t st);
+int ials_half_reg_op(int64_t nseg, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val, int64_t nrows_x, const float* X,
+                     float* Y, int64_t k, float lambda, float alpha, float alpha0, float nu, int device);
+int ials_block_half_reg_op(int64_t nseg, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val, int64_t nrows_x,
+                           const float* X, const float* Y_in, float* Y_out, int64_t k, int32_t block, float lambda, float alpha, float alpha0,
+                           float nu, int device);
 
 // Explicit ALS by block subspace sweeps (mfx_als_block_create; the explicit part of ials_block.hip): the objective
 // sum_j (r_j - <x_j, y>)^2 + rho |y|^2 of a segment, rho = lambda (reg 0) or fp32(lambda * n) for n stored entries (reg 1),
@@ -112,6 +141,10 @@ public:
     // explicit feedback by block subspace sweeps (mfx_als_block_create): k <= 1024, block = 0 or 1..128, reg 0 / 1
     static int create_block_explicit(AlsSolver** out, const mfx_csx* R, const mfx_coo* T, const mfx_params* p, int32_t block, int32_t reg,
                                      mfx_memspace space);
+    // the same two with an unobserved weight and a frequency-scaled regulariser (mfx_ials_create_reg: block < 0;
+    // mfx_ials_block_create_reg: block >= 0)
+    static int create_implicit_reg(AlsSolver** out, const mfx_csx* R, const mfx_params* p, float alpha, float alpha0, float nu, int32_t block,
+                                   mfx_memspace space);
     bool implicit() const { return implicit_; }
     int loss(double* out);  // implicit only: the objective at the current factors (ials.hip)
     ~AlsSolver();
@@ -158,6 +191,10 @@ private:
     uint32_t block_ = 0;             // > 0: block subspace sweeps with blocks of block_ coordinates
     IalsBlock bs_;
     int32_t reg_ = 0;                // explicit block sweeps: 1 = fp32(lambda * n) on the diagonal of a segment of n entries
+    // implicit feedback with an unobserved weight and a regulariser per segment (create_implicit_reg)
+    bool robj_ = false;
+    float alpha0_ = 1.f, nu_ = 0.f;
+    DevBuf<float> rho_rows_, rho_cols_;  // [m_], [n_]: formed once, the pattern of R is fixed
 };
 
 // Launches one half-sweep: Y[seg] = argmin over segment `seg` given factor rows X[x_rows + 1][k],

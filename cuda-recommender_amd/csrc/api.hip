@@ -324,6 +324,60 @@ int mfx_ials_half(int64_t nseg, int64_t nnz, const uint32_t* ptr, const uint32_t
     });
 }
 
+/* ------------------------------------------------------------------ implicit ALS: unobserved weight, scaled regulariser */
+int mfx_ials_create_reg(mfx_als_t* out, const mfx_csx* R, const mfx_params* p, float alpha, float alpha0, float nu, mfx_memspace space) {
+    return guarded("mfx_ials_create_reg", [&]() -> int {
+        MFX_REQUIRE(out, "mfx_ials_create_reg: out is NULL");
+        *out = nullptr;
+        AlsSolver* s = nullptr;
+        MFX_TRY(AlsSolver::create_implicit_reg(&s, R, p, alpha, alpha0, nu, -1, space));  // (argument checks before the device is touched)
+        *out = new mfx_als_s{s};
+        return MFX_OK;
+    });
+}
+int mfx_ials_block_create_reg(mfx_als_t* out, const mfx_csx* R, const mfx_params* p, float alpha, float alpha0, float nu, int32_t block,
+                              mfx_memspace space) {
+    return guarded("mfx_ials_block_create_reg", [&]() -> int {
+        MFX_REQUIRE(out, "mfx_ials_block_create_reg: out is NULL");
+        *out = nullptr;
+        MFX_REQUIRE(block >= 0, "implicit ALS by block sweeps: block = %d (0 = chosen from k, else 1 <= block <= %u)", block, kIalsBlockMaxBlock);
+        AlsSolver* s = nullptr;
+        MFX_TRY(AlsSolver::create_implicit_reg(&s, R, p, alpha, alpha0, nu, block, space));
+        *out = new mfx_als_s{s};
+        return MFX_OK;
+    });
+}
+int mfx_ials_half_reg(int64_t nseg, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val, int64_t nrows_x, const float* X,
+                      float* Y, int64_t k, float lambda, float alpha, float alpha0, float nu, int device) {
+    return guarded("mfx_ials_half_reg", [&]() -> int {
+        MFX_REQUIRE(nseg > 0 && nnz >= 0 && ptr && X && Y && nrows_x > 0, "mfx_ials_half_reg: bad argument");
+        MFX_REQUIRE(nnz == 0 || (idx && val), "mfx_ials_half_reg: null idx / val with nnz > 0");
+        MFX_REQUIRE(k >= 1 && k <= 128, "implicit ALS: rank k = %lld not supported (1 <= k <= 128)", (long long) k);
+        MFX_REQUIRE(std::isfinite(alpha) && alpha >= 0.f, "mfx_ials_half_reg: alpha = %g (finite and >= 0 required)", (double) alpha);
+        MFX_REQUIRE(nseg < (int64_t) 0xFFFFFFFFll && nrows_x < (int64_t) 0xFFFFFFFFll && nnz < (int64_t) 0xFFFF0000ll,
+                    "mfx_ials_half_reg: sizes exceed the 32-bit index range");
+        MFX_TRY(ialsr_check_params("mfx_ials_half_reg", lambda, alpha0, nu, nseg, nrows_x));
+        return ials_half_reg_op(nseg, nnz, ptr, idx, val, nrows_x, X, Y, k, lambda, alpha, alpha0, nu, device);
+    });
+}
+int mfx_ials_block_half_reg(int64_t nseg, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val, int64_t nrows_x,
+                            const float* X, const float* Y_in, float* Y_out, int64_t k, int32_t block, float lambda, float alpha,
+                            float alpha0, float nu, int device) {
+    return guarded("mfx_ials_block_half_reg", [&]() -> int {
+        MFX_REQUIRE(nseg > 0 && nnz >= 0 && ptr && X && Y_out && nrows_x > 0, "mfx_ials_block_half_reg: bad argument");
+        MFX_REQUIRE(nnz == 0 || (idx && val), "mfx_ials_block_half_reg: null idx / val with nnz > 0");
+        MFX_REQUIRE(k >= 1 && k <= (int64_t) kIalsBlockMaxRank, "implicit ALS by block sweeps: rank k = %lld not supported (1 <= k <= %u)",
+                    (long long) k, kIalsBlockMaxRank);
+        MFX_REQUIRE(block >= 0 && block <= (int32_t) kIalsBlockMaxBlock,
+                    "implicit ALS by block sweeps: block = %d (0 = chosen from k, else 1 <= block <= %u)", block, kIalsBlockMaxBlock);
+        MFX_REQUIRE(std::isfinite(alpha) && alpha >= 0.f, "mfx_ials_block_half_reg: alpha = %g (finite and >= 0 required)", (double) alpha);
+        MFX_REQUIRE(nseg < (int64_t) 0xFFFFFFFFll && nrows_x < (int64_t) 0xFFFFFFFFll && nnz < (int64_t) 0xFFFF0000ll,
+                    "mfx_ials_block_half_reg: sizes exceed the 32-bit index range");
+        MFX_TRY(ialsr_check_params("mfx_ials_block_half_reg", lambda, alpha0, nu, nseg, nrows_x));
+        return ials_block_half_reg_op(nseg, nnz, ptr, idx, val, nrows_x, X, Y_in, Y_out, k, block, lambda, alpha, alpha0, nu, device);
+    });
+}
+
 int mfx_als_run(const mfx_csx* R, const mfx_coo* T, float* W, float* H, const mfx_params* p,
                 mfx_iter_report* reports) {
     return guarded("mfx_als_run", [&]() -> int {
@@ -536,6 +590,18 @@ int mfx_rec_fold_in_block_setup(mfx_rec_t r, float lambda, float alpha, int32_t 
     return guarded("mfx_rec_fold_in_block_setup", [&]() -> int {
         MFX_REQUIRE(r && r->impl, "null recommender");
         return r->impl->fold_in_block_setup(lambda, alpha, block, sweeps, tol);
+    });
+}
+int mfx_rec_fold_in_setup_reg(mfx_rec_t r, float lambda, float alpha, float alpha0, float nu) {
+    return guarded("mfx_rec_fold_in_setup_reg", [&]() -> int {
+        MFX_REQUIRE(r && r->impl, "mfx_rec_fold_in_setup_reg: null handle");
+        return r->impl->fold_in_setup_reg(lambda, alpha, alpha0, nu);
+    });
+}
+int mfx_rec_fold_in_block_setup_reg(mfx_rec_t r, float lambda, float alpha, float alpha0, float nu, int32_t block, int32_t sweeps, float tol) {
+    return guarded("mfx_rec_fold_in_block_setup_reg", [&]() -> int {
+        MFX_REQUIRE(r && r->impl, "mfx_rec_fold_in_block_setup_reg: null handle");
+        return r->impl->fold_in_block_setup_reg(lambda, alpha, alpha0, nu, block, sweeps, tol);
     });
 }
 int mfx_rec_fold_in_block_setup_als(mfx_rec_t r, float lambda, int32_t reg, int32_t block, int32_t sweeps, float tol) {

@@ -8,6 +8,7 @@
 // gathered ones; the partials are then summed in partition order -- no float atomics, bitwise reproducible.
 #include <algorithm>
 #include <cfloat>
+#include <cmath>
 
 #include "als_solver.hpp"
 
@@ -209,6 +210,109 @@ __global__ __launch_bounds__(256) void k_ials_check(uint64_t n, const float* __r
     if (bad != ~0ull) atomicMin(first_bad, bad);
 }
 
+// ---- unobserved weight alpha0 and a regulariser per segment (mfx_ials_create_reg) -----------------------
+// G0 = fp32(alpha0 S) from S = X^T X as the kernels above sum it (launched with lambda = 0): one rounding on top of S
+__global__ __launch_bounds__(256) void k_ialsr_scale(float* __restrict__ G, uint32_t n, float alpha0) {
+#pragma clang fp contract(off)
+    const uint32_t e = blockIdx.x * 256 + threadIdx.x;
+    if (e < n) G[e] = alpha0 * G[e];
+}
+
+// rho[s] = fp32(lambda (n_s + alpha0 N)^nu), n_s = the stored entries of segment s with r > 0; all of it in fp64, unfused.
+// One wavefront per segment; the count is an integer sum (no order).
+__global__ __launch_bounds__(256) void k_ialsr_rho(const uint32_t* __restrict__ ptr, const float* __restrict__ val, uint32_t nseg, double lambda,
+                                                   double alpha0, double N, double nu, float* __restrict__ rho) {
+#pragma clang fp contract(off)
+    const uint32_t lane = threadIdx.x & 63, seg = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (seg >= nseg) return;
+    uint32_t cnt = 0;
+    for (uint32_t q = ptr[seg] + lane; q < ptr[seg + 1]; q += 64) cnt += val[q] > 0.f ? 1u : 0u;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
+    if (lane == 0) {
+        const double base = (double) cnt + alpha0 * N;
+        rho[seg] = (float) (lambda * pow(base, nu));
+    }
+}
+
+// The entry terms (alpha0 + w)(1 - s)^2 - alpha0 s^2, written as [(alpha0 + w)(1 - s)^2 - s^2] + (1 - alpha0) s^2 with the
+// bracket in the operations k_ials_loss_entries compiles to (one multiply, one fused multiply-subtract): at alpha0 = 1 the
+// second term adds an exact zero and the sum is that kernel's, bit for bit.
+__global__ __launch_bounds__(kLossBlock) void k_ialsr_loss_entries(uint32_t nseg, uint64_t nnz, const uint32_t* __restrict__ ptr,
+                                                                   const uint32_t* __restrict__ idx, const float* __restrict__ val,
+                                                                   const float* __restrict__ W, const float* __restrict__ H, uint32_t k,
+                                                                   float alpha, double alpha0, double* __restrict__ partials) {
+#pragma clang fp contract(off)
+    __shared__ double sh[kLossBlock];
+    double acc = 0.0;
+    for (uint64_t q = (uint64_t) blockIdx.x * kLossBlock + threadIdx.x; q < nnz; q += (uint64_t) gridDim.x * kLossBlock) {
+        const float r = val[q];
+        if (!(r > 0.f)) continue;  // an explicit zero is no entry
+        uint32_t a = 0, b = nseg;  // the row: last u with ptr[u] <= q
+        while (b - a > 1) {
+            const uint32_t m = (a + b) / 2;
+            if (ptr[m] <= q) a = m; else b = m;
+        }
+        const float* wu = W + (size_t) a * k;
+        const float* hi = H + (size_t) idx[q] * k;
+        float s = 0.f;
+        for (uint32_t t = 0; t < k; ++t) s = __builtin_fmaf(wu[t], hi[t], s);
+        const float w = alpha * r;
+        const double c = (double) w + alpha0, d = 1.0 - (double) s, ss = (double) s * (double) s;
+        double e = __builtin_fma(d, c * d, -ss);
+        e = __builtin_fma(1.0 - alpha0, ss, e);
+        acc += e;
+    }
+    const double t = block_sum(acc, sh);
+    if (threadIdx.x == 0) partials[blockIdx.x] = t;
+}
+
+// sum_s rho[s] |y_s|^2 in fp64: thread t takes the segments t, t + (grid threads), ...; one partial per workgroup
+__global__ __launch_bounds__(kLossBlock) void k_ialsr_loss_reg(const float* __restrict__ Y, uint32_t nseg, uint32_t k, const float* __restrict__ rho,
+                                                               double* __restrict__ partials) {
+    __shared__ double sh[kLossBlock];
+    double acc = 0.0;
+    for (uint64_t s = (uint64_t) blockIdx.x * kLossBlock + threadIdx.x; s < nseg; s += (uint64_t) gridDim.x * kLossBlock) {
+        const float* y = Y + (size_t) s * k;
+        double n2 = 0.0;
+        for (uint32_t t = 0; t < k; ++t) n2 = __builtin_fma((double) y[t], (double) y[t], n2);
+        acc = __builtin_fma((double) rho[s], n2, acc);
+    }
+    const double t = block_sum(acc, sh);
+    if (threadIdx.x == 0) partials[blockIdx.x] = t;
+}
+
+// alpha0 <W^T W, H^T H>_F + lambda (tr W^T W + tr H^T H) + the partials.  nu = 0 (rho = lambda for every segment): lambda is
+// passed and the partials are the entry terms alone, the operations of k_ials_loss_final; nu > 0: lambda = 0 and the partials
+// hold the entry terms and the two sums of k_ialsr_loss_reg.
+__global__ __launch_bounds__(kLossBlock) void k_ialsr_loss_final(const double* __restrict__ gw, const double* __restrict__ gh, uint32_t nparts,
+                                                                 uint32_t nb, uint32_t k, double lambda, double alpha0,
+                                                                 const double* __restrict__ partials, uint32_t npartials, double* __restrict__ out) {
+#pragma clang fp contract(off)
+    __shared__ double sh[kLossBlock];
+    double acc = 0.0;
+    for (uint32_t pi = threadIdx.x; pi < nb * nb; pi += kLossBlock) {
+        const uint32_t bi = pi / nb, bj = pi % nb;
+        for (int e = 0; e < 16; ++e) {
+            const uint32_t i = 4 * bi + e / 4, j = 4 * bj + e % 4;
+            if (i >= k || j >= k) continue;
+            double sw = 0.0, sv = 0.0;
+            for (uint32_t p = 0; p < nparts; ++p) {
+                sw += gw[((size_t) p * nb * nb + pi) * 16 + e];
+                sv += gh[((size_t) p * nb * nb + pi) * 16 + e];
+            }
+            acc = __builtin_fma(alpha0 * sw, sv, acc);
+            if (i == j) acc = __builtin_fma(lambda, sw + sv, acc);
+        }
+    }
+    const double t = block_sum(acc, sh);
+    if (threadIdx.x == 0) {
+        double s = t;
+        for (uint32_t b = 0; b < npartials; ++b) s += partials[b];
+        *out = s;
+    }
+}
+
 }  // namespace
 
 uint32_t ials_base_parts(uint32_t rows) {
@@ -268,6 +372,65 @@ int ials_loss_launch(const AlsHalf& rows, const float* W, uint32_t m, const floa
                        rows.val.get(), W, H, k, alpha, ep);
     MFX_HIP(hipGetLastError());
     hipLaunchKernelGGL(k_ials_loss_final, dim3(1), dim3(kLossBlock), 0, st, gw, gh, kGramF64Parts, nb, k, (double) lambda, ep, kLossBlocks, out);
+    MFX_HIP(hipGetLastError());
+    return MFX_OK;
+}
+
+int ialsr_scale_launch(float* G, size_t n, float alpha0, hipStream_t st) {
+    hipLaunchKernelGGL(k_ialsr_scale, dim3((uint32_t) ((n + 255) / 256)), dim3(256), 0, st, G, (uint32_t) n, alpha0);
+    MFX_HIP(hipGetLastError());
+    return MFX_OK;
+}
+
+int ialsr_base_gramian(const float* X, uint32_t rows, uint32_t k, float alpha0, float* part, float* G0, hipStream_t st) {
+    MFX_TRY(ials_base_gramian(X, rows, k, 0.f, part, G0, st));  // (S + 0 = S, bit for bit)
+    return ialsr_scale_launch(G0, (size_t) k * k, alpha0, st);
+}
+
+int ialsr_check_params(const char* fn, float lambda, float alpha0, float nu, int64_t rows, int64_t cols) {
+    MFX_REQUIRE(std::isfinite(alpha0) && alpha0 > 0.f, "%s: alpha0 = %g (finite and > 0 required)", fn, (double) alpha0);
+    MFX_REQUIRE(nu >= 0.f && nu <= 1.f, "%s: nu = %g (0 <= nu <= 1 required)", fn, (double) nu);
+    const double most = (1.0 + (double) alpha0) * (double) std::max(rows, cols);
+    const float top = (float) ((double) lambda * std::pow(most, (double) nu));
+    MFX_REQUIRE(std::isfinite(top), "%s: the regulariser lambda ((1 + alpha0) max(rows, cols))^nu = %g is not a finite fp32 number "
+                "(lambda = %g, alpha0 = %g, nu = %g)", fn, (double) top, (double) lambda, (double) alpha0, (double) nu);
+    return MFX_OK;
+}
+
+int ialsr_rho_launch(const AlsHalf& h, uint32_t N, float lambda, float alpha0, float nu, float* rho, hipStream_t st) {
+    if (h.nseg == 0) return MFX_OK;
+    hipLaunchKernelGGL(k_ialsr_rho, dim3((h.nseg + 3) / 4), dim3(256), 0, st, h.ptr.get(), h.val.get(), h.nseg, (double) lambda,
+                       (double) alpha0, (double) N, (double) nu, rho);
+    MFX_HIP(hipGetLastError());
+    return MFX_OK;
+}
+
+size_t ialsr_loss_ws_doubles(uint32_t k) { return ials_loss_ws_doubles(k) + 2 * (size_t) kLossBlocks; }
+
+int ialsr_loss_launch(const AlsHalf& rows, const float* W, uint32_t m, const float* H, uint32_t n, uint32_t k, float lambda, float alpha,
+                      float alpha0, float nu, const float* rho_rows, const float* rho_cols, double* ws, double* out, hipStream_t st) {
+    const uint32_t nb = (k + 3) / 4;
+    const size_t gsz = (size_t) kGramF64Parts * nb * nb * 16;
+    double* gw = ws;
+    double* gh = ws + gsz;
+    double* ep = ws + 2 * gsz;  // [kLossBlocks] entry terms, then (nu > 0) [kLossBlocks] each for the regularisers of W and H
+    const dim3 gg((nb * nb + 255) / 256, kGramF64Parts);
+    hipLaunchKernelGGL(k_gram_f64, gg, dim3(256), 0, st, W, m, k, nb, (m + kGramF64Parts - 1) / kGramF64Parts, gw);
+    MFX_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_gram_f64, gg, dim3(256), 0, st, H, n, k, nb, (n + kGramF64Parts - 1) / kGramF64Parts, gh);
+    MFX_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_ialsr_loss_entries, dim3(kLossBlocks), dim3(kLossBlock), 0, st, rows.nseg, rows.nnz, rows.ptr.get(), rows.idx.get(),
+                       rows.val.get(), W, H, k, alpha, (double) alpha0, ep);
+    MFX_HIP(hipGetLastError());
+    const bool uniform = nu == 0.f;  // rho = lambda everywhere: the regulariser from the traces of the Gramians already formed
+    if (!uniform) {
+        hipLaunchKernelGGL(k_ialsr_loss_reg, dim3(kLossBlocks), dim3(kLossBlock), 0, st, W, m, k, rho_rows, ep + kLossBlocks);
+        MFX_HIP(hipGetLastError());
+        hipLaunchKernelGGL(k_ialsr_loss_reg, dim3(kLossBlocks), dim3(kLossBlock), 0, st, H, n, k, rho_cols, ep + 2 * kLossBlocks);
+        MFX_HIP(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_ialsr_loss_final, dim3(1), dim3(kLossBlock), 0, st, gw, gh, kGramF64Parts, nb, k, uniform ? (double) lambda : 0.0,
+                       (double) alpha0, ep, uniform ? kLossBlocks : 3 * kLossBlocks, out);
     MFX_HIP(hipGetLastError());
     return MFX_OK;
 }

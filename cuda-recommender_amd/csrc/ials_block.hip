@@ -329,6 +329,16 @@ __global__ __launch_bounds__(256) void k_alsb_p(const float* __restrict__ Y, con
     P[e] = rho * Y[(size_t) seg * k + b0 + c];
 }
 
+// Implicit objective with a regulariser per segment (k_ialsrb_*): P[seg][c] = fmaf(rho[seg], y[b0 + c], P[seg][c]) on top of
+// P = Y G0[:, pi] as k_ialsb_gy left it; one thread per (segment, column of the block)
+__global__ __launch_bounds__(256) void k_ialsrb_p(const float* __restrict__ Y, const float* __restrict__ rho, uint32_t nseg, uint32_t k, uint32_t b0,
+                                                  uint32_t width, float* __restrict__ P) {
+    const size_t e = (size_t) blockIdx.x * 256 + threadIdx.x;
+    if (e >= (size_t) nseg * width) return;
+    const uint32_t seg = (uint32_t) (e / width), c = (uint32_t) (e % width);
+    P[e] = __builtin_fmaf(rho[seg], Y[(size_t) seg * k + b0 + c], P[e]);
+}
+
 // the first position whose value is not finite into *first_bad (grid-stride, one atomic per thread that found one)
 __global__ __launch_bounds__(256) void k_alsb_check(uint64_t n, const float* __restrict__ val, unsigned long long* __restrict__ first_bad) {
     unsigned long long bad = ~0ull;
@@ -434,7 +444,7 @@ int ialsb_pack_launch(IalsBlock& b, const float* X, uint32_t x_rows, hipStream_t
 }
 
 int ialsb_sweep_launch(IalsBlock& b, const AlsHalf& h, const float* X, uint32_t x_rows, float* Y, float alpha, uint32_t* spd_fail,
-                       hipStream_t st) {
+                       hipStream_t st, float alpha0, const float* rho) {
     const uint32_t k = b.k, d = b.d;
     MFX_REQUIRE(xb_offset(x_rows, d, (k + d - 1) / d) <= b.Xb.size() && (size_t) h.nseg * d <= std::max<size_t>(1, b.P.size()) &&
                     (size_t) h.nseg * d <= std::max<size_t>(1, b.Z.size()) && h.nnz + kAlsEntryPad <= b.score.size() &&
@@ -454,8 +464,15 @@ int ialsb_sweep_launch(IalsBlock& b, const AlsHalf& h, const float* X, uint32_t 
         }
         MFX_HIP(hipGetLastError());
         const float* Xblk = b.Xb.get() + xb_offset(x_rows, d, blk);
-        MFX_TRY(ialsb_step_launch(h, Xblk, x_rows, b.Z.get(), width, b.Gbb.get() + (size_t) blk * d * d, alpha, b.score.get(), b.P.get(),
-                                  b.ws.get(), spd_fail, st));
+        if (rho) {  // b.G is G0 = fp32(alpha0 X^T X): the regulariser's share of P, then the k_ialsrb_* systems
+            hipLaunchKernelGGL(k_ialsrb_p, dim3((uint32_t) (((size_t) h.nseg * width + 255) / 256)), dim3(256), 0, st, Y, rho, h.nseg, k, b0, width,
+                               b.P.get());
+            MFX_HIP(hipGetLastError());
+            MFX_TRY(ialsrb_step_launch(h, Xblk, x_rows, b.Z.get(), width, b.Gbb.get() + (size_t) blk * d * d, alpha, alpha0, rho, b.score.get(),
+                                       b.P.get(), b.ws.get(), spd_fail, st));
+        } else
+            MFX_TRY(ialsb_step_launch(h, Xblk, x_rows, b.Z.get(), width, b.Gbb.get() + (size_t) blk * d * d, alpha, b.score.get(), b.P.get(),
+                                      b.ws.get(), spd_fail, st));
         hipLaunchKernelGGL(k_ialsb_update, dim3(h.nitems), dim3(64), 0, st, h.items.get(), h.nitems, h.ptr.get(), h.idx.get(), Xblk, x_rows,
                            b.Z.get(), width, Y, k, b0, b.score.get());
         MFX_HIP(hipGetLastError());
@@ -464,15 +481,21 @@ int ialsb_sweep_launch(IalsBlock& b, const AlsHalf& h, const float* X, uint32_t 
 }
 
 int ialsb_half_launch(IalsBlock& b, const AlsHalf& h, const float* X, uint32_t x_rows, float* Y, float alpha, uint32_t* spd_fail,
-                      hipStream_t st) {
+                      hipStream_t st, float alpha0, const float* rho) {
     if (h.nseg == 0) return MFX_OK;
     MFX_TRY(ialsb_pack_launch(b, X, x_rows, st));
-    return ialsb_sweep_launch(b, h, X, x_rows, Y, alpha, spd_fail, st);
+    return ialsb_sweep_launch(b, h, X, x_rows, Y, alpha, spd_fail, st, alpha0, rho);
+}
+
+int ialsrb_gramian(IalsBlock& b, const float* X, uint32_t rows, float alpha0, hipStream_t st) {
+    MFX_TRY(ialsb_gramian(b, X, rows, 0.f, st));  // (S + 0 = S, bit for bit)
+    return ialsr_scale_launch(b.G.get(), (size_t) b.k * b.k, alpha0, st);
 }
 
 int ialsb_fold_launch(IalsBlock& b, const AlsHalf& h, const float* X, uint32_t x_rows, float* Y, float alpha, int32_t sweeps, float tol,
-                      int32_t* counts, uint32_t* spd_fail, hipStream_t st) {
-    return fold_loop(h, b.k, Y, sweeps, tol, counts, st, [&]() { return ialsb_sweep_launch(b, h, X, x_rows, Y, alpha, spd_fail, st); });
+                      int32_t* counts, uint32_t* spd_fail, hipStream_t st, float alpha0, const float* rho) {
+    return fold_loop(h, b.k, Y, sweeps, tol, counts, st,
+                     [&]() { return ialsb_sweep_launch(b, h, X, x_rows, Y, alpha, spd_fail, st, alpha0, rho); });
 }
 
 int ials_block_half_op(int64_t nseg, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val, int64_t nrows_x,
@@ -494,6 +517,33 @@ int ials_block_half_op(int64_t nseg, int64_t nnz, const uint32_t* ptr, const uin
     MFX_TRY(fail_cnt.alloc_zero(1, os.st));
     MFX_TRY(ialsb_gramian(b, dX.get(), (uint32_t) nrows_x, lambda, os.st));
     MFX_TRY(ialsb_half_launch(b, h, dX.get(), (uint32_t) nrows_x, dY.get(), alpha, fail_cnt.get(), os.st));
+    MFX_HIP(hipMemcpyAsync(Y_out, dY.get(), sizeof(float) * (size_t) nseg * k, hipMemcpyDeviceToHost, os.st));
+    MFX_HIP(hipStreamSynchronize(os.st));
+    return MFX_OK;
+}
+
+int ials_block_half_reg_op(int64_t nseg, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val, int64_t nrows_x,
+                           const float* X, const float* Y_in, float* Y_out, int64_t k, int32_t block, float lambda, float alpha, float alpha0,
+                           float nu, int device) {
+    MFX_TRY(use_device(device));
+    OpStream os;
+    MFX_HIP(hipStreamCreateWithFlags(&os.st, hipStreamNonBlocking));
+    AlsHalf h;
+    MFX_TRY(h.build((uint32_t) nseg, (uint64_t) nnz, (uint32_t) nrows_x, ptr, idx, val, MFX_HOST, kAlsChunk, os.st));
+    MFX_TRY(ials_check_values(h.val.get(), h.nnz, alpha, "mfx_ials_block_half_reg: value", os.st));
+    const uint32_t d = std::min<uint32_t>(block ? (uint32_t) block : ialsb_default_block((uint32_t) k), (uint32_t) k);
+    IalsBlock b;
+    MFX_TRY(b.alloc((uint32_t) k, d, (uint32_t) nrows_x, (uint32_t) nseg, (uint64_t) nnz, h.nslots, os.st));
+    DevBuf<float> dX, dY, rho;
+    DevBuf<uint32_t> fail_cnt;
+    MFX_TRY(dX.alloc((size_t) nrows_x * k)); MFX_TRY(dX.upload(X, (size_t) nrows_x * k, MFX_HOST, os.st));
+    MFX_TRY(dY.alloc_zero((size_t) nseg * k, os.st));
+    if (Y_in) MFX_TRY(dY.upload(Y_in, (size_t) nseg * k, MFX_HOST, os.st));
+    MFX_TRY(fail_cnt.alloc_zero(1, os.st));
+    MFX_TRY(rho.alloc((size_t) nseg));
+    MFX_TRY(ialsr_rho_launch(h, (uint32_t) nrows_x, lambda, alpha0, nu, rho.get(), os.st));
+    MFX_TRY(ialsrb_gramian(b, dX.get(), (uint32_t) nrows_x, alpha0, os.st));
+    MFX_TRY(ialsb_half_launch(b, h, dX.get(), (uint32_t) nrows_x, dY.get(), alpha, fail_cnt.get(), os.st, alpha0, rho.get()));
     MFX_HIP(hipMemcpyAsync(Y_out, dY.get(), sizeof(float) * (size_t) nseg * k, hipMemcpyDeviceToHost, os.st));
     MFX_HIP(hipStreamSynchronize(os.st));
     return MFX_OK;

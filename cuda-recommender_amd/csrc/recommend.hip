@@ -685,6 +685,7 @@ int Recommender::topn(const float* wp, uint32_t nu, const uint32_t* du, const ui
 int Recommender::fold_setup_begin(bool drop_g, bool drop_b) {
     MFX_TRY(use_device(device_));
     fold_model_ = -1;  // (until the setup is through)
+    fold_robj_ = false;
     if (drop_g) fold_g_.release();     // (what a direct setup kept)
     if (drop_b) fold_b_ = IalsBlock();  // (what a block setup kept)
     const size_t nh = ((size_t) cols_ + 1) * k_;
@@ -734,6 +735,53 @@ int Recommender::fold_in_block_setup(float lambda, float alpha, int32_t block, i
     fold_model_ = kFoldBlock;
     fold_lambda_ = lambda;
     fold_alpha_ = alpha;
+    fold_sweeps_ = sweeps;
+    fold_tol_ = tol;
+    return MFX_OK;
+}
+
+int Recommender::fold_in_setup_reg(float lambda, float alpha, float alpha0, float nu) {
+    MFX_REQUIRE(k_ <= 128, "mfx_rec_fold_in_setup_reg: fold-in solves ranks k <= 128 (the handle has k = %lld)", (long long) k_);
+    MFX_TRY(check_fold_lambda("mfx_rec_fold_in_setup_reg", lambda));
+    MFX_REQUIRE(std::isfinite(alpha) && alpha >= 0.f, "mfx_rec_fold_in_setup_reg: alpha = %g (finite and >= 0 required)", (double) alpha);
+    MFX_TRY(ialsr_check_params("mfx_rec_fold_in_setup_reg", lambda, alpha0, nu, cols_, cols_));
+    MFX_TRY(fold_setup_begin(false, true));
+    hipStream_t st = st_;
+    DevBuf<float> part;  // G0 = fp32(alpha0 H^T H), as the trainer's ialsr_base_gramian builds it
+    MFX_TRY(part.alloc(ials_base_ws_floats((uint32_t) cols_, (uint32_t) k_)));
+    MFX_TRY(fold_g_.alloc((size_t) k_ * k_));
+    MFX_TRY(ialsr_base_gramian(hx_.get(), (uint32_t) cols_, (uint32_t) k_, alpha0, part.get(), fold_g_.get(), st));
+    MFX_HIP(hipStreamSynchronize(st));
+    fold_model_ = MFX_FOLD_IMPLICIT;
+    fold_lambda_ = lambda;
+    fold_alpha_ = alpha;
+    fold_robj_ = true;
+    fold_alpha0_ = alpha0;
+    fold_nu_ = nu;
+    return MFX_OK;
+}
+
+int Recommender::fold_in_block_setup_reg(float lambda, float alpha, float alpha0, float nu, int32_t block, int32_t sweeps, float tol) {
+    MFX_REQUIRE(k_ <= (int64_t) kIalsBlockMaxRank, "mfx_rec_fold_in_block_setup_reg: block sweeps solve ranks k <= %u (the handle has k = %lld)",
+                kIalsBlockMaxRank, (long long) k_);
+    MFX_TRY(check_fold_lambda("mfx_rec_fold_in_block_setup_reg", lambda));
+    MFX_REQUIRE(std::isfinite(alpha) && alpha >= 0.f, "mfx_rec_fold_in_block_setup_reg: alpha = %g (finite and >= 0 required)", (double) alpha);
+    MFX_TRY(ialsr_check_params("mfx_rec_fold_in_block_setup_reg", lambda, alpha0, nu, cols_, cols_));
+    MFX_TRY(check_fold_sweeps("mfx_rec_fold_in_block_setup_reg", block, sweeps, tol));
+    MFX_TRY(fold_setup_begin(true, false));
+    hipStream_t st = st_;
+    const uint32_t k = (uint32_t) k_, d = std::min<uint32_t>(block ? (uint32_t) block : ialsb_default_block(k), k);
+    MFX_TRY(fold_b_.alloc(k, d, (uint32_t) cols_, 0, 0, 0, st));
+    MFX_TRY(ialsrb_gramian(fold_b_, hx_.get(), (uint32_t) cols_, alpha0, st));
+    MFX_TRY(ialsb_pack_launch(fold_b_, hx_.get(), (uint32_t) cols_, st));
+    MFX_HIP(hipStreamSynchronize(st));
+    fold_b_.gpart.release();
+    fold_model_ = kFoldBlock;
+    fold_lambda_ = lambda;
+    fold_alpha_ = alpha;
+    fold_robj_ = true;
+    fold_alpha0_ = alpha0;
+    fold_nu_ = nu;
     fold_sweeps_ = sweeps;
     fold_tol_ = tol;
     return MFX_OK;
@@ -800,13 +848,17 @@ int Recommender::fold_solve(int64_t nusers, int64_t nnz, const uint32_t* ptr, co
         MFX_TRY(als_check_finite(h.val.get(), h.nnz, "mfx_rec_fold_in: value", st));
     const auto t1 = clk::now();
 
-    DevBuf<float> Y, ws, wq;
+    DevBuf<float> Y, ws, wq, rho;
     DevBuf<uint32_t> spd_fail;
     DevBuf<int32_t> counts;
     MFX_TRY(Y.alloc_zero((size_t) nu * k, st));
     MFX_TRY(spd_fail.alloc_zero(1, st));
     if (fold_model_ != MFX_FOLD_ALS_EXACT && !by_blocks) MFX_TRY(ws.alloc(std::max<size_t>(1, als_ws_floats(h.nslots, k))));
     const uint32_t x_rows = (uint32_t) cols_;
+    if (fold_robj_) {  // the regulariser of every query row from its own entries, over the cols_ items
+        MFX_TRY(rho.alloc(nu));
+        MFX_TRY(ialsr_rho_launch(h, x_rows, fold_lambda_, fold_alpha0_, fold_nu_, rho.get(), st));
+    }
     struct QueryWs {  // the per-query part of fold_b_ goes when the call returns
         IalsBlock& b;
         ~QueryWs() { b.P.release(); b.Z.release(); b.score.release(); b.ws.release(); }
@@ -819,7 +871,7 @@ int Recommender::fold_solve(int64_t nusers, int64_t nnz, const uint32_t* ptr, co
             MFX_TRY(fold_b_.alloc_half(nu, h.nnz, h.nslots, st));
             if (fold_model_ == kFoldBlock)
                 MFX_TRY(ialsb_fold_launch(fold_b_, h, hx_.get(), x_rows, Y.get(), fold_alpha_, fold_sweeps_, fold_tol_, counts.get(),
-                                          spd_fail.get(), st));
+                                          spd_fail.get(), st, fold_alpha0_, fold_robj_ ? rho.get() : nullptr));
             else
                 MFX_TRY(alsb_fold_launch(fold_b_, h, hx_.get(), x_rows, Y.get(), fold_lambda_, fold_reg_, fold_sweeps_, fold_tol_,
                                          counts.get(), spd_fail.get(), st));
@@ -834,7 +886,11 @@ int Recommender::fold_solve(int64_t nusers, int64_t nnz, const uint32_t* ptr, co
             MFX_TRY(als_half_nreg_launch(h, hx_.get(), x_rows, Y.get(), k, fold_lambda_, ws.get(), spd_fail.get(), st));
             break;
         default:
-            MFX_TRY(ials_half_launch(h, hx_.get(), x_rows, Y.get(), k, fold_g_.get(), fold_alpha_, ws.get(), spd_fail.get(), st));
+            if (fold_robj_)
+                MFX_TRY(ialsr_half_launch(h, hx_.get(), x_rows, Y.get(), k, fold_g_.get(), fold_alpha_, fold_alpha0_, rho.get(), ws.get(),
+                                          spd_fail.get(), st));
+            else
+                MFX_TRY(ials_half_launch(h, hx_.get(), x_rows, Y.get(), k, fold_g_.get(), fold_alpha_, ws.get(), spd_fail.get(), st));
             break;
     }
     MFX_HIP(hipStreamSynchronize(st));

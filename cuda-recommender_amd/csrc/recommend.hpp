@@ -24,6 +24,10 @@ public:
     int fold_in_block_setup(float lambda, float alpha, int32_t block, int32_t sweeps, float tol);
     // block sweeps on the explicit objective (mfx_rec_fold_in_block_setup_als): reg 0 = lambda, 1 = lambda * entries of the row
     int fold_in_block_setup_als(float lambda, int32_t reg, int32_t block, int32_t sweeps, float tol);
+    // the implicit objective with an unobserved weight alpha0 and rho_u = fp32(lambda (n_u + alpha0 cols)^nu) per query row
+    // (mfx_rec_fold_in_setup_reg: k <= 128; mfx_rec_fold_in_block_setup_reg: block sweeps)
+    int fold_in_setup_reg(float lambda, float alpha, float alpha0, float nu);
+    int fold_in_block_setup_reg(float lambda, float alpha, float alpha0, float nu, int32_t block, int32_t sweeps, float tol);
     int fold_in(int64_t nusers, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val, float* W_out,
                 int32_t n_top, uint32_t* items, float* scores, mfx_memspace space);
     // mfx_rec_fold_in_warm: after a block setup only; W_init [nusers][k] / sweeps_done [nusers] in `space`, or NULL
@@ -90,6 +94,8 @@ private:
     // fold-in: model (-1 = not set up, kFoldBlock = block sweeps), H row-major [cols_ + 1][k_] with a zero last row, base Gramian [k_][k_] (implicit)
     int fold_model_ = -1;
     float fold_lambda_ = 0.f, fold_alpha_ = 0.f;
+    bool fold_robj_ = false;  // a _reg setup: fold_g_ / fold_b_.G hold fp32(alpha0 H^T H), rho is formed per query batch
+    float fold_alpha0_ = 1.f, fold_nu_ = 0.f;
     DevBuf<float> hx_, fold_g_;
     // fold-in by block sweeps: G = H^T H + lambda I, H block-major and the diagonal blocks of G, all packed at setup; P, Z,
     // the scores and the split-segment slots live for one query

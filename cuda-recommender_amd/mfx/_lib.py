@@ -106,6 +106,14 @@ SIGNATURES = {
                                         C.c_int]),
     "mfx_ials_block_half": (C.c_int, [C.c_int64, C.c_int64, u32p, u32p, f32p, C.c_int64, f32p, f32p, f32p, C.c_int64, C.c_int32,
                                       C.c_float, C.c_float, C.c_int]),
+    "mfx_ials_create_reg": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(mfx_csx), C.POINTER(mfx_params), C.c_float, C.c_float, C.c_float,
+                                      C.c_int]),
+    "mfx_ials_block_create_reg": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(mfx_csx), C.POINTER(mfx_params), C.c_float, C.c_float,
+                                            C.c_float, C.c_int32, C.c_int]),
+    "mfx_ials_half_reg": (C.c_int, [C.c_int64, C.c_int64, u32p, u32p, f32p, C.c_int64, f32p, f32p, C.c_int64,
+                                    C.c_float, C.c_float, C.c_float, C.c_float, C.c_int]),
+    "mfx_ials_block_half_reg": (C.c_int, [C.c_int64, C.c_int64, u32p, u32p, f32p, C.c_int64, f32p, f32p, f32p, C.c_int64, C.c_int32,
+                                          C.c_float, C.c_float, C.c_float, C.c_float, C.c_int]),
     "mfx_als_block_create": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(mfx_csx), C.POINTER(mfx_coo), C.POINTER(mfx_params), C.c_int32,
                                        C.c_int32, C.c_int]),
     "mfx_als_block_half": (C.c_int, [C.c_int64, C.c_int64, u32p, u32p, f32p, C.c_int64, f32p, f32p, f32p, C.c_int64, C.c_int32,
@@ -128,6 +136,9 @@ SIGNATURES = {
     "mfx_rec_fold_in": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                   C.c_void_p, C.c_void_p, C.c_int]),
     "mfx_rec_fold_in_block_setup": (C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_int32, C.c_int32, C.c_float]),
+    "mfx_rec_fold_in_setup_reg": (C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float]),
+    "mfx_rec_fold_in_block_setup_reg": (C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int32, C.c_int32,
+                                                  C.c_float]),
     "mfx_rec_fold_in_block_setup_als": (C.c_int, [C.c_void_p, C.c_float, C.c_int32, C.c_int32, C.c_int32, C.c_float]),
     "mfx_rec_fold_in_warm": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int]),

@@ -526,16 +526,26 @@ class AlsSolver:
             pass
 
 
+def _reg_pair(alpha0, nu):
+    """(alpha0, nu) of the _reg entry points, or None when neither is given (the un-suffixed entry point is called)."""
+    if alpha0 is None and nu is None:
+        return None
+    return (1.0 if alpha0 is None else float(alpha0), 0.0 if nu is None else float(nu))
+
+
 class ImplicitAlsSolver:
     """Resident implicit-feedback ALS (mfx_ials_create): R holds interaction strengths r >= 0, every (user, item)
     pair is in the loss with preference p = (r > 0) and confidence 1 + alpha r.  Factors use the ALS layout,
     W [rows][k] and H [cols][k].  device_arrays: the matrix as a dict of device tensors (mfx.synth_torch).
     block=None: the exact solver (k <= 128).  block=d (0 = chosen from k): block subspace sweeps over d coordinates at
     a time (mfx_ials_block_create, k <= 1024) -- a different method; there W, when given to set_factors, is the warm
-    start of the first half-sweep."""
+    start of the first half-sweep.
+    alpha0 / nu (either one given: mfx_ials_create_reg / mfx_ials_block_create_reg): the weight alpha0 > 0 of the unobserved
+    pairs and the exponent 0 <= nu <= 1 of the frequency-scaled regulariser lambda (n + alpha0 N)^nu of a row or column
+    with n entries over N; a lone alpha0 means nu = 0, a lone nu means alpha0 = 1."""
 
     def __init__(self, R: Optional[RatingData], parameters: parameter, alpha: float, device_arrays: Optional[dict] = None,
-                 block: Optional[int] = None):
+                 block: Optional[int] = None, alpha0: Optional[float] = None, nu: Optional[float] = None):
         self.handle = C.c_void_p()
         cp = parameters.to_c()
         if device_arrays is not None:
@@ -548,7 +558,13 @@ class ImplicitAlsSolver:
         else:
             self.rows, self.cols, self.k = R.rows, R.cols, int(parameters.k)
             csx, space = _csx(R), L.MFX_HOST
-        if block is None:
+        reg = _reg_pair(alpha0, nu)
+        if reg is not None and block is None:
+            L.check(L.lib().mfx_ials_create_reg(C.byref(self.handle), C.byref(csx), C.byref(cp), float(alpha), reg[0], reg[1], space))
+        elif reg is not None:
+            L.check(L.lib().mfx_ials_block_create_reg(C.byref(self.handle), C.byref(csx), C.byref(cp), float(alpha), reg[0], reg[1],
+                                                      int(block), space))
+        elif block is None:
             L.check(L.lib().mfx_ials_create(C.byref(self.handle), C.byref(csx), C.byref(cp), float(alpha), space))
         else:
             L.check(L.lib().mfx_ials_block_create(C.byref(self.handle), C.byref(csx), C.byref(cp), float(alpha), int(block), space))
@@ -645,21 +661,36 @@ def als_half(ptr, idx, val, X, k: int, lam: float, device: int = 0, variant: int
     return Y
 
 
-def ials_half(ptr, idx, val, X, k: int, lam: float, alpha: float, device: int = 0) -> np.ndarray:
-    """One implicit-feedback half-sweep (mfx_ials_half): Y [nseg][k] over all rows of X [nrows][k]."""
+def ials_half(ptr, idx, val, X, k: int, lam: float, alpha: float, device: int = 0, alpha0: Optional[float] = None,
+              nu: Optional[float] = None) -> np.ndarray:
+    """One implicit-feedback half-sweep (mfx_ials_half): Y [nseg][k] over all rows of X [nrows][k].  alpha0 / nu given:
+    mfx_ials_half_reg (see ImplicitAlsSolver)."""
     nseg = ptr.shape[0] - 1
     Y = np.empty((nseg, k), np.float32)
+    reg = _reg_pair(alpha0, nu)
+    if reg is not None:
+        L.check(L.lib().mfx_ials_half_reg(nseg, idx.shape[0], _u32(ptr), _u32(idx), _f32(val), X.shape[0], _f32(X), _f32(Y),
+                                          k, lam, alpha, reg[0], reg[1], device))
+        return Y
     L.check(L.lib().mfx_ials_half(nseg, idx.shape[0], _u32(ptr), _u32(idx), _f32(val), X.shape[0], _f32(X), _f32(Y),
                                   k, lam, alpha, device))
     return Y
 
 
-def ials_block_half(ptr, idx, val, X, k: int, lam: float, alpha: float, block: int, Y_in=None, device: int = 0) -> np.ndarray:
-    """One half-sweep of implicit ALS by block subspace sweeps (mfx_ials_block_half) from Y_in [nseg][k] (None = zeros)."""
+def ials_block_half(ptr, idx, val, X, k: int, lam: float, alpha: float, block: int, Y_in=None, device: int = 0,
+                    alpha0: Optional[float] = None, nu: Optional[float] = None) -> np.ndarray:
+    """One half-sweep of implicit ALS by block subspace sweeps (mfx_ials_block_half) from Y_in [nseg][k] (None = zeros).
+    alpha0 / nu given: mfx_ials_block_half_reg (see ImplicitAlsSolver)."""
     nseg = ptr.shape[0] - 1
     Y = np.empty((nseg, k), np.float32)
     if Y_in is not None:
         _f32c(Y_in, (nseg, k))
+    reg = _reg_pair(alpha0, nu)
+    if reg is not None:
+        L.check(L.lib().mfx_ials_block_half_reg(nseg, idx.shape[0], _u32(ptr), _u32(idx), _f32(val), X.shape[0], _f32(X),
+                                                _f32(Y_in) if Y_in is not None else None, _f32(Y), k, int(block), lam, alpha,
+                                                reg[0], reg[1], device))
+        return Y
     L.check(L.lib().mfx_ials_block_half(nseg, idx.shape[0], _u32(ptr), _u32(idx), _f32(val), X.shape[0], _f32(X),
                                         _f32(Y_in) if Y_in is not None else None, _f32(Y), k, int(block), lam, alpha, device))
     return Y
@@ -808,17 +839,34 @@ class Recommender:
         L.check(L.lib().mfx_rec_query(self.handle, n, pu, n_top, _vp(items), _vp(scores), L.MFX_HOST, item_slices))
         return items, scores
 
-    def fold_in_setup(self, model: int, lam: float, alpha: float = 0.0):
+    def fold_in_setup(self, model: int, lam: float, alpha: float = 0.0, alpha0: Optional[float] = None, nu: Optional[float] = None):
         """Prepares fold-in (mfx_rec_fold_in_setup): model MFX_FOLD_ALS / MFX_FOLD_ALS_EXACT / MFX_FOLD_CCD /
-        MFX_FOLD_IMPLICIT, regularisation lam, confidence scale alpha (implicit model).  k <= 128."""
+        MFX_FOLD_IMPLICIT, regularisation lam, confidence scale alpha (implicit model).  k <= 128.  alpha0 / nu given
+        (MFX_FOLD_IMPLICIT only): mfx_rec_fold_in_setup_reg, the objective of ImplicitAlsSolver(alpha0=, nu=)."""
+        reg = _reg_pair(alpha0, nu)
+        if reg is not None:
+            if int(model) != L.MFX_FOLD_IMPLICIT:
+                raise ValueError("alpha0 / nu apply to MFX_FOLD_IMPLICIT only")
+            L.check(L.lib().mfx_rec_fold_in_setup_reg(self.handle, float(lam), float(alpha), reg[0], reg[1]))
+            return
         L.check(L.lib().mfx_rec_fold_in_setup(self.handle, int(model), float(lam), float(alpha)))
 
     def fold_in_block_setup(self, lam: float, alpha: float, block: int = 0, sweeps: int = 8, tol: float = 0.0):
         """Prepares fold-in by block subspace sweeps (mfx_rec_fold_in_block_setup), the method of ImplicitAlsSolver(block=...):
         any k <= 1024.  block 0 = chosen from k, else 1..128; a row gets at most `sweeps` sweeps (1..1024), exactly `sweeps`
         with tol = 0, else it stops once a sweep moves it by at most tol of its largest entry.  A cold start at large alpha
-        converges slowly for short rows: choose sweeps / tol for the data, or pass W_init to fold_in."""
+        converges slowly for short rows: choose sweeps / tol for the data, or pass W_init to fold_in.  The objective of
+        ImplicitAlsSolver(block=, alpha0=, nu=): fold_in_block_setup_reg."""
         L.check(L.lib().mfx_rec_fold_in_block_setup(self.handle, float(lam), float(alpha), int(block), int(sweeps), float(tol)))
+
+    def fold_in_block_setup_reg(self, lam: float, alpha: float, alpha0: float = 1.0, nu: float = 0.0, block: int = 0, sweeps: int = 8,
+                                tol: float = 0.0):
+        """fold_in_block_setup on the objective of ImplicitAlsSolver(block=, alpha0=, nu=) (mfx_rec_fold_in_block_setup_reg):
+        the weight alpha0 > 0 of the unobserved pairs and the exponent 0 <= nu <= 1 of the regulariser
+        lam (n + alpha0 cols)^nu of a query row with n entries.  block, sweeps, tol and fold_in afterwards as there (its
+        parameter list is pinned by tests/test_foldin_block_host.py: hence a method of its own)."""
+        L.check(L.lib().mfx_rec_fold_in_block_setup_reg(self.handle, float(lam), float(alpha), float(alpha0), float(nu), int(block),
+                                                        int(sweeps), float(tol)))
 
     def fold_in_block_setup_als(self, lam: float, block: int = 0, sweeps: int = 8, tol: float = 0.0, count_reg: bool = False):
         """Prepares fold-in by block subspace sweeps on the explicit objective (mfx_rec_fold_in_block_setup_als), the method

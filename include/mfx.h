@@ -267,6 +267,33 @@ int mfx_ials_block_half(int64_t nseg, int64_t nnz, const uint32_t* ptr, const ui
                         int64_t nrows_x, const float* X, const float* Y_in, float* Y_out, int64_t k, int32_t block,
                         float lambda, float alpha, int device);
 
+/* Implicit ALS with an unobserved weight and a frequency-scaled regulariser (Rendle et al. 2021, "Revisiting the Performance
+ * of iALS on Item Recommendation Benchmarks": their unobserved_weight and regularization_exp).  alpha0 > 0 weighs the
+ * all-pairs term, 0 <= nu <= 1 scales the regulariser of a segment s (a user row or an item column) over the fixed factor X
+ * with N rows by its n_s stored entries with r > 0:
+ *     f_s(y) = sum_{r_j > 0} [(alpha0 + w_j)(1 - s_j)^2 - alpha0 s_j^2] + alpha0 y^T X^T X y + rho_s |y|^2,   w_j = fp32(alpha r_j)
+ *     rho_s  = fp32((double) lambda * pow((double) n_s + (double) alpha0 * (double) N, (double) nu))
+ * A half-sweep solves (G_s + sum_j w_j x_j x_j^T) y = sum_{r_j > 0} (alpha0 + w_j) x_j with G_s = G0 + rho_s I, one fp32 add
+ * on the diagonal of G0 = fp32(alpha0 X^T X) (X^T X summed as for mfx_ials_create).  An empty segment, and one whose entries
+ * are all explicit zeros, gives y = 0.  nu = 0: rho_s = lambda; at alpha0 = 1, nu = 0 mfx_ials_create_reg and mfx_ials_half_reg
+ * equal mfx_ials_create and mfx_ials_half bit for bit.  The block step of mfx_ials_block_create_reg is
+ *     A z = sum_{r_j > 0} ((alpha0 + w_j) - w_j s_j) x_jpi - P_s,   A = G_s[pi, pi] + sum_j w_j x_jpi x_jpi^T,
+ *     P_s[c] = fmaf(rho_s, y[b0 + c], (Y G0[:, pi])[s][c])
+ * with pi, d, z and s_j as for mfx_ials_block_create.  The handles are mfx_als_t as those of the un-suffixed functions:
+ * mfx_als_set_factors / _iterate / _get_factors / _kernel_times / _destroy work on them, and mfx_ials_loss returns
+ *     L = sum_{r > 0} [(alpha0 + w)(1 - s)^2 - alpha0 s^2] + alpha0 <W^T W, H^T H>_F + sum_u rho_u |w_u|^2 + sum_i rho_i |h_i|^2
+ * (rho_u over N = cols, rho_i over N = rows).  MFX_ERR_INVALID without touching the device: alpha0 <= 0 / NaN / Inf
+ * ("alpha0"), nu outside [0, 1] or NaN ("nu"), fp32(lambda ((1 + alpha0) max(rows, cols))^nu) not finite ("regulariser";
+ * the half operators take rows = nseg, cols = nrows_x), and everything the un-suffixed function refuses. */
+int mfx_ials_create_reg(mfx_als_t* out, const mfx_csx* R, const mfx_params* p, float alpha, float alpha0, float nu, mfx_memspace space);
+int mfx_ials_block_create_reg(mfx_als_t* out, const mfx_csx* R, const mfx_params* p, float alpha, float alpha0, float nu, int32_t block,
+                              mfx_memspace space);
+int mfx_ials_half_reg(int64_t nseg, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val, int64_t nrows_x, const float* X,
+                      float* Y, int64_t k, float lambda, float alpha, float alpha0, float nu, int device);
+int mfx_ials_block_half_reg(int64_t nseg, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val, int64_t nrows_x,
+                            const float* X, const float* Y_in, float* Y_out, int64_t k, int32_t block, float lambda, float alpha,
+                            float alpha0, float nu, int device);
+
 /* Explicit ALS by block subspace sweeps: the objective of mfx_als_create at ranks k up to 1024 (the range mfx_rec_query
  * scores), by the sweeps of mfx_ials_block_create.  For one segment (a user row or an item column), X the fixed other
  * factor and r_j the segment's stored values, the objective is
@@ -377,6 +404,15 @@ int mfx_rec_fold_in_block_setup(mfx_rec_t r, float lambda, float alpha, int32_t 
  * mfx_rec_fold_in_warm with W_init = NULL and sweeps_done = NULL.  MFX_ERR_INVALID: reg not 0 / 1, block outside 0..128,
  * sweeps outside 1..1024, tol < 0 or not finite, lambda <= 0 or not finite. */
 int mfx_rec_fold_in_block_setup_als(mfx_rec_t r, float lambda, int32_t reg, int32_t block, int32_t sweeps, float tol);
+/* Fold-in on the objective of mfx_ials_create_reg / mfx_ials_block_create_reg: a query row u has N = cols and n_u = its
+ * entries with r > 0; rho_u is formed on the device for every query batch.  mfx_rec_fold_in_setup_reg (k <= 128) keeps
+ * G0 = fp32(alpha0 H^T H) and makes mfx_rec_fold_in equal mfx_ials_half_reg of the same rows over the handle's H bit for bit;
+ * mfx_rec_fold_in_block_setup_reg keeps what mfx_rec_fold_in_block_setup keeps, over G0, and one sweep equals one
+ * mfx_ials_block_half_reg bit for bit.  Afterwards mfx_rec_fold_in and mfx_rec_fold_in_warm, the stop rule and "the last
+ * successful setup decides" are those of the un-suffixed setups.  MFX_ERR_INVALID: what those refuse, and alpha0 / nu /
+ * the regulariser as for mfx_ials_create_reg (rows = cols = the handle's cols). */
+int mfx_rec_fold_in_setup_reg(mfx_rec_t r, float lambda, float alpha, float alpha0, float nu);
+int mfx_rec_fold_in_block_setup_reg(mfx_rec_t r, float lambda, float alpha, float alpha0, float nu, int32_t block, int32_t sweeps, float tol);
 /* mfx_rec_fold_in with a start row per user and the sweep counts.  W_init [nusers][k] or NULL (start from 0);
  * sweeps_done [nusers] or NULL: the sweeps applied to each row.  An empty row gives w = 0 and 0 sweeps whatever W_init
  * holds.  The query checks are those of MFX_FOLD_IMPLICIT (after mfx_rec_fold_in_block_setup_als: finite values).  Valid

@@ -15,7 +15,12 @@ on rows already frozen (every sweep runs over the whole batch).
 
 --explicit (with --block) runs the sweeps on the explicit objective (mfx_rec_fold_in_block_setup_als, --reg 0 / 1).
 
+--alpha0 A --nu V (either one; a lone alpha0 means nu = 0, a lone nu means alpha0 = 1) run the implicit model, direct or with
+--block, on the objective with an unobserved weight and a frequency-scaled regulariser (mfx_rec_fold_in_setup_reg /
+mfx_rec_fold_in_block_setup_reg); without --block the model is then IMPLICIT_REG alone.  Not with --explicit.
+
     python tools/foldin_bench.py [--reps 5] [--k 64] [--n-top 10] [--block D --sweeps S --tol T [--explicit [--reg R]]]
+                                 [--alpha0 A --nu V]
 """
 import argparse
 import json
@@ -44,9 +49,14 @@ def main():
     ap.add_argument("--tol", type=float, default=0.0)
     ap.add_argument("--explicit", action="store_true", help="with --block: the explicit objective (mfx_rec_fold_in_block_setup_als)")
     ap.add_argument("--reg", type=int, default=0, help="with --explicit: 0 = lambda, 1 = lambda * entries of the row")
+    ap.add_argument("--alpha0", type=float, default=None, help="weight of the unobserved pairs (the _reg setups)")
+    ap.add_argument("--nu", type=float, default=None, help="exponent of the frequency-scaled regulariser, 0..1")
     a = ap.parse_args()
     if a.explicit and a.block is None:
         ap.error("--explicit needs --block")
+    reg = {key: v for key, v in (("alpha0", a.alpha0), ("nu", a.nu)) if v is not None}
+    if reg and a.explicit:
+        ap.error("--alpha0 / --nu apply to the implicit objective")
     import torch
     import mfx
     from mfx import synth_torch
@@ -78,16 +88,22 @@ def main():
         out.update({"block": a.block, "sweeps": a.sweeps, "tol": a.tol})
         if a.explicit:
             out.update({"explicit": True, "reg": a.reg})
+    if reg:
+        out.update({"alpha0": 1.0 if a.alpha0 is None else a.alpha0, "nu": 0.0 if a.nu is None else a.nu})
     models = (("BLOCK_ALS" if a.explicit else "BLOCK", None),) if by_blocks else (("ALS", mfx.MFX_FOLD_ALS), ("IMPLICIT", mfx.MFX_FOLD_IMPLICIT))
+    if reg:
+        models = (("BLOCK_REG", None),) if by_blocks else (("IMPLICIT_REG", mfx.MFX_FOLD_IMPLICIT),)
     with mfx.Recommender(W, H, 1) as r:
         for name, model in models:
             t0 = time.perf_counter()
             if by_blocks and a.explicit:
                 r.fold_in_block_setup_als(a.lam, block=a.block, sweeps=a.sweeps, tol=a.tol, count_reg=bool(a.reg))
+            elif by_blocks and reg:
+                r.fold_in_block_setup_reg(a.lam, a.alpha, out["alpha0"], out["nu"], block=a.block, sweeps=a.sweeps, tol=a.tol)
             elif by_blocks:
                 r.fold_in_block_setup(a.lam, a.alpha, block=a.block, sweeps=a.sweeps, tol=a.tol)
             else:
-                r.fold_in_setup(model, a.lam, a.alpha)
+                r.fold_in_setup(model, a.lam, a.alpha, **reg)
             setup_ms = (time.perf_counter() - t0) * 1e3
             for bname, q in batches.items():
                 r.fold_in(q, a.n_top)  # warm-up

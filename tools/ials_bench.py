@@ -16,8 +16,12 @@ alone), the flop and the gathered bytes of an iteration from the shapes.  --agai
 the same matrix, the ratings taken as ratings: ms per iteration and per half-sweep, the test RMSE after every iteration,
 flop and gathered bytes from the shapes (no base Gramian, no G y product).
 
+--alpha0 A --nu V (either one; a lone alpha0 means nu = 0, a lone nu means alpha0 = 1) run the implicit solvers, exact and
+--block alike, on the objective with an unobserved weight and a frequency-scaled regulariser (mfx_ials_create_reg /
+mfx_ials_block_create_reg); the record then carries "alpha0" and "nu".  Explicit runs are not affected.
+
     python tools/ials_bench.py [--ks 64,128] [--block 128:64,256:64] [--explicit-block 256:64] [--reg 0] [--again] [--iters 5]
-                               [--alpha 1.0] [--lam 0.05]
+                               [--alpha 1.0] [--lam 0.05] [--alpha0 0.3 --nu 0.5]
 """
 import argparse
 import json
@@ -75,11 +79,21 @@ def run_explicit_block(mfx, d_arrays, rows, cols, nnz, k, block, a):
             "gathered_tb_per_s": round(by / (med * 1e-3) / 1e12, 3), "test_rmse_per_iteration": rmse}
 
 
+def reg_kwargs(a):
+    """alpha0= / nu= of ImplicitAlsSolver as the command line gave them (none: the un-suffixed entry points)."""
+    kw = {}
+    if a.alpha0 is not None:
+        kw["alpha0"] = a.alpha0
+    if a.nu is not None:
+        kw["nu"] = a.nu
+    return kw
+
+
 def run_block(mfx, d_arrays, rows, cols, nnz, k, block, a):
     p = mfx.parameter()
     p.k, p.lambda_, p.log = k, a.lam, 1 if a.verbose else 0  # (log: the solver reports failed pivots on stdout)
     H0 = mfx.initial_col(cols, k)
-    s = mfx.ImplicitAlsSolver(None, p, a.alpha, device_arrays=d_arrays, block=block)
+    s = mfx.ImplicitAlsSolver(None, p, a.alpha, device_arrays=d_arrays, block=block, **reg_kwargs(a))
     s.set_factors(H0)
     losses = []
     for _ in range(a.iters):  # the loss curve from H0 (these iterations also warm up)
@@ -112,6 +126,8 @@ def main():
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--alpha", type=float, default=1.0)
     ap.add_argument("--lam", type=float, default=0.05)
+    ap.add_argument("--alpha0", type=float, default=None, help="weight of the unobserved pairs (mfx_ials_create_reg)")
+    ap.add_argument("--nu", type=float, default=None, help="exponent of the frequency-scaled regulariser, 0..1")
     ap.add_argument("--seed", type=int, default=1234)
     a = ap.parse_args()
     import torch
@@ -121,6 +137,9 @@ def main():
     rows, cols, nnz = int(d["rows"]), int(d["cols"]), int(d["csr_val"].numel())
     out = {"workload": f"{rows}x{cols} nnz={nnz}", "alpha": a.alpha, "lambda": a.lam, "iters": a.iters,
            "library": os.path.relpath(mfx.LIB_PATH, ROOT), "runs": []}
+    if reg_kwargs(a):
+        out["alpha0"] = 1.0 if a.alpha0 is None else a.alpha0
+        out["nu"] = 0.0 if a.nu is None else a.nu
     ks = [int(x) for x in a.ks.split(",") if x]
     blocks = [tuple(int(v) for v in x.split(":")) for x in a.block.split(",") if x]
     eblocks = [tuple(int(v) for v in x.split(":")) for x in a.explicit_block.split(",") if x]
@@ -138,7 +157,7 @@ def main():
         p = mfx.parameter()
         p.k, p.lambda_ = k, a.lam
         H0 = mfx.initial_col(cols, k)
-        s = mfx.ImplicitAlsSolver(None, p, a.alpha, device_arrays=d)
+        s = mfx.ImplicitAlsSolver(None, p, a.alpha, device_arrays=d, **reg_kwargs(a))
         s.set_factors(H0)
         s.iterate(1)  # warmup
         s.kernel_times()
