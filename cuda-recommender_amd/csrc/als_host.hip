@@ -1,0 +1,543 @@
+// als_host.hip -- host orchestration of the ALS solvers: the work items of an orientation (AlsHalf::build), the resident
+// solver (AlsSolver) and the one-shot entry points.  The kernels and their launches are als_solver.hip and the files that
+// compile it once more per family.
+#include "als_solver.hpp"
+
+#include <algorithm>
+#include <cmath>
+#include <cstdlib>
+#include <memory>
+
+#include "ccd_kernels.hpp"
+
+namespace mfx {
+
+size_t als_ws_floats(uint32_t nslots, uint32_t k) {
+    const size_t nt = (k + 31) / 32;
+    return (size_t) nslots * (nt * (nt + 1) / 2 * 1024 + nt * 64);
+}
+
+int AlsHalf::build(uint32_t nseg_, uint64_t nnz_, uint32_t G, const uint32_t* ptr_in, const uint32_t* idx_in,
+                   const float* val_in, mfx_memspace space, uint32_t chunk, hipStream_t st) {
+    MFX_REQUIRE(nnz_ == 0 || (idx_in && val_in), "null index / value array with %llu non-zeros", (unsigned long long) nnz_);
+    nseg = nseg_;
+    nnz = nnz_;
+    std::vector<uint32_t> hp((size_t) nseg + 1);
+    if (space == MFX_DEVICE) MFX_HIP(hipMemcpy(hp.data(), ptr_in, sizeof(uint32_t) * hp.size(), hipMemcpyDeviceToHost));
+    else memcpy(hp.data(), ptr_in, sizeof(uint32_t) * hp.size());
+    MFX_REQUIRE(hp[0] == 0 && hp[nseg] == nnz, "segment pointer array does not span [0, nnz]");
+    std::vector<AlsItem> it;
+    std::vector<AlsReduce> rd;
+    it.reserve((size_t) nseg + nnz / chunk + 1);
+    uint32_t slots = 0;
+    for (uint32_t s = 0; s < nseg; ++s) {
+        MFX_REQUIRE(hp[s] <= hp[s + 1], "segment pointer array is not monotone at %u", s);
+        const uint32_t lo = hp[s], hi = hp[s + 1];
+        if (hi - lo <= chunk) {
+            it.push_back(AlsItem{s, lo, hi, -1});
+        } else {
+            const uint32_t pieces = (hi - lo + chunk - 1) / chunk;
+            rd.push_back(AlsReduce{s, slots, pieces});
+            for (uint32_t c = 0; c < pieces; ++c)
+                it.push_back(AlsItem{s, lo + c * chunk, std::min(hi, lo + (c + 1) * chunk), (int32_t) (slots + c)});
+            slots += pieces;
+        }
+    }
+    nitems = (uint32_t) it.size();
+    nreduces = (uint32_t) rd.size();
+    nslots = slots;
+    MFX_TRY(ptr.alloc(hp.size())); MFX_TRY(ptr.upload(hp.data(), hp.size(), MFX_HOST, st));
+    // kAlsEntryPad extra entries each: entry nnz is (G, 0) = "the all-zero row of X, rating 0", the stand-in of k_als_gram<NT>
+    // for positions past a segment's end; the rest is zero padding that k_als_gram16 may read (and ignore) past the
+    // last segment
+    MFX_TRY(idx.alloc(nnz + kAlsEntryPad)); MFX_TRY(idx.upload(idx_in, nnz, space, st));
+    MFX_TRY(val.alloc(nnz + kAlsEntryPad)); MFX_TRY(val.upload(val_in, nnz, space, st));
+    MFX_HIP(hipMemsetAsync(idx.get() + nnz, 0, sizeof(uint32_t) * kAlsEntryPad, st));
+    MFX_HIP(hipMemsetAsync(val.get() + nnz, 0, sizeof(float) * kAlsEntryPad, st));
+    MFX_HIP(hipMemcpyAsync(idx.get() + nnz, &G, sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    MFX_TRY(items.alloc(nitems ? nitems : 1)); MFX_TRY(items.upload(it.data(), nitems, MFX_HOST, st));
+    MFX_TRY(reduces.alloc(nreduces ? nreduces : 1)); MFX_TRY(reduces.upload(rd.data(), nreduces, MFX_HOST, st));
+    MFX_HIP(hipStreamSynchronize(st));
+    // the Gramian kernels use idx[q] as a row of X without further checks
+    MFX_TRY(check_index_range(idx.get(), nnz, G, "ALS gather index", st));
+    return MFX_OK;
+}
+
+
+// ------------------------------------------------------------------------------------------------
+int AlsSolver::create(AlsSolver** out, const mfx_csx* R, const mfx_coo* T, const mfx_params* p, mfx_memspace space,
+                      const mfx_als_shard* shard) {
+    MFX_REQUIRE(out && R && p, "mfx_als_create: null argument");
+    std::unique_ptr<AlsSolver> s(new AlsSolver());
+    MFX_TRY(s->init(R, T, p, space, shard));
+    *out = s.release();
+    return MFX_OK;
+}
+
+int AlsSolver::create_implicit(AlsSolver** out, const mfx_csx* R, const mfx_params* p, float alpha, mfx_memspace space) {
+    MFX_REQUIRE(out && R && p, "mfx_ials_create: null argument");
+    MFX_REQUIRE(std::isfinite(alpha) && alpha >= 0.f, "mfx_ials_create: alpha = %g (finite and >= 0 required)", (double) alpha);
+    MFX_REQUIRE(p->k >= 1 && p->k <= 128, "implicit ALS: rank k = %u not supported (1 <= k <= 128)", p->k);
+    MFX_REQUIRE(p->schedule == 1, "implicit ALS: schedule must be 1 (there is no as-written mode)");
+    std::unique_ptr<AlsSolver> s(new AlsSolver());
+    s->implicit_ = true;
+    s->alpha_ = alpha;
+    MFX_TRY(s->init(R, nullptr, p, space, nullptr));
+    *out = s.release();
+    return MFX_OK;
+}
+
+int AlsSolver::create_block(AlsSolver** out, const mfx_csx* R, const mfx_params* p, float alpha, int32_t block, mfx_memspace space) {
+    MFX_REQUIRE(out && R && p, "mfx_ials_block_create: null argument");
+    MFX_REQUIRE(std::isfinite(alpha) && alpha >= 0.f, "mfx_ials_block_create: alpha = %g (finite and >= 0 required)", (double) alpha);
+    MFX_REQUIRE(p->k >= 1 && p->k <= kIalsBlockMaxRank, "implicit ALS by block sweeps: rank k = %u not supported (1 <= k <= %u)", p->k,
+                kIalsBlockMaxRank);
+    MFX_REQUIRE(block >= 0 && block <= (int32_t) kIalsBlockMaxBlock, "implicit ALS by block sweeps: block = %d (0 = chosen from k, else 1 <= block <= %u)",
+                block, kIalsBlockMaxBlock);
+    MFX_REQUIRE(p->schedule == 1, "implicit ALS by block sweeps: schedule must be 1 (there is no as-written mode)");
+    std::unique_ptr<AlsSolver> s(new AlsSolver());
+    s->implicit_ = true;
+    s->alpha_ = alpha;
+    s->block_ = std::min<uint32_t>(block ? (uint32_t) block : ialsb_default_block(p->k), p->k);
+    MFX_TRY(s->init(R, nullptr, p, space, nullptr));
+    *out = s.release();
+    return MFX_OK;
+}
+
+int AlsSolver::create_implicit_reg(AlsSolver** out, const mfx_csx* R, const mfx_params* p, float alpha, float alpha0, float nu, int32_t block,
+                                   mfx_memspace space) {
+    const bool blk = block >= 0;
+    const char* fn = blk ? "mfx_ials_block_create_reg" : "mfx_ials_create_reg";
+    MFX_REQUIRE(out && R && p, "%s: null argument", fn);
+    MFX_REQUIRE(space == MFX_HOST || space == MFX_DEVICE, "%s: bad memory space", fn);
+    MFX_REQUIRE(std::isfinite(alpha) && alpha >= 0.f, "%s: alpha = %g (finite and >= 0 required)", fn, (double) alpha);
+    if (blk) {
+        MFX_REQUIRE(p->k >= 1 && p->k <= kIalsBlockMaxRank, "implicit ALS by block sweeps: rank k = %u not supported (1 <= k <= %u)", p->k,
+                    kIalsBlockMaxRank);
+        MFX_REQUIRE(block <= (int32_t) kIalsBlockMaxBlock, "implicit ALS by block sweeps: block = %d (0 = chosen from k, else 1 <= block <= %u)",
+                    block, kIalsBlockMaxBlock);
+    } else {
+        MFX_REQUIRE(p->k >= 1 && p->k <= 128, "implicit ALS: rank k = %u not supported (1 <= k <= 128)", p->k);
+    }
+    MFX_REQUIRE(p->schedule == 1, "%s: schedule must be 1 (there is no as-written mode)", fn);
+    MFX_TRY(ialsr_check_params(fn, p->lambda, alpha0, nu, R->rows, R->cols));
+    std::unique_ptr<AlsSolver> s(new AlsSolver());
+    s->implicit_ = true;
+    s->alpha_ = alpha;
+    s->robj_ = true;
+    s->alpha0_ = alpha0;
+    s->nu_ = nu;
+    if (blk) s->block_ = std::min<uint32_t>(block ? (uint32_t) block : ialsb_default_block(p->k), p->k);
+    MFX_TRY(s->init(R, nullptr, p, space, nullptr));
+    *out = s.release();
+    return MFX_OK;
+}
+
+int AlsSolver::create_block_explicit(AlsSolver** out, const mfx_csx* R, const mfx_coo* T, const mfx_params* p, int32_t block, int32_t reg,
+                                     mfx_memspace space) {
+    MFX_REQUIRE(out && R && p, "mfx_als_block_create: null argument");
+    MFX_REQUIRE(p->k >= 1 && p->k <= kIalsBlockMaxRank, "explicit ALS by block sweeps: rank k = %u not supported (1 <= k <= %u)", p->k,
+                kIalsBlockMaxRank);
+    MFX_REQUIRE(block >= 0 && block <= (int32_t) kIalsBlockMaxBlock, "explicit ALS by block sweeps: block = %d (0 = chosen from k, else 1 <= block <= %u)",
+                block, kIalsBlockMaxBlock);
+    MFX_REQUIRE(reg == 0 || reg == 1, "explicit ALS by block sweeps: reg = %d (0 = lambda, 1 = lambda * entries of the segment)", reg);
+    MFX_REQUIRE(std::isfinite(p->lambda) && p->lambda > 0.f, "explicit ALS by block sweeps: lambda = %g (finite and > 0 required)", (double) p->lambda);
+    MFX_REQUIRE(p->schedule == 1, "explicit ALS by block sweeps: schedule must be 1 (there is no as-written mode)");
+    std::unique_ptr<AlsSolver> s(new AlsSolver());
+    s->block_ = std::min<uint32_t>(block ? (uint32_t) block : ialsb_default_block(p->k), p->k);
+    s->reg_ = reg;
+    MFX_TRY(s->init(R, T, p, space, nullptr));
+    *out = s.release();
+    return MFX_OK;
+}
+
+AlsSolver::~AlsSolver() {
+    (void) hipSetDevice(device_);
+    for (hipEvent_t& e : ev_)
+        if (e) (void) hipEventDestroy(e);
+    if (st_) {
+        (void) hipStreamSynchronize(st_);
+        (void) hipStreamDestroy(st_);
+    }
+}
+
+// Block boundaries of every rank, gathered through the communicator itself: each rank contributes
+// its own (lo, hi) into a zeroed vector and a sum all-reduce fills in the rest.
+static int gather_bounds(mfx_comm_s* c, int64_t lo, int64_t hi, std::vector<int64_t>* bounds, hipStream_t st) {
+    DevBuf<double> d;
+    std::vector<double> h((size_t) c->nranks * 2, 0.0);
+    h[(size_t) c->rank * 2] = (double) lo;
+    h[(size_t) c->rank * 2 + 1] = (double) hi;
+    MFX_TRY(d.alloc(h.size()));
+    MFX_TRY(d.upload(h.data(), h.size(), MFX_HOST, st));
+    MFX_TRY(comm_allreduce_f64(c, d.get(), h.size(), st));
+    MFX_HIP(hipMemcpyAsync(h.data(), d.get(), sizeof(double) * h.size(), hipMemcpyDeviceToHost, st));
+    MFX_HIP(hipStreamSynchronize(st));
+    bounds->assign((size_t) c->nranks + 1, 0);
+    for (int r = 0; r < c->nranks; ++r) {
+        MFX_REQUIRE((int64_t) h[(size_t) r * 2] == (*bounds)[r], "ALS shards are not contiguous in rank order");
+        (*bounds)[(size_t) r + 1] = (int64_t) h[(size_t) r * 2 + 1];
+    }
+    return MFX_OK;
+}
+
+int AlsSolver::init(const mfx_csx* R, const mfx_coo* T, const mfx_params* p, mfx_memspace space, const mfx_als_shard* shard) {
+    MFX_REQUIRE(R->rows > 0 && R->cols > 0 && R->nnz >= 0, "bad matrix shape");
+    MFX_REQUIRE(R->rows < (int64_t) 0xFFFFFFFFll && R->cols < (int64_t) 0xFFFFFFFFll &&
+                    R->nnz < (int64_t) 0xFFFF0000ll, "matrix exceeds 32-bit index range");
+    MFX_REQUIRE(p->k >= 1 && p->k <= (block_ ? kIalsBlockMaxRank : 128u), "ALS: rank k = %u not supported (1 <= k <= 128)", p->k);
+    MFX_REQUIRE(R->csc_col_ptr && R->csr_row_ptr, "null CSR/CSC pointer array");
+    p_ = *p;
+    device_ = p->device;
+    MFX_TRY(use_device(device_));
+    MFX_HIP(hipStreamCreateWithFlags(&st_, hipStreamNonBlocking));
+    for (hipEvent_t& e : ev_) MFX_HIP(hipEventCreate(&e));
+    m_ = (uint32_t) R->rows; n_ = (uint32_t) R->cols; k_ = p->k;
+    uint32_t lrows = m_, lcols = n_;
+    uint64_t nnz_rows = (uint64_t) R->nnz, nnz_cols = (uint64_t) R->nnz;
+    if (shard && shard->comm) {
+        MFX_REQUIRE(space == MFX_HOST, "sharded ALS takes host pointers");
+        MFX_REQUIRE(0 <= shard->row_lo && shard->row_lo <= shard->row_hi && shard->row_hi <= R->rows &&
+                        0 <= shard->col_lo && shard->col_lo <= shard->col_hi && shard->col_hi <= R->cols,
+                    "bad ALS shard ranges");
+        comm_ = shard->comm;
+        row_lo_ = (uint32_t) shard->row_lo; col_lo_ = (uint32_t) shard->col_lo;
+        lrows = (uint32_t) (shard->row_hi - shard->row_lo); lcols = (uint32_t) (shard->col_hi - shard->col_lo);
+        nnz_rows = R->csr_row_ptr[lrows]; nnz_cols = R->csc_col_ptr[lcols];
+        global_test_nnz_ = shard->global_test_nnz;
+        row_hi_ = (uint32_t) shard->row_hi; col_hi_ = (uint32_t) shard->col_hi;
+        // No collective in here (mfx.h, mfx_comm_agree): a rank that fails any check of its own setup must not leave
+        // the others inside one.  The block boundaries of the other ranks are gathered by the first iterate() call,
+        // which every rank reaches only after mfx_comm_agree reported that everybody's setup succeeded.
+    }
+    // W-half walks CSR rows with csr_val (src/ALS.cpp:132), H-half walks CSC columns
+    MFX_TRY(rows_.build(lrows, nnz_rows, n_, R->csr_row_ptr, R->csr_col_idx, R->csr_val, space, kAlsChunk, st_));
+    MFX_TRY(cols_.build(lcols, nnz_cols, m_, R->csc_col_ptr, R->csc_row_idx, R->csc_val, space, kAlsChunk, st_));
+    // one extra, all-zero row each: the Gramian kernel gathers it for positions past a segment's end
+    MFX_TRY(W_.alloc_zero(((size_t) m_ + 1) * k_, st_));
+    MFX_TRY(H_.alloc_zero(((size_t) n_ + 1) * k_, st_));
+    MFX_TRY(ws_.alloc(block_ ? 1 : std::max<size_t>(1, als_ws_floats(std::max(rows_.nslots, cols_.nslots), k_))));
+    MFX_TRY(spd_fail_.alloc_zero(1, st_));
+    if (std::getenv("MFX_ALS_PHASES")) { MFX_TRY(phases_.alloc_zero((size_t) kPhaseCopies * 8, st_)); }
+    nnz_test_ = T ? T->nnz : 0;
+    if (!comm_) global_test_nnz_ = nnz_test_;
+    if (nnz_test_ > 0) {
+        MFX_REQUIRE(T->row && T->col && T->val, "null test array");
+        MFX_TRY(t_row_.alloc(nnz_test_)); MFX_TRY(t_row_.upload(T->row, nnz_test_, space, st_));
+        MFX_TRY(t_col_.alloc(nnz_test_)); MFX_TRY(t_col_.upload(T->col, nnz_test_, space, st_));
+        MFX_TRY(t_val_.alloc(nnz_test_)); MFX_TRY(t_val_.upload(T->val, nnz_test_, space, st_));
+        MFX_TRY(check_index_range(t_row_.get(), (uint64_t) nnz_test_, m_, "test-set row", st_));
+        MFX_TRY(check_index_range(t_col_.get(), (uint64_t) nnz_test_, n_, "test-set column", st_));
+    }
+    MFX_TRY(rmse_partials_.alloc_zero(kRmseBlocks, st_));
+    MFX_TRY(rmse_sum_.alloc_zero(1, st_));
+    if (implicit_) {
+        MFX_TRY(ials_check_values(rows_.val.get(), rows_.nnz, alpha_, "implicit ALS: R (CSR) value", st_));
+        MFX_TRY(ials_check_values(cols_.val.get(), cols_.nnz, alpha_, "implicit ALS: R (CSC) value", st_));
+        if (block_) {
+            MFX_REQUIRE(rows_.nnz == cols_.nnz, "implicit ALS by block sweeps: the two orientations hold %llu and %llu entries",
+                        (unsigned long long) rows_.nnz, (unsigned long long) cols_.nnz);
+            MFX_TRY(bs_.alloc(k_, block_, std::max(m_, n_), std::max(m_, n_), rows_.nnz, std::max(rows_.nslots, cols_.nslots), st_));
+        } else {
+            MFX_TRY(G_.alloc((size_t) k_ * k_));
+            MFX_TRY(gpart_.alloc(ials_base_ws_floats(std::max(m_, n_), k_)));
+            MFX_TRY(loss_ws_.alloc(robj_ ? ialsr_loss_ws_doubles(k_) : ials_loss_ws_doubles(k_)));  // (block sweeps: on the first loss(), up to 1 GB at k = 1024)
+        }
+        MFX_TRY(loss_.alloc_zero(1, st_));
+        if (robj_) {  // rho of every row over the n_ items and of every column over the m_ users
+            MFX_TRY(rho_rows_.alloc(m_)); MFX_TRY(rho_cols_.alloc(n_));
+            MFX_TRY(ialsr_rho_launch(rows_, n_, p_.lambda, alpha0_, nu_, rho_rows_.get(), st_));
+            MFX_TRY(ialsr_rho_launch(cols_, m_, p_.lambda, alpha0_, nu_, rho_cols_.get(), st_));
+        }
+    } else if (block_) {
+        MFX_TRY(als_check_finite(rows_.val.get(), rows_.nnz, "explicit ALS by block sweeps: R (CSR) value", st_));
+        MFX_TRY(als_check_finite(cols_.val.get(), cols_.nnz, "explicit ALS by block sweeps: R (CSC) value", st_));
+        MFX_REQUIRE(rows_.nnz == cols_.nnz, "explicit ALS by block sweeps: the two orientations hold %llu and %llu entries",
+                    (unsigned long long) rows_.nnz, (unsigned long long) cols_.nnz);
+        MFX_TRY(bs_.alloc_explicit(k_, block_, std::max(m_, n_), std::max(m_, n_), rows_.nnz, std::max(rows_.nslots, cols_.nslots), st_));
+    }
+    MFX_HIP(hipStreamSynchronize(st_));
+    return MFX_OK;
+}
+
+
+// After a half-sweep every rank holds only its own block of the factor it just solved: ONE grouped exchange
+// (every owner broadcasts its block inside a single ncclGroupStart / End) makes the replica whole again.
+int AlsSolver::exchange(float* X, const std::vector<int64_t>& bounds) {
+    MFX_REQUIRE(shards_met_ && bounds.size() == (size_t) comm_->nranks + 1, "ALS exchange without validated shard boundaries");
+    std::vector<int64_t> elems(bounds.size());
+    for (size_t r = 0; r < bounds.size(); ++r) elems[r] = bounds[r] * (int64_t) k_;
+    return comm_allgather_blocks_f32(comm_, X, elems.data(), st_);
+}
+
+// First iterate() of a sharded solve: everyone's block boundaries.  Every rank sees the same gathered vector, so a
+// partition that is not contiguous in rank order or does not cover the matrix fails on ALL ranks alike.
+// The boundaries are gathered into LOCAL vectors and become the solver's only after every check has passed: a failed
+// first iterate() (not contiguous / does not cover) must leave the solver in the state "not met" -- round 3 keyed on
+// row_bounds_.empty(), which gather_bounds had already filled, so a second iterate() went on to exchange() with
+// unvalidated (or, for the columns, missing) boundaries.
+int AlsSolver::meet_shards() {
+    shards_met_ = false;
+    std::vector<int64_t> rb, cb;
+    MFX_TRY(gather_bounds(comm_, row_lo_, row_hi_, &rb, st_));
+    MFX_TRY(gather_bounds(comm_, col_lo_, col_hi_, &cb, st_));
+    const size_t want = (size_t) comm_->nranks + 1;
+    MFX_REQUIRE(rb.size() == want && cb.size() == want, "ALS shards: gathered %zu / %zu boundaries for %d ranks", rb.size(), cb.size(), comm_->nranks);
+    MFX_REQUIRE(rb.back() == (int64_t) m_ && cb.back() == (int64_t) n_, "ALS shards do not cover the matrix");
+    row_bounds_.swap(rb);
+    col_bounds_.swap(cb);
+    shards_met_ = true;
+    return MFX_OK;
+}
+
+int AlsSolver::print_phases(const char* what) {
+    unsigned long long h[8] = {};
+    std::vector<unsigned long long> all((size_t) kPhaseCopies * 8);
+    MFX_HIP(hipStreamSynchronize(st_));
+    MFX_HIP(hipMemcpy(all.data(), phases_.get(), sizeof(unsigned long long) * all.size(), hipMemcpyDeviceToHost));
+    MFX_HIP(hipMemset(phases_.get(), 0, sizeof(unsigned long long) * all.size()));
+    for (size_t c = 0; c < kPhaseCopies; ++c)
+        for (int q = 0; q < 8; ++q) h[q] += all[c * 8 + q];
+    const double n = h[4] ? (double) h[4] : 1.0;
+    fprintf(stderr, "[mfx als phases] %-22s systems %llu; s_memtime clocks per system: gramian %.0f, staging %.0f, factorisation %.0f (k > 64: MFMA updates %.0f, "
+            "diagonal passes %.0f, passes below %.0f), solves %.0f\n", what, h[4], h[0] / n, h[1] / n, h[2] / n, h[5] / n, h[6] / n, h[7] / n, h[3] / n);
+    return MFX_OK;
+}
+
+int AlsSolver::set_factors(const float* W, const float* H, mfx_memspace space) {
+    // W's initial content is irrelevant (overwritten before its first read, src/ALS.cpp:98-158)
+    MFX_REQUIRE(H, "mfx_als_set_factors: H is required");
+    MFX_TRY(use_device(device_));
+    if (W) MFX_TRY(W_.upload(W, (size_t) m_ * k_, space, st_));
+    else if (block_) MFX_HIP(hipMemsetAsync(W_.get(), 0, sizeof(float) * (size_t) m_ * k_, st_));  // W is the warm start of the first W-half
+    MFX_TRY(H_.upload(H, (size_t) n_ * k_, space, st_));
+    MFX_HIP(hipStreamSynchronize(st_));
+    factors_set_ = true;
+    return MFX_OK;
+}
+
+int AlsSolver::half_sweep(const AlsHalf& h, const float* X, uint32_t x_rows, float* Y, uint32_t y_lo, const float* rho, hipEvent_t ev_gram) {
+    if (block_ && !implicit_) {
+        MFX_TRY(alsb_half_launch(bs_, h, X, x_rows, Y, p_.lambda, reg_, spd_fail_.get(), st_));
+    } else if (block_ && robj_) {
+        MFX_TRY(ialsrb_gramian(bs_, X, x_rows, alpha0_, st_));
+        MFX_HIP(hipEventRecord(ev_gram, st_));
+        MFX_TRY(ialsb_half_launch(bs_, h, X, x_rows, Y, alpha_, spd_fail_.get(), st_, alpha0_, rho));
+    } else if (block_) {
+        MFX_TRY(ialsb_gramian(bs_, X, x_rows, p_.lambda, st_));
+        MFX_HIP(hipEventRecord(ev_gram, st_));
+        MFX_TRY(ialsb_half_launch(bs_, h, X, x_rows, Y, alpha_, spd_fail_.get(), st_));
+    } else if (robj_) {
+        MFX_TRY(ialsr_base_gramian(X, x_rows, k_, alpha0_, gpart_.get(), G_.get(), st_));
+        MFX_HIP(hipEventRecord(ev_gram, st_));
+        MFX_TRY(ialsr_half_launch(h, X, x_rows, Y, k_, G_.get(), alpha_, alpha0_, rho, ws_.get(), spd_fail_.get(), st_));
+    } else if (implicit_) {
+        MFX_TRY(ials_base_gramian(X, x_rows, k_, p_.lambda, gpart_.get(), G_.get(), st_));
+        MFX_HIP(hipEventRecord(ev_gram, st_));
+        MFX_TRY(ials_half_launch(h, X, x_rows, Y, k_, G_.get(), alpha_, ws_.get(), spd_fail_.get(), st_));
+    } else if (p_.schedule == 0)  // as written: the reference's arithmetic, bit for bit (als_exact.hip)
+        MFX_TRY(als_half_exact_launch(h, X, Y + (size_t) y_lo * k_, k_, p_.lambda, spd_fail_.get(), st_));
+    else
+        MFX_TRY(als_half_launch(h, X, x_rows, Y + (size_t) y_lo * k_, k_, p_.lambda, ws_.get(), spd_fail_.get(), st_, phases_.get()));
+    return MFX_OK;
+}
+
+int AlsSolver::iterate(int n_iter, int with_rmse, mfx_iter_report* reports) {
+    MFX_REQUIRE(n_iter >= 0, "n_iter must be >= 0");
+    MFX_REQUIRE(factors_set_, "mfx_als_iterate: call mfx_als_set_factors first");
+    MFX_TRY(use_device(device_));
+    if (comm_ && !shards_met_ && n_iter > 0) MFX_TRY(meet_shards());
+    for (int it = 0; it < n_iter; ++it) {
+        MFX_HIP(hipMemsetAsync(spd_fail_.get(), 0, sizeof(uint32_t), st_));
+        MFX_HIP(hipEventRecord(ev_[0], st_));
+        MFX_TRY(half_sweep(rows_, H_.get(), n_, W_.get(), row_lo_, rho_rows_.get(), ev_[4]));  // (ev_[4]: the base Gramian of H is done)
+        if (comm_) MFX_TRY(exchange(W_.get(), row_bounds_));
+        MFX_HIP(hipEventRecord(ev_[1], st_));
+        if (phases_.size()) MFX_TRY(print_phases("user half (W over H)"));
+        MFX_TRY(half_sweep(cols_, W_.get(), m_, H_.get(), col_lo_, rho_cols_.get(), ev_[5]));  // (ev_[5]: the base Gramian of W is done)
+        if (comm_) MFX_TRY(exchange(H_.get(), col_bounds_));
+        MFX_HIP(hipEventRecord(ev_[2], st_));
+        if (phases_.size()) MFX_TRY(print_phases("item half (H over W)"));
+        double rmse = 0.0, sum = 0.0;
+        if (with_rmse && global_test_nnz_ > 0) {
+            if (nnz_test_ > 0)
+                MFX_TRY(launch_test_sqerr(nnz_test_, t_row_.get(), t_col_.get(), t_val_.get(), W_.get(), H_.get(), m_, n_,
+                                          k_, 1, rmse_partials_.get(), kRmseBlocks, rmse_sum_.get(), st_));
+            else
+                MFX_HIP(hipMemsetAsync(rmse_sum_.get(), 0, sizeof(double), st_));
+            if (comm_) MFX_TRY(comm_allreduce_f64(comm_, rmse_sum_.get(), 1, st_));
+            MFX_HIP(hipMemcpyAsync(&sum, rmse_sum_.get(), sizeof(double), hipMemcpyDeviceToHost, st_));
+        }
+        MFX_HIP(hipEventRecord(ev_[3], st_));
+        uint32_t bad = 0;
+        MFX_HIP(hipMemcpyAsync(&bad, spd_fail_.get(), sizeof(uint32_t), hipMemcpyDeviceToHost, st_));
+        MFX_HIP(hipStreamSynchronize(st_));
+        if (with_rmse && global_test_nnz_ > 0) rmse = std::sqrt(sum / (double) global_test_nnz_);
+        float ms_w = 0.f, ms_h = 0.f, ms_r = 0.f, ms_gh = 0.f, ms_gw = 0.f;
+        if (implicit_) {
+            MFX_HIP(hipEventElapsedTime(&ms_gh, ev_[0], ev_[4]));
+            MFX_HIP(hipEventElapsedTime(&ms_w, ev_[4], ev_[1]));
+            MFX_HIP(hipEventElapsedTime(&ms_gw, ev_[1], ev_[5]));
+            MFX_HIP(hipEventElapsedTime(&ms_h, ev_[5], ev_[2]));
+            t_half_[2] += ms_gh * 1e-3; t_half_[3] += ms_gw * 1e-3; n_half_[2]++; n_half_[3]++;
+        } else {
+            MFX_HIP(hipEventElapsedTime(&ms_w, ev_[0], ev_[1]));
+            MFX_HIP(hipEventElapsedTime(&ms_h, ev_[1], ev_[2]));
+        }
+        MFX_HIP(hipEventElapsedTime(&ms_r, ev_[2], ev_[3]));
+        t_half_[0] += ms_w * 1e-3; t_half_[1] += ms_h * 1e-3; n_half_[0]++; n_half_[1]++;
+        mfx_iter_report rep;
+        rep.rank_time = 0.0;
+        rep.update_time = (ms_gh + ms_w + ms_gw + ms_h) * 1e-3;
+        rep.rmse = rmse;
+        rep.rmse_time = ms_r * 1e-3;
+        update_acc_ += rep.update_time;
+        ++iter_;
+        if (reports) reports[it] = rep;
+        // the reference prints this from inside the kernel for every failing pivot (ALS_CUDA.cu:11-13)
+        if (bad && p_.verbose && (!comm_ || comm_->rank == 0)) printf(" a is not positive definite! (%u systems or pivots)\n", bad);
+        if (p_.verbose && (!comm_ || comm_->rank == 0)) {
+            // log line format of cuda_src/ALS_CUDA.cu:360-361
+            printf("[-INFO-] iteration num %d \tupdate_time %.4lf|%.4lfs \tRMSE=%lf time:%fs\n", (int) iter_,
+                   rep.update_time, update_acc_, rep.rmse, rep.rmse_time);
+            fflush(stdout);
+        }
+    }
+    return MFX_OK;
+}
+
+int AlsSolver::get_factors(float* W, float* H, mfx_memspace space) {
+    MFX_TRY(use_device(device_));
+    const hipMemcpyKind kind = space == MFX_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+    if (W) MFX_HIP(hipMemcpyAsync(W, W_.get(), sizeof(float) * (size_t) m_ * k_, kind, st_));
+    if (H) MFX_HIP(hipMemcpyAsync(H, H_.get(), sizeof(float) * (size_t) n_ * k_, kind, st_));
+    MFX_HIP(hipStreamSynchronize(st_));
+    return MFX_OK;
+}
+
+int AlsSolver::kernel_times(int cap, const char** names, double* seconds, int64_t* launches) {
+    static const char* nm[2] = {"als_half_rows(W over H)", "als_half_cols(H over W)"};
+    static const char* nm_impl[4] = {"ials_half_rows(W over H)", "ials_half_cols(H over W)", "ials_base_gram(H)", "ials_base_gram(W)"};
+    static const char* nm_block[4] = {"ialsb_half_rows(W over H)", "ialsb_half_cols(H over W)", "ialsb_base_gram(H)", "ialsb_base_gram(W)"};
+    static const char* nm_eblock[2] = {"alsb_half_rows(W over H)", "alsb_half_cols(H over W)"};
+    int n = 0;
+    for (int i = 0; i < 4 && n < cap; ++i) {
+        if (!n_half_[i]) continue;
+        if (names) names[n] = block_ && !implicit_ ? nm_eblock[i] : block_ ? nm_block[i] : implicit_ ? nm_impl[i] : nm[i];
+        if (seconds) seconds[n] = t_half_[i];
+        if (launches) launches[n] = n_half_[i];
+        ++n;
+    }
+    for (int i = 0; i < 4; ++i) { t_half_[i] = 0; n_half_[i] = 0; }
+    return n;
+}
+
+int AlsSolver::loss(double* out) {
+    MFX_REQUIRE(implicit_, "mfx_ials_loss: not an implicit-feedback ALS handle (mfx_ials_create)");
+    MFX_REQUIRE(factors_set_, "mfx_ials_loss: call mfx_als_set_factors first");
+    MFX_TRY(use_device(device_));
+    if (!loss_ws_.size()) MFX_TRY(loss_ws_.alloc(robj_ ? ialsr_loss_ws_doubles(k_) : ials_loss_ws_doubles(k_)));
+    if (robj_)
+        MFX_TRY(ialsr_loss_launch(rows_, W_.get(), m_, H_.get(), n_, k_, p_.lambda, alpha_, alpha0_, nu_, rho_rows_.get(), rho_cols_.get(),
+                                  loss_ws_.get(), loss_.get(), st_));
+    else
+        MFX_TRY(ials_loss_launch(rows_, W_.get(), m_, H_.get(), n_, k_, p_.lambda, alpha_, loss_ws_.get(), loss_.get(), st_));
+    MFX_HIP(hipMemcpyAsync(out, loss_.get(), sizeof(double), hipMemcpyDeviceToHost, st_));
+    MFX_HIP(hipStreamSynchronize(st_));
+    return MFX_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+int HalfOp::open(int device, int64_t nseg, int64_t nnz, int64_t nrows_x, const uint32_t* ptr, const uint32_t* idx, const float* val) {
+    MFX_TRY(use_device(device));
+    MFX_HIP(hipStreamCreateWithFlags(&os.st, hipStreamNonBlocking));
+    return h.build((uint32_t) nseg, (uint64_t) nnz, (uint32_t) nrows_x, ptr, idx, val, MFX_HOST, kAlsChunk, os.st);
+}
+
+int HalfOp::upload(const float* X_in, int64_t nrows_x, int64_t k, bool zero_row, const float* Y_in) {
+    if (zero_row) MFX_TRY(X.alloc_zero(((size_t) nrows_x + 1) * k, os.st));
+    else MFX_TRY(X.alloc((size_t) nrows_x * k));
+    MFX_TRY(X.upload(X_in, (size_t) nrows_x * k, MFX_HOST, os.st));
+    MFX_TRY(Y.alloc_zero((size_t) h.nseg * k, os.st));
+    if (Y_in) MFX_TRY(Y.upload(Y_in, (size_t) h.nseg * k, MFX_HOST, os.st));
+    return fail_cnt.alloc_zero(1, os.st);
+}
+
+int HalfOp::download(float* Y_out) {
+    MFX_HIP(hipMemcpyAsync(Y_out, Y.get(), sizeof(float) * Y.size(), hipMemcpyDeviceToHost, os.st));
+    MFX_HIP(hipStreamSynchronize(os.st));
+    return MFX_OK;
+}
+
+int als_gramian_op(int64_t cnt, const uint32_t* idx, int64_t nrows_x, const float* X, int64_t k, float* A, int device) {
+    MFX_REQUIRE(k <= 128, "ALS: rank k = %lld not supported (1 <= k <= 128)", (long long) k);
+    MFX_TRY(use_device(device));
+    if (cnt == 0) { memset(A, 0, sizeof(float) * k * k); return MFX_OK; }
+    MFX_REQUIRE(cnt <= kAlsChunk, "mfx_als_gramian: at most %u gathered rows per call", kAlsChunk);
+    OpStream os;
+    MFX_HIP(hipStreamCreateWithFlags(&os.st, hipStreamNonBlocking));
+    DevBuf<uint32_t> didx, fail_cnt; DevBuf<float> dval, dX, dY, dA; DevBuf<AlsItem> ditem;
+    const uint32_t zrow = (uint32_t) nrows_x;
+    MFX_TRY(didx.alloc_zero(cnt + kAlsEntryPad, os.st)); MFX_TRY(didx.upload(idx, cnt, MFX_HOST, os.st));
+    MFX_HIP(hipMemcpyAsync(didx.get() + cnt, &zrow, sizeof(uint32_t), hipMemcpyHostToDevice, os.st));
+    MFX_TRY(check_index_range(didx.get(), (uint64_t) cnt, (uint32_t) nrows_x, "ALS gather index", os.st));
+    MFX_TRY(dval.alloc_zero(cnt + kAlsEntryPad, os.st));
+    MFX_TRY(dX.alloc_zero(((size_t) nrows_x + 1) * k, os.st)); MFX_TRY(dX.upload(X, (size_t) nrows_x * k, MFX_HOST, os.st));
+    MFX_TRY(dY.alloc_zero(k, os.st)); MFX_TRY(dA.alloc_zero((size_t) k * k, os.st));
+    MFX_TRY(fail_cnt.alloc_zero(1, os.st));
+    AlsItem it{0, 0, (uint32_t) cnt, -1};
+    MFX_TRY(ditem.alloc(1)); MFX_TRY(ditem.upload(&it, 1, MFX_HOST, os.st));
+    MFX_TRY(als_gramian_launch(ditem.get(), didx.get(), dval.get(), (uint32_t) cnt, dX.get(), (uint32_t) nrows_x, dY.get(), (uint32_t) k,
+                               fail_cnt.get(), dA.get(), os.st));
+    MFX_HIP(hipMemcpyAsync(A, dA.get(), sizeof(float) * k * k, hipMemcpyDeviceToHost, os.st));
+    MFX_HIP(hipStreamSynchronize(os.st));
+    return MFX_OK;
+}
+
+int als_half_op(int64_t nseg, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val,
+                int64_t nrows_x, const float* X, float* Y, int64_t k, float lambda, int variant, int device) {
+    MFX_REQUIRE(k <= 128, "ALS: rank k = %lld not supported (1 <= k <= 128)", (long long) k);
+    HalfOp op;
+    MFX_TRY(op.open(device, nseg, nnz, nrows_x, ptr, idx, val));
+    MFX_TRY(op.upload(X, nrows_x, k, true, nullptr));
+    DevBuf<float> ws;
+    MFX_TRY(ws.alloc(std::max<size_t>(1, als_ws_floats(op.h.nslots, (uint32_t) k))));
+    if (variant == 0) MFX_TRY(als_half_exact_launch(op.h, op.X.get(), op.Y.get(), (uint32_t) k, lambda, op.fail_cnt.get(), op.os.st));
+    else MFX_TRY(als_half_launch(op.h, op.X.get(), (uint32_t) nrows_x, op.Y.get(), (uint32_t) k, lambda, ws.get(), op.fail_cnt.get(), op.os.st));
+    return op.download(Y);
+}
+
+int ials_half_op(int64_t nseg, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val,
+                 int64_t nrows_x, const float* X, float* Y, int64_t k, float lambda, float alpha, int device) {
+    HalfOp op;
+    MFX_TRY(op.open(device, nseg, nnz, nrows_x, ptr, idx, val));
+    MFX_TRY(ials_check_values(op.h.val.get(), op.h.nnz, alpha, "mfx_ials_half: value", op.os.st));
+    MFX_TRY(op.upload(X, nrows_x, k, true, nullptr));
+    DevBuf<float> ws, G, part;
+    MFX_TRY(ws.alloc(std::max<size_t>(1, als_ws_floats(op.h.nslots, (uint32_t) k))));
+    MFX_TRY(G.alloc((size_t) k * k));
+    MFX_TRY(part.alloc(ials_base_ws_floats((uint32_t) nrows_x, (uint32_t) k)));
+    MFX_TRY(ials_base_gramian(op.X.get(), (uint32_t) nrows_x, (uint32_t) k, lambda, part.get(), G.get(), op.os.st));
+    MFX_TRY(ials_half_launch(op.h, op.X.get(), (uint32_t) nrows_x, op.Y.get(), (uint32_t) k, G.get(), alpha, ws.get(), op.fail_cnt.get(), op.os.st));
+    return op.download(Y);
+}
+
+int ials_half_reg_op(int64_t nseg, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val, int64_t nrows_x, const float* X,
+                     float* Y, int64_t k, float lambda, float alpha, float alpha0, float nu, int device) {
+    HalfOp op;
+    MFX_TRY(op.open(device, nseg, nnz, nrows_x, ptr, idx, val));
+    MFX_TRY(ials_check_values(op.h.val.get(), op.h.nnz, alpha, "mfx_ials_half_reg: value", op.os.st));
+    MFX_TRY(op.upload(X, nrows_x, k, true, nullptr));
+    DevBuf<float> ws, G, part, rho;
+    MFX_TRY(ws.alloc(std::max<size_t>(1, als_ws_floats(op.h.nslots, (uint32_t) k))));
+    MFX_TRY(G.alloc((size_t) k * k));
+    MFX_TRY(part.alloc(ials_base_ws_floats((uint32_t) nrows_x, (uint32_t) k)));
+    MFX_TRY(rho.alloc((size_t) nseg));
+    MFX_TRY(ialsr_rho_launch(op.h, (uint32_t) nrows_x, lambda, alpha0, nu, rho.get(), op.os.st));
+    MFX_TRY(ialsr_base_gramian(op.X.get(), (uint32_t) nrows_x, (uint32_t) k, alpha0, part.get(), G.get(), op.os.st));
+    MFX_TRY(ialsr_half_launch(op.h, op.X.get(), (uint32_t) nrows_x, op.Y.get(), (uint32_t) k, G.get(), alpha, alpha0, rho.get(), ws.get(),
+                              op.fail_cnt.get(), op.os.st));
+    return op.download(Y);
+}
+
+}  // namespace mfx

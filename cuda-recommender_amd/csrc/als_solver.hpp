@@ -23,6 +23,7 @@ struct AlsReduce {    // a segment whose Gramian was split over `nslots` consecu
 
 constexpr uint32_t kAlsChunk = 2048;  // gathered rows per wavefront before a segment is split (AlsHalf::build's `chunk`)
 constexpr uint32_t kAlsEntryPad = 128;  // entries behind AlsHalf::idx / val that the Gramian kernels may read (and ignore)
+constexpr uint32_t kPhaseCopies = 1024;  // MFX_ALS_PHASES=1: copies of the eight phase counters, one per blockIdx.x % kPhaseCopies
 
 // One orientation (rows over H, or columns over W).
 struct AlsHalf {
@@ -75,7 +76,7 @@ int ialsb_half_launch(IalsBlock& b, const AlsHalf& h, const float* X, uint32_t x
 // to stop early.  counts: device [h.nseg] (sweeps applied to each row) or NULL.
 int ialsb_fold_launch(IalsBlock& b, const AlsHalf& h, const float* X, uint32_t x_rows, float* Y, float alpha, int32_t sweeps, float tol,
                       int32_t* counts, uint32_t* spd_fail, hipStream_t st, float alpha0 = 1.f, const float* rho = nullptr);
-// ials_block_step.hip (als_solver.hip compiled with MFX_ALS_BLOCK): the systems of one block, Z [nseg][d] = the steps
+// ials_block_step.hip (als_solver.hip as the k_ialsb_* family): the systems of one block, Z [nseg][d] = the steps
 int ialsb_step_launch(const AlsHalf& h, const float* Xb, uint32_t x_rows, float* Z, uint32_t d, const float* Gbb, float alpha,
                       const float* score, const float* P, float* ws, uint32_t* spd_fail, hipStream_t st);
 int ials_block_half_op(int64_t nseg, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val, int64_t nrows_x,
@@ -92,10 +93,10 @@ int ialsr_rho_launch(const AlsHalf& h, uint32_t N, float lambda, float alpha0, f
 int ialsr_scale_launch(float* G, size_t n, float alpha0, hipStream_t st);
 int ialsr_base_gramian(const float* X, uint32_t rows, uint32_t k, float alpha0, float* part, float* G0, hipStream_t st);
 int ialsrb_gramian(IalsBlock& b, const float* X, uint32_t rows, float alpha0, hipStream_t st);
-// ials_reg_half.hip (als_solver.hip compiled with MFX_ALS_IMPLICIT and MFX_ALS_REG): the half-sweep, k <= 128
+// ials_reg_half.hip (als_solver.hip as the k_ialsr_* family): the half-sweep, k <= 128
 int ialsr_half_launch(const AlsHalf& h, const float* X, uint32_t x_rows, float* Y, uint32_t k, const float* G0, float alpha, float alpha0,
                       const float* rho, float* ws, uint32_t* spd_fail, hipStream_t st);
-// ials_reg_block_step.hip (MFX_ALS_BLOCK = 1 and MFX_ALS_REG): the systems of one block
+// ials_reg_block_step.hip (the k_ialsrb_* family): the systems of one block
 int ialsrb_step_launch(const AlsHalf& h, const float* Xb, uint32_t x_rows, float* Z, uint32_t d, const float* Gbb, float alpha, float alpha0,
                        const float* rho, const float* score, const float* P, float* ws, uint32_t* spd_fail, hipStream_t st);
 // the objective of these handles (generalises ials_loss_launch; nu = 0 takes the regulariser from the Gramians' traces)
@@ -121,7 +122,7 @@ int alsb_half_launch(IalsBlock& b, const AlsHalf& h, const float* X, uint32_t x_
 // Fold-in with the stop rule of ialsb_fold_launch, over a side packed before (alsb_pack_launch)
 int alsb_fold_launch(IalsBlock& b, const AlsHalf& h, const float* X, uint32_t x_rows, float* Y, float lambda, int32_t reg, int32_t sweeps,
                      float tol, int32_t* counts, uint32_t* spd_fail, hipStream_t st);
-// als_block_step.hip (als_solver.hip compiled with MFX_ALS_BLOCK = 2): the systems of one block, Z [nseg][d] = the steps;
+// als_block_step.hip (als_solver.hip as the k_alsb_* family): the systems of one block, Z [nseg][d] = the steps;
 // P [nseg][d] = rho y_block
 int alsb_step_launch(const AlsHalf& h, const float* Xb, uint32_t x_rows, float* Z, uint32_t d, float lambda, int32_t reg,
                      const float* score, const float* P, float* ws, uint32_t* spd_fail, hipStream_t st);
@@ -158,6 +159,9 @@ private:
     int init(const mfx_csx* R, const mfx_coo* T, const mfx_params* p, mfx_memspace space, const mfx_als_shard* shard);
     int exchange(float* X, const std::vector<int64_t>& bounds);  // every rank broadcasts its block of X (one grouped call)
     int meet_shards();  // first iterate() of a sharded solve: gathers everyone's block boundaries (never in create)
+    // One half-sweep of iterate(): Y [h.nseg][k] (this rank's rows from y_lo on) over the fixed X [x_rows][k]; rho = the
+    // regulariser of h's segments (robj_), ev_gram = the event recorded once the base Gramian of X is done (implicit_)
+    int half_sweep(const AlsHalf& h, const float* X, uint32_t x_rows, float* Y, uint32_t y_lo, const float* rho, hipEvent_t ev_gram);
     int device_ = 0;
     hipStream_t st_ = nullptr;
     mfx_params p_{};
@@ -225,6 +229,29 @@ size_t als_ws_floats(uint32_t nslots, uint32_t k);
 int als_half_exact_launch(const AlsHalf& h, const float* X, float* Y, uint32_t k, float lambda, uint32_t* spd_fail, hipStream_t st);
 // inverseMatrix_CholeskyMethod on one k x k matrix (host pointers), same arithmetic
 int als_inverse_op(int64_t k, const float* A, float* Ainv, int device);
+
+// The k x k Gramian (no lambda) of ONE unsplit item over `cnt` gathered rows into A (device); val, Y: the item's (unused)
+// ratings and solution row
+int als_gramian_launch(const AlsItem* item, const uint32_t* idx, const float* val, uint32_t cnt, const float* X, uint32_t x_rows, float* Y,
+                       uint32_t k, uint32_t* spd_fail, float* A, hipStream_t st);
+
+// ---- One-shot entry points (host pointers in and out; als_host.hip, ials_block.hip) -----------------------------------
+struct OpStream {  // a stream of the call's own, drained and destroyed on every way out
+    hipStream_t st = nullptr;
+    ~OpStream() { if (st) { (void) hipStreamSynchronize(st); (void) hipStreamDestroy(st); } }
+};
+// What the one-shot half-sweeps share: the stream, the segments as an AlsHalf, X and Y on the device, the failure counter.
+struct HalfOp {
+    OpStream os;
+    AlsHalf h;
+    DevBuf<float> X, Y;
+    DevBuf<uint32_t> fail_cnt;
+    // selects the device, creates the stream, builds h over nrows_x factor rows
+    int open(int device, int64_t nseg, int64_t nnz, int64_t nrows_x, const uint32_t* ptr, const uint32_t* idx, const float* val);
+    // X [nrows_x][k] (zero_row: with the all-zero row nrows_x behind it), Y [nseg][k] = Y_in or zeros, fail_cnt = 0
+    int upload(const float* X_in, int64_t nrows_x, int64_t k, bool zero_row, const float* Y_in);
+    int download(float* Y_out);  // Y to the host, after everything queued on the stream
+};
 
 int als_gramian_op(int64_t cnt, const uint32_t* idx, int64_t nrows_x, const float* X, int64_t k, float* A,
                    int device);

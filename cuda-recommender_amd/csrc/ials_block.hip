@@ -397,11 +397,6 @@ int one_block_start(float* Y, uint32_t nseg, uint32_t k, uint32_t d, hipStream_t
     return MFX_OK;
 }
 
-struct OpStream {
-    hipStream_t st = nullptr;
-    ~OpStream() { if (st) { (void) hipStreamSynchronize(st); (void) hipStreamDestroy(st); } }
-};
-
 }  // namespace
 
 int IalsBlock::alloc(uint32_t k_, uint32_t d_, uint32_t max_rows_x, uint32_t max_seg, uint64_t nnz, uint32_t nslots, hipStream_t st) {
@@ -500,53 +495,34 @@ int ialsb_fold_launch(IalsBlock& b, const AlsHalf& h, const float* X, uint32_t x
 
 int ials_block_half_op(int64_t nseg, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val, int64_t nrows_x,
                        const float* X, const float* Y_in, float* Y_out, int64_t k, int32_t block, float lambda, float alpha, int device) {
-    MFX_TRY(use_device(device));
-    OpStream os;
-    MFX_HIP(hipStreamCreateWithFlags(&os.st, hipStreamNonBlocking));
-    AlsHalf h;
-    MFX_TRY(h.build((uint32_t) nseg, (uint64_t) nnz, (uint32_t) nrows_x, ptr, idx, val, MFX_HOST, kAlsChunk, os.st));
-    MFX_TRY(ials_check_values(h.val.get(), h.nnz, alpha, "mfx_ials_block_half: value", os.st));
+    HalfOp op;
+    MFX_TRY(op.open(device, nseg, nnz, nrows_x, ptr, idx, val));
+    MFX_TRY(ials_check_values(op.h.val.get(), op.h.nnz, alpha, "mfx_ials_block_half: value", op.os.st));
     const uint32_t d = std::min<uint32_t>(block ? (uint32_t) block : ialsb_default_block((uint32_t) k), (uint32_t) k);
     IalsBlock b;
-    MFX_TRY(b.alloc((uint32_t) k, d, (uint32_t) nrows_x, (uint32_t) nseg, (uint64_t) nnz, h.nslots, os.st));
-    DevBuf<float> dX, dY;
-    DevBuf<uint32_t> fail_cnt;
-    MFX_TRY(dX.alloc((size_t) nrows_x * k)); MFX_TRY(dX.upload(X, (size_t) nrows_x * k, MFX_HOST, os.st));
-    MFX_TRY(dY.alloc_zero((size_t) nseg * k, os.st));
-    if (Y_in) MFX_TRY(dY.upload(Y_in, (size_t) nseg * k, MFX_HOST, os.st));
-    MFX_TRY(fail_cnt.alloc_zero(1, os.st));
-    MFX_TRY(ialsb_gramian(b, dX.get(), (uint32_t) nrows_x, lambda, os.st));
-    MFX_TRY(ialsb_half_launch(b, h, dX.get(), (uint32_t) nrows_x, dY.get(), alpha, fail_cnt.get(), os.st));
-    MFX_HIP(hipMemcpyAsync(Y_out, dY.get(), sizeof(float) * (size_t) nseg * k, hipMemcpyDeviceToHost, os.st));
-    MFX_HIP(hipStreamSynchronize(os.st));
-    return MFX_OK;
+    MFX_TRY(b.alloc((uint32_t) k, d, (uint32_t) nrows_x, (uint32_t) nseg, (uint64_t) nnz, op.h.nslots, op.os.st));
+    MFX_TRY(op.upload(X, nrows_x, k, false, Y_in));
+    MFX_TRY(ialsb_gramian(b, op.X.get(), (uint32_t) nrows_x, lambda, op.os.st));
+    MFX_TRY(ialsb_half_launch(b, op.h, op.X.get(), (uint32_t) nrows_x, op.Y.get(), alpha, op.fail_cnt.get(), op.os.st));
+    return op.download(Y_out);
 }
 
 int ials_block_half_reg_op(int64_t nseg, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val, int64_t nrows_x,
                            const float* X, const float* Y_in, float* Y_out, int64_t k, int32_t block, float lambda, float alpha, float alpha0,
                            float nu, int device) {
-    MFX_TRY(use_device(device));
-    OpStream os;
-    MFX_HIP(hipStreamCreateWithFlags(&os.st, hipStreamNonBlocking));
-    AlsHalf h;
-    MFX_TRY(h.build((uint32_t) nseg, (uint64_t) nnz, (uint32_t) nrows_x, ptr, idx, val, MFX_HOST, kAlsChunk, os.st));
-    MFX_TRY(ials_check_values(h.val.get(), h.nnz, alpha, "mfx_ials_block_half_reg: value", os.st));
+    HalfOp op;
+    MFX_TRY(op.open(device, nseg, nnz, nrows_x, ptr, idx, val));
+    MFX_TRY(ials_check_values(op.h.val.get(), op.h.nnz, alpha, "mfx_ials_block_half_reg: value", op.os.st));
     const uint32_t d = std::min<uint32_t>(block ? (uint32_t) block : ialsb_default_block((uint32_t) k), (uint32_t) k);
     IalsBlock b;
-    MFX_TRY(b.alloc((uint32_t) k, d, (uint32_t) nrows_x, (uint32_t) nseg, (uint64_t) nnz, h.nslots, os.st));
-    DevBuf<float> dX, dY, rho;
-    DevBuf<uint32_t> fail_cnt;
-    MFX_TRY(dX.alloc((size_t) nrows_x * k)); MFX_TRY(dX.upload(X, (size_t) nrows_x * k, MFX_HOST, os.st));
-    MFX_TRY(dY.alloc_zero((size_t) nseg * k, os.st));
-    if (Y_in) MFX_TRY(dY.upload(Y_in, (size_t) nseg * k, MFX_HOST, os.st));
-    MFX_TRY(fail_cnt.alloc_zero(1, os.st));
+    MFX_TRY(b.alloc((uint32_t) k, d, (uint32_t) nrows_x, (uint32_t) nseg, (uint64_t) nnz, op.h.nslots, op.os.st));
+    MFX_TRY(op.upload(X, nrows_x, k, false, Y_in));
+    DevBuf<float> rho;
     MFX_TRY(rho.alloc((size_t) nseg));
-    MFX_TRY(ialsr_rho_launch(h, (uint32_t) nrows_x, lambda, alpha0, nu, rho.get(), os.st));
-    MFX_TRY(ialsrb_gramian(b, dX.get(), (uint32_t) nrows_x, alpha0, os.st));
-    MFX_TRY(ialsb_half_launch(b, h, dX.get(), (uint32_t) nrows_x, dY.get(), alpha, fail_cnt.get(), os.st, alpha0, rho.get()));
-    MFX_HIP(hipMemcpyAsync(Y_out, dY.get(), sizeof(float) * (size_t) nseg * k, hipMemcpyDeviceToHost, os.st));
-    MFX_HIP(hipStreamSynchronize(os.st));
-    return MFX_OK;
+    MFX_TRY(ialsr_rho_launch(op.h, (uint32_t) nrows_x, lambda, alpha0, nu, rho.get(), op.os.st));
+    MFX_TRY(ialsrb_gramian(b, op.X.get(), (uint32_t) nrows_x, alpha0, op.os.st));
+    MFX_TRY(ialsb_half_launch(b, op.h, op.X.get(), (uint32_t) nrows_x, op.Y.get(), alpha, op.fail_cnt.get(), op.os.st, alpha0, rho.get()));
+    return op.download(Y_out);
 }
 
 // ---- Explicit feedback ------------------------------------------------------------------------------------------
@@ -620,25 +596,15 @@ int alsb_fold_launch(IalsBlock& b, const AlsHalf& h, const float* X, uint32_t x_
 
 int als_block_half_op(int64_t nseg, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val, int64_t nrows_x,
                       const float* X, const float* Y_in, float* Y_out, int64_t k, int32_t block, float lambda, int32_t reg, int device) {
-    MFX_TRY(use_device(device));
-    OpStream os;
-    MFX_HIP(hipStreamCreateWithFlags(&os.st, hipStreamNonBlocking));
-    AlsHalf h;
-    MFX_TRY(h.build((uint32_t) nseg, (uint64_t) nnz, (uint32_t) nrows_x, ptr, idx, val, MFX_HOST, kAlsChunk, os.st));
-    MFX_TRY(als_check_finite(h.val.get(), h.nnz, "mfx_als_block_half: value", os.st));
+    HalfOp op;
+    MFX_TRY(op.open(device, nseg, nnz, nrows_x, ptr, idx, val));
+    MFX_TRY(als_check_finite(op.h.val.get(), op.h.nnz, "mfx_als_block_half: value", op.os.st));
     const uint32_t d = std::min<uint32_t>(block ? (uint32_t) block : ialsb_default_block((uint32_t) k), (uint32_t) k);
     IalsBlock b;
-    MFX_TRY(b.alloc_explicit((uint32_t) k, d, (uint32_t) nrows_x, (uint32_t) nseg, (uint64_t) nnz, h.nslots, os.st));
-    DevBuf<float> dX, dY;
-    DevBuf<uint32_t> fail_cnt;
-    MFX_TRY(dX.alloc((size_t) nrows_x * k)); MFX_TRY(dX.upload(X, (size_t) nrows_x * k, MFX_HOST, os.st));
-    MFX_TRY(dY.alloc_zero((size_t) nseg * k, os.st));
-    if (Y_in) MFX_TRY(dY.upload(Y_in, (size_t) nseg * k, MFX_HOST, os.st));
-    MFX_TRY(fail_cnt.alloc_zero(1, os.st));
-    MFX_TRY(alsb_half_launch(b, h, dX.get(), (uint32_t) nrows_x, dY.get(), lambda, reg, fail_cnt.get(), os.st));
-    MFX_HIP(hipMemcpyAsync(Y_out, dY.get(), sizeof(float) * (size_t) nseg * k, hipMemcpyDeviceToHost, os.st));
-    MFX_HIP(hipStreamSynchronize(os.st));
-    return MFX_OK;
+    MFX_TRY(b.alloc_explicit((uint32_t) k, d, (uint32_t) nrows_x, (uint32_t) nseg, (uint64_t) nnz, op.h.nslots, op.os.st));
+    MFX_TRY(op.upload(X, nrows_x, k, false, Y_in));
+    MFX_TRY(alsb_half_launch(b, op.h, op.X.get(), (uint32_t) nrows_x, op.Y.get(), lambda, reg, op.fail_cnt.get(), op.os.st));
+    return op.download(Y_out);
 }
 
 }  // namespace mfx

@@ -6,7 +6,7 @@ values 1..5 and 15 % explicit zeros (seed 100 + k), lambda = 0.1.  Two size sets
     S: 14 segments, 10 579 entries, 17 work items, mean 622: the short class, segments unsplit, split in two and in three
     L:  5 segments, 16 385 entries, 10 work items, mean 1 638: the long class, segments unsplit, split in two and in four
 
-Dispatch mirror: work_items / launch_class restate AlsHalf::build and launch_half (csrc/als_solver.hip); the constants
+Dispatch mirror: work_items / launch_class restate AlsHalf::build (csrc/als_host.hip) and launch_half (csrc/als_solver.hip); the constants
 they rest on are read from the sources by dispatch_constants() and asserted, so a change in the dispatcher breaks the
 mirror loudly instead of silently moving a rank to another kernel.
 
@@ -57,11 +57,13 @@ def segments(seed, nrows_x, sizes, zero_frac=0.15):
 @functools.lru_cache(maxsize=None)
 def dispatch_constants():
     """(chunk, long_mean) = (kAlsChunk, the mean entries per work item from which k_als_gram16 runs its long form), read
-    from the sources; the rank conditions of launch_half are asserted as they stand."""
+    from the sources; the rank conditions of launch_half and the split rule of AlsHalf::build are asserted as they stand."""
     with open(os.path.join(CSRC, "als_solver.hpp")) as f:
         hpp = f.read()
     with open(os.path.join(CSRC, "als_solver.hip")) as f:
         hip = f.read()
+    with open(os.path.join(CSRC, "als_host.hip")) as f:
+        host = f.read()
     chunk = re.findall(r"constexpr\s+uint32_t\s+kAlsChunk\s*=\s*(\d+)\s*;", hpp)
     assert len(chunk) == 1, chunk
     longs = re.findall(r"longs\s*=\s*nnz\s*/\s*nitems\s*>=\s*(\d+)\s*,\s*full\s*=\s*a\.k\s*==\s*(\d+)\s*;", hip)
@@ -70,7 +72,7 @@ def dispatch_constants():
     assert len(g16) == 1, g16
     nt = re.findall(r"const\s+uint32_t\s+nt\s*=\s*\(a\.k\s*\+\s*31\)\s*/\s*32\s*;", hip)
     assert len(nt) == 1, nt
-    assert re.search(r"if\s*\(hi\s*-\s*lo\s*<=\s*chunk\)", hip) and re.search(r"pieces\s*=\s*\(hi\s*-\s*lo\s*\+\s*chunk\s*-\s*1\)\s*/\s*chunk\s*;", hip)
+    assert re.search(r"if\s*\(hi\s*-\s*lo\s*<=\s*chunk\)", host) and re.search(r"pieces\s*=\s*\(hi\s*-\s*lo\s*\+\s*chunk\s*-\s*1\)\s*/\s*chunk\s*;", host)
     assert tuple(map(int, g16[0])) == (32, 64, 4, 24) and int(longs[0][1]) == 64, (g16, longs)
     return int(chunk[0]), int(longs[0][0])
 

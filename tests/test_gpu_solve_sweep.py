@@ -1,6 +1,7 @@
 """Every ALS solve kernel at every rank and block width from 1 to 128, against the fp64 references of tests/solve_sweep.py.
 
-csrc/als_solver.hip is compiled five times (k_als_*, k_alsn_*, k_ials_*, k_ialsb_*, k_alsb_*); in each family launch_half
+csrc/als_solver.hip is compiled once per kernel family; five of them are swept here (k_als_*, k_alsn_*, k_ials_*, k_ialsb_*,
+k_alsb_*; test_gpu_ials_reg.py holds k_ialsr_* / k_ialsrb_* to k_ials_* / k_ialsb_* bit for bit).  In each family launch_half
 picks one of eight kernel classes from the rank k (in a block step: the block width d) and the mean entries per work item,
 and every class solves an unsplit segment in the gram kernel itself and a split one in its reducer:
 
