@@ -671,6 +671,26 @@ int mfx_rec_evaluate(mfx_rec_t r, const mfx_coo* T, float min_rating, int32_t n_
         return r->impl->evaluate(T, min_rating, n_cut, cutoffs, out, mrr, auc, users_evaluated, auc_users, space);
     });
 }
+int mfx_rec_query_candidates(mfx_rec_t r, int64_t nusers, const uint32_t* users, const uint32_t* cand_ptr, const uint32_t* cand_idx,
+                             int32_t flags, int32_t n_top, uint32_t* items, float* scores, uint32_t* n_eligible, mfx_memspace space) {
+    return guarded("mfx_rec_query_candidates", [&]() -> int {
+        MFX_REQUIRE(r && r->impl, "null recommender");
+        return r->impl->query_candidates(nusers, users, cand_ptr, cand_idx, flags, n_top, items, scores, n_eligible, space);
+    });
+}
+int mfx_rec_score(mfx_rec_t r, int64_t npairs, const uint32_t* users, const uint32_t* items, float* scores, mfx_memspace space) {
+    return guarded("mfx_rec_score", [&]() -> int {
+        MFX_REQUIRE(r && r->impl, "null recommender");
+        return r->impl->score(npairs, users, items, scores, space);
+    });
+}
+int mfx_rec_candidates_times(mfx_rec_t r, double seconds[3]) {
+    return guarded("mfx_rec_candidates_times", [&]() -> int {
+        MFX_REQUIRE(r && r->impl && seconds, "null recommender or seconds");
+        r->impl->candidates_times(seconds);
+        return MFX_OK;
+    });
+}
 int mfx_rec_destroy(mfx_rec_t r) {
     return guarded("mfx_rec_destroy", [&]() -> int {
         if (!r) return MFX_OK;

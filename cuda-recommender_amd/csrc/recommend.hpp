@@ -46,6 +46,11 @@ public:
     int evaluate(const mfx_coo* T, float min_rating, int32_t n_cut, const int32_t* cutoffs, double* out, double* mrr, double* auc,
                  int64_t* users_evaluated, int64_t* auc_users, mfx_memspace space);
     void rank_times(double out[3]) const { for (int i = 0; i < 3; ++i) out[i] = rank_s_[i]; }
+    // mfx_rec_query_candidates / mfx_rec_score / mfx_rec_candidates_times (rec_candidates.hip)
+    int query_candidates(int64_t nusers, const uint32_t* users, const uint32_t* cand_ptr, const uint32_t* cand_idx, int32_t flags,
+                         int32_t n_top, uint32_t* items, float* scores, uint32_t* n_eligible, mfx_memspace space);
+    int score(int64_t npairs, const uint32_t* users, const uint32_t* items, float* scores, mfx_memspace space);
+    void candidates_times(double out[3]) const { for (int i = 0; i < 3; ++i) out[i] = cand_s_[i]; }
     ~Recommender();
 
 private:
@@ -107,6 +112,7 @@ private:
     float fold_tol_ = 0.f;
     double fold_s_[3] = {0, 0, 0};  // host build / solve / score seconds of the last fold-in
     double rank_s_[3] = {0, 0, 0};  // device seconds of the last rank: target keys / counting pass / exclusion correction
+    double cand_s_[3] = {0, 0, 0};  // stream seconds of the last query_candidates / score: check + stage / score / merge of long lists
 };
 
 // The sums behind {HR, precision, recall, NDCG} at one cutoff, shared by mfx_topn_metrics (positions read off a list) and

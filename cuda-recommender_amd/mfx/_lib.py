@@ -14,6 +14,7 @@ MFX_COMM_ID_BYTES = 128
 MFX_VERSION = 2  # include/mfx.h
 MFX_FOLD_ALS, MFX_FOLD_ALS_EXACT, MFX_FOLD_CCD, MFX_FOLD_IMPLICIT = 0, 1, 2, 3  # include/mfx.h mfx_fold_model
 MFX_SIM_DOT, MFX_SIM_COSINE = 0, 1  # include/mfx.h mfx_rec_metric
+MFX_CAND_NO_EXCLUDE = 1  # include/mfx.h, flags of mfx_rec_query_candidates
 
 u32p = C.POINTER(C.c_uint32)
 f32p = C.POINTER(C.c_float)
@@ -152,6 +153,10 @@ SIGNATURES = {
     "mfx_rec_rank_times": (C.c_int, [C.c_void_p, f64p]),
     "mfx_rec_evaluate": (C.c_int, [C.c_void_p, C.POINTER(mfx_coo), C.c_float, C.c_int32, C.c_void_p, f64p, f64p, f64p, i64p, i64p,
                                    C.c_int]),
+    "mfx_rec_query_candidates": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_int]),
+    "mfx_rec_score": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    "mfx_rec_candidates_times": (C.c_int, [C.c_void_p, f64p]),
     "mfx_rec_destroy": (C.c_int, [C.c_void_p]),
     "mfx_topn_metrics": (C.c_int, [C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(mfx_coo), C.c_float, f64p,
                                    i64p]),

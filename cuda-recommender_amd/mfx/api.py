@@ -757,6 +757,95 @@ def _is_dev(a) -> bool:
     return hasattr(a, "data_ptr") and not isinstance(a, np.ndarray)
 
 
+def _ids_np(a, what: str) -> np.ndarray:
+    """`a` as a 1-D int64 array of ids in 0 .. 2^32 - 1, or ValueError."""
+    a = np.asarray(a)
+    if a.ndim != 1 or (a.size and a.dtype.kind not in "iu"):
+        raise ValueError(f"{what} must be a 1-D array of integer ids")
+    if a.dtype == np.uint64 and a.size and a.max() >= 2 ** 32:
+        raise ValueError(f"{what} must be below 2^32")
+    a = a.astype(np.int64)
+    if a.size and (a.min() < 0 or a.max() >= 2 ** 32):
+        raise ValueError(f"{what} must be non-negative and below 2^32")
+    return a
+
+
+def _ids_torch(t, what: str):
+    """`t` as a 1-D int64 tensor of ids in 0 .. 2^32 - 1 (a 32-bit tensor holds the uint32 bits), or ValueError."""
+    import torch
+    if t.dim() != 1 or t.dtype.is_floating_point or t.dtype == torch.bool or t.element_size() not in (4, 8):
+        raise ValueError(f"{what} must be a 1-D tensor of 32- or 64-bit integer ids")
+    if t.element_size() == 4:
+        return t.contiguous().view(torch.int32).to(torch.int64) & 0xFFFFFFFF
+    if t.numel() and (int(t.min()) < 0 or int(t.max()) >= 2 ** 32):
+        raise ValueError(f"{what} must be non-negative and below 2^32")
+    return t
+
+
+def _is_ids32(a) -> bool:
+    """A 1-D array of uint32 ids (tensor: any 32-bit integer type, its bits) that can go to the library as it is."""
+    if _is_dev(a):
+        return a.dim() == 1 and a.element_size() == 4 and not a.dtype.is_floating_point
+    return isinstance(a, np.ndarray) and a.ndim == 1 and a.dtype == np.uint32
+
+
+def _to_dev32(a, d):
+    """Ids (0 .. 2^32 - 1) as a contiguous int32 tensor on device d holding their uint32 bits."""
+    import torch
+    if not _is_dev(a):
+        return torch.from_numpy(np.ascontiguousarray(a).astype(np.uint32, copy=False).view(np.int32)).to(d)
+    if a.element_size() == 8:
+        a = a.to(torch.int32)  # (wraps: the low 32 bits)
+    return a.contiguous().view(torch.int32).to(d)
+
+
+def _candidate_lists(c):
+    """(ptr, idx) of the three forms Recommender.query_candidates takes."""
+    if hasattr(c, "csr_row_ptr") and hasattr(c, "csr_col_idx"):
+        return c.csr_row_ptr, c.csr_col_idx
+    if isinstance(c, tuple):
+        if len(c) != 2:
+            raise ValueError("candidates: a (ptr, idx) tuple has two arrays")
+        return c
+    if _is_dev(c):
+        import torch
+        if c.dim() != 2:
+            raise ValueError("candidates: a tensor of lists must be 2-D [U, C]")
+        U, n = int(c.shape[0]), int(c.shape[1])
+        return torch.arange(U + 1, dtype=torch.int64, device=c.device) * n, c.reshape(-1)
+    a = np.asarray(c)
+    if a.ndim != 2:
+        raise ValueError("candidates: an array of lists must be 2-D [U, C]")
+    return np.arange(a.shape[0] + 1, dtype=np.int64) * a.shape[1], a.reshape(-1)
+
+
+def _canonical_lists_np(ptr: np.ndarray, idx: np.ndarray):
+    """The CSR lists (int64 ptr from 0, non-decreasing; int64 idx) with every row sorted and without repeats and
+    PAD_ITEM entries -> (ptr, idx) int64."""
+    n = ptr.size - 1
+    idx = idx[:ptr[-1]] if n >= 0 else idx
+    rows = np.repeat(np.arange(n, dtype=np.int64), np.diff(ptr))
+    keep = idx != PAD_ITEM
+    key = np.unique(rows[keep] << 32 | idx[keep])
+    out = np.zeros(n + 1, np.int64)
+    np.cumsum(np.bincount(key >> 32, minlength=n), out=out[1:])
+    return out, key & 0xFFFFFFFF
+
+
+def _canonical_lists_torch(ptr, idx):
+    """_canonical_lists_np on int64 tensors, wherever they live."""
+    import torch
+    n = int(ptr.numel()) - 1
+    idx = idx[:int(ptr[-1])]
+    rows = torch.repeat_interleave(torch.arange(n, dtype=torch.int64, device=ptr.device), ptr[1:] - ptr[:-1])
+    keep = idx != PAD_ITEM
+    key = torch.unique(rows[keep] << 32 | idx[keep])
+    out = torch.zeros(n + 1, dtype=torch.int64, device=ptr.device)
+    if n:
+        out[1:] = torch.cumsum(torch.bincount(key >> 32, minlength=n), 0)
+    return out, key & 0xFFFFFFFF
+
+
 class Recommender:
     """Resident top-N recommender over trained factors (mfx_rec_*).
 
@@ -1044,6 +1133,102 @@ class Recommender:
         out = (C.c_double * 3)()
         L.check(L.lib().mfx_rec_rank_times(self.handle, out))
         return {"keys": out[0], "count": out[1], "exclude": out[2]}
+
+    def query_candidates(self, n_top: int, candidates, users=None, apply_exclude: bool = True, canonical: bool = False,
+                         on_device: bool = False, return_counts: bool = False):
+        """The n_top best eligible items of each user's own candidate list -> (items [U, n_top], scores [U, n_top][,
+        counts [U]]), ordered and padded like query (mfx_rec_query_candidates): the second stage after a retrieval step.
+        Slot q is users[q] (None: user q) with the q-th list.  `candidates`: a (ptr, idx) pair of CSR arrays, an object
+        with csr_row_ptr / csr_col_idx, or a 2-D [U, C] id array of equal-length lists as an ANN index returns them.
+        canonical=False: every list is sorted and loses its repeats and its PAD_ITEM entries first (numpy on the host,
+        torch on the device when tensors are given); canonical=True: the lists go to the library as they are, which
+        refuses ids that are not strictly ascending within a list.  An item is eligible as in rank_of: not in the user's
+        exclusion row (apply_exclude=False: the exclusion plays no part), kept by the item filter, its key not NaN;
+        counts is the number of eligible candidates per slot.  numpy in: uint32 items and counts; GPU tensors in or
+        on_device=True: int32 tensors holding the uint32 bits, as in query.
+        Measured at 480 189 x 17 770, k = 64, N = 10: for all users at once the full-catalogue query (24.6 ms) is
+        the faster call from a list length between 300 (9.8 ms) and 1 000 (28.0 ms) on, about 5 % of the catalogue; for a
+        batch of 1 024 users this call stays faster up to the whole catalogue as the list (0.98 against 1.36 ms).  The
+        choice between the two is the caller's."""
+        ptr, idx = _candidate_lists(candidates)
+        dev = on_device or any(_is_dev(a) for a in (ptr, idx, users))
+        if not 1 <= int(n_top) <= 1024:
+            raise ValueError("n_top must be in 1 .. 1024")
+        if _is_dev(ptr) != _is_dev(idx):
+            raise ValueError("the candidate arrays must both be host arrays or both tensors")
+        wide = _ids_torch if _is_dev(ptr) else _ids_np
+        ptr = wide(ptr, "candidate row pointers")
+        if not (canonical and _is_ids32(idx)):  # (canonical 32-bit ids are not copied here)
+            idx = wide(idx, "candidate ids")
+        n = int(ptr.shape[0]) - 1
+        if n < 0:
+            raise ValueError("candidate row pointers must have one entry per list and one more")
+        if users is None:
+            if n > self.rows:
+                raise ValueError(f"{n} candidate lists but the model has {self.rows} users: pass `users`")
+        else:
+            if not _is_ids32(users):
+                users = _ids_torch(users, "users") if _is_dev(users) else _ids_np(users, "users")
+            if int(users.shape[0]) != n:
+                raise ValueError(f"{int(users.shape[0])} users but {n} candidate lists")
+        if n and int(ptr[-1]) > int(idx.shape[0]):
+            raise ValueError("the candidate row pointers end past the candidate ids")
+        if not canonical:
+            if n and (int(ptr[0]) != 0 or bool((ptr[1:] < ptr[:-1]).any())):
+                raise ValueError("candidate row pointers must start at 0 and be non-decreasing")
+            ptr, idx = (_canonical_lists_torch if _is_dev(ptr) else _canonical_lists_np)(ptr, idx)
+        flags = 0 if apply_exclude else L.MFX_CAND_NO_EXCLUDE
+        fn = L.lib().mfx_rec_query_candidates
+        if dev:
+            import torch
+            d = torch.device("cuda", self.device)
+            tp, ti, tu = (None if a is None else _to_dev32(a, d) for a in (ptr, idx, users))
+            items = torch.empty((n, n_top), dtype=torch.int32, device=d)
+            scores = torch.empty((n, n_top), dtype=torch.float32, device=d)
+            counts = torch.empty((n,), dtype=torch.int32, device=d)
+            if n:
+                p = lambda t: C.c_void_p(int(t.data_ptr())) if t is not None and t.numel() else None
+                L.check(fn(self.handle, n, p(tu), p(tp), p(ti), flags, n_top, p(items), p(scores), p(counts), L.MFX_DEVICE))
+        else:
+            pp, pi = (np.ascontiguousarray(a).astype(np.uint32, copy=False) for a in (ptr, idx))
+            pu = None if users is None else np.ascontiguousarray(users).astype(np.uint32, copy=False)
+            items, scores, counts = np.empty((n, n_top), np.uint32), np.empty((n, n_top), np.float32), np.empty(n, np.uint32)
+            L.check(fn(self.handle, n, _vp(pu), _vp(pp), _vp(pi) if pi.size else None, flags, n_top, _vp(items), _vp(scores),
+                       _vp(counts), L.MFX_HOST))
+        return (items, scores, counts) if return_counts else (items, scores)
+
+    def score(self, users, items, on_device: bool = False):
+        """The model's score of each pair (users[p], items[p]) -> float32 [P] (mfx_rec_score): the score chain of
+        query, bit for bit, whether the item is eligible for the user or not -- the scores of rank_of without its
+        counting pass.  GPU tensors in (32-bit ids) or on_device=True: a float32 tensor on the device."""
+        if _is_dev(users) or _is_dev(items) or on_device:
+            import torch
+            d = torch.device("cuda", self.device)
+            tu, ti = (_to_dev32(_ids_torch(a, "pairs") if _is_dev(a) else _ids_np(a, "pairs"), d) for a in (users, items))
+            if tu.numel() != ti.numel():
+                raise ValueError("users and items must have one entry per pair")
+            n = int(tu.numel())
+            scores = torch.empty((n,), dtype=torch.float32, device=d)
+            if n:
+                p = lambda t: C.c_void_p(int(t.data_ptr()))
+                L.check(L.lib().mfx_rec_score(self.handle, n, p(tu), p(ti), p(scores), L.MFX_DEVICE))
+            return scores
+        pu, pi = _ids_np(users, "users"), _ids_np(items, "items")
+        if pu.shape != pi.shape:
+            raise ValueError("users and items must have one entry per pair")
+        pu, pi = pu.astype(np.uint32), pi.astype(np.uint32)
+        n = int(pu.size)
+        scores = np.empty(n, np.float32)
+        L.check(L.lib().mfx_rec_score(self.handle, n, _vp(pu), _vp(pi), _vp(scores), L.MFX_HOST))
+        return scores
+
+    def candidates_times(self) -> dict:
+        """Stream seconds of the last query_candidates by phase (mfx_rec_candidates_times): {"check": copies in, validity
+        checks, the piece table; "score": the kernel that scores and selects within every piece; "select": the merge of
+        lists longer than 2048 candidates}.  After score(): {"check": staging, "score": the kernel, "select": 0}."""
+        out = (C.c_double * 3)()
+        L.check(L.lib().mfx_rec_candidates_times(self.handle, out))
+        return {"check": out[0], "score": out[1], "select": out[2]}
 
     def evaluate(self, T, cutoffs=(10,), min_rating: float = float("-inf")) -> dict:
         """Ranking metrics of this model on the held-out set T (TestData or RatingData) from exact ranks

@@ -492,6 +492,42 @@ int mfx_rec_rank_times(mfx_rec_t r, double seconds[3]);
 int mfx_rec_evaluate(mfx_rec_t r, const mfx_coo* T, float min_rating, int32_t n_cut, const int32_t* cutoffs,
                      double* out /* [n_cut][4] */, double* mrr, double* auc, int64_t* users_evaluated, int64_t* auc_users,
                      mfx_memspace space);
+/* Re-ranking of given candidate lists, the second stage of a two-stage recommender: the n_top best eligible items of each
+ * slot's own list instead of the catalogue's.
+ * Slot q is user users[q] (q when users is NULL; any order, duplicates allowed) and its candidates are
+ * cand_idx[cand_ptr[q] .. cand_ptr[q+1]): a CSR of nusers rows, cand_ptr [nusers + 1] starting at 0 and non-decreasing,
+ * the ids of every row strictly ascending and below cols.  All of that is checked on the device; a violation is
+ * MFX_ERR_INVALID, the message names the first offending slot, and the handle stays usable.  A row may be empty or the
+ * whole catalogue.  cand_idx may be NULL when every row is empty.
+ * A candidate is eligible as mfx_rec_rank defines it: not in the user's row of the exclude matrix of mfx_rec_create
+ * (flag MFX_CAND_NO_EXCLUDE: the exclude matrix plays no part), kept by the item filter if one is set, its key not NaN.
+ * items [nusers][n_top], scores [nusers][n_top] or NULL: the eligible candidates in the order of mfx_rec_query (key
+ * descending, then item ascending; -0 == +0; +-inf ordinary values), padded with (0xFFFFFFFF, -INFINITY); a returned
+ * score is the score chain of mfx_rec_query, bit for bit.  n_eligible [nusers] or NULL: the eligible candidates of the
+ * slot.  `space` applies to all six arrays.  A slot's result does not depend on the batch, its order, the memory space
+ * or the factor layout.
+ * Nothing of size users x items is stored.  Workspace during the call: 4 bytes per slot twice (the lists longer than 2048
+ * candidates, the slot of every piece of work) plus 4 bytes per 2048 candidates, and, only when some list is longer than
+ * 2048, 16 * n_top bytes per 2048 candidates (at most 8 bytes per candidate) for the partial lists of its pieces; from
+ * the first call on the row-major copy of H that mfx_rec_rank keeps.  With `space` = MFX_HOST also the device copies
+ * of the arguments and results.
+ * MFX_ERR_INVALID: n_top outside 1..1024, unknown flag bits, cand_ptr or items NULL, cand_idx NULL with a non-empty
+ * list, a user >= rows, a bad memory space.  nusers == 0 is MFX_OK and touches nothing. */
+#define MFX_CAND_NO_EXCLUDE 1   /* do not take the handle's exclusion rows off the lists */
+int mfx_rec_query_candidates(mfx_rec_t r, int64_t nusers, const uint32_t* users, const uint32_t* cand_ptr,
+                             const uint32_t* cand_idx, int32_t flags, int32_t n_top, uint32_t* items, float* scores,
+                             uint32_t* n_eligible, mfx_memspace space);
+/* scores[p] = the score chain of (users[p], items[p]), bit for bit, eligible or not: the bits mfx_rec_rank returns in its
+ * scores, without the ranks.  Pairs in any order, duplicates allowed; ids checked on the device; `space` applies to the
+ * three arrays.  MFX_ERR_INVALID, the handle left usable: a NULL array with npairs > 0, a user >= rows, an item >= cols,
+ * a bad memory space.  npairs == 0 is MFX_OK. */
+int mfx_rec_score(mfx_rec_t r, int64_t npairs, const uint32_t* users, const uint32_t* items, float* scores,
+                  mfx_memspace space);
+/* Stream seconds of the last mfx_rec_query_candidates on r by phase: [0] check + stage (copies in, the validity
+ * checks and their read-back, the piece table), [1] score (the kernel that scores every piece and selects within it),
+ * [2] select (the merge of the lists longer than 2048 candidates; 0 when there is none).  After mfx_rec_score: [0] stage,
+ * [1] score, [2] 0. */
+int mfx_rec_candidates_times(mfx_rec_t r, double seconds[3]);
 int mfx_rec_destroy(mfx_rec_t r);
 
 /* ------------------------------------------------------------------------------------
