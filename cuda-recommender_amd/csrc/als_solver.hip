@@ -21,7 +21,7 @@
 #include <type_traits>
 
 // ---- The variant of this translation unit ------------------------------------------------------------------------
-// This file is compiled seven times: as itself (k_als_*) and through six small files that set the macros below and include
+// This file is compiled eleven times: as itself (k_als_*) and through ten small files that set the macros below and include
 // it.  A translation unit per family, so that the kernels of one compile to exactly the code they had without the others.
 //   file                     macros                            kernels     what they solve
 //   als_solver.hip           --                                k_als_*     explicit ALS, k <= 128
@@ -32,10 +32,15 @@
 //   ials_block_step.hip      MFX_ALS_BLOCK = 1                 k_ialsb_*   one block step of implicit ALS by block subspace sweeps (ials_block.hip)
 //   ials_reg_block_step.hip  MFX_ALS_BLOCK = 1, MFX_ALS_REG    k_ialsrb_*  the block step of the alpha0 / regulariser objective
 //   als_block_step.hip       MFX_ALS_BLOCK = 2                 k_alsb_*    one block step of EXPLICIT ALS by block sweeps (ials_block.hip, alsb_*)
+//   als_mrhs.hip             MFX_ALS_MRHS                      k_alsm_*    k_als_*, then n_targets more right-hand sides per segment against
+//                                                                          the segment's factor (mfx_rec_explain, "More right-hand sides" below)
+//   als_nreg_mrhs.hip        MFX_ALS_NREG, MFX_ALS_MRHS        k_alsnm_*   k_alsn_* likewise
+//   ials_half_mrhs.hip       MFX_ALS_IMPLICIT, MFX_ALS_MRHS    k_ialsm_*   k_ials_* likewise
+//   ials_reg_half_mrhs.hip   MFX_ALS_IMPLICIT, _REG, _MRHS     k_ialsrm_*  k_ialsr_* likewise
 // The macros are read in this header and nowhere else: it names the family, maps the macros onto constexpr traits and
 // declares AlsArgs, whose conditional tail needs them (a field that a family does not have must not be declared: the
 // kernel-argument layout of every family is part of what it compiles to).  The kernels below ask the traits; the entry
-// points at the bottom of the file, one per family, ask ALS_FAMILY.
+// points at the bottom of the file, one per family (the four *m_* families share one), ask ALS_FAMILY.
 #ifndef MFX_ALS_BLOCK
 #define MFX_ALS_BLOCK 0
 #endif
@@ -48,8 +53,14 @@
 #ifndef MFX_ALS_REG
 #define MFX_ALS_REG 0
 #endif
+#ifndef MFX_ALS_MRHS
+#define MFX_ALS_MRHS 0
+#endif
 #if MFX_ALS_REG && !MFX_ALS_IMPLICIT
 #error "MFX_ALS_REG needs MFX_ALS_IMPLICIT or MFX_ALS_BLOCK = 1"
+#endif
+#if MFX_ALS_MRHS && MFX_ALS_BLOCK
+#error "MFX_ALS_MRHS: a block step is not a solve of the segment's system"
 #endif
 // the family of this translation unit, and the prefix of its kernels' names
 #define ALS_FAMILY_ALS 0
@@ -59,7 +70,23 @@
 #define ALS_FAMILY_IALSB 4
 #define ALS_FAMILY_IALSRB 5
 #define ALS_FAMILY_ALSB 6
-#if MFX_ALS_BLOCK == 2
+#define ALS_FAMILY_ALSM 7
+#define ALS_FAMILY_ALSNM 8
+#define ALS_FAMILY_IALSM 9
+#define ALS_FAMILY_IALSRM 10
+#if MFX_ALS_MRHS && MFX_ALS_REG
+#define ALS_FAMILY ALS_FAMILY_IALSRM
+#define ALS_KERNEL(name) k_ialsrm_##name
+#elif MFX_ALS_MRHS && MFX_ALS_IMPLICIT
+#define ALS_FAMILY ALS_FAMILY_IALSM
+#define ALS_KERNEL(name) k_ialsm_##name
+#elif MFX_ALS_MRHS && MFX_ALS_NREG
+#define ALS_FAMILY ALS_FAMILY_ALSNM
+#define ALS_KERNEL(name) k_alsnm_##name
+#elif MFX_ALS_MRHS
+#define ALS_FAMILY ALS_FAMILY_ALSM
+#define ALS_KERNEL(name) k_alsm_##name
+#elif MFX_ALS_BLOCK == 2
 #define ALS_FAMILY ALS_FAMILY_ALSB
 #define ALS_KERNEL(name) k_alsb_##name
 #elif MFX_ALS_BLOCK && MFX_ALS_REG
@@ -80,6 +107,16 @@
 #else
 #define ALS_FAMILY ALS_FAMILY_ALS
 #define ALS_KERNEL(name) k_als_##name
+#endif
+// the entry point of a multi-right-hand-side family (als_solver.hpp)
+#if ALS_FAMILY == ALS_FAMILY_IALSRM
+#define ALS_MRHS_LAUNCH ialsr_half_mrhs_launch
+#elif ALS_FAMILY == ALS_FAMILY_IALSM
+#define ALS_MRHS_LAUNCH ials_half_mrhs_launch
+#elif ALS_FAMILY == ALS_FAMILY_ALSNM
+#define ALS_MRHS_LAUNCH als_half_nreg_mrhs_launch
+#elif ALS_FAMILY == ALS_FAMILY_ALSM
+#define ALS_MRHS_LAUNCH als_half_mrhs_launch
 #endif
 
 namespace mfx {
@@ -107,6 +144,10 @@ constexpr bool kBaseGramian = kDiag == Diag::kBase || kDiag == Diag::kBaseRho;
 constexpr bool kAlpha0 = MFX_ALS_REG != 0;
 static_assert(kAlpha0 == (kDiag == Diag::kBaseRho), "the unobserved weight and the regulariser per segment come together");
 static_assert(kBaseGramian == kImplicit, "the implicit families, and only they, start from a base Gramian");
+// More right-hand sides: after the system's own solve, n_targets more right-hand sides are solved against the same factor
+// L -- rows of a.X gathered at a.targets[seg * n_targets + t], solution into a.Z[seg * n_targets + t] ("More right-hand
+// sides" at factor_solve)
+constexpr bool kMultiRhs = MFX_ALS_MRHS != 0;
 
 // unfused multiply / subtract (HIP's __fmul_rn is a plain `*` and would be contracted into v_fma)
 __device__ __forceinline__ float mul_rn(float a, float b) {
@@ -164,6 +205,11 @@ struct AlsArgs {
     float alpha0;      // (k_ialsr_*, k_ialsrb_* only) weight of the all-pairs term; G is fp32(alpha0 X^T X)
     const float* rho;  // (k_ialsr_*, k_ialsrb_* only) [nseg]: the regulariser of every segment (ialsr_rho_launch)
 #endif
+#if MFX_ALS_MRHS
+    const uint32_t* targets;  // (k_*m_* only) [nseg][n_targets]: rows of X; an id >= x_rows (the padding 0xFFFFFFFF) reads the zero row
+    uint32_t n_targets;
+    float* Z;                 // (k_*m_* only) [nseg][n_targets][k]: zeroed by the caller (an empty segment writes nothing)
+#endif
 };
 // The fields of the conditional tail, readable in every family (null / 1 where the family has none)
 __device__ __forceinline__ const uint32_t* arg_seg_ptr(const AlsArgs& a) {
@@ -197,6 +243,27 @@ __device__ __forceinline__ float arg_alpha0(const AlsArgs& a) {
 __device__ __forceinline__ const float* arg_rho(const AlsArgs& a) {
 #if MFX_ALS_REG
     return a.rho;
+#else
+    return nullptr;
+#endif
+}
+__device__ __forceinline__ const uint32_t* arg_targets(const AlsArgs& a) {
+#if MFX_ALS_MRHS
+    return a.targets;
+#else
+    return nullptr;
+#endif
+}
+__device__ __forceinline__ uint32_t arg_n_targets(const AlsArgs& a) {
+#if MFX_ALS_MRHS
+    return a.n_targets;
+#else
+    return 0;
+#endif
+}
+__device__ __forceinline__ float* arg_Z(const AlsArgs& a) {
+#if MFX_ALS_MRHS
+    return a.Z;
 #else
     return nullptr;
 #endif
@@ -416,6 +483,69 @@ __device__ void chol_blocked(float* __restrict__ L, bool& spd_ok, const AlsArgs&
 // consecutive rows (lane-contiguous, conflict-free) -- and a step is scale, v_readlane, masked fma on the UNSCALED
 // unknowns (lane i carries z_i * L[i][i] until the end, as in the k <= 64 path).  Lane l owns rows l and l + 64; rows
 // k .. KP-1 are identity rows with a zero right-hand side, so no step needs a bound on k.
+// (kMultiRhs) The two passes of solve_blocked below on one more right-hand side, operation for operation: lane l comes in with
+// entries l and l + 64 of the rhs in z0 / z1 and leaves with those of the solution.  rp0 / rp1: 1 / L[l][l], 1 / L[r1][r1];
+// lanef: the lane as an opaque float.  (Why the system's own solve is not routed through it: see solve_regs_rhs.  A change
+// to either copy goes into the other.)
+template <int NT>
+__device__ __forceinline__ void solve_blocked_rhs(const float* __restrict__ L, float& z0, float& z1, float rp0, float rp1, float lanef,
+                                                  int lane, int r1) {
+    auto rl = [](float x, int src_lane) {
+        return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), src_lane));
+    };
+    // ---- forward: L z = b
+#pragma unroll
+    for (int B = 0; B < NT; ++B) {
+        float a0[32], a1[32];
+#pragma unroll
+        for (int q = 0; q < 32; q += 4) {  // entries past a row's diagonal: inside the image, masked below
+            const f32x4 x = *reinterpret_cast<const f32x4*>(L + roff(lane) + 32 * B + q);
+            const f32x4 y = *reinterpret_cast<const f32x4*>(L + roff(r1) + 32 * B + q);
+            a0[q] = x[0]; a0[q + 1] = x[1]; a0[q + 2] = x[2]; a0[q + 3] = x[3];
+            a1[q] = y[0]; a1[q + 1] = y[1]; a1[q + 2] = y[2]; a1[q + 3] = y[3];
+        }
+#pragma unroll
+        for (int t = 0; t < 32; ++t) {
+            const int i = 32 * B + t;
+            if (i < 64) {
+                const float zi = rl(z0 * rp0, i);
+                z0 = lanef > (float) i ? __builtin_fmaf(-a0[t], zi, z0) : z0;
+                z1 = __builtin_fmaf(-a1[t], zi, z1);                      // rows 64 .. are all below row i
+            } else {
+                const float zi = rl(z1 * rp1, i - 64);
+                z1 = lanef > (float) (i - 64) ? __builtin_fmaf(-a1[t], zi, z1) : z1;
+            }
+        }
+    }
+    z0 *= rp0;
+    z1 *= rp1;
+    // ---- backward: L^T y = z
+#pragma unroll
+    for (int B = NT - 1; B >= 0; --B) {
+        float a0[32], a1[32];
+#pragma unroll
+        for (int t = 0; t < 32; ++t) {  // element `lane` (and lane + 64) of rows 32 B + t: contiguous over the lanes
+            const float* row = L + roff(32 * B + t);
+            a0[t] = row[lane];
+            a1[t] = row[r1];
+        }
+#pragma unroll
+        for (int t = 31; t >= 0; --t) {
+            const int i = 32 * B + t;
+            if (i >= 64) {
+                const float yi = rl(z1 * rp1, i - 64);
+                z1 = lanef < (float) (i - 64) ? __builtin_fmaf(-a1[t], yi, z1) : z1;
+                z0 = __builtin_fmaf(-a0[t], yi, z0);                      // rows 0 .. 63 are all above row i
+            } else {
+                const float yi = rl(z0 * rp0, i);
+                z0 = lanef < (float) i ? __builtin_fmaf(-a0[t], yi, z0) : z0;
+            }
+        }
+    }
+    z0 *= rp0;
+    z1 *= rp1;
+}
+
 template <int NT>
 __device__ __forceinline__ void solve_blocked(const float* __restrict__ L, const float* __restrict__ bv, const AlsArgs& a, uint32_t seg, int k) {
     constexpr int KP = 32 * NT;
@@ -428,6 +558,7 @@ __device__ __forceinline__ void solve_blocked(const float* __restrict__ L, const
     const float rp1 = rcp_nr(L[roff(r1) + r1]);
     float lanef = (float) lane;
     asm volatile("" : "+v"(lanef));  // (opaque: keeps the masks float compares, see factor_solve k <= 64)
+    // (solve_blocked_rhs above restates the two passes below for the further right-hand sides of kMultiRhs: change both together)
     auto rl = [](float x, int src_lane) {
         return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), src_lane));
     };
@@ -485,6 +616,51 @@ __device__ __forceinline__ void solve_blocked(const float* __restrict__ L, const
     float* y = a.Y + (size_t) seg * k;
     if (lane < k) y[lane] = z0;
     if (has1 && lane + 64 < k) y[lane + 64] = z1;
+    if constexpr (kMultiRhs) {  // More right-hand sides (see factor_solve): the two passes again per target
+        const uint32_t nt = arg_n_targets(a);
+#pragma unroll 1
+        for (uint32_t t = 0; t < nt; ++t) {
+            const size_t zt = (size_t) seg * nt + t;
+            const uint32_t tg = arg_targets(a)[zt];
+            const float* x = a.X + (size_t) (tg < a.x_rows ? tg : a.x_rows) * k;
+            z0 = lane < k ? x[lane] : 0.f;
+            z1 = (has1 && lane + 64 < k) ? x[lane + 64] : 0.f;
+            solve_blocked_rhs<NT>(L, z0, z1, rp0, rp1, lanef, lane, r1);
+            float* z = arg_Z(a) + zt * k;
+            if (lane < k) z[lane] = z0;
+            if (has1 && lane + 64 < k) z[lane + 64] = z1;
+        }
+    }
+}
+
+// (kMultiRhs) The triangular solves of the k <= 64 path on one more right-hand side: the two loops of factor_solve, operation
+// for operation (see the comment there; a change to either copy goes into the other).  Lane i comes in with entry i of the rhs in z and leaves with that of the solution;
+// r2: the lane's row of L, in registers.  The system's own solve stays written out in factor_solve: routed through this
+// function it is the same arithmetic, but the kernels of the families without more right-hand sides then come out with another
+// register allocation (SGPR spills move), and they are to compile to the code they had.
+template <int KP>
+__device__ __forceinline__ void solve_regs_rhs(const f32x2 (&r2)[KP / 2], const float* __restrict__ L, int k, float rp, float lanef, int lane,
+                                               float& z) {
+    auto rl = [](float x, int src_lane) {
+        return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), src_lane));
+    };
+#pragma unroll
+    for (int i = 0; i < KP; ++i) {  // forward: L z = b
+        if (i < k) {
+            const float zi = rl(z * rp, i);
+            z = lanef > (float) i ? __builtin_fmaf(-r2[i / 2][i & 1], zi, z) : z;
+        }
+    }
+    z *= rp;  // = the solution of L z = b; the backward pass carries y_i * L[i][i] the same way
+#pragma unroll
+    for (int i = KP - 1; i >= 0; --i) {  // backward: L^T y = z
+        if (i < k) {
+            const float yi = rl(z * rp, i);
+            const float lij = L[roff(i) + lane];  // lanes >= i read past the row's diagonal: masked below
+            z = lanef < (float) i ? __builtin_fmaf(-lij, yi, z) : z;
+        }
+    }
+    z *= rp;
 }
 
 // LDS image -> + lambda, Cholesky, two triangular solves, Y[seg] <- solution.
@@ -587,6 +763,7 @@ __device__ void factor_solve(float* lds, const AlsArgs& a, uint32_t seg, unsigne
         // with a zero rhs: their updates add exact zeros.
         // (the lane masks of the solves are FLOAT compares on purpose: as integer compares they are the store masks
         // of the factorisation loop above, get computed there, and 128 of them are kept alive across it in VGPR lanes)
+        // (solve_regs_rhs restates the two loops below for the further right-hand sides of kMultiRhs: change both together)
         float z = lane < (uint32_t) k ? bv[lane] : 0.f;
         const float rp = lane < (uint32_t) k ? rcp_nr(L[roff((int) lane) + lane]) : 0.f;
         float lanef = (float) lane;
@@ -616,6 +793,22 @@ __device__ void factor_solve(float* lds, const AlsArgs& a, uint32_t seg, unsigne
         const bool broken = (int) lane < k && !(__builtin_fabsf(z) <= 3.0e38f);
         if (__ballot(broken) != 0 && lane == 0) atomicAdd(a.spd_fail, 1u);
         phase_mark(a, 3, tmark);
+        // More right-hand sides: z_t = A^-1 x_target for every target of the segment, against the rows of L that the
+        // factorisation left in r2[] -- one more pair of passes each (solve_regs_rhs: the two loops above, restated), no
+        // reload.  A target past x_rows (the padding id) is the all-zero row: its passes run on zeros.  FULL: position `lane`
+        // of the permuted system is column `col` of the row.
+        if constexpr (kMultiRhs) {
+            const uint32_t nt = arg_n_targets(a);
+            const uint32_t col = FULL ? 4 * (lane & 15) + (lane >> 4) : lane;
+#pragma unroll 1
+            for (uint32_t t = 0; t < nt; ++t) {
+                const size_t zt = (size_t) seg * nt + t;
+                const uint32_t tg = arg_targets(a)[zt];
+                float zz = (int) lane < k ? a.X[(size_t) (tg < a.x_rows ? tg : a.x_rows) * k + col] : 0.f;
+                solve_regs_rhs<KP>(r2, L, k, rp, lanef, (int) lane, zz);
+                if ((int) lane < k) arg_Z(a)[zt * k + col] = zz;
+            }
+        }
     }
 }
 
@@ -1194,7 +1387,8 @@ __global__ __launch_bounds__(64) void ALS_KERNEL(reduce16)(AlsArgs a) {
 // (waves per SIMD, pipeline depth) of k_als_gram16 for launches of long items / of tail-dominated items.  Depth:
 // measured at the Netflix shape, item half: (2 waves, depth 2) 4.90 ms, (2, 4) 4.93, (2, 6) 4.94, (3, 4) 5.09 -- the
 // gather of 25 GB of 256-byte rows from a 123 MB table runs at 5.2 TB/s either way.
-constexpr int kG16WavesLong = 2, kG16DepthLong = 2, kG16WavesShort = 4, kG16DepthShort = 2;
+// (kMultiRhs: the further solves of the implicit families leave the k < 64 form no room for four waves -- 152 VGPRs -- so they ask for three)
+constexpr int kG16WavesLong = 2, kG16DepthLong = 2, kG16WavesShort = kMultiRhs && kImplicit ? 3 : 4, kG16DepthShort = 2;
 int launch_half_16(const AlsArgs& base, uint32_t nitems, uint32_t nreduces, uint64_t nnz, hipStream_t st) {
     const size_t lds_bytes = ((size_t) roff_host(64) + 64) * sizeof(float);
     AlsArgs a = base;
@@ -1276,7 +1470,26 @@ AlsArgs half_args(const AlsHalf& h, const float* X, uint32_t x_rows, float* Y, u
 // ---- Entry points: one per family (declared in als_solver.hpp) ---------------------------------------------------------
 // The base-Gramian families leave a.lambda = 0: lambda is on G's diagonal already (Diag::kBase), or rho goes on the diagonal
 // with the start of the accumulators (Diag::kBaseRho).
-#if ALS_FAMILY == ALS_FAMILY_ALSB
+#if ALS_FAMILY >= ALS_FAMILY_ALSM
+// The four multi-right-hand-side families (mfx_rec_explain): the half-sweep of the family without, plus the targets and Z;
+// each takes from m what its diagonal needs
+int ALS_MRHS_LAUNCH(const AlsHalf& h, const float* X, uint32_t x_rows, float* Y, uint32_t k, const AlsMrhs& m, float* ws, uint32_t* spd_fail,
+                    hipStream_t st) {
+    AlsArgs a = half_args(h, X, x_rows, Y, k, ws, spd_fail);
+    a.targets = m.targets; a.n_targets = m.n_targets; a.Z = m.Z;
+#if ALS_FAMILY == ALS_FAMILY_IALSRM
+    a.alpha = m.alpha; a.G = m.G; a.alpha0 = m.alpha0; a.rho = m.rho;
+#elif ALS_FAMILY == ALS_FAMILY_IALSM
+    a.alpha = m.alpha; a.G = m.G;
+#elif ALS_FAMILY == ALS_FAMILY_ALSNM
+    a.lambda = m.lambda;
+    a.seg_ptr = h.ptr.get();
+#else
+    a.lambda = m.lambda;
+#endif
+    return launch_half(a, h.nitems, h.nreduces, h.nnz, st);
+}
+#elif ALS_FAMILY == ALS_FAMILY_ALSB
 int alsb_step_launch(const AlsHalf& h, const float* Xb, uint32_t x_rows, float* Z, uint32_t d, float lambda, int32_t reg,
                      const float* score, const float* P, float* ws, uint32_t* spd_fail, hipStream_t st) {
     AlsArgs a = half_args(h, Xb, x_rows, Z, d, ws, spd_fail);

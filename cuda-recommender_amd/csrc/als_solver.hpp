@@ -225,6 +225,29 @@ int ials_loss_launch(const AlsHalf& rows, const float* W, uint32_t m, const floa
 // floats of workspace needed for `nslots` partial slots at rank k
 size_t als_ws_floats(uint32_t nslots, uint32_t k);
 
+// The half-sweeps with more right-hand sides (als_mrhs.hip, als_nreg_mrhs.hip, ials_half_mrhs.hip, ials_reg_half_mrhs.hip:
+// the k_alsm_*, k_alsnm_*, k_ialsm_*, k_ialsrm_* families of als_solver.hip): Y as the family without computes it, bit for bit,
+// and Z[seg][t] = A_seg^-1 X[targets[seg][t]] by the same factor and the same substitution code.  A target >= x_rows (the
+// padding id 0xFFFFFFFF) reads the zero row; the caller zeroes Z (an empty segment writes none of it) and checks the ids.
+struct AlsMrhs {
+    const uint32_t* targets = nullptr;  // [nseg][n_targets]
+    uint32_t n_targets = 0;
+    float* Z = nullptr;                 // [nseg][n_targets][k]
+    float lambda = 0.f;                 // als_half_mrhs_launch, als_half_nreg_mrhs_launch
+    float alpha = 0.f;                  // the implicit two: as ials_half_launch / ialsr_half_launch take them
+    const float* G = nullptr;
+    float alpha0 = 1.f;                 // ialsr_half_mrhs_launch
+    const float* rho = nullptr;
+};
+int als_half_mrhs_launch(const AlsHalf& h, const float* X, uint32_t x_rows, float* Y, uint32_t k, const AlsMrhs& m, float* ws,
+                         uint32_t* spd_fail, hipStream_t st);
+int als_half_nreg_mrhs_launch(const AlsHalf& h, const float* X, uint32_t x_rows, float* Y, uint32_t k, const AlsMrhs& m, float* ws,
+                              uint32_t* spd_fail, hipStream_t st);
+int ials_half_mrhs_launch(const AlsHalf& h, const float* X, uint32_t x_rows, float* Y, uint32_t k, const AlsMrhs& m, float* ws,
+                          uint32_t* spd_fail, hipStream_t st);
+int ialsr_half_mrhs_launch(const AlsHalf& h, const float* X, uint32_t x_rows, float* Y, uint32_t k, const AlsMrhs& m, float* ws,
+                           uint32_t* spd_fail, hipStream_t st);
+
 // The half-sweep "as written" (als_exact.hip): the reference's arithmetic in its order, bit for bit.
 int als_half_exact_launch(const AlsHalf& h, const float* X, float* Y, uint32_t k, float lambda, uint32_t* spd_fail, hipStream_t st);
 // inverseMatrix_CholeskyMethod on one k x k matrix (host pointers), same arithmetic

@@ -618,6 +618,21 @@ int mfx_rec_fold_in_warm(mfx_rec_t r, int64_t nusers, int64_t nnz, const uint32_
         return r->impl->fold_in_warm(nusers, nnz, ptr, idx, val, W_init, W_out, sweeps_done, n_top, items, scores, space);
     });
 }
+int mfx_rec_explain(mfx_rec_t r, int64_t nusers, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val, int32_t n_targets,
+                    const uint32_t* targets, int32_t n_expl, uint32_t* expl_items, float* expl_contrib, float* totals, float* W_out,
+                    float* Z_out, mfx_memspace space) {
+    return guarded("mfx_rec_explain", [&]() -> int {
+        MFX_REQUIRE(r && r->impl, "mfx_rec_explain: null handle");
+        return r->impl->explain(nusers, nnz, ptr, idx, val, n_targets, targets, n_expl, expl_items, expl_contrib, totals, W_out, Z_out, space);
+    });
+}
+int mfx_rec_explain_times(mfx_rec_t r, double seconds[3]) {
+    return guarded("mfx_rec_explain_times", [&]() -> int {
+        MFX_REQUIRE(r && r->impl && seconds, "mfx_rec_explain_times: null argument");
+        r->impl->explain_times(seconds);
+        return MFX_OK;
+    });
+}
 int mfx_rec_fold_in_times(mfx_rec_t r, double seconds[3]) {
     return guarded("mfx_rec_fold_in_times", [&]() -> int {
         MFX_REQUIRE(r && r->impl && seconds, "null recommender or seconds");

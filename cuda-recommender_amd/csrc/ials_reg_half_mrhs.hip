@@ -1,0 +1,6 @@
+// ials_reg_half_mrhs.hip -- the k_ialsrm_* (k_ialsr_* with n_targets more right-hand sides per segment, for mfx_rec_explain):
+// als_solver.hip as that family of its variant table.
+#define MFX_ALS_IMPLICIT 1
+#define MFX_ALS_REG 1
+#define MFX_ALS_MRHS 1
+#include "als_solver.hip"

@@ -20,6 +20,9 @@
 //                         merge each.  (mfx_rec_merge of recommend.hip sorts all partial lists of a slot at once, which
 //                         caps them at 8192 entries; a whole catalogue of 10^6 items at n_top = 1024 leaves 500 000.)
 //   mfx_cand_score        mfx_rec_score: the same scoring step over a flat list of pairs, the W row per lane.
+//   mfx_expl_topn / mfx_expl_merge / mfx_expl_totals
+//                         mfx_rec_explain's second half ("Explanations" below): the same piece scheme over the query rows'
+//                         own entries, the chain against z = A^-1 h_target instead of a row of W.
 //
 // Two forms of the gather, LOAD_GROUP or not (DESIGN 5.8 has the measurement): one lane reads its own row with 16-byte
 // loads, or eight lanes read one 128-byte line of a row each, eight rows per wave instruction, and hand the lines to
@@ -309,6 +312,145 @@ __global__ __launch_bounds__(kCandThreads) void mfx_cand_score(const float* wp, 
     }
 }
 
+// ---- Explanations (mfx_rec_explain) ------------------------------------------------------------------------
+// The score of target t for fold-in row q splits over the row's entries: <h_t, w_q> = sum_e b_e <h_e, z_qt>, z_qt = A_q^-1 h_t
+// (the multi-right-hand-side solve of als_solver.hip leaves Z).  A piece of work is (slot, target, at most kCandChunk
+// consecutive entries of the row): the pieces of a slot are those of mfx_cand_pieces over the ROW pointers, the target is
+// blockIdx.y, so the grid follows the entry count.  Lane-owned chain with z as the left operand, one multiply by the
+// entry's weight, then the sort of mfx_cand_topn with the POSITION in the row as the id: ids may repeat in a row, positions
+// do not, and "contribution descending, then position ascending" is the total order of beats().  The item ids come back
+// in on the way out.  A row longer than a piece leaves one sorted partial list per piece and target; mfx_expl_merge merges
+// them as mfx_cand_merge does.
+// (Every target of a slot gathers the same rows of H.  One workgroup per (piece, target) reads them once per target, from
+// the L2 after the first; keeping n_targets accumulators per lane to read them once would cost up to 64 VGPRs and serialise
+// the n_targets sorts in one workgroup -- not done.)
+struct ExplArgs {
+    const float* Z;            // [nu][nt][k]
+    const float* hx;           // [cols + 1][k]: H row-major, the bits of the tiles
+    const uint32_t* ptr;       // [nu + 1] the query rows
+    const uint32_t* idx;
+    const float* val;
+    const uint32_t* targets;   // [nu][nt]; kPad: no target
+    const uint32_t* piece_slot;
+    int k, nt, n_expl;
+    int implicit;              // the weight of an entry r: 0: r; 1: add_rn(alpha0, fp32(alpha r)), and only r > 0 counts
+    float alpha, alpha0;
+    uint32_t b0;
+    size_t part_stride;        // entries of part_s / part_i per target
+    float* part_s;             // [nt][2 * (total / kCandChunk + 2)][n_expl]
+    uint32_t* part_i;
+    uint32_t* out_items;       // [nu][nt][n_expl]
+    float* out_contrib;
+};
+
+__device__ __forceinline__ float expl_mul(float a, float b) {
+#pragma clang fp contract(off)
+    return a * b;
+}
+__device__ __forceinline__ float expl_add(float a, float b) {
+#pragma clang fp contract(off)
+    return a + b;
+}
+
+__global__ __launch_bounds__(kCandThreads) void mfx_expl_topn(ExplArgs a) {
+    __shared__ float ks[kCandChunk];
+    __shared__ uint32_t is[kCandChunk];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const uint32_t b = a.b0 + blockIdx.x, t = blockIdx.y;
+    const uint32_t q = a.piece_slot[b];
+    const uint32_t lo_s = a.ptr[q], hi_s = a.ptr[q + 1];
+    const uint32_t blk0 = lo_s / kCandChunk, j = b - q - blk0;
+    const bool whole = hi_s - lo_s <= (uint32_t) kCandChunk;
+    if (whole && j) return;  // (the row crosses a chunk boundary: its first piece took all of it)
+    uint32_t lo = lo_s, hi = hi_s;
+    if (!whole) {
+        const uint64_t c0 = (uint64_t) (blk0 + j) * kCandChunk;
+        lo = c0 > lo_s ? (uint32_t) c0 : lo_s;
+        hi = c0 + kCandChunk < hi_s ? (uint32_t) (c0 + kCandChunk) : hi_s;
+    }
+    const uint32_t n = hi - lo;
+    const size_t qt = (size_t) q * a.nt + t;
+    const bool has_target = a.targets[qt] != kPad;  // (uniform in the workgroup)
+    const float* z = a.Z + qt * a.k;
+    int P = 64;
+    while (P < (int) n) P <<= 1;
+    for (uint32_t base = wave * 64; base < n; base += kCandThreads) {  // (uniform in the wave)
+        const uint32_t c = base + lane;
+        const bool valid = c < n;
+        const uint32_t item = valid ? a.idx[lo + c] : 0;
+        const float r = valid ? a.val[lo + c] : 0.f;
+        const float d = lane_chain(z, a.hx + (size_t) item * a.k, a.k, a.k);
+        const float w = a.implicit ? expl_add(a.alpha0, expl_mul(a.alpha, r)) : r;
+        const float key = expl_mul(w, d);
+        const bool ok = valid && has_target && key == key && (!a.implicit || r > 0.f);
+        if (valid) {
+            ks[c] = ok ? key : -INFINITY;
+            is[c] = ok ? lo - lo_s + c : kPad;
+        }
+    }
+    for (int c = (int) n + tid; c < P; c += kCandThreads) { ks[c] = -INFINITY; is[c] = kPad; }
+    int last = 128;  // (a barrier before the first stage)
+    for (int kk = 2; kk <= P; kk <<= 1) wg_bitonic_phase(ks, is, P, kk, last, tid);
+    __syncthreads();
+    if (whole) {
+        const size_t o = qt * a.n_expl;
+        for (int e = tid; e < a.n_expl; e += kCandThreads) {
+            const uint32_t pos = e < P ? is[e] : kPad;
+            a.out_items[o + e] = pos == kPad ? kPad : a.idx[lo_s + pos];
+            a.out_contrib[o + e] = e < P ? ks[e] : -INFINITY;
+        }
+    } else {
+        const size_t o = t * a.part_stride + (size_t) (2 * (size_t) (blk0 + j) + (j == 0)) * a.n_expl;
+        for (int e = tid; e < a.n_expl; e += kCandThreads) {
+            a.part_i[o + e] = e < P ? is[e] : kPad;
+            a.part_s[o + e] = e < P ? ks[e] : -INFINITY;
+        }
+    }
+}
+
+// One workgroup per (long row, target); M: the power of two >= n_expl.  The partial lists hold positions in the row.
+__global__ __launch_bounds__(kCandThreads) void mfx_expl_merge(ExplArgs a, const uint32_t* long_list, int M) {
+    __shared__ float ks[128];
+    __shared__ uint32_t is[128];
+    const int tid = threadIdx.x;
+    const uint32_t q = long_list[blockIdx.x], t = blockIdx.y;
+    const uint32_t lo_s = a.ptr[q], hi_s = a.ptr[q + 1];
+    const uint32_t blk0 = lo_s / kCandChunk, np = 1 + hi_s / kCandChunk - blk0;
+    for (int e = tid; e < M; e += kCandThreads) { ks[e] = -INFINITY; is[e] = kPad; }
+    for (uint32_t j = 0; j < np; ++j) {
+        const size_t src = t * a.part_stride + (size_t) (2 * (size_t) (blk0 + j) + (j == 0)) * a.n_expl;
+        __syncthreads();
+        for (int e = tid; e < M; e += kCandThreads) {  // the partial list, worst first: best n_expl so far + it = one bitonic run
+            ks[2 * M - 1 - e] = e < a.n_expl ? a.part_s[src + e] : -INFINITY;
+            is[2 * M - 1 - e] = e < a.n_expl ? a.part_i[src + e] : kPad;
+        }
+        int last = 128;
+        wg_bitonic_phase(ks, is, 2 * M, 2 * M, last, tid);
+    }
+    __syncthreads();
+    const size_t o = ((size_t) q * a.nt + t) * a.n_expl;
+    for (int e = tid; e < a.n_expl; e += kCandThreads) {
+        a.out_items[o + e] = is[e] == kPad ? kPad : a.idx[lo_s + is[e]];
+        a.out_contrib[o + e] = ks[e];
+    }
+}
+
+// totals[q][t]: the pair-scoring chain of mfx_cand_score over (Y[q], H[target]), both rows [k] floats apart; -inf for kPad
+__global__ void mfx_expl_totals(const float* Y, const float* hx, const uint32_t* targets, size_t n, int nt, int k, float* totals) {
+    for (size_t p = (size_t) blockIdx.x * blockDim.x + threadIdx.x; p < n; p += (size_t) gridDim.x * blockDim.x) {
+        const uint32_t tg = targets[p];
+        totals[p] = tg == kPad ? -INFINITY : lane_chain(Y + (p / nt) * k, hx + (size_t) tg * k, k, k);
+    }
+}
+
+// every target below cols or kPad; else the first offending position into *first
+__global__ void mfx_expl_check_targets(const uint32_t* targets, size_t n, uint32_t cols, unsigned long long* first) {
+    for (size_t p = (size_t) blockIdx.x * blockDim.x + threadIdx.x; p < n; p += (size_t) gridDim.x * blockDim.x) {
+        const uint32_t tg = targets[p];
+        if (tg >= cols && tg != kPad) atomicMin(first, (unsigned long long) p);
+    }
+}
+
 struct Events {  // four stream events around the three phases
     hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
     int create() {
@@ -460,6 +602,77 @@ int Recommender::query_candidates(int64_t nusers, const uint32_t* users, const u
         float ms = 0.f;
         MFX_HIP(hipEventElapsedTime(&ms, ev.e[i], ev.e[i + 1]));
         cand_s_[i] = 1e-3 * ms;
+    }
+    return MFX_OK;
+}
+
+int Recommender::explain_check_targets(const uint32_t* d_targets, size_t n, int32_t n_targets) {
+    DevBuf<unsigned long long> first;
+    MFX_TRY(first.alloc(1));
+    MFX_HIP(hipMemsetAsync(first.get(), 0xFF, sizeof(unsigned long long), st_));
+    hipLaunchKernelGGL(mfx_expl_check_targets, dim3(grid_for(n)), dim3(256), 0, st_, d_targets, n, (uint32_t) cols_, first.get());
+    MFX_LAUNCH_CHECK();
+    unsigned long long bad = ~0ull;
+    MFX_HIP(hipMemcpyAsync(&bad, first.get(), sizeof(bad), hipMemcpyDeviceToHost, st_));
+    MFX_HIP(hipStreamSynchronize(st_));
+    MFX_REQUIRE(bad == ~0ull, "mfx_rec_explain: target %llu of slot %llu is neither an item id in [0, %lld) nor the padding 0xFFFFFFFF",
+                bad % (unsigned long long) n_targets, bad / (unsigned long long) n_targets, (long long) cols_);
+    return MFX_OK;
+}
+
+// Device pointers throughout.  d_items / d_contrib: [nu][nt][n_expl] (unread for n_expl = 0), d_totals: [nu][nt] or NULL.
+int Recommender::explain_lists(const AlsHalf& h, const uint32_t* d_targets, int32_t nt, const float* Z, const float* Y, int32_t n_expl,
+                               uint32_t* d_items, float* d_contrib, float* d_totals) {
+    hipStream_t st = st_;
+    const uint32_t nu = h.nseg;
+    if (d_totals) {
+        const size_t n = (size_t) nu * nt;
+        hipLaunchKernelGGL(mfx_expl_totals, dim3(grid_for(n)), dim3(256), 0, st, Y, (const float*) hx_.get(), d_targets, n, (int) nt, (int) k_,
+                           d_totals);
+        MFX_LAUNCH_CHECK();
+    }
+    if (n_expl == 0) return MFX_OK;
+    // the rows longer than a piece (the pointers were checked on the way in)
+    DevBuf<CandInfo> info;
+    DevBuf<uint32_t> long_list, piece_slot, part_i;
+    DevBuf<float> part_s;
+    MFX_TRY(info.alloc(1));
+    MFX_TRY(long_list.alloc(nu));
+    CandInfo hi{kCandFine, 0, 0};
+    MFX_HIP(hipMemcpyAsync(info.get(), &hi, sizeof(hi), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(mfx_cand_check_ptr, dim3(grid_for(nu)), dim3(256), 0, st, (const uint32_t*) h.ptr.get(), nu, info.get(), long_list.get());
+    MFX_LAUNCH_CHECK();
+    MFX_HIP(hipMemcpyAsync(&hi, info.get(), sizeof(hi), hipMemcpyDeviceToHost, st));
+    MFX_HIP(hipStreamSynchronize(st));
+    const uint32_t total = (uint32_t) h.nnz;
+    const uint64_t npieces = (uint64_t) nu + total / kCandChunk;
+    MFX_TRY(piece_slot.alloc(npieces));
+    hipLaunchKernelGGL(mfx_cand_pieces, dim3(grid_for(nu)), dim3(256), 0, st, (const uint32_t*) h.ptr.get(), nu, piece_slot.get());
+    MFX_LAUNCH_CHECK();
+    ExplArgs a{};
+    a.Z = Z; a.hx = hx_.get(); a.ptr = h.ptr.get(); a.idx = h.idx.get(); a.val = h.val.get(); a.targets = d_targets;
+    a.piece_slot = piece_slot.get();
+    a.k = (int) k_; a.nt = nt; a.n_expl = n_expl;
+    a.implicit = fold_model_ == MFX_FOLD_IMPLICIT;
+    a.alpha = fold_alpha_; a.alpha0 = fold_robj_ ? fold_alpha0_ : 1.f;
+    a.part_stride = 2 * ((size_t) total / kCandChunk + 2) * n_expl;
+    if (hi.nlong) {
+        MFX_TRY(part_s.alloc(a.part_stride * nt));
+        MFX_TRY(part_i.alloc(a.part_stride * nt));
+    }
+    a.part_s = part_s.get(); a.part_i = part_i.get();
+    a.out_items = d_items; a.out_contrib = d_contrib;
+    for (uint64_t b0 = 0; b0 < npieces; b0 += 1u << 30) {  // (grid.x stays below 2^31)
+        a.b0 = (uint32_t) b0;
+        const dim3 grid((uint32_t) std::min<uint64_t>(npieces - b0, 1u << 30), (uint32_t) nt);
+        hipLaunchKernelGGL(mfx_expl_topn, grid, dim3(kCandThreads), 0, st, a);
+        MFX_LAUNCH_CHECK();
+    }
+    if (hi.nlong) {
+        int M = 1;
+        while (M < n_expl) M <<= 1;
+        hipLaunchKernelGGL(mfx_expl_merge, dim3(hi.nlong, (uint32_t) nt), dim3(kCandThreads), 0, st, a, (const uint32_t*) long_list.get(), M);
+        MFX_LAUNCH_CHECK();
     }
     return MFX_OK;
 }

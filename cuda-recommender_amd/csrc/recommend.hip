@@ -39,6 +39,7 @@
 #include <chrono>
 #include <cmath>
 #include <memory>
+#include <string>
 #include <unordered_map>
 
 #include "als_solver.hpp"   // AlsHalf and the half-sweep launchers (fold-in)
@@ -820,6 +821,120 @@ int Recommender::fold_in_warm(int64_t nusers, int64_t nnz, const uint32_t* ptr, 
     return fold_solve(nusers, nnz, ptr, idx, val, W_init, W_out, sweeps_done, n_top, items, scores, space);
 }
 
+// The query rows of mfx_rec_fold_in and mfx_rec_explain (fn) as one half-sweep over H, with the chunking of training, checked:
+// build() checks the pointers on the host and every index < cols on the device; then the exclusion check of mfx_rec_create
+// (ids non-decreasing in a row) and the value checks of the model that was set up.
+int Recommender::fold_rows(const char* fn, uint32_t nu, uint64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val,
+                           mfx_memspace space, AlsHalf& h) {
+    hipStream_t st = st_;
+    const std::string who = std::string(fn) + ": ", what = who + "value";
+    MFX_TRY(h.build(nu, nnz, (uint32_t) cols_, ptr, idx, val, space, kAlsChunk, st));
+    MFX_TRY(check_csr(h.ptr.get(), h.idx.get(), nu, (uint32_t) cols_, nnz, who.c_str(), "ptr", st));
+    if (fold_model_ == MFX_FOLD_IMPLICIT || fold_model_ == kFoldBlock)
+        MFX_TRY(ials_check_values(h.val.get(), h.nnz, fold_alpha_, what.c_str(), st));
+    else if (fold_model_ == kFoldBlockAls)
+        MFX_TRY(als_check_finite(h.val.get(), h.nnz, what.c_str(), st));
+    return MFX_OK;
+}
+
+// mfx_rec_explain: the fold-in rows by the multi-right-hand-side families of als_solver.hip (Y as mfx_rec_fold_in's family
+// computes it, and Z = A^-1 h_target per target), then the totals and the ranked contributions (rec_candidates.hip).
+int Recommender::explain(int64_t nusers, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val, int32_t n_targets,
+                         const uint32_t* targets, int32_t n_expl, uint32_t* expl_items, float* expl_contrib, float* totals, float* W_out,
+                         float* Z_out, mfx_memspace space) {
+    const char* fn = "mfx_rec_explain";
+    MFX_REQUIRE(fold_model_ >= 0, "%s: call mfx_rec_fold_in_setup (MFX_FOLD_ALS, MFX_FOLD_CCD, MFX_FOLD_IMPLICIT) or mfx_rec_fold_in_setup_reg first", fn);
+    MFX_REQUIRE(fold_model_ != MFX_FOLD_ALS_EXACT,
+                "%s: the rows of MFX_FOLD_ALS_EXACT are not the bits of the MFMA system whose factor the explanation uses; set up MFX_FOLD_ALS", fn);
+    MFX_REQUIRE(fold_model_ != kFoldBlock && fold_model_ != kFoldBlockAls,
+                "%s: not after a block setup (a sweep is not a solve, the split over the entries does not hold); set up mfx_rec_fold_in_setup "
+                "or mfx_rec_fold_in_setup_reg on a handle of rank <= 128", fn);
+    MFX_REQUIRE(nusers >= 0 && nusers < (int64_t) 0xFFFFFFFFll, "%s: bad nusers %lld", fn, (long long) nusers);
+    MFX_REQUIRE(nnz >= 0 && nnz < (int64_t) 0xFFFF0000ll, "%s: bad nnz %lld", fn, (long long) nnz);
+    MFX_REQUIRE(n_targets >= 1 && n_targets <= kMaxExplain, "%s: n_targets must be in [1, %d] (got %d)", fn, kMaxExplain, n_targets);
+    MFX_REQUIRE(n_expl >= 0 && n_expl <= kMaxExplain, "%s: n_expl must be in [0, %d] (got %d)", fn, kMaxExplain, n_expl);
+    MFX_REQUIRE(space == MFX_HOST || space == MFX_DEVICE, "%s: bad memory space", fn);
+    expl_s_[0] = expl_s_[1] = expl_s_[2] = 0.0;
+    if (nusers == 0) return MFX_OK;
+    MFX_REQUIRE(ptr && (nnz == 0 || (idx && val)), "%s: null ptr / idx / val", fn);
+    MFX_REQUIRE(targets, "%s: targets is NULL", fn);
+    MFX_REQUIRE(n_expl == 0 || (expl_items && expl_contrib), "%s: expl_items or expl_contrib is NULL", fn);
+    MFX_TRY(use_device(device_));
+    hipStream_t st = st_;
+    using clk = std::chrono::steady_clock;
+    const auto t0 = clk::now();
+    const uint32_t nu = (uint32_t) nusers, k = (uint32_t) k_;
+    const size_t npair = (size_t) nu * n_targets;
+    const bool host = space == MFX_HOST;
+    AlsHalf h;
+    MFX_TRY(fold_rows(fn, nu, (uint64_t) nnz, ptr, idx, val, space, h));
+    DevBuf<uint32_t> d_targets;
+    const uint32_t* dt = targets;
+    if (host) {
+        MFX_TRY(d_targets.alloc(npair));
+        MFX_TRY(d_targets.upload(targets, npair, MFX_HOST, st));
+        dt = d_targets.get();
+    }
+    MFX_TRY(explain_check_targets(dt, npair, n_targets));
+    const auto t1 = clk::now();
+
+    DevBuf<float> Y, Z, ws, rho, d_contrib, d_totals;
+    DevBuf<uint32_t> spd_fail, d_items;
+    MFX_TRY(Y.alloc_zero((size_t) nu * k, st));
+    MFX_TRY(Z.alloc_zero(npair * k, st));
+    MFX_TRY(spd_fail.alloc_zero(1, st));
+    MFX_TRY(ws.alloc(std::max<size_t>(1, als_ws_floats(h.nslots, k))));
+    const uint32_t x_rows = (uint32_t) cols_;
+    AlsMrhs m;
+    m.targets = dt; m.n_targets = (uint32_t) n_targets; m.Z = Z.get();
+    m.lambda = fold_lambda_; m.alpha = fold_alpha_; m.G = fold_g_.get();
+    if (fold_robj_) {  // the regulariser of every query row, as fold_solve forms it
+        MFX_TRY(rho.alloc(nu));
+        MFX_TRY(ialsr_rho_launch(h, x_rows, fold_lambda_, fold_alpha0_, fold_nu_, rho.get(), st));
+        m.alpha0 = fold_alpha0_; m.rho = rho.get();
+    }
+    switch (fold_model_) {
+        case MFX_FOLD_ALS: MFX_TRY(als_half_mrhs_launch(h, hx_.get(), x_rows, Y.get(), k, m, ws.get(), spd_fail.get(), st)); break;
+        case MFX_FOLD_CCD: MFX_TRY(als_half_nreg_mrhs_launch(h, hx_.get(), x_rows, Y.get(), k, m, ws.get(), spd_fail.get(), st)); break;
+        default:
+            if (fold_robj_) MFX_TRY(ialsr_half_mrhs_launch(h, hx_.get(), x_rows, Y.get(), k, m, ws.get(), spd_fail.get(), st));
+            else MFX_TRY(ials_half_mrhs_launch(h, hx_.get(), x_rows, Y.get(), k, m, ws.get(), spd_fail.get(), st));
+            break;
+    }
+    MFX_HIP(hipStreamSynchronize(st));
+    const auto t2 = clk::now();
+
+    const hipMemcpyKind out = host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+    if (W_out) MFX_HIP(hipMemcpyAsync(W_out, Y.get(), sizeof(float) * (size_t) nu * k, out, st));
+    if (Z_out) MFX_HIP(hipMemcpyAsync(Z_out, Z.get(), sizeof(float) * npair * k, out, st));
+    uint32_t* oi = expl_items;
+    float* oc = expl_contrib;
+    float* ot = totals;
+    const size_t nlist = npair * (size_t) n_expl;
+    if (host) {
+        if (n_expl) {
+            MFX_TRY(d_items.alloc(nlist));
+            MFX_TRY(d_contrib.alloc(nlist));
+            oi = d_items.get(); oc = d_contrib.get();
+        }
+        if (totals) { MFX_TRY(d_totals.alloc(npair)); ot = d_totals.get(); }
+    }
+    MFX_TRY(explain_lists(h, dt, n_targets, Z.get(), Y.get(), n_expl, oi, oc, ot));
+    if (host) {
+        if (n_expl) {
+            MFX_HIP(hipMemcpyAsync(expl_items, oi, sizeof(uint32_t) * nlist, hipMemcpyDeviceToHost, st));
+            MFX_HIP(hipMemcpyAsync(expl_contrib, oc, sizeof(float) * nlist, hipMemcpyDeviceToHost, st));
+        }
+        if (totals) MFX_HIP(hipMemcpyAsync(totals, ot, sizeof(float) * npair, hipMemcpyDeviceToHost, st));
+    }
+    MFX_HIP(hipStreamSynchronize(st));
+    const auto t3 = clk::now();
+    expl_s_[0] = std::chrono::duration<double>(t1 - t0).count();
+    expl_s_[1] = std::chrono::duration<double>(t2 - t1).count();
+    expl_s_[2] = std::chrono::duration<double>(t3 - t2).count();
+    return MFX_OK;
+}
+
 int Recommender::fold_solve(int64_t nusers, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val, const float* W_init,
                             float* W_out, int32_t* sweeps_done, int32_t n_top, uint32_t* items, float* scores, mfx_memspace space) {
     MFX_REQUIRE(fold_model_ >= 0, "mfx_rec_fold_in: call mfx_rec_fold_in_setup, mfx_rec_fold_in_block_setup or mfx_rec_fold_in_block_setup_als first");
@@ -836,16 +951,9 @@ int Recommender::fold_solve(int64_t nusers, int64_t nnz, const uint32_t* ptr, co
     using clk = std::chrono::steady_clock;
     const auto t0 = clk::now();
     const uint32_t nu = (uint32_t) nusers, k = (uint32_t) k_;
-    // the query rows as one half-sweep over H, with the chunking of training: build() checks the pointers on the host
-    // and every index < cols on the device; then the exclusion check of mfx_rec_create (ids non-decreasing in a row)
     AlsHalf h;
-    MFX_TRY(h.build(nu, (uint64_t) nnz, (uint32_t) cols_, ptr, idx, val, space, kAlsChunk, st));
-    MFX_TRY(check_csr(h.ptr.get(), h.idx.get(), nu, (uint32_t) cols_, (uint64_t) nnz, "mfx_rec_fold_in: ", "ptr", st));
+    MFX_TRY(fold_rows("mfx_rec_fold_in", nu, (uint64_t) nnz, ptr, idx, val, space, h));
     const bool by_blocks = fold_model_ == kFoldBlock || fold_model_ == kFoldBlockAls;
-    if (fold_model_ == MFX_FOLD_IMPLICIT || fold_model_ == kFoldBlock)
-        MFX_TRY(ials_check_values(h.val.get(), h.nnz, fold_alpha_, "mfx_rec_fold_in: value", st));
-    else if (fold_model_ == kFoldBlockAls)
-        MFX_TRY(als_check_finite(h.val.get(), h.nnz, "mfx_rec_fold_in: value", st));
     const auto t1 = clk::now();
 
     DevBuf<float> Y, ws, wq, rho;

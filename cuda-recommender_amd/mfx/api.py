@@ -1252,6 +1252,92 @@ class Recommender:
         return {"cutoffs": cuts, "hr": col(0), "precision": col(1), "recall": col(2), "ndcg": col(3), "mrr": mrr.value,
                 "auc": auc.value, "users": int(kept.value), "auc_users": int(auc_kept.value)}
 
+    def explain(self, rows, targets, n_expl: int = 10, on_device: bool = False, return_W: bool = False, return_Z: bool = False,
+                max_ws_bytes: int = 1 << 30) -> dict:
+        """Why the target items score what they score for fold-in users (mfx_rec_explain): the score of target t for the row
+        q splits over the row's own entries, <h_t, w_q> = sum_e b_e <h_e, A_q^-1 h_t>.  After fold_in_setup with MFX_FOLD_ALS,
+        MFX_FOLD_CCD or MFX_FOLD_IMPLICIT (alpha0= / nu= included); the explanation is of the fold-in row of the given
+        interactions, not of a row of this handle's W.
+        rows: as for fold_in.  targets [U, T], 1 <= T <= 64: item ids, 0xFFFFFFFF (or -1 in a signed array or tensor) = padding, so
+        the items of fold_in(rows, n_top) can be passed as they are.  Returns {"items" [U, T, n_expl]: the row's entries
+        (r > 0 only under the implicit models) by contribution descending, then position in the row, padded with 0xFFFFFFFF;
+        "contrib" [U, T, n_expl] float32, padded with -inf; "totals" [U, T]: the score fold_in reports for the target, -inf
+        for padding; "W" [U, k] with return_W, "Z" [U, T, k] = A^-1 h_target with return_Z}.  Tensors in, or on_device=True:
+        tensors out (items as int32 holding the uint32 ids).  The batch is cut into consecutive pieces whose Z workspace
+        (4 k T bytes per user) stays under max_ws_bytes; a row's result does not depend on the cut."""
+        ptr, idx, val = (rows.csr_row_ptr, rows.csr_col_idx, rows.csr_val) if hasattr(rows, "csr_row_ptr") else rows
+        if len(ptr.shape) != 1 or ptr.shape[0] < 1 or idx.shape != val.shape:
+            raise ValueError("rows: ptr [U + 1], idx [nnz], val [nnz]")
+        n, n_expl = int(ptr.shape[0]) - 1, int(n_expl)
+        if len(targets.shape) != 2 or int(targets.shape[0]) != n:
+            raise ValueError(f"targets must be [{n}, T]")
+        nt, k = int(targets.shape[1]), self.k
+        dev_in = any(_is_dev(a) for a in (ptr, idx, val, targets)) or on_device
+        step = max(1, int(max_ws_bytes) // max(1, 4 * k * nt))
+        fn = L.lib().mfx_rec_explain
+        if dev_in:
+            import torch
+            dev = torch.device("cuda", self.device)
+
+            def put(a, dt):
+                if not _is_dev(a):
+                    a = np.ascontiguousarray(a, dt)
+                    a = torch.from_numpy(a.view(np.int32) if dt == np.uint32 else a)
+                a = a.to(dev).contiguous()
+                assert a.element_size() == 4, "query tensors: 32-bit"
+                return a
+            ptr, idx, val, targets = put(ptr, np.uint32), put(idx, np.uint32), put(val, np.float32), put(targets, np.uint32)
+            new = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
+            out = {"items": new((n, nt, n_expl), torch.int32), "contrib": new((n, nt, n_expl), torch.float32),
+                   "totals": new((n, nt), torch.float32)}
+            if return_W:
+                out["W"] = new((n, k), torch.float32)
+            if return_Z:
+                out["Z"] = new((n, nt, k), torch.float32)
+            hp = (ptr.cpu().numpy().view(np.uint32).astype(np.int64)) if n > step else None
+            p = lambda t: C.c_void_p(int(t.data_ptr())) if t is not None and t.numel() else None
+            space = L.MFX_DEVICE
+        else:
+            ptr, idx = np.ascontiguousarray(ptr, np.uint32), np.ascontiguousarray(idx, np.uint32)
+            val, targets = np.ascontiguousarray(val, np.float32), np.asarray(targets)
+            if targets.dtype == np.int32:  # (the uint32 bits, as in an int32 tensor: -1 is the padding)
+                targets = np.ascontiguousarray(targets).view(np.uint32)
+            elif targets.dtype != np.uint32:
+                t64 = targets.astype(np.int64)
+                if targets.dtype.kind not in "iu" or (t64.size and (t64.min() < -1 or t64.max() > 0xFFFFFFFF)):
+                    raise ValueError("targets: integer item ids, 0xFFFFFFFF or -1 for padding")
+                targets = (t64 & 0xFFFFFFFF).astype(np.uint32)
+            targets = np.ascontiguousarray(targets)
+            out = {"items": np.empty((n, nt, n_expl), np.uint32), "contrib": np.empty((n, nt, n_expl), np.float32),
+                   "totals": np.empty((n, nt), np.float32)}
+            if return_W:
+                out["W"] = np.empty((n, k), np.float32)
+            if return_Z:
+                out["Z"] = np.empty((n, nt, k), np.float32)
+            hp = ptr.astype(np.int64)
+            p = lambda a: _vp(a) if a is not None and a.size else None
+            space = L.MFX_HOST
+        for u0 in range(0, max(n, 1), step):
+            u1 = min(n, u0 + step)
+            if u0 == 0 and u1 == n:
+                pp, lo, hi = ptr, 0, int(idx.shape[0])
+            else:
+                lo, hi = int(hp[u0]), int(hp[u1])
+                pp = ptr[u0:u1 + 1] - ptr[u0]
+                pp = pp.contiguous() if dev_in else np.ascontiguousarray(pp)
+            cut = lambda key: out[key][u0:u1] if key in out else None
+            L.check(fn(self.handle, u1 - u0, hi - lo, p(pp), p(idx[lo:hi]), p(val[lo:hi]), nt, p(targets[u0:u1]), n_expl,
+                       p(cut("items")), p(cut("contrib")), p(cut("totals")), p(cut("W")), p(cut("Z")), space))
+        return out
+
+    def explain_times(self) -> dict:
+        """Seconds of the last mfx_rec_explain call by phase (mfx_rec_explain_times): {"build": host build and checks,
+        "solve": the rows and the further right-hand sides, "contrib": totals, contributions and selection}.  After an
+        explain() that cut its batch: of the last piece."""
+        out = (C.c_double * 3)()
+        L.check(L.lib().mfx_rec_explain_times(self.handle, out))
+        return {"build": out[0], "solve": out[1], "contrib": out[2]}
+
     def fold_in_times(self) -> dict:
         """Seconds of the last fold_in call by phase (mfx_rec_fold_in_times): {"build", "solve", "score"}."""
         out = (C.c_double * 3)()

@@ -424,6 +424,46 @@ int mfx_rec_fold_in_warm(mfx_rec_t r, int64_t nusers, int64_t nnz, const uint32_
 /* Wall-clock seconds of the last mfx_rec_fold_in / mfx_rec_fold_in_warm on r, each phase ending in a stream synchronisation: [0] host build
  * (query upload, checks, the host-side split into work items), [1] solve, [2] score (packing, top-N, copies out). */
 int mfx_rec_fold_in_times(mfx_rec_t r, double seconds[3]);
+/* Why an item scores what it scores for a fold-in user: the score split over the user's own interactions.
+ * The fold-in row is w = A^-1 sum_e b_e h_e over the entries e = (item j_e, value r_e) of the query row, so the score of a
+ * target item i is <h_i, w> = sum_e b_e <h_e, A^-1 h_i>.  The explanation is of the fold-in row of the given interactions,
+ * not of a row of the handle's W.
+ * Valid after mfx_rec_fold_in_setup with MFX_FOLD_ALS, MFX_FOLD_CCD or MFX_FOLD_IMPLICIT, or mfx_rec_fold_in_setup_reg.
+ * MFX_ERR_INVALID (the handle stays usable) before any setup, after MFX_FOLD_ALS_EXACT (its rows are not the bits of the
+ * MFMA system: use MFX_FOLD_ALS) and after any block setup (a sweep is not a solve: the split does not hold).
+ * Query rows ptr / idx / val: as for mfx_rec_fold_in, with the same checks.  targets [nusers][n_targets]: item ids below
+ * cols, or 0xFFFFFFFF = padding (checked on the device), so the padded `items` of mfx_rec_fold_in may be passed as they
+ * are; a target may repeat and may be one of the row's own items.  The exclusion matrix and the item filter play no part.
+ * 1 <= n_targets <= 64, 0 <= n_expl <= 64 (0: expl_items / expl_contrib are not read), nusers = 0: MFX_OK, nothing touched.
+ *   system A of the row and weight b_e of an entry, per setup:
+ *     MFX_FOLD_ALS       sum h h^T + lambda I                     b_e = r_e                          every entry counts
+ *     MFX_FOLD_CCD       sum h h^T + fp32(lambda n) I             b_e = r_e                          every entry counts
+ *     MFX_FOLD_IMPLICIT  G + sum w_e h h^T, w_e = fp32(alpha r_e)  b_e = fp32(1 + w_e)                r_e > 0 counts
+ *     _setup_reg         G0 + rho I + sum w_e h h^T               b_e = fp32(alpha0 + w_e)           r_e > 0 counts
+ *   W_out [nusers][k] or NULL: the fold-in row, bit for bit what mfx_rec_fold_in returns for the row under the same
+ *     setup (an empty row: 0).
+ *   totals [nusers][n_targets] or NULL: the score chain of mfx_rec_query over (W_out[q], H[target]), bit for bit -- what
+ *     mfx_rec_fold_in reports for that item; -INFINITY for a padding target.
+ *   Z_out [nusers][n_targets][k] or NULL: z = A^-1 h_target by the factor L that gave W_out[q] and the same forward and
+ *     backward substitution, one more right-hand side per target; 0 for a padding target and for an empty row.
+ *   contribution of entry e to target t: d = the fmaf chain over c = 0 .. k-1 ascending from +0 of Z[q][t][c] * H[j_e][c]
+ *     (H: the handle's own bits), c_e = fp32(b_e * d), one rounding: bit-determined by the bits of Z_out.
+ *   expl_items / expl_contrib [nusers][n_targets][n_expl]: the counting entries of the row by c_e descending, then by
+ *     position in the row ascending (-0 == +0; a NaN contribution is dropped), padded with (0xFFFFFFFF, -INFINITY); two
+ *     entries with the same item id are two entries; every slot of a padding target is padding.
+ * A slot's results do not depend on the batch, its order, the memory space or the factor layout.  A system that is not
+ * positive definite is treated as mfx_rec_fold_in treats it (the row and what derives from it are not finite).
+ * Device workspace of a call: 4 k n_targets bytes per slot for Z, what mfx_rec_fold_in takes for the same rows, the lists
+ * (8 n_targets n_expl bytes per slot when `space` is MFX_HOST) and, when a row is longer than 2048 entries, two partial
+ * lists per 2048 entries of the batch and target (16 n_targets n_expl bytes per 2048 entries).  The caller cuts very
+ * large batches (mfx.Recommender.explain does, by max_ws_bytes). */
+int mfx_rec_explain(mfx_rec_t r, int64_t nusers, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val,
+                    int32_t n_targets, const uint32_t* targets, int32_t n_expl, uint32_t* expl_items, float* expl_contrib,
+                    float* totals, float* W_out, float* Z_out, mfx_memspace space);
+/* Wall-clock seconds of the last mfx_rec_explain on r, each phase ending in a stream synchronisation: [0] host build and
+ * checks (rows and targets), [1] solve (the row and the n_targets further right-hand sides), [2] totals, contributions,
+ * selection and the copies out. */
+int mfx_rec_explain_times(mfx_rec_t r, double seconds[3]);
 /* Item filter: keep [cols] bytes in `space`, non-zero = the item may be returned; NULL removes the filter.  Copied.
  * Applies to every later mfx_rec_query, mfx_rec_fold_in, mfx_rec_fold_in_warm and mfx_rec_similar on r until replaced:
  * the result is the unfiltered ranking with the filtered items removed and the list refilled, score bits unchanged
