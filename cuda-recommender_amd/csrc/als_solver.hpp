@@ -131,6 +131,29 @@ int als_check_finite(const float* d_val, uint64_t n, const char* what, hipStream
 int als_block_half_op(int64_t nseg, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val, int64_t nrows_x,
                       const float* X, const float* Y_in, float* Y_out, int64_t k, int32_t block, float lambda, int32_t reg, int device);
 
+// Fold-in by preconditioned conjugate gradients (rec_foldin_cg.hip; mfx_rec_fold_in_cg_setup): every row's system
+// is the fixed base plus a matrix of the rank of the row, so CG preconditioned by the inverse of the base ends after n + 1 steps
+// on a row of n entries.  reg 0: the implicit objective, A = G + sum_e w_e h_e h_e^T with G = H^T H + lambda I as ialsb_gramian
+// builds it and Minv a symmetric fp32 approximation of G^-1 (both [k][k], device); reg 1 / 2: the explicit objective with
+// rho = lambda / fp32(lambda * n) for a row of n entries, no G, the identity as preconditioner.
+struct FoldCg {
+    int32_t reg = 0;
+    float lambda = 0.f, alpha = 0.f;
+    const float* G = nullptr;
+    const float* Minv = nullptr;
+    int32_t steps = 1;  // the most steps a row gets
+    float tol = 0.f;    // > 0: a row is frozen once |b - A y| <= tol |b| (2-norms, fp32), tested on the start row too
+};
+// Minv [k][k] (host) from G [k][k] (host, symmetric): Cholesky and inverse in fp64 in a fixed loop order, rounded to fp32, the
+// upper triangle mirrored.  MFX_ERR_INVALID when G is not positive definite.
+int foldcg_inverse(const float* G, uint32_t k, float* Minv);
+// Up to m.steps steps in place on Y [h.nseg][k] over X [x_rows + 1][k] (last row zeros).  warm: Y holds the start rows, else
+// Y must be zero.  A row without entries or with b = 0 is zero and counts 0 steps.  tol = 0: nothing is read back; tol > 0: the
+// host reads one counter per step and stops when every row is frozen.  counts: device [h.nseg] (steps applied) or NULL.
+// *fail counts the rows that met <p, A p> < 0 or a non-finite one (they come back as NaN).
+int foldcg_launch(const AlsHalf& h, const float* X, uint32_t x_rows, uint32_t k, const FoldCg& m, float* Y, bool warm, int32_t* counts,
+                  uint32_t* fail, hipStream_t st);
+
 class AlsSolver {
 public:
     static int create(AlsSolver** out, const mfx_csx* R, const mfx_coo* T, const mfx_params* p,

@@ -610,6 +610,12 @@ int mfx_rec_fold_in_block_setup_als(mfx_rec_t r, float lambda, int32_t reg, int3
         return r->impl->fold_in_block_setup_als(lambda, reg, block, sweeps, tol);
     });
 }
+int mfx_rec_fold_in_cg_setup(mfx_rec_t r, int model, float lambda, float alpha, int32_t steps, float tol) {
+    return guarded("mfx_rec_fold_in_cg_setup", [&]() -> int {
+        MFX_REQUIRE(r && r->impl, "null recommender");
+        return r->impl->fold_in_cg_setup(model, lambda, alpha, steps, tol);
+    });
+}
 int mfx_rec_fold_in_warm(mfx_rec_t r, int64_t nusers, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val,
                          const float* W_init, float* W_out, int32_t* sweeps_done, int32_t n_top, uint32_t* items, float* scores,
                          mfx_memspace space) {

@@ -28,7 +28,9 @@
 // (the same bits the scores use), packs the solved rows like W and runs the same top-N pass with the query's own rows
 // as the exclusion.  Above rank 128 (mfx_rec_fold_in_block_setup) the rows are solved by the block subspace sweeps of
 // ials_block.hip instead, repeated up to a sweep count with a stop per row (ialsb_fold_launch); the explicit objectives of
-// MFX_FOLD_ALS / MFX_FOLD_CCD the same way after mfx_rec_fold_in_block_setup_als (alsb_fold_launch).
+// MFX_FOLD_ALS / MFX_FOLD_CCD the same way after mfx_rec_fold_in_block_setup_als (alsb_fold_launch).  After
+// mfx_rec_fold_in_cg_setup the rows are solved by conjugate gradients preconditioned by the inverse of the base Gramian
+// (rec_foldin_cg.hip, foldcg_launch), at any rank up to 1024: a solve with a residual bound, not a sweep.
 //
 // Item-to-item similarity (mfx_rec_similar) and the item filter (mfx_rec_set_item_filter) are one per-item fp32 factor on
 // the accumulator before the compare (mfx_rec_topn<KC, true>): an inverse norm for the cosine, 1 / NaN for kept / dropped
@@ -689,6 +691,7 @@ int Recommender::fold_setup_begin(bool drop_g, bool drop_b) {
     fold_robj_ = false;
     if (drop_g) fold_g_.release();     // (what a direct setup kept)
     if (drop_b) fold_b_ = IalsBlock();  // (what a block setup kept)
+    fold_minv_.release();               // (what a cg setup kept)
     const size_t nh = ((size_t) cols_ + 1) * k_;
     if (!hx_.get()) MFX_TRY(hx_.alloc(nh));
     hipLaunchKernelGGL(mfx_rec_unpack_h, dim3(grid_for(nh)), dim3(256), 0, st_, hp_.get(), (uint32_t) cols_, (int) k_, 2 * kc_, nch_,
@@ -737,6 +740,42 @@ int Recommender::fold_in_block_setup(float lambda, float alpha, int32_t block, i
     fold_lambda_ = lambda;
     fold_alpha_ = alpha;
     fold_sweeps_ = sweeps;
+    fold_tol_ = tol;
+    return MFX_OK;
+}
+
+int Recommender::fold_in_cg_setup(int model, float lambda, float alpha, int32_t steps, float tol) {
+    const char* fn = "mfx_rec_fold_in_cg_setup";
+    MFX_REQUIRE(model != MFX_FOLD_ALS_EXACT, "%s: model MFX_FOLD_ALS_EXACT is an order of operations, not an objective; set up MFX_FOLD_ALS", fn);
+    MFX_REQUIRE(model == MFX_FOLD_ALS || model == MFX_FOLD_CCD || model == MFX_FOLD_IMPLICIT, "%s: unknown model %d", fn, model);
+    MFX_REQUIRE(k_ <= (int64_t) kIalsBlockMaxRank, "%s: conjugate gradients solve ranks k <= %u (the handle has k = %lld)", fn, kIalsBlockMaxRank,
+                (long long) k_);
+    MFX_TRY(check_fold_lambda(fn, lambda));
+    MFX_REQUIRE(std::isfinite(alpha) && alpha >= 0.f, "%s: alpha = %g (finite and >= 0 required)", fn, (double) alpha);
+    MFX_REQUIRE(steps >= 1 && steps <= 1024, "%s: steps = %d (1 <= steps <= 1024)", fn, steps);
+    MFX_REQUIRE(std::isfinite(tol) && tol >= 0.f, "%s: tol = %g (finite and >= 0 required)", fn, (double) tol);
+    const bool implicit = model == MFX_FOLD_IMPLICIT;
+    MFX_TRY(fold_setup_begin(!implicit, true));
+    hipStream_t st = st_;
+    if (implicit) {  // G as the block trainer builds it (ialsb_gramian); Minv ~ G^-1 in fp64 on the host, rounded
+        const uint32_t k = (uint32_t) k_;
+        IalsBlock gb;
+        MFX_TRY(gb.alloc(k, std::min<uint32_t>(ialsb_default_block(k), k), (uint32_t) cols_, 0, 0, 0, st));
+        MFX_TRY(ialsb_gramian(gb, hx_.get(), (uint32_t) cols_, lambda, st));
+        std::vector<float> g((size_t) k * k), minv((size_t) k * k);
+        MFX_HIP(hipMemcpyAsync(g.data(), gb.G.get(), sizeof(float) * g.size(), hipMemcpyDeviceToHost, st));
+        MFX_HIP(hipStreamSynchronize(st));
+        MFX_TRY(foldcg_inverse(g.data(), k, minv.data()));
+        MFX_TRY(fold_minv_.alloc(minv.size()));
+        MFX_TRY(fold_minv_.upload(minv.data(), minv.size(), MFX_HOST, st));
+        fold_g_ = std::move(gb.G);
+    }
+    MFX_HIP(hipStreamSynchronize(st));
+    fold_model_ = kFoldCg;
+    fold_cg_model_ = model;
+    fold_lambda_ = lambda;
+    fold_alpha_ = implicit ? alpha : 0.f;
+    fold_sweeps_ = steps;
     fold_tol_ = tol;
     return MFX_OK;
 }
@@ -816,8 +855,8 @@ int Recommender::fold_in(int64_t nusers, int64_t nnz, const uint32_t* ptr, const
 
 int Recommender::fold_in_warm(int64_t nusers, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val, const float* W_init,
                               float* W_out, int32_t* sweeps_done, int32_t n_top, uint32_t* items, float* scores, mfx_memspace space) {
-    MFX_REQUIRE(fold_model_ == kFoldBlock || fold_model_ == kFoldBlockAls,
-                "mfx_rec_fold_in_warm: call mfx_rec_fold_in_block_setup or mfx_rec_fold_in_block_setup_als first");
+    MFX_REQUIRE(fold_model_ == kFoldBlock || fold_model_ == kFoldBlockAls || fold_model_ == kFoldCg,
+                "mfx_rec_fold_in_warm: call mfx_rec_fold_in_block_setup, mfx_rec_fold_in_block_setup_als or mfx_rec_fold_in_cg_setup first");
     return fold_solve(nusers, nnz, ptr, idx, val, W_init, W_out, sweeps_done, n_top, items, scores, space);
 }
 
@@ -830,9 +869,10 @@ int Recommender::fold_rows(const char* fn, uint32_t nu, uint64_t nnz, const uint
     const std::string who = std::string(fn) + ": ", what = who + "value";
     MFX_TRY(h.build(nu, nnz, (uint32_t) cols_, ptr, idx, val, space, kAlsChunk, st));
     MFX_TRY(check_csr(h.ptr.get(), h.idx.get(), nu, (uint32_t) cols_, nnz, who.c_str(), "ptr", st));
-    if (fold_model_ == MFX_FOLD_IMPLICIT || fold_model_ == kFoldBlock)
+    const bool cg_implicit = fold_model_ == kFoldCg && fold_cg_model_ == MFX_FOLD_IMPLICIT;
+    if (fold_model_ == MFX_FOLD_IMPLICIT || fold_model_ == kFoldBlock || cg_implicit)
         MFX_TRY(ials_check_values(h.val.get(), h.nnz, fold_alpha_, what.c_str(), st));
-    else if (fold_model_ == kFoldBlockAls)
+    else if (fold_model_ == kFoldBlockAls || fold_model_ == kFoldCg)
         MFX_TRY(als_check_finite(h.val.get(), h.nnz, what.c_str(), st));
     return MFX_OK;
 }
@@ -846,6 +886,9 @@ int Recommender::explain(int64_t nusers, int64_t nnz, const uint32_t* ptr, const
     MFX_REQUIRE(fold_model_ >= 0, "%s: call mfx_rec_fold_in_setup (MFX_FOLD_ALS, MFX_FOLD_CCD, MFX_FOLD_IMPLICIT) or mfx_rec_fold_in_setup_reg first", fn);
     MFX_REQUIRE(fold_model_ != MFX_FOLD_ALS_EXACT,
                 "%s: the rows of MFX_FOLD_ALS_EXACT are not the bits of the MFMA system whose factor the explanation uses; set up MFX_FOLD_ALS", fn);
+    MFX_REQUIRE(fold_model_ != kFoldCg,
+                "%s: not after mfx_rec_fold_in_cg_setup (the split over the entries needs the factor of a closed-form solve); set up "
+                "mfx_rec_fold_in_setup or mfx_rec_fold_in_setup_reg on a handle of rank <= 128", fn);
     MFX_REQUIRE(fold_model_ != kFoldBlock && fold_model_ != kFoldBlockAls,
                 "%s: not after a block setup (a sweep is not a solve, the split over the entries does not hold); set up mfx_rec_fold_in_setup "
                 "or mfx_rec_fold_in_setup_reg on a handle of rank <= 128", fn);
@@ -937,7 +980,8 @@ int Recommender::explain(int64_t nusers, int64_t nnz, const uint32_t* ptr, const
 
 int Recommender::fold_solve(int64_t nusers, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val, const float* W_init,
                             float* W_out, int32_t* sweeps_done, int32_t n_top, uint32_t* items, float* scores, mfx_memspace space) {
-    MFX_REQUIRE(fold_model_ >= 0, "mfx_rec_fold_in: call mfx_rec_fold_in_setup, mfx_rec_fold_in_block_setup or mfx_rec_fold_in_block_setup_als first");
+    MFX_REQUIRE(fold_model_ >= 0, "mfx_rec_fold_in: call mfx_rec_fold_in_setup, mfx_rec_fold_in_block_setup, mfx_rec_fold_in_block_setup_als or "
+                "mfx_rec_fold_in_cg_setup first");
     MFX_REQUIRE(nusers >= 0 && nusers < (int64_t) 0xFFFFFFFFll, "mfx_rec_fold_in: bad nusers %lld", (long long) nusers);
     MFX_REQUIRE(nnz >= 0 && nnz < (int64_t) 0xFFFF0000ll, "mfx_rec_fold_in: bad nnz %lld", (long long) nnz);
     MFX_REQUIRE(n_top >= 0 && n_top <= kMaxTop, "mfx_rec_fold_in: n_top must be in [0, %d] (got %d)", kMaxTop, n_top);
@@ -953,7 +997,7 @@ int Recommender::fold_solve(int64_t nusers, int64_t nnz, const uint32_t* ptr, co
     const uint32_t nu = (uint32_t) nusers, k = (uint32_t) k_;
     AlsHalf h;
     MFX_TRY(fold_rows("mfx_rec_fold_in", nu, (uint64_t) nnz, ptr, idx, val, space, h));
-    const bool by_blocks = fold_model_ == kFoldBlock || fold_model_ == kFoldBlockAls;
+    const bool by_blocks = fold_model_ == kFoldBlock || fold_model_ == kFoldBlockAls || fold_model_ == kFoldCg;  // (no als_ws_floats slots)
     const auto t1 = clk::now();
 
     DevBuf<float> Y, ws, wq, rho;
@@ -984,6 +1028,17 @@ int Recommender::fold_solve(int64_t nusers, int64_t nnz, const uint32_t* ptr, co
                 MFX_TRY(alsb_fold_launch(fold_b_, h, hx_.get(), x_rows, Y.get(), fold_lambda_, fold_reg_, fold_sweeps_, fold_tol_,
                                          counts.get(), spd_fail.get(), st));
             break;
+        case kFoldCg: {
+            if (W_init) MFX_TRY(Y.upload(W_init, (size_t) nu * k, space, st));
+            if (sweeps_done) MFX_TRY(counts.alloc(nu));
+            FoldCg m;
+            m.reg = fold_cg_model_ == MFX_FOLD_IMPLICIT ? 0 : fold_cg_model_ == MFX_FOLD_ALS ? 1 : 2;
+            m.lambda = fold_lambda_; m.alpha = fold_alpha_;
+            m.G = fold_g_.get(); m.Minv = fold_minv_.get();
+            m.steps = fold_sweeps_; m.tol = fold_tol_;
+            MFX_TRY(foldcg_launch(h, hx_.get(), x_rows, k, m, Y.get(), W_init != nullptr, counts.get(), spd_fail.get(), st));
+            break;
+        }
         case MFX_FOLD_ALS:
             MFX_TRY(als_half_launch(h, hx_.get(), x_rows, Y.get(), k, fold_lambda_, ws.get(), spd_fail.get(), st));
             break;

@@ -28,9 +28,12 @@ public:
     // (mfx_rec_fold_in_setup_reg: k <= 128; mfx_rec_fold_in_block_setup_reg: block sweeps)
     int fold_in_setup_reg(float lambda, float alpha, float alpha0, float nu);
     int fold_in_block_setup_reg(float lambda, float alpha, float alpha0, float nu, int32_t block, int32_t sweeps, float tol);
+    // by preconditioned conjugate gradients (mfx_rec_fold_in_cg_setup, rec_foldin_cg.hip): MFX_FOLD_ALS / _CCD / _IMPLICIT at
+    // any k <= 1024, up to `steps` steps per row, a row stops once |b - A y| <= tol |b|
+    int fold_in_cg_setup(int model, float lambda, float alpha, int32_t steps, float tol);
     int fold_in(int64_t nusers, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val, float* W_out,
                 int32_t n_top, uint32_t* items, float* scores, mfx_memspace space);
-    // mfx_rec_fold_in_warm: after a block setup only; W_init [nusers][k] / sweeps_done [nusers] in `space`, or NULL
+    // mfx_rec_fold_in_warm: after a block or cg setup only; W_init [nusers][k] / sweeps_done [nusers] in `space`, or NULL
     int fold_in_warm(int64_t nusers, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val, const float* W_init,
                      float* W_out, int32_t* sweeps_done, int32_t n_top, uint32_t* items, float* scores, mfx_memspace space);
     // mfx_rec_set_item_filter / mfx_rec_similar_setup / mfx_rec_item_norms / mfx_rec_similar
@@ -76,7 +79,7 @@ private:
     // takes a forced count as given (empty slices included: they merge as padding), as it always did.
     int pick_slices(int forced, int64_t blocks, int cap) const;
     // What every fold-in setup starts with: the device, fold_model_ = -1 until the setup is through, what another kind of
-    // setup kept (fold_g_ / fold_b_) dropped as asked, hx_ from the tiles.
+    // setup kept (fold_g_ / fold_b_) dropped as asked and fold_minv_ always (the cg setup builds it afterwards), hx_ from the tiles.
     int fold_setup_begin(bool drop_g, bool drop_b);
     // fac_keep_ (when keep is set) and fac_cos_ (after similar_setup) from the device filter bytes keep (NULL: no filter)
     int build_facs(const uint8_t* keep);
@@ -116,7 +119,11 @@ private:
     // fold-in by block sweeps: G = H^T H + lambda I, H block-major and the diagonal blocks of G, all packed at setup; P, Z,
     // the scores and the split-segment slots live for one query
     // (kFoldBlockAls: the explicit objective -- no G, only H block-major)
-    static constexpr int kFoldBlock = 100, kFoldBlockAls = 101;
+    // (kFoldCg: conjugate gradients on the objective fold_cg_model_ -- fold_g_ = G and fold_minv_ ~ G^-1 [k_][k_] for the
+    // implicit one, nothing but hx_ for the explicit ones; fold_sweeps_ / fold_tol_ hold the step cap and the residual bound)
+    static constexpr int kFoldBlock = 100, kFoldBlockAls = 101, kFoldCg = 102;
+    int fold_cg_model_ = 0;
+    DevBuf<float> fold_minv_;
     int32_t fold_reg_ = 0;
     IalsBlock fold_b_;
     int32_t fold_sweeps_ = 0;

@@ -141,6 +141,7 @@ SIGNATURES = {
     "mfx_rec_fold_in_block_setup_reg": (C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int32, C.c_int32,
                                                   C.c_float]),
     "mfx_rec_fold_in_block_setup_als": (C.c_int, [C.c_void_p, C.c_float, C.c_int32, C.c_int32, C.c_int32, C.c_float]),
+    "mfx_rec_fold_in_cg_setup": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_int32, C.c_float]),
     "mfx_rec_fold_in_warm": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int]),
     "mfx_rec_fold_in_times": (C.c_int, [C.c_void_p, f64p]),

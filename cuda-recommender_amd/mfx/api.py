@@ -944,8 +944,8 @@ class Recommender:
         """Prepares fold-in by block subspace sweeps (mfx_rec_fold_in_block_setup), the method of ImplicitAlsSolver(block=...):
         any k <= 1024.  block 0 = chosen from k, else 1..128; a row gets at most `sweeps` sweeps (1..1024), exactly `sweeps`
         with tol = 0, else it stops once a sweep moves it by at most tol of its largest entry.  A cold start at large alpha
-        converges slowly for short rows: choose sweeps / tol for the data, or pass W_init to fold_in.  The objective of
-        ImplicitAlsSolver(block=, alpha0=, nu=): fold_in_block_setup_reg."""
+        converges slowly for short rows: choose sweeps / tol for the data, pass W_init to fold_in, or use fold_in_cg_setup
+        (a solve with a residual bound).  The objective of ImplicitAlsSolver(block=, alpha0=, nu=): fold_in_block_setup_reg."""
         L.check(L.lib().mfx_rec_fold_in_block_setup(self.handle, float(lam), float(alpha), int(block), int(sweeps), float(tol)))
 
     def fold_in_block_setup_reg(self, lam: float, alpha: float, alpha0: float = 1.0, nu: float = 0.0, block: int = 0, sweeps: int = 8,
@@ -961,8 +961,16 @@ class Recommender:
         """Prepares fold-in by block subspace sweeps on the explicit objective (mfx_rec_fold_in_block_setup_als), the method
         of AlsSolver(block=...): any k <= 1024, the objective of MFX_FOLD_ALS, or with count_reg of MFX_FOLD_CCD.  block,
         sweeps and tol as in fold_in_block_setup.  A sweep is not a solve: with more than one block choose sweeps / tol
-        for the data, or pass W_init to fold_in."""
+        for the data, pass W_init to fold_in, or use fold_in_cg_setup (a solve with a residual bound)."""
         L.check(L.lib().mfx_rec_fold_in_block_setup_als(self.handle, float(lam), 1 if count_reg else 0, int(block), int(sweeps), float(tol)))
+
+    def fold_in_cg_setup(self, model: int, lam: float, alpha: float = 0.0, steps: int = 64, tol: float = 1e-5):
+        """Prepares fold-in by preconditioned conjugate gradients (mfx_rec_fold_in_cg_setup): model MFX_FOLD_ALS / MFX_FOLD_CCD /
+        MFX_FOLD_IMPLICIT at any k <= 1024.  A row gets at most `steps` steps (1..1024) and stops once its residual is at
+        most tol of its right-hand side (2-norms; tol = 0: exactly `steps`); a row of n entries needs at most n + 1 steps
+        in exact arithmetic.  The implicit model inverts the k x k base Gramian on the host at setup.  fold_in afterwards
+        takes W_init and return_sweeps; the counts are steps."""
+        L.check(L.lib().mfx_rec_fold_in_cg_setup(self.handle, int(model), float(lam), float(alpha), int(steps), float(tol)))
 
     def fold_in(self, rows, n_top: int = 0, on_device: bool = False, W_init=None, return_sweeps: bool = False):
         """Solves one factor row per query user against this handle's H and recommends from it (mfx_rec_fold_in).
@@ -970,8 +978,9 @@ class Recommender:
         or GPU tensors (32-bit ids, float32 values).  Returns (items [U, n_top], scores [U, n_top], W [U, k]), the lists
         with each row's own items excluded (None, None when n_top = 0).  Tensors in, or on_device=True: everything
         stays on the device and the results are tensors (items as int32 holding the uint32 ids).
-        After fold_in_block_setup / fold_in_block_setup_als only (mfx_rec_fold_in_warm): W_init [U, k], numpy or a GPU tensor like the rows, is the
-        start row of every user (None: zeros), and return_sweeps=True appends the int32 sweep counts [U] to the result."""
+        After fold_in_block_setup / fold_in_block_setup_als / fold_in_cg_setup only (mfx_rec_fold_in_warm): W_init [U, k], numpy or a GPU
+        tensor like the rows, is the start row of every user (None: zeros), and return_sweeps=True appends the int32 sweep
+        counts [U] to the result (after fold_in_cg_setup: the step counts)."""
         ptr, idx, val = (rows.csr_row_ptr, rows.csr_col_idx, rows.csr_val) if hasattr(rows, "csr_row_ptr") else rows
         if len(ptr.shape) != 1 or ptr.shape[0] < 1 or idx.shape != val.shape:
             raise ValueError("rows: ptr [U + 1], idx [nnz], val [nnz]")

@@ -386,8 +386,8 @@ int mfx_rec_fold_in(mfx_rec_t r, int64_t nusers, int64_t nnz, const uint32_t* pt
  * row's bits never change again, and the loop ends when every row is frozen or `sweeps` is reached (the host reads one
  * counter per sweep).  A row's bits and its sweep count do not depend on the other rows of the batch.
  * A sweep is not a solve: from w = 0 the distance to the minimiser shrinks by a factor per sweep that depends on the row,
- * and at large alpha short rows are the slow ones (DESIGN.md has the table): choose sweeps / tol for the data, or pass
- * the row's previous factors as W_init.
+ * and at large alpha short rows are the slow ones (DESIGN.md has the table): choose sweeps / tol for the data, pass
+ * the row's previous factors as W_init, or set up mfx_rec_fold_in_cg_setup, which solves and bounds the residual.
  * The last successful setup of any kind decides what mfx_rec_fold_in does; after this one it is mfx_rec_fold_in_warm
  * with W_init = NULL and sweeps_done = NULL.  MFX_ERR_INVALID: block outside 0..128, sweeps outside 1..1024, tol < 0 or
  * not finite, lambda <= 0 or not finite, alpha < 0 or not finite. */
@@ -398,7 +398,8 @@ int mfx_rec_fold_in_block_setup(mfx_rec_t r, float lambda, float alpha, int32_t 
  * rows' current values: with tol = 0, S sweeps equal S chained calls bit for bit; tol > 0 freezes rows by the rule above.
  * With a single block (block >= k) one sweep is the exact solve; with more blocks a sweep is not a solve: from w = 0 the
  * distance to the minimiser shrinks by a factor per sweep that depends on the row (DESIGN.md has the sweep counts):
- * choose sweeps / tol for the data, or pass the row's previous factors as W_init.  Values: finite (checked on the device);
+ * choose sweeps / tol for the data, pass the row's previous factors as W_init, or set up mfx_rec_fold_in_cg_setup (a solve
+ * with a residual bound).  Values: finite (checked on the device);
  * zeros and negative values are entries like any other.
  * The last successful setup of the three kinds decides what mfx_rec_fold_in does; after this one it is
  * mfx_rec_fold_in_warm with W_init = NULL and sweeps_done = NULL.  MFX_ERR_INVALID: reg not 0 / 1, block outside 0..128,
@@ -413,11 +414,38 @@ int mfx_rec_fold_in_block_setup_als(mfx_rec_t r, float lambda, int32_t reg, int3
  * the regulariser as for mfx_ials_create_reg (rows = cols = the handle's cols). */
 int mfx_rec_fold_in_setup_reg(mfx_rec_t r, float lambda, float alpha, float alpha0, float nu);
 int mfx_rec_fold_in_block_setup_reg(mfx_rec_t r, float lambda, float alpha, float alpha0, float nu, int32_t block, int32_t sweeps, float tol);
+/* Fold-in by conjugate gradients preconditioned by the inverse of the base Gramian, at any 1 <= k <= 1024: a solve with a
+ * residual bound, not a sweep.  H is fixed, so the system of a row of n entries is a fixed base plus a matrix of rank n, and
+ * the method ends, in exact arithmetic, after at most n + 1 steps: short rows are the cheap ones.
+ * model: MFX_FOLD_ALS, MFX_FOLD_CCD or MFX_FOLD_IMPLICIT, the objectives of mfx_rec_fold_in_setup (MFX_FOLD_ALS_EXACT is an
+ * order of operations, not an objective: refused).  steps: 1..1024, the most steps a row gets.  tol >= 0, finite.
+ *   implicit:  A p = G p + sum_e w_e <h_e, p> h_e,  b = sum_e fp32(1 + w_e) h_e,  w_e = fp32(alpha r_e),  preconditioner Minv
+ *              over the entries with r_e > 0; G = H^T H + lambda I as mfx_ials_block_half builds it, Minv [k][k] its inverse
+ *              by Cholesky in fp64 on the host, rounded to fp32 and symmetric (setup time grows as k^3: README has it)
+ *   explicit:  A p = rho p + sum_e <h_e, p> h_e,  b = sum_e r_e h_e,  rho = lambda (ALS) or fp32(lambda n) (CCD), over every
+ *              entry, zeros and negative values included; no G, the preconditioner is the identity
+ * From y = the start row (0 for mfx_rec_fold_in), r = b - A y, z = Minv r, p = z, gamma = <r, z>, a step is q = A p,
+ * a = gamma / <p, q>, y += a p, r -= a q, [stop test], z = Minv r, gamma' = <r, z>, p = z + (gamma' / gamma) p.
+ * A row without counting entries or with b = 0 gets w = 0 and 0 steps whatever the start row holds.  tol > 0: a row is
+ * frozen once |r| <= tol |b| (2-norms, fp32); the test runs on the start row too, so a good W_init costs 0 steps, and the
+ * step that reaches the bound is counted.  tol = 0: every other row gets exactly `steps` unless gamma becomes exactly 0.
+ * A frozen row's bits never change again; the loop ends when every row is frozen or `steps` is reached (the host reads one
+ * counter per step when tol > 0).  <p, q> < 0 or not finite (the inputs were not finite): the row comes back as NaN;
+ * <p, q> exactly 0 (the direction of a row long converged underflowed) freezes the row like gamma = 0.
+ * No float atomics: a row's bits and step count do not depend on the other rows of the batch, their order, the memory
+ * space or the factor layout, and a row stopped after s steps has the bits of the same row run with steps = s, tol = 0.
+ * Afterwards mfx_rec_fold_in is the cold start and mfx_rec_fold_in_warm is valid (sweeps_done receives the steps); query
+ * checks, exclusion, item filter, scoring and padding are those of mfx_rec_fold_in.  Keeps H row-major and, for the
+ * implicit model, G and Minv.  The last successful setup of the four kinds decides what mfx_rec_fold_in does.
+ * MFX_ERR_INVALID (the handle keeps what it had): model unknown or MFX_FOLD_ALS_EXACT, steps outside 1..1024, tol < 0 or not
+ * finite, lambda <= 0 or not finite, alpha < 0 or not finite, k > 1024. */
+int mfx_rec_fold_in_cg_setup(mfx_rec_t r, int model, float lambda, float alpha, int32_t steps, float tol);
 /* mfx_rec_fold_in with a start row per user and the sweep counts.  W_init [nusers][k] or NULL (start from 0);
- * sweeps_done [nusers] or NULL: the sweeps applied to each row.  An empty row gives w = 0 and 0 sweeps whatever W_init
- * holds.  The query checks are those of MFX_FOLD_IMPLICIT (after mfx_rec_fold_in_block_setup_als: finite values).  Valid
- * only after mfx_rec_fold_in_block_setup or mfx_rec_fold_in_block_setup_als: MFX_ERR_INVALID after mfx_rec_fold_in_setup
- * or no setup, and the handle stays usable. */
+ * sweeps_done [nusers] or NULL: the sweeps applied to each row (after mfx_rec_fold_in_cg_setup: the steps).  An empty row
+ * gives w = 0 and 0 sweeps whatever W_init holds.  The query checks are those of MFX_FOLD_IMPLICIT (after
+ * mfx_rec_fold_in_block_setup_als and the explicit models of mfx_rec_fold_in_cg_setup: finite values).  Valid only after
+ * mfx_rec_fold_in_block_setup, mfx_rec_fold_in_block_setup_als or mfx_rec_fold_in_cg_setup: MFX_ERR_INVALID after
+ * mfx_rec_fold_in_setup or no setup, and the handle stays usable. */
 int mfx_rec_fold_in_warm(mfx_rec_t r, int64_t nusers, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val,
                          const float* W_init, float* W_out, int32_t* sweeps_done, int32_t n_top, uint32_t* items,
                          float* scores, mfx_memspace space);
@@ -430,7 +458,8 @@ int mfx_rec_fold_in_times(mfx_rec_t r, double seconds[3]);
  * not of a row of the handle's W.
  * Valid after mfx_rec_fold_in_setup with MFX_FOLD_ALS, MFX_FOLD_CCD or MFX_FOLD_IMPLICIT, or mfx_rec_fold_in_setup_reg.
  * MFX_ERR_INVALID (the handle stays usable) before any setup, after MFX_FOLD_ALS_EXACT (its rows are not the bits of the
- * MFMA system: use MFX_FOLD_ALS) and after any block setup (a sweep is not a solve: the split does not hold).
+ * MFMA system: use MFX_FOLD_ALS), after any block setup (a sweep is not a solve: the split does not hold) and after
+ * mfx_rec_fold_in_cg_setup (closed-form setups only: the split uses the factor of the row's system).
  * Query rows ptr / idx / val: as for mfx_rec_fold_in, with the same checks.  targets [nusers][n_targets]: item ids below
  * cols, or 0xFFFFFFFF = padding (checked on the device), so the padded `items` of mfx_rec_fold_in may be passed as they
  * are; a target may repeat and may be one of the row's own items.  The exclusion matrix and the item filter play no part.
