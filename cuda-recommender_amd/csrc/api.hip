@@ -632,6 +632,15 @@ int mfx_rec_explain(mfx_rec_t r, int64_t nusers, int64_t nnz, const uint32_t* pt
         return r->impl->explain(nusers, nnz, ptr, idx, val, n_targets, targets, n_expl, expl_items, expl_contrib, totals, W_out, Z_out, space);
     });
 }
+int mfx_rec_explain_cg(mfx_rec_t r, int64_t nusers, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val, int32_t n_targets,
+                       const uint32_t* targets, int32_t n_expl, uint32_t* expl_items, float* expl_contrib, float* totals, float* W_out,
+                       float* Z_out, int32_t* row_steps, int32_t* target_steps, mfx_memspace space) {
+    return guarded("mfx_rec_explain_cg", [&]() -> int {
+        MFX_REQUIRE(r && r->impl, "mfx_rec_explain_cg: null handle");
+        return r->impl->explain_cg(nusers, nnz, ptr, idx, val, n_targets, targets, n_expl, expl_items, expl_contrib, totals, W_out, Z_out,
+                                   row_steps, target_steps, space);
+    });
+}
 int mfx_rec_explain_times(mfx_rec_t r, double seconds[3]) {
     return guarded("mfx_rec_explain_times", [&]() -> int {
         MFX_REQUIRE(r && r->impl && seconds, "mfx_rec_explain_times: null argument");

@@ -606,7 +606,7 @@ int Recommender::query_candidates(int64_t nusers, const uint32_t* users, const u
     return MFX_OK;
 }
 
-int Recommender::explain_check_targets(const uint32_t* d_targets, size_t n, int32_t n_targets) {
+int Recommender::explain_check_targets(const char* fn, const uint32_t* d_targets, size_t n, int32_t n_targets) {
     DevBuf<unsigned long long> first;
     MFX_TRY(first.alloc(1));
     MFX_HIP(hipMemsetAsync(first.get(), 0xFF, sizeof(unsigned long long), st_));
@@ -615,7 +615,7 @@ int Recommender::explain_check_targets(const uint32_t* d_targets, size_t n, int3
     unsigned long long bad = ~0ull;
     MFX_HIP(hipMemcpyAsync(&bad, first.get(), sizeof(bad), hipMemcpyDeviceToHost, st_));
     MFX_HIP(hipStreamSynchronize(st_));
-    MFX_REQUIRE(bad == ~0ull, "mfx_rec_explain: target %llu of slot %llu is neither an item id in [0, %lld) nor the padding 0xFFFFFFFF",
+    MFX_REQUIRE(bad == ~0ull, "%s: target %llu of slot %llu is neither an item id in [0, %lld) nor the padding 0xFFFFFFFF", fn,
                 bad % (unsigned long long) n_targets, bad / (unsigned long long) n_targets, (long long) cols_);
     return MFX_OK;
 }
@@ -653,7 +653,7 @@ int Recommender::explain_lists(const AlsHalf& h, const uint32_t* d_targets, int3
     a.Z = Z; a.hx = hx_.get(); a.ptr = h.ptr.get(); a.idx = h.idx.get(); a.val = h.val.get(); a.targets = d_targets;
     a.piece_slot = piece_slot.get();
     a.k = (int) k_; a.nt = nt; a.n_expl = n_expl;
-    a.implicit = fold_model_ == MFX_FOLD_IMPLICIT;
+    a.implicit = fold_model_ == MFX_FOLD_IMPLICIT || (fold_model_ == kFoldCg && fold_cg_model_ == MFX_FOLD_IMPLICIT);
     a.alpha = fold_alpha_; a.alpha0 = fold_robj_ ? fold_alpha0_ : 1.f;
     a.part_stride = 2 * ((size_t) total / kCandChunk + 2) * n_expl;
     if (hi.nlong) {

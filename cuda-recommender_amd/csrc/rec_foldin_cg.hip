@@ -21,7 +21,7 @@
 #include <algorithm>
 #include <cmath>
 
-#include "als_solver.hpp"
+#include "rec_foldin_cg.hpp"
 
 namespace mfx {
 namespace {
@@ -29,13 +29,7 @@ namespace {
 using f32x16 = __attribute__((ext_vector_type(16))) float;
 using f32x4 = __attribute__((ext_vector_type(4))) float;
 
-constexpr int kGatherRows = 4;  // rows of H in flight per wavefront of the gather
-
-__device__ __forceinline__ float wave_sum(float v) {  // butterfly over the 64 lanes: the same value, in a fixed order, in every lane
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
+// (kGatherRows, wave_sum, row_rho: rec_foldin_cg.hpp)
 
 // MODE bit 0: S = sum_e c_e <h_e, v> h_e with v = V[seg]; bit 1: B = sum_e d_e h_e.  implicit: an entry counts when r_e > 0,
 // c_e = w_e = fp32(alpha r_e), d_e = fp32(1 + w_e); explicit: every entry counts, c_e = 1, d_e = r_e.  C = columns per lane.
@@ -184,11 +178,6 @@ __global__ __launch_bounds__(256) void k_foldcg_dense(const float* __restrict__ 
             }
         }
     }
-}
-
-// rho of a row: 0 = none (implicit: G carries lambda), 1 = lambda, 2 = fp32(lambda * n) for a row of n entries
-__device__ __forceinline__ float row_rho(int32_t reg, float lambda, const uint32_t* __restrict__ ptr, uint32_t seg) {
-    return reg == 2 ? lambda * (float) (ptr[seg + 1] - ptr[seg]) : lambda;
 }
 
 // After the first gather (R = b; warm: Q = the gathered part of A y0, for the implicit model with G y0 added already), one
@@ -341,18 +330,6 @@ int gather(int mode, const AlsHalf& h, const float* X, uint32_t x_rows, uint32_t
     return MFX_OK;
 }
 
-int dense(const float* V, uint32_t nseg, uint32_t k, const float* M, const uint32_t* frozen, const float* add, float* out, hipStream_t st) {
-    const dim3 grid((nseg + 127) / 128, (k + 127) / 128), block(256);
-    switch (k > 128 ? 4 : (k + 31) / 32) {
-        case 1: hipLaunchKernelGGL(k_foldcg_dense<1>, grid, block, 0, st, V, nseg, k, M, frozen, add, out); break;
-        case 2: hipLaunchKernelGGL(k_foldcg_dense<2>, grid, block, 0, st, V, nseg, k, M, frozen, add, out); break;
-        case 3: hipLaunchKernelGGL(k_foldcg_dense<3>, grid, block, 0, st, V, nseg, k, M, frozen, add, out); break;
-        default: hipLaunchKernelGGL(k_foldcg_dense<4>, grid, block, 0, st, V, nseg, k, M, frozen, add, out); break;
-    }
-    MFX_HIP(hipGetLastError());
-    return MFX_OK;
-}
-
 // fp64 dot of two contiguous rows over [0, n): four partial sums in a fixed order
 double dot4(const double* a, const double* b, size_t n) {
     double s0 = 0, s1 = 0, s2 = 0, s3 = 0;
@@ -368,6 +345,18 @@ double dot4(const double* a, const double* b, size_t n) {
 }
 
 }  // namespace
+
+int foldcg_dense(const float* V, uint32_t nseg, uint32_t k, const float* M, const uint32_t* frozen, const float* add, float* out, hipStream_t st) {
+    const dim3 grid((nseg + 127) / 128, (k + 127) / 128), block(256);
+    switch (k > 128 ? 4 : (k + 31) / 32) {
+        case 1: hipLaunchKernelGGL(k_foldcg_dense<1>, grid, block, 0, st, V, nseg, k, M, frozen, add, out); break;
+        case 2: hipLaunchKernelGGL(k_foldcg_dense<2>, grid, block, 0, st, V, nseg, k, M, frozen, add, out); break;
+        case 3: hipLaunchKernelGGL(k_foldcg_dense<3>, grid, block, 0, st, V, nseg, k, M, frozen, add, out); break;
+        default: hipLaunchKernelGGL(k_foldcg_dense<4>, grid, block, 0, st, V, nseg, k, M, frozen, add, out); break;
+    }
+    MFX_HIP(hipGetLastError());
+    return MFX_OK;
+}
 
 int foldcg_inverse(const float* G, uint32_t k, float* Minv) {
     const size_t n = k;
@@ -432,23 +421,23 @@ int foldcg_launch(const AlsHalf& h, const float* X, uint32_t x_rows, uint32_t k,
 
     // b into R; warm: the gathered part of A y0 into Q, then G y0 on top (implicit)
     MFX_TRY(gather(warm ? 3 : 2, h, X, x_rows, k, implicit, m.alpha, Y, nullptr, Q.get(), R.get(), ws.get(), st));
-    if (warm && implicit) MFX_TRY(dense(Y, nseg, k, m.G, nullptr, Q.get(), Q.get(), st));
+    if (warm && implicit) MFX_TRY(foldcg_dense(Y, nseg, k, m.G, nullptr, Q.get(), Q.get(), st));
     hipLaunchKernelGGL(k_foldcg_start, grid, block, 0, st, h.ptr.get(), nseg, k, Y, R.get(), Z, P.get(), Q.get(), (int32_t) warm, m.reg, m.lambda,
                        m.tol, bb.get(), frozen.get(), counts);
     MFX_HIP(hipGetLastError());
-    if (implicit) MFX_TRY(dense(R.get(), nseg, k, m.Minv, frozen.get(), nullptr, Z, st));
+    if (implicit) MFX_TRY(foldcg_dense(R.get(), nseg, k, m.Minv, frozen.get(), nullptr, Z, st));
     hipLaunchKernelGGL(k_foldcg_dir, grid, block, 0, st, nseg, k, R.get(), Z, P.get(), 1, gamma.get(), frozen.get(), active.get());
     MFX_HIP(hipGetLastError());
     bool done = false;
     if (stop) MFX_TRY(all_frozen(0, done));
     for (int32_t s = 0; s < m.steps && !done; ++s) {
         MFX_TRY(gather(1, h, X, x_rows, k, implicit, m.alpha, P.get(), frozen.get(), Q.get(), nullptr, ws.get(), st));
-        if (implicit) MFX_TRY(dense(P.get(), nseg, k, m.G, frozen.get(), Q.get(), Q.get(), st));
+        if (implicit) MFX_TRY(foldcg_dense(P.get(), nseg, k, m.G, frozen.get(), Q.get(), Q.get(), st));
         hipLaunchKernelGGL(k_foldcg_step, grid, block, 0, st, h.ptr.get(), nseg, k, Y, R.get(), P.get(), Q.get(), m.reg, m.lambda, m.tol,
                            gamma.get(), bb.get(), frozen.get(), counts, fail);
         MFX_HIP(hipGetLastError());
         if (s + 1 == m.steps) break;  // (the direction of a step that never comes)
-        if (implicit) MFX_TRY(dense(R.get(), nseg, k, m.Minv, frozen.get(), nullptr, Z, st));
+        if (implicit) MFX_TRY(foldcg_dense(R.get(), nseg, k, m.Minv, frozen.get(), nullptr, Z, st));
         hipLaunchKernelGGL(k_foldcg_dir, grid, block, 0, st, nseg, k, R.get(), Z, P.get(), 0, gamma.get(), frozen.get(),
                            stop ? active.get() + s + 1 : nullptr);
         MFX_HIP(hipGetLastError());

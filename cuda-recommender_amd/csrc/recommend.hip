@@ -31,6 +31,8 @@
 // MFX_FOLD_ALS / MFX_FOLD_CCD the same way after mfx_rec_fold_in_block_setup_als (alsb_fold_launch).  After
 // mfx_rec_fold_in_cg_setup the rows are solved by conjugate gradients preconditioned by the inverse of the base Gramian
 // (rec_foldin_cg.hip, foldcg_launch), at any rank up to 1024: a solve with a residual bound, not a sweep.
+// Explanations (mfx_rec_explain) take Z = A^-1 h_target from the factor of a closed-form solve (k <= 128); after the cg
+// setup mfx_rec_explain_cg takes it from the same conjugate gradients over the pairs (rec_explain_cg.hip, explaincg_launch).
 //
 // Item-to-item similarity (mfx_rec_similar) and the item filter (mfx_rec_set_item_filter) are one per-item fp32 factor on
 // the accumulator before the compare (mfx_rec_topn<KC, true>): an inverse norm for the cosine, 1 / NaN for kept / dropped
@@ -48,6 +50,7 @@
 #include "ccd_kernels.hpp"  // check_index_range
 #include "rec_tiles.hpp"   // the tile pass, the workgroup shape, the total order
 #include "recommend.hpp"
+#include "rec_foldin_cg.hpp"
 
 namespace mfx {
 
@@ -892,6 +895,26 @@ int Recommender::explain(int64_t nusers, int64_t nnz, const uint32_t* ptr, const
     MFX_REQUIRE(fold_model_ != kFoldBlock && fold_model_ != kFoldBlockAls,
                 "%s: not after a block setup (a sweep is not a solve, the split over the entries does not hold); set up mfx_rec_fold_in_setup "
                 "or mfx_rec_fold_in_setup_reg on a handle of rank <= 128", fn);
+    return explain_run(fn, nusers, nnz, ptr, idx, val, n_targets, targets, n_expl, expl_items, expl_contrib, totals, W_out, Z_out, nullptr,
+                       nullptr, space);
+}
+
+// mfx_rec_explain_cg: the fold-in rows by foldcg_launch as mfx_rec_fold_in runs it (cold start), Z = the iterates of
+// A z = h_target by the same method over the pairs (rec_explain_cg.hip), then the same totals and contributions.
+int Recommender::explain_cg(int64_t nusers, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val, int32_t n_targets,
+                            const uint32_t* targets, int32_t n_expl, uint32_t* expl_items, float* expl_contrib, float* totals, float* W_out,
+                            float* Z_out, int32_t* row_steps, int32_t* target_steps, mfx_memspace space) {
+    const char* fn = "mfx_rec_explain_cg";
+    MFX_REQUIRE(fold_model_ == kFoldCg,
+                "%s: call mfx_rec_fold_in_cg_setup first (after a closed-form setup mfx_rec_explain explains; a block sweep is not a solve)", fn);
+    return explain_run(fn, nusers, nnz, ptr, idx, val, n_targets, targets, n_expl, expl_items, expl_contrib, totals, W_out, Z_out, row_steps,
+                       target_steps, space);
+}
+
+// What the two have in common; row_steps / target_steps: mfx_rec_explain_cg only.
+int Recommender::explain_run(const char* fn, int64_t nusers, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val,
+                             int32_t n_targets, const uint32_t* targets, int32_t n_expl, uint32_t* expl_items, float* expl_contrib,
+                             float* totals, float* W_out, float* Z_out, int32_t* row_steps, int32_t* target_steps, mfx_memspace space) {
     MFX_REQUIRE(nusers >= 0 && nusers < (int64_t) 0xFFFFFFFFll, "%s: bad nusers %lld", fn, (long long) nusers);
     MFX_REQUIRE(nnz >= 0 && nnz < (int64_t) 0xFFFF0000ll, "%s: bad nnz %lld", fn, (long long) nnz);
     MFX_REQUIRE(n_targets >= 1 && n_targets <= kMaxExplain, "%s: n_targets must be in [1, %d] (got %d)", fn, kMaxExplain, n_targets);
@@ -918,7 +941,7 @@ int Recommender::explain(int64_t nusers, int64_t nnz, const uint32_t* ptr, const
         MFX_TRY(d_targets.upload(targets, npair, MFX_HOST, st));
         dt = d_targets.get();
     }
-    MFX_TRY(explain_check_targets(dt, npair, n_targets));
+    MFX_TRY(explain_check_targets(fn, dt, npair, n_targets));
     const auto t1 = clk::now();
 
     DevBuf<float> Y, Z, ws, rho, d_contrib, d_totals;
@@ -926,7 +949,7 @@ int Recommender::explain(int64_t nusers, int64_t nnz, const uint32_t* ptr, const
     MFX_TRY(Y.alloc_zero((size_t) nu * k, st));
     MFX_TRY(Z.alloc_zero(npair * k, st));
     MFX_TRY(spd_fail.alloc_zero(1, st));
-    MFX_TRY(ws.alloc(std::max<size_t>(1, als_ws_floats(h.nslots, k))));
+    if (fold_model_ != kFoldCg) MFX_TRY(ws.alloc(std::max<size_t>(1, als_ws_floats(h.nslots, k))));
     const uint32_t x_rows = (uint32_t) cols_;
     AlsMrhs m;
     m.targets = dt; m.n_targets = (uint32_t) n_targets; m.Z = Z.get();
@@ -936,7 +959,20 @@ int Recommender::explain(int64_t nusers, int64_t nnz, const uint32_t* ptr, const
         MFX_TRY(ialsr_rho_launch(h, x_rows, fold_lambda_, fold_alpha0_, fold_nu_, rho.get(), st));
         m.alpha0 = fold_alpha0_; m.rho = rho.get();
     }
+    DevBuf<int32_t> counts, pair_counts;
     switch (fold_model_) {
+        case kFoldCg: {  // the row as fold_solve runs it from zero, then the pairs
+            if (row_steps) MFX_TRY(counts.alloc(nu));
+            if (target_steps) MFX_TRY(pair_counts.alloc(npair));
+            FoldCg cg;
+            cg.reg = fold_cg_model_ == MFX_FOLD_IMPLICIT ? 0 : fold_cg_model_ == MFX_FOLD_ALS ? 1 : 2;
+            cg.lambda = fold_lambda_; cg.alpha = fold_alpha_;
+            cg.G = fold_g_.get(); cg.Minv = fold_minv_.get();
+            cg.steps = fold_sweeps_; cg.tol = fold_tol_;
+            MFX_TRY(foldcg_launch(h, hx_.get(), x_rows, k, cg, Y.get(), false, counts.get(), spd_fail.get(), st));
+            MFX_TRY(explaincg_launch(h, hx_.get(), x_rows, k, cg, dt, (uint32_t) n_targets, Z.get(), pair_counts.get(), st));
+            break;
+        }
         case MFX_FOLD_ALS: MFX_TRY(als_half_mrhs_launch(h, hx_.get(), x_rows, Y.get(), k, m, ws.get(), spd_fail.get(), st)); break;
         case MFX_FOLD_CCD: MFX_TRY(als_half_nreg_mrhs_launch(h, hx_.get(), x_rows, Y.get(), k, m, ws.get(), spd_fail.get(), st)); break;
         default:
@@ -950,6 +986,8 @@ int Recommender::explain(int64_t nusers, int64_t nnz, const uint32_t* ptr, const
     const hipMemcpyKind out = host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
     if (W_out) MFX_HIP(hipMemcpyAsync(W_out, Y.get(), sizeof(float) * (size_t) nu * k, out, st));
     if (Z_out) MFX_HIP(hipMemcpyAsync(Z_out, Z.get(), sizeof(float) * npair * k, out, st));
+    if (row_steps) MFX_HIP(hipMemcpyAsync(row_steps, counts.get(), sizeof(int32_t) * (size_t) nu, out, st));
+    if (target_steps) MFX_HIP(hipMemcpyAsync(target_steps, pair_counts.get(), sizeof(int32_t) * npair, out, st));
     uint32_t* oi = expl_items;
     float* oc = expl_contrib;
     float* ot = totals;

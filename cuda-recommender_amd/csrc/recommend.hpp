@@ -59,6 +59,10 @@ public:
     int explain(int64_t nusers, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val, int32_t n_targets,
                 const uint32_t* targets, int32_t n_expl, uint32_t* expl_items, float* expl_contrib, float* totals, float* W_out, float* Z_out,
                 mfx_memspace space);
+    // mfx_rec_explain_cg: after mfx_rec_fold_in_cg_setup only; Z by conjugate gradients over the pairs (rec_explain_cg.hip)
+    int explain_cg(int64_t nusers, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val, int32_t n_targets,
+                   const uint32_t* targets, int32_t n_expl, uint32_t* expl_items, float* expl_contrib, float* totals, float* W_out, float* Z_out,
+                   int32_t* row_steps, int32_t* target_steps, mfx_memspace space);
     void explain_times(double out[3]) const { for (int i = 0; i < 3; ++i) out[i] = expl_s_[i]; }
     ~Recommender();
 
@@ -87,7 +91,10 @@ private:
     int ensure_hq();
     int fold_rows(const char* fn, uint32_t nu, uint64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val, mfx_memspace space,
                   AlsHalf& h);
-    int explain_check_targets(const uint32_t* d_targets, size_t n, int32_t n_targets);
+    int explain_run(const char* fn, int64_t nusers, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val, int32_t n_targets,
+                    const uint32_t* targets, int32_t n_expl, uint32_t* expl_items, float* expl_contrib, float* totals, float* W_out,
+                    float* Z_out, int32_t* row_steps, int32_t* target_steps, mfx_memspace space);
+    int explain_check_targets(const char* fn, const uint32_t* d_targets, size_t n, int32_t n_targets);
     int explain_lists(const AlsHalf& h, const uint32_t* d_targets, int32_t nt, const float* Z, const float* Y, int32_t n_expl,
                       uint32_t* d_items, float* d_contrib, float* d_totals);
     int fold_solve(int64_t nusers, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val, const float* W_init,
@@ -130,7 +137,7 @@ private:
     float fold_tol_ = 0.f;
     double fold_s_[3] = {0, 0, 0};  // host build / solve / score seconds of the last fold-in
     double rank_s_[3] = {0, 0, 0};  // device seconds of the last rank: target keys / counting pass / exclusion correction
-    double expl_s_[3] = {0, 0, 0};  // seconds of the last explain: host build + checks / solve / totals + contributions
+    double expl_s_[3] = {0, 0, 0};  // seconds of the last explain of either kind: host build + checks / solve / totals + contributions
     double cand_s_[3] = {0, 0, 0};  // stream seconds of the last query_candidates / score: check + stage / score / merge of long lists
 };
 

@@ -147,6 +147,8 @@ SIGNATURES = {
     "mfx_rec_fold_in_times": (C.c_int, [C.c_void_p, f64p]),
     "mfx_rec_explain": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    "mfx_rec_explain_cg": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "mfx_rec_explain_times": (C.c_int, [C.c_void_p, f64p]),
     "mfx_rec_set_item_filter": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
     "mfx_rec_similar_setup": (C.c_int, [C.c_void_p]),

@@ -1274,6 +1274,21 @@ class Recommender:
         for padding; "W" [U, k] with return_W, "Z" [U, T, k] = A^-1 h_target with return_Z}.  Tensors in, or on_device=True:
         tensors out (items as int32 holding the uint32 ids).  The batch is cut into consecutive pieces whose Z workspace
         (4 k T bytes per user) stays under max_ws_bytes; a row's result does not depend on the cut."""
+        return self._explain(False, rows, targets, n_expl, on_device, return_W, return_Z, False, max_ws_bytes)
+
+    def explain_cg(self, rows, targets, n_expl: int = 10, on_device: bool = False, return_W: bool = False, return_Z: bool = False,
+                   return_steps: bool = False, max_ws_bytes: int = 1 << 30) -> dict:
+        """explain() at any k <= 1024, after fold_in_cg_setup (mfx_rec_explain_cg): the row is fold_in's under that setup and
+        Z[q][t] is the conjugate-gradient iterate of A_q z = h_t from zero, with the setup's steps and tol and the stop rule
+        |r| <= tol |h_t|, so the contributions sum to the total up to about tol (|b| |z| + |h_t| |w|) (include/mfx.h).
+        Arguments and the returned dict are those of explain(); return_steps adds "row_steps" [U] (fold_in's step counts) and
+        "target_steps" [U, T] (0 for a padding target, a row without counting entries and a zero target row), int32.
+        The batch is cut into consecutive pieces whose device workspace (Z, residual, direction, A p and, under the implicit
+        model, the preconditioned residual: up to 20 k T bytes per user, plus the row solve's 16 k) stays under max_ws_bytes;
+        a row's result does not depend on the cut."""
+        return self._explain(True, rows, targets, n_expl, on_device, return_W, return_Z, return_steps, max_ws_bytes)
+
+    def _explain(self, cg: bool, rows, targets, n_expl, on_device, return_W, return_Z, return_steps, max_ws_bytes) -> dict:
         ptr, idx, val = (rows.csr_row_ptr, rows.csr_col_idx, rows.csr_val) if hasattr(rows, "csr_row_ptr") else rows
         if len(ptr.shape) != 1 or ptr.shape[0] < 1 or idx.shape != val.shape:
             raise ValueError("rows: ptr [U + 1], idx [nnz], val [nnz]")
@@ -1282,8 +1297,8 @@ class Recommender:
             raise ValueError(f"targets must be [{n}, T]")
         nt, k = int(targets.shape[1]), self.k
         dev_in = any(_is_dev(a) for a in (ptr, idx, val, targets)) or on_device
-        step = max(1, int(max_ws_bytes) // max(1, 4 * k * nt))
-        fn = L.lib().mfx_rec_explain
+        per_user = 4 * k * (5 * nt + 4) if cg else 4 * k * nt  # cg: the five arrays per pair, four per row of the row solve
+        step = max(1, int(max_ws_bytes) // max(1, per_user))
         if dev_in:
             import torch
             dev = torch.device("cuda", self.device)
@@ -1303,6 +1318,8 @@ class Recommender:
                 out["W"] = new((n, k), torch.float32)
             if return_Z:
                 out["Z"] = new((n, nt, k), torch.float32)
+            if return_steps:
+                out["row_steps"], out["target_steps"] = new((n,), torch.int32), new((n, nt), torch.int32)
             hp = (ptr.cpu().numpy().view(np.uint32).astype(np.int64)) if n > step else None
             p = lambda t: C.c_void_p(int(t.data_ptr())) if t is not None and t.numel() else None
             space = L.MFX_DEVICE
@@ -1323,6 +1340,8 @@ class Recommender:
                 out["W"] = np.empty((n, k), np.float32)
             if return_Z:
                 out["Z"] = np.empty((n, nt, k), np.float32)
+            if return_steps:
+                out["row_steps"], out["target_steps"] = np.empty(n, np.int32), np.empty((n, nt), np.int32)
             hp = ptr.astype(np.int64)
             p = lambda a: _vp(a) if a is not None and a.size else None
             space = L.MFX_HOST
@@ -1335,12 +1354,16 @@ class Recommender:
                 pp = ptr[u0:u1 + 1] - ptr[u0]
                 pp = pp.contiguous() if dev_in else np.ascontiguousarray(pp)
             cut = lambda key: out[key][u0:u1] if key in out else None
-            L.check(fn(self.handle, u1 - u0, hi - lo, p(pp), p(idx[lo:hi]), p(val[lo:hi]), nt, p(targets[u0:u1]), n_expl,
-                       p(cut("items")), p(cut("contrib")), p(cut("totals")), p(cut("W")), p(cut("Z")), space))
+            args = (self.handle, u1 - u0, hi - lo, p(pp), p(idx[lo:hi]), p(val[lo:hi]), nt, p(targets[u0:u1]), n_expl,
+                    p(cut("items")), p(cut("contrib")), p(cut("totals")), p(cut("W")), p(cut("Z")))
+            if cg:
+                L.check(L.lib().mfx_rec_explain_cg(*args, p(cut("row_steps")), p(cut("target_steps")), space))
+            else:
+                L.check(L.lib().mfx_rec_explain(*args, space))
         return out
 
     def explain_times(self) -> dict:
-        """Seconds of the last mfx_rec_explain call by phase (mfx_rec_explain_times): {"build": host build and checks,
+        """Seconds of the last mfx_rec_explain / mfx_rec_explain_cg call by phase (mfx_rec_explain_times): {"build": host build and checks,
         "solve": the rows and the further right-hand sides, "contrib": totals, contributions and selection}.  After an
         explain() that cut its batch: of the last piece."""
         out = (C.c_double * 3)()

@@ -459,7 +459,7 @@ int mfx_rec_fold_in_times(mfx_rec_t r, double seconds[3]);
  * Valid after mfx_rec_fold_in_setup with MFX_FOLD_ALS, MFX_FOLD_CCD or MFX_FOLD_IMPLICIT, or mfx_rec_fold_in_setup_reg.
  * MFX_ERR_INVALID (the handle stays usable) before any setup, after MFX_FOLD_ALS_EXACT (its rows are not the bits of the
  * MFMA system: use MFX_FOLD_ALS), after any block setup (a sweep is not a solve: the split does not hold) and after
- * mfx_rec_fold_in_cg_setup (closed-form setups only: the split uses the factor of the row's system).
+ * mfx_rec_fold_in_cg_setup (the split here uses the factor of the row's system: there mfx_rec_explain_cg explains).
  * Query rows ptr / idx / val: as for mfx_rec_fold_in, with the same checks.  targets [nusers][n_targets]: item ids below
  * cols, or 0xFFFFFFFF = padding (checked on the device), so the padded `items` of mfx_rec_fold_in may be passed as they
  * are; a target may repeat and may be one of the row's own items.  The exclusion matrix and the item filter play no part.
@@ -489,9 +489,39 @@ int mfx_rec_fold_in_times(mfx_rec_t r, double seconds[3]);
 int mfx_rec_explain(mfx_rec_t r, int64_t nusers, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val,
                     int32_t n_targets, const uint32_t* targets, int32_t n_expl, uint32_t* expl_items, float* expl_contrib,
                     float* totals, float* W_out, float* Z_out, mfx_memspace space);
-/* Wall-clock seconds of the last mfx_rec_explain on r, each phase ending in a stream synchronisation: [0] host build and
- * checks (rows and targets), [1] solve (the row and the n_targets further right-hand sides), [2] totals, contributions,
- * selection and the copies out. */
+/* mfx_rec_explain at any 1 <= k <= 1024, after mfx_rec_fold_in_cg_setup: the split <h_t, w> = sum_e b_e <h_e, z>, A z = h_t,
+ * holds for any method that solves for z, up to that method's residual, and conjugate gradients solve.
+ * Valid only after a successful mfx_rec_fold_in_cg_setup (MFX_FOLD_ALS, MFX_FOLD_CCD or MFX_FOLD_IMPLICIT); lambda, alpha,
+ * steps and tol are that setup's.  MFX_ERR_INVALID (the handle stays usable, the message names mfx_rec_fold_in_cg_setup)
+ * before any setup, after mfx_rec_fold_in_setup / _setup_reg (mfx_rec_explain explains there) and after any block setup.
+ * Arguments and checks are those of mfx_rec_explain, the rows checked as mfx_rec_fold_in checks them under the cg setup;
+ * nusers * n_targets < 2^31.  row_steps [nusers] and target_steps [nusers][n_targets] may be NULL; `space` applies to
+ * every array.
+ *   W_out, row_steps: bit for bit what mfx_rec_fold_in (the cold start) and its sweeps_done give for the row.
+ *   Z_out[q][t]: the iterate of A_q z = h_t from z = 0 by exactly the recurrence of mfx_rec_fold_in_cg_setup, with the A and
+ *     the preconditioner of row q (the table there: implicit over the entries with r_e > 0, explicit over every entry) and
+ *     b = the handle's own bits of H[target].  The stop rule is |r| <= tol |h_t| (2-norms, fp32), tested on the start too, the
+ *     step that reaches it counted into target_steps; tol = 0: exactly `steps` steps unless gamma becomes exactly 0.
+ *     A padding target, a row without counting entries (implicit: no r_e > 0; explicit: an empty row) and a target with
+ *     h_t = 0: z = 0 and 0 steps.  <p, q> < 0 or not finite: the pair's z is NaN and frozen; <p, q> exactly 0 freezes it.
+ *   totals, expl_items, expl_contrib: the definitions of mfx_rec_explain from W_out and Z_out (the score chain; b_e = r_e,
+ *     or fp32(1 + fp32(alpha r_e)) over r_e > 0 for the implicit model; order, padding and duplicates as there).
+ * Accuracy: the split holds up to the residuals.  With r_w = b - A w and r_z = h_t - A z (A symmetric),
+ * <b, z> - <h_t, w> = <r_w, z> - <r_z, w>, so |sum_e c_e - total| <~ tol (|b| |z| + |h_t| |w|) plus fp32 rounding; a smaller
+ * tol at setup tightens it.
+ * No float atomics: the bits and the step count of a (row, target) pair do not depend on the batch, its order, duplicates,
+ * n_targets, the other targets of the slot, the target's position in it, the memory space or the factor layout, and a pair
+ * stopped after s steps has the bits of the same pair run with steps = s, tol = 0.
+ * Device workspace of a call: per slot 4 k n_targets bytes each for Z, the residual, the direction and A p, and for the
+ * preconditioned residual under the implicit model; 16 bytes per pair; 4 k n_targets bytes per partial slot of a row longer
+ * than 2048 entries (one slot per 2048 entries); what mfx_rec_fold_in takes for the same rows under this setup, and the
+ * lists as for mfx_rec_explain.  The caller cuts very large batches (mfx.Recommender.explain_cg does, by max_ws_bytes). */
+int mfx_rec_explain_cg(mfx_rec_t r, int64_t nusers, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val,
+                       int32_t n_targets, const uint32_t* targets, int32_t n_expl, uint32_t* expl_items, float* expl_contrib,
+                       float* totals, float* W_out, float* Z_out, int32_t* row_steps, int32_t* target_steps, mfx_memspace space);
+/* Wall-clock seconds of the last mfx_rec_explain or mfx_rec_explain_cg on r, each phase ending in a stream synchronisation:
+ * [0] host build and checks (rows and targets), [1] solve (the row and the n_targets further right-hand sides; _cg: the row
+ * solve plus the target solves), [2] totals, contributions, selection and the copies out. */
 int mfx_rec_explain_times(mfx_rec_t r, double seconds[3]);
 /* Item filter: keep [cols] bytes in `space`, non-zero = the item may be returned; NULL removes the filter.  Copied.
  * Applies to every later mfx_rec_query, mfx_rec_fold_in, mfx_rec_fold_in_warm and mfx_rec_similar on r until replaced:

@@ -13,9 +13,15 @@ cholesky_solve against the target rows, bmm for the contributions, topk.
 With --parent-pkg DIR (a built cuda-recommender_amd tree of the parent commit): the unchanged all-user fold_in(n_top = 10)
 and query(10) at k = 64 on that tree and on this one, alternated, --regress-runs fresh processes each.
 
+With --cg [--k 256]: mfx_rec_explain_cg instead, after fold_in_cg_setup(MFX_FOLD_IMPLICIT, tol = 1e-4) at alpha = 1 and
+alpha = 40: the same batches, targets and n_expl; per batch fold_in(n_top = 10) and explain_cg under the same setup,
+alternated, with their phases, the step counts, and the solve phase per target relative to fold-in's solve:
+(explain_cg solve - fold_in solve) / n_targets / fold_in solve -- below 1 where the targets of a slot share the gathered rows.
+With --parent-pkg the unchanged paths are the all-user query(10) at k = 64 and the all-user cg fold-in at --k.
+
 Prints ONE JSON line (also to --out FILE).
 
-    python tools/explain_bench.py [--reps 5] [--ks 64,128] [--parent-pkg DIR] [--regress-runs 4] [--out FILE]
+    python tools/explain_bench.py [--reps 5] [--ks 64,128] [--cg [--k 256]] [--parent-pkg DIR] [--regress-runs 4] [--out FILE]
 """
 import argparse
 import json
@@ -30,6 +36,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "cuda-recommender_amd")
 ROWS, COLS, NNZ = 480189, 17770, 99_072_112
 LAM, ALPHA, N_TOP, N_EXPL = 0.05, 1.0, 10, 10
+CG_TOL, CG_ALPHAS = 1e-4, (1.0, 40.0)
 
 
 def timed(fn, reps, sync):
@@ -76,6 +83,70 @@ def regress_child(a):
     return 0
 
 
+def cg_regress_child(a):
+    """All-user query(10) at k = 64 and all-user cg fold_in(n_top = 10) at k = a.k, tol = 1e-4, with the package in
+    a.regress_child: one JSON line."""
+    sys.path.insert(0, a.regress_child)
+    import torch
+    import mfx
+    dev = torch.device("cuda:0")
+    d, H = data(a.seed, 64, torch, dev)
+    gw = torch.Generator(device=dev)
+    gw.manual_seed(7)
+    W = (torch.randn(int(d["rows"]), 64, generator=gw, device=dev) * 0.3).contiguous()
+    with mfx.Recommender(W, H, 1) as r:
+        query = timed(lambda: r.query(N_TOP, on_device=True), a.reps, torch.cuda.synchronize)
+    del W, H
+    q = (d["csr_row_ptr"], d["csr_col_idx"], d["csr_val"])
+    g = torch.Generator(device=dev)
+    g.manual_seed(a.k)
+    H = (torch.randn(int(d["cols"]), a.k, generator=g, device=dev) * 0.3).contiguous()
+    with mfx.Recommender(torch.zeros(1, a.k, device=dev), H, 1) as r:
+        r.fold_in_cg_setup(mfx.MFX_FOLD_IMPLICIT, LAM, ALPHA, steps=64, tol=CG_TOL)
+        fold = timed(lambda: r.fold_in(q, N_TOP), a.reps, torch.cuda.synchronize)
+    print(json.dumps({"fold_in_ms": float(np.median(fold)), "query_ms": float(np.median(query))}))
+    return 0
+
+
+def cg_points(a, mfx, torch, dev, H, batches, alpha):
+    """fold_in(n_top = 10) and explain_cg under one cg setup, alternated, per batch."""
+    sync = torch.cuda.synchronize
+    points = []
+    with mfx.Recommender(torch.zeros(1, a.k, device=dev), H, 1) as r:
+        r.fold_in_cg_setup(mfx.MFX_FOLD_IMPLICIT, LAM, alpha, steps=64, tol=CG_TOL)
+        for name, q in batches.items():
+            targets = r.fold_in(q, N_TOP)[0]
+            call = lambda: r.explain_cg(q, targets, N_EXPL, return_steps=True, max_ws_bytes=1 << 40)
+            fold, expl, fsplit, esplit = [], [], [], []
+            r.fold_in(q, N_TOP)
+            res = call()
+            sync()
+            for _ in range(a.reps):                          # alternated
+                t0 = time.perf_counter()
+                r.fold_in(q, N_TOP)
+                sync()
+                fold.append((time.perf_counter() - t0) * 1e3)
+                fsplit.append(r.fold_in_times())
+                t0 = time.perf_counter()
+                call()
+                sync()
+                expl.append((time.perf_counter() - t0) * 1e3)
+                esplit.append(r.explain_times())
+            fm, em = int(np.argsort(fold)[len(fold) // 2]), int(np.argsort(expl)[len(expl) // 2])
+            ts, rs = res["target_steps"].float(), res["row_steps"].float()
+            pt = {"batch": name, "users": int(q[0].numel()) - 1, "nnz": int(q[1].numel()), "alpha": alpha,
+                  "fold_in": dict(stats(fold), phases_ms={key: round(v * 1e3, 3) for key, v in fsplit[fm].items()}),
+                  "explain_cg": dict(stats(expl), phases_ms={key: round(v * 1e3, 3) for key, v in esplit[em].items()}),
+                  "row_steps_mean_max": [round(float(rs.mean()), 3), int(rs.max())],
+                  "target_steps_mean_max": [round(float(ts.mean()), 3), int(ts.max())]}
+            fs, es = pt["fold_in"]["phases_ms"]["solve"], pt["explain_cg"]["phases_ms"]["solve"]
+            pt["explain_cg_over_fold_in"] = round(pt["explain_cg"]["ms_median"] / pt["fold_in"]["ms_median"], 3)
+            pt["target_solve_per_target_over_fold_in_solve"] = round((es - fs) / N_TOP / fs, 3)
+            points.append(pt)
+            print(json.dumps(pt), file=sys.stderr, flush=True)
+    return points
+
+
 def torch_explain(torch, H, G, q, targets):
     """The same answer from torch ops on the device for one batch: (items, contrib) [U, T, n_expl]."""
     ptr, idx, val = q
@@ -104,13 +175,15 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--ks", default="64,128")
     ap.add_argument("--seed", type=int, default=1234)
+    ap.add_argument("--cg", action="store_true", help="mfx_rec_explain_cg under fold_in_cg_setup at rank --k")
+    ap.add_argument("--k", type=int, default=256)
     ap.add_argument("--parent-pkg", default=None)
     ap.add_argument("--regress-runs", type=int, default=4)
     ap.add_argument("--regress-child", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if a.regress_child:
-        return regress_child(a)
+        return cg_regress_child(a) if a.cg else regress_child(a)
     sys.path.insert(0, PKG)
     import torch
     import mfx
@@ -118,7 +191,9 @@ def main():
     sync = torch.cuda.synchronize
     out = {"tool": "explain_bench", "workload": f"{ROWS}x{COLS} nnz={NNZ}", "model": "IMPLICIT", "lambda": LAM, "alpha": ALPHA,
            "n_targets": N_TOP, "n_expl": N_EXPL, "reps": a.reps, "query_arrays": "device", "cases": []}
-    for k in [int(x) for x in a.ks.split(",") if x]:
+    if a.cg:
+        out.update(tool="explain_bench --cg", alpha=list(CG_ALPHAS), k=a.k, steps=64, tol=CG_TOL)
+    for k in [a.k] if a.cg else [int(x) for x in a.ks.split(",") if x]:
         d, H = data(a.seed, k, torch, dev)
         rows = int(d["rows"])
         rp, ci, cv = d["csr_row_ptr"], d["csr_col_idx"], d["csr_val"]
@@ -134,6 +209,11 @@ def main():
         batches = {str(n): batch(np.sort(np.random.default_rng(n).choice(rows, n, replace=False))) for n in (1, 64, 1024)}
         batches["all"] = (rp, ci, cv)
         case = {"k": k, "points": []}
+        if a.cg:
+            for alpha in CG_ALPHAS:
+                case["points"] += cg_points(a, mfx, torch, dev, H, batches, alpha)
+            out["cases"].append(case)
+            break
         with mfx.Recommender(torch.zeros(1, k, device=dev), H, 1) as r:
             r.fold_in_setup(mfx.MFX_FOLD_IMPLICIT, LAM, ALPHA)
             for name, q in batches.items():
@@ -176,14 +256,17 @@ def main():
         for _ in range(a.regress_runs):
             for name, pkg in (("parent", os.path.abspath(a.parent_pkg)), ("this", PKG)):
                 cmd = [sys.executable, os.path.abspath(__file__), "--regress-child", pkg, "--reps", str(a.reps), "--seed", str(a.seed)]
+                cmd += ["--cg", "--k", str(a.k)] if a.cg else []
                 p = subprocess.run(cmd, stdout=subprocess.PIPE, text=True, check=True, timeout=300)
                 runs[name].append(json.loads(p.stdout.strip().splitlines()[-1]))
-        reg = {"workload": "all users, k = 64, N = 10, IMPLICIT"}
+        reg = {"workload": f"all users, N = 10: query at k = 64, cg fold-in (IMPLICIT, tol = {CG_TOL}) at k = {a.k}" if a.cg
+               else "all users, k = 64, N = 10, IMPLICIT"}
         for key in ("fold_in_ms", "query_ms"):
             pv, tv = [x[key] for x in runs["parent"]], [x[key] for x in runs["this"]]
             spread = max(pv) - min(pv)
             reg[key] = {"parent": pv, "this": tv, "parent_median": float(np.median(pv)), "this_median": float(np.median(tv)),
-                        "parent_spread": spread, "no_slower": bool(np.median(tv) <= np.median(pv) + spread)}
+                        "parent_spread": spread, "no_slower": bool(np.median(tv) <= np.median(pv) + spread),
+                        "ranges_overlap": bool(min(tv) <= max(pv) and min(pv) <= max(tv))}
         out["regression"] = reg
         print(json.dumps(reg), file=sys.stderr, flush=True)
     line = json.dumps(out)
