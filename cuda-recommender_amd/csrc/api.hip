@@ -573,10 +573,14 @@ int mfx_rec_query(mfx_rec_t r, int64_t nusers, const uint32_t* users, int32_t n_
         return r->impl->query(nusers, users, n_top, items, scores, space, item_slices);
     });
 }
+// The seven fold-in setups: each fills a FoldSpec for Recommender::fold_setup, which checks it in the entry point's order.
+using FoldM = FoldPlan::Method;
+using FoldO = FoldPlan::Objective;
+
 int mfx_rec_fold_in_setup(mfx_rec_t r, int model, float lambda, float alpha) {
     return guarded("mfx_rec_fold_in_setup", [&]() -> int {
         MFX_REQUIRE(r && r->impl, "null recommender");
-        return r->impl->fold_in_setup(model, lambda, alpha);
+        return r->impl->fold_setup("mfx_rec_fold_in_setup", FoldSpec::of_model(FoldM::Direct, model, lambda, alpha));
     });
 }
 int mfx_rec_fold_in(mfx_rec_t r, int64_t nusers, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val,
@@ -589,31 +593,41 @@ int mfx_rec_fold_in(mfx_rec_t r, int64_t nusers, int64_t nnz, const uint32_t* pt
 int mfx_rec_fold_in_block_setup(mfx_rec_t r, float lambda, float alpha, int32_t block, int32_t sweeps, float tol) {
     return guarded("mfx_rec_fold_in_block_setup", [&]() -> int {
         MFX_REQUIRE(r && r->impl, "null recommender");
-        return r->impl->fold_in_block_setup(lambda, alpha, block, sweeps, tol);
+        FoldSpec s{FoldM::Blocks, FoldO::Implicit};
+        s.lambda = lambda; s.alpha = alpha; s.block = block; s.cap = sweeps; s.tol = tol;
+        return r->impl->fold_setup("mfx_rec_fold_in_block_setup", s);
     });
 }
 int mfx_rec_fold_in_setup_reg(mfx_rec_t r, float lambda, float alpha, float alpha0, float nu) {
     return guarded("mfx_rec_fold_in_setup_reg", [&]() -> int {
         MFX_REQUIRE(r && r->impl, "mfx_rec_fold_in_setup_reg: null handle");
-        return r->impl->fold_in_setup_reg(lambda, alpha, alpha0, nu);
+        FoldSpec s{FoldM::Direct, FoldO::ImplicitReg, MFX_FOLD_IMPLICIT};
+        s.lambda = lambda; s.alpha = alpha; s.alpha0 = alpha0; s.nu = nu;
+        return r->impl->fold_setup("mfx_rec_fold_in_setup_reg", s);
     });
 }
 int mfx_rec_fold_in_block_setup_reg(mfx_rec_t r, float lambda, float alpha, float alpha0, float nu, int32_t block, int32_t sweeps, float tol) {
     return guarded("mfx_rec_fold_in_block_setup_reg", [&]() -> int {
         MFX_REQUIRE(r && r->impl, "mfx_rec_fold_in_block_setup_reg: null handle");
-        return r->impl->fold_in_block_setup_reg(lambda, alpha, alpha0, nu, block, sweeps, tol);
+        FoldSpec s{FoldM::Blocks, FoldO::ImplicitReg};
+        s.lambda = lambda; s.alpha = alpha; s.alpha0 = alpha0; s.nu = nu; s.block = block; s.cap = sweeps; s.tol = tol;
+        return r->impl->fold_setup("mfx_rec_fold_in_block_setup_reg", s);
     });
 }
 int mfx_rec_fold_in_block_setup_als(mfx_rec_t r, float lambda, int32_t reg, int32_t block, int32_t sweeps, float tol) {
     return guarded("mfx_rec_fold_in_block_setup_als", [&]() -> int {
         MFX_REQUIRE(r && r->impl, "null recommender");
-        return r->impl->fold_in_block_setup_als(lambda, reg, block, sweeps, tol);
+        FoldSpec s{FoldM::Blocks, reg == 1 ? FoldO::Ccd : FoldO::Als, reg};
+        s.lambda = lambda; s.block = block; s.cap = sweeps; s.tol = tol;
+        return r->impl->fold_setup("mfx_rec_fold_in_block_setup_als", s);
     });
 }
 int mfx_rec_fold_in_cg_setup(mfx_rec_t r, int model, float lambda, float alpha, int32_t steps, float tol) {
     return guarded("mfx_rec_fold_in_cg_setup", [&]() -> int {
         MFX_REQUIRE(r && r->impl, "null recommender");
-        return r->impl->fold_in_cg_setup(model, lambda, alpha, steps, tol);
+        FoldSpec s = FoldSpec::of_model(FoldM::Cg, model, lambda, alpha);
+        s.cap = steps; s.tol = tol;
+        return r->impl->fold_setup("mfx_rec_fold_in_cg_setup", s);
     });
 }
 int mfx_rec_fold_in_warm(mfx_rec_t r, int64_t nusers, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val,

@@ -653,8 +653,8 @@ int Recommender::explain_lists(const AlsHalf& h, const uint32_t* d_targets, int3
     a.Z = Z; a.hx = hx_.get(); a.ptr = h.ptr.get(); a.idx = h.idx.get(); a.val = h.val.get(); a.targets = d_targets;
     a.piece_slot = piece_slot.get();
     a.k = (int) k_; a.nt = nt; a.n_expl = n_expl;
-    a.implicit = fold_model_ == MFX_FOLD_IMPLICIT || (fold_model_ == kFoldCg && fold_cg_model_ == MFX_FOLD_IMPLICIT);
-    a.alpha = fold_alpha_; a.alpha0 = fold_robj_ ? fold_alpha0_ : 1.f;
+    a.implicit = plan_.implicit();
+    a.alpha = plan_.alpha; a.alpha0 = plan_.alpha0;
     a.part_stride = 2 * ((size_t) total / kCandChunk + 2) * n_expl;
     if (hi.nlong) {
         MFX_TRY(part_s.alloc(a.part_stride * nt));

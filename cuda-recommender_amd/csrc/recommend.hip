@@ -391,12 +391,7 @@ int check_batch(const char* fn, const char* ids_name, const char* n_name, const 
     return MFX_OK;
 }
 
-// The argument checks the fold-in setups share, in two halves: every setup checks lambda, then its own alpha or reg, and
-// the block setups then check block / sweeps / tol.  fn is the entry point's name.
-int check_fold_lambda(const char* fn, float lambda) {
-    MFX_REQUIRE(std::isfinite(lambda) && lambda > 0.f, "%s: lambda = %g (finite and > 0 required)", fn, (double) lambda);
-    return MFX_OK;
-}
+// What the block setups of fold-in check last (fold_setup): block / sweeps / tol.  fn is the entry point's name.
 int check_fold_sweeps(const char* fn, int32_t block, int32_t sweeps, float tol) {
     MFX_REQUIRE(block >= 0 && block <= (int32_t) kIalsBlockMaxBlock, "%s: block = %d (0 = chosen from k, else 1 <= block <= %u)", fn,
                 block, kIalsBlockMaxBlock);
@@ -688,166 +683,79 @@ int Recommender::topn(const float* wp, uint32_t nu, const uint32_t* du, const ui
     return MFX_OK;
 }
 
-int Recommender::fold_setup_begin(bool drop_g, bool drop_b) {
+// Every fold-in setup: validate (nothing is touched before, so a refused call leaves the previous setup usable), begin (the
+// old plan goes as a whole before anything new is allocated; hx_ from the tiles), build what (method, objective) needs, and
+// commit the finished plan.  A failure after validation leaves the handle "not set up".
+int Recommender::fold_setup(const char* fn, const FoldSpec& s) {
+    using M = FoldPlan::Method;
+    using O = FoldPlan::Objective;
+    const bool direct = s.method == M::Direct || s.method == M::DirectExact, blocks = s.method == M::Blocks, cg = s.method == M::Cg;
+    const bool reg = s.objective == O::ImplicitReg;
+    FoldPlan p;
+    p.method = s.method;
+    p.objective = s.objective;
+    p.lambda = s.lambda;
+    p.alpha = p.implicit() ? s.alpha : 0.f;
+    if (reg) { p.alpha0 = s.alpha0; p.nu = s.nu; }
+    if (p.iterative()) { p.cap = s.cap; p.tol = s.tol; }
+
+    // the checks of every entry point in its order, each with its text (an entry point without alpha passes 0)
+    if (cg) MFX_REQUIRE(s.arg != MFX_FOLD_ALS_EXACT, "%s: model MFX_FOLD_ALS_EXACT is an order of operations, not an objective; set up MFX_FOLD_ALS", fn);
+    if (!blocks)
+        MFX_REQUIRE(s.arg == MFX_FOLD_ALS || s.arg == MFX_FOLD_ALS_EXACT || s.arg == MFX_FOLD_CCD || s.arg == MFX_FOLD_IMPLICIT,
+                    "%s: unknown model %d", fn, s.arg);
+    MFX_REQUIRE(k_ <= (direct ? 128 : (int64_t) kIalsBlockMaxRank), "%s: %s ranks k <= %u (the handle has k = %lld)", fn,
+                direct ? "fold-in solves" : blocks ? "block sweeps solve" : "conjugate gradients solve", direct ? 128u : kIalsBlockMaxRank,
+                (long long) k_);
+    MFX_REQUIRE(std::isfinite(s.lambda) && s.lambda > 0.f, "%s: lambda = %g (finite and > 0 required)", fn, (double) s.lambda);
+    MFX_REQUIRE(std::isfinite(s.alpha) && s.alpha >= 0.f, "%s: alpha = %g (finite and >= 0 required)", fn, (double) s.alpha);
+    if (reg) MFX_TRY(ialsr_check_params(fn, s.lambda, s.alpha0, s.nu, cols_, cols_));
+    if (blocks && !p.implicit()) MFX_REQUIRE(s.arg == 0 || s.arg == 1, "%s: reg = %d (0 = lambda, 1 = lambda * entries of the row)", fn, s.arg);
+    if (blocks) MFX_TRY(check_fold_sweeps(fn, s.block, s.cap, s.tol));
+    if (cg) {
+        MFX_REQUIRE(s.cap >= 1 && s.cap <= 1024, "%s: steps = %d (1 <= steps <= 1024)", fn, s.cap);
+        MFX_REQUIRE(std::isfinite(s.tol) && s.tol >= 0.f, "%s: tol = %g (finite and >= 0 required)", fn, (double) s.tol);
+    }
+
     MFX_TRY(use_device(device_));
-    fold_model_ = -1;  // (until the setup is through)
-    fold_robj_ = false;
-    if (drop_g) fold_g_.release();     // (what a direct setup kept)
-    if (drop_b) fold_b_ = IalsBlock();  // (what a block setup kept)
-    fold_minv_.release();               // (what a cg setup kept)
+    plan_ = FoldPlan();  // not set up until the new plan is through; the old one's buffers go before the new ones come
+    hipStream_t st = st_;
     const size_t nh = ((size_t) cols_ + 1) * k_;
     if (!hx_.get()) MFX_TRY(hx_.alloc(nh));
-    hipLaunchKernelGGL(mfx_rec_unpack_h, dim3(grid_for(nh)), dim3(256), 0, st_, hp_.get(), (uint32_t) cols_, (int) k_, 2 * kc_, nch_,
-                       hx_.get());
+    hipLaunchKernelGGL(mfx_rec_unpack_h, dim3(grid_for(nh)), dim3(256), 0, st, hp_.get(), (uint32_t) cols_, (int) k_, 2 * kc_, nch_, hx_.get());
     MFX_LAUNCH_CHECK();
-    return MFX_OK;
-}
 
-int Recommender::fold_in_setup(int model, float lambda, float alpha) {
-    MFX_REQUIRE(model == MFX_FOLD_ALS || model == MFX_FOLD_ALS_EXACT || model == MFX_FOLD_CCD || model == MFX_FOLD_IMPLICIT,
-                "mfx_rec_fold_in_setup: unknown model %d", model);
-    MFX_REQUIRE(k_ <= 128, "mfx_rec_fold_in_setup: fold-in solves ranks k <= 128 (the handle has k = %lld)", (long long) k_);
-    MFX_TRY(check_fold_lambda("mfx_rec_fold_in_setup", lambda));
-    MFX_REQUIRE(std::isfinite(alpha) && alpha >= 0.f, "mfx_rec_fold_in_setup: alpha = %g (finite and >= 0 required)", (double) alpha);
-    MFX_TRY(fold_setup_begin(false, true));
-    hipStream_t st = st_;
+    const uint32_t k = (uint32_t) k_, cols = (uint32_t) cols_, d = std::min<uint32_t>(s.block ? (uint32_t) s.block : ialsb_default_block(k), k);
     DevBuf<float> part;
-    if (model == MFX_FOLD_IMPLICIT) {  // the base Gramian of the implicit system, as the trainer's ials_base_gramian builds it
-        MFX_TRY(part.alloc(ials_base_ws_floats((uint32_t) cols_, (uint32_t) k_)));
-        MFX_TRY(fold_g_.alloc((size_t) k_ * k_));
-        MFX_TRY(ials_base_gramian(hx_.get(), (uint32_t) cols_, (uint32_t) k_, lambda, part.get(), fold_g_.get(), st));
-    }
-    MFX_HIP(hipStreamSynchronize(st));
-    fold_model_ = model;
-    fold_lambda_ = lambda;
-    fold_alpha_ = alpha;
-    return MFX_OK;
-}
-
-int Recommender::fold_in_block_setup(float lambda, float alpha, int32_t block, int32_t sweeps, float tol) {
-    MFX_REQUIRE(k_ <= (int64_t) kIalsBlockMaxRank, "mfx_rec_fold_in_block_setup: block sweeps solve ranks k <= %u (the handle has k = %lld)",
-                kIalsBlockMaxRank, (long long) k_);
-    MFX_TRY(check_fold_lambda("mfx_rec_fold_in_block_setup", lambda));
-    MFX_REQUIRE(std::isfinite(alpha) && alpha >= 0.f, "mfx_rec_fold_in_block_setup: alpha = %g (finite and >= 0 required)", (double) alpha);
-    MFX_TRY(check_fold_sweeps("mfx_rec_fold_in_block_setup", block, sweeps, tol));
-    MFX_TRY(fold_setup_begin(true, false));
-    hipStream_t st = st_;
-    // the Gramian as the block trainer and mfx_ials_block_half build it (ialsb_gramian), and what they pack once per half
-    const uint32_t k = (uint32_t) k_, d = std::min<uint32_t>(block ? (uint32_t) block : ialsb_default_block(k), k);
-    MFX_TRY(fold_b_.alloc(k, d, (uint32_t) cols_, 0, 0, 0, st));
-    MFX_TRY(ialsb_gramian(fold_b_, hx_.get(), (uint32_t) cols_, lambda, st));
-    MFX_TRY(ialsb_pack_launch(fold_b_, hx_.get(), (uint32_t) cols_, st));
-    MFX_HIP(hipStreamSynchronize(st));
-    fold_b_.gpart.release();
-    fold_model_ = kFoldBlock;
-    fold_lambda_ = lambda;
-    fold_alpha_ = alpha;
-    fold_sweeps_ = sweeps;
-    fold_tol_ = tol;
-    return MFX_OK;
-}
-
-int Recommender::fold_in_cg_setup(int model, float lambda, float alpha, int32_t steps, float tol) {
-    const char* fn = "mfx_rec_fold_in_cg_setup";
-    MFX_REQUIRE(model != MFX_FOLD_ALS_EXACT, "%s: model MFX_FOLD_ALS_EXACT is an order of operations, not an objective; set up MFX_FOLD_ALS", fn);
-    MFX_REQUIRE(model == MFX_FOLD_ALS || model == MFX_FOLD_CCD || model == MFX_FOLD_IMPLICIT, "%s: unknown model %d", fn, model);
-    MFX_REQUIRE(k_ <= (int64_t) kIalsBlockMaxRank, "%s: conjugate gradients solve ranks k <= %u (the handle has k = %lld)", fn, kIalsBlockMaxRank,
-                (long long) k_);
-    MFX_TRY(check_fold_lambda(fn, lambda));
-    MFX_REQUIRE(std::isfinite(alpha) && alpha >= 0.f, "%s: alpha = %g (finite and >= 0 required)", fn, (double) alpha);
-    MFX_REQUIRE(steps >= 1 && steps <= 1024, "%s: steps = %d (1 <= steps <= 1024)", fn, steps);
-    MFX_REQUIRE(std::isfinite(tol) && tol >= 0.f, "%s: tol = %g (finite and >= 0 required)", fn, (double) tol);
-    const bool implicit = model == MFX_FOLD_IMPLICIT;
-    MFX_TRY(fold_setup_begin(!implicit, true));
-    hipStream_t st = st_;
-    if (implicit) {  // G as the block trainer builds it (ialsb_gramian); Minv ~ G^-1 in fp64 on the host, rounded
-        const uint32_t k = (uint32_t) k_;
+    if (direct && p.implicit()) {  // the base Gramian as the trainer builds it: H^T H + lambda I, or under ImplicitReg fp32(alpha0 H^T H)
+        MFX_TRY(part.alloc(ials_base_ws_floats(cols, k)));
+        MFX_TRY(p.g.alloc((size_t) k * k));
+        if (reg) MFX_TRY(ialsr_base_gramian(hx_.get(), cols, k, s.alpha0, part.get(), p.g.get(), st));
+        else MFX_TRY(ials_base_gramian(hx_.get(), cols, k, s.lambda, part.get(), p.g.get(), st));
+    } else if (blocks && p.implicit()) {  // the Gramian as the block trainer and mfx_ials_block_half build it, and what they pack once per half
+        MFX_TRY(p.b.alloc(k, d, cols, 0, 0, 0, st));
+        if (reg) MFX_TRY(ialsrb_gramian(p.b, hx_.get(), cols, s.alpha0, st));
+        else MFX_TRY(ialsb_gramian(p.b, hx_.get(), cols, s.lambda, st));
+        MFX_TRY(ialsb_pack_launch(p.b, hx_.get(), cols, st));
+    } else if (blocks) {  // no G, only H block-major
+        MFX_TRY(p.b.alloc_explicit(k, d, cols, 0, 0, 0, st));
+        MFX_TRY(alsb_pack_launch(p.b, hx_.get(), cols, st));
+    } else if (cg && p.implicit()) {  // G as the block trainer builds it (ialsb_gramian); Minv ~ G^-1 in fp64 on the host, rounded
         IalsBlock gb;
-        MFX_TRY(gb.alloc(k, std::min<uint32_t>(ialsb_default_block(k), k), (uint32_t) cols_, 0, 0, 0, st));
-        MFX_TRY(ialsb_gramian(gb, hx_.get(), (uint32_t) cols_, lambda, st));
+        MFX_TRY(gb.alloc(k, d, cols, 0, 0, 0, st));
+        MFX_TRY(ialsb_gramian(gb, hx_.get(), cols, s.lambda, st));
         std::vector<float> g((size_t) k * k), minv((size_t) k * k);
         MFX_HIP(hipMemcpyAsync(g.data(), gb.G.get(), sizeof(float) * g.size(), hipMemcpyDeviceToHost, st));
         MFX_HIP(hipStreamSynchronize(st));
         MFX_TRY(foldcg_inverse(g.data(), k, minv.data()));
-        MFX_TRY(fold_minv_.alloc(minv.size()));
-        MFX_TRY(fold_minv_.upload(minv.data(), minv.size(), MFX_HOST, st));
-        fold_g_ = std::move(gb.G);
-    }
-    MFX_HIP(hipStreamSynchronize(st));
-    fold_model_ = kFoldCg;
-    fold_cg_model_ = model;
-    fold_lambda_ = lambda;
-    fold_alpha_ = implicit ? alpha : 0.f;
-    fold_sweeps_ = steps;
-    fold_tol_ = tol;
-    return MFX_OK;
-}
+        MFX_TRY(p.minv.alloc(minv.size()));
+        MFX_TRY(p.minv.upload(minv.data(), minv.size(), MFX_HOST, st));
+        p.g = std::move(gb.G);
+    }  // (the explicit objectives of Direct, DirectExact and Cg need hx_ alone)
 
-int Recommender::fold_in_setup_reg(float lambda, float alpha, float alpha0, float nu) {
-    MFX_REQUIRE(k_ <= 128, "mfx_rec_fold_in_setup_reg: fold-in solves ranks k <= 128 (the handle has k = %lld)", (long long) k_);
-    MFX_TRY(check_fold_lambda("mfx_rec_fold_in_setup_reg", lambda));
-    MFX_REQUIRE(std::isfinite(alpha) && alpha >= 0.f, "mfx_rec_fold_in_setup_reg: alpha = %g (finite and >= 0 required)", (double) alpha);
-    MFX_TRY(ialsr_check_params("mfx_rec_fold_in_setup_reg", lambda, alpha0, nu, cols_, cols_));
-    MFX_TRY(fold_setup_begin(false, true));
-    hipStream_t st = st_;
-    DevBuf<float> part;  // G0 = fp32(alpha0 H^T H), as the trainer's ialsr_base_gramian builds it
-    MFX_TRY(part.alloc(ials_base_ws_floats((uint32_t) cols_, (uint32_t) k_)));
-    MFX_TRY(fold_g_.alloc((size_t) k_ * k_));
-    MFX_TRY(ialsr_base_gramian(hx_.get(), (uint32_t) cols_, (uint32_t) k_, alpha0, part.get(), fold_g_.get(), st));
     MFX_HIP(hipStreamSynchronize(st));
-    fold_model_ = MFX_FOLD_IMPLICIT;
-    fold_lambda_ = lambda;
-    fold_alpha_ = alpha;
-    fold_robj_ = true;
-    fold_alpha0_ = alpha0;
-    fold_nu_ = nu;
-    return MFX_OK;
-}
-
-int Recommender::fold_in_block_setup_reg(float lambda, float alpha, float alpha0, float nu, int32_t block, int32_t sweeps, float tol) {
-    MFX_REQUIRE(k_ <= (int64_t) kIalsBlockMaxRank, "mfx_rec_fold_in_block_setup_reg: block sweeps solve ranks k <= %u (the handle has k = %lld)",
-                kIalsBlockMaxRank, (long long) k_);
-    MFX_TRY(check_fold_lambda("mfx_rec_fold_in_block_setup_reg", lambda));
-    MFX_REQUIRE(std::isfinite(alpha) && alpha >= 0.f, "mfx_rec_fold_in_block_setup_reg: alpha = %g (finite and >= 0 required)", (double) alpha);
-    MFX_TRY(ialsr_check_params("mfx_rec_fold_in_block_setup_reg", lambda, alpha0, nu, cols_, cols_));
-    MFX_TRY(check_fold_sweeps("mfx_rec_fold_in_block_setup_reg", block, sweeps, tol));
-    MFX_TRY(fold_setup_begin(true, false));
-    hipStream_t st = st_;
-    const uint32_t k = (uint32_t) k_, d = std::min<uint32_t>(block ? (uint32_t) block : ialsb_default_block(k), k);
-    MFX_TRY(fold_b_.alloc(k, d, (uint32_t) cols_, 0, 0, 0, st));
-    MFX_TRY(ialsrb_gramian(fold_b_, hx_.get(), (uint32_t) cols_, alpha0, st));
-    MFX_TRY(ialsb_pack_launch(fold_b_, hx_.get(), (uint32_t) cols_, st));
-    MFX_HIP(hipStreamSynchronize(st));
-    fold_b_.gpart.release();
-    fold_model_ = kFoldBlock;
-    fold_lambda_ = lambda;
-    fold_alpha_ = alpha;
-    fold_robj_ = true;
-    fold_alpha0_ = alpha0;
-    fold_nu_ = nu;
-    fold_sweeps_ = sweeps;
-    fold_tol_ = tol;
-    return MFX_OK;
-}
-
-int Recommender::fold_in_block_setup_als(float lambda, int32_t reg, int32_t block, int32_t sweeps, float tol) {
-    MFX_REQUIRE(k_ <= (int64_t) kIalsBlockMaxRank, "mfx_rec_fold_in_block_setup_als: block sweeps solve ranks k <= %u (the handle has k = %lld)",
-                kIalsBlockMaxRank, (long long) k_);
-    MFX_TRY(check_fold_lambda("mfx_rec_fold_in_block_setup_als", lambda));
-    MFX_REQUIRE(reg == 0 || reg == 1, "mfx_rec_fold_in_block_setup_als: reg = %d (0 = lambda, 1 = lambda * entries of the row)", reg);
-    MFX_TRY(check_fold_sweeps("mfx_rec_fold_in_block_setup_als", block, sweeps, tol));
-    MFX_TRY(fold_setup_begin(true, true));
-    hipStream_t st = st_;
-    const uint32_t k = (uint32_t) k_, d = std::min<uint32_t>(block ? (uint32_t) block : ialsb_default_block(k), k);
-    MFX_TRY(fold_b_.alloc_explicit(k, d, (uint32_t) cols_, 0, 0, 0, st));
-    MFX_TRY(alsb_pack_launch(fold_b_, hx_.get(), (uint32_t) cols_, st));
-    MFX_HIP(hipStreamSynchronize(st));
-    fold_model_ = kFoldBlockAls;
-    fold_lambda_ = lambda;
-    fold_alpha_ = 0.f;
-    fold_reg_ = reg;
-    fold_sweeps_ = sweeps;
-    fold_tol_ = tol;
+    p.b.gpart.release();  // (the tile partials of the block Gramian)
+    plan_ = std::move(p);
     return MFX_OK;
 }
 
@@ -858,7 +766,7 @@ int Recommender::fold_in(int64_t nusers, int64_t nnz, const uint32_t* ptr, const
 
 int Recommender::fold_in_warm(int64_t nusers, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val, const float* W_init,
                               float* W_out, int32_t* sweeps_done, int32_t n_top, uint32_t* items, float* scores, mfx_memspace space) {
-    MFX_REQUIRE(fold_model_ == kFoldBlock || fold_model_ == kFoldBlockAls || fold_model_ == kFoldCg,
+    MFX_REQUIRE(plan_.iterative(),
                 "mfx_rec_fold_in_warm: call mfx_rec_fold_in_block_setup, mfx_rec_fold_in_block_setup_als or mfx_rec_fold_in_cg_setup first");
     return fold_solve(nusers, nnz, ptr, idx, val, W_init, W_out, sweeps_done, n_top, items, scores, space);
 }
@@ -872,12 +780,15 @@ int Recommender::fold_rows(const char* fn, uint32_t nu, uint64_t nnz, const uint
     const std::string who = std::string(fn) + ": ", what = who + "value";
     MFX_TRY(h.build(nu, nnz, (uint32_t) cols_, ptr, idx, val, space, kAlsChunk, st));
     MFX_TRY(check_csr(h.ptr.get(), h.idx.get(), nu, (uint32_t) cols_, nnz, who.c_str(), "ptr", st));
-    const bool cg_implicit = fold_model_ == kFoldCg && fold_cg_model_ == MFX_FOLD_IMPLICIT;
-    if (fold_model_ == MFX_FOLD_IMPLICIT || fold_model_ == kFoldBlock || cg_implicit)
-        MFX_TRY(ials_check_values(h.val.get(), h.nnz, fold_alpha_, what.c_str(), st));
-    else if (fold_model_ == kFoldBlockAls || fold_model_ == kFoldCg)
-        MFX_TRY(als_check_finite(h.val.get(), h.nnz, what.c_str(), st));
+    if (plan_.implicit()) MFX_TRY(ials_check_values(h.val.get(), h.nnz, plan_.alpha, what.c_str(), st));
+    else if (plan_.iterative()) MFX_TRY(als_check_finite(h.val.get(), h.nnz, what.c_str(), st));  // (the direct explicit methods: none)
     return MFX_OK;
+}
+
+int Recommender::fold_rho(const AlsHalf& h, DevBuf<float>& rho) {
+    if (plan_.objective != FoldPlan::Objective::ImplicitReg) return MFX_OK;
+    MFX_TRY(rho.alloc(h.nseg));
+    return ialsr_rho_launch(h, (uint32_t) cols_, plan_.lambda, plan_.alpha0, plan_.nu, rho.get(), st_);
 }
 
 // mfx_rec_explain: the fold-in rows by the multi-right-hand-side families of als_solver.hip (Y as mfx_rec_fold_in's family
@@ -886,13 +797,14 @@ int Recommender::explain(int64_t nusers, int64_t nnz, const uint32_t* ptr, const
                          const uint32_t* targets, int32_t n_expl, uint32_t* expl_items, float* expl_contrib, float* totals, float* W_out,
                          float* Z_out, mfx_memspace space) {
     const char* fn = "mfx_rec_explain";
-    MFX_REQUIRE(fold_model_ >= 0, "%s: call mfx_rec_fold_in_setup (MFX_FOLD_ALS, MFX_FOLD_CCD, MFX_FOLD_IMPLICIT) or mfx_rec_fold_in_setup_reg first", fn);
-    MFX_REQUIRE(fold_model_ != MFX_FOLD_ALS_EXACT,
+    using M = FoldPlan::Method;
+    MFX_REQUIRE(plan_.method != M::None, "%s: call mfx_rec_fold_in_setup (MFX_FOLD_ALS, MFX_FOLD_CCD, MFX_FOLD_IMPLICIT) or mfx_rec_fold_in_setup_reg first", fn);
+    MFX_REQUIRE(plan_.method != M::DirectExact,
                 "%s: the rows of MFX_FOLD_ALS_EXACT are not the bits of the MFMA system whose factor the explanation uses; set up MFX_FOLD_ALS", fn);
-    MFX_REQUIRE(fold_model_ != kFoldCg,
+    MFX_REQUIRE(plan_.method != M::Cg,
                 "%s: not after mfx_rec_fold_in_cg_setup (the split over the entries needs the factor of a closed-form solve); set up "
                 "mfx_rec_fold_in_setup or mfx_rec_fold_in_setup_reg on a handle of rank <= 128", fn);
-    MFX_REQUIRE(fold_model_ != kFoldBlock && fold_model_ != kFoldBlockAls,
+    MFX_REQUIRE(plan_.explains(),
                 "%s: not after a block setup (a sweep is not a solve, the split over the entries does not hold); set up mfx_rec_fold_in_setup "
                 "or mfx_rec_fold_in_setup_reg on a handle of rank <= 128", fn);
     return explain_run(fn, nusers, nnz, ptr, idx, val, n_targets, targets, n_expl, expl_items, expl_contrib, totals, W_out, Z_out, nullptr,
@@ -905,7 +817,7 @@ int Recommender::explain_cg(int64_t nusers, int64_t nnz, const uint32_t* ptr, co
                             const uint32_t* targets, int32_t n_expl, uint32_t* expl_items, float* expl_contrib, float* totals, float* W_out,
                             float* Z_out, int32_t* row_steps, int32_t* target_steps, mfx_memspace space) {
     const char* fn = "mfx_rec_explain_cg";
-    MFX_REQUIRE(fold_model_ == kFoldCg,
+    MFX_REQUIRE(plan_.method == FoldPlan::Method::Cg,
                 "%s: call mfx_rec_fold_in_cg_setup first (after a closed-form setup mfx_rec_explain explains; a block sweep is not a solve)", fn);
     return explain_run(fn, nusers, nnz, ptr, idx, val, n_targets, targets, n_expl, expl_items, expl_contrib, totals, W_out, Z_out, row_steps,
                        target_steps, space);
@@ -949,36 +861,29 @@ int Recommender::explain_run(const char* fn, int64_t nusers, int64_t nnz, const 
     MFX_TRY(Y.alloc_zero((size_t) nu * k, st));
     MFX_TRY(Z.alloc_zero(npair * k, st));
     MFX_TRY(spd_fail.alloc_zero(1, st));
-    if (fold_model_ != kFoldCg) MFX_TRY(ws.alloc(std::max<size_t>(1, als_ws_floats(h.nslots, k))));
+    const FoldPlan& p = plan_;
+    const bool by_cg = p.method == FoldPlan::Method::Cg;  // (else Direct: explain and explain_cg let nothing else through)
+    if (!by_cg) MFX_TRY(ws.alloc(std::max<size_t>(1, als_ws_floats(h.nslots, k))));
     const uint32_t x_rows = (uint32_t) cols_;
+    MFX_TRY(fold_rho(h, rho));
     AlsMrhs m;
     m.targets = dt; m.n_targets = (uint32_t) n_targets; m.Z = Z.get();
-    m.lambda = fold_lambda_; m.alpha = fold_alpha_; m.G = fold_g_.get();
-    if (fold_robj_) {  // the regulariser of every query row, as fold_solve forms it
-        MFX_TRY(rho.alloc(nu));
-        MFX_TRY(ialsr_rho_launch(h, x_rows, fold_lambda_, fold_alpha0_, fold_nu_, rho.get(), st));
-        m.alpha0 = fold_alpha0_; m.rho = rho.get();
-    }
+    m.lambda = p.lambda; m.alpha = p.alpha; m.G = p.g.get();
+    m.alpha0 = p.alpha0; m.rho = rho.get();
     DevBuf<int32_t> counts, pair_counts;
-    switch (fold_model_) {
-        case kFoldCg: {  // the row as fold_solve runs it from zero, then the pairs
-            if (row_steps) MFX_TRY(counts.alloc(nu));
-            if (target_steps) MFX_TRY(pair_counts.alloc(npair));
-            FoldCg cg;
-            cg.reg = fold_cg_model_ == MFX_FOLD_IMPLICIT ? 0 : fold_cg_model_ == MFX_FOLD_ALS ? 1 : 2;
-            cg.lambda = fold_lambda_; cg.alpha = fold_alpha_;
-            cg.G = fold_g_.get(); cg.Minv = fold_minv_.get();
-            cg.steps = fold_sweeps_; cg.tol = fold_tol_;
-            MFX_TRY(foldcg_launch(h, hx_.get(), x_rows, k, cg, Y.get(), false, counts.get(), spd_fail.get(), st));
-            MFX_TRY(explaincg_launch(h, hx_.get(), x_rows, k, cg, dt, (uint32_t) n_targets, Z.get(), pair_counts.get(), st));
-            break;
+    if (by_cg) {  // the row as fold_solve runs it from zero, then the pairs
+        if (row_steps) MFX_TRY(counts.alloc(nu));
+        if (target_steps) MFX_TRY(pair_counts.alloc(npair));
+        const FoldCg cg = p.cg();
+        MFX_TRY(foldcg_launch(h, hx_.get(), x_rows, k, cg, Y.get(), false, counts.get(), spd_fail.get(), st));
+        MFX_TRY(explaincg_launch(h, hx_.get(), x_rows, k, cg, dt, (uint32_t) n_targets, Z.get(), pair_counts.get(), st));
+    } else {
+        switch (p.objective) {
+            case FoldPlan::Objective::Als: MFX_TRY(als_half_mrhs_launch(h, hx_.get(), x_rows, Y.get(), k, m, ws.get(), spd_fail.get(), st)); break;
+            case FoldPlan::Objective::Ccd: MFX_TRY(als_half_nreg_mrhs_launch(h, hx_.get(), x_rows, Y.get(), k, m, ws.get(), spd_fail.get(), st)); break;
+            case FoldPlan::Objective::Implicit: MFX_TRY(ials_half_mrhs_launch(h, hx_.get(), x_rows, Y.get(), k, m, ws.get(), spd_fail.get(), st)); break;
+            case FoldPlan::Objective::ImplicitReg: MFX_TRY(ialsr_half_mrhs_launch(h, hx_.get(), x_rows, Y.get(), k, m, ws.get(), spd_fail.get(), st)); break;
         }
-        case MFX_FOLD_ALS: MFX_TRY(als_half_mrhs_launch(h, hx_.get(), x_rows, Y.get(), k, m, ws.get(), spd_fail.get(), st)); break;
-        case MFX_FOLD_CCD: MFX_TRY(als_half_nreg_mrhs_launch(h, hx_.get(), x_rows, Y.get(), k, m, ws.get(), spd_fail.get(), st)); break;
-        default:
-            if (fold_robj_) MFX_TRY(ialsr_half_mrhs_launch(h, hx_.get(), x_rows, Y.get(), k, m, ws.get(), spd_fail.get(), st));
-            else MFX_TRY(ials_half_mrhs_launch(h, hx_.get(), x_rows, Y.get(), k, m, ws.get(), spd_fail.get(), st));
-            break;
     }
     MFX_HIP(hipStreamSynchronize(st));
     const auto t2 = clk::now();
@@ -1018,7 +923,10 @@ int Recommender::explain_run(const char* fn, int64_t nusers, int64_t nnz, const 
 
 int Recommender::fold_solve(int64_t nusers, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val, const float* W_init,
                             float* W_out, int32_t* sweeps_done, int32_t n_top, uint32_t* items, float* scores, mfx_memspace space) {
-    MFX_REQUIRE(fold_model_ >= 0, "mfx_rec_fold_in: call mfx_rec_fold_in_setup, mfx_rec_fold_in_block_setup, mfx_rec_fold_in_block_setup_als or "
+    using M = FoldPlan::Method;
+    using O = FoldPlan::Objective;
+    FoldPlan& p = plan_;
+    MFX_REQUIRE(p.method != M::None, "mfx_rec_fold_in: call mfx_rec_fold_in_setup, mfx_rec_fold_in_block_setup, mfx_rec_fold_in_block_setup_als or "
                 "mfx_rec_fold_in_cg_setup first");
     MFX_REQUIRE(nusers >= 0 && nusers < (int64_t) 0xFFFFFFFFll, "mfx_rec_fold_in: bad nusers %lld", (long long) nusers);
     MFX_REQUIRE(nnz >= 0 && nnz < (int64_t) 0xFFFF0000ll, "mfx_rec_fold_in: bad nnz %lld", (long long) nnz);
@@ -1035,7 +943,6 @@ int Recommender::fold_solve(int64_t nusers, int64_t nnz, const uint32_t* ptr, co
     const uint32_t nu = (uint32_t) nusers, k = (uint32_t) k_;
     AlsHalf h;
     MFX_TRY(fold_rows("mfx_rec_fold_in", nu, (uint64_t) nnz, ptr, idx, val, space, h));
-    const bool by_blocks = fold_model_ == kFoldBlock || fold_model_ == kFoldBlockAls || fold_model_ == kFoldCg;  // (no als_ws_floats slots)
     const auto t1 = clk::now();
 
     DevBuf<float> Y, ws, wq, rho;
@@ -1043,55 +950,43 @@ int Recommender::fold_solve(int64_t nusers, int64_t nnz, const uint32_t* ptr, co
     DevBuf<int32_t> counts;
     MFX_TRY(Y.alloc_zero((size_t) nu * k, st));
     MFX_TRY(spd_fail.alloc_zero(1, st));
-    if (fold_model_ != MFX_FOLD_ALS_EXACT && !by_blocks) MFX_TRY(ws.alloc(std::max<size_t>(1, als_ws_floats(h.nslots, k))));
+    if (p.method == M::Direct) MFX_TRY(ws.alloc(std::max<size_t>(1, als_ws_floats(h.nslots, k))));
     const uint32_t x_rows = (uint32_t) cols_;
-    if (fold_robj_) {  // the regulariser of every query row from its own entries, over the cols_ items
-        MFX_TRY(rho.alloc(nu));
-        MFX_TRY(ialsr_rho_launch(h, x_rows, fold_lambda_, fold_alpha0_, fold_nu_, rho.get(), st));
-    }
-    struct QueryWs {  // the per-query part of fold_b_ goes when the call returns
+    MFX_TRY(fold_rho(h, rho));
+    struct QueryWs {  // the per-query part of the plan's block state goes when the call returns
         IalsBlock& b;
         ~QueryWs() { b.P.release(); b.Z.release(); b.score.release(); b.ws.release(); }
-    } query_ws{fold_b_};
-    switch (fold_model_) {
-        case kFoldBlock:
-        case kFoldBlockAls:
-            if (W_init) MFX_TRY(Y.upload(W_init, (size_t) nu * k, space, st));
-            if (sweeps_done) MFX_TRY(counts.alloc(nu));
-            MFX_TRY(fold_b_.alloc_half(nu, h.nnz, h.nslots, st));
-            if (fold_model_ == kFoldBlock)
-                MFX_TRY(ialsb_fold_launch(fold_b_, h, hx_.get(), x_rows, Y.get(), fold_alpha_, fold_sweeps_, fold_tol_, counts.get(),
-                                          spd_fail.get(), st, fold_alpha0_, fold_robj_ ? rho.get() : nullptr));
+    } query_ws{p.b};
+    if (W_init) MFX_TRY(Y.upload(W_init, (size_t) nu * k, space, st));  // (both given to an iterative method only: fold_in_warm)
+    if (sweeps_done) MFX_TRY(counts.alloc(nu));
+    switch (p.method) {
+        case M::None: break;  // (refused above)
+        case M::Blocks:
+            MFX_TRY(p.b.alloc_half(nu, h.nnz, h.nslots, st));
+            if (p.implicit())
+                MFX_TRY(ialsb_fold_launch(p.b, h, hx_.get(), x_rows, Y.get(), p.alpha, p.cap, p.tol, counts.get(), spd_fail.get(), st, p.alpha0,
+                                          rho.get()));
             else
-                MFX_TRY(alsb_fold_launch(fold_b_, h, hx_.get(), x_rows, Y.get(), fold_lambda_, fold_reg_, fold_sweeps_, fold_tol_,
-                                         counts.get(), spd_fail.get(), st));
+                MFX_TRY(alsb_fold_launch(p.b, h, hx_.get(), x_rows, Y.get(), p.lambda, p.objective == O::Ccd ? 1 : 0, p.cap, p.tol, counts.get(),
+                                         spd_fail.get(), st));
             break;
-        case kFoldCg: {
-            if (W_init) MFX_TRY(Y.upload(W_init, (size_t) nu * k, space, st));
-            if (sweeps_done) MFX_TRY(counts.alloc(nu));
-            FoldCg m;
-            m.reg = fold_cg_model_ == MFX_FOLD_IMPLICIT ? 0 : fold_cg_model_ == MFX_FOLD_ALS ? 1 : 2;
-            m.lambda = fold_lambda_; m.alpha = fold_alpha_;
-            m.G = fold_g_.get(); m.Minv = fold_minv_.get();
-            m.steps = fold_sweeps_; m.tol = fold_tol_;
-            MFX_TRY(foldcg_launch(h, hx_.get(), x_rows, k, m, Y.get(), W_init != nullptr, counts.get(), spd_fail.get(), st));
+        case M::Cg:
+            MFX_TRY(foldcg_launch(h, hx_.get(), x_rows, k, p.cg(), Y.get(), W_init != nullptr, counts.get(), spd_fail.get(), st));
             break;
-        }
-        case MFX_FOLD_ALS:
-            MFX_TRY(als_half_launch(h, hx_.get(), x_rows, Y.get(), k, fold_lambda_, ws.get(), spd_fail.get(), st));
+        case M::DirectExact:
+            MFX_TRY(als_half_exact_launch(h, hx_.get(), Y.get(), k, p.lambda, spd_fail.get(), st));
             break;
-        case MFX_FOLD_ALS_EXACT:
-            MFX_TRY(als_half_exact_launch(h, hx_.get(), Y.get(), k, fold_lambda_, spd_fail.get(), st));
-            break;
-        case MFX_FOLD_CCD:
-            MFX_TRY(als_half_nreg_launch(h, hx_.get(), x_rows, Y.get(), k, fold_lambda_, ws.get(), spd_fail.get(), st));
-            break;
-        default:
-            if (fold_robj_)
-                MFX_TRY(ialsr_half_launch(h, hx_.get(), x_rows, Y.get(), k, fold_g_.get(), fold_alpha_, fold_alpha0_, rho.get(), ws.get(),
-                                          spd_fail.get(), st));
-            else
-                MFX_TRY(ials_half_launch(h, hx_.get(), x_rows, Y.get(), k, fold_g_.get(), fold_alpha_, ws.get(), spd_fail.get(), st));
+        case M::Direct:
+            switch (p.objective) {
+                case O::Als: MFX_TRY(als_half_launch(h, hx_.get(), x_rows, Y.get(), k, p.lambda, ws.get(), spd_fail.get(), st)); break;
+                case O::Ccd: MFX_TRY(als_half_nreg_launch(h, hx_.get(), x_rows, Y.get(), k, p.lambda, ws.get(), spd_fail.get(), st)); break;
+                case O::Implicit:
+                    MFX_TRY(ials_half_launch(h, hx_.get(), x_rows, Y.get(), k, p.g.get(), p.alpha, ws.get(), spd_fail.get(), st));
+                    break;
+                case O::ImplicitReg:
+                    MFX_TRY(ialsr_half_launch(h, hx_.get(), x_rows, Y.get(), k, p.g.get(), p.alpha, p.alpha0, rho.get(), ws.get(), spd_fail.get(), st));
+                    break;
+            }
             break;
     }
     MFX_HIP(hipStreamSynchronize(st));

@@ -7,10 +7,68 @@
 // rank count of rec_rank.hip runs too, is in rec_tiles.hpp.
 #pragma once
 
-#include "als_solver.hpp"  // IalsBlock (fold-in by block sweeps)
+#include "als_solver.hpp"  // IalsBlock (fold-in by block sweeps), FoldCg
 #include "common.hpp"
 
 namespace mfx {
+
+// What a fold-in setup leaves in the handle: how the query rows are solved, on which objective, with which parameters, and
+// the device state built for that.  The two axes are independent; fold_setup builds the combinations that exist.  A setup
+// builds a fresh plan, so a field it does not set holds its default, never what an earlier setup left.
+struct FoldPlan {
+    // Direct: one closed-form solve per row at k <= 128 by the MFMA half-sweep families; DirectExact: MFX_FOLD_ALS_EXACT, the
+    // same system in the reference's order of operations; Blocks: block subspace sweeps; Cg: conjugate gradients
+    enum class Method { None, Direct, DirectExact, Blocks, Cg };
+    // what goes on the diagonal: Als lambda, Ccd fp32(lambda * entries of the row), Implicit the base Gramian's lambda,
+    // ImplicitReg fp32(lambda (n + alpha0 cols)^nu) per query row, with alpha0 the weight of the unobserved pairs
+    enum class Objective { Als, Ccd, Implicit, ImplicitReg };
+    Method method = Method::None;
+    Objective objective = Objective::Als;
+    float lambda = 0.f, alpha = 0.f, alpha0 = 1.f, nu = 0.f;  // alpha: 0 on an explicit objective
+    int32_t cap = 0;  // the most sweeps (Blocks) or steps (Cg) a row gets
+    float tol = 0.f;
+    // Direct: the base Gramian [k][k] (Implicit: H^T H + lambda I; ImplicitReg: fp32(alpha0 H^T H)); Cg / Implicit:
+    // G = H^T H + lambda I and minv ~ G^-1
+    DevBuf<float> g, minv;
+    // Blocks: H block-major, and on the implicit objectives G (as above) with its diagonal blocks; P, Z, the scores and the
+    // split-segment slots live for one query
+    IalsBlock b;
+
+    bool implicit() const { return objective == Objective::Implicit || objective == Objective::ImplicitReg; }
+    // takes W_init and reports sweeps_done (mfx_rec_fold_in_warm); needs no als_ws_floats workspace
+    bool iterative() const { return method == Method::Blocks || method == Method::Cg; }
+    // closed-form, and the factor is the MFMA system's: what mfx_rec_explain splits
+    bool explains() const { return method == Method::Direct; }
+    FoldCg cg() const {  // Cg only
+        FoldCg m;
+        m.reg = implicit() ? 0 : objective == Objective::Als ? 1 : 2;
+        m.lambda = lambda; m.alpha = alpha;
+        m.G = g.get(); m.Minv = minv.get();
+        m.steps = cap; m.tol = tol;
+        return m;
+    }
+};
+
+// What a setup entry point asks for.  arg is its model (Direct, DirectExact, Cg) or reg (Blocks on an explicit objective)
+// argument as the caller gave it, which fold_setup checks in the entry point's own place; method and objective are what a
+// valid one selects.
+struct FoldSpec {
+    FoldPlan::Method method;
+    FoldPlan::Objective objective;
+    int arg = 0;
+    float lambda = 0.f, alpha = 0.f, alpha0 = 1.f, nu = 0.f;
+    int32_t block = 0, cap = 0;  // block: the requested width (Blocks), 0 = chosen from k; cap: sweeps or steps
+    float tol = 0.f;
+    // for an entry point that takes a model: Direct or Cg as asked (DirectExact for MFX_FOLD_ALS_EXACT) and the model's
+    // objective; fold_setup refuses by arg a model that is unknown or not for the method, so what those map to is never used
+    static FoldSpec of_model(FoldPlan::Method method, int model, float lambda, float alpha) {
+        using O = FoldPlan::Objective;
+        FoldSpec s{method == FoldPlan::Method::Direct && model == MFX_FOLD_ALS_EXACT ? FoldPlan::Method::DirectExact : method,
+                   model == MFX_FOLD_IMPLICIT ? O::Implicit : model == MFX_FOLD_CCD ? O::Ccd : O::Als, model};
+        s.lambda = lambda; s.alpha = alpha;
+        return s;
+    }
+};
 
 class Recommender {
 public:
@@ -18,19 +76,9 @@ public:
                       int layout, const mfx_csx* exclude, mfx_memspace space, int device);
     int query(int64_t nusers, const uint32_t* users, int32_t n_top, uint32_t* items, float* scores,
               mfx_memspace space, int item_slices);
-    // fold-in (mfx_rec_fold_in_setup / mfx_rec_fold_in): solve query rows against H, then score them
-    int fold_in_setup(int model, float lambda, float alpha);
-    // the same by block subspace sweeps (mfx_rec_fold_in_block_setup): any k, up to `sweeps` sweeps per row
-    int fold_in_block_setup(float lambda, float alpha, int32_t block, int32_t sweeps, float tol);
-    // block sweeps on the explicit objective (mfx_rec_fold_in_block_setup_als): reg 0 = lambda, 1 = lambda * entries of the row
-    int fold_in_block_setup_als(float lambda, int32_t reg, int32_t block, int32_t sweeps, float tol);
-    // the implicit objective with an unobserved weight alpha0 and rho_u = fp32(lambda (n_u + alpha0 cols)^nu) per query row
-    // (mfx_rec_fold_in_setup_reg: k <= 128; mfx_rec_fold_in_block_setup_reg: block sweeps)
-    int fold_in_setup_reg(float lambda, float alpha, float alpha0, float nu);
-    int fold_in_block_setup_reg(float lambda, float alpha, float alpha0, float nu, int32_t block, int32_t sweeps, float tol);
-    // by preconditioned conjugate gradients (mfx_rec_fold_in_cg_setup, rec_foldin_cg.hip): MFX_FOLD_ALS / _CCD / _IMPLICIT at
-    // any k <= 1024, up to `steps` steps per row, a row stops once |b - A y| <= tol |b|
-    int fold_in_cg_setup(int model, float lambda, float alpha, int32_t steps, float tol);
+    // fold-in: the one setup behind the seven mfx_rec_fold_in_*setup* entry points (fn: the entry point, for its refusals),
+    // then mfx_rec_fold_in: solve query rows against H and score them
+    int fold_setup(const char* fn, const FoldSpec& s);
     int fold_in(int64_t nusers, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val, float* W_out,
                 int32_t n_top, uint32_t* items, float* scores, mfx_memspace space);
     // mfx_rec_fold_in_warm: after a block or cg setup only; W_init [nusers][k] / sweeps_done [nusers] in `space`, or NULL
@@ -82,13 +130,12 @@ private:
     // per CU; at most cap, and none empty.  rank() passes its item_slices; topn() calls this for item_slices = 0 only and
     // takes a forced count as given (empty slices included: they merge as padding), as it always did.
     int pick_slices(int forced, int64_t blocks, int cap) const;
-    // What every fold-in setup starts with: the device, fold_model_ = -1 until the setup is through, what another kind of
-    // setup kept (fold_g_ / fold_b_) dropped as asked and fold_minv_ always (the cg setup builds it afterwards), hx_ from the tiles.
-    int fold_setup_begin(bool drop_g, bool drop_b);
     // fac_keep_ (when keep is set) and fac_cos_ (after similar_setup) from the device filter bytes keep (NULL: no filter)
     int build_facs(const uint8_t* keep);
     // hq_ from the tiles unless it is there already (similar_setup builds it too): the rows of H that rank() gathers
     int ensure_hq();
+    // the regulariser of every query row of h from its own entries into rho [h.nseg], under ImplicitReg (else rho stays empty)
+    int fold_rho(const AlsHalf& h, DevBuf<float>& rho);
     int fold_rows(const char* fn, uint32_t nu, uint64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val, mfx_memspace space,
                   AlsHalf& h);
     int explain_run(const char* fn, int64_t nusers, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val, int32_t n_targets,
@@ -117,24 +164,10 @@ private:
     // (row pointers and indices of the identity exclusion), inverse norms with NaN at the filtered items [nblk_ * 32]
     DevBuf<float> hq_, sim_n2_, sim_c_, fac_cos_;
     DevBuf<uint32_t> sim_id_;
-    // fold-in: model (-1 = not set up, kFoldBlock = block sweeps), H row-major [cols_ + 1][k_] with a zero last row, base Gramian [k_][k_] (implicit)
-    int fold_model_ = -1;
-    float fold_lambda_ = 0.f, fold_alpha_ = 0.f;
-    bool fold_robj_ = false;  // a _reg setup: fold_g_ / fold_b_.G hold fp32(alpha0 H^T H), rho is formed per query batch
-    float fold_alpha0_ = 1.f, fold_nu_ = 0.f;
-    DevBuf<float> hx_, fold_g_;
-    // fold-in by block sweeps: G = H^T H + lambda I, H block-major and the diagonal blocks of G, all packed at setup; P, Z,
-    // the scores and the split-segment slots live for one query
-    // (kFoldBlockAls: the explicit objective -- no G, only H block-major)
-    // (kFoldCg: conjugate gradients on the objective fold_cg_model_ -- fold_g_ = G and fold_minv_ ~ G^-1 [k_][k_] for the
-    // implicit one, nothing but hx_ for the explicit ones; fold_sweeps_ / fold_tol_ hold the step cap and the residual bound)
-    static constexpr int kFoldBlock = 100, kFoldBlockAls = 101, kFoldCg = 102;
-    int fold_cg_model_ = 0;
-    DevBuf<float> fold_minv_;
-    int32_t fold_reg_ = 0;
-    IalsBlock fold_b_;
-    int32_t fold_sweeps_ = 0;
-    float fold_tol_ = 0.f;
+    // fold-in: H row-major [cols_ + 1][k_] with a zero last row (built by the first setup, the same for every plan), and what
+    // the last setup that went through left (method None: not set up)
+    DevBuf<float> hx_;
+    FoldPlan plan_;
     double fold_s_[3] = {0, 0, 0};  // host build / solve / score seconds of the last fold-in
     double rank_s_[3] = {0, 0, 0};  // device seconds of the last rank: target keys / counting pass / exclusion correction
     double expl_s_[3] = {0, 0, 0};  // seconds of the last explain of either kind: host build + checks / solve / totals + contributions
