@@ -104,6 +104,26 @@ int AlsSolver::create_block(AlsSolver** out, const mfx_csx* R, const mfx_params*
     return MFX_OK;
 }
 
+int AlsSolver::create_cg(AlsSolver** out, const mfx_csx* R, const mfx_params* p, float alpha, int32_t steps, float tol, mfx_memspace space) {
+    MFX_REQUIRE(out && R && p, "mfx_ials_cg_create: null argument");
+    MFX_REQUIRE(space == MFX_HOST || space == MFX_DEVICE, "mfx_ials_cg_create: bad memory space");
+    MFX_REQUIRE(std::isfinite(alpha) && alpha >= 0.f, "mfx_ials_cg_create: alpha = %g (finite and >= 0 required)", (double) alpha);
+    MFX_REQUIRE(p->k >= 1 && p->k <= kIalsBlockMaxRank, "implicit ALS by conjugate gradients: rank k = %u not supported (1 <= k <= %u)", p->k,
+                kIalsBlockMaxRank);
+    MFX_REQUIRE(steps >= 1, "implicit ALS by conjugate gradients: steps = %d (>= 1 required)", steps);
+    MFX_REQUIRE(std::isfinite(tol) && tol >= 0.f, "implicit ALS by conjugate gradients: tol = %g (finite and >= 0 required)", (double) tol);
+    MFX_REQUIRE(p->schedule == 1, "implicit ALS by conjugate gradients: schedule must be 1 (there is no as-written mode)");
+    std::unique_ptr<AlsSolver> s(new AlsSolver());
+    s->implicit_ = true;
+    s->alpha_ = alpha;
+    s->cg_ = true;
+    s->cg_steps_ = steps;
+    s->cg_tol_ = tol;
+    MFX_TRY(s->init(R, nullptr, p, space, nullptr));
+    *out = s.release();
+    return MFX_OK;
+}
+
 int AlsSolver::create_implicit_reg(AlsSolver** out, const mfx_csx* R, const mfx_params* p, float alpha, float alpha0, float nu, int32_t block,
                                    mfx_memspace space) {
     const bool blk = block >= 0;
@@ -185,7 +205,7 @@ int AlsSolver::init(const mfx_csx* R, const mfx_coo* T, const mfx_params* p, mfx
     MFX_REQUIRE(R->rows > 0 && R->cols > 0 && R->nnz >= 0, "bad matrix shape");
     MFX_REQUIRE(R->rows < (int64_t) 0xFFFFFFFFll && R->cols < (int64_t) 0xFFFFFFFFll &&
                     R->nnz < (int64_t) 0xFFFF0000ll, "matrix exceeds 32-bit index range");
-    MFX_REQUIRE(p->k >= 1 && p->k <= (block_ ? kIalsBlockMaxRank : 128u), "ALS: rank k = %u not supported (1 <= k <= 128)", p->k);
+    MFX_REQUIRE(p->k >= 1 && p->k <= (block_ || cg_ ? kIalsBlockMaxRank : 128u), "ALS: rank k = %u not supported (1 <= k <= 128)", p->k);
     MFX_REQUIRE(R->csc_col_ptr && R->csr_row_ptr, "null CSR/CSC pointer array");
     p_ = *p;
     device_ = p->device;
@@ -216,7 +236,7 @@ int AlsSolver::init(const mfx_csx* R, const mfx_coo* T, const mfx_params* p, mfx
     // one extra, all-zero row each: the Gramian kernel gathers it for positions past a segment's end
     MFX_TRY(W_.alloc_zero(((size_t) m_ + 1) * k_, st_));
     MFX_TRY(H_.alloc_zero(((size_t) n_ + 1) * k_, st_));
-    MFX_TRY(ws_.alloc(block_ ? 1 : std::max<size_t>(1, als_ws_floats(std::max(rows_.nslots, cols_.nslots), k_))));
+    MFX_TRY(ws_.alloc(block_ || cg_ ? 1 : std::max<size_t>(1, als_ws_floats(std::max(rows_.nslots, cols_.nslots), k_))));
     MFX_TRY(spd_fail_.alloc_zero(1, st_));
     if (std::getenv("MFX_ALS_PHASES")) { MFX_TRY(phases_.alloc_zero((size_t) kPhaseCopies * 8, st_)); }
     nnz_test_ = T ? T->nnz : 0;
@@ -238,6 +258,10 @@ int AlsSolver::init(const mfx_csx* R, const mfx_coo* T, const mfx_params* p, mfx
             MFX_REQUIRE(rows_.nnz == cols_.nnz, "implicit ALS by block sweeps: the two orientations hold %llu and %llu entries",
                         (unsigned long long) rows_.nnz, (unsigned long long) cols_.nnz);
             MFX_TRY(bs_.alloc(k_, block_, std::max(m_, n_), std::max(m_, n_), rows_.nnz, std::max(rows_.nslots, cols_.nslots), st_));
+        } else if (cg_) {  // (the objective's workspace: on the first loss(), as for the block sweeps)
+            MFX_TRY(cgs_.alloc(k_, std::max(m_, n_), std::max(m_, n_), std::max(rows_.nslots, cols_.nslots), cg_steps_));
+            MFX_TRY(cg_fail_.alloc_zero(4, st_));
+            MFX_TRY(cg_cnt_.alloc_zero(6, st_));
         } else {
             MFX_TRY(G_.alloc((size_t) k_ * k_));
             MFX_TRY(gpart_.alloc(ials_base_ws_floats(std::max(m_, n_), k_)));
@@ -309,7 +333,8 @@ int AlsSolver::set_factors(const float* W, const float* H, mfx_memspace space) {
     MFX_REQUIRE(H, "mfx_als_set_factors: H is required");
     MFX_TRY(use_device(device_));
     if (W) MFX_TRY(W_.upload(W, (size_t) m_ * k_, space, st_));
-    else if (block_) MFX_HIP(hipMemsetAsync(W_.get(), 0, sizeof(float) * (size_t) m_ * k_, st_));  // W is the warm start of the first W-half
+    else if (block_ || cg_) MFX_HIP(hipMemsetAsync(W_.get(), 0, sizeof(float) * (size_t) m_ * k_, st_));  // W is the warm start of the first W-half
+    w_cold_ = !W;
     MFX_TRY(H_.upload(H, (size_t) n_ * k_, space, st_));
     MFX_HIP(hipStreamSynchronize(st_));
     factors_set_ = true;
@@ -317,7 +342,13 @@ int AlsSolver::set_factors(const float* W, const float* H, mfx_memspace space) {
 }
 
 int AlsSolver::half_sweep(const AlsHalf& h, const float* X, uint32_t x_rows, float* Y, uint32_t y_lo, const float* rho, hipEvent_t ev_gram) {
-    if (block_ && !implicit_) {
+    if (cg_) {  // &h == &rows_: the W-half, the only one that may be cold (Y is then zero)
+        const int half = &h == &rows_ ? 0 : 1;
+        const bool warm = half == 1 || !w_cold_;
+        MFX_TRY(ialscg_half_launch(cgs_, h, X, x_rows, Y, warm, p_.lambda, alpha_, cg_steps_, cg_tol_, cg_fail_.get() + 2 * half,
+                                   cg_cnt_.get() + 3 * half, ev_gram, ev_[6 + half], st_));
+        if (half == 0) w_cold_ = false;
+    } else if (block_ && !implicit_) {
         MFX_TRY(alsb_half_launch(bs_, h, X, x_rows, Y, p_.lambda, reg_, spd_fail_.get(), st_));
     } else if (block_ && robj_) {
         MFX_TRY(ialsrb_gramian(bs_, X, x_rows, alpha0_, st_));
@@ -349,6 +380,7 @@ int AlsSolver::iterate(int n_iter, int with_rmse, mfx_iter_report* reports) {
     if (comm_ && !shards_met_ && n_iter > 0) MFX_TRY(meet_shards());
     for (int it = 0; it < n_iter; ++it) {
         MFX_HIP(hipMemsetAsync(spd_fail_.get(), 0, sizeof(uint32_t), st_));
+        if (cg_) MFX_HIP(hipMemsetAsync(cg_fail_.get(), 0, sizeof(uint32_t) * 4, st_));
         MFX_HIP(hipEventRecord(ev_[0], st_));
         MFX_TRY(half_sweep(rows_, H_.get(), n_, W_.get(), row_lo_, rho_rows_.get(), ev_[4]));  // (ev_[4]: the base Gramian of H is done)
         if (comm_) MFX_TRY(exchange(W_.get(), row_bounds_));
@@ -371,10 +403,33 @@ int AlsSolver::iterate(int n_iter, int with_rmse, mfx_iter_report* reports) {
         MFX_HIP(hipEventRecord(ev_[3], st_));
         uint32_t bad = 0;
         MFX_HIP(hipMemcpyAsync(&bad, spd_fail_.get(), sizeof(uint32_t), hipMemcpyDeviceToHost, st_));
+        uint32_t cg_bad[4] = {0, 0, 0, 0};
+        unsigned long long cg_cnt[6] = {0, 0, 0, 0, 0, 0};
+        if (cg_) {
+            MFX_HIP(hipMemcpyAsync(cg_bad, cg_fail_.get(), sizeof(cg_bad), hipMemcpyDeviceToHost, st_));
+            MFX_HIP(hipMemcpyAsync(cg_cnt, cg_cnt_.get(), sizeof(cg_cnt), hipMemcpyDeviceToHost, st_));
+        }
         MFX_HIP(hipStreamSynchronize(st_));
+        if (cg_) {  // a failed inverse or failed rows: reported as the failed systems of the other solvers are
+            for (int hf = 0; hf < 2; ++hf) {
+                for (int q = 0; q < 3; ++q) cg_stats_[4 * hf + q] = (int64_t) cg_cnt[3 * hf + q];
+                cg_stats_[4 * hf + 3] = (int64_t) cg_bad[2 * hf + 1];
+            }
+            cg_stats_set_ = true;
+            bad = cg_bad[0] + cg_bad[1] + cg_bad[2] + cg_bad[3];
+        }
         if (with_rmse && global_test_nnz_ > 0) rmse = std::sqrt(sum / (double) global_test_nnz_);
-        float ms_w = 0.f, ms_h = 0.f, ms_r = 0.f, ms_gh = 0.f, ms_gw = 0.f;
-        if (implicit_) {
+        float ms_w = 0.f, ms_h = 0.f, ms_r = 0.f, ms_gh = 0.f, ms_gw = 0.f, ms_ih = 0.f, ms_iw = 0.f;
+        if (cg_) {  // Gramian, inverse, solve of either half
+            MFX_HIP(hipEventElapsedTime(&ms_gh, ev_[0], ev_[4]));
+            MFX_HIP(hipEventElapsedTime(&ms_ih, ev_[4], ev_[6]));
+            MFX_HIP(hipEventElapsedTime(&ms_w, ev_[6], ev_[1]));
+            MFX_HIP(hipEventElapsedTime(&ms_gw, ev_[1], ev_[5]));
+            MFX_HIP(hipEventElapsedTime(&ms_iw, ev_[5], ev_[7]));
+            MFX_HIP(hipEventElapsedTime(&ms_h, ev_[7], ev_[2]));
+            t_half_[2] += ms_gh * 1e-3; t_half_[3] += ms_gw * 1e-3; n_half_[2]++; n_half_[3]++;
+            t_half_[4] += ms_ih * 1e-3; t_half_[5] += ms_iw * 1e-3; n_half_[4]++; n_half_[5]++;
+        } else if (implicit_) {
             MFX_HIP(hipEventElapsedTime(&ms_gh, ev_[0], ev_[4]));
             MFX_HIP(hipEventElapsedTime(&ms_w, ev_[4], ev_[1]));
             MFX_HIP(hipEventElapsedTime(&ms_gw, ev_[1], ev_[5]));
@@ -388,7 +443,7 @@ int AlsSolver::iterate(int n_iter, int with_rmse, mfx_iter_report* reports) {
         t_half_[0] += ms_w * 1e-3; t_half_[1] += ms_h * 1e-3; n_half_[0]++; n_half_[1]++;
         mfx_iter_report rep;
         rep.rank_time = 0.0;
-        rep.update_time = (ms_gh + ms_w + ms_gw + ms_h) * 1e-3;
+        rep.update_time = (ms_gh + ms_ih + ms_w + ms_gw + ms_iw + ms_h) * 1e-3;
         rep.rmse = rmse;
         rep.rmse_time = ms_r * 1e-3;
         update_acc_ += rep.update_time;
@@ -420,16 +475,25 @@ int AlsSolver::kernel_times(int cap, const char** names, double* seconds, int64_
     static const char* nm_impl[4] = {"ials_half_rows(W over H)", "ials_half_cols(H over W)", "ials_base_gram(H)", "ials_base_gram(W)"};
     static const char* nm_block[4] = {"ialsb_half_rows(W over H)", "ialsb_half_cols(H over W)", "ialsb_base_gram(H)", "ialsb_base_gram(W)"};
     static const char* nm_eblock[2] = {"alsb_half_rows(W over H)", "alsb_half_cols(H over W)"};
+    static const char* nm_cg[6] = {"ialscg_half_rows(W over H)", "ialscg_half_cols(H over W)", "ialscg_base_gram(H)", "ialscg_base_gram(W)",
+                                   "ialscg_inverse(H)", "ialscg_inverse(W)"};
     int n = 0;
-    for (int i = 0; i < 4 && n < cap; ++i) {
+    for (int i = 0; i < 6 && n < cap; ++i) {
         if (!n_half_[i]) continue;
-        if (names) names[n] = block_ && !implicit_ ? nm_eblock[i] : block_ ? nm_block[i] : implicit_ ? nm_impl[i] : nm[i];
+        if (names) names[n] = cg_ ? nm_cg[i] : block_ && !implicit_ ? nm_eblock[i] : block_ ? nm_block[i] : implicit_ ? nm_impl[i] : nm[i];
         if (seconds) seconds[n] = t_half_[i];
         if (launches) launches[n] = n_half_[i];
         ++n;
     }
-    for (int i = 0; i < 4; ++i) { t_half_[i] = 0; n_half_[i] = 0; }
+    for (int i = 0; i < 6; ++i) { t_half_[i] = 0; n_half_[i] = 0; }
     return n;
+}
+
+int AlsSolver::cg_stats(int64_t out[8]) {
+    MFX_REQUIRE(cg_, "mfx_ials_cg_stats: not a handle of mfx_ials_cg_create");
+    MFX_REQUIRE(out, "mfx_ials_cg_stats: out is NULL");
+    for (int i = 0; i < 8; ++i) out[i] = cg_stats_set_ ? cg_stats_[i] : 0;
+    return MFX_OK;
 }
 
 int AlsSolver::loss(double* out) {

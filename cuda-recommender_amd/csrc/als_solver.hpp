@@ -54,6 +54,8 @@ struct IalsBlock {
     int alloc_half(uint32_t max_seg, uint64_t nnz, uint32_t nslots, hipStream_t st);
     // explicit ALS by block sweeps (alsb_*): Xb and the per-half part, no G, gpart, Gbb
     int alloc_explicit(uint32_t k, uint32_t d, uint32_t max_rows_x, uint32_t max_seg, uint64_t nnz, uint32_t nslots, hipStream_t st);
+    // G and gpart alone, for ialsb_gramian over up to max_rows_x rows (implicit ALS by conjugate gradients)
+    int alloc_gramian(uint32_t k, uint32_t max_rows_x);
 };
 constexpr uint32_t kIalsBlockMaxRank = 1024, kIalsBlockMaxBlock = 128;
 inline uint32_t ialsb_default_block(uint32_t k) { return k < 64 ? k : 64; }  // mfx_ials_block_create, block = 0
@@ -151,8 +153,47 @@ int foldcg_inverse(const float* G, uint32_t k, float* Minv);
 // Y must be zero.  A row without entries or with b = 0 is zero and counts 0 steps.  tol = 0: nothing is read back; tol > 0: the
 // host reads one counter per step and stops when every row is frozen.  counts: device [h.nseg] (steps applied) or NULL.
 // *fail counts the rows that met <p, A p> < 0 or a non-finite one (they come back as NaN).
+// ws: NULL = the call allocates its vectors and frees them; else a caller-owned set (FoldCgWs::alloc) large enough for h, k
+// and m.steps, reused from call to call.  frozen of ws then tells afterwards which rows met the stop rule.
+struct FoldCgWs {
+    DevBuf<float> R, Z, P, Q;    // [max_seg][k] each: 16 k bytes per row
+    DevBuf<float> part, bb, gamma;
+    DevBuf<uint32_t> frozen, active;
+    int alloc(uint32_t max_seg, uint32_t k, uint32_t nslots, int32_t steps);
+};
 int foldcg_launch(const AlsHalf& h, const float* X, uint32_t x_rows, uint32_t k, const FoldCg& m, float* Y, bool warm, int32_t* counts,
-                  uint32_t* fail, hipStream_t st);
+                  uint32_t* fail, hipStream_t st, FoldCgWs* ws = nullptr);
+
+// Device inverse of one symmetric positive definite matrix (spd_inverse.hip; mfx_spd_inverse): Minv [k][k] ~ G^-1
+// for G [k][k], both fp32 on the device, 1 <= k <= 1024, by a blocked Cholesky G = L L^T, a blocked L^-1 and Minv = L^-T L^-1
+// on 32 x 32 MFMA tiles (the diagonal blocks in fp64 in LDS).  G is not modified; Minv is exactly symmetric and its bits depend
+// on (G, k) alone.  ws: spd_inverse_ws_floats(k) floats.  Stream-ordered launches only; nothing is read back.  A pivot <= 0 or
+// not finite counts into *fail (device) and the stages still run to their end: Minv is then unspecified.
+size_t spd_inverse_ws_floats(uint32_t k);
+int spd_inverse_launch(const float* G, uint32_t k, float* Minv, float* ws, uint32_t* fail, hipStream_t st);
+int spd_inverse_op(int64_t k, const float* A, float* Ainv, int device);  // host pointers; MFX_ERR_INVALID when A is not positive definite
+
+// Implicit ALS by preconditioned conjugate gradients (ials_cg.hip; mfx_ials_cg_create): what a half-sweep at rank
+// k <= 1024 keeps on the device besides the factors.  One set serves both orientations.  The four CG vectors are allocated
+// once for the larger side: 16 k bytes per row of it on top of the factors.
+struct IalsCg {
+    uint32_t k = 0;
+    IalsBlock gb;                 // G and its partials alone (IalsBlock::alloc_gramian)
+    DevBuf<float> Minv, inv_ws;   // [k][k] ~ G^-1, the workspace of spd_inverse_launch
+    FoldCgWs ws;
+    DevBuf<int32_t> counts;       // [max_seg]: steps applied to every row of the last half
+    int alloc(uint32_t k, uint32_t max_rows_x, uint32_t max_seg, uint32_t nslots, int32_t steps);
+};
+// One half in place on Y [h.nseg][k] over X [x_rows + 1][k] (last row zeros): G = ialsb_gramian(X, lambda), Minv =
+// spd_inverse_launch(G), foldcg_launch from Y (warm) or from zero (Y must be zero).  fails: device [2], the inverse's pivots and
+// the rows that failed, added to; stats: device [3], set to the row-steps applied, the most steps of a row and the rows that
+// used all `steps` without meeting tol (0 when tol = 0).  ev_gram / ev_inv (or NULL): recorded after the Gramian / the inverse.
+int ialscg_half_launch(IalsCg& c, const AlsHalf& h, const float* X, uint32_t x_rows, float* Y, bool warm, float lambda, float alpha,
+                       int32_t steps, float tol, uint32_t* fails, unsigned long long* stats, hipEvent_t ev_gram, hipEvent_t ev_inv,
+                       hipStream_t st);
+int ials_cg_half_op(int64_t nseg, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val, int64_t nrows_x, const float* X,
+                    const float* Y_in, float* Y_out, int64_t k, float lambda, float alpha, int32_t steps, float tol, int32_t* counts,
+                    int device);
 
 class AlsSolver {
 public:
@@ -169,6 +210,11 @@ public:
     // mfx_ials_block_create_reg: block >= 0)
     static int create_implicit_reg(AlsSolver** out, const mfx_csx* R, const mfx_params* p, float alpha, float alpha0, float nu, int32_t block,
                                    mfx_memspace space);
+    // implicit feedback by preconditioned conjugate gradients (mfx_ials_cg_create): k <= 1024, at most `steps` steps per row
+    // and half, a row stops once |b - A y| <= tol |b| (tol = 0: never)
+    static int create_cg(AlsSolver** out, const mfx_csx* R, const mfx_params* p, float alpha, int32_t steps, float tol, mfx_memspace space);
+    // the last iteration of a create_cg handle, W-half then H-half: row-steps, most steps of a row, rows out of steps, failed rows
+    int cg_stats(int64_t out[8]);
     bool implicit() const { return implicit_; }
     int loss(double* out);  // implicit only: the objective at the current factors (ials.hip)
     ~AlsSolver();
@@ -207,9 +253,10 @@ private:
     int64_t iter_ = 0;
     double update_acc_ = 0;
     bool factors_set_ = false;
-    hipEvent_t ev_[6] = {};
-    double t_half_[4] = {0, 0, 0, 0};  // [0], [1]: the two half-sweeps; implicit: [2], [3] the base Gramians of H and W
-    int64_t n_half_[4] = {0, 0, 0, 0};
+    hipEvent_t ev_[8] = {};
+    // [0], [1]: the two half-sweeps; implicit: [2], [3] the base Gramians of H and W; cg_: [4], [5] their inverses
+    double t_half_[6] = {0, 0, 0, 0, 0, 0};
+    int64_t n_half_[6] = {0, 0, 0, 0, 0, 0};
     // implicit feedback
     bool implicit_ = false;
     float alpha_ = 0.f;
@@ -222,6 +269,15 @@ private:
     bool robj_ = false;
     float alpha0_ = 1.f, nu_ = 0.f;
     DevBuf<float> rho_rows_, rho_cols_;  // [m_], [n_]: formed once, the pattern of R is fixed
+    // implicit feedback by conjugate gradients (create_cg)
+    bool cg_ = false, w_cold_ = false;   // w_cold_: set_factors got no W, the next W-half starts from zero
+    int32_t cg_steps_ = 0;
+    float cg_tol_ = 0.f;
+    IalsCg cgs_;
+    DevBuf<uint32_t> cg_fail_;           // [4]: inverse pivots and failed rows of the W-half, of the H-half
+    DevBuf<unsigned long long> cg_cnt_;  // [6]: the three counts of ialscg_half_launch, W-half then H-half
+    int64_t cg_stats_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    bool cg_stats_set_ = false;
 };
 
 // Launches one half-sweep: Y[seg] = argmin over segment `seg` given factor rows X[x_rows + 1][k],

@@ -277,6 +277,45 @@ int mfx_ials_block_half(int64_t nseg, int64_t nnz, const uint32_t* ptr, const ui
         return ials_block_half_op(nseg, nnz, ptr, idx, val, nrows_x, X, Y_in, Y_out, k, block, lambda, alpha, device);
     });
 }
+/* ------------------------------------------------------------------ implicit ALS by conjugate gradients */
+int mfx_ials_cg_create(mfx_als_t* out, const mfx_csx* R, const mfx_params* p, float alpha, int32_t steps, float tol, mfx_memspace space) {
+    return guarded("mfx_ials_cg_create", [&]() -> int {
+        MFX_REQUIRE(out, "mfx_ials_cg_create: out is NULL");
+        *out = nullptr;
+        AlsSolver* s = nullptr;
+        MFX_TRY(AlsSolver::create_cg(&s, R, p, alpha, steps, tol, space));  // (argument checks before the device is touched)
+        *out = new mfx_als_s{s};
+        return MFX_OK;
+    });
+}
+int mfx_ials_cg_stats(mfx_als_t s, int64_t out[8]) {
+    return guarded("mfx_ials_cg_stats", [&]() -> int {
+        MFX_REQUIRE(s && s->impl, "mfx_ials_cg_stats: null handle");
+        return s->impl->cg_stats(out);
+    });
+}
+int mfx_ials_cg_half(int64_t nseg, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val, int64_t nrows_x, const float* X,
+                     const float* Y_in, float* Y_out, int64_t k, float lambda, float alpha, int32_t steps, float tol, int32_t* counts,
+                     int device) {
+    return guarded("mfx_ials_cg_half", [&]() -> int {
+        MFX_REQUIRE(nseg > 0 && nnz >= 0 && ptr && X && Y_out && nrows_x > 0, "mfx_ials_cg_half: bad argument");
+        MFX_REQUIRE(nnz == 0 || (idx && val), "mfx_ials_cg_half: null idx / val with nnz > 0");
+        MFX_REQUIRE(k >= 1 && k <= (int64_t) kIalsBlockMaxRank, "implicit ALS by conjugate gradients: rank k = %lld not supported (1 <= k <= %u)",
+                    (long long) k, kIalsBlockMaxRank);
+        MFX_REQUIRE(steps >= 1, "implicit ALS by conjugate gradients: steps = %d (>= 1 required)", steps);
+        MFX_REQUIRE(std::isfinite(tol) && tol >= 0.f, "implicit ALS by conjugate gradients: tol = %g (finite and >= 0 required)", (double) tol);
+        MFX_REQUIRE(std::isfinite(alpha) && alpha >= 0.f, "mfx_ials_cg_half: alpha = %g (finite and >= 0 required)", (double) alpha);
+        MFX_REQUIRE(nseg < (int64_t) 0xFFFFFFFFll && nrows_x < (int64_t) 0xFFFFFFFFll && nnz < (int64_t) 0xFFFF0000ll,
+                    "mfx_ials_cg_half: sizes exceed the 32-bit index range");
+        return ials_cg_half_op(nseg, nnz, ptr, idx, val, nrows_x, X, Y_in, Y_out, k, lambda, alpha, steps, tol, counts, device);
+    });
+}
+int mfx_spd_inverse(int64_t k, const float* A, float* Ainv, int device) {
+    return guarded("mfx_spd_inverse", [&]() -> int {
+        MFX_REQUIRE(A && Ainv, "mfx_spd_inverse: null argument");
+        return spd_inverse_op(k, A, Ainv, device);
+    });
+}
 /* ------------------------------------------------------------------ explicit ALS by block subspace sweeps */
 int mfx_als_block_create(mfx_als_t* out, const mfx_csx* R, const mfx_coo* T, const mfx_params* p, int32_t block, int32_t reg,
                          mfx_memspace space) {

@@ -409,6 +409,12 @@ int IalsBlock::alloc(uint32_t k_, uint32_t d_, uint32_t max_rows_x, uint32_t max
     return alloc_half(max_seg, nnz, nslots, st);
 }
 
+int IalsBlock::alloc_gramian(uint32_t k_, uint32_t max_rows_x) {
+    k = k_; d = 0;
+    MFX_TRY(G.alloc((size_t) k * k));
+    return gpart.alloc((size_t) gram_parts(max_rows_x, k) * gram_tiles(k) * 1024);
+}
+
 int IalsBlock::alloc_half(uint32_t max_seg, uint64_t nnz, uint32_t nslots, hipStream_t st) {
     MFX_TRY(P.alloc(std::max<size_t>(1, (size_t) max_seg * d)));
     MFX_TRY(Z.alloc(std::max<size_t>(1, (size_t) max_seg * d)));

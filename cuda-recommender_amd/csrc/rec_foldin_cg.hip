@@ -384,26 +384,49 @@ int foldcg_inverse(const float* G, uint32_t k, float* Minv) {
     return MFX_OK;
 }
 
+int FoldCgWs::alloc(uint32_t max_seg, uint32_t k, uint32_t nslots, int32_t steps) {
+    const size_t nk = std::max<size_t>(1, (size_t) max_seg * k);
+    MFX_TRY(R.alloc(nk));
+    MFX_TRY(Z.alloc(nk));
+    MFX_TRY(P.alloc(nk));
+    MFX_TRY(Q.alloc(nk));
+    MFX_TRY(part.alloc(std::max<size_t>(1, (size_t) nslots * 2 * k)));
+    MFX_TRY(bb.alloc(std::max<uint32_t>(1, max_seg)));
+    MFX_TRY(gamma.alloc(std::max<uint32_t>(1, max_seg)));
+    MFX_TRY(frozen.alloc(std::max<uint32_t>(1, max_seg)));
+    return active.alloc((size_t) steps + 1);
+}
+
 int foldcg_launch(const AlsHalf& h, const float* X, uint32_t x_rows, uint32_t k, const FoldCg& m, float* Y, bool warm, int32_t* counts,
-                  uint32_t* fail, hipStream_t st) {
+                  uint32_t* fail, hipStream_t st, FoldCgWs* cw) {
     const uint32_t nseg = h.nseg;
     if (nseg == 0) return MFX_OK;
     const bool implicit = m.reg == 0;
     MFX_REQUIRE(!implicit || (m.G && m.Minv), "fold-in by conjugate gradients: the implicit model needs G and Minv");
     const size_t nk = (size_t) nseg * k;
-    DevBuf<float> R, Zb, P, Q, ws, bb, gamma;
-    DevBuf<uint32_t> frozen, active;  // active [1 + steps]: the rows still active after the start and after each step
-    DevBuf<int32_t> own_counts;
-    MFX_TRY(R.alloc(nk));
-    MFX_TRY(P.alloc(nk));
-    MFX_TRY(Q.alloc(nk));
-    if (implicit) MFX_TRY(Zb.alloc(nk));
-    MFX_TRY(ws.alloc(std::max<size_t>(1, (size_t) h.nslots * 2 * k)));
-    MFX_TRY(bb.alloc(nseg));
-    MFX_TRY(gamma.alloc(nseg));
-    MFX_TRY(frozen.alloc(nseg));
     const bool stop = m.tol > 0.f;
-    if (stop) MFX_TRY(active.alloc_zero((size_t) m.steps + 1, st));
+    FoldCgWs own;  // the call's own vectors when the caller brought none
+    DevBuf<int32_t> own_counts;
+    if (cw) {
+        MFX_REQUIRE(cw->R.size() >= nk && cw->Z.size() >= nk && cw->P.size() >= nk && cw->Q.size() >= nk &&
+                        cw->part.size() >= std::max<size_t>(1, (size_t) h.nslots * 2 * k) && cw->bb.size() >= nseg && cw->gamma.size() >= nseg &&
+                        cw->frozen.size() >= nseg && cw->active.size() >= (size_t) m.steps + 1,
+                    "conjugate gradients: the caller's workspace is too small for this half");
+        if (stop) MFX_HIP(hipMemsetAsync(cw->active.get(), 0, sizeof(uint32_t) * ((size_t) m.steps + 1), st));
+    } else {
+        cw = &own;
+        MFX_TRY(own.R.alloc(nk));
+        MFX_TRY(own.P.alloc(nk));
+        MFX_TRY(own.Q.alloc(nk));
+        if (implicit) MFX_TRY(own.Z.alloc(nk));
+        MFX_TRY(own.part.alloc(std::max<size_t>(1, (size_t) h.nslots * 2 * k)));
+        MFX_TRY(own.bb.alloc(nseg));
+        MFX_TRY(own.gamma.alloc(nseg));
+        MFX_TRY(own.frozen.alloc(nseg));
+        if (stop) MFX_TRY(own.active.alloc_zero((size_t) m.steps + 1, st));  // [1 + steps]: the rows still active after the start and after each step
+    }
+    DevBuf<float>&R = cw->R, &Zb = cw->Z, &P = cw->P, &Q = cw->Q, &ws = cw->part, &bb = cw->bb, &gamma = cw->gamma;
+    DevBuf<uint32_t>&frozen = cw->frozen, &active = cw->active;
     if (!counts) {
         MFX_TRY(own_counts.alloc(nseg));
         counts = own_counts.get();
@@ -426,7 +449,8 @@ int foldcg_launch(const AlsHalf& h, const float* X, uint32_t x_rows, uint32_t k,
                        m.tol, bb.get(), frozen.get(), counts);
     MFX_HIP(hipGetLastError());
     if (implicit) MFX_TRY(foldcg_dense(R.get(), nseg, k, m.Minv, frozen.get(), nullptr, Z, st));
-    hipLaunchKernelGGL(k_foldcg_dir, grid, block, 0, st, nseg, k, R.get(), Z, P.get(), 1, gamma.get(), frozen.get(), active.get());
+    hipLaunchKernelGGL(k_foldcg_dir, grid, block, 0, st, nseg, k, R.get(), Z, P.get(), 1, gamma.get(), frozen.get(),
+                       stop ? active.get() : nullptr);
     MFX_HIP(hipGetLastError());
     bool done = false;
     if (stop) MFX_TRY(all_frozen(0, done));

@@ -107,6 +107,12 @@ SIGNATURES = {
                                         C.c_int]),
     "mfx_ials_block_half": (C.c_int, [C.c_int64, C.c_int64, u32p, u32p, f32p, C.c_int64, f32p, f32p, f32p, C.c_int64, C.c_int32,
                                       C.c_float, C.c_float, C.c_int]),
+    "mfx_ials_cg_create": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(mfx_csx), C.POINTER(mfx_params), C.c_float, C.c_int32, C.c_float,
+                                     C.c_int]),
+    "mfx_ials_cg_stats": (C.c_int, [C.c_void_p, i64p]),
+    "mfx_ials_cg_half": (C.c_int, [C.c_int64, C.c_int64, u32p, u32p, f32p, C.c_int64, f32p, f32p, f32p, C.c_int64, C.c_float, C.c_float,
+                                   C.c_int32, C.c_float, C.POINTER(C.c_int32), C.c_int]),
+    "mfx_spd_inverse": (C.c_int, [C.c_int64, f32p, f32p, C.c_int]),
     "mfx_ials_create_reg": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(mfx_csx), C.POINTER(mfx_params), C.c_float, C.c_float, C.c_float,
                                       C.c_int]),
     "mfx_ials_block_create_reg": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(mfx_csx), C.POINTER(mfx_params), C.c_float, C.c_float,

@@ -542,11 +542,17 @@ class ImplicitAlsSolver:
     start of the first half-sweep.
     alpha0 / nu (either one given: mfx_ials_create_reg / mfx_ials_block_create_reg): the weight alpha0 > 0 of the unobserved
     pairs and the exponent 0 <= nu <= 1 of the frequency-scaled regulariser lambda (n + alpha0 N)^nu of a row or column
-    with n entries over N; a lone alpha0 means nu = 0, a lone nu means alpha0 = 1."""
+    with n entries over N; a lone alpha0 means nu = 0, a lone nu means alpha0 = 1.
+    cg=(steps, tol): preconditioned conjugate gradients (mfx_ials_cg_create, k <= 1024): every half-sweep solves each row's
+    system from its current value in at most `steps` steps, a row stopping once its relative residual is <= tol; W, when
+    given to set_factors, is the warm start of the first half-sweep (else it starts cold).  Not with block=, alpha0=, nu=."""
 
     def __init__(self, R: Optional[RatingData], parameters: parameter, alpha: float, device_arrays: Optional[dict] = None,
-                 block: Optional[int] = None, alpha0: Optional[float] = None, nu: Optional[float] = None):
+                 block: Optional[int] = None, alpha0: Optional[float] = None, nu: Optional[float] = None,
+                 cg: Optional[tuple] = None):
         self.handle = C.c_void_p()
+        if cg is not None and (block is not None or alpha0 is not None or nu is not None):
+            raise ValueError("ImplicitAlsSolver: cg= cannot be combined with block=, alpha0= or nu=")
         cp = parameters.to_c()
         if device_arrays is not None:
             d = device_arrays
@@ -559,7 +565,10 @@ class ImplicitAlsSolver:
             self.rows, self.cols, self.k = R.rows, R.cols, int(parameters.k)
             csx, space = _csx(R), L.MFX_HOST
         reg = _reg_pair(alpha0, nu)
-        if reg is not None and block is None:
+        if cg is not None:
+            steps, tol = cg
+            L.check(L.lib().mfx_ials_cg_create(C.byref(self.handle), C.byref(csx), C.byref(cp), float(alpha), int(steps), float(tol), space))
+        elif reg is not None and block is None:
             L.check(L.lib().mfx_ials_create_reg(C.byref(self.handle), C.byref(csx), C.byref(cp), float(alpha), reg[0], reg[1], space))
         elif reg is not None:
             L.check(L.lib().mfx_ials_block_create_reg(C.byref(self.handle), C.byref(csx), C.byref(cp), float(alpha), reg[0], reg[1],
@@ -592,6 +601,14 @@ class ImplicitAlsSolver:
         out = C.c_double(0.0)
         L.check(L.lib().mfx_ials_loss(self.handle, C.byref(out)))
         return float(out.value)
+
+    def cg_stats(self) -> dict:
+        """The last iteration of a cg= solver (mfx_ials_cg_stats): for the W-half ("rows") and the H-half ("cols") the
+        row-steps applied, the most steps a row took, the rows that ran out of steps without meeting tol, the failed rows."""
+        out = (C.c_int64 * 8)()
+        L.check(L.lib().mfx_ials_cg_stats(self.handle, out))
+        keys = ("row_steps", "max_steps", "unconverged", "failed")
+        return {half: {key: int(out[4 * i + j]) for j, key in enumerate(keys)} for i, half in enumerate(("rows", "cols"))}
 
     def kernel_times(self):
         return _kernel_times(L.lib().mfx_als_kernel_times, self.handle)
@@ -696,6 +713,21 @@ def ials_block_half(ptr, idx, val, X, k: int, lam: float, alpha: float, block: i
     return Y
 
 
+def ials_cg_half(ptr, idx, val, X, k: int, lam: float, alpha: float, steps: int, tol: float, Y_in=None, return_steps: bool = False,
+                 device: int = 0):
+    """One half-sweep of implicit ALS by conjugate gradients (mfx_ials_cg_half) from Y_in [nseg][k] (None = cold, from
+    zero).  return_steps: also the steps applied to every row, int32 [nseg]."""
+    nseg = ptr.shape[0] - 1
+    Y = np.empty((nseg, k), np.float32)
+    if Y_in is not None:
+        _f32c(Y_in, (nseg, k))
+    counts = np.zeros(nseg, np.int32) if return_steps else None
+    L.check(L.lib().mfx_ials_cg_half(nseg, idx.shape[0], _u32(ptr), _u32(idx), _f32(val), X.shape[0], _f32(X),
+                                     _f32(Y_in) if Y_in is not None else None, _f32(Y), k, lam, alpha, int(steps), float(tol),
+                                     counts.ctypes.data_as(C.POINTER(C.c_int32)) if return_steps else None, device))
+    return (Y, counts) if return_steps else Y
+
+
 def als_block_half(ptr, idx, val, X, k: int, lam: float, block: int, Y_in=None, count_reg: bool = False, device: int = 0) -> np.ndarray:
     """One half-sweep of explicit ALS by block subspace sweeps (mfx_als_block_half) from Y_in [nseg][k] (None = zeros);
     count_reg: lambda times the entries of the segment on the diagonal instead of lambda."""
@@ -713,6 +745,15 @@ def als_inverse(A, device: int = 0) -> np.ndarray:
     A = np.ascontiguousarray(A, np.float32)
     out = np.empty_like(A)
     L.check(L.lib().mfx_als_inverse(A.shape[0], _f32(A), _f32(out), device))
+    return out
+
+
+def spd_inverse(A, device: int = 0) -> np.ndarray:
+    """The inverse of one symmetric positive definite matrix, k <= 1024, on the device (mfx_spd_inverse): blocked Cholesky
+    on the fp32 matrix cores, exactly symmetric, the same bits on every call."""
+    A = np.ascontiguousarray(A, np.float32)
+    out = np.empty_like(A)
+    L.check(L.lib().mfx_spd_inverse(A.shape[0], _f32(A), _f32(out), device))
     return out
 
 

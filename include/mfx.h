@@ -267,6 +267,33 @@ int mfx_ials_block_half(int64_t nseg, int64_t nnz, const uint32_t* ptr, const ui
                         int64_t nrows_x, const float* X, const float* Y_in, float* Y_out, int64_t k, int32_t block,
                         float lambda, float alpha, int device);
 
+/* Implicit ALS by preconditioned conjugate gradients: the same objective at ranks k up to 1024, every half-sweep solving its
+ * systems to a stated tolerance.  A segment's system over the fixed side X is
+ *     A y = b,   A = G + sum_{r_j > 0} w_j x_j x_j^T,   b = sum_{r_j > 0} fp32(1 + w_j) x_j,   G = X^T X + lambda I,
+ * the fixed base plus a matrix of the rank of the segment, so conjugate gradients preconditioned by Minv ~ G^-1 end, in exact
+ * arithmetic, after n + 1 steps on a segment of n entries.  A half-sweep forms G, inverts it on the device (mfx_spd_inverse's
+ * kernels) and runs the recurrence of mfx_rec_fold_in_cg_setup on every segment from its CURRENT row (warm start): at most
+ * `steps` steps, a row stops once |b - A y| <= tol |b| (2-norms, fp32; tol = 0: every row takes `steps` steps unless its
+ * direction vanishes).  An empty segment gives y = 0.  Returns an mfx_als_t: mfx_als_set_factors / _iterate / _get_factors /
+ * _kernel_times / _destroy and mfx_ials_loss work on it as on mfx_ials_block_create's.  mfx_als_set_factors: H required;
+ * W NULL = the first W-half starts cold (from zero), else W is its warm start.  One iterate step = W-half over H, then
+ * H-half over the new W.  A failed inverse (G not positive definite) or failed rows are reported as the other solvers
+ * report a failed system; mfx_ials_cg_stats counts them.  Memory on the device besides the matrix and the factors: the four
+ * CG vectors, 16 k bytes per row of the larger side, and 5 k^2 floats.  Single GPU.
+ * MFX_ERR_INVALID without touching the device: k outside 1..1024 ("rank"), steps < 1 ("steps"), tol < 0 / NaN / Inf
+ * ("tol"), alpha < 0 / NaN / Inf ("alpha"), schedule != 1 ("schedule"), a null argument. */
+int mfx_ials_cg_create(mfx_als_t* out, const mfx_csx* R, const mfx_params* p, float alpha, int32_t steps, float tol,
+                       mfx_memspace space);
+/* The last iteration of an mfx_ials_cg_create handle (zeros before the first): out[0..3] the W-half, out[4..7] the H-half:
+ * the row-steps applied, the most steps any row took, the rows that used all `steps` without meeting tol (0 when
+ * tol = 0), the failed rows.  MFX_ERR_INVALID on a handle of another kind. */
+int mfx_ials_cg_stats(mfx_als_t s, int64_t out[8]);
+/* Single operator for tests: one half-sweep from Y_in [nseg][k] (NULL = cold, from zero) to Y_out [nseg][k], host pointers,
+ * by the code of the trainer's half.  counts: [nseg], the steps applied to every row, or NULL. */
+int mfx_ials_cg_half(int64_t nseg, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val,
+                     int64_t nrows_x, const float* X, const float* Y_in, float* Y_out, int64_t k, float lambda, float alpha,
+                     int32_t steps, float tol, int32_t* counts, int device);
+
 /* Implicit ALS with an unobserved weight and a frequency-scaled regulariser (Rendle et al. 2021, "Revisiting the Performance
  * of iALS on Item Recommendation Benchmarks": their unobserved_weight and regularization_exp).  alpha0 > 0 weighs the
  * all-pairs term, 0 <= nu <= 1 scales the regulariser of a segment s (a user row or an item column) over the fixed factor X
@@ -660,6 +687,11 @@ int mfx_als_gramian(int64_t cnt, const uint32_t* idx, int64_t nrows_x, const flo
  * inverseMatrix_CholeskyMethod (src/ALS.cpp:6-64) on one k x k matrix, in the reference's operation order
  * (bit-identical to the CPU reference): Ainv = A^-1 via Cholesky, mirrored. */
 int mfx_als_inverse(int64_t k, const float* A, float* Ainv, int device);
+/* Ainv ~ A^-1 of one symmetric positive definite matrix A [k][k], 1 <= k <= 1024, host pointers, computed on the device by
+ * a blocked Cholesky A = L L^T, a blocked L^-1 and L^-T L^-1 on the fp32 matrix cores (the diagonal blocks in fp64): the
+ * preconditioner of mfx_ials_cg_create.  Ainv is exactly symmetric and its bits depend on (A, k) alone.  MFX_ERR_INVALID
+ * for k outside 1..1024 (without touching the device) and for an A that is not positive definite or not finite. */
+int mfx_spd_inverse(int64_t k, const float* A, float* Ainv, int device);
 /* One ALS half-sweep, updateW_overH_kernel / updateH_overW_kernel
  * (cuda_src/ALS_CUDA.cu:81-181): for every segment solve (X^T X + lambda I) y = X^T r.
  * variant 1 (default path): MFMA Gramian, Cholesky factorisation and two triangular solves; variant 0:

@@ -20,8 +20,14 @@ flop and gathered bytes from the shapes (no base Gramian, no G y product).
 --block alike, on the objective with an unobserved weight and a frequency-scaled regulariser (mfx_ials_create_reg /
 mfx_ials_block_create_reg); the record then carries "alpha0" and "nu".  Explicit runs are not affected.
 
+--cg STEPS:TOL adds runs of the conjugate-gradient trainer (mfx_ials_cg_create) at every rank of --cg-ks (default: --ks)
+from the same H0 (W cold): ms per iteration (every iteration listed: warm starts change the steps), the split Gramian /
+inverse / solve, mean and most steps per half from mfx_ials_cg_stats and the loss after every iteration; and the time of
+the device inverse alone (the trainer's ialscg_inverse on a small matrix) at k = 256 and 1024, next to the whole
+mfx_spd_inverse call from host pointers.
+
     python tools/ials_bench.py [--ks 64,128] [--block 128:64,256:64] [--explicit-block 256:64] [--reg 0] [--again] [--iters 5]
-                               [--alpha 1.0] [--lam 0.05] [--alpha0 0.3 --nu 0.5]
+                               [--alpha 1.0] [--lam 0.05] [--alpha0 0.3 --nu 0.5] [--cg 64:1e-4 --cg-ks 256,1024]
 """
 import argparse
 import json
@@ -115,12 +121,73 @@ def run_block(mfx, d_arrays, rows, cols, nnz, k, block, a):
             "loss_per_iteration": losses}
 
 
+def run_cg(mfx, d_arrays, rows, cols, k, steps, tol, a):
+    p = mfx.parameter()
+    p.k, p.lambda_, p.log = k, a.lam, 1 if a.verbose else 0
+    H0 = mfx.initial_col(cols, k)
+    s = mfx.ImplicitAlsSolver(None, p, a.alpha, device_arrays=d_arrays, cg=(steps, tol))
+    s.set_factors(H0)
+    losses, stats = [], []
+    for _ in range(a.iters):  # the loss curve and the steps from H0, W cold (these iterations also warm up)
+        s.iterate(1)
+        losses.append(s.loss())
+        st = s.cg_stats()
+        stats.append({"mean_steps_user_half": round(st["rows"]["row_steps"] / rows, 3), "max_steps_user_half": st["rows"]["max_steps"],
+                      "mean_steps_item_half": round(st["cols"]["row_steps"] / cols, 3), "max_steps_item_half": st["cols"]["max_steps"],
+                      "unconverged": st["rows"]["unconverged"] + st["cols"]["unconverged"],
+                      "failed": st["rows"]["failed"] + st["cols"]["failed"]})
+    s.kernel_times()
+    s.set_factors(H0)  # the same iterations again, warmed up: the times
+    ms = [r.update_time * 1e3 for r in s.iterate(a.iters)]
+    kt = s.kernel_times()
+    s.close()
+    per = {name: t * 1e3 / n for name, (t, n) in kt.items()}
+    return {"kind": "cg", "k": k, "steps": steps, "tol": tol, "ms_per_iteration": round(float(np.median(ms)), 3),
+            "ms_of_every_iteration": [round(x, 3) for x in ms],
+            "ms_solve_user_half": round(per["ialscg_half_rows(W over H)"], 3), "ms_solve_item_half": round(per["ialscg_half_cols(H over W)"], 3),
+            "ms_base_gram_H": round(per["ialscg_base_gram(H)"], 3), "ms_base_gram_W": round(per["ialscg_base_gram(W)"], 3),
+            "ms_inverse_H": round(per["ialscg_inverse(H)"], 3), "ms_inverse_W": round(per["ialscg_inverse(W)"], 3),
+            "steps_per_iteration": stats, "loss_per_iteration": losses}
+
+
+def inverse_times(mfx, ks=(256, 1024)):
+    """ms of the device inverse alone (the trainer's ialscg_inverse events on a 600 x 500 matrix, after a warm-up iteration)
+    and of a whole mfx_spd_inverse call from host pointers (allocation, upload, inverse, download)."""
+    import time
+    from mfx import dataset as ds
+    rng = np.random.default_rng(7)
+    mask = rng.random((600, 500)) < 0.05
+    r, c = np.nonzero(mask)
+    R = ds.from_coo(600, 500, r, c, np.ones(r.size, np.float32))
+    out = []
+    for k in ks:
+        p = mfx.parameter()
+        p.k, p.lambda_ = k, 0.05
+        s = mfx.ImplicitAlsSolver(R, p, 1.0, cg=(2, 0.0))
+        s.set_factors((rng.standard_normal((500, k)) * 0.1).astype(np.float32))
+        s.iterate(1)
+        s.kernel_times()
+        s.iterate(5)
+        per = {name: t * 1e3 / n for name, (t, n) in s.kernel_times().items()}
+        s.close()
+        X = rng.standard_normal((4 * k, k)).astype(np.float32) / np.sqrt(k)
+        A = (X.T @ X + 0.1 * np.eye(k, dtype=np.float32)).astype(np.float32)
+        mfx.spd_inverse(A)
+        t0 = time.perf_counter()
+        mfx.spd_inverse(A)
+        out.append({"k": k, "ms_device_inverse": round(0.5 * (per["ialscg_inverse(H)"] + per["ialscg_inverse(W)"]), 4),
+                    "ms_whole_call_from_host_pointers": round((time.perf_counter() - t0) * 1e3, 3)})
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--ks", default="64,128")
     ap.add_argument("--block", default="", help="k:d,k:d,... runs of the block subspace sweeps")
     ap.add_argument("--explicit-block", default="", help="k:d,k:d,... runs of explicit ALS by block subspace sweeps")
     ap.add_argument("--reg", type=int, default=0, help="explicit block runs: 0 = lambda, 1 = lambda * entries of the segment")
+    ap.add_argument("--cg", default="", help="STEPS:TOL runs of the conjugate-gradient trainer at every rank of --cg-ks")
+    ap.add_argument("--cg-ks", default="", help="ranks of the --cg runs (default: --ks)")
     ap.add_argument("--again", action="store_true", help="repeat the exact runs after the block runs")
     ap.add_argument("--verbose", action="store_true", help="block runs: the solver's own log lines (failed pivots) before the JSON line")
     ap.add_argument("--iters", type=int, default=5)
@@ -143,9 +210,17 @@ def main():
     ks = [int(x) for x in a.ks.split(",") if x]
     blocks = [tuple(int(v) for v in x.split(":")) for x in a.block.split(",") if x]
     eblocks = [tuple(int(v) for v in x.split(":")) for x in a.explicit_block.split(",") if x]
-    plan = ([("exact", k, None) for k in ks] + [("block", k, b) for k, b in blocks] + [("explicit_block", k, b) for k, b in eblocks] +
-            ([("exact", k, None) for k in ks] if a.again else []))
+    cg = (int(a.cg.split(":")[0]), float(a.cg.split(":")[1])) if a.cg else None
+    cg_ks = [int(x) for x in a.cg_ks.split(",") if x] if a.cg_ks else ks
+    plan = ([("exact", k, None) for k in ks] + [("block", k, b) for k, b in blocks] + [("cg", k, None) for k in (cg_ks if cg else [])] +
+            [("explicit_block", k, b) for k, b in eblocks] + ([("exact", k, None) for k in ks] if a.again else []))
+    if cg:
+        out["device_inverse"] = inverse_times(mfx)
     for kind, k, block in plan:
+        if kind == "cg":
+            out["runs"].append(run_cg(mfx, d, rows, cols, k, cg[0], cg[1], a))
+            torch.cuda.synchronize()
+            continue
         if kind == "explicit_block":
             out["runs"].append(run_explicit_block(mfx, d, rows, cols, nnz, k, block, a))
             torch.cuda.synchronize()
