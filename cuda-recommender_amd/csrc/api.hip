@@ -767,6 +767,38 @@ int mfx_rec_score(mfx_rec_t r, int64_t npairs, const uint32_t* users, const uint
         return r->impl->score(npairs, users, items, scores, space);
     });
 }
+int mfx_rec_ivf_setup(mfx_rec_t r, int32_t nlist, const uint32_t* assign, const float* centroids, mfx_memspace space) {
+    return guarded("mfx_rec_ivf_setup", [&]() -> int {
+        MFX_REQUIRE(r && r->impl, "null recommender");
+        return r->impl->ivf_setup(nlist, assign, centroids, space);
+    });
+}
+int mfx_rec_ivf_lists(mfx_rec_t r, uint32_t* list_ptr, uint32_t* list_idx, mfx_memspace space) {
+    return guarded("mfx_rec_ivf_lists", [&]() -> int {
+        MFX_REQUIRE(r && r->impl, "null recommender");
+        return r->impl->ivf_lists(list_ptr, list_idx, space);
+    });
+}
+int mfx_rec_ivf_probe(mfx_rec_t r, int64_t nusers, const uint32_t* users, int32_t nprobe, uint32_t* lists, float* scores, mfx_memspace space) {
+    return guarded("mfx_rec_ivf_probe", [&]() -> int {
+        MFX_REQUIRE(r && r->impl, "null recommender");
+        return r->impl->ivf_probe(nusers, users, nprobe, lists, scores, space);
+    });
+}
+int mfx_rec_query_ivf(mfx_rec_t r, int64_t nusers, const uint32_t* users, int32_t nprobe, int32_t n_top, uint32_t* items, float* scores,
+                      mfx_memspace space) {
+    return guarded("mfx_rec_query_ivf", [&]() -> int {
+        MFX_REQUIRE(r && r->impl, "null recommender");
+        return r->impl->query_ivf(nusers, users, nprobe, n_top, items, scores, space);
+    });
+}
+int mfx_rec_ivf_times(mfx_rec_t r, double seconds[4]) {
+    return guarded("mfx_rec_ivf_times", [&]() -> int {
+        MFX_REQUIRE(r && r->impl && seconds, "null recommender or seconds");
+        r->impl->ivf_times(seconds);
+        return MFX_OK;
+    });
+}
 int mfx_rec_candidates_times(mfx_rec_t r, double seconds[3]) {
     return guarded("mfx_rec_candidates_times", [&]() -> int {
         MFX_REQUIRE(r && r->impl && seconds, "null recommender or seconds");

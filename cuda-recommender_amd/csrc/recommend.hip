@@ -39,6 +39,9 @@
 // items.  The query operand is H itself packed like W, self-exclusion an identity exclusion CSR, and the cosine's second
 // factor c[q] is applied once per output slot where the final N are written (flush or mfx_rec_merge), so the order is
 // the keys'.
+//
+// IVF retrieval (mfx_rec_query_ivf, rec_ivf.hip) runs the same top-N pass over the centroids of its item lists as the probe
+// (topn with another tile set) and sends its per-probe partial lists through mfx_rec_merge (merge_launch).
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -543,14 +546,15 @@ int Recommender::set_item_filter(const uint8_t* keep, mfx_memspace space) {
     if (!keep) {
         keep_.release();
         fac_keep_.release();
-        return build_facs(nullptr);
+        MFX_TRY(build_facs(nullptr));
+        return ivf_refresh_fac();
     }
     DevBuf<uint8_t> nk;  // (the handle keeps its filter if this one cannot be taken)
     MFX_TRY(nk.alloc((size_t) cols_));
     MFX_TRY(nk.upload(keep, (size_t) cols_, space, st_));
     MFX_TRY(build_facs(nk.get()));
     keep_ = std::move(nk);
-    return MFX_OK;
+    return ivf_refresh_fac();
 }
 
 int Recommender::similar_setup() {
@@ -614,8 +618,10 @@ int Recommender::similar(int64_t nq, const uint32_t* query_items, int metric, in
 
 int Recommender::topn(const float* wp, uint32_t nu, const uint32_t* du, const uint32_t* ex_ptr, const uint32_t* ex_idx,
                       int32_t n_top, uint32_t* items, float* scores, mfx_memspace space, int item_slices, const float* fac,
-                      const float* qfac) {
+                      const float* qfac, const TileSet* tiles) {
     hipStream_t st = st_;
+    const TileSet own{hp_.get(), (uint32_t) cols_, nblk_};
+    const TileSet& ts = tiles ? *tiles : own;
     int L = 64;
     while (L < n_top + 32) L <<= 1;
 
@@ -626,7 +632,7 @@ int Recommender::topn(const float* wp, uint32_t nu, const uint32_t* du, const ui
     };
     // slices: as forced, or chosen for the user blocks of one launch, at most what one merge takes
     const int slices = item_slices ? item_slices : pick_slices(0, (per_launch(1) + kRecUsers - 1) / kRecUsers, kMaxMerge / n_top);
-    const int bps = (nblk_ + slices - 1) / slices;
+    const int bps = (ts.nblk + slices - 1) / slices;
     const uint32_t qc = per_launch(slices);
 
     DevBuf<uint32_t> d_items;
@@ -647,12 +653,12 @@ int Recommender::topn(const float* wp, uint32_t nu, const uint32_t* du, const ui
 
     RecArgs a{};
     a.wp = wp;
-    a.hp = hp_.get();
+    a.hp = ts.hp;
     a.users = du;
     a.ex_ptr = ex_ptr;
     a.ex_idx = ex_idx;
-    a.cols = (uint32_t) cols_;
-    a.kt = kt_; a.nch = nch_; a.nblk = nblk_; a.bps = bps; a.n_top = n_top; a.L = L;
+    a.cols = ts.cols;
+    a.kt = kt_; a.nch = nch_; a.nblk = ts.nblk; a.bps = bps; a.n_top = n_top; a.L = L;
     a.ls = ls.get(); a.li = li.get();
     a.out_items = oi; a.out_scores = os;
     a.fac = fac; a.qfac = qfac;
@@ -680,6 +686,23 @@ int Recommender::topn(const float* wp, uint32_t nu, const uint32_t* du, const ui
         if (scores) MFX_HIP(hipMemcpyAsync(scores, os, sizeof(float) * nu * n_top, hipMemcpyDeviceToHost, st));
     }
     MFX_HIP(hipStreamSynchronize(st));
+    return MFX_OK;
+}
+
+int Recommender::merge_launch(const float* ls, const uint32_t* li, uint32_t q0, uint32_t nq, int slices, int L, int n_top,
+                              uint32_t* out_items, float* out_scores) {
+    int P = 1;
+    while (P < slices * n_top) P <<= 1;
+    hipLaunchKernelGGL(mfx_rec_merge, dim3(nq), dim3(64), (size_t) P * 8, st_, ls, li, q0, nq, slices, L, n_top, P, out_items, out_scores,
+                       (const uint32_t*) nullptr, (const float*) nullptr);
+    MFX_LAUNCH_CHECK();
+    return MFX_OK;
+}
+
+int Recommender::pack_h_launch(const float* H, int layout, uint32_t cols, int nblk, float* hp) {
+    hipLaunchKernelGGL(mfx_rec_pack_h, dim3(grid_for((size_t) nblk * kTile * kt_)), dim3(256), 0, st_, H, layout, cols, (int) k_, 2 * kc_, nch_,
+                       nblk, hp);
+    MFX_LAUNCH_CHECK();
     return MFX_OK;
 }
 

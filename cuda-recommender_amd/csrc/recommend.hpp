@@ -70,6 +70,21 @@ struct FoldSpec {
     }
 };
 
+// What mfx_rec_ivf_setup leaves in the handle (rec_ivf.hip): the items in list order.  Every list starts on a tile and is
+// padded to whole tiles, so no tile of hp holds items of two lists.
+struct IvfIndex {
+    int32_t nlist = 0;       // 0: not set up
+    int nblk = 0;            // tiles of hp: sum over the lists of ceil(size / 32)
+    int nblkc = 0;           // tiles of cp: ceil(nlist / 32)
+    DevBuf<float> hp;        // [nblk][nch][2*KC][32]: H in list order, the bits of the handle's own tiles
+    DevBuf<float> cp;        // [nblkc][nch][2*KC][32]: the centroids packed like H
+    DevBuf<float> fac;       // [nblk * 32]: the item filter's 1 / NaN in list order (empty without a filter)
+    DevBuf<uint32_t> ids;    // [nblk * 32]: position -> item id, 0xFFFFFFFF at the padding
+    DevBuf<uint32_t> blk_ptr;   // [nlist + 1]: first tile of every list
+    DevBuf<uint32_t> list_ptr;  // [nlist + 1], list_idx [cols]: the lists as mfx_rec_ivf_lists returns them
+    DevBuf<uint32_t> list_idx;
+};
+
 class Recommender {
 public:
     static int create(Recommender** out, const float* W, const float* H, int64_t rows, int64_t cols, int64_t k,
@@ -102,6 +117,12 @@ public:
                          int32_t n_top, uint32_t* items, float* scores, uint32_t* n_eligible, mfx_memspace space);
     int score(int64_t npairs, const uint32_t* users, const uint32_t* items, float* scores, mfx_memspace space);
     void candidates_times(double out[3]) const { for (int i = 0; i < 3; ++i) out[i] = cand_s_[i]; }
+    // mfx_rec_ivf_setup / mfx_rec_ivf_lists / mfx_rec_ivf_probe / mfx_rec_query_ivf / mfx_rec_ivf_times (rec_ivf.hip)
+    int ivf_setup(int32_t nlist, const uint32_t* assign, const float* centroids, mfx_memspace space);
+    int ivf_lists(uint32_t* list_ptr, uint32_t* list_idx, mfx_memspace space);
+    int ivf_probe(int64_t nusers, const uint32_t* users, int32_t nprobe, uint32_t* lists, float* scores, mfx_memspace space);
+    int query_ivf(int64_t nusers, const uint32_t* users, int32_t nprobe, int32_t n_top, uint32_t* items, float* scores, mfx_memspace space);
+    void ivf_times(double out[4]) const { for (int i = 0; i < 4; ++i) out[i] = ivf_s_[i]; }
     // mfx_rec_explain / mfx_rec_explain_times (recommend.hip; the lists: rec_candidates.hip)
     static constexpr int kMaxExplain = 64;
     int explain(int64_t nusers, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val, int32_t n_targets,
@@ -119,9 +140,24 @@ private:
     // excludes the items of row users[q] (q) of ex_ptr / ex_idx (ex_ptr NULL: none).  Device pointers except items /
     // scores, which live in `space`.  fac (NULL: none) [nblk_ * 32]: the ranking key of an item is fp32(score * fac[item]);
     // qfac (NULL: none, needs fac) [query id]: a slot's returned scores are fp32(key * qfac[users[q]]), the order the keys'.
+    // tiles (NULL: the handle's own H): another packed item side of the same k, e.g. the centroids of the ivf index; then
+    // item_slices is taken as given (pick_slices knows the handle's tiles only).
+    struct TileSet {
+        const float* hp;
+        uint32_t cols;
+        int nblk;
+    };
     int topn(const float* wp, uint32_t nu, const uint32_t* users, const uint32_t* ex_ptr, const uint32_t* ex_idx,
              int32_t n_top, uint32_t* items, float* scores, mfx_memspace space, int item_slices, const float* fac,
-             const float* qfac);
+             const float* qfac, const TileSet* tiles = nullptr);
+    // mfx_rec_merge of recommend.hip over the partial lists ls / li [slices][nq][L] of batch slots q0 .. q0 + nq
+    int merge_launch(const float* ls, const uint32_t* li, uint32_t q0, uint32_t nq, int slices, int L, int n_top, uint32_t* out_items,
+                     float* out_scores);
+    // mfx_rec_pack_h of recommend.hip: H [cols][k] (layout 1) or [k][cols] (layout 0) on the device into tiles hp
+    int pack_h_launch(const float* H, int layout, uint32_t cols, int nblk, float* hp);
+    // the ivf index's copy of the item filter's factor, after the filter or the index changed (rec_ivf.hip)
+    int ivf_refresh_fac();
+    int ivf_probe_dev(uint32_t nu, const uint32_t* du, int32_t nprobe, uint32_t* lists, float* scores, mfx_memspace space);
     // The ids of a batch [n] from `space` onto the device (buf holds the copy) with every id < bound checked; *dev is where
     // they are, NULL for ids = NULL.  `what` opens the refusal ("mfx_rec_query: user id").
     int stage_ids(const uint32_t* ids, uint32_t n, mfx_memspace space, uint32_t bound, const char* what, DevBuf<uint32_t>& buf,
@@ -171,6 +207,8 @@ private:
     double fold_s_[3] = {0, 0, 0};  // host build / solve / score seconds of the last fold-in
     double rank_s_[3] = {0, 0, 0};  // device seconds of the last rank: target keys / counting pass / exclusion correction
     double expl_s_[3] = {0, 0, 0};  // seconds of the last explain of either kind: host build + checks / solve / totals + contributions
+    IvfIndex ivf_;
+    double ivf_s_[4] = {0, 0, 0, 0};  // stream seconds of the last query_ivf: probe / work-item build / list pass / merge
     double cand_s_[3] = {0, 0, 0};  // stream seconds of the last query_candidates / score: check + stage / score / merge of long lists
 };
 

@@ -4,7 +4,7 @@ from .api import (AlsSolver, CcdSolver, Comm, TestData, UsageError, als_gramian,
                   calculate_rmse_directly, device_count, extract_shard, golden_compare, initial_col,
                   kernel_wrapper_als_NV, kernel_wrapper_ccdpp_NV, parameter, parse_command_line,
                   partition_cols, partition_rows, rank_one_sweep, solvertype, test_data_of, test_rmse, update_rating)
-from .api import PAD_ITEM, PAD_RANK, Recommender, recommend, topn_metrics  # noqa: F401
+from .api import PAD_ITEM, PAD_RANK, Recommender, ivf_kmeans, recommend, topn_metrics  # noqa: F401
 from .api import ImplicitAlsSolver, ials_half, ials_block_half, ials_cg_half, spd_inverse  # noqa: F401
 from .api import als_block_half  # noqa: F401
 from ._lib import LIB_PATH, MfxError, lib  # noqa: F401

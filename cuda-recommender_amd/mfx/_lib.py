@@ -169,6 +169,11 @@ SIGNATURES = {
                                            C.c_void_p, C.c_void_p, C.c_int]),
     "mfx_rec_score": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "mfx_rec_candidates_times": (C.c_int, [C.c_void_p, f64p]),
+    "mfx_rec_ivf_setup": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int]),
+    "mfx_rec_ivf_lists": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    "mfx_rec_ivf_probe": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int]),
+    "mfx_rec_query_ivf": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int]),
+    "mfx_rec_ivf_times": (C.c_int, [C.c_void_p, f64p]),
     "mfx_rec_destroy": (C.c_int, [C.c_void_p]),
     "mfx_topn_metrics": (C.c_int, [C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(mfx_coo), C.c_float, f64p,
                                    i64p]),

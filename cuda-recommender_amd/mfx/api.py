@@ -887,6 +887,77 @@ def _canonical_lists_torch(ptr, idx):
     return out, key & 0xFFFFFFFF
 
 
+_KMEANS_CHUNK = 1 << 24  # distances of one assignment step held at a time (items x lists)
+
+
+def _kmeans_assign_np(H: np.ndarray, Cn: np.ndarray) -> np.ndarray:
+    """The nearest centroid of every row by ||c||^2 - 2 <h, c> in fp32 (||h||^2 is common to a row's candidates);
+    argmin takes the first minimum: ties go to the lowest list id."""
+    cn = np.einsum("ij,ij->i", Cn, Cn)
+    out = np.empty(H.shape[0], np.int64)
+    step = max(1, _KMEANS_CHUNK // Cn.shape[0])
+    for i0 in range(0, H.shape[0], step):
+        out[i0:i0 + step] = np.argmin(cn[None, :] - 2.0 * (H[i0:i0 + step] @ Cn.T), axis=1)
+    return out
+
+
+def _kmeans_np(H: np.ndarray, first: np.ndarray, iters: int):
+    nlist = first.size
+    Cn = H[first].copy()
+    for _ in range(iters):
+        a = _kmeans_assign_np(H, Cn)
+        order = np.argsort(a, kind="stable")
+        counts = np.bincount(a, minlength=nlist)
+        full = np.nonzero(counts)[0]
+        starts = (np.cumsum(counts) - counts)[full]
+        sums = np.add.reduceat(H[order], starts, axis=0, dtype=np.float64)
+        Cn[full] = (sums / counts[full, None]).astype(np.float32)  # an empty cluster keeps its centroid
+    return _kmeans_assign_np(H, Cn).astype(np.uint32), Cn
+
+
+def _kmeans_torch(H, first: np.ndarray, iters: int):
+    import torch
+    nlist = first.size
+    Cn = H[torch.from_numpy(first).to(H.device)].clone()
+    step = max(1, _KMEANS_CHUNK // nlist)
+
+    def assign():
+        cn = (Cn * Cn).sum(1)
+        return torch.cat([torch.argmin(cn[None, :] - 2.0 * (H[i0:i0 + step] @ Cn.t()), dim=1) for i0 in range(0, H.shape[0], step)])
+
+    for _ in range(iters):
+        a = assign()
+        counts = torch.bincount(a, minlength=nlist)
+        sums = torch.zeros_like(Cn).index_add_(0, a, H)
+        full = counts > 0
+        Cn[full] = sums[full] / counts[full, None].to(H.dtype)
+    return assign().to(torch.int32), Cn
+
+
+def ivf_kmeans(H, nlist: int, iters: int = 10, seed: int = 0):
+    """A clustering of the items for Recommender.ivf_setup -> (assign uint32 [cols], centroids float32 [nlist, k]).
+
+    H [cols, k] float32: numpy (computed with numpy) or a torch tensor (computed on its device; assign is then an int32
+    tensor, the bits of the uint32 ids).  Plain Lloyd iterations on the squared L2 distance: the initial centroids are
+    nlist distinct rows chosen by np.random.default_rng(seed).choice(cols, nlist, replace=False); a cluster that empties keeps its centroid and stays empty;
+    after the last update one more assignment follows, so the returned assignment belongs to the returned centroids;
+    ties go to the lowest list id.  nlist <= cols."""
+    if len(tuple(H.shape)) != 2:
+        raise ValueError("H must be [cols, k]")
+    cols = int(H.shape[0])
+    if not 1 <= nlist <= cols:
+        raise ValueError(f"nlist must be in [1, cols = {cols}] (got {nlist})")
+    if iters < 0:
+        raise ValueError("iters must be >= 0")
+    first = np.random.default_rng(seed).choice(cols, nlist, replace=False).astype(np.int64)
+    if _is_dev(H):
+        import torch
+        if H.dtype != torch.float32:
+            raise ValueError("H must be float32")
+        return _kmeans_torch(H.contiguous(), first, iters)
+    return _kmeans_np(np.ascontiguousarray(H, dtype=np.float32), first, iters)
+
+
 class Recommender:
     """Resident top-N recommender over trained factors (mfx_rec_*).
 
@@ -1279,6 +1350,100 @@ class Recommender:
         out = (C.c_double * 3)()
         L.check(L.lib().mfx_rec_candidates_times(self.handle, out))
         return {"check": out[0], "score": out[1], "select": out[2]}
+
+    def ivf_setup(self, assign, centroids):
+        """Builds the IVF index from a clustering of the items (mfx_rec_ivf_setup): assign [cols] the list of every item
+        (uint32 numpy array, or a 32-bit integer GPU tensor holding those bits), centroids float32 [nlist, k], both host
+        arrays or both GPU tensors.  Any assignment will do (ivf_kmeans makes one); a second call replaces the index.
+        One more copy of H on the device."""
+        dev = _is_dev(assign)
+        if dev != _is_dev(centroids):
+            raise ValueError("assign and centroids must both be host arrays or both device tensors")
+        if len(tuple(centroids.shape)) != 2 or int(centroids.shape[1]) != self.k:
+            raise ValueError(f"centroids must be [nlist, {self.k}]")
+        if tuple(assign.shape) != (self.cols,):
+            raise ValueError(f"assign must have one entry per item ({self.cols})")
+        nlist = int(centroids.shape[0])
+        if dev:
+            import torch
+            assert centroids.dtype == torch.float32 and centroids.is_contiguous(), "centroids: contiguous float32 tensor"
+            assert assign.is_contiguous() and assign.element_size() == 4 and not assign.dtype.is_floating_point, \
+                "assign: contiguous 32-bit integer tensor"
+            torch.cuda.synchronize(assign.device)  # (the library reads on its own stream: what torch has queued on them comes first)
+            L.check(L.lib().mfx_rec_ivf_setup(self.handle, nlist, C.c_void_p(int(assign.data_ptr())),
+                                              C.c_void_p(int(centroids.data_ptr())), L.MFX_DEVICE))
+        else:
+            a = _ids_np(assign, "assign").astype(np.uint32)
+            c = np.ascontiguousarray(centroids, dtype=np.float32)
+            L.check(L.lib().mfx_rec_ivf_setup(self.handle, nlist, _vp(a), _vp(c), L.MFX_HOST))
+        self._nlist = nlist
+
+    def ivf_build(self, H, nlist: int, iters: int = 10, seed: int = 0):
+        """ivf_kmeans(H, nlist, iters, seed) followed by ivf_setup -> (assign, centroids).  H as the constructor took it
+        ([k, cols] for layout 0, which is transposed here)."""
+        if self.layout == 0:
+            H = H.t().contiguous() if _is_dev(H) else np.ascontiguousarray(np.asarray(H).T)
+        assign, centroids = ivf_kmeans(H, nlist, iters, seed)
+        self.ivf_setup(assign, centroids)
+        return assign, centroids
+
+    def ivf_lists(self):
+        """The lists of the index as built (mfx_rec_ivf_lists) -> (list_ptr uint32 [nlist + 1], list_idx uint32 [cols]):
+        list l is list_idx[list_ptr[l]:list_ptr[l + 1]], item ids ascending."""
+        ptr = np.empty(getattr(self, "_nlist", 0) + 1, np.uint32)
+        idx = np.empty(self.cols, np.uint32)
+        L.check(L.lib().mfx_rec_ivf_lists(self.handle, _vp(ptr), _vp(idx), L.MFX_HOST))
+        return ptr, idx
+
+    def _ivf_batch(self, width: int, users, on_device: bool, call):
+        """(ids [U, width], scores [U, width]) of call(n, users pointer, ids pointer, scores pointer, space), the batch
+        taken as query takes it."""
+        if _is_dev(users) or on_device:
+            import torch
+            dev = torch.device("cuda", self.device)
+            if users is not None:
+                assert users.is_contiguous() and users.element_size() == 4, "users: contiguous 32-bit tensor"
+                n = int(users.numel())
+                pu = C.c_void_p(int(users.data_ptr())) if n else None
+            else:
+                n, pu = self.rows, None
+            ids = torch.empty((n, width), dtype=torch.int32, device=dev)
+            scores = torch.empty((n, width), dtype=torch.float32, device=dev)
+            if n:
+                L.check(call(n, pu, C.c_void_p(int(ids.data_ptr())), C.c_void_p(int(scores.data_ptr())), L.MFX_DEVICE))
+            return ids, scores
+        if users is None:
+            n, pu, keep = self.rows, None, None
+        else:
+            keep = _ids_np(users, "users").astype(np.uint32)
+            n, pu = int(keep.size), _vp(keep)
+        ids = np.empty((n, width), np.uint32)
+        scores = np.empty((n, width), np.float32)
+        L.check(call(n, pu, _vp(ids), _vp(scores), L.MFX_HOST))
+        return ids, scores
+
+    def ivf_probe(self, nprobe: int, users=None, on_device: bool = False):
+        """The nprobe lists each of `users` (None: all users in order) probes, best first -> (lists uint32 [U, nprobe],
+        scores float32 [U, nprobe]) (mfx_rec_ivf_probe): the score of a list is the score chain against its centroid;
+        slots left over (fewer than nprobe lists with a score that is not NaN) hold PAD_ITEM / -inf.  Device in or
+        on_device=True: int32 / float32 tensors, as in query."""
+        fn = L.lib().mfx_rec_ivf_probe
+        return self._ivf_batch(nprobe, users, on_device, lambda n, pu, pi, ps, sp: fn(self.handle, n, pu, nprobe, pi, ps, sp))
+
+    def query_ivf(self, n_top: int, nprobe: int, users=None, on_device: bool = False):
+        """Top-n_top items of `users` over the items of the nprobe lists each of them probes -> (items [U, n_top], scores
+        [U, n_top]) (mfx_rec_query_ivf): exactly query_candidates on the union of the probed lists, so exclusion rows,
+        item filter, order, padding and score bits are query's, and nprobe = nlist is query itself.
+        1 <= nprobe <= min(nlist, 1024), nprobe * n_top <= 8192.  Device in or on_device=True as in query."""
+        fn = L.lib().mfx_rec_query_ivf
+        return self._ivf_batch(n_top, users, on_device, lambda n, pu, pi, ps, sp: fn(self.handle, n, pu, nprobe, n_top, pi, ps, sp))
+
+    def ivf_times(self) -> dict:
+        """Stream seconds of the last query_ivf by phase (mfx_rec_ivf_times): {"probe", "build" (the work items), "pass"
+        (the list pass), "merge"}."""
+        out = (C.c_double * 4)()
+        L.check(L.lib().mfx_rec_ivf_times(self.handle, out))
+        return {"probe": out[0], "build": out[1], "pass": out[2], "merge": out[3]}
 
     def evaluate(self, T, cutoffs=(10,), min_rating: float = float("-inf")) -> dict:
         """Ranking metrics of this model on the held-out set T (TestData or RatingData) from exact ranks

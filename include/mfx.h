@@ -654,6 +654,51 @@ int mfx_rec_score(mfx_rec_t r, int64_t npairs, const uint32_t* users, const uint
  * [2] select (the merge of the lists longer than 2048 candidates; 0 when there is none).  After mfx_rec_score: [0] stage,
  * [1] score, [2] 0. */
 int mfx_rec_candidates_times(mfx_rec_t r, double seconds[3]);
+/* Inverted-file (IVF) retrieval, the first stage that mfx_rec_query_candidates is the second stage of: the items are
+ * partitioned into nlist lists, each with a centroid; a query scores the user against the centroids, takes the best
+ * nprobe lists and ranks only the items of those lists.  The clustering is the caller's (Python: mfx.ivf_kmeans).
+ *
+ * mfx_rec_ivf_setup builds the index on r.  assign [cols]: the list of every item, each < nlist (checked on the device);
+ * centroids [nlist][k], row-major whatever the handle's layout; 1 <= nlist <= 65536; empty lists are allowed.  `space`
+ * applies to both arrays, which are copied.  It may be called again: a successful call replaces the index, a refused one
+ * leaves the handle as it was.  The index keeps on the device one more copy of H (packed in list order from the handle's
+ * own packed H, so the bits are the ones mfx_rec_query scores with; every list padded to a multiple of 32 items, at most
+ * 32 * nlist padding items), 8 bytes per item for the position -> item id table and the lists, 8 bytes per list, the
+ * packed centroids, and 4 bytes per item while an item filter is set.
+ * mfx_rec_ivf_lists returns the lists as built: list_ptr [nlist + 1], list_idx [cols]; list l is
+ * list_idx[list_ptr[l] .. list_ptr[l+1]), item ids ascending.
+ *
+ * mfx_rec_ivf_probe: the lists a query probes, lists [nusers][nprobe], scores [nusers][nprobe] or NULL.  The score of
+ * (user u, list l) is the fp32 FMA chain of mfx_rec_query over t = 0 .. k-1 with the centroid in H's place; lists are
+ * ranked by score descending, then list id ascending; -0 == +0; a NaN score is never probed; the slots left over hold
+ * (0xFFFFFFFF, -INFINITY).  So the result equals mfx_rec_query(n_top = nprobe) on a handle made from the same W with the
+ * centroids as its items and no exclusion, bit for bit.
+ *
+ * mfx_rec_query_ivf: the top n_top of each slot over the items of its probed lists.  items [nusers][n_top], scores
+ * [nusers][n_top] or NULL equal mfx_rec_query_candidates for the same users with each slot's candidate list the
+ * ascending union of its probed lists: the handle's exclusion rows, the item filter (honoured whether
+ * mfx_rec_set_item_filter was called before or after mfx_rec_ivf_setup), the total order, the padding with
+ * (0xFFFFFFFF, -INFINITY), the score bits and the NaN rule are those.  In particular nprobe = nlist equals
+ * mfx_rec_query bit for bit.  Slot q is user users[q] (q when users is NULL; any order, duplicates allowed); a slot's
+ * result does not depend on the batch, its order, the memory space or the factor layout.
+ * Ranges: 1 <= nprobe <= min(nlist, 1024) (the probe is a top-N pass), 1 <= n_top <= 1024, nprobe * n_top <= 8192 (the
+ * per-probe partial lists go through the merge of mfx_rec_query's item slices).
+ * Workspace during a query: 4 * nprobe bytes per slot for the probes, nprobe candidate lists of 8 * L bytes per slot
+ * (L = the power of two >= n_top + 32, at least 64; the slots are taken in chunks so that these stay under 1 GiB), and
+ * 4 bytes per (slot, probe) pair plus 12 bytes per list for the work items.
+ *
+ * MFX_ERR_INVALID, the handle left usable: anything outside those ranges, an assign entry >= nlist, a user id >= rows,
+ * a NULL array that is needed, a bad memory space, any of mfx_rec_ivf_lists / _probe / mfx_rec_query_ivf before a
+ * successful mfx_rec_ivf_setup.  nusers == 0 is MFX_OK and touches nothing.
+ * mfx_rec_ivf_times: stream seconds of the last mfx_rec_query_ivf on r: [0] probe, [1] work-item build, [2] list pass,
+ * [3] merge (0 for nprobe = 1); zeros before the first one. */
+int mfx_rec_ivf_setup(mfx_rec_t r, int32_t nlist, const uint32_t* assign, const float* centroids, mfx_memspace space);
+int mfx_rec_ivf_lists(mfx_rec_t r, uint32_t* list_ptr, uint32_t* list_idx, mfx_memspace space);
+int mfx_rec_ivf_probe(mfx_rec_t r, int64_t nusers, const uint32_t* users, int32_t nprobe, uint32_t* lists, float* scores,
+                      mfx_memspace space);
+int mfx_rec_query_ivf(mfx_rec_t r, int64_t nusers, const uint32_t* users, int32_t nprobe, int32_t n_top, uint32_t* items,
+                      float* scores, mfx_memspace space);
+int mfx_rec_ivf_times(mfx_rec_t r, double seconds[4]);
 int mfx_rec_destroy(mfx_rec_t r);
 
 /* ------------------------------------------------------------------------------------
