@@ -7,6 +7,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <memory>
+#include <string>
 
 #include "ccd_kernels.hpp"
 
@@ -65,109 +66,172 @@ int AlsHalf::build(uint32_t nseg_, uint64_t nnz_, uint32_t G, const uint32_t* pt
 
 
 // ------------------------------------------------------------------------------------------------
-int AlsSolver::create(AlsSolver** out, const mfx_csx* R, const mfx_coo* T, const mfx_params* p, mfx_memspace space,
-                      const mfx_als_shard* shard) {
-    MFX_REQUIRE(out && R && p, "mfx_als_create: null argument");
-    std::unique_ptr<AlsSolver> s(new AlsSolver());
-    MFX_TRY(s->init(R, T, p, space, shard));
-    *out = s.release();
-    return MFX_OK;
+// The pairs that exist: the family's name in the texts, the names of kernel_times (the two half-sweeps, the base Gramians of H
+// and W, their inverses; what a pair never times is never read).  A new (method, objective) pair is a row here, a case in
+// als_plan_half and, where it keeps buffers of its own, in AlsPlan::alloc.
+struct AlsPair {
+    AlsPlan::Method method;
+    AlsPlan::Objective objective;
+    const char* family;
+    const char* names[6];
+};
+#define MFX_ALS_NAMES(p) {p "_half_rows(W over H)", p "_half_cols(H over W)", p "_base_gram(H)", p "_base_gram(W)", p "_inverse(H)", p "_inverse(W)"}
+using PM = AlsPlan::Method;
+using PO = AlsPlan::Objective;
+static const AlsPair kAlsPairs[] = {
+    {PM::Direct, PO::Als, "ALS", MFX_ALS_NAMES("als")},
+    {PM::DirectExact, PO::Als, "ALS", MFX_ALS_NAMES("als")},
+    {PM::Direct, PO::Implicit, "implicit ALS", MFX_ALS_NAMES("ials")},
+    {PM::Direct, PO::ImplicitReg, "implicit ALS", MFX_ALS_NAMES("ials")},
+    {PM::Blocks, PO::Als, "explicit ALS by block sweeps", MFX_ALS_NAMES("alsb")},
+    {PM::Blocks, PO::Ccd, "explicit ALS by block sweeps", MFX_ALS_NAMES("alsb")},
+    {PM::Blocks, PO::Implicit, "implicit ALS by block sweeps", MFX_ALS_NAMES("ialsb")},
+    {PM::Blocks, PO::ImplicitReg, "implicit ALS by block sweeps", MFX_ALS_NAMES("ialsb")},
+    {PM::Cg, PO::Implicit, "implicit ALS by conjugate gradients", MFX_ALS_NAMES("ialscg")},
+};
+#undef MFX_ALS_NAMES
+static const AlsPair* als_pair(PM m, PO o) {
+    for (const AlsPair& pr : kAlsPairs)
+        if (pr.method == m && pr.objective == o) return &pr;
+    return nullptr;
 }
+static uint32_t als_max_rank(PM m) { return m == PM::Blocks || m == PM::Cg ? kIalsBlockMaxRank : 128u; }
 
-int AlsSolver::create_implicit(AlsSolver** out, const mfx_csx* R, const mfx_params* p, float alpha, mfx_memspace space) {
-    MFX_REQUIRE(out && R && p, "mfx_ials_create: null argument");
-    MFX_REQUIRE(std::isfinite(alpha) && alpha >= 0.f, "mfx_ials_create: alpha = %g (finite and >= 0 required)", (double) alpha);
-    MFX_REQUIRE(p->k >= 1 && p->k <= 128, "implicit ALS: rank k = %u not supported (1 <= k <= 128)", p->k);
-    MFX_REQUIRE(p->schedule == 1, "implicit ALS: schedule must be 1 (there is no as-written mode)");
-    std::unique_ptr<AlsSolver> s(new AlsSolver());
-    s->implicit_ = true;
-    s->alpha_ = alpha;
-    MFX_TRY(s->init(R, nullptr, p, space, nullptr));
-    *out = s.release();
-    return MFX_OK;
-}
-
-int AlsSolver::create_block(AlsSolver** out, const mfx_csx* R, const mfx_params* p, float alpha, int32_t block, mfx_memspace space) {
-    MFX_REQUIRE(out && R && p, "mfx_ials_block_create: null argument");
-    MFX_REQUIRE(std::isfinite(alpha) && alpha >= 0.f, "mfx_ials_block_create: alpha = %g (finite and >= 0 required)", (double) alpha);
-    MFX_REQUIRE(p->k >= 1 && p->k <= kIalsBlockMaxRank, "implicit ALS by block sweeps: rank k = %u not supported (1 <= k <= %u)", p->k,
-                kIalsBlockMaxRank);
-    MFX_REQUIRE(block >= 0 && block <= (int32_t) kIalsBlockMaxBlock, "implicit ALS by block sweeps: block = %d (0 = chosen from k, else 1 <= block <= %u)",
-                block, kIalsBlockMaxBlock);
-    MFX_REQUIRE(p->schedule == 1, "implicit ALS by block sweeps: schedule must be 1 (there is no as-written mode)");
-    std::unique_ptr<AlsSolver> s(new AlsSolver());
-    s->implicit_ = true;
-    s->alpha_ = alpha;
-    s->block_ = std::min<uint32_t>(block ? (uint32_t) block : ialsb_default_block(p->k), p->k);
-    MFX_TRY(s->init(R, nullptr, p, space, nullptr));
-    *out = s.release();
-    return MFX_OK;
-}
-
-int AlsSolver::create_cg(AlsSolver** out, const mfx_csx* R, const mfx_params* p, float alpha, int32_t steps, float tol, mfx_memspace space) {
-    MFX_REQUIRE(out && R && p, "mfx_ials_cg_create: null argument");
-    MFX_REQUIRE(space == MFX_HOST || space == MFX_DEVICE, "mfx_ials_cg_create: bad memory space");
-    MFX_REQUIRE(std::isfinite(alpha) && alpha >= 0.f, "mfx_ials_cg_create: alpha = %g (finite and >= 0 required)", (double) alpha);
-    MFX_REQUIRE(p->k >= 1 && p->k <= kIalsBlockMaxRank, "implicit ALS by conjugate gradients: rank k = %u not supported (1 <= k <= %u)", p->k,
-                kIalsBlockMaxRank);
-    MFX_REQUIRE(steps >= 1, "implicit ALS by conjugate gradients: steps = %d (>= 1 required)", steps);
-    MFX_REQUIRE(std::isfinite(tol) && tol >= 0.f, "implicit ALS by conjugate gradients: tol = %g (finite and >= 0 required)", (double) tol);
-    MFX_REQUIRE(p->schedule == 1, "implicit ALS by conjugate gradients: schedule must be 1 (there is no as-written mode)");
-    std::unique_ptr<AlsSolver> s(new AlsSolver());
-    s->implicit_ = true;
-    s->alpha_ = alpha;
-    s->cg_ = true;
-    s->cg_steps_ = steps;
-    s->cg_tol_ = tol;
-    MFX_TRY(s->init(R, nullptr, p, space, nullptr));
-    *out = s.release();
-    return MFX_OK;
-}
-
-int AlsSolver::create_implicit_reg(AlsSolver** out, const mfx_csx* R, const mfx_params* p, float alpha, float alpha0, float nu, int32_t block,
-                                   mfx_memspace space) {
-    const bool blk = block >= 0;
-    const char* fn = blk ? "mfx_ials_block_create_reg" : "mfx_ials_create_reg";
-    MFX_REQUIRE(out && R && p, "%s: null argument", fn);
-    MFX_REQUIRE(space == MFX_HOST || space == MFX_DEVICE, "%s: bad memory space", fn);
-    MFX_REQUIRE(std::isfinite(alpha) && alpha >= 0.f, "%s: alpha = %g (finite and >= 0 required)", fn, (double) alpha);
-    if (blk) {
-        MFX_REQUIRE(p->k >= 1 && p->k <= kIalsBlockMaxRank, "implicit ALS by block sweeps: rank k = %u not supported (1 <= k <= %u)", p->k,
-                    kIalsBlockMaxRank);
-        MFX_REQUIRE(block <= (int32_t) kIalsBlockMaxBlock, "implicit ALS by block sweeps: block = %d (0 = chosen from k, else 1 <= block <= %u)",
-                    block, kIalsBlockMaxBlock);
-    } else {
-        MFX_REQUIRE(p->k >= 1 && p->k <= 128, "implicit ALS: rank k = %u not supported (1 <= k <= 128)", p->k);
+// The checks of the fourteen entry points, each in the order and with the text it always had.  What differs between them
+// beyond the pair: a create checks alpha first and a half after the pair's own parameters; reg and lambda of the explicit
+// block sweeps are named by the family in the create and by the function in the half; the sizes of a half are checked late
+// (mfx_als_half: first).  mfx_als_create checks its rank with the matrix (AlsSolver::init).
+int als_spec_check(const AlsSpec& s, int64_t k, float lambda, int64_t rows, int64_t cols, int64_t nnz) {
+    const AlsPair* pr = als_pair(s.method, s.objective);
+    MFX_REQUIRE(pr, "%s: there is no ALS trainer of method %d on objective %d", s.fn, (int) s.method, (int) s.objective);
+    const char* fam = pr->family;
+    const bool implicit = s.objective == PO::Implicit || s.objective == PO::ImplicitReg, reg = s.objective == PO::ImplicitReg;
+    auto sizes = [&]() -> int {
+        MFX_REQUIRE(!s.half || (rows < (int64_t) 0xFFFFFFFFll && cols < (int64_t) 0xFFFFFFFFll && nnz < (int64_t) 0xFFFF0000ll),
+                    "%s: sizes exceed the 32-bit index range", s.fn);
+        return MFX_OK;
+    };
+    auto alpha = [&]() -> int {
+        MFX_REQUIRE(!implicit || (std::isfinite(s.alpha) && s.alpha >= 0.f), "%s: alpha = %g (finite and >= 0 required)", s.fn, (double) s.alpha);
+        return MFX_OK;
+    };
+    if (!implicit && s.method != PM::Blocks) {  // Direct or DirectExact on Als
+        MFX_TRY(sizes());
+        MFX_REQUIRE(!s.half || k <= 128, "ALS: rank k = %lld not supported (1 <= k <= 128)", (long long) k);
+        return MFX_OK;
     }
-    MFX_REQUIRE(p->schedule == 1, "%s: schedule must be 1 (there is no as-written mode)", fn);
-    MFX_TRY(ialsr_check_params(fn, p->lambda, alpha0, nu, R->rows, R->cols));
-    std::unique_ptr<AlsSolver> s(new AlsSolver());
-    s->implicit_ = true;
-    s->alpha_ = alpha;
-    s->robj_ = true;
-    s->alpha0_ = alpha0;
-    s->nu_ = nu;
-    if (blk) s->block_ = std::min<uint32_t>(block ? (uint32_t) block : ialsb_default_block(p->k), p->k);
-    MFX_TRY(s->init(R, nullptr, p, space, nullptr));
-    *out = s.release();
+    if (!s.half) {
+        MFX_REQUIRE(!(s.method == PM::Cg || reg) || s.space == MFX_HOST || s.space == MFX_DEVICE, "%s: bad memory space", s.fn);
+        MFX_TRY(alpha());
+    }
+    MFX_REQUIRE(k >= 1 && k <= (int64_t) als_max_rank(s.method), "%s: rank k = %lld not supported (1 <= k <= %u)", fam, (long long) k,
+                als_max_rank(s.method));
+    if (s.method == PM::Blocks) {
+        MFX_REQUIRE(s.block >= 0 && s.block <= (int32_t) kIalsBlockMaxBlock, "%s: block = %d (0 = chosen from k, else 1 <= block <= %u)", fam,
+                    s.block, kIalsBlockMaxBlock);
+        if (!implicit) {
+            MFX_REQUIRE(s.reg == 0 || s.reg == 1, "%s: reg = %d (0 = lambda, 1 = lambda * entries of the segment)", s.half ? s.fn : fam, s.reg);
+            MFX_REQUIRE(std::isfinite(lambda) && lambda > 0.f, "%s: lambda = %g (finite and > 0 required)", s.half ? s.fn : fam, (double) lambda);
+        }
+    }
+    if (s.method == PM::Cg) {
+        MFX_REQUIRE(s.cap >= 1, "%s: steps = %d (>= 1 required)", fam, s.cap);
+        MFX_REQUIRE(std::isfinite(s.tol) && s.tol >= 0.f, "%s: tol = %g (finite and >= 0 required)", fam, (double) s.tol);
+    }
+    if (s.half) MFX_TRY(alpha());
+    else MFX_REQUIRE(s.schedule == 1, "%s: schedule must be 1 (there is no as-written mode)", reg ? s.fn : fam);
+    MFX_TRY(sizes());
+    if (reg) MFX_TRY(ialsr_check_params(s.fn, lambda, s.alpha0, s.nu, rows, cols));
     return MFX_OK;
 }
 
-int AlsSolver::create_block_explicit(AlsSolver** out, const mfx_csx* R, const mfx_coo* T, const mfx_params* p, int32_t block, int32_t reg,
-                                     mfx_memspace space) {
-    MFX_REQUIRE(out && R && p, "mfx_als_block_create: null argument");
-    MFX_REQUIRE(p->k >= 1 && p->k <= kIalsBlockMaxRank, "explicit ALS by block sweeps: rank k = %u not supported (1 <= k <= %u)", p->k,
-                kIalsBlockMaxRank);
-    MFX_REQUIRE(block >= 0 && block <= (int32_t) kIalsBlockMaxBlock, "explicit ALS by block sweeps: block = %d (0 = chosen from k, else 1 <= block <= %u)",
-                block, kIalsBlockMaxBlock);
-    MFX_REQUIRE(reg == 0 || reg == 1, "explicit ALS by block sweeps: reg = %d (0 = lambda, 1 = lambda * entries of the segment)", reg);
-    MFX_REQUIRE(std::isfinite(p->lambda) && p->lambda > 0.f, "explicit ALS by block sweeps: lambda = %g (finite and > 0 required)", (double) p->lambda);
-    MFX_REQUIRE(p->schedule == 1, "explicit ALS by block sweeps: schedule must be 1 (there is no as-written mode)");
-    std::unique_ptr<AlsSolver> s(new AlsSolver());
-    s->block_ = std::min<uint32_t>(block ? (uint32_t) block : ialsb_default_block(p->k), p->k);
-    s->reg_ = reg;
-    MFX_TRY(s->init(R, T, p, space, nullptr));
-    *out = s.release();
+int AlsPlan::set(const AlsSpec& s, uint32_t k_, float lambda_) {
+    pair = als_pair(s.method, s.objective);
+    MFX_REQUIRE(pair, "%s: there is no ALS trainer of method %d on objective %d", s.fn, (int) s.method, (int) s.objective);
+    method = s.method; objective = s.objective;
+    k = k_; lambda = lambda_;
+    alpha = implicit() ? s.alpha : 0.f;
+    alpha0 = s.alpha0; nu = s.nu;
+    if (method == Method::Blocks) block = std::min<uint32_t>(s.block ? (uint32_t) s.block : ialsb_default_block(k), k);
+    cap = s.cap; tol = s.tol;
+    return MFX_OK;
+}
+
+size_t AlsPlan::loss_ws_doubles() const { return objective == Objective::ImplicitReg ? ialsr_loss_ws_doubles(k) : ials_loss_ws_doubles(k); }
+
+int AlsPlan::alloc(uint32_t max_rows_x, uint32_t max_seg, uint64_t nnz, uint32_t nslots, hipStream_t st) {
+    switch (method) {
+        case Method::Blocks:
+            return implicit() ? bs.alloc(k, block, max_rows_x, max_seg, nnz, nslots, st)
+                              : bs.alloc_explicit(k, block, max_rows_x, max_seg, nnz, nslots, st);
+        case Method::Cg:
+            MFX_TRY(cgs.alloc(k, max_rows_x, max_seg, nslots, cap));
+            MFX_TRY(cg_fail.alloc_zero(4, st));
+            return cg_cnt.alloc_zero(6, st);
+        default:
+            MFX_TRY(ws.alloc(std::max<size_t>(1, als_ws_floats(nslots, k))));
+            if (!implicit()) return MFX_OK;
+            MFX_TRY(G.alloc((size_t) k * k));
+            return gpart.alloc(ials_base_ws_floats(max_rows_x, k));
+    }
+}
+
+int AlsPlan::check_values(const AlsHalf& h, const char* what, hipStream_t st) const {
+    if (implicit()) return ials_check_values(h.val.get(), h.nnz, alpha, what, st);
+    if (method == Method::Blocks) return als_check_finite(h.val.get(), h.nnz, what, st);
+    return MFX_OK;
+}
+
+int als_plan_half(AlsPlan& pl, const AlsHalf& h, const float* X, uint32_t x_rows, float* Y, bool warm, const float* rho, hipEvent_t ev_gram,
+                  hipEvent_t ev_inv, uint32_t* fails, unsigned long long* stats, hipStream_t st, unsigned long long* phases) {
+    const uint32_t k = pl.k;
+    constexpr auto pair_of = [](PM m, PO o) { return (int) m * 4 + (int) o; };
+    auto gram_done = [&]() -> int {
+        if (ev_gram) MFX_HIP(hipEventRecord(ev_gram, st));
+        return MFX_OK;
+    };
+    switch (pair_of(pl.method, pl.objective)) {
+        case pair_of(PM::Direct, PO::Als):
+            return als_half_launch(h, X, x_rows, Y, k, pl.lambda, pl.ws.get(), fails, st, phases);
+        case pair_of(PM::DirectExact, PO::Als):  // as written: the reference's arithmetic, bit for bit (als_exact.hip)
+            return als_half_exact_launch(h, X, Y, k, pl.lambda, fails, st);
+        case pair_of(PM::Direct, PO::Implicit):
+            MFX_TRY(ials_base_gramian(X, x_rows, k, pl.lambda, pl.gpart.get(), pl.G.get(), st));
+            MFX_TRY(gram_done());
+            return ials_half_launch(h, X, x_rows, Y, k, pl.G.get(), pl.alpha, pl.ws.get(), fails, st);
+        case pair_of(PM::Direct, PO::ImplicitReg):
+            MFX_TRY(ialsr_base_gramian(X, x_rows, k, pl.alpha0, pl.gpart.get(), pl.G.get(), st));
+            MFX_TRY(gram_done());
+            return ialsr_half_launch(h, X, x_rows, Y, k, pl.G.get(), pl.alpha, pl.alpha0, rho, pl.ws.get(), fails, st);
+        case pair_of(PM::Blocks, PO::Als):
+        case pair_of(PM::Blocks, PO::Ccd):
+            return alsb_half_launch(pl.bs, h, X, x_rows, Y, pl.lambda, pl.objective == PO::Ccd, fails, st);
+        case pair_of(PM::Blocks, PO::Implicit):
+            MFX_TRY(ialsb_gramian(pl.bs, X, x_rows, pl.lambda, st));
+            MFX_TRY(gram_done());
+            return ialsb_half_launch(pl.bs, h, X, x_rows, Y, pl.alpha, fails, st);
+        case pair_of(PM::Blocks, PO::ImplicitReg):
+            MFX_TRY(ialsrb_gramian(pl.bs, X, x_rows, pl.alpha0, st));
+            MFX_TRY(gram_done());
+            return ialsb_half_launch(pl.bs, h, X, x_rows, Y, pl.alpha, fails, st, pl.alpha0, rho);
+        case pair_of(PM::Cg, PO::Implicit):
+            return ialscg_half_launch(pl.cgs, h, X, x_rows, Y, warm, pl.lambda, pl.alpha, pl.cap, pl.tol, fails, stats, ev_gram, ev_inv, st);
+    }
+    return fail(MFX_ERR_INVALID, "ALS: no half-sweep of method %d on objective %d", (int) pl.method, (int) pl.objective);
+}
+
+// ------------------------------------------------------------------------------------------------
+int AlsSolver::create(AlsSolver** out, const mfx_csx* R, const mfx_coo* T, const mfx_params* p, mfx_memspace space, const mfx_als_shard* shard,
+                      const AlsSpec& spec) {
+    MFX_REQUIRE(out && R && p, "%s: null argument", spec.fn);
+    AlsSpec s = spec;
+    s.schedule = p->schedule;
+    s.space = space;
+    if (s.method == PM::Direct && s.objective == PO::Als && p->schedule == 0) s.method = PM::DirectExact;
+    MFX_TRY(als_spec_check(s, p->k, p->lambda, R->rows, R->cols, R->nnz));
+    std::unique_ptr<AlsSolver> a(new AlsSolver());
+    MFX_TRY(a->init(R, T, p, space, shard, s));
+    *out = a.release();
     return MFX_OK;
 }
 
@@ -201,11 +265,11 @@ static int gather_bounds(mfx_comm_s* c, int64_t lo, int64_t hi, std::vector<int6
     return MFX_OK;
 }
 
-int AlsSolver::init(const mfx_csx* R, const mfx_coo* T, const mfx_params* p, mfx_memspace space, const mfx_als_shard* shard) {
+int AlsSolver::init(const mfx_csx* R, const mfx_coo* T, const mfx_params* p, mfx_memspace space, const mfx_als_shard* shard, const AlsSpec& spec) {
     MFX_REQUIRE(R->rows > 0 && R->cols > 0 && R->nnz >= 0, "bad matrix shape");
     MFX_REQUIRE(R->rows < (int64_t) 0xFFFFFFFFll && R->cols < (int64_t) 0xFFFFFFFFll &&
                     R->nnz < (int64_t) 0xFFFF0000ll, "matrix exceeds 32-bit index range");
-    MFX_REQUIRE(p->k >= 1 && p->k <= (block_ || cg_ ? kIalsBlockMaxRank : 128u), "ALS: rank k = %u not supported (1 <= k <= 128)", p->k);
+    MFX_REQUIRE(p->k >= 1 && p->k <= als_max_rank(spec.method), "ALS: rank k = %u not supported (1 <= k <= 128)", p->k);
     MFX_REQUIRE(R->csc_col_ptr && R->csr_row_ptr, "null CSR/CSC pointer array");
     p_ = *p;
     device_ = p->device;
@@ -236,7 +300,6 @@ int AlsSolver::init(const mfx_csx* R, const mfx_coo* T, const mfx_params* p, mfx
     // one extra, all-zero row each: the Gramian kernel gathers it for positions past a segment's end
     MFX_TRY(W_.alloc_zero(((size_t) m_ + 1) * k_, st_));
     MFX_TRY(H_.alloc_zero(((size_t) n_ + 1) * k_, st_));
-    MFX_TRY(ws_.alloc(block_ || cg_ ? 1 : std::max<size_t>(1, als_ws_floats(std::max(rows_.nslots, cols_.nslots), k_))));
     MFX_TRY(spd_fail_.alloc_zero(1, st_));
     if (std::getenv("MFX_ALS_PHASES")) { MFX_TRY(phases_.alloc_zero((size_t) kPhaseCopies * 8, st_)); }
     nnz_test_ = T ? T->nnz : 0;
@@ -251,34 +314,23 @@ int AlsSolver::init(const mfx_csx* R, const mfx_coo* T, const mfx_params* p, mfx
     }
     MFX_TRY(rmse_partials_.alloc_zero(kRmseBlocks, st_));
     MFX_TRY(rmse_sum_.alloc_zero(1, st_));
-    if (implicit_) {
-        MFX_TRY(ials_check_values(rows_.val.get(), rows_.nnz, alpha_, "implicit ALS: R (CSR) value", st_));
-        MFX_TRY(ials_check_values(cols_.val.get(), cols_.nnz, alpha_, "implicit ALS: R (CSC) value", st_));
-        if (block_) {
-            MFX_REQUIRE(rows_.nnz == cols_.nnz, "implicit ALS by block sweeps: the two orientations hold %llu and %llu entries",
-                        (unsigned long long) rows_.nnz, (unsigned long long) cols_.nnz);
-            MFX_TRY(bs_.alloc(k_, block_, std::max(m_, n_), std::max(m_, n_), rows_.nnz, std::max(rows_.nslots, cols_.nslots), st_));
-        } else if (cg_) {  // (the objective's workspace: on the first loss(), as for the block sweeps)
-            MFX_TRY(cgs_.alloc(k_, std::max(m_, n_), std::max(m_, n_), std::max(rows_.nslots, cols_.nslots), cg_steps_));
-            MFX_TRY(cg_fail_.alloc_zero(4, st_));
-            MFX_TRY(cg_cnt_.alloc_zero(6, st_));
-        } else {
-            MFX_TRY(G_.alloc((size_t) k_ * k_));
-            MFX_TRY(gpart_.alloc(ials_base_ws_floats(std::max(m_, n_), k_)));
-            MFX_TRY(loss_ws_.alloc(robj_ ? ialsr_loss_ws_doubles(k_) : ials_loss_ws_doubles(k_)));  // (block sweeps: on the first loss(), up to 1 GB at k = 1024)
-        }
+    // the pair: the value checks on the CSR copy, then on the CSC copy, then its buffers for the larger of the two halves
+    MFX_TRY(plan_.set(spec, k_, p_.lambda));
+    const char* fam = plan_.implicit() ? "implicit ALS" : plan_.pair->family;
+    MFX_TRY(plan_.check_values(rows_, (std::string(fam) + ": R (CSR) value").c_str(), st_));
+    MFX_TRY(plan_.check_values(cols_, (std::string(fam) + ": R (CSC) value").c_str(), st_));
+    MFX_REQUIRE(plan_.method != PM::Blocks || rows_.nnz == cols_.nnz, "%s: the two orientations hold %llu and %llu entries", plan_.pair->family,
+                (unsigned long long) rows_.nnz, (unsigned long long) cols_.nnz);
+    MFX_TRY(plan_.alloc(std::max(m_, n_), std::max(m_, n_), rows_.nnz, std::max(rows_.nslots, cols_.nslots), st_));
+    if (plan_.implicit()) {
+        // (block sweeps and conjugate gradients: on the first loss(), up to 1 GB at k = 1024)
+        if (plan_.direct()) MFX_TRY(plan_.loss_ws.alloc(plan_.loss_ws_doubles()));
         MFX_TRY(loss_.alloc_zero(1, st_));
-        if (robj_) {  // rho of every row over the n_ items and of every column over the m_ users
-            MFX_TRY(rho_rows_.alloc(m_)); MFX_TRY(rho_cols_.alloc(n_));
-            MFX_TRY(ialsr_rho_launch(rows_, n_, p_.lambda, alpha0_, nu_, rho_rows_.get(), st_));
-            MFX_TRY(ialsr_rho_launch(cols_, m_, p_.lambda, alpha0_, nu_, rho_cols_.get(), st_));
-        }
-    } else if (block_) {
-        MFX_TRY(als_check_finite(rows_.val.get(), rows_.nnz, "explicit ALS by block sweeps: R (CSR) value", st_));
-        MFX_TRY(als_check_finite(cols_.val.get(), cols_.nnz, "explicit ALS by block sweeps: R (CSC) value", st_));
-        MFX_REQUIRE(rows_.nnz == cols_.nnz, "explicit ALS by block sweeps: the two orientations hold %llu and %llu entries",
-                    (unsigned long long) rows_.nnz, (unsigned long long) cols_.nnz);
-        MFX_TRY(bs_.alloc_explicit(k_, block_, std::max(m_, n_), std::max(m_, n_), rows_.nnz, std::max(rows_.nslots, cols_.nslots), st_));
+    }
+    if (plan_.objective == PO::ImplicitReg) {  // rho of every row over the n_ items and of every column over the m_ users
+        MFX_TRY(plan_.rho_rows.alloc(m_)); MFX_TRY(plan_.rho_cols.alloc(n_));
+        MFX_TRY(ialsr_rho_launch(rows_, n_, p_.lambda, plan_.alpha0, plan_.nu, plan_.rho_rows.get(), st_));
+        MFX_TRY(ialsr_rho_launch(cols_, m_, p_.lambda, plan_.alpha0, plan_.nu, plan_.rho_cols.get(), st_));
     }
     MFX_HIP(hipStreamSynchronize(st_));
     return MFX_OK;
@@ -333,7 +385,7 @@ int AlsSolver::set_factors(const float* W, const float* H, mfx_memspace space) {
     MFX_REQUIRE(H, "mfx_als_set_factors: H is required");
     MFX_TRY(use_device(device_));
     if (W) MFX_TRY(W_.upload(W, (size_t) m_ * k_, space, st_));
-    else if (block_ || cg_) MFX_HIP(hipMemsetAsync(W_.get(), 0, sizeof(float) * (size_t) m_ * k_, st_));  // W is the warm start of the first W-half
+    else if (plan_.warm_start()) MFX_HIP(hipMemsetAsync(W_.get(), 0, sizeof(float) * (size_t) m_ * k_, st_));  // W is the warm start of the first W-half
     w_cold_ = !W;
     MFX_TRY(H_.upload(H, (size_t) n_ * k_, space, st_));
     MFX_HIP(hipStreamSynchronize(st_));
@@ -341,35 +393,17 @@ int AlsSolver::set_factors(const float* W, const float* H, mfx_memspace space) {
     return MFX_OK;
 }
 
-int AlsSolver::half_sweep(const AlsHalf& h, const float* X, uint32_t x_rows, float* Y, uint32_t y_lo, const float* rho, hipEvent_t ev_gram) {
-    if (cg_) {  // &h == &rows_: the W-half, the only one that may be cold (Y is then zero)
-        const int half = &h == &rows_ ? 0 : 1;
-        const bool warm = half == 1 || !w_cold_;
-        MFX_TRY(ialscg_half_launch(cgs_, h, X, x_rows, Y, warm, p_.lambda, alpha_, cg_steps_, cg_tol_, cg_fail_.get() + 2 * half,
-                                   cg_cnt_.get() + 3 * half, ev_gram, ev_[6 + half], st_));
-        if (half == 0) w_cold_ = false;
-    } else if (block_ && !implicit_) {
-        MFX_TRY(alsb_half_launch(bs_, h, X, x_rows, Y, p_.lambda, reg_, spd_fail_.get(), st_));
-    } else if (block_ && robj_) {
-        MFX_TRY(ialsrb_gramian(bs_, X, x_rows, alpha0_, st_));
-        MFX_HIP(hipEventRecord(ev_gram, st_));
-        MFX_TRY(ialsb_half_launch(bs_, h, X, x_rows, Y, alpha_, spd_fail_.get(), st_, alpha0_, rho));
-    } else if (block_) {
-        MFX_TRY(ialsb_gramian(bs_, X, x_rows, p_.lambda, st_));
-        MFX_HIP(hipEventRecord(ev_gram, st_));
-        MFX_TRY(ialsb_half_launch(bs_, h, X, x_rows, Y, alpha_, spd_fail_.get(), st_));
-    } else if (robj_) {
-        MFX_TRY(ialsr_base_gramian(X, x_rows, k_, alpha0_, gpart_.get(), G_.get(), st_));
-        MFX_HIP(hipEventRecord(ev_gram, st_));
-        MFX_TRY(ialsr_half_launch(h, X, x_rows, Y, k_, G_.get(), alpha_, alpha0_, rho, ws_.get(), spd_fail_.get(), st_));
-    } else if (implicit_) {
-        MFX_TRY(ials_base_gramian(X, x_rows, k_, p_.lambda, gpart_.get(), G_.get(), st_));
-        MFX_HIP(hipEventRecord(ev_gram, st_));
-        MFX_TRY(ials_half_launch(h, X, x_rows, Y, k_, G_.get(), alpha_, ws_.get(), spd_fail_.get(), st_));
-    } else if (p_.schedule == 0)  // as written: the reference's arithmetic, bit for bit (als_exact.hip)
-        MFX_TRY(als_half_exact_launch(h, X, Y + (size_t) y_lo * k_, k_, p_.lambda, spd_fail_.get(), st_));
-    else
-        MFX_TRY(als_half_launch(h, X, x_rows, Y + (size_t) y_lo * k_, k_, p_.lambda, ws_.get(), spd_fail_.get(), st_, phases_.get()));
+int AlsSolver::half_sweep(int half) {
+    const bool cg = plan_.method == PM::Cg;
+    const AlsHalf& h = half ? cols_ : rows_;
+    const float* X = half ? W_.get() : H_.get();
+    float* Y = half ? H_.get() + (size_t) col_lo_ * k_ : W_.get() + (size_t) row_lo_ * k_;
+    const float* rho = half ? plan_.rho_cols.get() : plan_.rho_rows.get();
+    // the W-half is the only one that may be cold (W is then zero); ev_[4 + half]: the base Gramian of the fixed side is done,
+    // ev_[6 + half]: its inverse
+    MFX_TRY(als_plan_half(plan_, h, X, half ? m_ : n_, Y, half == 1 || !w_cold_, rho, ev_[4 + half], ev_[6 + half],
+                          cg ? plan_.cg_fail.get() + 2 * half : spd_fail_.get(), cg ? plan_.cg_cnt.get() + 3 * half : nullptr, st_, phases_.get()));
+    if (half == 0) w_cold_ = false;
     return MFX_OK;
 }
 
@@ -378,15 +412,16 @@ int AlsSolver::iterate(int n_iter, int with_rmse, mfx_iter_report* reports) {
     MFX_REQUIRE(factors_set_, "mfx_als_iterate: call mfx_als_set_factors first");
     MFX_TRY(use_device(device_));
     if (comm_ && !shards_met_ && n_iter > 0) MFX_TRY(meet_shards());
+    const bool cg = plan_.method == PM::Cg;
     for (int it = 0; it < n_iter; ++it) {
         MFX_HIP(hipMemsetAsync(spd_fail_.get(), 0, sizeof(uint32_t), st_));
-        if (cg_) MFX_HIP(hipMemsetAsync(cg_fail_.get(), 0, sizeof(uint32_t) * 4, st_));
+        if (cg) MFX_HIP(hipMemsetAsync(plan_.cg_fail.get(), 0, sizeof(uint32_t) * 4, st_));
         MFX_HIP(hipEventRecord(ev_[0], st_));
-        MFX_TRY(half_sweep(rows_, H_.get(), n_, W_.get(), row_lo_, rho_rows_.get(), ev_[4]));  // (ev_[4]: the base Gramian of H is done)
+        MFX_TRY(half_sweep(0));
         if (comm_) MFX_TRY(exchange(W_.get(), row_bounds_));
         MFX_HIP(hipEventRecord(ev_[1], st_));
         if (phases_.size()) MFX_TRY(print_phases("user half (W over H)"));
-        MFX_TRY(half_sweep(cols_, W_.get(), m_, H_.get(), col_lo_, rho_cols_.get(), ev_[5]));  // (ev_[5]: the base Gramian of W is done)
+        MFX_TRY(half_sweep(1));
         if (comm_) MFX_TRY(exchange(H_.get(), col_bounds_));
         MFX_HIP(hipEventRecord(ev_[2], st_));
         if (phases_.size()) MFX_TRY(print_phases("item half (H over W)"));
@@ -405,12 +440,12 @@ int AlsSolver::iterate(int n_iter, int with_rmse, mfx_iter_report* reports) {
         MFX_HIP(hipMemcpyAsync(&bad, spd_fail_.get(), sizeof(uint32_t), hipMemcpyDeviceToHost, st_));
         uint32_t cg_bad[4] = {0, 0, 0, 0};
         unsigned long long cg_cnt[6] = {0, 0, 0, 0, 0, 0};
-        if (cg_) {
-            MFX_HIP(hipMemcpyAsync(cg_bad, cg_fail_.get(), sizeof(cg_bad), hipMemcpyDeviceToHost, st_));
-            MFX_HIP(hipMemcpyAsync(cg_cnt, cg_cnt_.get(), sizeof(cg_cnt), hipMemcpyDeviceToHost, st_));
+        if (cg) {
+            MFX_HIP(hipMemcpyAsync(cg_bad, plan_.cg_fail.get(), sizeof(cg_bad), hipMemcpyDeviceToHost, st_));
+            MFX_HIP(hipMemcpyAsync(cg_cnt, plan_.cg_cnt.get(), sizeof(cg_cnt), hipMemcpyDeviceToHost, st_));
         }
         MFX_HIP(hipStreamSynchronize(st_));
-        if (cg_) {  // a failed inverse or failed rows: reported as the failed systems of the other solvers are
+        if (cg) {  // a failed inverse or failed rows: reported as the failed systems of the other solvers are
             for (int hf = 0; hf < 2; ++hf) {
                 for (int q = 0; q < 3; ++q) cg_stats_[4 * hf + q] = (int64_t) cg_cnt[3 * hf + q];
                 cg_stats_[4 * hf + 3] = (int64_t) cg_bad[2 * hf + 1];
@@ -420,25 +455,22 @@ int AlsSolver::iterate(int n_iter, int with_rmse, mfx_iter_report* reports) {
         }
         if (with_rmse && global_test_nnz_ > 0) rmse = std::sqrt(sum / (double) global_test_nnz_);
         float ms_w = 0.f, ms_h = 0.f, ms_r = 0.f, ms_gh = 0.f, ms_gw = 0.f, ms_ih = 0.f, ms_iw = 0.f;
-        if (cg_) {  // Gramian, inverse, solve of either half
-            MFX_HIP(hipEventElapsedTime(&ms_gh, ev_[0], ev_[4]));
-            MFX_HIP(hipEventElapsedTime(&ms_ih, ev_[4], ev_[6]));
-            MFX_HIP(hipEventElapsedTime(&ms_w, ev_[6], ev_[1]));
-            MFX_HIP(hipEventElapsedTime(&ms_gw, ev_[1], ev_[5]));
-            MFX_HIP(hipEventElapsedTime(&ms_iw, ev_[5], ev_[7]));
-            MFX_HIP(hipEventElapsedTime(&ms_h, ev_[7], ev_[2]));
+        // either half: the base Gramian of the fixed side and its inverse, where the plan has them, then the solve
+        hipEvent_t from_w = ev_[0], from_h = ev_[1];
+        if (plan_.has_base_gramian()) {
+            MFX_HIP(hipEventElapsedTime(&ms_gh, from_w, ev_[4]));
+            MFX_HIP(hipEventElapsedTime(&ms_gw, from_h, ev_[5]));
+            from_w = ev_[4]; from_h = ev_[5];
             t_half_[2] += ms_gh * 1e-3; t_half_[3] += ms_gw * 1e-3; n_half_[2]++; n_half_[3]++;
-            t_half_[4] += ms_ih * 1e-3; t_half_[5] += ms_iw * 1e-3; n_half_[4]++; n_half_[5]++;
-        } else if (implicit_) {
-            MFX_HIP(hipEventElapsedTime(&ms_gh, ev_[0], ev_[4]));
-            MFX_HIP(hipEventElapsedTime(&ms_w, ev_[4], ev_[1]));
-            MFX_HIP(hipEventElapsedTime(&ms_gw, ev_[1], ev_[5]));
-            MFX_HIP(hipEventElapsedTime(&ms_h, ev_[5], ev_[2]));
-            t_half_[2] += ms_gh * 1e-3; t_half_[3] += ms_gw * 1e-3; n_half_[2]++; n_half_[3]++;
-        } else {
-            MFX_HIP(hipEventElapsedTime(&ms_w, ev_[0], ev_[1]));
-            MFX_HIP(hipEventElapsedTime(&ms_h, ev_[1], ev_[2]));
         }
+        if (plan_.has_inverse()) {
+            MFX_HIP(hipEventElapsedTime(&ms_ih, from_w, ev_[6]));
+            MFX_HIP(hipEventElapsedTime(&ms_iw, from_h, ev_[7]));
+            from_w = ev_[6]; from_h = ev_[7];
+            t_half_[4] += ms_ih * 1e-3; t_half_[5] += ms_iw * 1e-3; n_half_[4]++; n_half_[5]++;
+        }
+        MFX_HIP(hipEventElapsedTime(&ms_w, from_w, ev_[1]));
+        MFX_HIP(hipEventElapsedTime(&ms_h, from_h, ev_[2]));
         MFX_HIP(hipEventElapsedTime(&ms_r, ev_[2], ev_[3]));
         t_half_[0] += ms_w * 1e-3; t_half_[1] += ms_h * 1e-3; n_half_[0]++; n_half_[1]++;
         mfx_iter_report rep;
@@ -471,16 +503,10 @@ int AlsSolver::get_factors(float* W, float* H, mfx_memspace space) {
 }
 
 int AlsSolver::kernel_times(int cap, const char** names, double* seconds, int64_t* launches) {
-    static const char* nm[2] = {"als_half_rows(W over H)", "als_half_cols(H over W)"};
-    static const char* nm_impl[4] = {"ials_half_rows(W over H)", "ials_half_cols(H over W)", "ials_base_gram(H)", "ials_base_gram(W)"};
-    static const char* nm_block[4] = {"ialsb_half_rows(W over H)", "ialsb_half_cols(H over W)", "ialsb_base_gram(H)", "ialsb_base_gram(W)"};
-    static const char* nm_eblock[2] = {"alsb_half_rows(W over H)", "alsb_half_cols(H over W)"};
-    static const char* nm_cg[6] = {"ialscg_half_rows(W over H)", "ialscg_half_cols(H over W)", "ialscg_base_gram(H)", "ialscg_base_gram(W)",
-                                   "ialscg_inverse(H)", "ialscg_inverse(W)"};
     int n = 0;
     for (int i = 0; i < 6 && n < cap; ++i) {
         if (!n_half_[i]) continue;
-        if (names) names[n] = cg_ ? nm_cg[i] : block_ && !implicit_ ? nm_eblock[i] : block_ ? nm_block[i] : implicit_ ? nm_impl[i] : nm[i];
+        if (names) names[n] = plan_.pair->names[i];
         if (seconds) seconds[n] = t_half_[i];
         if (launches) launches[n] = n_half_[i];
         ++n;
@@ -490,22 +516,23 @@ int AlsSolver::kernel_times(int cap, const char** names, double* seconds, int64_
 }
 
 int AlsSolver::cg_stats(int64_t out[8]) {
-    MFX_REQUIRE(cg_, "mfx_ials_cg_stats: not a handle of mfx_ials_cg_create");
+    MFX_REQUIRE(plan_.method == PM::Cg, "mfx_ials_cg_stats: not a handle of mfx_ials_cg_create");
     MFX_REQUIRE(out, "mfx_ials_cg_stats: out is NULL");
     for (int i = 0; i < 8; ++i) out[i] = cg_stats_set_ ? cg_stats_[i] : 0;
     return MFX_OK;
 }
 
 int AlsSolver::loss(double* out) {
-    MFX_REQUIRE(implicit_, "mfx_ials_loss: not an implicit-feedback ALS handle (mfx_ials_create)");
+    MFX_REQUIRE(plan_.implicit(), "mfx_ials_loss: not an implicit-feedback ALS handle (mfx_ials_create)");
     MFX_REQUIRE(factors_set_, "mfx_ials_loss: call mfx_als_set_factors first");
     MFX_TRY(use_device(device_));
-    if (!loss_ws_.size()) MFX_TRY(loss_ws_.alloc(robj_ ? ialsr_loss_ws_doubles(k_) : ials_loss_ws_doubles(k_)));
-    if (robj_)
-        MFX_TRY(ialsr_loss_launch(rows_, W_.get(), m_, H_.get(), n_, k_, p_.lambda, alpha_, alpha0_, nu_, rho_rows_.get(), rho_cols_.get(),
-                                  loss_ws_.get(), loss_.get(), st_));
+    AlsPlan& pl = plan_;
+    if (!pl.loss_ws.size()) MFX_TRY(pl.loss_ws.alloc(pl.loss_ws_doubles()));
+    if (pl.objective == PO::ImplicitReg)
+        MFX_TRY(ialsr_loss_launch(rows_, W_.get(), m_, H_.get(), n_, k_, pl.lambda, pl.alpha, pl.alpha0, pl.nu, pl.rho_rows.get(), pl.rho_cols.get(),
+                                  pl.loss_ws.get(), loss_.get(), st_));
     else
-        MFX_TRY(ials_loss_launch(rows_, W_.get(), m_, H_.get(), n_, k_, p_.lambda, alpha_, loss_ws_.get(), loss_.get(), st_));
+        MFX_TRY(ials_loss_launch(rows_, W_.get(), m_, H_.get(), n_, k_, pl.lambda, pl.alpha, pl.loss_ws.get(), loss_.get(), st_));
     MFX_HIP(hipMemcpyAsync(out, loss_.get(), sizeof(double), hipMemcpyDeviceToHost, st_));
     MFX_HIP(hipStreamSynchronize(st_));
     return MFX_OK;
@@ -558,50 +585,31 @@ int als_gramian_op(int64_t cnt, const uint32_t* idx, int64_t nrows_x, const floa
     return MFX_OK;
 }
 
-int als_half_op(int64_t nseg, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val,
-                int64_t nrows_x, const float* X, float* Y, int64_t k, float lambda, int variant, int device) {
-    MFX_REQUIRE(k <= 128, "ALS: rank k = %lld not supported (1 <= k <= 128)", (long long) k);
+int als_plan_half_op(const AlsSpec& spec, const HalfSegs& g, const float* X, const float* Y_in, float* Y_out, int64_t k, float lambda,
+                     int32_t* counts, int device) {
     HalfOp op;
-    MFX_TRY(op.open(device, nseg, nnz, nrows_x, ptr, idx, val));
-    MFX_TRY(op.upload(X, nrows_x, k, true, nullptr));
-    DevBuf<float> ws;
-    MFX_TRY(ws.alloc(std::max<size_t>(1, als_ws_floats(op.h.nslots, (uint32_t) k))));
-    if (variant == 0) MFX_TRY(als_half_exact_launch(op.h, op.X.get(), op.Y.get(), (uint32_t) k, lambda, op.fail_cnt.get(), op.os.st));
-    else MFX_TRY(als_half_launch(op.h, op.X.get(), (uint32_t) nrows_x, op.Y.get(), (uint32_t) k, lambda, ws.get(), op.fail_cnt.get(), op.os.st));
-    return op.download(Y);
-}
-
-int ials_half_op(int64_t nseg, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val,
-                 int64_t nrows_x, const float* X, float* Y, int64_t k, float lambda, float alpha, int device) {
-    HalfOp op;
-    MFX_TRY(op.open(device, nseg, nnz, nrows_x, ptr, idx, val));
-    MFX_TRY(ials_check_values(op.h.val.get(), op.h.nnz, alpha, "mfx_ials_half: value", op.os.st));
-    MFX_TRY(op.upload(X, nrows_x, k, true, nullptr));
-    DevBuf<float> ws, G, part;
-    MFX_TRY(ws.alloc(std::max<size_t>(1, als_ws_floats(op.h.nslots, (uint32_t) k))));
-    MFX_TRY(G.alloc((size_t) k * k));
-    MFX_TRY(part.alloc(ials_base_ws_floats((uint32_t) nrows_x, (uint32_t) k)));
-    MFX_TRY(ials_base_gramian(op.X.get(), (uint32_t) nrows_x, (uint32_t) k, lambda, part.get(), G.get(), op.os.st));
-    MFX_TRY(ials_half_launch(op.h, op.X.get(), (uint32_t) nrows_x, op.Y.get(), (uint32_t) k, G.get(), alpha, ws.get(), op.fail_cnt.get(), op.os.st));
-    return op.download(Y);
-}
-
-int ials_half_reg_op(int64_t nseg, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val, int64_t nrows_x, const float* X,
-                     float* Y, int64_t k, float lambda, float alpha, float alpha0, float nu, int device) {
-    HalfOp op;
-    MFX_TRY(op.open(device, nseg, nnz, nrows_x, ptr, idx, val));
-    MFX_TRY(ials_check_values(op.h.val.get(), op.h.nnz, alpha, "mfx_ials_half_reg: value", op.os.st));
-    MFX_TRY(op.upload(X, nrows_x, k, true, nullptr));
-    DevBuf<float> ws, G, part, rho;
-    MFX_TRY(ws.alloc(std::max<size_t>(1, als_ws_floats(op.h.nslots, (uint32_t) k))));
-    MFX_TRY(G.alloc((size_t) k * k));
-    MFX_TRY(part.alloc(ials_base_ws_floats((uint32_t) nrows_x, (uint32_t) k)));
-    MFX_TRY(rho.alloc((size_t) nseg));
-    MFX_TRY(ialsr_rho_launch(op.h, (uint32_t) nrows_x, lambda, alpha0, nu, rho.get(), op.os.st));
-    MFX_TRY(ialsr_base_gramian(op.X.get(), (uint32_t) nrows_x, (uint32_t) k, alpha0, part.get(), G.get(), op.os.st));
-    MFX_TRY(ialsr_half_launch(op.h, op.X.get(), (uint32_t) nrows_x, op.Y.get(), (uint32_t) k, G.get(), alpha, alpha0, rho.get(), ws.get(),
-                              op.fail_cnt.get(), op.os.st));
-    return op.download(Y);
+    AlsPlan pl;
+    MFX_TRY(pl.set(spec, (uint32_t) k, lambda));
+    MFX_TRY(op.open(device, g.nseg, g.nnz, g.nrows_x, g.ptr, g.idx, g.val));
+    MFX_TRY(pl.check_values(op.h, (std::string(spec.fn) + ": value").c_str(), op.os.st));
+    MFX_TRY(pl.alloc((uint32_t) g.nrows_x, op.h.nseg, op.h.nnz, op.h.nslots, op.os.st));
+    MFX_TRY(op.upload(X, g.nrows_x, k, pl.method != PM::Blocks, Y_in));  // (the block sweeps gather the zero row from their packed copy)
+    if (pl.objective == PO::ImplicitReg) {
+        MFX_TRY(pl.rho_rows.alloc(op.h.nseg));
+        MFX_TRY(ialsr_rho_launch(op.h, (uint32_t) g.nrows_x, lambda, pl.alpha0, pl.nu, pl.rho_rows.get(), op.os.st));
+    }
+    const bool cg = pl.method == PM::Cg;
+    MFX_TRY(als_plan_half(pl, op.h, op.X.get(), (uint32_t) g.nrows_x, op.Y.get(), Y_in != nullptr, pl.rho_rows.get(), nullptr, nullptr,
+                          cg ? pl.cg_fail.get() : op.fail_cnt.get(), pl.cg_cnt.get(), op.os.st));
+    uint32_t bad_pivots = 0;
+    if (cg) {
+        MFX_HIP(hipMemcpyAsync(&bad_pivots, pl.cg_fail.get(), sizeof(bad_pivots), hipMemcpyDeviceToHost, op.os.st));
+        if (counts) MFX_HIP(hipMemcpyAsync(counts, pl.cgs.counts.get(), sizeof(int32_t) * (size_t) g.nseg, hipMemcpyDeviceToHost, op.os.st));
+    }
+    MFX_TRY(op.download(Y_out));
+    MFX_REQUIRE(bad_pivots == 0, "%s: X^T X + lambda I is not positive definite (%u pivots <= 0 or not finite): X must be finite and "
+                "lambda > 0 unless X has full rank", spec.fn, bad_pivots);
+    return MFX_OK;
 }
 
 }  // namespace mfx

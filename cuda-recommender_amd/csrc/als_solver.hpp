@@ -81,8 +81,6 @@ int ialsb_fold_launch(IalsBlock& b, const AlsHalf& h, const float* X, uint32_t x
 // ials_block_step.hip (als_solver.hip as the k_ialsb_* family): the systems of one block, Z [nseg][d] = the steps
 int ialsb_step_launch(const AlsHalf& h, const float* Xb, uint32_t x_rows, float* Z, uint32_t d, const float* Gbb, float alpha,
                       const float* score, const float* P, float* ws, uint32_t* spd_fail, hipStream_t st);
-int ials_block_half_op(int64_t nseg, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val, int64_t nrows_x,
-                       const float* X, const float* Y_in, float* Y_out, int64_t k, int32_t block, float lambda, float alpha, int device);
 
 // Implicit ALS with an unobserved weight alpha0 and a regulariser per segment rho_s = fp32(lambda (n_s + alpha0 N)^nu), n_s the
 // segment's entries with r > 0 and N the rows of the fixed side (mfx_ials_create_reg, mfx_ials_block_create_reg).
@@ -105,11 +103,6 @@ int ialsrb_step_launch(const AlsHalf& h, const float* Xb, uint32_t x_rows, float
 size_t ialsr_loss_ws_doubles(uint32_t k);
 int ialsr_loss_launch(const AlsHalf& rows, const float* W, uint32_t m, const float* H, uint32_t n, uint32_t k, float lambda, float alpha,
                       float alpha0, float nu, const float* rho_rows, const float* rho_cols, double* ws, double* out, hipStream_t st);
-int ials_half_reg_op(int64_t nseg, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val, int64_t nrows_x, const float* X,
-                     float* Y, int64_t k, float lambda, float alpha, float alpha0, float nu, int device);
-int ials_block_half_reg_op(int64_t nseg, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val, int64_t nrows_x,
-                           const float* X, const float* Y_in, float* Y_out, int64_t k, int32_t block, float lambda, float alpha, float alpha0,
-                           float nu, int device);
 
 // Explicit ALS by block subspace sweeps (mfx_als_block_create; the explicit part of ials_block.hip): the objective
 // sum_j (r_j - <x_j, y>)^2 + rho |y|^2 of a segment, rho = lambda (reg 0) or fp32(lambda * n) for n stored entries (reg 1),
@@ -130,8 +123,6 @@ int alsb_step_launch(const AlsHalf& h, const float* Xb, uint32_t x_rows, float* 
                      const float* score, const float* P, float* ws, uint32_t* spd_fail, hipStream_t st);
 // MFX_ERR_INVALID unless every value is finite (device-side check)
 int als_check_finite(const float* d_val, uint64_t n, const char* what, hipStream_t st);
-int als_block_half_op(int64_t nseg, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val, int64_t nrows_x,
-                      const float* X, const float* Y_in, float* Y_out, int64_t k, int32_t block, float lambda, int32_t reg, int device);
 
 // Fold-in by preconditioned conjugate gradients (rec_foldin_cg.hip; mfx_rec_fold_in_cg_setup): every row's system
 // is the fixed base plus a matrix of the rank of the row, so CG preconditioned by the inverse of the base ends after n + 1 steps
@@ -191,31 +182,80 @@ struct IalsCg {
 int ialscg_half_launch(IalsCg& c, const AlsHalf& h, const float* X, uint32_t x_rows, float* Y, bool warm, float lambda, float alpha,
                        int32_t steps, float tol, uint32_t* fails, unsigned long long* stats, hipEvent_t ev_gram, hipEvent_t ev_inv,
                        hipStream_t st);
-int ials_cg_half_op(int64_t nseg, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val, int64_t nrows_x, const float* X,
-                    const float* Y_in, float* Y_out, int64_t k, float lambda, float alpha, int32_t steps, float tol, int32_t* counts,
-                    int device);
+
+// What a trainer is: how a half-sweep solves its segments, on which objective, with which parameters, and the device state
+// built for that pair (FoldPlan of recommend.hpp is the same thing for fold-in).  The pairs that exist are the rows of
+// kAlsPairs (als_host.hip); als_plan_half is the one place that knows which launches make a half-sweep of each.
+struct AlsSpec;
+struct AlsPair;
+struct AlsPlan {
+    // Direct: one closed-form solve per segment at k <= 128 by the MFMA half-sweep families; DirectExact: the same system in
+    // the reference's order of operations (schedule 0, variant 0); Blocks: block subspace sweeps; Cg: conjugate gradients
+    enum class Method { Direct, DirectExact, Blocks, Cg };
+    // what goes on the diagonal: Als lambda, Ccd fp32(lambda * entries of the segment), Implicit the base Gramian's lambda,
+    // ImplicitReg fp32(lambda (n + alpha0 N)^nu) per segment, with alpha0 the weight of the unobserved pairs
+    enum class Objective { Als, Ccd, Implicit, ImplicitReg };
+    Method method = Method::Direct;
+    Objective objective = Objective::Als;
+    const AlsPair* pair = nullptr;  // the row of kAlsPairs
+    uint32_t k = 0;
+    float lambda = 0.f, alpha = 0.f, alpha0 = 1.f, nu = 0.f;  // alpha: 0 on an explicit objective
+    uint32_t block = 0;  // Blocks: the width used, min(k, the width asked for or ialsb_default_block(k))
+    int32_t cap = 0;     // Cg: the most steps a row gets in one half
+    float tol = 0.f;
+    DevBuf<float> ws;                  // Direct: partial slots of split segments (als_ws_floats at rank k)
+    DevBuf<float> G, gpart;            // Direct, implicit: base Gramian [k][k] of the fixed side, its per-partition partials
+    IalsBlock bs;                      // Blocks
+    IalsCg cgs;                        // Cg
+    DevBuf<uint32_t> cg_fail;          // Cg [4]: inverse pivots and failed rows of the W-half, of the H-half
+    DevBuf<unsigned long long> cg_cnt; // Cg [6]: the three counts of ialscg_half_launch, W-half then H-half
+    DevBuf<float> rho_rows, rho_cols;  // ImplicitReg [rows], [cols]: formed once, the pattern of R is fixed (a one-shot: rho_rows)
+    DevBuf<double> loss_ws;            // implicit: fp64 Gramians + entry partials of the objective
+
+    bool implicit() const { return objective == Objective::Implicit || objective == Objective::ImplicitReg; }
+    bool direct() const { return method == Method::Direct || method == Method::DirectExact; }
+    bool has_base_gramian() const { return implicit(); }  // a half-sweep starts with the Gramian of the fixed side (ev_gram)
+    bool has_inverse() const { return method == Method::Cg; }  // ... and inverts it (ev_inv)
+    bool warm_start() const { return method == Method::Blocks || method == Method::Cg; }  // a half-sweep starts from Y's rows
+    size_t loss_ws_doubles() const;
+    // the parameters of a checked spec (als_spec_check) at rank k; touches no device
+    int set(const AlsSpec& s, uint32_t k, float lambda);
+    // the buffers of the pair for halves of up to max_seg segments, nnz entries and nslots partial slots over up to max_rows_x
+    // fixed rows (rho_*, loss_ws: by the caller)
+    int alloc(uint32_t max_rows_x, uint32_t max_seg, uint64_t nnz, uint32_t nslots, hipStream_t st);
+    // the values a half may hold: implicit finite, >= 0 and alpha * value finite; Blocks on an explicit objective finite
+    int check_values(const AlsHalf& h, const char* what, hipStream_t st) const;
+};
+
+// What an entry point asks for: the pair, the parameters as the caller gave them and the entry point's name for the texts.
+struct AlsSpec {
+    AlsPlan::Method method;
+    AlsPlan::Objective objective;
+    const char* fn;
+    bool half = false;  // a single-half entry point (rows = segments, cols = fixed rows), not a create
+    float alpha = 0.f, alpha0 = 1.f, nu = 0.f;
+    int32_t block = 0, reg = 0, cap = 1;  // block: the width asked for (Blocks), 0 = chosen from k; reg: of the explicit Blocks
+    float tol = 0.f;
+    int32_t schedule = 1;              // a create: mfx_params::schedule and the memory space, filled in by AlsSolver::create
+    mfx_memspace space = MFX_HOST;
+};
+// MFX_ERR_INVALID with the entry point's own text for the first thing wrong, in the entry point's own order; touches no device
+int als_spec_check(const AlsSpec& s, int64_t k, float lambda, int64_t rows, int64_t cols, int64_t nnz);
+
+// One half-sweep of a plan: Y [h.nseg][k] over the fixed X [x_rows + 1][k] (last row zeros; Blocks: [x_rows][k] will do).
+// warm (Cg): Y holds the start rows, else Y must be zero.  rho (ImplicitReg): the regulariser of h's segments.  ev_gram /
+// ev_inv (or NULL): recorded after the base Gramian / its inverse, where the plan has one.  fails: device, the failed systems
+// are added to it ([1]; Cg [2]: the inverse's pivots and the failed rows); stats: Cg, device [3] (ialscg_half_launch).
+int als_plan_half(AlsPlan& pl, const AlsHalf& h, const float* X, uint32_t x_rows, float* Y, bool warm, const float* rho, hipEvent_t ev_gram,
+                  hipEvent_t ev_inv, uint32_t* fails, unsigned long long* stats, hipStream_t st, unsigned long long* phases = nullptr);
 
 class AlsSolver {
 public:
-    static int create(AlsSolver** out, const mfx_csx* R, const mfx_coo* T, const mfx_params* p,
-                      mfx_memspace space, const mfx_als_shard* shard = nullptr);
-    // implicit feedback (mfx_ials_create): R holds interaction strengths r >= 0, confidence 1 + alpha r
-    static int create_implicit(AlsSolver** out, const mfx_csx* R, const mfx_params* p, float alpha, mfx_memspace space);
-    // implicit feedback by block subspace sweeps (mfx_ials_block_create): k <= 1024, block = 0 or 1..128
-    static int create_block(AlsSolver** out, const mfx_csx* R, const mfx_params* p, float alpha, int32_t block, mfx_memspace space);
-    // explicit feedback by block subspace sweeps (mfx_als_block_create): k <= 1024, block = 0 or 1..128, reg 0 / 1
-    static int create_block_explicit(AlsSolver** out, const mfx_csx* R, const mfx_coo* T, const mfx_params* p, int32_t block, int32_t reg,
-                                     mfx_memspace space);
-    // the same two with an unobserved weight and a frequency-scaled regulariser (mfx_ials_create_reg: block < 0;
-    // mfx_ials_block_create_reg: block >= 0)
-    static int create_implicit_reg(AlsSolver** out, const mfx_csx* R, const mfx_params* p, float alpha, float alpha0, float nu, int32_t block,
-                                   mfx_memspace space);
-    // implicit feedback by preconditioned conjugate gradients (mfx_ials_cg_create): k <= 1024, at most `steps` steps per row
-    // and half, a row stops once |b - A y| <= tol |b| (tol = 0: never)
-    static int create_cg(AlsSolver** out, const mfx_csx* R, const mfx_params* p, float alpha, int32_t steps, float tol, mfx_memspace space);
-    // the last iteration of a create_cg handle, W-half then H-half: row-steps, most steps of a row, rows out of steps, failed rows
+    // every mfx_*_create of an ALS trainer: checks the spec, then builds the solver and the plan of the pair
+    static int create(AlsSolver** out, const mfx_csx* R, const mfx_coo* T, const mfx_params* p, mfx_memspace space, const mfx_als_shard* shard,
+                      const AlsSpec& spec);
+    // the last iteration of a Cg handle, W-half then H-half: row-steps, most steps of a row, rows out of steps, failed rows
     int cg_stats(int64_t out[8]);
-    bool implicit() const { return implicit_; }
     int loss(double* out);  // implicit only: the objective at the current factors (ials.hip)
     ~AlsSolver();
     int set_factors(const float* W, const float* H, mfx_memspace space);
@@ -225,12 +265,11 @@ public:
 
 private:
     AlsSolver() = default;
-    int init(const mfx_csx* R, const mfx_coo* T, const mfx_params* p, mfx_memspace space, const mfx_als_shard* shard);
+    int init(const mfx_csx* R, const mfx_coo* T, const mfx_params* p, mfx_memspace space, const mfx_als_shard* shard, const AlsSpec& spec);
     int exchange(float* X, const std::vector<int64_t>& bounds);  // every rank broadcasts its block of X (one grouped call)
     int meet_shards();  // first iterate() of a sharded solve: gathers everyone's block boundaries (never in create)
-    // One half-sweep of iterate(): Y [h.nseg][k] (this rank's rows from y_lo on) over the fixed X [x_rows][k]; rho = the
-    // regulariser of h's segments (robj_), ev_gram = the event recorded once the base Gramian of X is done (implicit_)
-    int half_sweep(const AlsHalf& h, const float* X, uint32_t x_rows, float* Y, uint32_t y_lo, const float* rho, hipEvent_t ev_gram);
+    // One half-sweep of iterate(), half 0: W (this rank's rows from row_lo_ on) over H, half 1: H over W
+    int half_sweep(int half);
     int device_ = 0;
     hipStream_t st_ = nullptr;
     mfx_params p_{};
@@ -242,7 +281,8 @@ private:
     bool shards_met_ = false;  // both boundary vectors gathered AND validated (meet_shards)
     int64_t global_test_nnz_ = 0;
     AlsHalf rows_, cols_;
-    DevBuf<float> W_, H_, ws_;
+    DevBuf<float> W_, H_;
+    AlsPlan plan_;
     DevBuf<uint32_t> spd_fail_;
     DevBuf<unsigned long long> phases_;  // MFX_ALS_PHASES=1: per-phase clocks of the half-sweep kernels (diagnostic)
     int print_phases(const char* what);
@@ -254,28 +294,11 @@ private:
     double update_acc_ = 0;
     bool factors_set_ = false;
     hipEvent_t ev_[8] = {};
-    // [0], [1]: the two half-sweeps; implicit: [2], [3] the base Gramians of H and W; cg_: [4], [5] their inverses
+    // [0], [1]: the two half-sweeps; with a base Gramian: [2], [3] those of H and W; with an inverse: [4], [5] those
     double t_half_[6] = {0, 0, 0, 0, 0, 0};
     int64_t n_half_[6] = {0, 0, 0, 0, 0, 0};
-    // implicit feedback
-    bool implicit_ = false;
-    float alpha_ = 0.f;
-    DevBuf<float> G_, gpart_;        // base Gramian [k][k] of the fixed side, its per-partition partials
-    DevBuf<double> loss_ws_, loss_;  // fp64 Gramians + entry partials of the objective, the objective
-    uint32_t block_ = 0;             // > 0: block subspace sweeps with blocks of block_ coordinates
-    IalsBlock bs_;
-    int32_t reg_ = 0;                // explicit block sweeps: 1 = fp32(lambda * n) on the diagonal of a segment of n entries
-    // implicit feedback with an unobserved weight and a regulariser per segment (create_implicit_reg)
-    bool robj_ = false;
-    float alpha0_ = 1.f, nu_ = 0.f;
-    DevBuf<float> rho_rows_, rho_cols_;  // [m_], [n_]: formed once, the pattern of R is fixed
-    // implicit feedback by conjugate gradients (create_cg)
-    bool cg_ = false, w_cold_ = false;   // w_cold_: set_factors got no W, the next W-half starts from zero
-    int32_t cg_steps_ = 0;
-    float cg_tol_ = 0.f;
-    IalsCg cgs_;
-    DevBuf<uint32_t> cg_fail_;           // [4]: inverse pivots and failed rows of the W-half, of the H-half
-    DevBuf<unsigned long long> cg_cnt_;  // [6]: the three counts of ialscg_half_launch, W-half then H-half
+    DevBuf<double> loss_;   // implicit: the objective
+    bool w_cold_ = false;   // Cg: set_factors got no W, the next W-half starts from zero
     int64_t cg_stats_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     bool cg_stats_set_ = false;
 };
@@ -337,7 +360,7 @@ int als_inverse_op(int64_t k, const float* A, float* Ainv, int device);
 int als_gramian_launch(const AlsItem* item, const uint32_t* idx, const float* val, uint32_t cnt, const float* X, uint32_t x_rows, float* Y,
                        uint32_t k, uint32_t* spd_fail, float* A, hipStream_t st);
 
-// ---- One-shot entry points (host pointers in and out; als_host.hip, ials_block.hip) -----------------------------------
+// ---- One-shot entry points (host pointers in and out; als_host.hip) ----------------------------------------------------
 struct OpStream {  // a stream of the call's own, drained and destroyed on every way out
     hipStream_t st = nullptr;
     ~OpStream() { if (st) { (void) hipStreamSynchronize(st); (void) hipStreamDestroy(st); } }
@@ -357,10 +380,18 @@ struct HalfOp {
 
 int als_gramian_op(int64_t cnt, const uint32_t* idx, int64_t nrows_x, const float* X, int64_t k, float* A,
                    int device);
-int als_half_op(int64_t nseg, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val,
-                int64_t nrows_x, const float* X, float* Y, int64_t k, float lambda, int variant, int device);
-int ials_half_op(int64_t nseg, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val,
-                 int64_t nrows_x, const float* X, float* Y, int64_t k, float lambda, float alpha, int device);
+// The segments of a single-half entry point as the caller gave them
+struct HalfSegs {
+    int64_t nseg, nnz;
+    const uint32_t* ptr;
+    const uint32_t* idx;
+    const float* val;
+    int64_t nrows_x;
+};
+// One half-sweep of the pair of a checked spec, by als_plan_half over buffers that AlsPlan::alloc sized to this half: every
+// mfx_*_half.  Y_in: the start rows (Blocks, Cg) or NULL; counts (Cg): host [nseg], the steps applied to each row, or NULL
+int als_plan_half_op(const AlsSpec& spec, const HalfSegs& g, const float* X, const float* Y_in, float* Y_out, int64_t k, float lambda,
+                     int32_t* counts, int device);
 
 }  // namespace mfx
 

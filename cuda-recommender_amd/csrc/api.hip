@@ -187,25 +187,40 @@ int mfx_ccdpp_run(const mfx_csx* R, const mfx_coo* T, float* W, float* H, const 
 }
 
 /* ------------------------------------------------------------------ ALS */
+// The seven creates and the seven single halves of the ALS trainers: each fills an AlsSpec, which als_spec_check checks in the
+// entry point's own order (AlsSolver::create, als_half).
+using AlsM = AlsPlan::Method;
+using AlsO = AlsPlan::Objective;
+
+static int als_create(mfx_als_t* out, const mfx_csx* R, const mfx_coo* T, const mfx_params* p, mfx_memspace space, const mfx_als_shard* shard,
+                      const AlsSpec& spec) {
+    MFX_REQUIRE(out, "%s: out is NULL", spec.fn);
+    *out = nullptr;
+    AlsSolver* s = nullptr;
+    MFX_TRY(AlsSolver::create(&s, R, T, p, space, shard, spec));  // (argument checks before the device is touched)
+    *out = new mfx_als_s{s};
+    return MFX_OK;
+}
+// The checks of a half's arrays, then of its spec, then the half itself.  k_positive: mfx_als_half counts k <= 0 as a bad argument
+static int als_half(AlsSpec spec, const HalfSegs& g, const float* X, const float* Y_in, float* Y_out, int64_t k, float lambda, int32_t* counts,
+                    int device, bool k_positive = false) {
+    spec.half = true;
+    MFX_REQUIRE(g.nseg > 0 && g.nnz >= 0 && g.ptr && X && Y_out && (!k_positive || k > 0) && g.nrows_x > 0, "%s: bad argument", spec.fn);
+    MFX_REQUIRE(g.nnz == 0 || (g.idx && g.val), "%s: null idx / val with nnz > 0", spec.fn);
+    MFX_TRY(als_spec_check(spec, k, lambda, g.nseg, g.nrows_x, g.nnz));  // (with the sizes: their place differs by entry point)
+    return als_plan_half_op(spec, g, X, Y_in, Y_out, k, lambda, counts, device);
+}
+
 int mfx_als_create(mfx_als_t* out, const mfx_csx* R, const mfx_coo* T, const mfx_params* p, mfx_memspace space) {
     return guarded("mfx_als_create", [&]() -> int {
-        MFX_REQUIRE(out, "mfx_als_create: out is NULL");
-        *out = nullptr;
-        AlsSolver* s = nullptr;
-        MFX_TRY(AlsSolver::create(&s, R, T, p, space));
-        *out = new mfx_als_s{s};
-        return MFX_OK;
+        return als_create(out, R, T, p, space, nullptr, AlsSpec{AlsM::Direct, AlsO::Als, "mfx_als_create"});
     });
 }
 int mfx_als_create_sharded(mfx_als_t* out, const mfx_csx* R, const mfx_coo* T, const mfx_params* p,
                            const mfx_als_shard* shard) {
     return guarded("mfx_als_create_sharded", [&]() -> int {
         MFX_REQUIRE(out && shard && shard->comm, "mfx_als_create_sharded: null argument");
-        *out = nullptr;
-        AlsSolver* s = nullptr;
-        MFX_TRY(AlsSolver::create(&s, R, T, p, MFX_HOST, shard));
-        *out = new mfx_als_s{s};
-        return MFX_OK;
+        return als_create(out, R, T, p, MFX_HOST, shard, AlsSpec{AlsM::Direct, AlsO::Als, "mfx_als_create"});
     });
 }
 int mfx_als_set_factors(mfx_als_t s, const float* W, const float* H, mfx_memspace space) {
@@ -243,49 +258,33 @@ int mfx_als_destroy(mfx_als_t s) {
 /* ------------------------------------------------------------------ implicit-feedback ALS */
 int mfx_ials_create(mfx_als_t* out, const mfx_csx* R, const mfx_params* p, float alpha, mfx_memspace space) {
     return guarded("mfx_ials_create", [&]() -> int {
-        MFX_REQUIRE(out, "mfx_ials_create: out is NULL");
-        *out = nullptr;
-        AlsSolver* s = nullptr;
-        MFX_TRY(AlsSolver::create_implicit(&s, R, p, alpha, space));  // (argument checks before the device is touched)
-        *out = new mfx_als_s{s};
-        return MFX_OK;
+        AlsSpec s{AlsM::Direct, AlsO::Implicit, "mfx_ials_create"};
+        s.alpha = alpha;
+        return als_create(out, R, nullptr, p, space, nullptr, s);
     });
 }
 int mfx_ials_block_create(mfx_als_t* out, const mfx_csx* R, const mfx_params* p, float alpha, int32_t block, mfx_memspace space) {
     return guarded("mfx_ials_block_create", [&]() -> int {
-        MFX_REQUIRE(out, "mfx_ials_block_create: out is NULL");
-        *out = nullptr;
-        AlsSolver* s = nullptr;
-        MFX_TRY(AlsSolver::create_block(&s, R, p, alpha, block, space));  // (argument checks before the device is touched)
-        *out = new mfx_als_s{s};
-        return MFX_OK;
+        AlsSpec s{AlsM::Blocks, AlsO::Implicit, "mfx_ials_block_create"};
+        s.alpha = alpha; s.block = block;
+        return als_create(out, R, nullptr, p, space, nullptr, s);
     });
 }
 int mfx_ials_block_half(int64_t nseg, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val,
                         int64_t nrows_x, const float* X, const float* Y_in, float* Y_out, int64_t k, int32_t block,
                         float lambda, float alpha, int device) {
     return guarded("mfx_ials_block_half", [&]() -> int {
-        MFX_REQUIRE(nseg > 0 && nnz >= 0 && ptr && X && Y_out && nrows_x > 0, "mfx_ials_block_half: bad argument");
-        MFX_REQUIRE(nnz == 0 || (idx && val), "mfx_ials_block_half: null idx / val with nnz > 0");
-        MFX_REQUIRE(k >= 1 && k <= (int64_t) kIalsBlockMaxRank, "implicit ALS by block sweeps: rank k = %lld not supported (1 <= k <= %u)",
-                    (long long) k, kIalsBlockMaxRank);
-        MFX_REQUIRE(block >= 0 && block <= (int32_t) kIalsBlockMaxBlock,
-                    "implicit ALS by block sweeps: block = %d (0 = chosen from k, else 1 <= block <= %u)", block, kIalsBlockMaxBlock);
-        MFX_REQUIRE(std::isfinite(alpha) && alpha >= 0.f, "mfx_ials_block_half: alpha = %g (finite and >= 0 required)", (double) alpha);
-        MFX_REQUIRE(nseg < (int64_t) 0xFFFFFFFFll && nrows_x < (int64_t) 0xFFFFFFFFll && nnz < (int64_t) 0xFFFF0000ll,
-                    "mfx_ials_block_half: sizes exceed the 32-bit index range");
-        return ials_block_half_op(nseg, nnz, ptr, idx, val, nrows_x, X, Y_in, Y_out, k, block, lambda, alpha, device);
+        AlsSpec s{AlsM::Blocks, AlsO::Implicit, "mfx_ials_block_half"};
+        s.alpha = alpha; s.block = block;
+        return als_half(s, {nseg, nnz, ptr, idx, val, nrows_x}, X, Y_in, Y_out, k, lambda, nullptr, device);
     });
 }
 /* ------------------------------------------------------------------ implicit ALS by conjugate gradients */
 int mfx_ials_cg_create(mfx_als_t* out, const mfx_csx* R, const mfx_params* p, float alpha, int32_t steps, float tol, mfx_memspace space) {
     return guarded("mfx_ials_cg_create", [&]() -> int {
-        MFX_REQUIRE(out, "mfx_ials_cg_create: out is NULL");
-        *out = nullptr;
-        AlsSolver* s = nullptr;
-        MFX_TRY(AlsSolver::create_cg(&s, R, p, alpha, steps, tol, space));  // (argument checks before the device is touched)
-        *out = new mfx_als_s{s};
-        return MFX_OK;
+        AlsSpec s{AlsM::Cg, AlsO::Implicit, "mfx_ials_cg_create"};
+        s.alpha = alpha; s.cap = steps; s.tol = tol;
+        return als_create(out, R, nullptr, p, space, nullptr, s);
     });
 }
 int mfx_ials_cg_stats(mfx_als_t s, int64_t out[8]) {
@@ -298,16 +297,9 @@ int mfx_ials_cg_half(int64_t nseg, int64_t nnz, const uint32_t* ptr, const uint3
                      const float* Y_in, float* Y_out, int64_t k, float lambda, float alpha, int32_t steps, float tol, int32_t* counts,
                      int device) {
     return guarded("mfx_ials_cg_half", [&]() -> int {
-        MFX_REQUIRE(nseg > 0 && nnz >= 0 && ptr && X && Y_out && nrows_x > 0, "mfx_ials_cg_half: bad argument");
-        MFX_REQUIRE(nnz == 0 || (idx && val), "mfx_ials_cg_half: null idx / val with nnz > 0");
-        MFX_REQUIRE(k >= 1 && k <= (int64_t) kIalsBlockMaxRank, "implicit ALS by conjugate gradients: rank k = %lld not supported (1 <= k <= %u)",
-                    (long long) k, kIalsBlockMaxRank);
-        MFX_REQUIRE(steps >= 1, "implicit ALS by conjugate gradients: steps = %d (>= 1 required)", steps);
-        MFX_REQUIRE(std::isfinite(tol) && tol >= 0.f, "implicit ALS by conjugate gradients: tol = %g (finite and >= 0 required)", (double) tol);
-        MFX_REQUIRE(std::isfinite(alpha) && alpha >= 0.f, "mfx_ials_cg_half: alpha = %g (finite and >= 0 required)", (double) alpha);
-        MFX_REQUIRE(nseg < (int64_t) 0xFFFFFFFFll && nrows_x < (int64_t) 0xFFFFFFFFll && nnz < (int64_t) 0xFFFF0000ll,
-                    "mfx_ials_cg_half: sizes exceed the 32-bit index range");
-        return ials_cg_half_op(nseg, nnz, ptr, idx, val, nrows_x, X, Y_in, Y_out, k, lambda, alpha, steps, tol, counts, device);
+        AlsSpec s{AlsM::Cg, AlsO::Implicit, "mfx_ials_cg_half"};
+        s.alpha = alpha; s.cap = steps; s.tol = tol;
+        return als_half(s, {nseg, nnz, ptr, idx, val, nrows_x}, X, Y_in, Y_out, k, lambda, counts, device);
     });
 }
 int mfx_spd_inverse(int64_t k, const float* A, float* Ainv, int device) {
@@ -320,28 +312,17 @@ int mfx_spd_inverse(int64_t k, const float* A, float* Ainv, int device) {
 int mfx_als_block_create(mfx_als_t* out, const mfx_csx* R, const mfx_coo* T, const mfx_params* p, int32_t block, int32_t reg,
                          mfx_memspace space) {
     return guarded("mfx_als_block_create", [&]() -> int {
-        MFX_REQUIRE(out, "mfx_als_block_create: out is NULL");
-        *out = nullptr;
-        AlsSolver* s = nullptr;
-        MFX_TRY(AlsSolver::create_block_explicit(&s, R, T, p, block, reg, space));  // (argument checks before the device is touched)
-        *out = new mfx_als_s{s};
-        return MFX_OK;
+        AlsSpec s{AlsM::Blocks, reg == 1 ? AlsO::Ccd : AlsO::Als, "mfx_als_block_create"};
+        s.block = block; s.reg = reg;
+        return als_create(out, R, T, p, space, nullptr, s);
     });
 }
 int mfx_als_block_half(int64_t nseg, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val, int64_t nrows_x,
                        const float* X, const float* Y_in, float* Y_out, int64_t k, int32_t block, float lambda, int32_t reg, int device) {
     return guarded("mfx_als_block_half", [&]() -> int {
-        MFX_REQUIRE(nseg > 0 && nnz >= 0 && ptr && X && Y_out && nrows_x > 0, "mfx_als_block_half: bad argument");
-        MFX_REQUIRE(nnz == 0 || (idx && val), "mfx_als_block_half: null idx / val with nnz > 0");
-        MFX_REQUIRE(k >= 1 && k <= (int64_t) kIalsBlockMaxRank, "explicit ALS by block sweeps: rank k = %lld not supported (1 <= k <= %u)",
-                    (long long) k, kIalsBlockMaxRank);
-        MFX_REQUIRE(block >= 0 && block <= (int32_t) kIalsBlockMaxBlock,
-                    "explicit ALS by block sweeps: block = %d (0 = chosen from k, else 1 <= block <= %u)", block, kIalsBlockMaxBlock);
-        MFX_REQUIRE(reg == 0 || reg == 1, "mfx_als_block_half: reg = %d (0 = lambda, 1 = lambda * entries of the segment)", reg);
-        MFX_REQUIRE(std::isfinite(lambda) && lambda > 0.f, "mfx_als_block_half: lambda = %g (finite and > 0 required)", (double) lambda);
-        MFX_REQUIRE(nseg < (int64_t) 0xFFFFFFFFll && nrows_x < (int64_t) 0xFFFFFFFFll && nnz < (int64_t) 0xFFFF0000ll,
-                    "mfx_als_block_half: sizes exceed the 32-bit index range");
-        return als_block_half_op(nseg, nnz, ptr, idx, val, nrows_x, X, Y_in, Y_out, k, block, lambda, reg, device);
+        AlsSpec s{AlsM::Blocks, reg == 1 ? AlsO::Ccd : AlsO::Als, "mfx_als_block_half"};
+        s.block = block; s.reg = reg;
+        return als_half(s, {nseg, nnz, ptr, idx, val, nrows_x}, X, Y_in, Y_out, k, lambda, nullptr, device);
     });
 }
 int mfx_ials_loss(mfx_als_t s, double* loss) {
@@ -353,25 +334,18 @@ int mfx_ials_loss(mfx_als_t s, double* loss) {
 int mfx_ials_half(int64_t nseg, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val,
                   int64_t nrows_x, const float* X, float* Y, int64_t k, float lambda, float alpha, int device) {
     return guarded("mfx_ials_half", [&]() -> int {
-        MFX_REQUIRE(nseg > 0 && nnz >= 0 && ptr && X && Y && nrows_x > 0, "mfx_ials_half: bad argument");
-        MFX_REQUIRE(nnz == 0 || (idx && val), "mfx_ials_half: null idx / val with nnz > 0");
-        MFX_REQUIRE(k >= 1 && k <= 128, "implicit ALS: rank k = %lld not supported (1 <= k <= 128)", (long long) k);
-        MFX_REQUIRE(std::isfinite(alpha) && alpha >= 0.f, "mfx_ials_half: alpha = %g (finite and >= 0 required)", (double) alpha);
-        MFX_REQUIRE(nseg < (int64_t) 0xFFFFFFFFll && nrows_x < (int64_t) 0xFFFFFFFFll && nnz < (int64_t) 0xFFFF0000ll,
-                    "mfx_ials_half: sizes exceed the 32-bit index range");
-        return ials_half_op(nseg, nnz, ptr, idx, val, nrows_x, X, Y, k, lambda, alpha, device);
+        AlsSpec s{AlsM::Direct, AlsO::Implicit, "mfx_ials_half"};
+        s.alpha = alpha;
+        return als_half(s, {nseg, nnz, ptr, idx, val, nrows_x}, X, nullptr, Y, k, lambda, nullptr, device);
     });
 }
 
 /* ------------------------------------------------------------------ implicit ALS: unobserved weight, scaled regulariser */
 int mfx_ials_create_reg(mfx_als_t* out, const mfx_csx* R, const mfx_params* p, float alpha, float alpha0, float nu, mfx_memspace space) {
     return guarded("mfx_ials_create_reg", [&]() -> int {
-        MFX_REQUIRE(out, "mfx_ials_create_reg: out is NULL");
-        *out = nullptr;
-        AlsSolver* s = nullptr;
-        MFX_TRY(AlsSolver::create_implicit_reg(&s, R, p, alpha, alpha0, nu, -1, space));  // (argument checks before the device is touched)
-        *out = new mfx_als_s{s};
-        return MFX_OK;
+        AlsSpec s{AlsM::Direct, AlsO::ImplicitReg, "mfx_ials_create_reg"};
+        s.alpha = alpha; s.alpha0 = alpha0; s.nu = nu;
+        return als_create(out, R, nullptr, p, space, nullptr, s);
     });
 }
 int mfx_ials_block_create_reg(mfx_als_t* out, const mfx_csx* R, const mfx_params* p, float alpha, float alpha0, float nu, int32_t block,
@@ -379,41 +353,28 @@ int mfx_ials_block_create_reg(mfx_als_t* out, const mfx_csx* R, const mfx_params
     return guarded("mfx_ials_block_create_reg", [&]() -> int {
         MFX_REQUIRE(out, "mfx_ials_block_create_reg: out is NULL");
         *out = nullptr;
+        // (this entry point alone refuses a negative block before it looks at anything else)
         MFX_REQUIRE(block >= 0, "implicit ALS by block sweeps: block = %d (0 = chosen from k, else 1 <= block <= %u)", block, kIalsBlockMaxBlock);
-        AlsSolver* s = nullptr;
-        MFX_TRY(AlsSolver::create_implicit_reg(&s, R, p, alpha, alpha0, nu, block, space));
-        *out = new mfx_als_s{s};
-        return MFX_OK;
+        AlsSpec s{AlsM::Blocks, AlsO::ImplicitReg, "mfx_ials_block_create_reg"};
+        s.alpha = alpha; s.alpha0 = alpha0; s.nu = nu; s.block = block;
+        return als_create(out, R, nullptr, p, space, nullptr, s);
     });
 }
 int mfx_ials_half_reg(int64_t nseg, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val, int64_t nrows_x, const float* X,
                       float* Y, int64_t k, float lambda, float alpha, float alpha0, float nu, int device) {
     return guarded("mfx_ials_half_reg", [&]() -> int {
-        MFX_REQUIRE(nseg > 0 && nnz >= 0 && ptr && X && Y && nrows_x > 0, "mfx_ials_half_reg: bad argument");
-        MFX_REQUIRE(nnz == 0 || (idx && val), "mfx_ials_half_reg: null idx / val with nnz > 0");
-        MFX_REQUIRE(k >= 1 && k <= 128, "implicit ALS: rank k = %lld not supported (1 <= k <= 128)", (long long) k);
-        MFX_REQUIRE(std::isfinite(alpha) && alpha >= 0.f, "mfx_ials_half_reg: alpha = %g (finite and >= 0 required)", (double) alpha);
-        MFX_REQUIRE(nseg < (int64_t) 0xFFFFFFFFll && nrows_x < (int64_t) 0xFFFFFFFFll && nnz < (int64_t) 0xFFFF0000ll,
-                    "mfx_ials_half_reg: sizes exceed the 32-bit index range");
-        MFX_TRY(ialsr_check_params("mfx_ials_half_reg", lambda, alpha0, nu, nseg, nrows_x));
-        return ials_half_reg_op(nseg, nnz, ptr, idx, val, nrows_x, X, Y, k, lambda, alpha, alpha0, nu, device);
+        AlsSpec s{AlsM::Direct, AlsO::ImplicitReg, "mfx_ials_half_reg"};
+        s.alpha = alpha; s.alpha0 = alpha0; s.nu = nu;
+        return als_half(s, {nseg, nnz, ptr, idx, val, nrows_x}, X, nullptr, Y, k, lambda, nullptr, device);
     });
 }
 int mfx_ials_block_half_reg(int64_t nseg, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val, int64_t nrows_x,
                             const float* X, const float* Y_in, float* Y_out, int64_t k, int32_t block, float lambda, float alpha,
                             float alpha0, float nu, int device) {
     return guarded("mfx_ials_block_half_reg", [&]() -> int {
-        MFX_REQUIRE(nseg > 0 && nnz >= 0 && ptr && X && Y_out && nrows_x > 0, "mfx_ials_block_half_reg: bad argument");
-        MFX_REQUIRE(nnz == 0 || (idx && val), "mfx_ials_block_half_reg: null idx / val with nnz > 0");
-        MFX_REQUIRE(k >= 1 && k <= (int64_t) kIalsBlockMaxRank, "implicit ALS by block sweeps: rank k = %lld not supported (1 <= k <= %u)",
-                    (long long) k, kIalsBlockMaxRank);
-        MFX_REQUIRE(block >= 0 && block <= (int32_t) kIalsBlockMaxBlock,
-                    "implicit ALS by block sweeps: block = %d (0 = chosen from k, else 1 <= block <= %u)", block, kIalsBlockMaxBlock);
-        MFX_REQUIRE(std::isfinite(alpha) && alpha >= 0.f, "mfx_ials_block_half_reg: alpha = %g (finite and >= 0 required)", (double) alpha);
-        MFX_REQUIRE(nseg < (int64_t) 0xFFFFFFFFll && nrows_x < (int64_t) 0xFFFFFFFFll && nnz < (int64_t) 0xFFFF0000ll,
-                    "mfx_ials_block_half_reg: sizes exceed the 32-bit index range");
-        MFX_TRY(ialsr_check_params("mfx_ials_block_half_reg", lambda, alpha0, nu, nseg, nrows_x));
-        return ials_block_half_reg_op(nseg, nnz, ptr, idx, val, nrows_x, X, Y_in, Y_out, k, block, lambda, alpha, alpha0, nu, device);
+        AlsSpec s{AlsM::Blocks, AlsO::ImplicitReg, "mfx_ials_block_half_reg"};
+        s.alpha = alpha; s.alpha0 = alpha0; s.nu = nu; s.block = block;
+        return als_half(s, {nseg, nnz, ptr, idx, val, nrows_x}, X, Y_in, Y_out, k, lambda, nullptr, device);
     });
 }
 
@@ -585,11 +546,8 @@ int mfx_als_inverse(int64_t k, const float* A, float* Ainv, int device) {
 int mfx_als_half(int64_t nseg, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val,
                  int64_t nrows_x, const float* X, float* Y, int64_t k, float lambda, int variant, int device) {
     return guarded("mfx_als_half", [&]() -> int {
-        MFX_REQUIRE(nseg > 0 && nnz >= 0 && ptr && X && Y && k > 0 && nrows_x > 0, "mfx_als_half: bad argument");
-        MFX_REQUIRE(nnz == 0 || (idx && val), "mfx_als_half: null idx / val with nnz > 0");
-        MFX_REQUIRE(nseg < (int64_t) 0xFFFFFFFFll && nrows_x < (int64_t) 0xFFFFFFFFll && nnz < (int64_t) 0xFFFF0000ll,
-                    "mfx_als_half: sizes exceed the 32-bit index range");
-        return als_half_op(nseg, nnz, ptr, idx, val, nrows_x, X, Y, k, lambda, variant, device);
+        const AlsSpec s{variant == 0 ? AlsM::DirectExact : AlsM::Direct, AlsO::Als, "mfx_als_half"};
+        return als_half(s, {nseg, nnz, ptr, idx, val, nrows_x}, X, nullptr, Y, k, lambda, nullptr, device, true);
     });
 }
 

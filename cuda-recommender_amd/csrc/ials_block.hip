@@ -499,38 +499,6 @@ int ialsb_fold_launch(IalsBlock& b, const AlsHalf& h, const float* X, uint32_t x
                      [&]() { return ialsb_sweep_launch(b, h, X, x_rows, Y, alpha, spd_fail, st, alpha0, rho); });
 }
 
-int ials_block_half_op(int64_t nseg, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val, int64_t nrows_x,
-                       const float* X, const float* Y_in, float* Y_out, int64_t k, int32_t block, float lambda, float alpha, int device) {
-    HalfOp op;
-    MFX_TRY(op.open(device, nseg, nnz, nrows_x, ptr, idx, val));
-    MFX_TRY(ials_check_values(op.h.val.get(), op.h.nnz, alpha, "mfx_ials_block_half: value", op.os.st));
-    const uint32_t d = std::min<uint32_t>(block ? (uint32_t) block : ialsb_default_block((uint32_t) k), (uint32_t) k);
-    IalsBlock b;
-    MFX_TRY(b.alloc((uint32_t) k, d, (uint32_t) nrows_x, (uint32_t) nseg, (uint64_t) nnz, op.h.nslots, op.os.st));
-    MFX_TRY(op.upload(X, nrows_x, k, false, Y_in));
-    MFX_TRY(ialsb_gramian(b, op.X.get(), (uint32_t) nrows_x, lambda, op.os.st));
-    MFX_TRY(ialsb_half_launch(b, op.h, op.X.get(), (uint32_t) nrows_x, op.Y.get(), alpha, op.fail_cnt.get(), op.os.st));
-    return op.download(Y_out);
-}
-
-int ials_block_half_reg_op(int64_t nseg, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val, int64_t nrows_x,
-                           const float* X, const float* Y_in, float* Y_out, int64_t k, int32_t block, float lambda, float alpha, float alpha0,
-                           float nu, int device) {
-    HalfOp op;
-    MFX_TRY(op.open(device, nseg, nnz, nrows_x, ptr, idx, val));
-    MFX_TRY(ials_check_values(op.h.val.get(), op.h.nnz, alpha, "mfx_ials_block_half_reg: value", op.os.st));
-    const uint32_t d = std::min<uint32_t>(block ? (uint32_t) block : ialsb_default_block((uint32_t) k), (uint32_t) k);
-    IalsBlock b;
-    MFX_TRY(b.alloc((uint32_t) k, d, (uint32_t) nrows_x, (uint32_t) nseg, (uint64_t) nnz, op.h.nslots, op.os.st));
-    MFX_TRY(op.upload(X, nrows_x, k, false, Y_in));
-    DevBuf<float> rho;
-    MFX_TRY(rho.alloc((size_t) nseg));
-    MFX_TRY(ialsr_rho_launch(op.h, (uint32_t) nrows_x, lambda, alpha0, nu, rho.get(), op.os.st));
-    MFX_TRY(ialsrb_gramian(b, op.X.get(), (uint32_t) nrows_x, alpha0, op.os.st));
-    MFX_TRY(ialsb_half_launch(b, op.h, op.X.get(), (uint32_t) nrows_x, op.Y.get(), alpha, op.fail_cnt.get(), op.os.st, alpha0, rho.get()));
-    return op.download(Y_out);
-}
-
 // ---- Explicit feedback ------------------------------------------------------------------------------------------
 int IalsBlock::alloc_explicit(uint32_t k_, uint32_t d_, uint32_t max_rows_x, uint32_t max_seg, uint64_t nnz, uint32_t nslots, hipStream_t st) {
     k = k_; d = d_;
@@ -598,19 +566,6 @@ int alsb_half_launch(IalsBlock& b, const AlsHalf& h, const float* X, uint32_t x_
 int alsb_fold_launch(IalsBlock& b, const AlsHalf& h, const float* X, uint32_t x_rows, float* Y, float lambda, int32_t reg, int32_t sweeps,
                      float tol, int32_t* counts, uint32_t* spd_fail, hipStream_t st) {
     return fold_loop(h, b.k, Y, sweeps, tol, counts, st, [&]() { return alsb_sweep_launch(b, h, X, x_rows, Y, lambda, reg, spd_fail, st); });
-}
-
-int als_block_half_op(int64_t nseg, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val, int64_t nrows_x,
-                      const float* X, const float* Y_in, float* Y_out, int64_t k, int32_t block, float lambda, int32_t reg, int device) {
-    HalfOp op;
-    MFX_TRY(op.open(device, nseg, nnz, nrows_x, ptr, idx, val));
-    MFX_TRY(als_check_finite(op.h.val.get(), op.h.nnz, "mfx_als_block_half: value", op.os.st));
-    const uint32_t d = std::min<uint32_t>(block ? (uint32_t) block : ialsb_default_block((uint32_t) k), (uint32_t) k);
-    IalsBlock b;
-    MFX_TRY(b.alloc_explicit((uint32_t) k, d, (uint32_t) nrows_x, (uint32_t) nseg, (uint64_t) nnz, op.h.nslots, op.os.st));
-    MFX_TRY(op.upload(X, nrows_x, k, false, Y_in));
-    MFX_TRY(alsb_half_launch(b, op.h, op.X.get(), (uint32_t) nrows_x, op.Y.get(), lambda, reg, op.fail_cnt.get(), op.os.st));
-    return op.download(Y_out);
 }
 
 }  // namespace mfx

@@ -72,28 +72,4 @@ int ialscg_half_launch(IalsCg& c, const AlsHalf& h, const float* X, uint32_t x_r
     return MFX_OK;
 }
 
-int ials_cg_half_op(int64_t nseg, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val, int64_t nrows_x, const float* X,
-                    const float* Y_in, float* Y_out, int64_t k, float lambda, float alpha, int32_t steps, float tol, int32_t* counts,
-                    int device) {
-    HalfOp op;
-    MFX_TRY(op.open(device, nseg, nnz, nrows_x, ptr, idx, val));
-    MFX_TRY(ials_check_values(op.h.val.get(), op.h.nnz, alpha, "mfx_ials_cg_half: value", op.os.st));
-    IalsCg c;
-    MFX_TRY(c.alloc((uint32_t) k, (uint32_t) nrows_x, (uint32_t) nseg, op.h.nslots, steps));
-    MFX_TRY(op.upload(X, nrows_x, k, true, Y_in));
-    DevBuf<uint32_t> fails;
-    DevBuf<unsigned long long> stats;
-    MFX_TRY(fails.alloc_zero(2, op.os.st));
-    MFX_TRY(stats.alloc(3));
-    MFX_TRY(ialscg_half_launch(c, op.h, op.X.get(), (uint32_t) nrows_x, op.Y.get(), Y_in != nullptr, lambda, alpha, steps, tol, fails.get(),
-                               stats.get(), nullptr, nullptr, op.os.st));
-    uint32_t bad[2] = {0, 0};
-    MFX_HIP(hipMemcpyAsync(bad, fails.get(), sizeof(bad), hipMemcpyDeviceToHost, op.os.st));
-    if (counts) MFX_HIP(hipMemcpyAsync(counts, c.counts.get(), sizeof(int32_t) * (size_t) nseg, hipMemcpyDeviceToHost, op.os.st));
-    MFX_TRY(op.download(Y_out));
-    MFX_REQUIRE(bad[0] == 0, "mfx_ials_cg_half: X^T X + lambda I is not positive definite (%u pivots <= 0 or not finite): X must be finite and "
-                "lambda > 0 unless X has full rank", bad[0]);
-    return MFX_OK;
-}
-
 }  // namespace mfx

@@ -203,6 +203,16 @@ def _coo(T) -> L.mfx_coo:
     return L.mfx_coo(int(T.test_val.shape[0]), _vp(T.test_row), _vp(T.test_col), _vp(T.test_val))
 
 
+def _device_csx_coo(d: dict):
+    """(mfx_csx, mfx_coo) over the device tensors of a layout dict (mfx.synth_torch); the test triplets are optional."""
+    ptr = lambda t: C.c_void_p(int(t.data_ptr())) if t is not None and t.numel() else None
+    csx = L.mfx_csx(int(d["rows"]), int(d["cols"]), int(d["csr_val"].numel()), ptr(d["csc_col_ptr"]), ptr(d["csc_row_idx"]),
+                    ptr(d["csc_val"]), ptr(d["csr_row_ptr"]), ptr(d["csr_col_idx"]), ptr(d["csr_val"]))
+    tv = d.get("test_val")
+    coo = L.mfx_coo(int(tv.numel()) if tv is not None else 0, ptr(d.get("test_row")), ptr(d.get("test_col")), ptr(tv))
+    return csx, coo
+
+
 def _f32c(a, shape=None) -> np.ndarray:
     assert isinstance(a, np.ndarray) and a.dtype == np.float32 and a.flags["C_CONTIGUOUS"], "need C-contiguous float32"
     if shape is not None:
@@ -425,7 +435,37 @@ class CcdSolver:
             pass
 
 
-class AlsSolver:
+class _AlsHandle:
+    """What the resident ALS trainers share: an mfx_als_t, the shape (rows, cols, k) and the factor and timing calls."""
+
+    def set_factors(self, H, W=None):
+        _f32c(H, (self.cols, self.k))
+        if W is not None:
+            _f32c(W, (self.rows, self.k))
+        L.check(L.lib().mfx_als_set_factors(self.handle, _vp(W) if W is not None else None, _vp(H), L.MFX_HOST))
+
+    def get_factors(self):
+        W = np.empty((self.rows, self.k), np.float32)
+        H = np.empty((self.cols, self.k), np.float32)
+        L.check(L.lib().mfx_als_get_factors(self.handle, _vp(W), _vp(H), L.MFX_HOST))
+        return W, H
+
+    def kernel_times(self):
+        return _kernel_times(L.lib().mfx_als_kernel_times, self.handle)
+
+    def close(self):
+        if self.handle:
+            L.lib().mfx_als_destroy(self.handle)
+            self.handle = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class AlsSolver(_AlsHandle):
     """Resident ALS (mfx_als_*)."""
 
     def __init__(self, R: RatingData, T, parameters: parameter, comm: Optional[Comm] = None,
@@ -447,14 +487,8 @@ class AlsSolver:
                 raise ValueError("ALS by block sweeps is single GPU: comm must be None")
             reg = 1 if count_reg else 0
             if device_arrays is not None:
-                d = device_arrays
-                ptr = lambda t: C.c_void_p(int(t.data_ptr())) if t is not None and t.numel() else None
-                self.rows, self.cols, self.k = int(d["rows"]), int(d["cols"]), int(parameters.k)
-                csx = L.mfx_csx(self.rows, self.cols, int(d["csr_val"].numel()), ptr(d["csc_col_ptr"]), ptr(d["csc_row_idx"]),
-                                ptr(d["csc_val"]), ptr(d["csr_row_ptr"]), ptr(d["csr_col_idx"]), ptr(d["csr_val"]))
-                tv = d.get("test_val")
-                coo = L.mfx_coo(int(tv.numel()) if tv is not None else 0, ptr(d.get("test_row")), ptr(d.get("test_col")), ptr(tv))
-                space = L.MFX_DEVICE
+                self.rows, self.cols, self.k = int(device_arrays["rows"]), int(device_arrays["cols"]), int(parameters.k)
+                (csx, coo), space = _device_csx_coo(device_arrays), L.MFX_DEVICE
             else:
                 self.rows, self.cols, self.k = R.rows, R.cols, int(parameters.k)
                 csx, coo, space = _csx(R), _coo(T), L.MFX_HOST
@@ -462,13 +496,8 @@ class AlsSolver:
             return
         if device_arrays is not None:
             assert comm is None, "device-resident inputs: single-GPU ALS only"
-            d = device_arrays
-            ptr = lambda t: C.c_void_p(int(t.data_ptr())) if t is not None and t.numel() else None
-            self.rows, self.cols, self.k = int(d["rows"]), int(d["cols"]), int(parameters.k)
-            csx = L.mfx_csx(self.rows, self.cols, int(d["csr_val"].numel()), ptr(d["csc_col_ptr"]), ptr(d["csc_row_idx"]), ptr(d["csc_val"]),
-                            ptr(d["csr_row_ptr"]), ptr(d["csr_col_idx"]), ptr(d["csr_val"]))
-            tv = d.get("test_val")
-            coo = L.mfx_coo(int(tv.numel()) if tv is not None else 0, ptr(d.get("test_row")), ptr(d.get("test_col")), ptr(tv))
+            self.rows, self.cols, self.k = int(device_arrays["rows"]), int(device_arrays["cols"]), int(parameters.k)
+            csx, coo = _device_csx_coo(device_arrays)
             L.check(L.lib().mfx_als_create(C.byref(self.handle), C.byref(csx), C.byref(coo), C.byref(cp), L.MFX_DEVICE))
             return
         self.rows, self.cols, self.k = R.rows, R.cols, int(parameters.k)
@@ -494,36 +523,10 @@ class AlsSolver:
         shard = L.mfx_als_shard(comm.handle, rl, rh, cl, ch, int(R.test_val.shape[0]))
         L.check(L.lib().mfx_als_create_sharded(C.byref(self.handle), C.byref(csx), C.byref(coo), C.byref(cp), C.byref(shard)))
 
-    def set_factors(self, H, W=None):
-        _f32c(H, (self.cols, self.k))
-        if W is not None:
-            _f32c(W, (self.rows, self.k))
-        L.check(L.lib().mfx_als_set_factors(self.handle, _vp(W) if W is not None else None, _vp(H), L.MFX_HOST))
-
     def iterate(self, n_iter: int, with_rmse: bool = True):
         reports = (L.mfx_iter_report * max(1, n_iter))()
         L.check(L.lib().mfx_als_iterate(self.handle, n_iter, 1 if with_rmse else 0, reports))
         return list(reports)[:n_iter]
-
-    def get_factors(self):
-        W = np.empty((self.rows, self.k), np.float32)
-        H = np.empty((self.cols, self.k), np.float32)
-        L.check(L.lib().mfx_als_get_factors(self.handle, _vp(W), _vp(H), L.MFX_HOST))
-        return W, H
-
-    def kernel_times(self):
-        return _kernel_times(L.lib().mfx_als_kernel_times, self.handle)
-
-    def close(self):
-        if self.handle:
-            L.lib().mfx_als_destroy(self.handle)
-            self.handle = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def _reg_pair(alpha0, nu):
@@ -533,7 +536,7 @@ def _reg_pair(alpha0, nu):
     return (1.0 if alpha0 is None else float(alpha0), 0.0 if nu is None else float(nu))
 
 
-class ImplicitAlsSolver:
+class ImplicitAlsSolver(_AlsHandle):
     """Resident implicit-feedback ALS (mfx_ials_create): R holds interaction strengths r >= 0, every (user, item)
     pair is in the loss with preference p = (r > 0) and confidence 1 + alpha r.  Factors use the ALS layout,
     W [rows][k] and H [cols][k].  device_arrays: the matrix as a dict of device tensors (mfx.synth_torch).
@@ -555,12 +558,8 @@ class ImplicitAlsSolver:
             raise ValueError("ImplicitAlsSolver: cg= cannot be combined with block=, alpha0= or nu=")
         cp = parameters.to_c()
         if device_arrays is not None:
-            d = device_arrays
-            ptr = lambda t: C.c_void_p(int(t.data_ptr())) if t is not None and t.numel() else None
-            self.rows, self.cols, self.k = int(d["rows"]), int(d["cols"]), int(parameters.k)
-            csx = L.mfx_csx(self.rows, self.cols, int(d["csr_val"].numel()), ptr(d["csc_col_ptr"]), ptr(d["csc_row_idx"]),
-                            ptr(d["csc_val"]), ptr(d["csr_row_ptr"]), ptr(d["csr_col_idx"]), ptr(d["csr_val"]))
-            space = L.MFX_DEVICE
+            self.rows, self.cols, self.k = int(device_arrays["rows"]), int(device_arrays["cols"]), int(parameters.k)
+            csx, space = _device_csx_coo(device_arrays)[0], L.MFX_DEVICE
         else:
             self.rows, self.cols, self.k = R.rows, R.cols, int(parameters.k)
             csx, space = _csx(R), L.MFX_HOST
@@ -578,23 +577,11 @@ class ImplicitAlsSolver:
         else:
             L.check(L.lib().mfx_ials_block_create(C.byref(self.handle), C.byref(csx), C.byref(cp), float(alpha), int(block), space))
 
-    def set_factors(self, H, W=None):
-        _f32c(H, (self.cols, self.k))
-        if W is not None:
-            _f32c(W, (self.rows, self.k))
-        L.check(L.lib().mfx_als_set_factors(self.handle, _vp(W) if W is not None else None, _vp(H), L.MFX_HOST))
-
     def iterate(self, n_iter: int):
         """n_iter (W-half, H-half) sweeps; the reports carry update_time (rmse stays 0)."""
         reports = (L.mfx_iter_report * max(1, n_iter))()
         L.check(L.lib().mfx_als_iterate(self.handle, n_iter, 0, reports))
         return list(reports)[:n_iter]
-
-    def get_factors(self):
-        W = np.empty((self.rows, self.k), np.float32)
-        H = np.empty((self.cols, self.k), np.float32)
-        L.check(L.lib().mfx_als_get_factors(self.handle, _vp(W), _vp(H), L.MFX_HOST))
-        return W, H
 
     def loss(self) -> float:
         """The implicit objective at the current factors (fp64, include/mfx.h mfx_ials_loss)."""
@@ -609,20 +596,6 @@ class ImplicitAlsSolver:
         L.check(L.lib().mfx_ials_cg_stats(self.handle, out))
         keys = ("row_steps", "max_steps", "unconverged", "failed")
         return {half: {key: int(out[4 * i + j]) for j, key in enumerate(keys)} for i, half in enumerate(("rows", "cols"))}
-
-    def kernel_times(self):
-        return _kernel_times(L.lib().mfx_als_kernel_times, self.handle)
-
-    def close(self):
-        if self.handle:
-            L.lib().mfx_als_destroy(self.handle)
-            self.handle = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 # ---------------------------------------------------------------------------------------------
