@@ -410,16 +410,17 @@ struct OpCtx {
 // variants of the single-operator entry points: -1 reference order / 0 wave per segment (plain layout), 1 flat (plain),
 // 2 flat with the layout chosen for the shape, >= 16 explicit LDS panel, <= -16 explicit cache panel.  Anything else is an error.
 static bool op_variant_ok(int variant) { return variant == -1 || variant == 0 || variant == 1 || variant == 2 || variant >= 16 || variant <= -16; }
-static FlatLayoutOptions op_layout(int variant, int64_t nseg, int64_t nnz, int64_t vec_len) {
+static FlatLayoutOptions op_layout(const CcdKnobs& kn, int variant, int64_t nseg, int64_t nnz, int64_t vec_len) {
     mfx_params p;
     mfx_params_default(&p);
     p.panel_rows = (variant >= 16 || variant <= -16) ? variant : variant == 2 ? 0 : -1;
-    return choose_layout(p, (uint32_t) nseg, (uint64_t) nnz, (uint32_t) vec_len, sizeof(float), variant == 0 || variant == -1);
+    return choose_layout(p, kn, (uint32_t) nseg, (uint64_t) nnz, (uint32_t) vec_len, sizeof(float), variant == 0 || variant == -1);
 }
 
 int mfx_rank_one_sweep(int64_t nseg, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val,
                        int64_t vec_len, const float* vec, float lambda, float* out, int variant, int device) {
     return guarded("mfx_rank_one_sweep", [&]() -> int {
+        const CcdKnobs kn = CcdKnobs::from_env();
         MFX_REQUIRE(nseg > 0 && nnz >= 0 && vec_len > 0 && ptr && vec && out, "mfx_rank_one_sweep: bad argument");
         MFX_REQUIRE(nnz == 0 || (idx && val), "mfx_rank_one_sweep: null idx / val with nnz > 0");
         MFX_REQUIRE(nseg < (int64_t) 0xFFFFFFFFll && vec_len < (int64_t) 0xFFFFFFFFll && nnz < (int64_t) 0xFFFF0000ll,
@@ -429,22 +430,22 @@ int mfx_rank_one_sweep(int64_t nseg, int64_t nnz, const uint32_t* ptr, const uin
         MFX_TRY(cx.open(device));
         SegStreamStore s;
         MFX_TRY(s.build((uint32_t) nseg, (uint64_t) nnz, (uint32_t) vec_len, ptr, idx, val, MFX_HOST,
-                        op_layout(variant, nseg, nnz, vec_len), 0, cx.st));
+                        op_layout(kn, variant, nseg, nnz, vec_len), 0, cx.st));
         DevBuf<float> dvec, dout, gh;
         MFX_TRY(dvec.alloc(vec_len)); MFX_TRY(dvec.upload(vec, vec_len, MFX_HOST, cx.st));
         MFX_TRY(dout.alloc(nseg));
         FinalizeArgs f; f.lambda = lambda; f.out_vec = dout.get();
         if (variant == -1) {  // the reference's summation order: sums and division in one kernel (ccd_reforder.hip)
             std::vector<uint32_t> order;
-            const char* e_fused = std::getenv("MFX_REF_FUSED");
-            const bool old_form = e_fused && std::atoi(e_fused) == 0;  // (A/B: the r3 / early-r4 kernels)
-            const uint32_t nlong = ref_sweep_order(ptr, (uint32_t) nseg, &order, !old_form);
+            const bool old_form = !kn.ref_fused;  // (MFX_REF_FUSED=0, A/B: the r3 / early-r4 kernels)
+            const uint32_t nlong = ref_sweep_order(ptr, (uint32_t) nseg, &order, !old_form, kn.ref_long);
             DevBuf<uint32_t> dorder;
             MFX_TRY(dorder.alloc(order.size())); MFX_TRY(dorder.upload(order.data(), order.size(), MFX_HOST, cx.st));
             if (old_form) {
-                MFX_TRY(launch_sweep_ref(s.view, dorder.get(), nlong, dvec.get(), lambda, dout.get(), cx.st));
+                MFX_TRY(launch_sweep_ref(s.view, dorder.get(), nlong, dvec.get(), lambda, dout.get(), cx.st, kn.ref_sweep_dpp));
             } else {
-                RefStreams rs;
+                RefOwnerCtx rs;
+                kn.apply(rs);
                 rs.main = cx.st;  // (one stream: the long segments' kernel first, the others behind it)
                 MFX_TRY(launch_ref_owner(FM_SWEEP, s.view, dorder.get(), nlong, dvec.get(), nullptr, f, rs));
             }
@@ -470,6 +471,7 @@ int mfx_update_rating(int64_t nseg, int64_t nnz, const uint32_t* ptr, const uint
                       int64_t vec_len, const float* gathered, const float* per_seg, int add, int variant,
                       int device) {
     return guarded("mfx_update_rating", [&]() -> int {
+        const CcdKnobs kn = CcdKnobs::from_env();
         MFX_REQUIRE(nseg > 0 && nnz >= 0 && vec_len > 0 && ptr && gathered && per_seg, "mfx_update_rating: bad argument");
         MFX_REQUIRE(nnz == 0 || (idx && val), "mfx_update_rating: null idx / val with nnz > 0");
         MFX_REQUIRE(nseg < (int64_t) 0xFFFFFFFFll && vec_len < (int64_t) 0xFFFFFFFFll && nnz < (int64_t) 0xFFFF0000ll,
@@ -479,7 +481,7 @@ int mfx_update_rating(int64_t nseg, int64_t nnz, const uint32_t* ptr, const uint
         MFX_TRY(cx.open(device));
         SegStreamStore s;
         MFX_TRY(s.build((uint32_t) nseg, (uint64_t) nnz, (uint32_t) vec_len, ptr, idx, val, MFX_HOST,
-                        op_layout(variant, nseg, nnz, vec_len), 0, cx.st));
+                        op_layout(kn, variant, nseg, nnz, vec_len), 0, cx.st));
         DevBuf<float> dg, dp;
         MFX_TRY(dg.alloc(vec_len)); MFX_TRY(dg.upload(gathered, vec_len, MFX_HOST, cx.st));
         MFX_TRY(dp.alloc(nseg)); MFX_TRY(dp.upload(per_seg, nseg, MFX_HOST, cx.st));

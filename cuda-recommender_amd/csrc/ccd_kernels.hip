@@ -659,7 +659,7 @@ __builtin_nontemporal_store(f32x4{vo[0], vo[1], vo[2], vo[3]}, val4 + tile * 64)
 // node costs ~4.8 us whether it streams 1e5 or 1e6 ratings (profiles/r04_kernel_stats_ml1m.csv) -- so an outer
 // iteration is (nodes per rank) x k x ~5 us, and the flat-stream form needs four nodes per rank: its nnz-balanced
 // spans cut segments across workgroups, so the sums must meet in a second kernel (k_finalize), and meeting inside
-// the pass ("last workgroup finalizes") costs more than the node it saves (ccd_solver.hpp, fuse_finalize_).  Here a
+// the pass ("last workgroup finalizes") costs more than the node it saves (ccd_solver.hpp, CcdSolver::use_fused).  Here a
 // segment has ONE owner instead: a wavefront for a short segment, a whole workgroup for a long one (the lists are
 // made once per store, longest first).  The owner has the complete (g, h), divides, and writes the factor entry and
 // the operand packs of the next passes itself: two nodes per rank.  Measured (profiles/r04_exp_small.txt), ML-1M shape
@@ -1614,9 +1614,6 @@ int launch_seg_owner(FlatMode mode, const SegStreamDev& s, const void* gather, c
     MFX_LAUNCH_CHECK();
     return MFX_OK;
 }
-uint32_t seg_owner_long_threshold() {
-    if (const char* e = std::getenv("MFX_OWNER_LONG")) { const int v = std::atoi(e); if (v > 0) return (uint32_t) v; }  // (A/B)
-    return kSegOwnerLong;
-}
+uint32_t seg_owner_long_threshold(uint32_t knob) { return knob ? knob : kSegOwnerLong; }  // (the knob: A/B)
 
 }  // namespace mfx

@@ -71,7 +71,7 @@ struct SegStreamDev {
     const uint32_t* fz_orphans = nullptr;      // [fz_norphans]
     uint32_t fz_norphans = 0, fz_ngroups = 0, fz_max_chunk_groups = 0;
     // (r4) segment-owner fused passes of small matrices (plain layout; k_seg_owner in ccd_kernels.hip): nullptr = not available
-    const uint32_t* own_long = nullptr;        // [own_nlong][4] (segment, first entry, end, 0) of the segments of >= seg_owner_long_threshold() entries: one workgroup each
+    const uint32_t* own_long = nullptr;        // [own_nlong][4] (segment, first entry, end, 0) of the segments of >= seg_owner_long_threshold(...) entries: one workgroup each
     const uint32_t* own_short = nullptr;       // [own_nshort][4] all other segments, longest first: one wavefront each
     uint32_t own_nlong = 0, own_nshort = 0;
     uint32_t own_max_len = 0;                  // the longest segment (the owner form gives balance up: the solver declines it beyond 65536 entries)
@@ -133,9 +133,12 @@ int launch_resid_wave(const SegStreamDev& s, const float* gathered, const float*
 // right in unfused fp32 from (0, lambda * count) -- RankOneUpdate_Original_float (src/CCD.cpp:6-16) bit for bit.
 // order: dispatch order of the segments (ref_sweep_order: longest first) or nullptr (ascending).
 // nlong: the leading `order` entries that take the two-wave plain-add form (ref_sweep_order's return value; 0 with order == nullptr)
-int launch_sweep_ref(const SegStreamDev& s, const uint32_t* order, uint32_t nlong, const float* vec, float lambda, float* out, hipStream_t st);
+// dpp_form: MFX_REF_SWEEP_DPP, the single-kernel launch shape whatever nlong says (A/B)
+int launch_sweep_ref(const SegStreamDev& s, const uint32_t* order, uint32_t nlong, const float* vec, float lambda, float* out, hipStream_t st,
+                     bool dpp_form = false);
 // owner_form: the count of long segments for launch_ref_owner (>= 4096 entries) instead of launch_sweep_ref's (>= 32768)
-uint32_t ref_sweep_order(const uint32_t* ptr_host, uint32_t nseg, std::vector<uint32_t>* order, bool owner_form = false);
+// ref_long: MFX_REF_LONG, a threshold that overrides both (0: none)
+uint32_t ref_sweep_order(const uint32_t* ptr_host, uint32_t nseg, std::vector<uint32_t>* order, bool owner_form = false, uint32_t ref_long = 0);
 
 // partials + carries of a flat pass -> dense gh[0..nseg) = g, gh[nseg..2nseg) = h (0 for empty).
 int launch_combine_dense(const SegStreamDev& s, float* gh, hipStream_t st);
@@ -169,12 +172,16 @@ int launch_finalize(const SegStreamDev& s, const FinalizeArgs& a, hipStream_t st
 // FM_FCSR (perseg must be f.pack2) or the read-only FM_SWEEP -- with every sum in the reference's order and the division g / h from
 // h = lambda * count + ... (src/CCD.cpp:6-16): bit for bit the reference's values.  order / nlong: ref_sweep_order's.  Items holding a
 // long segment run as a second kernel on rs.side when it is set (joined into rs.main before returning), else behind each other on rs.main.
-struct RefStreams {
+struct RefOwnerCtx {
     hipStream_t main = nullptr, side = nullptr;
     hipEvent_t fork = nullptr, join = nullptr;
+    // knobs of k_ref_quad's launch (CcdKnobs::apply, ccd_solver.hpp)
+    long quad_tab = -1;        // MFX_REF_QUAD_TAB: -1 the default rule, 0 never the LDS table, n > 1 a table of n bytes whatever it covers
+    long quad_tab_bytes = 0;   // MFX_REF_QUAD_TAB_BYTES: a smaller table under the default rule (<= 0: the whole of it)
+    uint32_t quad_wgs = 0;     // MFX_REF_QUAD_WGS: grid cap of the form without a table (0: the default)
 };
 int launch_ref_owner(FlatMode mode, const SegStreamDev& s, const uint32_t* order, uint32_t nlong, const void* gather, const void* perseg,
-                     const FinalizeArgs& f, const RefStreams& rs);
+                     const FinalizeArgs& f, const RefOwnerCtx& rs);
 
 // calrmse_r1 (src/tools.cpp:261-270): resid[q] -= Wt[row] * Ht[col] - oldWt[row] * oldHt[col]; *sum_out = sum resid^2
 // resid[q] = val[q] - sum_t W[t][row] * H[t][col] (fp32, rank order): where a rank trace starts from
@@ -190,7 +197,7 @@ int launch_flat_fused(FlatMode mode, const SegStreamDev& s, const void* gather, 
 // (r4) pass + finalize of one rank-one half-step in ONE launch, every segment owned by one wavefront / workgroup (small matrices,
 // plain layout): FM_FCSC / FM_FCSR (perseg must be f.pack2) or the read-only FM_SWEEP (perseg nullptr, only f.out_vec is written)
 int launch_seg_owner(FlatMode mode, const SegStreamDev& s, const void* gather, const void* perseg, const FinalizeArgs& f, hipStream_t st);
-uint32_t seg_owner_long_threshold();
+uint32_t seg_owner_long_threshold(uint32_t knob);  // knob: MFX_OWNER_LONG (0: the default)
 // first / last segment of every workgroup chunk's real entries (0xFFFFFFFF / 0 for a chunk of padding only)
 // wg_spans: spans per workgroup chunk (16 for LDS panels, 4 for the plain layout's 256-thread workgroups)
 int launch_chunk_seg_range(const SegStreamDev& s, uint32_t wg_spans, const uint32_t* panel_end, uint32_t* seg_first, uint32_t* seg_last, hipStream_t st);

@@ -289,7 +289,7 @@ __global__ __launch_bounds__(kRef2Block) void k_sweep_ref2(uint32_t nseg, uint32
 // for bit (a sum that started at +0 or lambda * count >= 0 is never -0), so chunks are aligned to 16 bytes and rows of different
 // lengths share a wave without masks in the chain.
 //
-// On top of it the reference-order mode gets the SCHEDULE of the default path (ccd_solver.hip, rank_fused_owner): the pending
+// On top of it the reference-order mode gets the SCHEDULE of the default path (ccd_solver.hip, rank_fused: the Owner schedule): the pending
 // subtraction of rank t - 1, the add-back of rank t and the first sweep of rank t in one pass per copy -- r' = (r - a b) + c d with
 // the reference's own unfused roundings (the element update of every other path), the term from r' -- and the division and the
 // operand packs of the next pass written by the segment's owner: two launches per rank instead of four sweeps / passes, no separate
@@ -700,7 +700,7 @@ __global__ __launch_bounds__(kSplitBlock) void k_ref_split(RefOwnerArgs a) {
 uint32_t ref_split_items(uint32_t nlong) { return (nlong + 3u) / 4u; }
 
 int launch_ref_owner(FlatMode mode, const SegStreamDev& s, const uint32_t* order, uint32_t nlong, const void* gather, const void* perseg,
-                     const FinalizeArgs& f, const RefStreams& rs) {
+                     const FinalizeArgs& f, const RefOwnerCtx& rs) {
     if (s.nseg == 0) return MFX_OK;
     MFX_REQUIRE(s.panel_rows == 0 && !s.scatter && s.ptr && s.idx && s.val && order, "launch_ref_owner: needs the plain layout and the dispatch order");
     MFX_REQUIRE(!f.gh_dense && !f.cnt_override && !f.pack4_as3 && !f.nmf && !f.fundec_seg && f.out_vec, "launch_ref_owner: dense / overridden / extended finalize inputs are not supported");
@@ -745,12 +745,11 @@ int launch_ref_owner(FlatMode mode, const SegStreamDev& s, const uint32_t* order
         const uint32_t nq = a.nitems - a.item0;
         // the LDS table form when a CU's LDS covers at least a quarter of the operand table (MFX_REF_QUAD_TAB=0: never; = n > 1: a table
         // of n bytes whatever it covers -- tests and the fuzzer exercise partly covered tables on small matrices with it)
-        const char* tab_env = std::getenv("MFX_REF_QUAD_TAB");
-        const long tab_set = tab_env ? std::atol(tab_env) : -1;
+        const long tab_set = rs.quad_tab;
         const size_t elem = mode == FM_SWEEP ? sizeof(float) : mode == FM_FCSC ? sizeof(float2) : sizeof(F3r);
-        const char* cap_env = std::getenv("MFX_REF_QUAD_TAB_BYTES");  // (A/B: a smaller table under the default rule -- two workgroups per CU from 80 KB down:
-                                                                      // Netflix shape 73.4 ms per outer iteration with 80 KB, 71.7 with 106 KB, 75.2 with 53 KB, 66-68 with the full 160 KB)
-        const size_t tab_cap = cap_env && std::atol(cap_env) > 0 ? std::min<size_t>((size_t) std::atol(cap_env), kQuadTabBytes) : kQuadTabBytes;
+        // (MFX_REF_QUAD_TAB_BYTES, A/B: a smaller table under the default rule -- two workgroups per CU from 80 KB down:
+        // Netflix shape 73.4 ms per outer iteration with 80 KB, 71.7 with 106 KB, 75.2 with 53 KB, 66-68 with the full 160 KB)
+        const size_t tab_cap = rs.quad_tab_bytes > 0 ? std::min<size_t>((size_t) rs.quad_tab_bytes, kQuadTabBytes) : kQuadTabBytes;
         const size_t tab_bytes = tab_set > 1 ? std::min<size_t>((size_t) tab_set, kQuadTabBytes) : tab_cap;
         const uint32_t tab_n = (uint32_t) std::min<size_t>(s.gather_len, tab_bytes / elem);
         const bool tab = tab_set != 0 && tab_n > 0 && (tab_set > 1 || ((uint64_t) tab_n * 4u >= s.gather_len && nq >= 64u));
@@ -780,7 +779,7 @@ int launch_ref_owner(FlatMode mode, const SegStreamDev& s, const uint32_t* order
             }
         } else {
             const uint32_t waves_per_block = kQuadBlock / 64;
-            static const uint32_t cap = [] { const char* e = std::getenv("MFX_REF_QUAD_WGS"); const int v = e ? std::atoi(e) : 0; return v > 0 ? (uint32_t) v : 256u * 16u; }();
+            const uint32_t cap = rs.quad_wgs ? rs.quad_wgs : 256u * 16u;  // (MFX_REF_QUAD_WGS)
             const uint32_t grid = std::min<uint32_t>((nq + waves_per_block - 1) / waves_per_block, cap);
             switch (mode) {
                 case FM_SWEEP: hipLaunchKernelGGL((k_ref_quad<FM_SWEEP, false>), dim3(grid), dim3(kQuadBlock), 0, st_quad, a, 0u); break;
@@ -799,13 +798,13 @@ int launch_ref_owner(FlatMode mode, const SegStreamDev& s, const uint32_t* order
 }
 
 // Segments by descending length (ties: ascending id): the dispatch order of k_sweep_ref.
-uint32_t ref_sweep_order(const uint32_t* ptr_host, uint32_t nseg, std::vector<uint32_t>* order, bool owner_form) {
+uint32_t ref_sweep_order(const uint32_t* ptr_host, uint32_t nseg, std::vector<uint32_t>* order, bool owner_form, uint32_t ref_long) {
     order->resize(nseg);
     std::iota(order->begin(), order->end(), 0u);
     std::stable_sort(order->begin(), order->end(), [&](uint32_t x, uint32_t y) {
         return ptr_host[x + 1] - ptr_host[x] > ptr_host[y + 1] - ptr_host[y];
     });
-    const uint32_t env_thr = [] { const char* e = std::getenv("MFX_REF_LONG"); const int v = e ? std::atoi(e) : 0; return v > 0 ? (uint32_t) v : 0u; }();  // (A/B, tests)
+    const uint32_t env_thr = ref_long;  // (MFX_REF_LONG: A/B, tests)
     const uint32_t thr = env_thr ? env_thr : (owner_form ? kRefSplit : kRefLong);
     uint32_t nlong = 0;
     while (nlong < nseg && nlong < 8192u && ptr_host[(*order)[nlong] + 1] - ptr_host[(*order)[nlong]] >= thr) ++nlong;
@@ -816,11 +815,12 @@ uint32_t ref_sweep_order(const uint32_t* ptr_host, uint32_t nseg, std::vector<ui
     return nlong;
 }
 
-int launch_sweep_ref(const SegStreamDev& s, const uint32_t* order, uint32_t nlong, const float* vec, float lambda, float* out, hipStream_t st) {
+int launch_sweep_ref(const SegStreamDev& s, const uint32_t* order, uint32_t nlong, const float* vec, float lambda, float* out, hipStream_t st,
+                     bool dpp_form) {
     if (s.nseg == 0) return MFX_OK;
     MFX_REQUIRE(s.panel_rows == 0 && s.ptr && (s.nnz == 0 || (s.idx && s.val)), "the reference-order sweep needs the plain layout");
-    static const bool dpp_form = [] { const char* e = std::getenv("MFX_REF_SWEEP_DPP"); return e && std::atoi(e) != 0; }();  // (A/B: the r3 kernel alone)
-    if (dpp_form || !order || nlong == 0) {  // (no long segment -- e.g. the row side of the Netflix shape: the r3 launch shape, 0.61 against 0.79 ms)
+    if (dpp_form ||  // (MFX_REF_SWEEP_DPP, A/B: the r3 kernel alone)
+        !order || nlong == 0) {  // (no long segment -- e.g. the row side of the Netflix shape: the r3 launch shape, 0.61 against 0.79 ms)
         const uint32_t waves_per_block = kRefBlock / 64;
         const uint32_t grid = std::min<uint32_t>((s.nseg + waves_per_block - 1) / waves_per_block, 256u * 8u);
         hipLaunchKernelGGL(k_sweep_ref, dim3(grid), dim3(kRefBlock), 0, st, s.nseg, order, s.ptr, s.idx, s.val, vec, lambda, out);

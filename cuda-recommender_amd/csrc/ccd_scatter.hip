@@ -48,7 +48,7 @@
 //
 // (r4) PANEL GROUPS.  A store can be launched group by group (consecutive panels each; SegStreamDev::scat_ngroups), each
 // launch aligned on its own, so that in a sharded solve group j's sums are combined, all-reduced and finalized on a
-// second stream while group j + 1 is streamed (CcdSolver::rank_fused_scatter).  The sums are integers: any grouping
+// second stream while group j + 1 is streamed (CcdSolver::half_step, the Scatter schedule).  The sums are integers: any grouping
 // gives the same bits (test_scatter_overlap_groups_are_bit_identical).
 //
 // The per-element arithmetic is the reference's (unfused multiply, subtract, multiply, add) as in the flat

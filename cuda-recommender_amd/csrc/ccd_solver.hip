@@ -23,9 +23,9 @@
 namespace mfx {
 
 namespace {
-// MFX_SETUP_TIMING=1 prints where the one-time layout build spends its time.
+// MFX_SETUP_TIMING=1 (FlatLayoutOptions::setup_timing) prints where the one-time layout build spends its time.
 struct PhaseTimer {
-    bool on = getenv("MFX_SETUP_TIMING") != nullptr;
+    bool on;
     std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
     void lap(const char* what) {
         if (!on) return;
@@ -46,25 +46,25 @@ int SegStreamStore::build(uint32_t nseg, uint64_t nnz, uint32_t G, const uint32_
     if (build_mode != 1) {
         bool done = false;
         MFX_TRY(build_device(nseg, nnz, G, ptr, idx, val, space, opt, st, &done));
-        if (done) { built_on_device_ = true; MFX_TRY(build_fuse_tables(st)); return build_owner_lists(st); }
+        if (done) { built_on_device_ = true; MFX_TRY(build_fuse_tables(opt, st)); return build_owner_lists(opt, st); }
         MFX_REQUIRE(build_mode != 2, "layout_build = 2: the pattern is not grouped (some segment visits a panel more than "
                                      "once; sort the indices inside every row / column) -- the device builder cannot take it");
     }
     MFX_REQUIRE(!opt.scatter, "the scatter layout is built by the device pipeline only (pattern not grouped, or layout_build = 1)");
     MFX_TRY(build_host(nseg, nnz, G, ptr, idx, val, space, opt, st));
-    MFX_TRY(build_fuse_tables(st));
-    return build_owner_lists(st);
+    MFX_TRY(build_fuse_tables(opt, st));
+    return build_owner_lists(opt, st);
 }
 
 // (r4) Owner lists of the segment-owner fused passes (k_seg_owner): plain layout of a small matrix only.  Long segments
 // (one workgroup each) and the rest (one wavefront each), both longest first so that the big items start first.
-int SegStreamStore::build_owner_lists(hipStream_t st) {
+int SegStreamStore::build_owner_lists(const FlatLayoutOptions& opt, hipStream_t st) {
     if (view.panel_rows != 0 || view.scatter || view.nseg == 0 || !view.ptr || view.nnz >= 4000000ull) return MFX_OK;
     std::vector<uint32_t> ptr_h((size_t) view.nseg + 1);
     MFX_HIP(hipMemcpyAsync(ptr_h.data(), view.ptr, sizeof(uint32_t) * ptr_h.size(), hipMemcpyDeviceToHost, st));
     MFX_HIP(hipStreamSynchronize(st));
     std::vector<uint32_t> longs, shorts;
-    const uint32_t thr = seg_owner_long_threshold();
+    const uint32_t thr = seg_owner_long_threshold(opt.owner_long);
     for (uint32_t c = 0; c < view.nseg; ++c) (ptr_h[c + 1] - ptr_h[c] >= thr ? longs : shorts).push_back(c);
     auto by_len = [&](uint32_t x, uint32_t y) { return ptr_h[x + 1] - ptr_h[x] > ptr_h[y + 1] - ptr_h[y]; };
     std::stable_sort(longs.begin(), longs.end(), by_len);
@@ -87,7 +87,7 @@ int SegStreamStore::build_owner_lists(hipStream_t st) {
 // Fused finalize: which segment groups each workgroup chunk contributes to, how many chunks a group waits for, and
 // the dispatch order (ascending first segment).  One small kernel finds every chunk's first / last segment; the
 // rest is host arithmetic over a few thousand chunks.
-int SegStreamStore::build_fuse_tables(hipStream_t st) {
+int SegStreamStore::build_fuse_tables(const FlatLayoutOptions& opt, hipStream_t st) {
     // LDS panels with 16-span workgroups (1024 threads), or (r4) the plain layout: 256-thread workgroups of four spans
     const bool plain = view.panel_rows == 0;
     if (!(plain || (view.lds_panels && view.spans_per_wg == 16)) || view.scatter || view.nseg == 0 || view.nspans == 0 || !view.ptr_v || !view.rank_code) return MFX_OK;
@@ -123,9 +123,8 @@ int SegStreamStore::build_fuse_tables(hipStream_t st) {
     // MFX_FUSE_FINALIZE=2: dispatch in ascending order of the first segment, so that a group's chunks run at about
     // the same time and groups complete all along the pass (1: stored, panel-major order -- groups complete while the
     // last panel is processed).  Measured slower still: every panel's slice is then live at once.
-    const char* fz_env = std::getenv("MFX_FUSE_FINALIZE");
-    if (fz_env && std::atoi(fz_env) == 2)
-    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return first[a] < first[b]; });  // padding-only chunks last
+    if (opt.fuse_by_first_seg)
+        std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return first[a] < first[b]; });  // padding-only chunks last
     MFX_TRY(fz_order_.alloc(nchunks)); MFX_TRY(fz_order_.upload(order.data(), nchunks, MFX_HOST, st));
     MFX_TRY(fz_g0_.alloc(nchunks)); MFX_TRY(fz_g0_.upload(g0.data(), nchunks, MFX_HOST, st));
     MFX_TRY(fz_g1_.alloc(nchunks)); MFX_TRY(fz_g1_.upload(g1.data(), nchunks, MFX_HOST, st));
@@ -145,7 +144,7 @@ int SegStreamStore::build_fuse_tables(hipStream_t st) {
 int SegStreamStore::build_device(uint32_t nseg, uint64_t nnz, uint32_t G, const uint32_t* ptr, const uint32_t* idx,
                                  const float* val, mfx_memspace space, const FlatLayoutOptions& opt, hipStream_t st, bool* done) {
     *done = false;
-    PhaseTimer tm;
+    PhaseTimer tm{opt.setup_timing};
     DevBuf<uint32_t> in_ptr, in_idx;
     DevBuf<float> in_val;
     LayoutBuildIn in;
@@ -278,7 +277,7 @@ int SegStreamStore::build_device(uint32_t nseg, uint64_t nnz, uint32_t G, const 
         // one workgroup per CU (a workgroup takes the whole LDS) unless the solver asks for fewer (CUs left to a concurrent
         // collective); MFX_SCATTER_WGS overrides for experiments and tests
         uint32_t want = opt.scatter_wgs ? opt.scatter_wgs : (cus > 0 ? (uint32_t) cus : 256u);
-        if (const char* e = std::getenv("MFX_SCATTER_WGS")) { const int v = std::atoi(e); if (v > 0) want = (uint32_t) v; }
+        if (opt.scatter_wgs_pin) want = opt.scatter_wgs_pin;
         // panel groups (consecutive panels; one launch each, SegStreamDev::scat_ngroups): every launch spreads ITS chunks
         // over the workgroups; the slabs are numbered across the groups, so a panel's slabs stay consecutive
         const uint32_t ngroups = std::max(1u, std::min(std::min(opt.scatter_groups, P), (uint32_t) SegStreamDev::kMaxScatterGroups));
@@ -349,7 +348,7 @@ int SegStreamStore::build_host(uint32_t nseg, uint64_t nnz, uint32_t G, const ui
                                const float* val, mfx_memspace space, const FlatLayoutOptions& opt, hipStream_t st) {
     // The host builder (one pass over the pattern, a few threads); device-resident inputs are brought
     // down once for it.  Takes every pattern, and is the checker of the device pipeline in the tests.
-    PhaseTimer tm;
+    PhaseTimer tm{opt.setup_timing};
     std::vector<uint32_t> ptr_buf, idx_buf;
     std::vector<float> val_buf;
     const uint32_t* ptr_h = ptr;
@@ -486,9 +485,10 @@ int SegStreamStore::unpermute(float* out, hipStream_t st) {
 // LDS bytes per gathered index of the CSR copy's slice: (v_prev_new, v_t_old, v_t_new) -- ccd_kernels.hip, ModeTraits<FM_FCSR>::S
 constexpr uint32_t kCsrSliceBytes = 12;
 
-FlatLayoutOptions choose_layout(const mfx_params& p, uint32_t nseg, uint64_t nnz, uint32_t G, uint32_t elem_bytes,
+FlatLayoutOptions choose_layout(const mfx_params& p, const CcdKnobs& kn, uint32_t nseg, uint64_t nnz, uint32_t G, uint32_t elem_bytes,
                                 bool need_plain) {
     FlatLayoutOptions o;
+    kn.apply(o);
     o.tiles_per_span = p.tiles_per_span > 0 ? (uint32_t) p.tiles_per_span : 0;
     // 16 waves x 2 workgroups (64 KB of LDS each) = 32 resident waves per CU
     o.spans_per_wg = p.wg_waves > 0 ? (uint32_t) p.wg_waves : 16;
@@ -508,8 +508,7 @@ FlatLayoutOptions choose_layout(const mfx_params& p, uint32_t nseg, uint64_t nnz
     // 40/48/56/64/72 KB give 30.1/29.9/28.0/29.1/28.4 ms per outer iteration.
     // (round 2, 12-byte CSR slice entries, CSC / CSR pass per launch: 48 KB 199 / 230 us, 56 KB 183 / 191, 64 KB 187 / 231,
     // 71 KB 187 / 192 -- profiles/r02_exp_slice.txt)
-    uint32_t slice_kb = 56;
-    if (const char* e = std::getenv("MFX_SLICE_KB")) { const int v = std::atoi(e); if (v >= 8 && v <= 150) slice_kb = (uint32_t) v; }  // (A/B)
+    const uint32_t slice_kb = kn.slice_kb;  // (56 unless MFX_SLICE_KB says otherwise: A/B)
     uint32_t pr = p.panel_rows > 0 ? (uint32_t) p.panel_rows : (slice_kb * 1024u) / elem_bytes - 1;
     if (pr >= G) pr = G;  // the whole gathered vector fits: one panel
     const uint64_t npanels = (G + pr - 1) / pr;
@@ -518,10 +517,7 @@ FlatLayoutOptions choose_layout(const mfx_params& p, uint32_t nseg, uint64_t nnz
     // shape, CSR copy: 4777 / 4777 / 1123 columns -> 3 x 3559: 51 instead of 64 KB of LDS per workgroup): fused CSR pass 37.9 -> 26.5 us,
     // outer iteration at k = 40 2.78 -> 2.32 ms; ML-20M shape 5.07 -> 4.47 ms; 300 000 x 40 000 with 3e7 ratings 6.36 -> 5.67 ms;
     // Netflix shape 25.0 -> 24.9 ms (profiles/r04_exp_midsize.txt).  MFX_EQUAL_PANELS=0: full slices + remainder (A/B).
-    if (p.panel_rows == 0 && npanels > 1) {
-        const char* e = std::getenv("MFX_EQUAL_PANELS");
-        if (!(e && std::atoi(e) == 0)) pr = (uint32_t) ((G + npanels - 1) / npanels);
-    }
+    if (p.panel_rows == 0 && npanels > 1 && kn.equal_panels) pr = (uint32_t) ((G + npanels - 1) / npanels);
     const double mean_vseg = (double) nnz / ((double) npanels * (double) (nseg ? nseg : 1));
     // ... unless the matrix is small enough that the per-(panel, segment) bookkeeping stays cheap: up to 8 M virtual
     // segments the LDS panels still win (700 000 x 40 000 with 3e7 / 1.5e7 / 8e6 ratings, 7.1 / 3.6 / 1.9 entries per
@@ -623,6 +619,83 @@ void KernelProfiler::reset_totals() {
 #define PROF(id, call) PROFS(id, st_, call)
 
 // ------------------------------------------------------------------------------------------------
+// The schedules, one row each, indexed by CcdPlan::Schedule.  The as-written sequences book their residual passes where a fused
+// schedule books a rank's stored passes; their wave-per-segment kernels (kernel_variant 0) and the scatter layout's have ids of
+// their own (CcdSolver::sweep / resid).  A rank pair books its read-only passes as sweeps and its catch-up passes as the fused ones.
+using KP = KernelProfiler;
+static constexpr CcdPlan::Row kCcdSchedules[(int) CcdPlan::Schedule::Count] = {
+    {"as written", KP::K_RESID, KP::K_RESID, KP::K_SWEEP, false},
+    {"reference order, as written", KP::K_RESID, KP::K_RESID, KP::K_SWEEP_REF, false},
+    {"reference order, owner passes", KP::K_SWEEP_REF, KP::K_SWEEP_REF, KP::K_SWEEP_REF, false},
+    {"flat", KP::K_FCSC, KP::K_FCSR, KP::K_SWEEP, true},
+    {"flat, rank pairs", KP::K_FCSC, KP::K_FCSR, KP::K_SWEEP, true},
+    {"segment owners", KP::K_FCSC, KP::K_FCSR, KP::K_SWEEP, true},
+    {"scatter", KP::K_SCAT_V, KP::K_SCAT_U, KP::K_SCAT_SWEEP, true},
+};
+const CcdPlan::Row& CcdPlan::row() const { return kCcdSchedules[(int) schedule]; }
+
+void ccd_overlap_request(const CcdKnobs& kn, bool sharded, uint32_t* groups, uint32_t* reserve_cus) {
+    // (r4) sharded solve in the scatter layout: the column pass runs panel group by panel group, and group j's sums are
+    // combined, all-reduced and finalized on a second stream while group j + 1 is streamed -- only the last group's
+    // exchange stays exposed.  RCCL's kernels need CUs of their own for that: one block of rcclGenericKernel holds 19.7 KB
+    // of LDS and ~280 registers per lane, and neither fits next to a scatter workgroup (150 KB of LDS, 4 x 112 registers per
+    // SIMD lane), so the column pass leaves `reserve` CUs free.  MFX_OVERLAP_GROUPS (1 = off) / MFX_COMM_RESERVE_CUS.
+    // Off by default: two groups cost ~60-85 us per rank-one update on one GPU; whether the half of the
+    // all-reduce they hide is longer than that can only be measured on more than one GPU -- bench.py's config5_strong leg
+    // does, with 1 and with 2 groups, and keeps the better.
+    *groups = 1; *reserve_cus = 0;
+    if (!sharded) return;
+    *groups = (uint32_t) std::max(1, std::min(kn.overlap_groups, (int) SegStreamDev::kMaxScatterGroups));
+    const int reserve = kn.comm_reserve_cus < 0 ? (*groups > 1 ? 16 : 0) : kn.comm_reserve_cus;
+    *reserve_cus = *groups > 1 ? (uint32_t) reserve : 0u;
+}
+
+CcdPlan ccd_plan_choose(const mfx_params& p, const CcdKnobs& kn, bool sharded, uint32_t groups, uint32_t reserve_cus,
+                        const SegStreamDev& csc, const SegStreamDev& csr) {
+    using S = CcdPlan::Schedule;
+    CcdPlan pl;
+    pl.scatter = csc.scatter;  // (both stores or neither: build_stores)
+    pl.fuse_finalize = kn.fuse_finalize != 0;  // opt-in: see CcdSolver::use_fused
+    pl.ext_on = p.do_nmf != 0 || p.eps > 0.f || p.rank_trace != 0;  // opt-in extensions
+    pl.overlap_groups = pl.scatter ? std::min(groups, csr.scat_ngroups) : 1u;
+    pl.comm_reserve_cus = reserve_cus;
+    pl.ref_sweep_dpp = kn.ref_sweep_dpp;
+    const bool plain_fused = p.schedule == 1 && p.kernel_variant == 1 && !pl.scatter && !sharded;  // what the owner passes and the pairs both ask
+    // (r4) small matrices (plain layout on both sides, single GPU, no extensions): segment-owner fused passes
+    // ... as long as there are few enough segments: one wavefront per segment means (rows + columns) waves per rank, and a wave
+    // of a 20-entry row fills 8 % of its lanes.  Measured under graph replay (profiles/r04_exp_small.txt, owner vs flat, ms per
+    // outer iteration): 6040 x 3706 0.54 / 0.79, 20 000 x 8 000 0.89 / 1.04, 30 000 x 10 000 (3.9 M ratings) 1.38 / 1.87 -- but
+    // 70 000 x 2 000 2.00 / 1.79, 2 000 x 70 000 1.95 / 1.77, 200 000 x 100 000 2.07 / 1.17.  MFX_OWNER_PASSES=1 forces, 0 forbids.
+    // ... and no segment so long that its one owner becomes the whole pass (a 256-thread workgroup walks 2048 entries per round)
+    const bool few_segments = std::max(csr.nseg, csc.nseg) <= 40000u && std::max(csc.own_max_len, csr.own_max_len) <= 65536u;
+    const bool owner = kn.owner_passes != 0 && (few_segments || kn.owner_passes == 1) && plain_fused && csc.own_short && csr.own_short && !pl.ext_on;
+    // deferred residual writes (rank_pair): the plain fused schedule on LDS panels, one inner iteration, nothing opt-in.
+    // MFX_DEFER_RESID=0 keeps one stored pass per copy and rank (A/B).
+    auto fits = [](const SegStreamDev& v, size_t entry) {  // the catch-up pass's slice + float4 operand window in one CU's LDS
+        return ((size_t) v.panel_rows + 1) * entry + 15 + 1024 * sizeof(float4) <= 160 * 1024;
+    };
+    const bool pairs = kn.defer_resid && plain_fused && p.maxinneriter == 1 && !pl.fuse_finalize && !pl.ext_on && csc.lds_panels && csr.lds_panels &&
+                       fits(csc, sizeof(float4)) && fits(csr, sizeof(float4) + sizeof(float)) && p.k >= 2;
+    if (p.schedule == 0) pl.schedule = p.kernel_variant != -1 ? S::AsWritten : kn.ref_fused ? S::RefOwner : S::RefAsWritten;
+    else pl.schedule = pl.scatter ? S::Scatter : owner ? S::Owner : pairs ? S::FlatPairs : S::Flat;
+    // schedule 0 keeps its launch events on (its rank / update split is derived from them) -- but the owner passes have no
+    // sweep / update split to report: launch events only when profiling is asked for
+    pl.books_split = p.schedule == 0;
+    pl.events_forced = pl.as_written();
+    pl.flush_primes_packs = pl.schedule != S::RefAsWritten;  // (the operand packs belong to the fused schedules)
+    // persistent flat passes (k_flat's PERSIST form): resident workgroups walk contiguous chunk ranges, so a panel's slice is
+    // staged once per workgroup and panel instead of once per chunk.  On for all four passes of rank_pair: the catch-up passes,
+    // whose slices fill a CU's LDS (one workgroup per CU, two windows), and the read-only passes (two per CU at 64 VGPRs, one
+    // window; DESIGN.md sections 4 and 10.0).  MFX_FLAT_PERSIST=0: one chunk per workgroup as before (A/B, the tests' reference); a value
+    // above 1 is a bit mask over FlatMode (A/B per pass: 0x30 the read-only passes, 0xC0 the catch-up passes).  MFX_FLAT_WGS pins the workgroup count of every persistent pass (tests).
+    uint32_t modes = (1u << FM_FCSC_RO) | (1u << FM_FCSR_RO) | (1u << FM_FCSC2) | (1u << FM_FCSR2);
+    if (kn.flat_persist == 0) modes = 0; else if (kn.flat_persist > 1) modes &= (uint32_t) kn.flat_persist;
+    pl.persist_modes = pl.schedule == S::FlatPairs ? modes : 0u;
+    pl.persist_wgs = kn.flat_wgs;
+    return pl;
+}
+
+// ------------------------------------------------------------------------------------------------
 int CcdSolver::create(CcdSolver** out, const mfx_csx* R, const mfx_coo* T, const mfx_params* p,
                       mfx_memspace space, const mfx_shard* shard) {
     MFX_REQUIRE(out && R && p, "mfx_ccd_create: null argument");
@@ -648,12 +721,12 @@ CcdSolver::~CcdSolver() {
         (void) hipStreamSynchronize(st2_);
         (void) hipStreamDestroy(st2_);
     }
-    if (ref_streams_.side) {
-        (void) hipStreamSynchronize(ref_streams_.side);
-        (void) hipStreamDestroy(ref_streams_.side);
+    if (ref_ctx_.side) {
+        (void) hipStreamSynchronize(ref_ctx_.side);
+        (void) hipStreamDestroy(ref_ctx_.side);
     }
-    if (ref_streams_.fork) (void) hipEventDestroy(ref_streams_.fork);
-    if (ref_streams_.join) (void) hipEventDestroy(ref_streams_.join);
+    if (ref_ctx_.fork) (void) hipEventDestroy(ref_ctx_.fork);
+    if (ref_ctx_.join) (void) hipEventDestroy(ref_ctx_.join);
     if (st_) {
         (void) hipStreamSynchronize(st_);
         (void) hipStreamDestroy(st_);
@@ -676,45 +749,33 @@ int CcdSolver::init(const mfx_csx* R, const mfx_coo* T, const mfx_params* p, mfx
     MFX_HIP(hipStreamCreateWithFlags(&st_, hipStreamNonBlocking));
     for (hipEvent_t& e : ev_) MFX_HIP(hipEventCreate(&e));
     m_ = (uint32_t) R->rows; n_ = (uint32_t) R->cols; k_ = p->k; nnz_ = (uint64_t) R->nnz;
-    prof_.enable(p->profile != 0 || p->schedule == 0);
-    if (const char* e = std::getenv("MFX_FUSE_FINALIZE")) fuse_finalize_ = std::atoi(e) != 0 ? 1 : 0;  // opt-in: see fuse_finalize_
+    const CcdKnobs kn = CcdKnobs::from_env();
+    const bool sharded = shard && shard->comm;
 
     // Layouts.  Hyper-sparse shapes (LDS-sized panels would leave < 8 entries per (panel, segment) pair on
     // either side, so that side would fall back to L2 "cache panels") take the scatter layout on BOTH sides
     // (ccd_scatter.hip); kernel_variant = 2 forces it, panel_rows != 0 or kernel_variant = 0 rule it out.
     MFX_REQUIRE(p->kernel_variant >= -1 && p->kernel_variant <= 3, "kernel_variant must be -1 ... 3");
     MFX_REQUIRE(p->kernel_variant != -1 || p->schedule == 0, "kernel_variant = -1 (reference-order sweeps) goes with schedule = 0");
-    MFX_REQUIRE(p->kernel_variant != -1 || !(shard && shard->comm), "kernel_variant = -1 is a single-GPU parity mode (a sharded sum has no reference order)");
-    ref_order_ = p->kernel_variant == -1;
+    MFX_REQUIRE(p->kernel_variant != -1 || !sharded, "kernel_variant = -1 is a single-GPU parity mode (a sharded sum has no reference order)");
     const bool need_plain = p->schedule == 0 && p->kernel_variant <= 0;
     bool want_scatter = p->kernel_variant == 2 || p->kernel_variant == 3;  // 3: scatter with explicit 32-bit ids
     if (!want_scatter && !need_plain && p->panel_rows == 0 && p->layout_build != 1) {
-        const FlatLayoutOptions a = choose_layout(*p, m_, nnz_, n_, kCsrSliceBytes, false), b = choose_layout(*p, n_, nnz_, m_, sizeof(float2), false);
+        const FlatLayoutOptions a = choose_layout(*p, kn, m_, nnz_, n_, kCsrSliceBytes, false), b = choose_layout(*p, kn, n_, nnz_, m_, sizeof(float2), false);
         want_scatter = (a.panel_rows && !a.lds) || (b.panel_rows && !b.lds);
     }
-    // (r4) sharded solve in the scatter layout: the column pass runs panel group by panel group, and group j's sums are
-    // combined, all-reduced and finalized on a second stream while group j + 1 is streamed -- only the last group's
-    // exchange stays exposed.  RCCL's kernels need CUs of their own for that: one block of rcclGenericKernel holds 19.7 KB
-    // of LDS and ~280 registers per lane, and neither fits next to a scatter workgroup (150 KB of LDS, 4 x 112 registers per
-    // SIMD lane), so the column pass leaves `reserve` CUs free.  MFX_OVERLAP_GROUPS (1 = off) / MFX_COMM_RESERVE_CUS.
-    if (shard && shard->comm) {
-        // Off by default: two groups cost ~60-85 us per rank-one update on one GPU; whether the half of the
-        // all-reduce they hide is longer than that can only be measured on more than one GPU -- bench.py's config5_strong leg
-        // does, with 1 and with 2 groups, and keeps the better.
-        int groups = 1, reserve = -1;
-        if (const char* e = std::getenv("MFX_OVERLAP_GROUPS")) groups = std::atoi(e);
-        if (const char* e = std::getenv("MFX_COMM_RESERVE_CUS")) reserve = std::atoi(e);
-        overlap_groups_ = (uint32_t) std::max(1, std::min(groups, (int) SegStreamDev::kMaxScatterGroups));
-        if (reserve < 0) reserve = overlap_groups_ > 1 ? 16 : 0;
-        comm_reserve_cus_ = overlap_groups_ > 1 ? (uint32_t) reserve : 0u;
-    }
-    int rc = build_stores(R, p, space, want_scatter);
+    uint32_t groups, reserve_cus;
+    ccd_overlap_request(kn, sharded, &groups, &reserve_cus);
+    int rc = build_stores(R, p, kn, space, want_scatter, groups, reserve_cus);
     if (rc != MFX_OK && want_scatter && p->kernel_variant != 2 && p->kernel_variant != 3) {  // e.g. unsorted indices: the ordinary layouts take anything
         csr_ = SegStreamStore(); csc_ = SegStreamStore();
-        rc = build_stores(R, p, space, false);
+        rc = build_stores(R, p, kn, space, false, groups, reserve_cus);
     }
     MFX_TRY(rc);
-    if (scatter_) {  // bound of a fixed-point sum: the fullest local index of each store = the OTHER store's longest segment
+    plan_ = ccd_plan_choose(*p, kn, sharded, groups, reserve_cus, csc_.view, csr_.view);
+    if (kn.setup_timing) fprintf(stderr, "[mfx setup] schedule: %s\n", plan_.row().name);
+    prof_.enable(p->profile != 0 || plan_.events_forced);
+    if (plan_.scatter) {  // bound of a fixed-point sum: the fullest local index of each store = the OTHER store's longest segment
         for (int side = 0; side < 2; ++side) {
             SegStreamStore& other = side == 0 ? csc_ : csr_;
             std::vector<uint32_t> cnt(other.view.nseg);
@@ -724,45 +785,31 @@ int CcdSolver::init(const mfx_csx* R, const mfx_coo* T, const mfx_params* p, mfx
             (side == 0 ? csr_ : csc_).view.scat_max_local_cnt = mx;  // csr_'s local dimension is the columns
         }
     }
-    {   // (r4) small matrices (plain layout on both sides, single GPU, no extensions): segment-owner fused passes
-        const char* e = std::getenv("MFX_OWNER_PASSES");
-        // ... as long as there are few enough segments: one wavefront per segment means (rows + columns) waves per rank, and a wave
-        // of a 20-entry row fills 8 % of its lanes.  Measured under graph replay (profiles/r04_exp_small.txt, owner vs flat, ms per
-        // outer iteration): 6040 x 3706 0.54 / 0.79, 20 000 x 8 000 0.89 / 1.04, 30 000 x 10 000 (3.9 M ratings) 1.38 / 1.87 -- but
-        // 70 000 x 2 000 2.00 / 1.79, 2 000 x 70 000 1.95 / 1.77, 200 000 x 100 000 2.07 / 1.17.  MFX_OWNER_PASSES=1 forces, 0 forbids.
-        // ... and no segment so long that its one owner becomes the whole pass (a 256-thread workgroup walks 2048 entries per round)
-        const bool few_segments = std::max(m_, n_) <= 40000u && std::max(csc_.view.own_max_len, csr_.view.own_max_len) <= 65536u;
-        owner_mode_ = !(e && std::atoi(e) == 0) && (few_segments || (e && std::atoi(e) == 1)) && p->schedule == 1 && p->kernel_variant == 1 && !scatter_ &&
-                      !(shard && shard->comm) && csc_.view.own_short && csr_.view.own_short && !(p->do_nmf || p->eps > 0.f || p->rank_trace);
-    }
-    if (!scatter_) overlap_groups_ = 1;
-    overlap_groups_ = std::min(overlap_groups_, csr_.view.scat_ngroups);
-    if (overlap_groups_ > 1) {
+    // what the chosen schedule needs, in the order it was always allocated
+    if (plan_.overlap_groups > 1) {
         MFX_HIP(hipStreamCreateWithFlags(&st2_, hipStreamNonBlocking));
-        for (uint32_t g = 0; g < overlap_groups_; ++g) MFX_HIP(hipEventCreateWithFlags(&ev_grp_[g], hipEventDisableTiming));
+        for (uint32_t g = 0; g < plan_.overlap_groups; ++g) MFX_HIP(hipEventCreateWithFlags(&ev_grp_[g], hipEventDisableTiming));
         MFX_HIP(hipEventCreateWithFlags(&ev_join_, hipEventDisableTiming));
     }
-    if (ref_order_) {  // dispatch order of the reference-order sweeps: longest segment first (ccd_reforder.hip)
-        const char* e = std::getenv("MFX_REF_FUSED");
-        ref_fused_ = !(e && std::atoi(e) == 0);
+    const bool ref_owner = plan_.schedule == CcdPlan::Schedule::RefOwner;
+    if (ref_owner || plan_.schedule == CcdPlan::Schedule::RefAsWritten) {  // dispatch order of the reference-order sweeps: longest segment first (ccd_reforder.hip)
         for (int side = 0; side < 2; ++side) {
             const SegStreamDev& v = side == 0 ? csc_.view : csr_.view;
             std::vector<uint32_t> ptr_h((size_t) v.nseg + 1), order;
             MFX_HIP(hipMemcpyAsync(ptr_h.data(), v.ptr, sizeof(uint32_t) * ptr_h.size(), hipMemcpyDeviceToHost, st_));
             MFX_HIP(hipStreamSynchronize(st_));
-            (side == 0 ? ref_nlong_csc_ : ref_nlong_csr_) = ref_sweep_order(ptr_h.data(), v.nseg, &order, ref_fused_);
+            (side == 0 ? ref_nlong_csc_ : ref_nlong_csr_) = ref_sweep_order(ptr_h.data(), v.nseg, &order, ref_owner, kn.ref_long);
             DevBuf<uint32_t>& dst = side == 0 ? ref_order_csc_ : ref_order_csr_;
             MFX_TRY(dst.alloc(order.size()));
             MFX_TRY(dst.upload(order.data(), order.size(), MFX_HOST, st_));
             MFX_HIP(hipStreamSynchronize(st_));
         }
-        if (ref_fused_) {
-            // (the owner passes have no sweep / update split to report: launch events only when profiling is asked for)
-            prof_.enable(p->profile != 0);
-            ref_streams_.main = st_;
-            MFX_HIP(hipStreamCreateWithFlags(&ref_streams_.side, hipStreamNonBlocking));
-            MFX_HIP(hipEventCreateWithFlags(&ref_streams_.fork, hipEventDisableTiming));
-            MFX_HIP(hipEventCreateWithFlags(&ref_streams_.join, hipEventDisableTiming));
+        if (ref_owner) {
+            kn.apply(ref_ctx_);
+            ref_ctx_.main = st_;
+            MFX_HIP(hipStreamCreateWithFlags(&ref_ctx_.side, hipStreamNonBlocking));
+            MFX_HIP(hipEventCreateWithFlags(&ref_ctx_.fork, hipEventDisableTiming));
+            MFX_HIP(hipEventCreateWithFlags(&ref_ctx_.join, hipEventDisableTiming));
             MFX_TRY(ref_zero_cols_.alloc_zero(n_, st_));
         }
     }
@@ -775,7 +822,7 @@ int CcdSolver::init(const mfx_csx* R, const mfx_coo* T, const mfx_params* p, mfx
     MFX_TRY(gh_cols_.alloc_zero((size_t) 2 * n_, st_));
     MFX_TRY(gh_rows_.alloc_zero((size_t) 2 * m_, st_));
 
-    if (shard && shard->comm) {
+    if (sharded) {
         MFX_REQUIRE(shard->global_col_nnz, "sharded solve needs global_col_nnz");
         comm_ = shard->comm;
         MFX_TRY(global_col_nnz_.alloc(n_));
@@ -798,9 +845,8 @@ int CcdSolver::init(const mfx_csx* R, const mfx_coo* T, const mfx_params* p, mfx
     MFX_TRY(rmse_partials_.alloc_zero(kRmseBlocks, st_));
     // opt-in extensions
     MFX_REQUIRE(p->eps >= 0.f && p->eps < 1.f, "eps must be in [0, 1)");
-    ext_on_ = p->do_nmf != 0 || p->eps > 0.f || p->rank_trace != 0;
     if (p->eps > 0.f || p->rank_trace) MFX_REQUIRE(!comm_, "eps / rank_trace are not available in a sharded solve");
-    MFX_REQUIRE(!ref_order_ || !(p->do_nmf || p->eps > 0.f), "do_nmf / eps are not available with kernel_variant = -1");
+    MFX_REQUIRE(p->kernel_variant != -1 || !(p->do_nmf || p->eps > 0.f), "do_nmf / eps are not available with kernel_variant = -1");
     if (p->eps > 0.f) {
         MFX_TRY(fundec_seg_.alloc_zero(std::max(m_, n_), st_));
         MFX_TRY(fundec_sum_.alloc_zero(1, st_));
@@ -812,33 +858,15 @@ int CcdSolver::init(const mfx_csx* R, const mfx_coo* T, const mfx_params* p, mfx
         MFX_TRY(r1_sum_.alloc_zero(1, st_));
         for (hipEvent_t& e : ev_rank_) MFX_HIP(hipEventCreate(&e));
     }
-    {   // deferred residual writes (rank_pair): the plain fused schedule on LDS panels, one inner iteration, nothing opt-in.
-        // MFX_DEFER_RESID=0 keeps one stored pass per copy and rank (A/B).
-        const char* e = std::getenv("MFX_DEFER_RESID");
-        auto fits = [](const SegStreamDev& v, size_t entry) {  // the catch-up pass's slice + float4 operand window in one CU's LDS
-            return ((size_t) v.panel_rows + 1) * entry + 15 + 1024 * sizeof(float4) <= 160 * 1024;
-        };
-        defer_resid_ = !(e && std::atoi(e) == 0) && p->schedule == 1 && p->maxinneriter == 1 && p->kernel_variant == 1 && !scatter_ &&
-                       !owner_mode_ && !ref_order_ && !comm_ && fuse_finalize_ == 0 && !ext_on_ && csc_.view.lds_panels && csr_.view.lds_panels &&
-                       fits(csc_.view, sizeof(float4)) && fits(csr_.view, sizeof(float4) + sizeof(float)) && k_ >= 2;
-        if (defer_resid_) MFX_TRY(packD_.alloc_zero(m_, st_));
-    }
-    {   // persistent flat passes (k_flat's PERSIST form): resident workgroups walk contiguous chunk ranges, so a panel's slice is
-        // staged once per workgroup and panel instead of once per chunk.  On for all four passes of rank_pair: the catch-up passes,
-        // whose slices fill a CU's LDS (one workgroup per CU, two windows), and the read-only passes (two per CU at 64 VGPRs, one
-        // window; DESIGN.md sections 4 and 10.0).  MFX_FLAT_PERSIST=0: one chunk per workgroup as before (A/B, the tests' reference); a value
-        // above 1 is a bit mask over FlatMode (A/B per pass: 0x30 the read-only passes, 0xC0 the catch-up passes).  MFX_FLAT_WGS pins the workgroup count of every persistent pass (tests).
-        uint32_t modes = (1u << FM_FCSC_RO) | (1u << FM_FCSR_RO) | (1u << FM_FCSC2) | (1u << FM_FCSR2);
-        if (const char* e = std::getenv("MFX_FLAT_PERSIST")) { const long v = std::strtol(e, nullptr, 0); if (v == 0) modes = 0; else if (v > 1) modes &= (uint32_t) v; }
-        uint32_t wgs = 0;
-        if (const char* e = std::getenv("MFX_FLAT_WGS")) { const int v = std::atoi(e); if (v > 0) wgs = (uint32_t) v; }
+    if (plan_.schedule == CcdPlan::Schedule::FlatPairs) MFX_TRY(packD_.alloc_zero(m_, st_));
+    {   // persistent flat passes (ccd_plan_choose): the views carry the modes, the device's CU count and the workgroup pin
         int dev = 0, cus = 0;
         MFX_HIP(hipGetDevice(&dev));
         MFX_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
         for (SegStreamDev* v : {&csc_.view, &csr_.view}) {
-            v->flat_persist_modes = defer_resid_ && cus > 0 ? modes : 0u;
+            v->flat_persist_modes = cus > 0 ? plan_.persist_modes : 0u;
             v->flat_cus = cus > 0 ? (uint32_t) cus : 0u;
-            v->flat_persist_wgs = wgs;
+            v->flat_persist_wgs = plan_.persist_wgs;
         }
     }
     MFX_TRY(rmse_sum_.alloc_zero(1, st_));
@@ -848,20 +876,22 @@ int CcdSolver::init(const mfx_csx* R, const mfx_coo* T, const mfx_params* p, mfx
 
 // Both orientations, side by side (the serial stretches of one overlap the parallel passes / transfers of
 // the other).  Error text is thread-local, so it is carried across.
-int CcdSolver::build_stores(const mfx_csx* R, const mfx_params* p, mfx_memspace space, bool scatter) {
+int CcdSolver::build_stores(const mfx_csx* R, const mfx_params* p, const CcdKnobs& kn, mfx_memspace space, bool scatter, uint32_t overlap_groups,
+                            uint32_t reserve_cus) {
     const bool need_plain = p->schedule == 0 && p->kernel_variant <= 0;
     auto options = [&](uint32_t nseg, uint32_t G, uint32_t elem_bytes, bool is_csr) {
-        if (!scatter) return choose_layout(*p, nseg, nnz_, G, elem_bytes, need_plain);
+        if (!scatter) return choose_layout(*p, kn, nseg, nnz_, G, elem_bytes, need_plain);
         // scatter: 24 B of LDS per local index (operand pair + two 64-bit accumulators) and the whole 160 KB of a CU
         // for one workgroup: 6816 + 1 padding slot = 163 608 B.  Fewer, larger panels = fewer re-reads of the
         // streamed operand, which is what bounds the pass (6144 -> 6816: 10 % fewer line fills).
         constexpr uint32_t kScatterPanel = 6816;
         FlatLayoutOptions o;
+        kn.apply(o);
         o.scatter = true; o.lds = true; o.spans_per_wg = 16;
         o.scatter_ids32 = p->kernel_variant == 3;
         o.panel_rows = std::min<uint32_t>(p->panel_rows > 0 ? (uint32_t) p->panel_rows : kScatterPanel, std::max<uint32_t>(G, 1u));
         // the row-major store is the one the COLUMN pass streams: it alone is launched by panel groups / on fewer CUs
-        const uint32_t groups = is_csr ? overlap_groups_ : 1u;
+        const uint32_t groups = is_csr ? overlap_groups : 1u;
         o.scatter_groups = groups;
         // (r4) PHASE ALIGNMENT.  The persistent workgroups own equal, contiguous ranges of the panel-major stream, and inside
         // a panel the streamed operand is read in ascending order: workgroup w starts at phase frac(w * P / nwg) of "its"
@@ -876,12 +906,11 @@ int CcdSolver::build_stores(const mfx_csx* R, const mfx_params* p, mfx_memspace 
         // range is kept, so a skewed matrix only blurs the windows.  With panel groups every LAUNCH is aligned on its own:
         // the panels of a group against the workgroups of its launch.  MFX_SCATTER_PANEL_MULT=0: round 3's panel count.
         int dev = 0, cus = 0;
-        const char* mult_env = std::getenv("MFX_SCATTER_PANEL_MULT");
-        const bool align = !(mult_env && std::atoi(mult_env) == 0);
+        const bool align = kn.scatter_panel_mult;
         if (p->panel_rows == 0 && hipGetDevice(&dev) == hipSuccess &&
             hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus >= 16) {
             uint32_t nwg = (uint32_t) cus;
-            if (is_csr && comm_reserve_cus_ > 0 && comm_reserve_cus_ + 8 <= nwg) { nwg = (nwg - comm_reserve_cus_) / 8 * 8; o.scatter_wgs = nwg; }
+            if (is_csr && reserve_cus > 0 && reserve_cus + 8 <= nwg) { nwg = (nwg - reserve_cus) / 8 * 8; o.scatter_wgs = nwg; }
             const uint32_t q = nwg / 8, p0 = (G + kScatterPanel - 1) / kScatterPanel;
             auto gcd = [](uint32_t a, uint32_t b) { while (b) { const uint32_t t = a % b; a = b; b = t; } return a; };
             uint32_t P = 0;
@@ -899,7 +928,6 @@ int CcdSolver::build_stores(const mfx_csx* R, const mfx_params* p, mfx_memspace 
         o.tiles_per_span = p->tiles_per_span > 0 ? (uint32_t) p->tiles_per_span : (nnz_ >= (32u << 20) ? 4u : 0u);
         return o;
     };
-    scatter_ = scatter;
     int rc_csr = MFX_OK;
     std::string err_csr;
     // (host allocations of several GB can fail: no exception may leave a thread or cross the C ABI;
@@ -1064,148 +1092,84 @@ int CcdSolver::rank_trace(int cap, double* rmse, double* seconds, int iters_cap,
     return (int) trace_done_.size();
 }
 
-int CcdSolver::rank_fused_scatter(uint32_t t) {
-    const uint32_t next = (t + 1) % k_;
-    // same invariant as rank_fused: packA = (u_prev_new | 0, W[t] old), packB = (v_prev_new | 0, H[t] old).
-    // v-update: stream the ROW-major copy; columns are local (slice packB, accumulators), rows stream (packA)
-    FinalizeArgs fv = fin_base();
-    fv.lambda = p_.lambda; fv.out_vec = Ht(t); fv.pack2 = packB_.get(); fv.next_vec = Ht(next); fv.pack4 = packC_.get();
-    fv.pack4_as3 = true;  // 12-byte triples: a quarter fewer line fills of the streamed operand in the u-pass
-    if (overlap_groups_ > 1) {
-        // panel group g: pass on st_; its combine -> all-reduce -> finalize on st2_, under the pass of group g + 1.  A group's
-        // finalize writes H[t], packB and the triples for ITS columns only; the launches still to come read packB for
-        // theirs.  st_ joins st2_ before the u-pass, which needs every column's new value.
-        for (uint32_t g = 0; g < overlap_groups_; ++g) {
-            PROF(KernelProfiler::K_SCAT_V, launch_scatter(SM_V, csr_.view, packB_.get(), packA_.get(), 0, st_, (int) g));
-            MFX_HIP(hipEventRecord(ev_grp_[g], st_));
-            MFX_HIP(hipStreamWaitEvent(st2_, ev_grp_[g], 0));
-            MFX_TRY(scatter_finalize(true, fv, (int) g, st2_));
+int CcdSolver::flat_pass(int id, bool cols, FlatMode mode, const void* gather, const void* perseg, const FinalizeArgs& f, const float* gather_aux) {
+    SegStreamStore& s = cols ? csc_ : csr_;
+    PROF(id, launch_flat(mode, s.view, gather, perseg, 0, st_, gather_aux));
+    if (cols) return finalize_cols(f);
+    PROF(KernelProfiler::K_FINALIZE, launch_finalize(s.view, f, st_));
+    return MFX_OK;
+}
+
+int CcdSolver::half_step(bool cols, FlatMode mode, const void* gather, const void* perseg, const FinalizeArgs& f) {
+    const CcdPlan::Row& row = plan_.row();
+    const int id = mode == FM_SWEEP ? row.sweep : cols ? row.pass_cols : row.pass_rows;
+    SegStreamStore& s = cols ? csc_ : csr_;
+    switch (plan_.schedule) {
+        case CcdPlan::Schedule::Flat:
+        case CcdPlan::Schedule::FlatPairs:
+            // With MFX_FUSE_FINALIZE=1 the finalize of each pass runs INSIDE the pass (fused_finalize, ccd_kernels.hip): on LDS
+            // panels not in the read-only sweep, and the column side of a sharded solve keeps the separate kernel -- its sums go
+            // through the all-reduce first.  Off by default: bit-identical, but measured SLOWER than pass + k_finalize (use_fused).
+            if (use_fused(s) && !(cols && comm_) && (mode != FM_SWEEP || s.view.panel_rows == 0)) {
+                PROF(id, launch_flat_fused(mode, s.view, gather, perseg, f, st_));
+                return MFX_OK;
+            }
+            return flat_pass(id, cols, mode, gather, perseg, f);
+        case CcdPlan::Schedule::Owner:  // (r4) small matrices: every segment has one owner, which finalizes it inside the pass (k_seg_owner)
+            PROF(id, launch_seg_owner(mode, s.view, gather, perseg, f, st_));
+            return MFX_OK;
+        case CcdPlan::Schedule::RefOwner:  // (r4) every sum in the reference's order, the element update the reference's own
+            PROF(id, launch_ref_owner(mode, s.view, (cols ? ref_order_csc_ : ref_order_csr_).get(), cols ? ref_nlong_csc_ : ref_nlong_csr_, gather, perseg, f, ref_ctx_));
+            return MFX_OK;
+        case CcdPlan::Schedule::Scatter: {
+            // sums over columns stream the ROW-major copy (columns are local: slice = perseg, accumulators; rows stream: gather),
+            // sums over rows the COLUMN-major copy
+            const SegStreamDev& src = (cols ? csr_ : csc_).view;
+            const ScatterMode sm = mode == FM_SWEEP ? SM_SWEEP : cols ? SM_V : SM_U;
+            if (cols && mode != FM_SWEEP && plan_.overlap_groups > 1) {
+                // panel group g: pass on st_; its combine -> all-reduce -> finalize on st2_, under the pass of group g + 1.  A group's
+                // finalize writes H[t], packB and the triples for ITS columns only; the launches still to come read packB for
+                // theirs.  st_ joins st2_ before the u-pass, which needs every column's new value.
+                for (uint32_t g = 0; g < plan_.overlap_groups; ++g) {
+                    PROF(id, launch_scatter(sm, src, perseg, gather, 0, st_, (int) g));
+                    MFX_HIP(hipEventRecord(ev_grp_[g], st_));
+                    MFX_HIP(hipStreamWaitEvent(st2_, ev_grp_[g], 0));
+                    MFX_TRY(scatter_finalize(true, f, (int) g, st2_));
+                }
+                MFX_HIP(hipEventRecord(ev_join_, st2_));
+                MFX_HIP(hipStreamWaitEvent(st_, ev_join_, 0));
+                return MFX_OK;
+            }
+            PROF(id, launch_scatter(sm, src, perseg, gather, 0, st_));
+            return scatter_finalize(cols, f);
         }
-        MFX_HIP(hipEventRecord(ev_join_, st2_));
-        MFX_HIP(hipStreamWaitEvent(st_, ev_join_, 0));
-    } else {
-        PROF(KernelProfiler::K_SCAT_V, launch_scatter(SM_V, csr_.view, packB_.get(), packA_.get(), 0, st_));
-        MFX_TRY(scatter_finalize(true, fv));
+        default:
+            return fail(MFX_ERR_INVALID, "half_step: the %s schedule has no fused half-step", row.name);
     }
-    // u-update: stream the COLUMN-major copy; rows are local (slice packA), columns stream (packC, triples)
-    PROF(KernelProfiler::K_SCAT_U, launch_scatter(SM_U, csc_.view, packA_.get(), packC_.get(), 0, st_));
-    FinalizeArgs fu = fin_base();
-    fu.lambda = p_.lambda; fu.out_vec = Wt(t); fu.pack2 = packA_.get(); fu.next_vec = Wt(next);
-    MFX_TRY(scatter_finalize(false, fu));
-    bool stop = false;
-    MFX_TRY(inner_stop(t, 1, &stop));
-    for (int it = 2; it <= p_.maxinneriter && !stop; ++it) {  // remaining inner iterations: read-only sweeps
-        MFX_TRY(sweep(csc_, Wt(t), Ht(t), true));
-        MFX_TRY(sweep(csr_, Ht(t), Wt(t), false));
-        MFX_TRY(inner_stop(t, it, &stop));
-    }
-    if (p_.maxinneriter > 1) {
-        PROF(KernelProfiler::K_PACK, launch_pack2(m_, Wt(t), Wt(next), packA_.get(), st_));
-        PROF(KernelProfiler::K_PACK, launch_pack2(n_, Ht(t), Ht(next), packB_.get(), st_));
-    }
-    pending_sub_ = (int32_t) t;
-    return MFX_OK;
 }
 
-// (r4) Small matrices: two launches per rank -- every segment has one owner, which finalizes it inside the pass (k_seg_owner).
-int CcdSolver::rank_fused_owner(uint32_t t) {
-    const uint32_t next = (t + 1) % k_;
-    // same invariant as rank_fused: packA = (u_prev_new | 0, W[t] old), packB = (v_prev_new | 0, H[t] old)
-    FinalizeArgs fv = fin_base();
-    fv.lambda = p_.lambda; fv.out_vec = Ht(t); fv.pack2 = packB_.get(); fv.next_vec = Ht(next); fv.pack4 = packC_.get();
-    PROF(KernelProfiler::K_FCSC, launch_seg_owner(FM_FCSC, csc_.view, packA_.get(), packB_.get(), fv, st_));
-    FinalizeArgs fu = fin_base();
-    fu.lambda = p_.lambda; fu.out_vec = Wt(t); fu.pack2 = packA_.get(); fu.next_vec = Wt(next);
-    PROF(KernelProfiler::K_FCSR, launch_seg_owner(FM_FCSR, csr_.view, packC_.get(), packA_.get(), fu, st_));
-    for (int it = 2; it <= p_.maxinneriter; ++it) {  // remaining inner iterations: read-only sweeps, finalized by their owners too
-        FinalizeArgs f2 = fin_base(); f2.out_vec = Ht(t);
-        PROF(KernelProfiler::K_SWEEP, launch_seg_owner(FM_SWEEP, csc_.view, Wt(t), nullptr, f2, st_));
-        FinalizeArgs f3 = fin_base(); f3.out_vec = Wt(t);
-        PROF(KernelProfiler::K_SWEEP, launch_seg_owner(FM_SWEEP, csr_.view, Ht(t), nullptr, f3, st_));
-    }
-    if (p_.maxinneriter > 1) {  // the packs must carry the FINAL (u_t, v_t)
-        PROF(KernelProfiler::K_PACK, launch_pack2(m_, Wt(t), Wt(next), packA_.get(), st_));
-        PROF(KernelProfiler::K_PACK, launch_pack2(n_, Ht(t), Ht(next), packB_.get(), st_));
-    }
-    pending_sub_ = (int32_t) t;
-    return MFX_OK;
-}
-
-// (r4) Reference-order mode on the schedule of rank_fused_owner: every sum in the reference's order (launch_ref_owner), the
-// element update the reference's own -- two launches per rank, no separate residual pass; bit for bit the as-written sequence.
-int CcdSolver::rank_ref_fused(uint32_t t, bool add_back) {
-    const uint32_t next = (t + 1) % k_;
-    // invariant on entry, as in rank_fused: packA = (u_prev_new | 0, W[t] old), packB = (v_prev_new | 0, H[t] old)
-    if (!add_back)  // first outer iteration: the reference does not add rank t back (src/CCD.cpp:100-104; H starts at 0, so the term
-                    // is u * 0 anyway) -- the column side's add-back operand reads 0 whatever H holds
-        PROF(KernelProfiler::K_PACK, launch_pack2(n_, pending_sub_ >= 0 ? Ht((uint32_t) pending_sub_) : nullptr, ref_zero_cols_.get(), packB_.get(), st_));
-    FinalizeArgs fv = fin_base();
-    fv.lambda = p_.lambda; fv.out_vec = Ht(t); fv.pack2 = packB_.get(); fv.next_vec = Ht(next); fv.pack4 = packC_.get();
-    PROF(KernelProfiler::K_SWEEP_REF, launch_ref_owner(FM_FCSC, csc_.view, ref_order_csc_.get(), ref_nlong_csc_, packA_.get(), packB_.get(), fv, ref_streams_));
-    FinalizeArgs fu = fin_base();
-    fu.lambda = p_.lambda; fu.out_vec = Wt(t); fu.pack2 = packA_.get(); fu.next_vec = Wt(next);
-    PROF(KernelProfiler::K_SWEEP_REF, launch_ref_owner(FM_FCSR, csr_.view, ref_order_csr_.get(), ref_nlong_csr_, packC_.get(), packA_.get(), fu, ref_streams_));
-    bool stop = false;
-    MFX_TRY(inner_stop(t, 1, &stop));
-    for (int it = 2; it <= p_.maxinneriter && !stop; ++it) {  // remaining inner iterations: read-only sweeps
-        FinalizeArgs f2 = fin_base(); f2.out_vec = Ht(t);
-        PROF(KernelProfiler::K_SWEEP_REF, launch_ref_owner(FM_SWEEP, csc_.view, ref_order_csc_.get(), ref_nlong_csc_, Wt(t), nullptr, f2, ref_streams_));
-        FinalizeArgs f3 = fin_base(); f3.out_vec = Wt(t);
-        PROF(KernelProfiler::K_SWEEP_REF, launch_ref_owner(FM_SWEEP, csr_.view, ref_order_csr_.get(), ref_nlong_csr_, Ht(t), nullptr, f3, ref_streams_));
-        MFX_TRY(inner_stop(t, it, &stop));
-    }
-    if (p_.maxinneriter > 1) {  // the packs must carry the FINAL (u_t, v_t)
-        PROF(KernelProfiler::K_PACK, launch_pack2(m_, Wt(t), Wt(next), packA_.get(), st_));
-        PROF(KernelProfiler::K_PACK, launch_pack2(n_, Ht(t), Ht(next), packB_.get(), st_));
-    }
-    pending_sub_ = (int32_t) t;
-    return MFX_OK;
-}
-
-int CcdSolver::rank_fused(uint32_t t) {
-    if (scatter_) return rank_fused_scatter(t);
-    if (owner_mode_) return rank_fused_owner(t);
+int CcdSolver::rank_fused(uint32_t t, bool add_back) {
     const uint32_t next = (t + 1) % k_;
     // invariant on entry: packA = (u_prev_new | 0, W[t] old), packB = (v_prev_new | 0, H[t] old)
-    // With MFX_FUSE_FINALIZE=1 the finalize of each pass runs INSIDE the pass (fused_finalize, ccd_kernels.hip);
-    // the column side of a sharded solve keeps the separate kernel: its sums go through the all-reduce first.
-    // Off by default: bit-identical, but measured SLOWER than pass + k_finalize (see the comment there).
+    if (plan_.schedule == CcdPlan::Schedule::RefOwner && !add_back)
+        // first outer iteration: the reference does not add rank t back (src/CCD.cpp:100-104; H starts at 0, so the term
+        // is u * 0 anyway) -- the column side's add-back operand reads 0 whatever H holds
+        PROF(KernelProfiler::K_PACK, launch_pack2(n_, pending_sub_ >= 0 ? Ht((uint32_t) pending_sub_) : nullptr, ref_zero_cols_.get(), packB_.get(), st_));
     FinalizeArgs fv = fin_base();
-    fv.lambda = p_.lambda; fv.out_vec = Ht(t); fv.pack2 = packB_.get(); fv.next_vec = Ht(next);
-    fv.pack4 = packC_.get();
-    if (use_fused(csc_) && !comm_) {
-        PROF(KernelProfiler::K_FCSC, launch_flat_fused(FM_FCSC, csc_.view, packA_.get(), packB_.get(), fv, st_));
-    } else {
-        PROF(KernelProfiler::K_FCSC, launch_flat(FM_FCSC, csc_.view, packA_.get(), packB_.get(), 0, st_));
-        MFX_TRY(finalize_cols(fv));
-    }
-    // per-row scalars of the CSR pass are exactly packA (u_prev_new, u_t_old), indexed by row
+    fv.out_vec = Ht(t); fv.pack2 = packB_.get(); fv.next_vec = Ht(next); fv.pack4 = packC_.get();
+    fv.pack4_as3 = plan_.schedule == CcdPlan::Schedule::Scatter;  // 12-byte triples: a quarter fewer line fills of the streamed operand in the u-pass
+    MFX_TRY(half_step(true, FM_FCSC, packA_.get(), packB_.get(), fv));
+    // per-row scalars of the row pass are exactly packA (u_prev_new, u_t_old), indexed by row
     FinalizeArgs fu = fin_base();
-    fu.lambda = p_.lambda; fu.out_vec = Wt(t); fu.pack2 = packA_.get(); fu.next_vec = Wt(next);
-    if (use_fused(csr_)) {
-        PROF(KernelProfiler::K_FCSR, launch_flat_fused(FM_FCSR, csr_.view, packC_.get(), packA_.get(), fu, st_));
-    } else {
-        PROF(KernelProfiler::K_FCSR, launch_flat(FM_FCSR, csr_.view, packC_.get(), packA_.get(), 0, st_));
-        PROF(KernelProfiler::K_FINALIZE, launch_finalize(csr_.view, fu, st_));
-    }
-
+    fu.out_vec = Wt(t); fu.pack2 = packA_.get(); fu.next_vec = Wt(next);
+    MFX_TRY(half_step(false, FM_FCSR, packC_.get(), packA_.get(), fu));
     bool stop = false;
     MFX_TRY(inner_stop(t, 1, &stop));
     for (int it = 2; it <= p_.maxinneriter && !stop; ++it) {  // remaining inner iterations: read-only sweeps
         FinalizeArgs f2 = fin_base(); f2.out_vec = Ht(t);
-        if (use_fused(csc_) && !comm_ && csc_.view.panel_rows == 0) {
-            PROF(KernelProfiler::K_SWEEP, launch_flat_fused(FM_SWEEP, csc_.view, Wt(t), nullptr, f2, st_));
-        } else {
-            PROF(KernelProfiler::K_SWEEP, launch_flat(FM_SWEEP, csc_.view, Wt(t), nullptr, 0, st_));
-            MFX_TRY(finalize_cols(f2));
-        }
+        MFX_TRY(half_step(true, FM_SWEEP, Wt(t), nullptr, f2));
         FinalizeArgs f3 = fin_base(); f3.out_vec = Wt(t);
-        if (use_fused(csr_) && csr_.view.panel_rows == 0) {
-            PROF(KernelProfiler::K_SWEEP, launch_flat_fused(FM_SWEEP, csr_.view, Ht(t), nullptr, f3, st_));
-        } else {
-            PROF(KernelProfiler::K_SWEEP, launch_flat(FM_SWEEP, csr_.view, Ht(t), nullptr, 0, st_));
-            PROF(KernelProfiler::K_FINALIZE, launch_finalize(csr_.view, f3, st_));
-        }
+        MFX_TRY(half_step(false, FM_SWEEP, Ht(t), nullptr, f3));
         MFX_TRY(inner_stop(t, it, &stop));
     }
     if (p_.maxinneriter > 1) {  // the packs must carry the FINAL (u_t, v_t)
@@ -1216,7 +1180,7 @@ int CcdSolver::rank_fused(uint32_t t) {
     return MFX_OK;
 }
 
-// Ranks t and t + 1 with ONE stored pass per copy (defer_resid_).  A fused pass applies one elementwise update to its copy
+// Ranks t and t + 1 with ONE stored pass per copy (FlatPairs).  A fused pass applies one elementwise update to its copy
 // and stores it; the stored value is only a cache of that fixed sequence of roundings.  So rank t streams both copies
 // read-only (FM_FCSC_RO / FM_FCSR_RO: today's sums, 6.25 instead of 10.25 bytes per rating), and rank t + 1's passes
 // (FM_FCSC2 / FM_FCSR2) start from the older stored value, redo rank t's update in registers with the same operands in the
@@ -1230,22 +1194,19 @@ int CcdSolver::rank_pair(uint32_t t) {
     // ---- rank t: read-only passes; the finalizes also leave the quads (packC: columns, packD_: rows) ----
     FinalizeArgs fv = fin_base();
     fv.out_vec = Ht(t); fv.pack2 = packB_.get(); fv.next_vec = Ht(t1); fv.quad = packC_.get();  // (its first three = the pack4 of rank_fused)
-    PROF(KernelProfiler::K_SWEEP, launch_flat(FM_FCSC_RO, csc_.view, packA_.get(), packB_.get(), 0, st_));
-    PROF(KernelProfiler::K_FINALIZE, launch_finalize(csc_.view, fv, st_));
+    const CcdPlan::Row& row = plan_.row();
+    MFX_TRY(flat_pass(row.sweep, true, FM_FCSC_RO, packA_.get(), packB_.get(), fv));
     FinalizeArgs fu = fin_base();
     fu.out_vec = Wt(t); fu.pack2 = packA_.get(); fu.next_vec = Wt(t1); fu.quad = packD_.get();
-    PROF(KernelProfiler::K_SWEEP, launch_flat(FM_FCSR_RO, csr_.view, packC_.get(), packA_.get(), 0, st_));
-    PROF(KernelProfiler::K_FINALIZE, launch_finalize(csr_.view, fu, st_));
+    MFX_TRY(flat_pass(row.sweep, false, FM_FCSR_RO, packC_.get(), packA_.get(), fu));
     // ---- rank t + 1: catch-up passes (rank t's update, then its own), stored ----
     // packA = (u_t, W[t+1] old), packB = (v_t, H[t+1] old); packC / packD_ = the quads of rank t
     FinalizeArgs fv1 = fin_base();
     fv1.out_vec = Ht(t1); fv1.pack2 = packB_.get(); fv1.next_vec = Ht(next1);  // (no pack4: packC stays the column quads)
-    PROF(KernelProfiler::K_FCSC, launch_flat(FM_FCSC2, csc_.view, packD_.get(), packC_.get(), 0, st_));
-    PROF(KernelProfiler::K_FINALIZE, launch_finalize(csc_.view, fv1, st_));
+    MFX_TRY(flat_pass(row.pass_cols, true, FM_FCSC2, packD_.get(), packC_.get(), fv1));
     FinalizeArgs fu1 = fin_base();
     fu1.out_vec = Wt(t1); fu1.pack2 = packA_.get(); fu1.next_vec = Wt(next1);
-    PROF(KernelProfiler::K_FCSR, launch_flat(FM_FCSR2, csr_.view, packC_.get(), packD_.get(), 0, st_, Ht(t1)));
-    PROF(KernelProfiler::K_FINALIZE, launch_finalize(csr_.view, fu1, st_));
+    MFX_TRY(flat_pass(row.pass_rows, false, FM_FCSR2, packC_.get(), packD_.get(), fu1, Ht(t1)));
     pending_sub_ = (int32_t) t1;
     return MFX_OK;
 }
@@ -1255,45 +1216,42 @@ int CcdSolver::flush_pending() {
     const uint32_t t = (uint32_t) pending_sub_, next = (t + 1) % k_;
     MFX_TRY(resid(csc_, Wt(t), Ht(t), 0));
     MFX_TRY(resid(csr_, Ht(t), Wt(t), 0));
-    if (ref_order_ && !ref_fused_) { pending_sub_ = -1; return MFX_OK; }  // (the operand packs below belong to the fused schedules)
-    PROF(KernelProfiler::K_PACK, launch_pack2(m_, nullptr, Wt(next), packA_.get(), st_));
-    PROF(KernelProfiler::K_PACK, launch_pack2(n_, nullptr, Ht(next), packB_.get(), st_));
+    if (plan_.flush_primes_packs) {
+        PROF(KernelProfiler::K_PACK, launch_pack2(m_, nullptr, Wt(next), packA_.get(), st_));
+        PROF(KernelProfiler::K_PACK, launch_pack2(n_, nullptr, Ht(next), packB_.get(), st_));
+    }
     pending_sub_ = -1;
     return MFX_OK;
 }
 
+// The read-only sweep and the residual pass of the as-written sequences (and of flush_pending), over whatever layout was built.
 int CcdSolver::sweep(SegStreamStore& s, const float* vec, float* out, bool is_col_side) {
     FinalizeArgs f = fin_base();
-    f.lambda = p_.lambda;
     f.out_vec = out;
-    if (scatter_) {  // sums over columns stream the row-major store (vec = u, by row), and vice versa
+    if (plan_.scatter) {  // sums over columns stream the row-major store (vec = u, by row), and vice versa
         SegStreamStore& src = is_col_side ? csr_ : csc_;
         PROF(KernelProfiler::K_SCAT_SWEEP, launch_scatter(SM_SWEEP, src.view, nullptr, vec, 0, st_));
         return scatter_finalize(is_col_side, f);
     }
-    if (ref_order_) {  // g, h and the division in one kernel, in the reference's order; no separate finalize
-        PROF(KernelProfiler::K_SWEEP_REF, launch_sweep_ref(s.view, (is_col_side ? ref_order_csc_ : ref_order_csr_).get(), is_col_side ? ref_nlong_csc_ : ref_nlong_csr_, vec, p_.lambda, out, st_));
+    if (plan_.schedule == CcdPlan::Schedule::RefAsWritten) {  // g, h and the division in one kernel, in the reference's order; no separate finalize
+        PROF(plan_.row().sweep, launch_sweep_ref(s.view, (is_col_side ? ref_order_csc_ : ref_order_csr_).get(), is_col_side ? ref_nlong_csc_ : ref_nlong_csr_, vec,
+                                                 p_.lambda, out, st_, plan_.ref_sweep_dpp));
         return MFX_OK;
     }
-    if (p_.kernel_variant == 0) {
-        float* gh = is_col_side ? gh_cols_.get() : gh_rows_.get();
-        PROF(KernelProfiler::K_SWEEP_WAVE, launch_sweep_wave(s.view, vec, gh, gh + s.view.nseg, st_));
-        f.gh_dense = gh;
-        if (is_col_side && comm_) {
-            PROF(KernelProfiler::K_ALLREDUCE, comm_allreduce_f32(comm_, gh, (size_t) 2 * n_, st_));
-            f.cnt_override = global_col_nnz_.get();
-        }
-        PROF(KernelProfiler::K_FINALIZE, launch_finalize(s.view, f, st_));
-    } else {
-        PROF(KernelProfiler::K_SWEEP, launch_flat(FM_SWEEP, s.view, vec, nullptr, 0, st_));
-        if (is_col_side) MFX_TRY(finalize_cols(f));
-        else PROF(KernelProfiler::K_FINALIZE, launch_finalize(s.view, f, st_));
+    if (p_.kernel_variant != 0) return flat_pass(plan_.row().sweep, is_col_side, FM_SWEEP, vec, nullptr, f);
+    float* gh = is_col_side ? gh_cols_.get() : gh_rows_.get();
+    PROF(KernelProfiler::K_SWEEP_WAVE, launch_sweep_wave(s.view, vec, gh, gh + s.view.nseg, st_));
+    f.gh_dense = gh;
+    if (is_col_side && comm_) {
+        PROF(KernelProfiler::K_ALLREDUCE, comm_allreduce_f32(comm_, gh, (size_t) 2 * n_, st_));
+        f.cnt_override = global_col_nnz_.get();
     }
+    PROF(KernelProfiler::K_FINALIZE, launch_finalize(s.view, f, st_));
     return MFX_OK;
 }
 
 int CcdSolver::resid(SegStreamStore& s, const float* gathered, const float* per_seg, int add) {
-    if (scatter_) {  // the store's own copy: local index = its gathered dimension (slice), segment id streams
+    if (plan_.scatter) {  // the store's own copy: local index = its gathered dimension (slice), segment id streams
         PROF(KernelProfiler::K_SCAT_RESID, launch_scatter(SM_RESID, s.view, gathered, per_seg, add, st_));
         return MFX_OK;
     }
@@ -1309,39 +1267,25 @@ int CcdSolver::resid(SegStreamStore& s, const float* gathered, const float* per_
 int CcdSolver::rank_as_written(uint32_t t, bool add_back) {
     float* u = Wt(t);
     float* v = Ht(t);
-    if (ref_order_ && ref_fused_) return rank_ref_fused(t, add_back);
-    if (ref_order_) {
-        // (r4) reference-order mode: the subtraction of rank t - 1 and the add-back of rank t are two consecutive elementwise passes
-        // over the same copy (src/CCD.cpp:100-134) -- applied in ONE pass per copy, in the same order and with the same two roundings
-        // per element (element_op<FM_FCSC>: (r - a b) + c d, unfused), so every stored residual keeps the reference's bits while the
-        // mode streams each copy once per rank instead of twice.  The subtraction of a rank stays pending until the next rank (or a
-        // reader of the residual: flush_pending) applies it.
-        if (pending_sub_ >= 0) {
-            const uint32_t prev = (uint32_t) pending_sub_;
-            if (add_back) {
-                PROF(KernelProfiler::K_PACK, launch_pack2(m_, Wt(prev), u, packA_.get(), st_));
-                PROF(KernelProfiler::K_PACK, launch_pack2(n_, Ht(prev), v, packB_.get(), st_));
-                PROF(KernelProfiler::K_RESID, launch_flat(FM_FCSC, csc_.view, packA_.get(), packB_.get(), 0, st_));  // (its sums are not used)
-                PROF(KernelProfiler::K_RESID, launch_flat(FM_FCSC, csr_.view, packB_.get(), packA_.get(), 0, st_));
-            } else {
-                MFX_TRY(resid(csc_, Wt(prev), Ht(prev), 0));
-                MFX_TRY(resid(csr_, Ht(prev), Wt(prev), 0));
-            }
-            pending_sub_ = -1;
-        } else if (add_back) {
-            MFX_TRY(resid(csc_, u, v, 1));
-            MFX_TRY(resid(csr_, v, u, 1));
+    // (r4) RefAsWritten: the subtraction of rank t - 1 and the add-back of rank t are two consecutive elementwise passes
+    // over the same copy (src/CCD.cpp:100-134) -- applied in ONE pass per copy, in the same order and with the same two roundings
+    // per element (element_op<FM_FCSC>: (r - a b) + c d, unfused), so every stored residual keeps the reference's bits while the
+    // mode streams each copy once per rank instead of twice.  The subtraction of a rank stays pending until the next rank (or a
+    // reader of the residual: flush_pending) applies it.
+    const bool merged = plan_.schedule == CcdPlan::Schedule::RefAsWritten;
+    if (merged && pending_sub_ >= 0) {
+        const uint32_t prev = (uint32_t) pending_sub_;
+        if (add_back) {
+            PROF(KernelProfiler::K_PACK, launch_pack2(m_, Wt(prev), u, packA_.get(), st_));
+            PROF(KernelProfiler::K_PACK, launch_pack2(n_, Ht(prev), v, packB_.get(), st_));
+            PROF(KernelProfiler::K_RESID, launch_flat(FM_FCSC, csc_.view, packA_.get(), packB_.get(), 0, st_));  // (its sums are not used)
+            PROF(KernelProfiler::K_RESID, launch_flat(FM_FCSC, csr_.view, packB_.get(), packA_.get(), 0, st_));
+        } else {
+            MFX_TRY(resid(csc_, Wt(prev), Ht(prev), 0));
+            MFX_TRY(resid(csr_, Ht(prev), Wt(prev), 0));
         }
-        bool stop = false;
-        for (int it = 1; it <= p_.maxinneriter && !stop; ++it) {
-            MFX_TRY(sweep(csc_, u, v, true));
-            MFX_TRY(sweep(csr_, v, u, false));
-            MFX_TRY(inner_stop(t, it, &stop));
-        }
-        pending_sub_ = (int32_t) t;
-        return MFX_OK;
-    }
-    if (add_back) {
+        pending_sub_ = -1;
+    } else if (add_back) {
         MFX_TRY(resid(csc_, u, v, 1));
         MFX_TRY(resid(csr_, v, u, 1));
     }
@@ -1350,6 +1294,10 @@ int CcdSolver::rank_as_written(uint32_t t, bool add_back) {
         MFX_TRY(sweep(csc_, u, v, true));   // v <- rank-one over columns, using u
         MFX_TRY(sweep(csr_, v, u, false));  // u <- rank-one over rows, using the new v
         MFX_TRY(inner_stop(t, it, &stop));
+    }
+    if (merged) {
+        pending_sub_ = (int32_t) t;
+        return MFX_OK;
     }
     MFX_TRY(resid(csc_, u, v, 0));
     MFX_TRY(resid(csr_, v, u, 0));
@@ -1379,7 +1327,7 @@ int CcdSolver::test_rmse(double* rmse_out) {
 // captured once and replayed: one host call per outer iteration instead of 4k.  Matters when the
 // kernels are a few microseconds long (ML-100K / ML-1M sized inputs); irrelevant at Netflix size.
 int CcdSolver::enqueue_outer_iteration(int64_t oiter) {
-    const bool graphable = p_.schedule == 1 && p_.graph >= 0 && !comm_ && !prof_.enabled() && !graph_failed_ && !ext_on_;
+    const bool graphable = plan_.row().graphable && p_.graph >= 0 && !comm_ && !prof_.enabled() && !graph_failed_ && !plan_.ext_on;
     if (graphable && graph_exec_) {
         MFX_HIP(hipGraphLaunch(graph_exec_, st_));
         pending_sub_ = (int32_t) k_ - 1;
@@ -1398,7 +1346,7 @@ int CcdSolver::enqueue_outer_iteration(int64_t oiter) {
     early_stop_ = 0;
     uint32_t done = 0;
     for (uint32_t t = 0; t < k_ && rc == MFX_OK; ++t) {
-        if (defer_resid_ && t + 1 < k_) {  // (with odd k the last rank is an ordinary fused one)
+        if (plan_.schedule == CcdPlan::Schedule::FlatPairs && t + 1 < k_) {  // (with odd k the last rank is an ordinary flat one)
             rc = rank_pair(t);
             ++t;
             done += 2;
@@ -1406,17 +1354,17 @@ int CcdSolver::enqueue_outer_iteration(int64_t oiter) {
         }
         if (p_.eps > 0.f && early_stop_ >= 5) break;  // LIBPMF: five ranks stopped in their first inner iteration
         if (p_.rank_trace) rc = trace_begin(t);
-        if (rc == MFX_OK) rc = p_.schedule == 0 ? rank_as_written(t, oiter > 1) : rank_fused(t);
+        if (rc == MFX_OK) rc = plan_.as_written() ? rank_as_written(t, oiter > 1) : rank_fused(t, oiter > 1);
         if (rc == MFX_OK && p_.rank_trace) rc = trace_end(t);
         ++done;
     }
-    if (rc == MFX_OK && done < k_ && p_.schedule == 1 && pending_sub_ >= 0) {
+    if (rc == MFX_OK && done < k_ && !plan_.as_written() && pending_sub_ >= 0) {
         // the next outer iteration starts at rank 0, not at the rank the packs were primed for
         const uint32_t last = (uint32_t) pending_sub_;
         PROF(KernelProfiler::K_PACK, launch_pack2(m_, Wt(last), Wt(0), packA_.get(), st_));
         PROF(KernelProfiler::K_PACK, launch_pack2(n_, Ht(last), Ht(0), packB_.get(), st_));
     }
-    if (ext_on_) {
+    if (plan_.ext_on) {
         trace_done_.push_back((int32_t) done);
         if (p_.rank_trace) { trace_rmse_.resize(trace_done_.size() * k_, std::nan("")); trace_secs_.resize(trace_done_.size() * k_, 0.0); }
     }
@@ -1445,7 +1393,7 @@ int CcdSolver::iterate(int n_outer, int with_rmse, mfx_iter_report* reports) {
         // take that hit before the first timed iteration, with an all-reduce of the (still zero) column
         // buffer.  Every rank reaches this point with the same n_outer, so the collective is matched.
         MFX_TRY(comm_allreduce_f32(comm_, gh_cols_.get(), (size_t) 2 * n_, st_));
-        if (overlap_groups_ > 1) {  // ... and the panel-group sized ones on the stream they will run on
+        if (plan_.overlap_groups > 1) {  // ... and the panel-group sized ones on the stream they will run on
             const SegStreamDev& v = csr_.view;
             MFX_HIP(hipStreamSynchronize(st_));
             for (uint32_t g = 0; g < v.scat_ngroups; ++g)
@@ -1478,7 +1426,7 @@ int CcdSolver::iterate(int n_outer, int with_rmse, mfx_iter_report* reports) {
         MFX_HIP(hipEventElapsedTime(&ms_iter, ev_[0], ev_[1]));
         MFX_HIP(hipEventElapsedTime(&ms_rmse, ev_[2], ev_[3]));
         mfx_iter_report rep;
-        if (p_.schedule == 0) {  // the reference's split: sweeps vs residual updates
+        if (plan_.books_split) {  // the reference's split: sweeps vs residual updates
             auto d = [&](int id) { return prof_.seconds[id] - before[id]; };
             rep.update_time = d(KernelProfiler::K_RESID) + d(KernelProfiler::K_RESID_WAVE);
             rep.rank_time = ms_iter * 1e-3 - rep.update_time;
@@ -1506,7 +1454,7 @@ int CcdSolver::iterate(int n_outer, int with_rmse, mfx_iter_report* reports) {
 int CcdSolver::set_profile(bool on) {
     // (schedule 0 keeps its launch events on regardless: its rank/update split is derived from them)
     p_.profile = on ? 1 : 0;
-    prof_.enable(on || (p_.schedule == 0 && !ref_fused_));
+    prof_.enable(on || plan_.events_forced);
     prof_.reset_totals();
     return MFX_OK;
 }

@@ -154,6 +154,11 @@ struct FlatLayoutOptions {
     uint32_t scatter_groups = 1;  // panel groups the pass can be launched by (ccd_kernels.hpp, SegStreamDev::scat_ngroups)
     uint32_t scatter_wgs = 0;     // persistent workgroups per launch; 0 = one per CU
     const float* val = nullptr;   // input-order values for emit_val; nullptr = zeros
+    // environment knobs of the device-side build (CcdKnobs::apply, ccd_solver.hpp); build_flat_layout reads none of them
+    bool setup_timing = false;       // MFX_SETUP_TIMING: print where the build spends its time
+    bool fuse_by_first_seg = false;  // MFX_FUSE_FINALIZE=2: dispatch order of the in-pass finalize
+    uint32_t scatter_wgs_pin = 0;    // MFX_SCATTER_WGS: overrides scatter_wgs and the CU count
+    uint32_t owner_long = 0;         // MFX_OWNER_LONG: entries from which a segment gets a workgroup of its own; 0 = the default
 };
 
 // ptr/idx are the input orientation (host pointers); G is the gathered dimension.
