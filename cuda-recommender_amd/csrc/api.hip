@@ -766,6 +766,22 @@ int mfx_rec_candidates_times(mfx_rec_t r, double seconds[3]) {
         return MFX_OK;
     });
 }
+int mfx_rec_diversify(mfx_rec_t r, int64_t nusers, const uint32_t* users, const float* Wq, const uint32_t* cand_ptr,
+                      const uint32_t* cand_idx, int32_t flags, int metric, float tradeoff, int32_t n_top, uint32_t* items, float* scores,
+                      float* values, uint32_t* n_eligible, mfx_memspace space, int form) {
+    return guarded("mfx_rec_diversify", [&]() -> int {
+        MFX_REQUIRE(r && r->impl, "null recommender");
+        return r->impl->diversify(nusers, users, Wq, cand_ptr, cand_idx, flags, metric, tradeoff, n_top, items, scores, values, n_eligible,
+                                  space, form);
+    });
+}
+int mfx_rec_diversify_times(mfx_rec_t r, double seconds[3]) {
+    return guarded("mfx_rec_diversify_times", [&]() -> int {
+        MFX_REQUIRE(r && r->impl && seconds, "null recommender or seconds");
+        r->impl->diversify_times(seconds);
+        return MFX_OK;
+    });
+}
 int mfx_rec_destroy(mfx_rec_t r) {
     return guarded("mfx_rec_destroy", [&]() -> int {
         if (!r) return MFX_OK;

@@ -32,15 +32,13 @@
 #include <cstdlib>
 #include <cstring>
 
-#include "rec_tiles.hpp"
+#include "rec_cand.hpp"  // the piece size, lane_chain, excluded, Events: shared with rec_diversify.hip
 #include "recommend.hpp"
 
 namespace mfx {
 
 namespace {
 
-constexpr int kCandChunk = 2048;    // candidates of one piece: 16 KiB of LDS for the sort
-constexpr int kCandThreads = 256, kCandWaves = 4;
 constexpr int kStageT = 32;         // floats of a row per LDS stage: one 128-byte line
 constexpr int kStageStride = 36;    // floats between the rows of a stage: 16-byte reads of 16 consecutive rows hit 64 distinct banks
 constexpr int kStageRows = 64;
@@ -72,40 +70,6 @@ struct CandArgs {
     float* out_scores;         // may be NULL
     uint32_t* n_el;            // may be NULL; zeroed, pieces add
 };
-
-__device__ inline void wave_sync() {
-    __threadfence_block();
-    __builtin_amdgcn_wave_barrier();
-}
-
-__device__ inline bool excluded(const uint32_t* ex, uint32_t lo, uint32_t hi, uint32_t item) {
-    const uint32_t end = hi;
-    while (lo < hi) {
-        const uint32_t mid = lo + (hi - lo) / 2;
-        if (ex[mid] < item) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo < end && ex[lo] == item;
-}
-
-// The score chain of rec_rank.hip's chain_score: fma over t = 0 .. k-1 ascending from +0, the row read by its lane.
-__device__ inline float lane_chain(const float* wr, const float* hr, int k, int kt) {
-    float acc = 0.f;
-    int t = 0;
-    if ((kt & 3) == 0) {
-#pragma unroll 4  // (four 16-byte loads of the row in flight)
-        for (; t + 4 <= k; t += 4) {
-            const f32x4 h = *reinterpret_cast<const f32x4*>(hr + t);
-            const f32x4 w = *reinterpret_cast<const f32x4*>(wr + t);
-            acc = __builtin_fmaf(h.x, w.x, acc);
-            acc = __builtin_fmaf(h.y, w.y, acc);
-            acc = __builtin_fmaf(h.z, w.z, acc);
-            acc = __builtin_fmaf(h.w, w.w, acc);
-        }
-    }
-    for (; t < k; ++t) acc = __builtin_fmaf(hr[t], wr[t], acc);
-    return acc;
-}
 
 // The scores of the 64 candidates of a wave, lane l owning (row wr of W, item): every lane of the wave calls this, the
 // ones without a candidate with item 0.  stg: the wave's kStageRows x kStageStride floats of LDS (LOAD_GROUP only).
@@ -451,18 +415,6 @@ __global__ void mfx_expl_check_targets(const uint32_t* targets, size_t n, uint32
     }
 }
 
-struct Events {  // four stream events around the three phases
-    hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
-    int create() {
-        for (auto& x : e) MFX_HIP(hipEventCreate(&x));
-        return MFX_OK;
-    }
-    ~Events() {
-        for (auto x : e)
-            if (x) (void) hipEventDestroy(x);
-    }
-};
-
 // Which form of the gather a call takes: `measured` (what was faster on the MI355X) unless MFX_CAND_LOAD=group
 // or =lane forces one -- the hook of tools/candidates_bench.py, which records both; the results are the same bits.
 bool load_by_group(bool measured) {
@@ -478,6 +430,56 @@ constexpr int kGroupMinKt = 128;
 constexpr uint64_t kGroupMinMeanList = 512;
 
 }  // namespace
+
+int Recommender::cand_stage(const char* fn, uint32_t nu, const uint32_t* cand_ptr, const uint32_t* cand_idx, mfx_memspace space,
+                            CandLists& l) {
+    l.ptr = cand_ptr;
+    l.idx = cand_idx;
+    l.idx_grid = 2048;  // (the number of candidates is still on the device: a fixed grid strides over them)
+    if (space != MFX_HOST) return MFX_OK;
+    const uint32_t total = cand_ptr[nu];
+    MFX_REQUIRE(total == 0 || cand_idx, "%s: cand_idx is NULL but the lists hold %u candidates", fn, total);
+    MFX_TRY(l.d_ptr.alloc((size_t) nu + 1));
+    MFX_TRY(l.d_ptr.upload(cand_ptr, (size_t) nu + 1, MFX_HOST, st_));
+    l.ptr = l.d_ptr.get();
+    if (total) {
+        MFX_TRY(l.d_idx.alloc(total));
+        MFX_TRY(l.d_idx.upload(cand_idx, total, MFX_HOST, st_));
+    }
+    l.idx = l.d_idx.get();
+    l.idx_grid = grid_for(total);
+    return MFX_OK;
+}
+
+// the one host round trip: the rows are valid or not, how many candidates there are, how many lists are longer than a chunk
+int Recommender::cand_check(const char* fn, uint32_t nu, CandLists& l) {
+    hipStream_t st = st_;
+    DevBuf<CandInfo> info;
+    MFX_TRY(info.alloc(1));
+    MFX_TRY(l.long_list.alloc(nu));
+    CandInfo hi{kCandFine, 0, 0};
+    MFX_HIP(hipMemcpyAsync(info.get(), &hi, sizeof(hi), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(mfx_cand_check_ptr, dim3(grid_for(nu)), dim3(256), 0, st, l.ptr, nu, info.get(), l.long_list.get());
+    MFX_LAUNCH_CHECK();
+    if (l.idx) {
+        hipLaunchKernelGGL(mfx_cand_check_idx, dim3(l.idx_grid), dim3(256), 0, st, l.ptr, l.idx, nu, (uint32_t) cols_, info.get());
+        MFX_LAUNCH_CHECK();
+    }
+    MFX_HIP(hipMemcpyAsync(&hi, info.get(), sizeof(hi), hipMemcpyDeviceToHost, st));
+    MFX_HIP(hipStreamSynchronize(st));
+    if (hi.first != kCandFine) {
+        const unsigned long long slot = hi.first >> 2;
+        switch ((int) (hi.first & 3)) {
+            case 0: return fail(MFX_ERR_INVALID, "%s: cand_ptr is not non-decreasing from 0 at slot %llu", fn, slot);
+            case 1: return fail(MFX_ERR_INVALID, "%s: the list of slot %llu has an item id out of range [0, %lld)", fn, slot, (long long) cols_);
+            default: return fail(MFX_ERR_INVALID, "%s: the item ids of slot %llu are not strictly ascending", fn, slot);
+        }
+    }
+    l.total = hi.total;
+    l.nlong = hi.nlong;
+    MFX_REQUIRE(l.total == 0 || l.idx, "%s: cand_idx is NULL but the lists hold %u candidates", fn, l.total);
+    return MFX_OK;
+}
 
 int Recommender::query_candidates(int64_t nusers, const uint32_t* users, const uint32_t* cand_ptr, const uint32_t* cand_idx,
                                   int32_t flags, int32_t n_top, uint32_t* items, float* scores, uint32_t* n_eligible,
@@ -500,50 +502,16 @@ int Recommender::query_candidates(int64_t nusers, const uint32_t* users, const u
     MFX_TRY(ev.create());
     MFX_HIP(hipEventRecord(ev.e[0], st));
 
-    DevBuf<uint32_t> d_users, d_ptr, d_idx, long_list, piece_slot, d_items, d_nel, part_i;
+    DevBuf<uint32_t> d_users, piece_slot, d_items, d_nel, part_i;
     DevBuf<float> d_scores, part_s;
-    DevBuf<CandInfo> info;
+    CandLists lists;
     const uint32_t* du = nullptr;
     MFX_TRY(stage_ids(users, nu, space, (uint32_t) rows_, "mfx_rec_query_candidates: user id", d_users, &du));
-    const uint32_t* dp = cand_ptr;
-    const uint32_t* di = cand_idx;
-    if (host) {
-        const uint32_t total = cand_ptr[nu];
-        MFX_REQUIRE(total == 0 || cand_idx, "%s: cand_idx is NULL but the lists hold %u candidates", fn, total);
-        MFX_TRY(d_ptr.alloc((size_t) nu + 1));
-        MFX_TRY(d_ptr.upload(cand_ptr, (size_t) nu + 1, MFX_HOST, st));
-        dp = d_ptr.get();
-        if (total) {
-            MFX_TRY(d_idx.alloc(total));
-            MFX_TRY(d_idx.upload(cand_idx, total, MFX_HOST, st));
-        }
-        di = d_idx.get();
-    }
-    // the one host round trip: the rows are valid or not, how many candidates there are, how many lists need the merge
-    MFX_TRY(info.alloc(1));
-    MFX_TRY(long_list.alloc(nu));
-    CandInfo hi{kCandFine, 0, 0};
-    MFX_HIP(hipMemcpyAsync(info.get(), &hi, sizeof(hi), hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(mfx_cand_check_ptr, dim3(grid_for(nu)), dim3(256), 0, st, dp, nu, info.get(), long_list.get());
-    MFX_LAUNCH_CHECK();
-    if (di) {
-        // (the number of candidates is still on the device: a fixed grid strides over them)
-        hipLaunchKernelGGL(mfx_cand_check_idx, dim3(host ? grid_for(cand_ptr[nu]) : 2048), dim3(256), 0, st, dp, di, nu, (uint32_t) cols_,
-                           info.get());
-        MFX_LAUNCH_CHECK();
-    }
-    MFX_HIP(hipMemcpyAsync(&hi, info.get(), sizeof(hi), hipMemcpyDeviceToHost, st));
-    MFX_HIP(hipStreamSynchronize(st));
-    if (hi.first != kCandFine) {
-        const unsigned long long slot = hi.first >> 2;
-        switch ((int) (hi.first & 3)) {
-            case 0: return fail(MFX_ERR_INVALID, "%s: cand_ptr is not non-decreasing from 0 at slot %llu", fn, slot);
-            case 1: return fail(MFX_ERR_INVALID, "%s: the list of slot %llu has an item id out of range [0, %lld)", fn, slot, (long long) cols_);
-            default: return fail(MFX_ERR_INVALID, "%s: the item ids of slot %llu are not strictly ascending", fn, slot);
-        }
-    }
-    const uint32_t total = hi.total;
-    MFX_REQUIRE(total == 0 || di, "%s: cand_idx is NULL but the lists hold %u candidates", fn, total);
+    MFX_TRY(cand_stage(fn, nu, cand_ptr, cand_idx, space, lists));
+    MFX_TRY(cand_check(fn, nu, lists));
+    const uint32_t* dp = lists.ptr;
+    const uint32_t* di = lists.idx;
+    const uint32_t total = lists.total;
 
     const uint64_t npieces = (uint64_t) nu + total / kCandChunk;
     MFX_TRY(piece_slot.alloc(npieces));
@@ -559,7 +527,7 @@ int Recommender::query_candidates(int64_t nusers, const uint32_t* users, const u
         if (n_eligible) { MFX_TRY(d_nel.alloc(nu)); onel = d_nel.get(); }
     }
     if (onel) MFX_HIP(hipMemsetAsync(onel, 0, sizeof(uint32_t) * nu, st));
-    if (hi.nlong) {
+    if (lists.nlong) {
         const size_t np = 2 * ((size_t) total / kCandChunk + 2) * n_top;
         MFX_TRY(part_s.alloc(np));
         MFX_TRY(part_i.alloc(np));
@@ -585,10 +553,10 @@ int Recommender::query_candidates(int64_t nusers, const uint32_t* users, const u
         MFX_LAUNCH_CHECK();
     }
     MFX_HIP(hipEventRecord(ev.e[2], st));
-    if (hi.nlong) {
+    if (lists.nlong) {
         int M = 1;
         while (M < n_top) M <<= 1;
-        hipLaunchKernelGGL(mfx_cand_merge, dim3(hi.nlong), dim3(kCandThreads), 0, st, a, (const uint32_t*) long_list.get(), M);
+        hipLaunchKernelGGL(mfx_cand_merge, dim3(lists.nlong), dim3(kCandThreads), 0, st, a, (const uint32_t*) lists.long_list.get(), M);
         MFX_LAUNCH_CHECK();
     }
     MFX_HIP(hipEventRecord(ev.e[3], st));

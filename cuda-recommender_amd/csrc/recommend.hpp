@@ -85,6 +85,17 @@ struct IvfIndex {
     DevBuf<uint32_t> list_idx;
 };
 
+// The candidate lists of a batch on the device, as the checks of rec_candidates.hip leave them (mfx_rec_query_candidates,
+// mfx_rec_diversify).
+struct CandLists {
+    DevBuf<uint32_t> d_ptr, d_idx;  // the copies, when the caller's arrays live on the host
+    DevBuf<uint32_t> long_list;     // [nu], the first nlong filled: the slots whose list is longer than 2048, in any order
+    const uint32_t* ptr = nullptr;  // [nu + 1], on the device
+    const uint32_t* idx = nullptr;  // NULL when the caller passed none
+    int idx_grid = 0;               // workgroups of the check of the ids
+    uint32_t total = 0, nlong = 0;  // after cand_check: ptr[nu] and the number of long lists
+};
+
 class Recommender {
 public:
     static int create(Recommender** out, const float* W, const float* H, int64_t rows, int64_t cols, int64_t k,
@@ -117,6 +128,11 @@ public:
                          int32_t n_top, uint32_t* items, float* scores, uint32_t* n_eligible, mfx_memspace space);
     int score(int64_t npairs, const uint32_t* users, const uint32_t* items, float* scores, mfx_memspace space);
     void candidates_times(double out[3]) const { for (int i = 0; i < 3; ++i) out[i] = cand_s_[i]; }
+    // mfx_rec_diversify / mfx_rec_diversify_times (rec_diversify.hip)
+    int diversify(int64_t nusers, const uint32_t* users, const float* Wq, const uint32_t* cand_ptr, const uint32_t* cand_idx, int32_t flags,
+                  int metric, float tradeoff, int32_t n_top, uint32_t* items, float* scores, float* values, uint32_t* n_eligible,
+                  mfx_memspace space, int form);
+    void diversify_times(double out[3]) const { for (int i = 0; i < 3; ++i) out[i] = div_s_[i]; }
     // mfx_rec_ivf_setup / mfx_rec_ivf_lists / mfx_rec_ivf_probe / mfx_rec_query_ivf / mfx_rec_ivf_times (rec_ivf.hip)
     int ivf_setup(int32_t nlist, const uint32_t* assign, const float* centroids, mfx_memspace space);
     int ivf_lists(uint32_t* list_ptr, uint32_t* list_idx, mfx_memspace space);
@@ -162,6 +178,12 @@ private:
     // they are, NULL for ids = NULL.  `what` opens the refusal ("mfx_rec_query: user id").
     int stage_ids(const uint32_t* ids, uint32_t n, mfx_memspace space, uint32_t bound, const char* what, DevBuf<uint32_t>& buf,
                   const uint32_t** dev);
+    // The candidate lists of nu slots (rec_candidates.hip).  cand_stage: onto the device when they live on the host (l.ptr /
+    // l.idx are where they are then).  cand_check: the device-side checks of mfx_rec_query_candidates and their one host round
+    // trip (it synchronises the stream): MFX_ERR_INVALID naming the first offending slot, else l.total, l.nlong and
+    // l.long_list.  `fn` opens the refusals.
+    int cand_stage(const char* fn, uint32_t nu, const uint32_t* cand_ptr, const uint32_t* cand_idx, mfx_memspace space, CandLists& l);
+    int cand_check(const char* fn, uint32_t nu, CandLists& l);
     // Item slices (grid.y) of a tile pass over `blocks` workgroups of slots: `forced`, or for 0 enough for about two workgroups
     // per CU; at most cap, and none empty.  rank() passes its item_slices; topn() calls this for item_slices = 0 only and
     // takes a forced count as given (empty slices included: they merge as padding), as it always did.
@@ -210,6 +232,7 @@ private:
     IvfIndex ivf_;
     double ivf_s_[4] = {0, 0, 0, 0};  // stream seconds of the last query_ivf: probe / work-item build / list pass / merge
     double cand_s_[3] = {0, 0, 0};  // stream seconds of the last query_candidates / score: check + stage / score / merge of long lists
+    double div_s_[3] = {0, 0, 0};   // stream seconds of the last diversify: check + stage / relevance / selection
 };
 
 // The sums behind {HR, precision, recall, NDCG} at one cutoff, shared by mfx_topn_metrics (positions read off a list) and

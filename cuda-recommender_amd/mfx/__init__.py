@@ -10,4 +10,4 @@ from .api import als_block_half  # noqa: F401
 from ._lib import LIB_PATH, MfxError, lib  # noqa: F401
 from ._lib import MFX_FOLD_ALS, MFX_FOLD_ALS_EXACT, MFX_FOLD_CCD, MFX_FOLD_IMPLICIT  # noqa: F401
 from ._lib import MFX_SIM_DOT, MFX_SIM_COSINE  # noqa: F401
-from ._lib import MFX_CAND_NO_EXCLUDE  # noqa: F401
+from ._lib import MFX_CAND_NO_EXCLUDE, MFX_DIV_NO_EXCLUDE  # noqa: F401

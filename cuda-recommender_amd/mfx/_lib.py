@@ -15,6 +15,7 @@ MFX_VERSION = 2  # include/mfx.h
 MFX_FOLD_ALS, MFX_FOLD_ALS_EXACT, MFX_FOLD_CCD, MFX_FOLD_IMPLICIT = 0, 1, 2, 3  # include/mfx.h mfx_fold_model
 MFX_SIM_DOT, MFX_SIM_COSINE = 0, 1  # include/mfx.h mfx_rec_metric
 MFX_CAND_NO_EXCLUDE = 1  # include/mfx.h, flags of mfx_rec_query_candidates
+MFX_DIV_NO_EXCLUDE = 1  # include/mfx.h, flags of mfx_rec_diversify
 
 u32p = C.POINTER(C.c_uint32)
 f32p = C.POINTER(C.c_float)
@@ -169,6 +170,9 @@ SIGNATURES = {
                                            C.c_void_p, C.c_void_p, C.c_int]),
     "mfx_rec_score": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "mfx_rec_candidates_times": (C.c_int, [C.c_void_p, f64p]),
+    "mfx_rec_diversify": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int, C.c_float,
+                                    C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
+    "mfx_rec_diversify_times": (C.c_int, [C.c_void_p, f64p]),
     "mfx_rec_ivf_setup": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int]),
     "mfx_rec_ivf_lists": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "mfx_rec_ivf_probe": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int]),

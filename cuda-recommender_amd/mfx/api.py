@@ -1244,33 +1244,10 @@ class Recommender:
         the faster call from a list length between 300 (9.8 ms) and 1 000 (28.0 ms) on, about 5 % of the catalogue; for a
         batch of 1 024 users this call stays faster up to the whole catalogue as the list (0.98 against 1.36 ms).  The
         choice between the two is the caller's."""
-        ptr, idx = _candidate_lists(candidates)
-        dev = on_device or any(_is_dev(a) for a in (ptr, idx, users))
         if not 1 <= int(n_top) <= 1024:
             raise ValueError("n_top must be in 1 .. 1024")
-        if _is_dev(ptr) != _is_dev(idx):
-            raise ValueError("the candidate arrays must both be host arrays or both tensors")
-        wide = _ids_torch if _is_dev(ptr) else _ids_np
-        ptr = wide(ptr, "candidate row pointers")
-        if not (canonical and _is_ids32(idx)):  # (canonical 32-bit ids are not copied here)
-            idx = wide(idx, "candidate ids")
-        n = int(ptr.shape[0]) - 1
-        if n < 0:
-            raise ValueError("candidate row pointers must have one entry per list and one more")
-        if users is None:
-            if n > self.rows:
-                raise ValueError(f"{n} candidate lists but the model has {self.rows} users: pass `users`")
-        else:
-            if not _is_ids32(users):
-                users = _ids_torch(users, "users") if _is_dev(users) else _ids_np(users, "users")
-            if int(users.shape[0]) != n:
-                raise ValueError(f"{int(users.shape[0])} users but {n} candidate lists")
-        if n and int(ptr[-1]) > int(idx.shape[0]):
-            raise ValueError("the candidate row pointers end past the candidate ids")
-        if not canonical:
-            if n and (int(ptr[0]) != 0 or bool((ptr[1:] < ptr[:-1]).any())):
-                raise ValueError("candidate row pointers must start at 0 and be non-decreasing")
-            ptr, idx = (_canonical_lists_torch if _is_dev(ptr) else _canonical_lists_np)(ptr, idx)
+        ptr, idx, users, n = self._candidate_batch(candidates, users, canonical)
+        dev = on_device or any(_is_dev(a) for a in (ptr, idx, users))
         flags = 0 if apply_exclude else L.MFX_CAND_NO_EXCLUDE
         fn = L.lib().mfx_rec_query_candidates
         if dev:
@@ -1290,6 +1267,141 @@ class Recommender:
             L.check(fn(self.handle, n, _vp(pu), _vp(pp), _vp(pi) if pi.size else None, flags, n_top, _vp(items), _vp(scores),
                        _vp(counts), L.MFX_HOST))
         return (items, scores, counts) if return_counts else (items, scores)
+
+    def _candidate_batch(self, candidates, users, canonical: bool, own_vectors: int = -1):
+        """The lists of query_candidates / diversify as the library takes them -> (ptr, idx, users, number of slots):
+        int64 (or, canonical, the caller's 32-bit) arrays or tensors, each list sorted and without repeats and PAD_ITEM
+        entries unless canonical.  own_vectors >= 0: the slots bring that many query vectors instead of users."""
+        ptr, idx = _candidate_lists(candidates)
+        if _is_dev(ptr) != _is_dev(idx):
+            raise ValueError("the candidate arrays must both be host arrays or both tensors")
+        wide = _ids_torch if _is_dev(ptr) else _ids_np
+        ptr = wide(ptr, "candidate row pointers")
+        if not (canonical and _is_ids32(idx)):  # (canonical 32-bit ids are not copied here)
+            idx = wide(idx, "candidate ids")
+        n = int(ptr.shape[0]) - 1
+        if n < 0:
+            raise ValueError("candidate row pointers must have one entry per list and one more")
+        if own_vectors >= 0:
+            if own_vectors != n:
+                raise ValueError(f"{own_vectors} query vectors but {n} candidate lists")
+        elif users is None:
+            if n > self.rows:
+                raise ValueError(f"{n} candidate lists but the model has {self.rows} users: pass `users`")
+        else:
+            if not _is_ids32(users):
+                users = _ids_torch(users, "users") if _is_dev(users) else _ids_np(users, "users")
+            if int(users.shape[0]) != n:
+                raise ValueError(f"{int(users.shape[0])} users but {n} candidate lists")
+        if n and int(ptr[-1]) > int(idx.shape[0]):
+            raise ValueError("the candidate row pointers end past the candidate ids")
+        if not canonical:
+            if n and (int(ptr[0]) != 0 or bool((ptr[1:] < ptr[:-1]).any())):
+                raise ValueError("candidate row pointers must start at 0 and be non-decreasing")
+            ptr, idx = (_canonical_lists_torch if _is_dev(ptr) else _canonical_lists_np)(ptr, idx)
+        return ptr, idx, users, n
+
+    def diversify(self, n_top: int, candidates, users=None, vectors=None, tradeoff: float = 0.5, metric: int = L.MFX_SIM_COSINE,
+                  apply_exclude: bool = True, canonical: bool = False, on_device: bool = False, return_values: bool = False,
+                  return_counts: bool = False, form: int = 0):
+        """Diversity re-ranking of each slot's candidate list by greedy maximal marginal relevance -> (items [U, n_top],
+        scores [U, n_top][, values [U, n_top]][, counts [U]]) in pick order (mfx_rec_diversify; the rule, bit for bit, is
+        in include/mfx.h).  Step by step the pick is the eligible candidate with the greatest
+        tradeoff * score - (1 - tradeoff) * (its greatest similarity to the items picked so far, at least 0); ties go to
+        the greater score, then to the smaller id.  tradeoff = 1 is query_candidates; 0 looks at the scores only to break
+        ties.  metric: MFX_SIM_COSINE or MFX_SIM_DOT between rows of H, as similar_items computes them.
+        `candidates`, `users`, `canonical`, `apply_exclude` and the device forms as in query_candidates; a list holds at
+        most 2048 candidates after canonicalisation, n_top is at most 128.  `vectors` float32 [U, k] (numpy or GPU tensor):
+        the slots' own query vectors instead of users -- the W of fold_in, a session vector; they have no exclusion rows,
+        so apply_exclude must be False with them.  values: what the pick maximised at each step; counts: the eligible
+        candidates per slot.  form: 0, or 1 / 2 to force one form of the selection kernel (a test hook, the same bits)."""
+        if not 1 <= int(n_top) <= 128:
+            raise ValueError("n_top must be in 1 .. 128")
+        tradeoff = float(tradeoff)
+        if not 0.0 <= tradeoff <= 1.0:  # (NaN fails both)
+            raise ValueError("tradeoff must be in 0 .. 1")
+        if int(metric) not in (L.MFX_SIM_DOT, L.MFX_SIM_COSINE):
+            raise ValueError("metric must be MFX_SIM_DOT or MFX_SIM_COSINE")
+        if int(form) not in (0, 1, 2):
+            raise ValueError("form must be 0, 1 or 2")
+        nvec = -1
+        if vectors is not None:
+            if users is not None:
+                raise ValueError("pass users or vectors, not both")
+            if apply_exclude:
+                raise ValueError("vectors have no exclusion rows: pass apply_exclude=False")
+            if not _is_dev(vectors):
+                vectors = np.ascontiguousarray(vectors, np.float32)
+            if len(vectors.shape) != 2 or int(vectors.shape[1]) != self.k:
+                raise ValueError(f"vectors must be [U, {self.k}]")
+            nvec = int(vectors.shape[0])
+        ptr, idx, users, n = self._candidate_batch(candidates, users, canonical, nvec)
+        dev = on_device or any(_is_dev(a) for a in (ptr, idx, users, vectors))
+        flags = 0 if apply_exclude else L.MFX_DIV_NO_EXCLUDE
+        fn = L.lib().mfx_rec_diversify
+        if dev:
+            import torch
+            d = torch.device("cuda", self.device)
+            tp, ti, tu = (None if a is None else _to_dev32(a, d) for a in (ptr, idx, users))
+            tv = None
+            if vectors is not None:
+                tv = (vectors if _is_dev(vectors) else torch.from_numpy(vectors)).to(d, torch.float32).contiguous()
+            items = torch.empty((n, n_top), dtype=torch.int32, device=d)
+            scores = torch.empty((n, n_top), dtype=torch.float32, device=d)
+            values = torch.empty((n, n_top), dtype=torch.float32, device=d)
+            counts = torch.empty((n,), dtype=torch.int32, device=d)
+            if n:
+                p = lambda t: C.c_void_p(int(t.data_ptr())) if t is not None and t.numel() else None
+                L.check(fn(self.handle, n, p(tu), p(tv), p(tp), p(ti), flags, int(metric), tradeoff, n_top, p(items), p(scores),
+                           p(values), p(counts), L.MFX_DEVICE, int(form)))
+        else:
+            pp, pi = (np.ascontiguousarray(a).astype(np.uint32, copy=False) for a in (ptr, idx))
+            pu = None if users is None else np.ascontiguousarray(users).astype(np.uint32, copy=False)
+            pv = vectors
+            items, scores, values = np.empty((n, n_top), np.uint32), np.empty((n, n_top), np.float32), np.empty((n, n_top), np.float32)
+            counts = np.empty(n, np.uint32)
+            L.check(fn(self.handle, n, _vp(pu), _vp(pv), _vp(pp), _vp(pi) if pi.size else None, flags, int(metric), tradeoff, n_top,
+                       _vp(items), _vp(scores), _vp(values), _vp(counts), L.MFX_HOST, int(form)))
+        out = (items, scores)
+        if return_values:
+            out += (values,)
+        if return_counts:
+            out += (counts,)
+        return out
+
+    def diversify_times(self) -> dict:
+        """Stream seconds of the last diversify by phase (mfx_rec_diversify_times): {"check": copies in, validity checks,
+        similar_setup when it runs; "relevance": the kernel that scores the lists; "select": the kernel of the greedy steps}."""
+        out = (C.c_double * 3)()
+        L.check(L.lib().mfx_rec_diversify_times(self.handle, out))
+        return {"check": out[0], "relevance": out[1], "select": out[2]}
+
+    def query_diverse(self, n_top: int, pool: int, users=None, tradeoff: float = 0.5, metric: int = L.MFX_SIM_COSINE,
+                      on_device: bool = False):
+        """The one-call form: query(pool) for `users`, then diversify(n_top) over each user's pool -> (items [U, n_top],
+        scores [U, n_top]) in pick order.  n_top <= pool <= 1024.  The pool is the exact top-`pool` of the catalogue under the
+        exclusion rows and the item filter, so nothing is left for the second step to exclude."""
+        if not 1 <= int(n_top) <= 128:
+            raise ValueError("n_top must be in 1 .. 128")
+        if not int(n_top) <= int(pool) <= 1024:
+            raise ValueError("pool must be in n_top .. 1024")
+        if on_device and users is not None and not _is_dev(users):
+            import torch
+            users = _to_dev32(_ids_np(users, "users"), torch.device("cuda", self.device))
+        items, _ = self.query(int(pool), users, on_device=on_device)
+        if _is_dev(items):
+            import torch
+            ids = torch.sort(items.to(torch.int64) & 0xFFFFFFFF, dim=1).values  # (the padding sorts last)
+            lens = (ids != PAD_ITEM).sum(1)
+            ptr = torch.zeros(ids.shape[0] + 1, dtype=torch.int64, device=ids.device)
+            ptr[1:] = torch.cumsum(lens, 0)
+            idx = ids[ids != PAD_ITEM].to(torch.int32)
+        else:
+            ids = np.sort(items, axis=1)
+            ptr = np.zeros(ids.shape[0] + 1, np.int64)
+            np.cumsum((ids != PAD_ITEM).sum(1), out=ptr[1:])
+            idx = ids[ids != PAD_ITEM]
+        return self.diversify(n_top, (ptr, idx), users=users, tradeoff=tradeoff, metric=metric, canonical=True, on_device=on_device)
 
     def score(self, users, items, on_device: bool = False):
         """The model's score of each pair (users[p], items[p]) -> float32 [P] (mfx_rec_score): the score chain of

@@ -654,6 +654,48 @@ int mfx_rec_score(mfx_rec_t r, int64_t npairs, const uint32_t* users, const uint
  * [2] select (the merge of the lists longer than 2048 candidates; 0 when there is none).  After mfx_rec_score: [0] stage,
  * [1] score, [2] 0. */
 int mfx_rec_candidates_times(mfx_rec_t r, double seconds[3]);
+/* Diversity re-ranking of given candidate lists by greedy maximal marginal relevance (MMR): the page a caller shows
+ * instead of the n_top nearest neighbours of one another that relevance alone returns.
+ * Slot q has a user and a candidate list exactly as in mfx_rec_query_candidates: the list is a CSR row, ids strictly
+ * ascending and below cols, checked on the device.  A candidate is eligible as defined there: not in the user's exclusion
+ * row (flag MFX_DIV_NO_EXCLUDE: the exclude matrix plays no part), kept by the item filter, its score not NaN.  E: the
+ * eligible candidates of the slot.
+ *   rel(i) = the score chain of mfx_rec_query for (user, i), bit for bit;
+ *   a = tradeoff as fp32, b = fp32(1 - a), D_0(i) = +0 for every i in E.
+ * For s = 1 .. min(n_top, |E|):
+ *   1. value_s(i) = fmaf(-b, D_{s-1}(i), fp32(a * rel(i))) for every i in E not picked yet;
+ *   2. i_s = the candidate of the greatest value, then of the greater rel, then of the smaller item id; a NaN value
+ *      counts as -INFINITY, and -0 == +0 in both comparisons;
+ *   3. D_s(i) = sim(i_s, i) if that is greater than D_{s-1}(i), else D_{s-1}(i); a NaN similarity leaves D as it was.
+ * sim by metric: MFX_SIM_DOT: sim(j, i) = the chain fma(H[j][t], H[i][t], acc) over t = 0 .. k-1 from +0, the s(q, i) of
+ * mfx_rec_similar; MFX_SIM_COSINE: fp32(fp32(s(j, i) * c[i]) * c[j]), the score mfx_rec_similar(query j, MFX_SIM_COSINE)
+ * returns for item i, with the c of mfx_rec_item_norms.  D starts at +0, so a similarity below 0 never raises a candidate's
+ * D: items less alike than orthogonal ones are penalised like orthogonal ones, not rewarded.
+ * items [nusers][n_top] in pick order; scores [nusers][n_top] or NULL: rel; values [nusers][n_top] or NULL: the value at
+ * the moment of the pick as computed (it may be NaN); n_eligible [nusers] or NULL: |E|.  The positions left over hold
+ * (0xFFFFFFFF, -INFINITY, -INFINITY).  A slot's result does not depend on the batch, its order, the memory space, the
+ * factor layout or `form`.  With tradeoff = 1 and finite similarities value = rel, and items and scores equal those of
+ * mfx_rec_query_candidates with the same flags, bit for bit.
+ * users as in mfx_rec_query_candidates.  Wq: NULL, or [nusers][k] row-major query vectors in `space` that take the place
+ * of the rows of W (the W_out of mfx_rec_fold_in, session vectors, anything without an id): rel is then the same chain
+ * over Wq[q]; users must be NULL and MFX_DIV_NO_EXCLUDE set.
+ * Ranges: 1 <= n_top <= 128; every list at most 2048 candidates (one piece of mfx_rec_query_candidates); 0 <= tradeoff
+ * <= 1; 1 <= k <= 1024.  form: 0 automatic; 1 and 2 are test hooks that force the two forms of the selection kernel (1: the
+ * eligible rows of H staged once in LDS, 2: re-read at every step; the same bits); form 1 where the rows of the batch's
+ * longest list do not fit in LDS is MFX_ERR_INVALID.  The call runs mfx_rec_similar_setup if it has not run.
+ * Workspace during the call: 8 bytes per candidate, 8 bytes per slot, nusers * kt floats with Wq, and with `space` =
+ * MFX_HOST the device copies of the arguments and results.
+ * MFX_ERR_INVALID, the handle left usable, the message naming the first offending slot where there is one: anything
+ * outside the ranges, an unknown metric, unknown flag bits, a list that is too long, what mfx_rec_query_candidates refuses
+ * about pointers and ids, Wq with users or without the flag, form outside 0 .. 2.  nusers == 0 is MFX_OK and touches nothing. */
+#define MFX_DIV_NO_EXCLUDE 1   /* do not take the handle's exclusion rows off the lists */
+int mfx_rec_diversify(mfx_rec_t r, int64_t nusers, const uint32_t* users, const float* Wq, const uint32_t* cand_ptr,
+                      const uint32_t* cand_idx, int32_t flags, int metric, float tradeoff, int32_t n_top, uint32_t* items,
+                      float* scores, float* values, uint32_t* n_eligible, mfx_memspace space, int form);
+/* Stream seconds of the last mfx_rec_diversify on r by phase: [0] check + stage (copies in, the validity checks and their
+ * read-back, mfx_rec_similar_setup when it runs, the packing of Wq), [1] relevance (the kernel that scores every list and
+ * compacts its eligible candidates), [2] selection (the kernel of the greedy steps). */
+int mfx_rec_diversify_times(mfx_rec_t r, double seconds[3]);
 /* Inverted-file (IVF) retrieval, the first stage that mfx_rec_query_candidates is the second stage of: the items are
  * partitioned into nlist lists, each with a centroid; a query scores the user against the centroids, takes the best
  * nprobe lists and ranks only the items of those lists.  The clustering is the caller's (Python: mfx.ivf_kmeans).
