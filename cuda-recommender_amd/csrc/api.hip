@@ -6,6 +6,7 @@
 #include <stdexcept>
 
 #include "als_solver.hpp"
+#include "bpr.hpp"
 #include "ccd_solver.hpp"
 #include "recommend.hpp"
 
@@ -376,6 +377,72 @@ int mfx_ials_block_half_reg(int64_t nseg, int64_t nnz, const uint32_t* ptr, cons
         s.alpha = alpha; s.alpha0 = alpha0; s.nu = nu; s.block = block;
         return als_half(s, {nseg, nnz, ptr, idx, val, nrows_x}, X, Y_in, Y_out, k, lambda, nullptr, device);
     });
+}
+
+/* ------------------------------------------------------------------ BPR: deterministic mini-batch pairwise ranking */
+int mfx_bpr_create(mfx_bpr_t* out, const mfx_csx* R, const mfx_params* p, float lr, int64_t batch, uint64_t seed, mfx_memspace space) {
+    return guarded("mfx_bpr_create", [&]() -> int {
+        MFX_REQUIRE(out, "mfx_bpr_create: out is NULL");
+        *out = nullptr;
+        BprSolver* s = nullptr;
+        MFX_TRY(BprSolver::create(&s, R, p, lr, batch, seed, space));
+        *out = new mfx_bpr_s{s};
+        return MFX_OK;
+    });
+}
+int mfx_bpr_set_factors(mfx_bpr_t s, const float* W, const float* H, mfx_memspace space) {
+    return guarded("mfx_bpr_set_factors", [&]() -> int {
+        MFX_REQUIRE(s && s->impl, "null solver");
+        return s->impl->set_factors(W, H, space);
+    });
+}
+int mfx_bpr_get_factors(mfx_bpr_t s, float* W, float* H, mfx_memspace space) {
+    return guarded("mfx_bpr_get_factors", [&]() -> int {
+        MFX_REQUIRE(s && s->impl, "null solver");
+        return s->impl->get_factors(W, H, space);
+    });
+}
+int mfx_bpr_steps(mfx_bpr_t s, int64_t n_steps, int64_t stats[4], double* seconds) {
+    return guarded("mfx_bpr_steps", [&]() -> int {
+        MFX_REQUIRE(s && s->impl, "null solver");
+        return s->impl->steps(n_steps, stats, seconds);
+    });
+}
+int mfx_bpr_epochs(mfx_bpr_t s, int32_t n_epochs, int64_t* stats, double* seconds) {
+    return guarded("mfx_bpr_epochs", [&]() -> int {
+        MFX_REQUIRE(s && s->impl, "null solver");
+        return s->impl->epochs(n_epochs, stats, seconds);
+    });
+}
+int mfx_bpr_position(mfx_bpr_t s, int64_t* next_slot) {
+    return guarded("mfx_bpr_position", [&]() -> int {
+        MFX_REQUIRE(s && s->impl && next_slot, "null solver or next_slot");
+        *next_slot = s->impl->position();
+        return MFX_OK;
+    });
+}
+int mfx_bpr_kernel_times(mfx_bpr_t s, double seconds[4]) {
+    return guarded("mfx_bpr_kernel_times", [&]() -> int {
+        MFX_REQUIRE(s && s->impl && seconds, "null solver or seconds");
+        s->impl->times(seconds);
+        return MFX_OK;
+    });
+}
+int mfx_bpr_destroy(mfx_bpr_t s) {
+    return guarded("mfx_bpr_destroy", [&]() -> int {
+        if (!s) return MFX_OK;
+        delete s->impl;
+        delete s;
+        return MFX_OK;
+    });
+}
+int mfx_bpr_triples(uint64_t seed, int64_t first_slot, int64_t count, const mfx_csx* R, uint32_t* u, uint32_t* i, uint32_t* j,
+                    uint8_t* skipped) {
+    return guarded("mfx_bpr_triples", [&]() -> int { return bpr_triples(seed, first_slot, count, R, u, i, j, skipped); });
+}
+int mfx_bpr_apply(int64_t rows, int64_t cols, int64_t k, float* W, float* H, int64_t n, const uint32_t* u, const uint32_t* i,
+                  const uint32_t* j, const uint8_t* skipped, float lr, float lambda, int64_t stats[4], int device) {
+    return guarded("mfx_bpr_apply", [&]() -> int { return bpr_apply(rows, cols, k, W, H, n, u, i, j, skipped, lr, lambda, stats, device); });
 }
 
 int mfx_als_run(const mfx_csx* R, const mfx_coo* T, float* W, float* H, const mfx_params* p,

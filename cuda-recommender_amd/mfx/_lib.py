@@ -126,6 +126,18 @@ SIGNATURES = {
                                        C.c_int32, C.c_int]),
     "mfx_als_block_half": (C.c_int, [C.c_int64, C.c_int64, u32p, u32p, f32p, C.c_int64, f32p, f32p, f32p, C.c_int64, C.c_int32,
                                      C.c_float, C.c_int32, C.c_int]),
+    "mfx_bpr_create": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(mfx_csx), C.POINTER(mfx_params), C.c_float, C.c_int64, C.c_uint64,
+                                 C.c_int]),
+    "mfx_bpr_set_factors": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    "mfx_bpr_get_factors": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    "mfx_bpr_steps": (C.c_int, [C.c_void_p, C.c_int64, i64p, f64p]),
+    "mfx_bpr_epochs": (C.c_int, [C.c_void_p, C.c_int32, i64p, f64p]),
+    "mfx_bpr_position": (C.c_int, [C.c_void_p, i64p]),
+    "mfx_bpr_kernel_times": (C.c_int, [C.c_void_p, f64p]),
+    "mfx_bpr_destroy": (C.c_int, [C.c_void_p]),
+    "mfx_bpr_triples": (C.c_int, [C.c_uint64, C.c_int64, C.c_int64, C.POINTER(mfx_csx), u32p, u32p, u32p, C.c_void_p]),
+    "mfx_bpr_apply": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, f32p, f32p, C.c_int64, u32p, u32p, u32p, C.c_void_p, C.c_float,
+                                C.c_float, i64p, C.c_int]),
     "mfx_comm_unique_id": (C.c_int, [C.c_void_p]),
     "mfx_comm_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "mfx_comm_create_local": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int]),

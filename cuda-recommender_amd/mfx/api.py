@@ -598,6 +598,117 @@ class ImplicitAlsSolver(_AlsHandle):
         return {half: {key: int(out[4 * i + j]) for j, key in enumerate(keys)} for i, half in enumerate(("rows", "cols"))}
 
 
+def _bpr_report(stats, seconds: float) -> dict:
+    slots, skipped, bad, correct = (int(x) for x in stats)
+    counted = slots - skipped - bad
+    return {"slots": slots, "skipped": skipped, "bad": bad, "correct": correct,
+            "auc": correct / counted if counted else float("nan"), "seconds": float(seconds)}
+
+
+class BprSolver:
+    """Resident BPR training (mfx_bpr_*, include/mfx.h): every stored entry of R is a positive interaction, a slot pairs
+    it with an item drawn by a stateless hash of (seed, slot number), and `batch` slots make one step at frozen factors
+    whose sums are exact -- so the factors are fixed bit for bit by (R, seed, parameters, batch).  Reads k, lambda_, device
+    and profile of `parameters`.  Factors use the ALS layout, W [rows][k] and H [cols][k]; without set_factors the first
+    step draws 0.1 * N(0, 1) factors from numpy.random.default_rng(init_seed).  device_arrays: the matrix as a dict of device
+    tensors (mfx.synth_torch); only its CSR pointers and ids are read."""
+
+    def __init__(self, R: Optional[RatingData], parameters: parameter, lr: float, batch: int, seed: int = 0,
+                 device_arrays: Optional[dict] = None, init_seed: Optional[int] = None):
+        self.handle = C.c_void_p()
+        cp = parameters.to_c()
+        if device_arrays is not None:
+            self.rows, self.cols, self.k = int(device_arrays["rows"]), int(device_arrays["cols"]), int(parameters.k)
+            csx, space = _device_csx_coo(device_arrays)[0], L.MFX_DEVICE
+        else:
+            self.rows, self.cols, self.k = R.rows, R.cols, int(parameters.k)
+            csx, space = _csx(R), L.MFX_HOST
+        self._init_seed, self._have_factors = init_seed, False
+        L.check(L.lib().mfx_bpr_create(C.byref(self.handle), C.byref(csx), C.byref(cp), float(lr), int(batch), int(seed), space))
+
+    def set_factors(self, W, H):
+        _f32c(W, (self.rows, self.k))
+        _f32c(H, (self.cols, self.k))
+        L.check(L.lib().mfx_bpr_set_factors(self.handle, _vp(W), _vp(H), L.MFX_HOST))
+        self._have_factors = True
+
+    def _default_factors(self):
+        if not self._have_factors:
+            rng = np.random.default_rng(self._init_seed)
+            W = (0.1 * rng.standard_normal((self.rows, self.k))).astype(np.float32)
+            H = (0.1 * rng.standard_normal((self.cols, self.k))).astype(np.float32)
+            self.set_factors(W, H)
+
+    def get_factors(self):
+        W = np.empty((self.rows, self.k), np.float32)
+        H = np.empty((self.cols, self.k), np.float32)
+        L.check(L.lib().mfx_bpr_get_factors(self.handle, _vp(W), _vp(H), L.MFX_HOST))
+        return W, H
+
+    def steps(self, n: int) -> dict:
+        """n steps from the current slot: {"slots", "skipped", "bad", "correct", "auc", "seconds"} of the call."""
+        self._default_factors()
+        stats, sec = (C.c_int64 * 4)(), C.c_double(0.0)
+        L.check(L.lib().mfx_bpr_steps(self.handle, int(n), stats, C.byref(sec)))
+        return _bpr_report(stats, sec.value)
+
+    def iterate(self, n_epochs: int) -> List[dict]:
+        """n_epochs epochs (the first finishes a started one): one report per epoch."""
+        self._default_factors()
+        n = int(n_epochs)
+        stats, sec = (C.c_int64 * (4 * max(1, n)))(), (C.c_double * max(1, n))()
+        L.check(L.lib().mfx_bpr_epochs(self.handle, n, stats, sec))
+        return [_bpr_report(stats[4 * e:4 * e + 4], sec[e]) for e in range(n)]
+
+    def position(self) -> int:
+        out = C.c_int64(0)
+        L.check(L.lib().mfx_bpr_position(self.handle, C.byref(out)))
+        return int(out.value)
+
+    def kernel_times(self) -> dict:
+        """Stream seconds since create by kernel, collected with parameters.profile = 1 only."""
+        out = (C.c_double * 4)()
+        L.check(L.lib().mfx_bpr_kernel_times(self.handle, out))
+        return dict(zip(("sample", "gradient", "scatter", "apply"), (float(x) for x in out)))
+
+    def close(self):
+        if self.handle:
+            L.lib().mfx_bpr_destroy(self.handle)
+            self.handle = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def bpr_triples(R: RatingData, seed: int, first: int, count: int):
+    """(u, i, j uint32 [count], skipped bool [count]) of the slots first .. first + count - 1 (mfx_bpr_triples: the
+    sampler of BprSolver on the host, no GPU)."""
+    count = int(count)
+    u, i, j = (np.empty(count, np.uint32) for _ in range(3))
+    s = np.empty(count, np.uint8)
+    csx = _csx(R)
+    L.check(L.lib().mfx_bpr_triples(int(seed), int(first), count, C.byref(csx), _u32(u), _u32(i), _u32(j), _vp(s)))
+    return u, i, j, s.astype(bool)
+
+
+def bpr_apply(W, H, u, i, j, lr: float, lam: float, skipped=None, device: int = 0):
+    """One BPR step on the given triples at the factors W [rows][k], H [cols][k] (mfx_bpr_apply): returns (W', H', stats);
+    a slot is skipped only where `skipped` says so."""
+    W, H = np.array(_f32c(W)), np.array(_f32c(H))
+    assert W.ndim == 2 and H.ndim == 2 and W.shape[1] == H.shape[1]
+    u, i, j = (np.ascontiguousarray(a, np.uint32) for a in (u, i, j))
+    assert u.shape == i.shape == j.shape and u.ndim == 1
+    s = None if skipped is None else np.ascontiguousarray(skipped, np.uint8)
+    assert s is None or s.shape == u.shape
+    stats = (C.c_int64 * 4)()
+    L.check(L.lib().mfx_bpr_apply(W.shape[0], H.shape[0], W.shape[1], _f32(W), _f32(H), u.shape[0], _u32(u), _u32(i), _u32(j),
+                                  _vp(s), float(lr), float(lam), stats, device))
+    return W, H, _bpr_report(stats, 0.0)
+
+
 # ---------------------------------------------------------------------------------------------
 # single operators (one per reference function on the path)
 # ---------------------------------------------------------------------------------------------

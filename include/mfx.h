@@ -354,6 +354,81 @@ int mfx_als_block_half(int64_t nseg, int64_t nnz, const uint32_t* ptr, const uin
                        float lambda, int32_t reg, int device);
 
 /* ------------------------------------------------------------------------------------
+ * BPR training (Bayesian Personalised Ranking, Rendle et al. 2009) by deterministic mini-batch steps: the trainer that
+ * optimises the ranking itself.  Every bit of the factors is fixed by (data, seed, parameters, batch): the sums of a
+ * step are exact integer sums, so neither the order of the slots nor the launch geometry plays a part.
+ *
+ * Data.  Every stored entry of the CSR side of R is a positive interaction; values and the CSC side are not read.  The
+ * ids of every row must be strictly ascending and below cols, the pointers ascend from 0 to nnz (mfx/dataset.from_coo
+ * produces this); checked on the device at create, a violation is MFX_ERR_INVALID naming the first such row.  Factors in
+ * the ALS layout, W [rows][k] and H [cols][k], 1 <= k <= 1024; rows, cols, nnz < 2^32 - 1.
+ *
+ * One step takes n <= batch slots; slot t holds (u, i, j) = (user, positive item, sampled item) and is SKIPPED when j is
+ * in row u.  Every slot reads the factors as they were before the step.  For a slot that is not skipped:
+ *   d_c = fp32(H[i][c] - H[j][c]);
+ *   x   = the fp32 FMA chain acc = fmaf(W[u][c], d_c, acc) over c = 0 .. k-1 from +0 (the chain of mfx_rec_score);
+ *   g   = 1 / (1 + e^x) by this sequence of single fp32 operations (round to nearest even, no contraction):
+ *           xc = min(max(x, -80), 80);  n = rint(xc * 0x3FB8AA3B [1.44269502]);
+ *           r  = (xc - n * 0.693359375) - n * 0xB95E8083 [-2.12194442e-4];
+ *           p  = c6; p = p * r + c5; ... p = p * r + c0 (a multiply, then an add), c6 .. c0 = fp32 of 1/720, 1/120,
+ *                1/24, 1/6, 1/2, 1, 1 [0x3AB60B61, 0x3C088889, 0x3D2AAAAB, 0x3E2AAAAB, 0.5, 1, 1];
+ *           e  = ldexp(p, n) (exact);  g = 1 / (1 + e), the division correctly rounded.
+ *         Relative error against fp64 on |x| <= 30: 2.8e-7.  Saturation: g = 1 for x <= -16.64, g = 0x05BFECBB [1.80e-35]
+ *         for x >= 80; never NaN for finite x.
+ *   terms: fp32(g * d_c) for row u of W, fp32(g * W[u][c]) for row i of H and its exact negative for row j of H.
+ * The slot is BAD when x is not finite or a term has magnitude >= 64; a bad slot contributes nothing and is counted.
+ * (batch <= 2^20 slots give a row of H at most 2^21 terms: the sums stay below 2^27, the limit of csrc/ccd_scatter.hip.)
+ * Sums.  Every term is truncated toward zero to a multiple of 2^-36 and the terms of a row are added exactly, as 64-bit
+ * integers; a_c = the fp32 nearest to the sum (one rounding, int64 -> fp32, ties to even, then the exact scale).
+ * Update of every row touched by at least one counted slot (neither skipped nor bad), m = the number of such slots of
+ * the row (for an item: as positive plus as sampled), lambda = p->lambda:
+ *   new = fp32(old + fp32(lr * fp32(a_c - fp32(fp32(lambda * fp32(m)) * old))));
+ * untouched rows keep their bits.  With batch = 1 this is classical BPR-SGD; a batch is the sum of its slots' steps at
+ * frozen parameters, so lr times the most occurrences of one row in a batch should stay modest: that is the caller's
+ * choice of batch.  Counts of a call: slots, skipped, bad, correct (x > 0 among the counted).
+ *
+ * The sampler is a stateless function of (seed, slot number n = 0, 1, 2, ... over the solver's life).  With
+ *   fin(z): z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9; z = (z ^ (z >> 27)) * 0x94D049BB133111EB; z ^ (z >> 31)
+ *   G = 0x9E3779B97F4A7C15, s0 = fin(seed + G), out(c) = fin(s0 + (c + 1) * G)           (all modulo 2^64):
+ *   p = out(2n) mod nnz, j = out(2n + 1) mod cols, u = the row with csr_row_ptr[u] <= p < csr_row_ptr[u + 1],
+ *   i = csr_col_idx[p]; skipped when j is in row u.
+ * An epoch is nnz slots cut into steps of `batch`; the last step of an epoch is shorter when batch does not divide nnz.
+ *
+ * mfx_bpr_create reads k, lambda, device and profile of *p.  MFX_ERR_INVALID without touching the device: k outside
+ * 1..1024, batch outside 1..2^20, lr or lambda negative or not finite, nnz = 0, cols < 2, a null argument.  Memory on the
+ * device: the factors, 8 bytes beside every factor element (the accumulators), 8 bytes per row and column, the CSR
+ * pointers and ids, 18 bytes per slot of a step.  After create no step's cost grows with rows + cols.
+ * mfx_bpr_set_factors copies W and H (both required); stepping or mfx_bpr_get_factors before it is MFX_ERR_INVALID and
+ * leaves the handle usable.  mfx_bpr_steps runs n_steps steps from the current slot; mfx_bpr_epochs runs n_epochs
+ * epochs, the first of them being the remaining steps of a started epoch; stats [4] (per epoch: [n_epochs][4]) = slots,
+ * skipped, bad, correct of the call (the epoch), seconds (per epoch: [n_epochs]) its stream time; either may be NULL.
+ * mfx_bpr_position: the number of the next slot.  mfx_bpr_kernel_times: stream seconds since create of the sampler, the
+ * gradient kernel, the scatter of the terms and the apply, collected only when p->profile != 0 (it synchronises every step).
+ * mfx_bpr_triples is the sampler on the host (no device is touched): the slots first_slot .. first_slot + count - 1 of
+ * `seed` over the host matrix R; skipped [count] holds 0 / 1.
+ * mfx_bpr_apply is the single operator: one step on the caller's n <= 2^20 triples and host factors, in place.  It has no
+ * matrix: a slot is skipped only where skipped[t] != 0 (skipped = NULL: none); ids are checked on the device
+ * (MFX_ERR_INVALID naming the first slot with u >= rows or an item >= cols; W and H are left as they were).  i == j is
+ * allowed: the row is touched twice by that slot, m counts both, the terms cancel.  The solver's step is the sampler
+ * followed by exactly this code path.
+ * ---------------------------------------------------------------------------------- */
+typedef struct mfx_bpr_s* mfx_bpr_t;
+int mfx_bpr_create(mfx_bpr_t* out, const mfx_csx* R, const mfx_params* p, float lr, int64_t batch, uint64_t seed,
+                   mfx_memspace space);
+int mfx_bpr_set_factors(mfx_bpr_t s, const float* W, const float* H, mfx_memspace space);
+int mfx_bpr_get_factors(mfx_bpr_t s, float* W, float* H, mfx_memspace space);
+int mfx_bpr_steps(mfx_bpr_t s, int64_t n_steps, int64_t stats[4], double* seconds);
+int mfx_bpr_epochs(mfx_bpr_t s, int32_t n_epochs, int64_t* stats /* [n_epochs][4] */, double* seconds /* [n_epochs] */);
+int mfx_bpr_position(mfx_bpr_t s, int64_t* next_slot);
+int mfx_bpr_kernel_times(mfx_bpr_t s, double seconds[4]);
+int mfx_bpr_destroy(mfx_bpr_t s);
+int mfx_bpr_triples(uint64_t seed, int64_t first_slot, int64_t count, const mfx_csx* R, uint32_t* u, uint32_t* i, uint32_t* j,
+                    uint8_t* skipped);
+int mfx_bpr_apply(int64_t rows, int64_t cols, int64_t k, float* W, float* H, int64_t n, const uint32_t* u, const uint32_t* i,
+                  const uint32_t* j, const uint8_t* skipped /* may be NULL */, float lr, float lambda, int64_t stats[4],
+                  int device);
+
+/* ------------------------------------------------------------------------------------
  * Top-N recommendation: a resident handle over trained factors that returns, for each
  * requested user, the n_top highest-scoring items the user must not be excluded from.
  * Score of (u, i) = the fp32 fused multiply-add chain in ascending t: acc = +0, then
