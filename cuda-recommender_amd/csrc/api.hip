@@ -8,6 +8,7 @@
 #include "als_solver.hpp"
 #include "bpr.hpp"
 #include "ccd_solver.hpp"
+#include "knn.hpp"
 #include "recommend.hpp"
 
 namespace mfx {
@@ -443,6 +444,64 @@ int mfx_bpr_triples(uint64_t seed, int64_t first_slot, int64_t count, const mfx_
 int mfx_bpr_apply(int64_t rows, int64_t cols, int64_t k, float* W, float* H, int64_t n, const uint32_t* u, const uint32_t* i,
                   const uint32_t* j, const uint8_t* skipped, float lr, float lambda, int64_t stats[4], int device) {
     return guarded("mfx_bpr_apply", [&]() -> int { return bpr_apply(rows, cols, k, W, H, n, u, i, j, skipped, lr, lambda, stats, device); });
+}
+
+/* ------------------------------------------------------------------ item-kNN: neighbour lists on the interaction matrix */
+int mfx_knn_build(mfx_knn_t* out, const mfx_csx* X, int32_t K, int32_t tile_items, mfx_memspace space, int device) {
+    return guarded("mfx_knn_build", [&]() -> int {
+        MFX_REQUIRE(out, "mfx_knn_build: out is NULL");
+        *out = nullptr;
+        Knn* h = nullptr;
+        MFX_TRY(Knn::build(&h, X, K, tile_items, space, device));
+        *out = new mfx_knn_s{h};
+        return MFX_OK;
+    });
+}
+int mfx_knn_create_from_lists(mfx_knn_t* out, int64_t cols, int32_t K, const uint32_t* nbr_idx, const float* nbr_sim, mfx_memspace space,
+                              int device) {
+    return guarded("mfx_knn_create_from_lists", [&]() -> int {
+        MFX_REQUIRE(out, "mfx_knn_create_from_lists: out is NULL");
+        *out = nullptr;
+        Knn* h = nullptr;
+        MFX_TRY(Knn::from_lists(&h, cols, K, nbr_idx, nbr_sim, space, device));
+        *out = new mfx_knn_s{h};
+        return MFX_OK;
+    });
+}
+int mfx_knn_lists(mfx_knn_t h, uint32_t* nbr_idx, float* nbr_sim, mfx_memspace space) {
+    return guarded("mfx_knn_lists", [&]() -> int {
+        MFX_REQUIRE(h && h->impl, "mfx_knn_lists: null handle");
+        return h->impl->lists(nbr_idx, nbr_sim, space);
+    });
+}
+int mfx_knn_neighbours(mfx_knn_t h, int64_t nq, const uint32_t* items, int32_t n_top, uint32_t* out_items, float* out_sims,
+                       mfx_memspace space) {
+    return guarded("mfx_knn_neighbours", [&]() -> int {
+        MFX_REQUIRE(h && h->impl, "mfx_knn_neighbours: null handle");
+        return h->impl->neighbours(nq, items, n_top, out_items, out_sims, space);
+    });
+}
+int mfx_knn_recommend(mfx_knn_t h, int64_t nusers, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val, int32_t n_top,
+                      int flags, int32_t tile_items, uint32_t* items, float* scores, int64_t* bad_rows, mfx_memspace space) {
+    return guarded("mfx_knn_recommend", [&]() -> int {
+        MFX_REQUIRE(h && h->impl, "mfx_knn_recommend: null handle");
+        return h->impl->recommend(nusers, nnz, ptr, idx, val, n_top, flags, tile_items, items, scores, bad_rows, space);
+    });
+}
+int mfx_knn_times(mfx_knn_t h, double seconds[4]) {
+    return guarded("mfx_knn_times", [&]() -> int {
+        MFX_REQUIRE(h && h->impl && seconds, "mfx_knn_times: null handle or seconds");
+        h->impl->times(seconds);
+        return MFX_OK;
+    });
+}
+int mfx_knn_destroy(mfx_knn_t h) {
+    return guarded("mfx_knn_destroy", [&]() -> int {
+        if (!h) return MFX_OK;
+        delete h->impl;
+        delete h;
+        return MFX_OK;
+    });
 }
 
 int mfx_als_run(const mfx_csx* R, const mfx_coo* T, float* W, float* H, const mfx_params* p,

@@ -16,6 +16,7 @@ MFX_FOLD_ALS, MFX_FOLD_ALS_EXACT, MFX_FOLD_CCD, MFX_FOLD_IMPLICIT = 0, 1, 2, 3  
 MFX_SIM_DOT, MFX_SIM_COSINE = 0, 1  # include/mfx.h mfx_rec_metric
 MFX_CAND_NO_EXCLUDE = 1  # include/mfx.h, flags of mfx_rec_query_candidates
 MFX_DIV_NO_EXCLUDE = 1  # include/mfx.h, flags of mfx_rec_diversify
+MFX_KNN_KEEP_SEEN = 1  # include/mfx.h, flags of mfx_knn_recommend
 
 u32p = C.POINTER(C.c_uint32)
 f32p = C.POINTER(C.c_float)
@@ -138,6 +139,14 @@ SIGNATURES = {
     "mfx_bpr_triples": (C.c_int, [C.c_uint64, C.c_int64, C.c_int64, C.POINTER(mfx_csx), u32p, u32p, u32p, C.c_void_p]),
     "mfx_bpr_apply": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, f32p, f32p, C.c_int64, u32p, u32p, u32p, C.c_void_p, C.c_float,
                                 C.c_float, i64p, C.c_int]),
+    "mfx_knn_build": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(mfx_csx), C.c_int32, C.c_int32, C.c_int, C.c_int]),
+    "mfx_knn_create_from_lists": (C.c_int, [C.POINTER(C.c_void_p), C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
+    "mfx_knn_lists": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    "mfx_knn_neighbours": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int]),
+    "mfx_knn_recommend": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int, C.c_int32,
+                                    C.c_void_p, C.c_void_p, i64p, C.c_int]),
+    "mfx_knn_times": (C.c_int, [C.c_void_p, f64p]),
+    "mfx_knn_destroy": (C.c_int, [C.c_void_p]),
     "mfx_comm_unique_id": (C.c_int, [C.c_void_p]),
     "mfx_comm_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "mfx_comm_create_local": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int]),

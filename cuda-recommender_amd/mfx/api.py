@@ -710,6 +710,183 @@ def bpr_apply(W, H, u, i, j, lr: float, lam: float, skipped=None, device: int = 
 
 
 # ---------------------------------------------------------------------------------------------
+# item-kNN: the neighbourhood model on the interaction matrix (mfx_knn_*)
+# ---------------------------------------------------------------------------------------------
+def knn_weights(R: RatingData, scheme: Optional[str], k1: float = 1.2, b: float = 0.75) -> RatingData:
+    """The interaction matrix R with the values of an item-kNN weighting, both orientations filled alike (pure numpy; the
+    test triplets are carried over).  Every value is computed in fp64 and rounded to fp32 once.  With N = rows, c_i the
+    entries of column i, n_u those of row u and nbar their mean over all rows:
+      "cosine": x = r / ||r_.i||_2;
+      "tfidf":  y = sqrt(r) * (ln N - ln(1 + c_i)), then column-normalised as for cosine;
+      "bm25":   x = r * (k1 + 1) / (k1 * (1 - b + b * n_u / nbar) + r) * (ln N - ln(1 + c_i)), not normalised;
+      None:     the values as they are.
+    A column whose norm is 0 keeps zeros; empty columns stay empty."""
+    if scheme not in ("cosine", "tfidf", "bm25", None):
+        raise ValueError('scheme must be "cosine", "tfidf", "bm25" or None')
+    R.check_types()
+    if scheme is None:
+        return R.copy()
+    cptr = R.csc_col_ptr.astype(np.int64)
+    rptr = R.csr_row_ptr.astype(np.int64)
+    cnt = np.diff(cptr)
+    col = np.repeat(np.arange(R.cols, dtype=np.int64), cnt)
+    row = R.csc_row_idx.astype(np.int64)
+    r = R.csc_val.astype(np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        idf = np.log(np.float64(R.rows)) - np.log(1.0 + cnt.astype(np.float64))
+        if scheme == "bm25":
+            n_u = np.diff(rptr).astype(np.float64)
+            nbar = n_u.sum() / R.rows
+            x = r * (k1 + 1.0) / (k1 * (1.0 - b + b * n_u[row] / nbar) + r) * idf[col]
+        else:
+            y = r if scheme == "cosine" else np.sqrt(r) * idf[col]
+            norm = np.sqrt(np.bincount(col, weights=y * y, minlength=R.cols))
+            x = np.where(norm[col] > 0, y / norm[col], 0.0)
+    x = x.astype(np.float32)
+    to_csr = np.lexsort((col, row))  # the CSC entries in (row, column) order: the CSR side
+    if not np.array_equal(col[to_csr], R.csr_col_idx.astype(np.int64)):
+        raise ValueError("the CSR and CSC sides of R do not hold the same entries in ascending order")
+    out = R.copy()
+    out.csc_val = x
+    out.csr_val = np.ascontiguousarray(x[to_csr])
+    return out
+
+
+class ItemKnn:
+    """Item-kNN on the interaction matrix (mfx_knn_*, include/mfx.h): the K nearest items of every item by the exact
+    fixed-point X^T X of the weighted matrix, and recommendations as sums over the user's own items -- every bit fixed by
+    the data.  R: a RatingData; weighting "cosine" / "tfidf" / "bm25" / None as in knn_weights (k1, b: BM25).
+    device_arrays: the already weighted matrix as a dict of device tensors (mfx.synth_torch) instead of R; weighting must
+    then be None.  tile_items: the test hook of mfx_knn_build."""
+
+    def __init__(self, R: Optional[RatingData], K: int, weighting: Optional[str] = "cosine", k1: float = 1.2, b: float = 0.75,
+                 device: int = 0, device_arrays: Optional[dict] = None, tile_items: int = 0):
+        self.handle = C.c_void_p()
+        self.device, self.K, self.bad_rows = int(device), int(K), 0
+        if device_arrays is not None:
+            if weighting is not None:
+                raise ValueError("device_arrays are taken as they are: pass weighting=None")
+            self.cols = int(device_arrays["cols"])
+            csx, space = _device_csx_coo(device_arrays)[0], L.MFX_DEVICE
+        else:
+            X = knn_weights(R, weighting, k1, b)
+            self.cols = X.cols
+            csx, space = _csx(X), L.MFX_HOST
+        L.check(L.lib().mfx_knn_build(C.byref(self.handle), C.byref(csx), self.K, int(tile_items), space, self.device))
+
+    @classmethod
+    def from_lists(cls, nbr_idx, nbr_sim, device: int = 0) -> "ItemKnn":
+        """A model from given lists nbr_idx [cols][K] (uint32, PAD_ITEM at the tail only) and nbr_sim [cols][K] (float32):
+        numpy arrays, or GPU tensors (the ids as int32 bits)."""
+        if tuple(nbr_idx.shape) != tuple(nbr_sim.shape) or len(nbr_idx.shape) != 2:
+            raise ValueError("nbr_idx and nbr_sim must both be [cols][K]")
+        self = cls.__new__(cls)
+        self.handle = C.c_void_p()
+        self.device, self.bad_rows = int(device), 0
+        self.cols, self.K = int(nbr_idx.shape[0]), int(nbr_idx.shape[1])
+        if _is_dev(nbr_idx) != _is_dev(nbr_sim):
+            raise ValueError("nbr_idx and nbr_sim must both be host arrays or both device tensors")
+        if _is_dev(nbr_idx):
+            assert nbr_idx.is_contiguous() and nbr_idx.element_size() == 4 and nbr_sim.is_contiguous() and nbr_sim.element_size() == 4
+            pi, ps, space = C.c_void_p(int(nbr_idx.data_ptr())), C.c_void_p(int(nbr_sim.data_ptr())), L.MFX_DEVICE
+        else:
+            nbr_idx = np.ascontiguousarray(nbr_idx, np.uint32)
+            nbr_sim = np.ascontiguousarray(nbr_sim, np.float32)
+            pi, ps, space = _vp(nbr_idx), _vp(nbr_sim), L.MFX_HOST
+        L.check(L.lib().mfx_knn_create_from_lists(C.byref(self.handle), self.cols, self.K, pi, ps, space, self.device))
+        return self
+
+    def lists(self):
+        """(nbr_idx uint32 [cols][K], nbr_sim float32 [cols][K]): unused slots hold PAD_ITEM and -inf."""
+        idx = np.empty((self.cols, self.K), np.uint32)
+        sim = np.empty((self.cols, self.K), np.float32)
+        L.check(L.lib().mfx_knn_lists(self.handle, _vp(idx), _vp(sim), L.MFX_HOST))
+        return idx, sim
+
+    def neighbours(self, n_top: int, items=None, on_device: bool = False):
+        """The first n_top <= K stored neighbours of `items` (None: every item in order) -> (ids [Q, n_top], sims
+        [Q, n_top]).  An `items` tensor on the GPU or on_device=True: the results are int32 / float32 tensors on it."""
+        n_top = int(n_top)
+        if _is_dev(items) or on_device:
+            import torch
+            dev = torch.device("cuda", self.device)
+            q = _to_dev32(items, dev) if items is not None else None
+            n = int(q.numel()) if q is not None else self.cols
+            ids = torch.empty((n, n_top), dtype=torch.int32, device=dev)
+            sims = torch.empty((n, n_top), dtype=torch.float32, device=dev)
+            p = lambda t: C.c_void_p(int(t.data_ptr())) if t is not None and t.numel() else None
+            L.check(L.lib().mfx_knn_neighbours(self.handle, n, p(q), n_top, p(ids), p(sims), L.MFX_DEVICE))
+            return ids, sims
+        q = _ids_np(items, "items").astype(np.uint32) if items is not None else None
+        n = int(q.size) if q is not None else self.cols
+        ids = np.empty((n, n_top), np.uint32)
+        sims = np.empty((n, n_top), np.float32)
+        L.check(L.lib().mfx_knn_neighbours(self.handle, n, _vp(q), n_top, _vp(ids), _vp(sims), L.MFX_HOST))
+        return ids, sims
+
+    def recommend(self, rows, n_top: int, keep_seen: bool = False, on_device: bool = False, tile_items: int = 0):
+        """Top-n_top items of the users given by their interactions -> (items [U, n_top], scores [U, n_top]); the rows'
+        own items are left out unless keep_seen.  rows: a RatingData-like CSR (csr_row_ptr / csr_col_idx / csr_val) or a
+        (ptr, idx, val) triple of numpy arrays or GPU tensors, as for Recommender.fold_in.  The number of bad rows (all
+        pads: a term that is not finite or of magnitude >= 64) is left in self.bad_rows.  Tensors in, or on_device=True:
+        the results are tensors on the device (items as int32 holding the uint32 ids)."""
+        ptr, idx, val = (rows.csr_row_ptr, rows.csr_col_idx, rows.csr_val) if hasattr(rows, "csr_row_ptr") else rows
+        if len(ptr.shape) != 1 or ptr.shape[0] < 1 or tuple(idx.shape) != tuple(val.shape) or len(idx.shape) != 1:
+            raise ValueError("rows: ptr [U + 1], idx [nnz], val [nnz]")
+        n, nnz, n_top = int(ptr.shape[0]) - 1, int(idx.shape[0]), int(n_top)
+        flags = L.MFX_KNN_KEEP_SEEN if keep_seen else 0
+        bad = C.c_int64(0)
+        if any(_is_dev(a) for a in (ptr, idx, val)) or on_device:
+            import torch
+            dev = torch.device("cuda", self.device)
+
+            def put(a, dt):
+                if not _is_dev(a):
+                    a = np.ascontiguousarray(a, dt)
+                    a = torch.from_numpy(a.view(np.int32) if dt == np.uint32 else a).to(dev)
+                assert a.is_contiguous() and a.element_size() == 4, "query tensors: contiguous 32-bit"
+                return a
+            keep = [put(ptr, np.uint32), put(idx, np.uint32), put(val, np.float32)]
+            items = torch.empty((n, n_top), dtype=torch.int32, device=dev)
+            scores = torch.empty((n, n_top), dtype=torch.float32, device=dev)
+            p = lambda t: C.c_void_p(int(t.data_ptr())) if t.numel() else None
+            L.check(L.lib().mfx_knn_recommend(self.handle, n, nnz, p(keep[0]), p(keep[1]), p(keep[2]), n_top, flags, int(tile_items),
+                                              p(items), p(scores), C.byref(bad), L.MFX_DEVICE))
+        else:
+            ptr, idx = np.ascontiguousarray(ptr, np.uint32), np.ascontiguousarray(idx, np.uint32)
+            val = np.ascontiguousarray(val, np.float32)
+            items = np.empty((n, n_top), np.uint32)
+            scores = np.empty((n, n_top), np.float32)
+            L.check(L.lib().mfx_knn_recommend(self.handle, n, nnz, _vp(ptr), _vp(idx), _vp(val), n_top, flags, int(tile_items),
+                                              _vp(items), _vp(scores), C.byref(bad), L.MFX_HOST))
+        self.bad_rows = int(bad.value)
+        return items, scores
+
+    def times(self) -> dict:
+        """Seconds of the build (checks and work order, similarity pass) and of recommend summed over the calls (checks, pass)."""
+        out = (C.c_double * 4)()
+        L.check(L.lib().mfx_knn_times(self.handle, out))
+        return dict(zip(("build_checks", "build_pass", "recommend_checks", "recommend_pass"), (float(x) for x in out)))
+
+    def close(self):
+        if self.handle:
+            L.lib().mfx_knn_destroy(self.handle)
+            self.handle = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+# ---------------------------------------------------------------------------------------------
 # single operators (one per reference function on the path)
 # ---------------------------------------------------------------------------------------------
 def _u32(a):

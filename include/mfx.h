@@ -429,6 +429,65 @@ int mfx_bpr_apply(int64_t rows, int64_t cols, int64_t k, float* W, float* H, int
                   int device);
 
 /* ------------------------------------------------------------------------------------
+ * Item-kNN: the neighbourhood model on the interaction matrix itself (Sarwar et al. 2001; cosine, TF-IDF and BM25
+ * weightings as in the usual libraries).  Every bit of the lists and of the scores is fixed by the data: the sums are
+ * exact integer sums, so no order of summation, batch or tile width plays a part.
+ *
+ * Input.  X holds BOTH orientations of the same rows x cols matrix (users x items).  Its values are taken as given: any
+ * weighting is the caller's (mfx.knn_weights in Python).  Every CSR row must hold strictly ascending ids below cols and
+ * every CSC column strictly ascending ids below rows, the pointers ascending from 0 to nnz (mfx/dataset.from_coo produces
+ * this); checked on the device at build, a violation is MFX_ERR_INVALID naming the first such row (column).  That the two
+ * sides hold the same entries is not checked.  rows, cols, nnz < 2^32 - 1.
+ *
+ * Similarity.  For items i != j the term of a user u that holds both is one unfused fp32 multiply t = fp32(x_ui * x_uj).
+ * The term is truncated toward zero to a multiple of 2^-36 (the conversion of csrc/ccd_scatter.hip), the terms of a pair
+ * are added as 64-bit integers, and s_ij = the fp32 nearest to the sum (one rounding int64 -> fp32, ties to even, then the
+ * exact scale).  Hence s_ij and s_ji have the same bits.
+ * Neighbours of i: the items j != i whose integer sum is not 0, ordered by similarity descending, then item ascending;
+ * the first K are kept, 1 <= K <= 1024.  Unused slots hold item 0xFFFFFFFF and similarity -INFINITY, at the tail only.
+ * Storage: nbr_idx [cols][K] and nbr_sim [cols][K].
+ * Limits.  A term that is not finite or of magnitude >= 64, or a column of more than 2^21 entries, makes the build fail
+ * with MFX_ERR_INVALID naming the smallest such item (for a term: the smaller item i of a pair that has one is named by
+ * its own list).  Under these limits no sum reaches 2^27.
+ *
+ * Recommendation for users given by CSR rows of (item i, value x), the form of mfx_rec_fold_in: new users and training
+ * users are the same call.  For every entry and every stored neighbour slot (j, s_ij) of i that is not a pad the term is
+ * fp32(x * s_ij), put on the same 2^-36 grid and added as a 64-bit integer (modulo 2^64) into the accumulator of j; the
+ * score of j is the fp32 of its sum.  Eligible: the items j whose integer sum is not 0 and that are not in the row; with
+ * MFX_KNN_KEEP_SEEN the row's own items stay in.  Order and padding are those of mfx_rec_query, 1 <= n_top <= 1024.
+ * A row is BAD if it has a term that is not finite or of magnitude >= 64, or more than 2^21 entries: it returns all pads
+ * and is counted in *bad_rows (host memory, may be NULL); the other rows of the batch are unaffected.  The rows' pointers
+ * must ascend from 0 to nnz and their ids be strictly ascending and below cols: checked on the device, MFX_ERR_INVALID
+ * naming the first such row.  Every row's result is independent of the batch and of the tile width.
+ *
+ * tile_items: 0 = automatic, min(cols rounded up to 64, M); > 0 forces the width of the accumulator tile (a test hook like
+ * item_slices of mfx_rec_query): a multiple of 64, at most M = 8192 for a selection of up to 512 (K at build, n_top at
+ * recommend), 8128 above.
+ * mfx_knn_create_from_lists makes a handle from given lists (copied).  Checked on the device, MFX_ERR_INVALID naming the
+ * first bad item: ids below cols or pad, pads at the tail only, similarities of real slots finite.  No order is required:
+ * the recommendation sum is order-free.
+ * mfx_knn_lists copies the lists out (either array may be NULL).  mfx_knn_neighbours: the first n_top <= K stored slots of
+ * the queried items (items = NULL: 0 .. nq - 1), out_sims may be NULL; an item >= cols is MFX_ERR_INVALID naming the query.
+ * mfx_knn_times: seconds of the build's checks and work order and of its similarity pass (host clock), and stream seconds
+ * of the checks and of the pass of mfx_knn_recommend summed over the calls.  mfx_knn_destroy(NULL) is 0.
+ * MFX_ERR_INVALID without touching the device: a null argument, K or n_top out of range, nnz = 0 or cols < 2 (build and
+ * from_lists), an unknown memory space or flag, a bad tile_items.  A failed build or from_lists leaves *out NULL.
+ * ---------------------------------------------------------------------------------- */
+typedef struct mfx_knn_s* mfx_knn_t;
+#define MFX_KNN_KEEP_SEEN 1 /* flags of mfx_knn_recommend */
+int mfx_knn_build(mfx_knn_t* out, const mfx_csx* X, int32_t K, int32_t tile_items, mfx_memspace space, int device);
+int mfx_knn_create_from_lists(mfx_knn_t* out, int64_t cols, int32_t K, const uint32_t* nbr_idx, const float* nbr_sim,
+                              mfx_memspace space, int device);
+int mfx_knn_lists(mfx_knn_t h, uint32_t* nbr_idx, float* nbr_sim, mfx_memspace space);
+int mfx_knn_neighbours(mfx_knn_t h, int64_t nq, const uint32_t* items, int32_t n_top, uint32_t* out_items, float* out_sims,
+                       mfx_memspace space);
+int mfx_knn_recommend(mfx_knn_t h, int64_t nusers, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val,
+                      int32_t n_top, int flags, int32_t tile_items, uint32_t* items, float* scores, int64_t* bad_rows,
+                      mfx_memspace space);
+int mfx_knn_times(mfx_knn_t h, double seconds[4]);
+int mfx_knn_destroy(mfx_knn_t h);
+
+/* ------------------------------------------------------------------------------------
  * Top-N recommendation: a resident handle over trained factors that returns, for each
  * requested user, the n_top highest-scoring items the user must not be excluded from.
  * Score of (u, i) = the fp32 fused multiply-add chain in ascending t: acc = +0, then
