@@ -63,6 +63,37 @@ def similarities(X):
     return S
 
 
+def similarity_rows(X, items):
+    """The integer sums of the given items only, int64 [len(items)][cols]: similarities(X)[items] without the dense
+    cols x cols matrix, from the CSC column of each item and the CSR rows of its users.  Raises BadTerm with the smallest of
+    the given items that has a bad term or an over-long column (given every item: the item similarities names)."""
+    items = np.asarray(items, np.int64).reshape(-1)
+    rptr = X.csr_row_ptr.astype(np.int64)
+    cptr = X.csc_col_ptr.astype(np.int64)
+    S = np.zeros((len(items), X.cols), np.int64)
+    bad_item = None
+    for n, i in enumerate(items):
+        c0, c1 = cptr[i], cptr[i + 1]
+        bad = c1 - c0 > MAX_ENTRIES
+        users = X.csc_row_idx[c0:c1].astype(np.int64)
+        lens = rptr[users + 1] - rptr[users]
+        at = np.repeat(rptr[users] - (np.cumsum(lens) - lens), lens) + np.arange(lens.sum())  # every entry of the users' rows
+        j = X.csr_col_idx[at].astype(np.int64)
+        with np.errstate(all="ignore"):
+            t = np.repeat(X.csc_val[c0:c1].astype(_F), lens) * X.csr_val[at].astype(_F)
+        assert t.dtype == _F
+        off = j != i
+        b = _bad(t) & off
+        bad = bad or bool(b.any())
+        if bad:
+            bad_item = int(i) if bad_item is None else min(bad_item, int(i))
+            continue
+        np.add.at(S[n], j[off], to_fixed(t[off]))
+    if bad_item is not None:
+        raise BadTerm(bad_item)
+    return S
+
+
 def top_lists(S, keep):
     """Rows of integer sums -> (ids uint32 [n][keep], values fp32 [n][keep]): the non-zero entries of a row by value
     descending, then item ascending; pads (PAD, -inf) at the tail."""

@@ -111,6 +111,83 @@ def test_reference_refuses_what_the_contract_refuses(mfx):
     assert err.value.item == int(c.csr_col_idx[e])  # (the row's smallest item: every pair with the NaN is bad)
 
 
+def _with_holes_and_signs(mfx):
+    """+-1 values (pairs that meet and cancel), column 3 and row 5 empty."""
+    rng = np.random.default_rng(31)
+    cells = rng.choice(30 * 14, 200, replace=False)
+    r, c = cells // 14, cells % 14
+    keep = (r != 5) & (c != 3)
+    v = (2 * rng.integers(0, 2, 200) - 1).astype(F)
+    return mfx.dataset.from_coo(30, 14, r[keep], c[keep], v[keep])
+
+
+@pytest.mark.parametrize("name", ["small_int", "ratings", "normal", "cosine", "signs"])
+def test_similarity_rows_equal_the_dense_reference(mfx, name):
+    """similarity_rows (the sparse reference of the wide catalogues) against similarities, the reference pinned above: every
+    item at once, a subset in an order of its own with an item twice, one item, and no item."""
+    if name == "signs":
+        X = _with_holes_and_signs(mfx)
+        assert X.csc_col_ptr[3] == X.csc_col_ptr[4]  # an empty column: a row of zeros
+    elif name == "cosine":
+        X = mfx.knn_weights(random_matrix(mfx, 37, 29, 400, 6), "cosine")
+    else:
+        X = random_matrix(mfx, 37, 29, 400, 5, name)
+    S = kx.similarities(X)
+    assert np.array_equal(kx.similarity_rows(X, np.arange(X.cols)), S)
+    sub = np.array([X.cols - 1, 3, 0, 7, 3])
+    got = kx.similarity_rows(X, sub)
+    assert got.dtype == np.int64 and got.shape == (5, X.cols) and np.array_equal(got, S[sub])
+    assert np.array_equal(kx.similarity_rows(X, [3]), S[3:4])
+    assert kx.similarity_rows(X, []).shape == (0, X.cols)
+    if name == "signs":
+        D = np.zeros((X.rows, X.cols), np.int64)
+        D[np.repeat(np.arange(X.rows), np.diff(X.csr_row_ptr.astype(np.int64))), X.csr_col_idx] = 1
+        co = D.T @ D
+        np.fill_diagonal(co, 0)
+        assert np.any((S == 0) & (co > 0))  # pairs that meet but whose terms cancel
+        assert not S[3].any() and not S[:, 3].any()
+    ids, sims = kx.top_lists(kx.similarity_rows(X, sub), 6)
+    want = kx.build(X, 6)
+    assert np.array_equal(ids, want[0][sub]) and np.array_equal(bits(sims), bits(want[1][sub]))
+
+
+def test_similarity_rows_refuse_with_the_same_item(mfx):
+    X = random_matrix(mfx, 20, 12, 100, 8)
+    u = int(np.argmax(np.diff(X.csr_row_ptr.astype(np.int64)) >= 3))
+    e = int(X.csr_row_ptr[u])
+    first, second, third = (int(X.csr_col_idx[e + q]) for q in range(3))
+
+    def put(Y, item, value):  # on both sides
+        Y.csr_val[int(Y.csr_row_ptr[u]) + int(np.nonzero(Y.csr_col_idx[Y.csr_row_ptr[u]:Y.csr_row_ptr[u + 1]] == item)[0][0])] = value
+        c0, c1 = int(Y.csc_col_ptr[item]), int(Y.csc_col_ptr[item + 1])
+        Y.csc_val[c0 + int(np.nonzero(Y.csc_row_idx[c0:c1] == u)[0][0])] = value
+
+    c = X.copy()
+    put(c, second, 9.0)
+    put(c, third, 8.0)  # the term 72 for the pair (second, third) only: with ratings up to 5 every other term stays below 64
+    with pytest.raises(kx.BadTerm) as want:
+        kx.similarities(c)
+    assert want.value.item == second
+    with pytest.raises(kx.BadTerm) as err:
+        kx.similarity_rows(c, np.arange(c.cols))
+    assert err.value.item == want.value.item
+    with pytest.raises(kx.BadTerm) as err:
+        kx.similarity_rows(c, [third, second])  # whatever the order of the items
+    assert err.value.item == second
+    with pytest.raises(kx.BadTerm) as err:
+        kx.similarity_rows(c, [third])  # of the items asked for, the smallest bad one
+    assert err.value.item == third
+    clean = [i for i in range(c.cols) if i not in (second, third)]
+    assert np.array_equal(kx.similarity_rows(c, clean)[:, clean], kx.similarities(X)[np.ix_(clean, clean)])  # the others are served
+    c = X.copy()
+    put(c, second, np.nan)
+    with pytest.raises(kx.BadTerm) as want:
+        kx.similarities(c)
+    with pytest.raises(kx.BadTerm) as err:
+        kx.similarity_rows(c, np.arange(c.cols))
+    assert err.value.item == want.value.item == first  # (the row's smallest item: every pair with the NaN is bad)
+
+
 # ------------------------------------------------------------------------------------------------ the weights
 def _weights_by_loops(R, scheme, k1, b):
     """Entry by entry in Python floats: {(u, i): x}."""
