@@ -445,6 +445,38 @@ int mfx_bpr_apply(int64_t rows, int64_t cols, int64_t k, float* W, float* H, int
                   const uint32_t* j, const uint8_t* skipped, float lr, float lambda, int64_t stats[4], int device) {
     return guarded("mfx_bpr_apply", [&]() -> int { return bpr_apply(rows, cols, k, W, H, n, u, i, j, skipped, lr, lambda, stats, device); });
 }
+int mfx_bpr_create_neg(mfx_bpr_t* out, const mfx_csx* R, const mfx_params* p, float lr, int64_t batch, uint64_t seed, int32_t mode,
+                       int64_t negatives, const float* rank_weight, mfx_memspace space) {
+    return guarded("mfx_bpr_create_neg", [&]() -> int {
+        MFX_REQUIRE(out, "mfx_bpr_create_neg: out is NULL");
+        *out = nullptr;
+        BprSolver* s = nullptr;
+        MFX_TRY(BprSolver::create(&s, R, p, lr, batch, seed, space, "mfx_bpr_create_neg", mode, negatives, rank_weight));
+        *out = new mfx_bpr_s{s};
+        return MFX_OK;
+    });
+}
+int mfx_bpr_trials(uint64_t seed, int64_t first_slot, int64_t count, int64_t negatives, const mfx_csx* R, uint32_t* u, uint32_t* i,
+                   uint32_t* items, uint8_t* member) {
+    return guarded("mfx_bpr_trials", [&]() -> int { return bpr_trials(seed, first_slot, count, negatives, R, u, i, items, member); });
+}
+int mfx_bpr_rank_weights(int64_t cols, int64_t negatives, float* out) {
+    return guarded("mfx_bpr_rank_weights", [&]() -> int { return bpr_rank_weights(cols, negatives, out); });
+}
+int mfx_bpr_apply_neg(int64_t rows, int64_t cols, int64_t k, float* W, float* H, int64_t n, const uint32_t* u, const uint32_t* i,
+                      int64_t negatives, const uint32_t* items, const uint8_t* member, int32_t mode, const float* rank_weight, float lr,
+                      float lambda, int64_t stats[4], uint32_t* j_out, uint32_t* t_out, int device) {
+    return guarded("mfx_bpr_apply_neg", [&]() -> int {
+        return bpr_apply_neg(rows, cols, k, W, H, n, u, i, negatives, items, member, mode, rank_weight, lr, lambda, stats, j_out, t_out, device);
+    });
+}
+int mfx_bpr_trial_stats(mfx_bpr_t s, int64_t out[2]) {
+    return guarded("mfx_bpr_trial_stats", [&]() -> int {
+        MFX_REQUIRE(s && s->impl && out, "null solver or out");
+        s->impl->trial_stats(out);
+        return MFX_OK;
+    });
+}
 
 /* ------------------------------------------------------------------ item-kNN: neighbour lists on the interaction matrix */
 int mfx_knn_build(mfx_knn_t* out, const mfx_csx* X, int32_t K, int32_t tile_items, mfx_memspace space, int device) {

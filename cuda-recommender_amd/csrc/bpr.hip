@@ -18,12 +18,14 @@
 //                  and claim back to their rest state.  Rows nobody touched are neither read nor written, so after create
 //                  no kernel and no memset runs over rows + cols.
 // The factors are read by k_bpr_grad and k_bpr_scatter and written by k_bpr_apply alone: every slot sees the factors of
-// before the step.
+// before the step.  With negative sampling by trials (bpr_neg.hip) k_bpr_trials runs after the sampler and picks
+// j among M trial items; in WARP it also writes g and the state, and k_bpr_grad is left out.
 #include <algorithm>
 #include <cmath>
 #include <memory>
 
 #include "bpr.hpp"
+#include "bpr_device.hpp"
 
 #ifndef MFX_LAUNCH_CHECK
 #define MFX_LAUNCH_CHECK() MFX_HIP(hipGetLastError())
@@ -38,57 +40,8 @@ using f32x4 = __attribute__((ext_vector_type(4))) float;
 constexpr uint32_t kNoClaim = 0xFFFFFFFFu;
 constexpr int64_t kBprMaxBatch = 1 << 20;
 constexpr int kBprThreads = 256;
-constexpr uint8_t kCounted = 0, kSkipped = 1, kBad = 2;
-constexpr uint64_t kGolden = 0x9E3779B97F4A7C15ull;
 
-// ---------------------------------------------------------------------------------------------- the sampler
-__host__ __device__ inline uint64_t bpr_fin(uint64_t z) {  // the splitmix64 finaliser
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-__host__ __device__ inline uint64_t bpr_stream(uint64_t seed) { return bpr_fin(seed + kGolden); }
-__host__ __device__ inline uint64_t bpr_draw(uint64_t s0, uint64_t ctr) { return bpr_fin(s0 + (ctr + 1) * kGolden); }
-
-// Slot n of the stream s0 over the matrix (ptr, idx): the entry p = a mod nnz gives the user (the row that holds p) and the
-// positive item, b mod cols the sampled item, skipped when it is in the row (the search of rec_cand.hpp's excluded()).
-// ptr must be non-decreasing from 0 to nnz: then every read stays inside ptr [rows + 1] and idx [nnz].
-__host__ __device__ inline void bpr_sample(uint64_t s0, uint64_t n, const uint32_t* ptr, const uint32_t* idx, uint32_t rows, uint32_t cols,
-                                           uint32_t nnz, uint32_t* u, uint32_t* i, uint32_t* j, uint8_t* skipped) {
-    const uint32_t p = (uint32_t) (bpr_draw(s0, 2 * n) % nnz);
-    const uint32_t item = (uint32_t) (bpr_draw(s0, 2 * n + 1) % cols);
-    uint32_t lo = 0, hi = rows;  // ptr[lo] <= p < ptr[hi]
-    while (hi - lo > 1) {
-        const uint32_t mid = lo + (hi - lo) / 2;
-        if (ptr[mid] <= p) lo = mid;
-        else hi = mid;
-    }
-    uint32_t a = ptr[lo], b = ptr[lo + 1];
-    const uint32_t end = b;
-    while (a < b) {
-        const uint32_t mid = a + (b - a) / 2;
-        if (idx[mid] < item) a = mid + 1;
-        else b = mid;
-    }
-    *u = lo;
-    *i = idx[p];
-    *j = item;
-    *skipped = a < end && idx[a] == item;
-}
-
-// ---------------------------------------------------------------------------------------------- single fp32 operations
-__device__ __forceinline__ float mul_rn(float a, float b) {
-#pragma clang fp contract(off)
-    return a * b;
-}
-__device__ __forceinline__ float add_rn(float a, float b) {
-#pragma clang fp contract(off)
-    return a + b;
-}
-__device__ __forceinline__ float sub_rn(float a, float b) {
-#pragma clang fp contract(off)
-    return a - b;
-}
+// (the sampler and the single fp32 operations: bpr_device.hpp)
 
 // g = 1 / (1 + e^x), the recipe of include/mfx.h: clamp to +-80, n = rint(x * log2 e), r = (x - n * LN2_HI) - n * LN2_LO,
 // the degree-6 Taylor polynomial of e^r by Horner in separately rounded multiplies and adds, e = ldexp(poly, n) (exact: the
@@ -352,8 +305,10 @@ int BprCore::step(uint32_t n, float lr, float lambda) {
     a.n = n; a.k = (int) k_; a.gs = gs_; a.gsh = __builtin_ctz((unsigned) gs_);
     a.lr = lr; a.lambda = lambda;
     if (profile_) MFX_HIP(hipEventRecord(ev_[1], st_));
-    hipLaunchKernelGGL(k_bpr_grad, dim3(grid_of(n)), dim3(kBprThreads), 0, st_, a);
-    MFX_LAUNCH_CHECK();
+    if (neg_mode_ != MFX_BPR_NEG_WARP) {  // (WARP: k_bpr_trials has written g and the state, its weight is no sigmoid)
+        hipLaunchKernelGGL(k_bpr_grad, dim3(grid_of(n)), dim3(kBprThreads), 0, st_, a);
+        MFX_LAUNCH_CHECK();
+    }
     if (profile_) MFX_HIP(hipEventRecord(ev_[2], st_));
     hipLaunchKernelGGL(k_bpr_scatter, dim3(grid_of((uint64_t) n * gs_)), dim3(kBprThreads), 0, st_, a);
     MFX_LAUNCH_CHECK();
@@ -373,11 +328,12 @@ int BprCore::step(uint32_t n, float lr, float lambda) {
 }
 
 // ---------------------------------------------------------------------------------------------- the solver
-int BprSolver::create(BprSolver** out, const mfx_csx* R, const mfx_params* p, float lr, int64_t batch, uint64_t seed, mfx_memspace space) {
-    const char* fn = "mfx_bpr_create";
+int BprSolver::create(BprSolver** out, const mfx_csx* R, const mfx_params* p, float lr, int64_t batch, uint64_t seed, mfx_memspace space,
+                      const char* fn, int mode, int64_t negatives, const float* rank_weight) {
     MFX_REQUIRE(out && R && p, "%s: null argument", fn);
     *out = nullptr;
     MFX_TRY(check_space(fn, space));
+    MFX_TRY(bpr_check_neg(fn, mode, negatives, rank_weight));
     MFX_REQUIRE(p->k >= 1 && p->k <= 1024, "%s: k must be in [1, 1024] (got %u)", fn, p->k);
     MFX_REQUIRE(batch >= 1 && batch <= kBprMaxBatch, "%s: batch must be in [1, 2^20] (got %lld)", fn, (long long) batch);
     MFX_REQUIRE(std::isfinite(lr) && lr >= 0.f, "%s: lr must be finite and >= 0 (got %g)", fn, (double) lr);
@@ -392,6 +348,7 @@ int BprSolver::create(BprSolver** out, const mfx_csx* R, const mfx_params* p, fl
     MFX_TRY(s->core_.init(R->rows, R->cols, p->k, std::min<int64_t>(batch, R->nnz), p->device));
     s->core_.batch_ = batch;  // (a step never has more than nnz slots: the slot arrays are sized for min(batch, nnz))
     s->core_.profile_ = p->profile != 0;
+    if (mode != MFX_BPR_NEG_UNIFORM) MFX_TRY(s->core_.init_neg(mode, (int) negatives, rank_weight));
     hipStream_t st = s->core_.st_;
     const uint32_t rows = (uint32_t) R->rows;
     MFX_TRY(s->ptr_.alloc((size_t) rows + 1));
@@ -439,7 +396,9 @@ int BprSolver::run(int64_t n_steps, bool to_epoch_end, int64_t stats[4], double*
     MFX_HIP(hipMemsetAsync(core_.stats_.get(), 0, 4 * sizeof(unsigned long long), st));
     hipEvent_t t0 = core_.ev_[5], t1 = core_.ev_[6];
     MFX_HIP(hipEventRecord(t0, st));
-    const uint64_t s0 = bpr_stream(seed_), nnz = (uint64_t) nnz_;
+    const uint64_t s0 = bpr_stream(seed_), s1 = bpr_trial_stream(seed_), nnz = (uint64_t) nnz_;
+    const bool neg = core_.neg_mode_ != MFX_BPR_NEG_UNIFORM;
+    if (neg) MFX_HIP(hipMemsetAsync(core_.tstats_.get(), 0, 2 * sizeof(unsigned long long), st));
     int64_t slots = 0;
     for (int64_t s = 0; to_epoch_end || s < n_steps; ++s) {
         const uint32_t n = (uint32_t) std::min<uint64_t>((uint64_t) core_.batch_, nnz - pos_ % nnz);
@@ -447,15 +406,20 @@ int BprSolver::run(int64_t n_steps, bool to_epoch_end, int64_t stats[4], double*
         hipLaunchKernelGGL(k_bpr_sample, dim3(grid_of(n)), dim3(kBprThreads), 0, st, s0, pos_, n, ptr_.get(), idx_.get(), (uint32_t) core_.rows_,
                            (uint32_t) core_.cols_, (uint32_t) nnz_, core_.u_.get(), core_.i_.get(), core_.j_.get(), core_.skip_.get());
         MFX_LAUNCH_CHECK();
+        if (neg) MFX_TRY(core_.trials(n, nullptr, nullptr, s1, pos_, ptr_.get(), idx_.get()));
         MFX_TRY(core_.step(n, lr_, lambda_));
         pos_ += n;
         slots += n;
         if (to_epoch_end && pos_ % nnz == 0) break;
     }
     MFX_HIP(hipEventRecord(t1, st));
-    unsigned long long h[4] = {0, 0, 0, 0};
+    unsigned long long h[4] = {0, 0, 0, 0}, ht[2] = {0, 0};
     MFX_HIP(hipMemcpyAsync(h, core_.stats_.get(), sizeof(h), hipMemcpyDeviceToHost, st));
+    if (neg) MFX_HIP(hipMemcpyAsync(ht, core_.tstats_.get(), sizeof(ht), hipMemcpyDeviceToHost, st));
     MFX_HIP(hipStreamSynchronize(st));
+    // (uniform: the one trial is chosen unless it is in the row)
+    tstat_[0] += neg ? (int64_t) ht[0] : (int64_t) h[1];
+    tstat_[1] += neg ? (int64_t) ht[1] : slots - (int64_t) h[1];
     float ms = 0.f;
     MFX_HIP(hipEventElapsedTime(&ms, t0, t1));
     if (seconds) *seconds = 1e-3 * ms;

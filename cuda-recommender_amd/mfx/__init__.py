@@ -8,6 +8,7 @@ from .api import PAD_ITEM, PAD_RANK, Recommender, ivf_kmeans, recommend, topn_me
 from .api import ImplicitAlsSolver, ials_half, ials_block_half, ials_cg_half, spd_inverse  # noqa: F401
 from .api import als_block_half  # noqa: F401
 from .api import BprSolver, bpr_apply, bpr_triples  # noqa: F401
+from .api import bpr_apply_neg, bpr_rank_weights, bpr_trials  # noqa: F401
 from .api import ItemKnn, knn_weights  # noqa: F401
 from ._lib import LIB_PATH, MfxError, lib  # noqa: F401
 from ._lib import MFX_KNN_KEEP_SEEN  # noqa: F401

@@ -139,6 +139,13 @@ SIGNATURES = {
     "mfx_bpr_triples": (C.c_int, [C.c_uint64, C.c_int64, C.c_int64, C.POINTER(mfx_csx), u32p, u32p, u32p, C.c_void_p]),
     "mfx_bpr_apply": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, f32p, f32p, C.c_int64, u32p, u32p, u32p, C.c_void_p, C.c_float,
                                 C.c_float, i64p, C.c_int]),
+    "mfx_bpr_create_neg": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(mfx_csx), C.POINTER(mfx_params), C.c_float, C.c_int64, C.c_uint64,
+                                     C.c_int32, C.c_int64, C.c_void_p, C.c_int]),
+    "mfx_bpr_trials": (C.c_int, [C.c_uint64, C.c_int64, C.c_int64, C.c_int64, C.POINTER(mfx_csx), u32p, u32p, u32p, C.c_void_p]),
+    "mfx_bpr_rank_weights": (C.c_int, [C.c_int64, C.c_int64, C.c_void_p]),
+    "mfx_bpr_apply_neg": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, f32p, f32p, C.c_int64, u32p, u32p, C.c_int64, u32p, C.c_void_p,
+                                    C.c_int32, C.c_void_p, C.c_float, C.c_float, i64p, C.c_void_p, C.c_void_p, C.c_int]),
+    "mfx_bpr_trial_stats": (C.c_int, [C.c_void_p, i64p]),
     "mfx_knn_build": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(mfx_csx), C.c_int32, C.c_int32, C.c_int, C.c_int]),
     "mfx_knn_create_from_lists": (C.c_int, [C.POINTER(C.c_void_p), C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
     "mfx_knn_lists": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),

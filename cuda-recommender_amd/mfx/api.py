@@ -598,6 +598,9 @@ class ImplicitAlsSolver(_AlsHandle):
         return {half: {key: int(out[4 * i + j]) for j, key in enumerate(keys)} for i, half in enumerate(("rows", "cols"))}
 
 
+_BPR_LOSS = {"bpr": 1, "warp": 2}  # MFX_BPR_NEG_HARDEST, MFX_BPR_NEG_WARP (include/mfx.h)
+
+
 def _bpr_report(stats, seconds: float) -> dict:
     slots, skipped, bad, correct = (int(x) for x in stats)
     counted = slots - skipped - bad
@@ -611,10 +614,18 @@ class BprSolver:
     whose sums are exact -- so the factors are fixed bit for bit by (R, seed, parameters, batch).  Reads k, lambda_, device
     and profile of `parameters`.  Factors use the ALS layout, W [rows][k] and H [cols][k]; without set_factors the first
     step draws 0.1 * N(0, 1) factors from numpy.random.default_rng(init_seed).  device_arrays: the matrix as a dict of device
-    tensors (mfx.synth_torch); only its CSR pointers and ids are read."""
+    tensors (mfx.synth_torch); only its CSR pointers and ids are read.
+
+    negatives = M > 1 or loss = "warp" samples the negative by M trials per slot scored at the frozen factors
+    (mfx_bpr_create_neg): loss = "bpr" trains against the best-scored trial outside the user's row (hardest of M),
+    loss = "warp" against the first trial that violates the margin of 1, with the step scaled by rank_weight [M] of the
+    number of trials it took (None: bpr_rank_weights(cols, M), LightFM's log weight).  The defaults are the uniform
+    sampler, mfx_bpr_create."""
 
     def __init__(self, R: Optional[RatingData], parameters: parameter, lr: float, batch: int, seed: int = 0,
-                 device_arrays: Optional[dict] = None, init_seed: Optional[int] = None):
+                 device_arrays: Optional[dict] = None, init_seed: Optional[int] = None, negatives: int = 1, loss: str = "bpr",
+                 rank_weight=None):
+        assert loss in _BPR_LOSS, loss
         self.handle = C.c_void_p()
         cp = parameters.to_c()
         if device_arrays is not None:
@@ -624,7 +635,20 @@ class BprSolver:
             self.rows, self.cols, self.k = R.rows, R.cols, int(parameters.k)
             csx, space = _csx(R), L.MFX_HOST
         self._init_seed, self._have_factors = init_seed, False
-        L.check(L.lib().mfx_bpr_create(C.byref(self.handle), C.byref(csx), C.byref(cp), float(lr), int(batch), int(seed), space))
+        if loss == "bpr" and int(negatives) == 1 and rank_weight is None:
+            L.check(L.lib().mfx_bpr_create(C.byref(self.handle), C.byref(csx), C.byref(cp), float(lr), int(batch), int(seed), space))
+        else:
+            rw = None if rank_weight is None else np.ascontiguousarray(rank_weight, np.float32)
+            assert rw is None or rw.shape == (int(negatives),), "rank_weight must hold one weight per trial"
+            L.check(L.lib().mfx_bpr_create_neg(C.byref(self.handle), C.byref(csx), C.byref(cp), float(lr), int(batch), int(seed),
+                                               _BPR_LOSS[loss], int(negatives), _vp(rw), space))
+
+    def trial_stats(self) -> dict:
+        """Since create (mfx_bpr_trial_stats): the slots that ended without a chosen trial and the sum of the chosen trial
+        numbers -- with WARP the trials scored up to the violator."""
+        out = (C.c_int64 * 2)()
+        L.check(L.lib().mfx_bpr_trial_stats(self.handle, out))
+        return {"none_chosen": int(out[0]), "chosen_trial_sum": int(out[1])}
 
     def set_factors(self, W, H):
         _f32c(W, (self.rows, self.k))
@@ -707,6 +731,45 @@ def bpr_apply(W, H, u, i, j, lr: float, lam: float, skipped=None, device: int = 
     L.check(L.lib().mfx_bpr_apply(W.shape[0], H.shape[0], W.shape[1], _f32(W), _f32(H), u.shape[0], _u32(u), _u32(i), _u32(j),
                                   _vp(s), float(lr), float(lam), stats, device))
     return W, H, _bpr_report(stats, 0.0)
+
+
+def bpr_trials(R: RatingData, seed: int, first: int, count: int, negatives: int):
+    """(u, i uint32 [count], items uint32 [count][negatives], member bool [count][negatives]) of the slots first .. first +
+    count - 1 (mfx_bpr_trials: the trial sampler of BprSolver(negatives=...) on the host, no GPU)."""
+    count, m = int(count), int(negatives)
+    u, i = (np.empty(count, np.uint32) for _ in range(2))
+    items = np.empty((count, max(m, 0)), np.uint32)
+    member = np.empty((count, max(m, 0)), np.uint8)
+    csx = _csx(R)
+    L.check(L.lib().mfx_bpr_trials(int(seed), int(first), count, m, C.byref(csx), _u32(u), _u32(i), _u32(items), _vp(member)))
+    return u, i, items, member.astype(bool)
+
+
+def bpr_rank_weights(cols: int, negatives: int) -> np.ndarray:
+    """The default WARP weights (mfx_bpr_rank_weights): out[t - 1] = float32(log(max(1, (cols - 1) // t)))."""
+    out = np.empty(max(int(negatives), 0), np.float32)
+    L.check(L.lib().mfx_bpr_rank_weights(int(cols), int(negatives), _vp(out)))
+    return out
+
+
+def bpr_apply_neg(W, H, u, i, items, lr: float, lam: float, loss: str = "bpr", member=None, rank_weight=None, device: int = 0):
+    """One step on the caller's trials items [n][M] at the factors W [rows][k], H [cols][k] (mfx_bpr_apply_neg): loss "bpr"
+    is hardest of M, "warp" is WARP.  Returns (W', H', report, j, t): j [n] the chosen items and t [n] the chosen trials,
+    0 where none was chosen.  A trial is a member of the user's row only where `member` says so."""
+    W, H = np.array(_f32c(W)), np.array(_f32c(H))
+    assert W.ndim == 2 and H.ndim == 2 and W.shape[1] == H.shape[1]
+    u, i, items = (np.ascontiguousarray(a, np.uint32) for a in (u, i, items))
+    assert u.shape == i.shape and u.ndim == 1 and items.ndim == 2 and items.shape[0] == u.shape[0]
+    n, m = items.shape
+    mem = None if member is None else np.ascontiguousarray(member, np.uint8)
+    assert mem is None or mem.shape == items.shape
+    rw = None if rank_weight is None else np.ascontiguousarray(rank_weight, np.float32)
+    assert rw is None or rw.shape == (m,)
+    stats = (C.c_int64 * 4)()
+    j, t = np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+    L.check(L.lib().mfx_bpr_apply_neg(W.shape[0], H.shape[0], W.shape[1], _f32(W), _f32(H), n, _u32(u), _u32(i), m, _u32(items), _vp(mem),
+                                      _BPR_LOSS[loss], _vp(rw), float(lr), float(lam), stats, _vp(j), _vp(t), device))
+    return W, H, _bpr_report(stats, 0.0), j, t
 
 
 # ---------------------------------------------------------------------------------------------

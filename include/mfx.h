@@ -411,7 +411,48 @@ int mfx_als_block_half(int64_t nseg, int64_t nnz, const uint32_t* ptr, const uin
  * (MFX_ERR_INVALID naming the first slot with u >= rows or an item >= cols; W and H are left as they were).  i == j is
  * allowed: the row is touched twice by that slot, m counts both, the terms cancel.  The solver's step is the sampler
  * followed by exactly this code path.
+ *
+ * Negative sampling by trials (mfx_bpr_create_neg, mfx_bpr_apply_neg).  A slot gets M = `negatives` trial items, 1 <= M <=
+ * 1024, scored at the factors of before the step, and a mode picks one of them as j.  Every bit is fixed by (data, seed,
+ * parameters, batch, M, mode).  Modes: MFX_BPR_NEG_UNIFORM = 0 requires M = 1 and is mfx_bpr_create; MFX_BPR_NEG_HARDEST = 1
+ * (hardest of M, dynamic negative sampling, Zhang et al. 2013); MFX_BPR_NEG_WARP = 2 (Weston et al. 2011).
+ * Trials of slot n: they depend neither on the mode nor on M, so the trials of M are the first M of those of M + 1.
+ *   (u, i) as above; trial 1 is the sampled item above, c_1 = out(2n + 1) mod cols;
+ *   trial t >= 2: c_t = fin(b_n + t * G) mod cols with b_n = fin(s1 + (n + 1) * G), s1 = fin(seed + 2 * G)  (modulo 2^64);
+ *   member_t = 1 when c_t is in row u.
+ * Scores: s_i = the fp32 FMA chain acc = fmaf(W[u][c], H[i][c], acc) over c = 0 .. k-1 from +0 (the chain of
+ * mfx_rec_score), s_t the same chain with H[c_t]; one lane owns a chain, no sum crosses lanes.
+ * HARDEST.  Eligible are the trials with member_t = 0; with none the slot is skipped.  Otherwise j = c_t of the eligible
+ * trial that comes first in this order: a NaN score ranks below every number; then the greater score; then the smaller t
+ * (+0 and -0, and equal infinities, are ties).  The slot (u, i, j) then takes the step above unchanged (d-chain, sigmoid,
+ * bad rule, counts), so M = 1 is mfx_bpr_create bit for bit.
+ * WARP.  If s_i is not finite the slot is bad.  Otherwise t = 1 .. M in order, members passed over: the first trial with
+ * !(fp32(s_i - s_t) >= 1) (one fp32 subtraction, so a NaN s_t violates) is the violator, j = c_t and g = rank_weight[t - 1].
+ * Without a violator the slot is skipped.  It is bad if the violator's s_t is not finite, or unless every term satisfies
+ * |fp32(g * d_c)| < 64 and |fp32(g * W[u][c])| < 64 with d_c = fp32(H[i][c] - H[j][c]) (a NaN is not below 64).  Terms,
+ * fixed point, counts, claim and update are those above with g in place of the sigmoid; a weight of 0 still counts the
+ * slot, so its regularisation applies.  `correct` counts the counted slots with fp32(s_i - s_t) > 0.
+ * Rank weights: rank_weight [M], fp32, each finite and >= 0 (else MFX_ERR_INVALID), read in WARP only.  NULL selects
+ * mfx_bpr_rank_weights(cols, M, out): out[t - 1] = (float) log((double) max(1, (cols - 1) / t)), an integer division
+ * (LightFM's weight: the draws needed estimate the rank of the positive item); filled on the host.
+ * mfx_bpr_create_neg: mfx_bpr_create with a mode; its handle works with every mfx_bpr_* call.  Its refusals and, also
+ * without touching the device: a mode out of range, M outside 1 .. 1024, UNIFORM with M != 1, a bad table.  The trial items
+ * are not stored: 4 more bytes per slot of a step.  mfx_bpr_kernel_times counts the trials kernel under the sampler; in
+ * WARP the gradient kernel does not run.
+ * mfx_bpr_trials is the trial sampler on the host (no device is touched): items and member [count][M] of the slots
+ * first_slot .. first_slot + count - 1, u and i [count] as mfx_bpr_triples gives them.  mfx_bpr_rank_weights: host only;
+ * cols >= 1.
+ * mfx_bpr_apply_neg is the single operator on the caller's trials: items [n][M], member [n][M] (NULL: none; it computes no
+ * membership itself), n <= 2^20, host factors in place; ids are checked on the device as mfx_bpr_apply does (the first
+ * slot with u >= rows, i >= cols or a trial item >= cols is named).  UNIFORM is refused here.  j_out [n] (the chosen item,
+ * undefined where none was chosen) and t_out [n] (the chosen trial, 0 = none) may be NULL.  The solver's step at M > 1 or in
+ * WARP is the two samplers followed by exactly this code path.
+ * mfx_bpr_trial_stats, since create: out[0] = the slots that ended without a chosen trial (HARDEST: no eligible trial;
+ * WARP: no violator, or s_i not finite; UNIFORM: skipped), out[1] = the sum of the chosen trial numbers t.
  * ---------------------------------------------------------------------------------- */
+#define MFX_BPR_NEG_UNIFORM 0
+#define MFX_BPR_NEG_HARDEST 1
+#define MFX_BPR_NEG_WARP 2
 typedef struct mfx_bpr_s* mfx_bpr_t;
 int mfx_bpr_create(mfx_bpr_t* out, const mfx_csx* R, const mfx_params* p, float lr, int64_t batch, uint64_t seed,
                    mfx_memspace space);
@@ -427,6 +468,17 @@ int mfx_bpr_triples(uint64_t seed, int64_t first_slot, int64_t count, const mfx_
 int mfx_bpr_apply(int64_t rows, int64_t cols, int64_t k, float* W, float* H, int64_t n, const uint32_t* u, const uint32_t* i,
                   const uint32_t* j, const uint8_t* skipped /* may be NULL */, float lr, float lambda, int64_t stats[4],
                   int device);
+int mfx_bpr_create_neg(mfx_bpr_t* out, const mfx_csx* R, const mfx_params* p, float lr, int64_t batch, uint64_t seed,
+                       int32_t mode, int64_t negatives, const float* rank_weight /* [negatives] or NULL */, mfx_memspace space);
+int mfx_bpr_trials(uint64_t seed, int64_t first_slot, int64_t count, int64_t negatives, const mfx_csx* R, uint32_t* u,
+                   uint32_t* i, uint32_t* items /* [count][negatives] */, uint8_t* member /* [count][negatives] */);
+int mfx_bpr_rank_weights(int64_t cols, int64_t negatives, float* out /* [negatives] */);
+int mfx_bpr_apply_neg(int64_t rows, int64_t cols, int64_t k, float* W, float* H, int64_t n, const uint32_t* u, const uint32_t* i,
+                      int64_t negatives, const uint32_t* items /* [n][negatives] */, const uint8_t* member /* or NULL: none */,
+                      int32_t mode, const float* rank_weight /* WARP: NULL = default */, float lr, float lambda,
+                      int64_t stats[4], uint32_t* j_out /* [n] or NULL */, uint32_t* t_out /* [n] or NULL, 0 = none chosen */,
+                      int device);
+int mfx_bpr_trial_stats(mfx_bpr_t s, int64_t out[2]);
 
 /* ------------------------------------------------------------------------------------
  * Item-kNN: the neighbourhood model on the interaction matrix itself (Sarwar et al. 2001; cosine, TF-IDF and BM25

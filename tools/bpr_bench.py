@@ -14,10 +14,22 @@ In the same process a torch baseline runs the same batch mathematics -- torch.ra
 user and the membership, index_add_ for the three scatters -- for --torch-steps steps per point: float atomics in arrival
 order, so it is NOT reproducible; its time per slot is scaled to an epoch.
 
-With --parent-pkg DIR (a built cuda-recommender_amd tree of the parent commit): the unchanged all-user query and one
-implicit-ALS iteration (k = 64), each in a fresh process per tree, parent and this tree alternated --regress-runs times.
+With --negatives M[,M...] --loss bpr|warp[,...] every point is run once per (loss, M): negatives = 1 with loss bpr is the
+uniform sampler, negatives > 1 hardest of M, loss warp WARP with the default rank weights (mfx_bpr_create_neg).  The record
+then carries the trials per slot of the timed epoch from trial_stats -- by the contract's sequential definition: M for
+hardest of M; for WARP the chosen trial number, or M where no trial violated -- and the gathered bytes per second of the
+trials kernel, (trials + 1) * k * 4 bytes per slot over the "sample" phase of the profiled steps (which holds the sampler's
+own few microseconds as well, so the figure is a little low), to be read against the rate query_candidates reaches on
+gathered rows of H (GATHER_TBS).  WARP trains at --warp-lr (its rank weight, up to ln(cols - 1), multiplies the step: at the
+lr of the other modes the factors leave the range of the fixed point within an epoch and the slots are counted bad).  The
+kernel scores whole rounds of its lane group, so it gathers somewhat more than the sequential definition counts.  The torch
+baseline runs for the uniform sampler only.
 
-    python tools/bpr_bench.py [--ks 64,128] [--batches 4096,65536,1048576] [--parent-pkg DIR] [--regress-runs 4] [--out FILE]
+With --parent-pkg DIR (a built cuda-recommender_amd tree of the parent commit): the unchanged all-user query, one
+implicit-ALS iteration and one uniform BPR epoch at batch 65 536 (k = 64), each in a fresh process per tree, parent and this tree alternated --regress-runs times.
+
+    python tools/bpr_bench.py [--ks 64,128] [--batches 4096,65536,1048576] [--negatives 1,8,32] [--loss bpr,warp]
+                              [--parent-pkg DIR] [--regress-runs 4] [--out FILE]
 """
 import argparse
 import json
@@ -31,6 +43,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "cuda-recommender_amd")
 FLOAT_ATOMIC_TBS = 1.3  # chip-wide added bytes per second of global FLOAT atomic adds (the guide's figure)
+GATHER_TBS = 4.7        # gathered bytes per second of H rows that query_candidates reaches (README, all users x 1 000)
 
 
 def matrix(a, torch):
@@ -73,16 +86,27 @@ def torch_steps(torch, d, W, H, batch, steps, lr, lam):
     return time.perf_counter() - t0, int(counted)
 
 
-def point(torch, mfx, d, a, k, batch):
+def point(torch, mfx, d, a, k, batch, loss="bpr", negatives=1):
     p = mfx.parameter()
     p.k, p.lambda_ = k, a.lam
     nnz = int(d["csr_val"].numel())
-    rec = {"k": k, "batch": batch, "steps_per_epoch": -(-nnz // batch)}
-    s = mfx.BprSolver(None, p, a.lr, batch, seed=1, device_arrays=d, init_seed=k)
+    uniform = loss == "bpr" and negatives == 1
+    rec = {"k": k, "batch": batch, "loss": loss, "negatives": negatives, "steps_per_epoch": -(-nnz // batch)}
+    neg = {} if uniform else {"negatives": negatives, "loss": loss}
+    lr = a.warp_lr if loss == "warp" else a.lr
+    rec["lr"] = lr
+    s = mfx.BprSolver(None, p, lr, batch, seed=1, device_arrays=d, init_seed=k, **neg)
     s.steps(min(a.warm, max(1, nnz // batch // 4)))
     s.iterate(1)  # (finishes the started epoch: more warm-up, and the next call is a whole epoch)
+    ts0 = s.trial_stats()
     e = s.iterate(1)[0]
+    ts1 = s.trial_stats()
+    trained = None if uniform else s.get_factors()
     s.close()
+    none, tsum = (ts1[key] - ts0[key] for key in ("none_chosen", "chosen_trial_sum"))
+    # (WARP: a slot without a chosen trial went through all M, unless its s_i was no number -- bad slots, none in a sane run)
+    trials = float(negatives) if loss == "bpr" else (tsum + none * negatives) / max(1, e["slots"])
+    rec.update({"none_chosen": none, "mean_chosen_trial": round(tsum / max(1, e["slots"] - none), 3), "trials_per_slot": round(trials, 3)})
     counted = e["slots"] - e["skipped"] - e["bad"]
     rec.update({"seconds_per_epoch": round(e["seconds"], 4), "counted_triples_per_second": round(counted / e["seconds"], 1),
                 "skipped": e["skipped"], "bad": e["bad"], "auc_of_the_epoch": round(e["auc"], 4),
@@ -90,17 +114,28 @@ def point(torch, mfx, d, a, k, batch):
                 "epoch_added_tb_per_s": round(counted * 3 * k * 8 / e["seconds"] / 1e12, 4),
                 "floor_seconds_per_epoch_at_float_atomic_rate": round(counted * 3 * k * 8 / (FLOAT_ATOMIC_TBS * 1e12), 4)})
     p.profile = 1
-    s = mfx.BprSolver(None, p, a.lr, batch, seed=1, device_arrays=d, init_seed=k)
+    s = mfx.BprSolver(None, p, lr, batch, seed=1, device_arrays=d, init_seed=k, **neg)
     n = min(a.profile_steps, rec["steps_per_epoch"])
+    if trained is not None:  # (the trials WARP needs depend on the state of training: profile at the timed epoch's factors)
+        s.set_factors(*trained)
     s.steps(min(3, n))
-    t0 = s.kernel_times()
+    t0, ts0 = s.kernel_times(), s.trial_stats()
     r = s.steps(n)
-    t1 = s.kernel_times()
+    t1, ts1 = s.kernel_times(), s.trial_stats()
     s.close()
     cnt = r["slots"] - r["skipped"] - r["bad"]
     split = {name: (t1[name] - t0[name]) / n for name in t1}
     rec["us_per_step"] = {name: round(v * 1e6, 2) for name, v in split.items()}
     rec["scatter_added_tb_per_s"] = round(cnt * 3 * k * 8 / (split["scatter"] * n) / 1e12, 4) if split["scatter"] > 0 else None
+    if not uniform:
+        none, tsum = (ts1[key] - ts0[key] for key in ("none_chosen", "chosen_trial_sum"))
+        ptrials = float(negatives) if loss == "bpr" else (tsum + none * negatives) / max(1, r["slots"])
+        gathered = r["slots"] * (ptrials + 1) * k * 4
+        rec["profiled_trials_per_slot"] = round(ptrials, 3)
+        rec["trials_gathered_bytes_per_slot"] = round((ptrials + 1) * k * 4, 1)
+        rec["trials_gathered_tb_per_s"] = round(gathered / (split["sample"] * n) / 1e12, 4) if split["sample"] > 0 else None
+        rec["gather_yardstick_tb_per_s"] = GATHER_TBS
+        return rec
     W = torch.randn(int(d["rows"]), k, device="cuda:0") * 0.1
     H = torch.randn(int(d["cols"]), k, device="cuda:0") * 0.1
     ts, tc = torch_steps(torch, d, W, H, batch, min(a.torch_steps, rec["steps_per_epoch"]), a.lr, a.lam)
@@ -123,6 +158,12 @@ def regress_child(a):
     s.iterate(1)
     ials = float(np.median([r.update_time * 1e3 for r in s.iterate(3)]))
     s.close()
+    p.lambda_ = 0.01
+    s = mfx.BprSolver(None, p, 0.05, 65536, seed=1, device_arrays=d, init_seed=64)  # the uniform sampler
+    s.steps(20)
+    s.iterate(1)
+    bpr = s.iterate(1)[0]["seconds"] * 1e3
+    s.close()
     rp, ci = d["csr_row_ptr"].cpu().numpy().view(np.uint32), d["csr_col_idx"].cpu().numpy().view(np.uint32)
     del d
     ex = mfx.dataset.RatingData(a.rows, a.cols, rp, ci, np.zeros(0, np.float32), np.zeros(a.cols + 1, np.uint32),
@@ -140,7 +181,7 @@ def regress_child(a):
             torch.cuda.synchronize()
             if rep:
                 ts.append((time.perf_counter() - t0) * 1e3)
-    print(json.dumps({"query_ms": float(np.median(ts)), "ials_iteration_ms": ials}))
+    print(json.dumps({"query_ms": float(np.median(ts)), "ials_iteration_ms": ials, "bpr_uniform_epoch_ms": bpr}))
 
 
 def main():
@@ -150,7 +191,10 @@ def main():
     ap.add_argument("--nnz", type=int, default=99_072_112)
     ap.add_argument("--ks", default="64,128")
     ap.add_argument("--batches", default="4096,65536,1048576")
+    ap.add_argument("--negatives", default="1", help="trials per slot, comma list; 1 with --loss bpr is the uniform sampler")
+    ap.add_argument("--loss", default="bpr", help="bpr (uniform / hardest of M) and / or warp, comma list")
     ap.add_argument("--lr", type=float, default=0.05)
+    ap.add_argument("--warp-lr", type=float, default=0.005)
     ap.add_argument("--lam", type=float, default=0.01)
     ap.add_argument("--warm", type=int, default=20)
     ap.add_argument("--profile-steps", type=int, default=50)
@@ -165,15 +209,17 @@ def main():
     sys.path.insert(0, PKG)
     import torch
     import mfx
-    out = {"tool": "bpr_bench", "rows": a.rows, "cols": a.cols, "nnz": a.nnz, "lr": a.lr, "lambda": a.lam,
+    out = {"tool": "bpr_bench", "rows": a.rows, "cols": a.cols, "nnz": a.nnz, "lr": a.lr, "warp_lr": a.warp_lr, "lambda": a.lam,
            "float_atomic_tb_per_s_of_the_guide": FLOAT_ATOMIC_TBS, "points": []}
     ks = [int(x) for x in a.ks.split(",") if x]
     if ks:
         d = matrix(a, torch)
         for k in ks:
             for batch in (int(x) for x in a.batches.split(",") if x):
-                out["points"].append(point(torch, mfx, d, a, k, batch))
-                print(json.dumps(out["points"][-1]), file=sys.stderr, flush=True)
+                for loss in (x for x in a.loss.split(",") if x):
+                    for m in (int(x) for x in a.negatives.split(",") if x):
+                        out["points"].append(point(torch, mfx, d, a, k, batch, loss, m))
+                        print(json.dumps(out["points"][-1]), file=sys.stderr, flush=True)
         del d
         torch.cuda.empty_cache()
     if a.parent_pkg:
@@ -185,7 +231,8 @@ def main():
                 p = subprocess.run(cmd, stdout=subprocess.PIPE, text=True, check=True, timeout=600)
                 runs[name].append(json.loads(p.stdout.strip().splitlines()[-1]))
         out["regression"] = {"k": 64}
-        for key, what in (("query_ms", "all-user query, n_top = 10"), ("ials_iteration_ms", "one implicit-ALS iteration")):
+        for key, what in (("query_ms", "all-user query, n_top = 10"), ("ials_iteration_ms", "one implicit-ALS iteration"),
+                          ("bpr_uniform_epoch_ms", "one BPR epoch, uniform sampler, batch 65 536")):
             pr, th = [x[key] for x in runs["parent"]], [x[key] for x in runs["this"]]
             pm, tm = float(np.median(pr)), float(np.median(th))
             spread = max(pr) - min(pr)
