@@ -10,6 +10,7 @@
 #include "ccd_solver.hpp"
 #include "knn.hpp"
 #include "recommend.hpp"
+#include "slim.hpp"
 
 namespace mfx {
 
@@ -529,6 +530,67 @@ int mfx_knn_times(mfx_knn_t h, double seconds[4]) {
 }
 int mfx_knn_destroy(mfx_knn_t h) {
     return guarded("mfx_knn_destroy", [&]() -> int {
+        if (!h) return MFX_OK;
+        delete h->impl;
+        delete h;
+        return MFX_OK;
+    });
+}
+
+/* ------------------------------------------------------------------ SLIM: sparse linear item models on given supports */
+int mfx_slim_train(mfx_slim_t* out, const mfx_csx* X, int32_t K, const uint32_t* support, float l1, float l2, int32_t sweeps, float tol, int flags,
+                   int32_t tile_items, int64_t* failed, mfx_memspace space, int device) {
+    return guarded("mfx_slim_train", [&]() -> int {
+        MFX_REQUIRE(out, "mfx_slim_train: out is NULL");
+        *out = nullptr;
+        Slim* h = nullptr;
+        MFX_TRY(Slim::train(&h, X, K, support, SlimParams{l1, l2, tol, sweeps, flags}, tile_items, failed, space, device));
+        *out = new mfx_slim_s{h};
+        return MFX_OK;
+    });
+}
+int mfx_slim_gram(const mfx_csx* X, int32_t K, const uint32_t* support, int32_t tile_items, float* blocks, mfx_memspace space, int device) {
+    return guarded("mfx_slim_gram", [&]() -> int { return Slim::gram(X, K, support, tile_items, blocks, space, device); });
+}
+int mfx_slim_solve(int64_t n, int32_t K, const float* blocks, const uint32_t* n_real, float l1, float l2, int32_t sweeps, float tol, int flags,
+                   float* w, int32_t* sweeps_used, int64_t* failed, mfx_memspace space, int device) {
+    return guarded("mfx_slim_solve", [&]() -> int {
+        return Slim::solve(n, K, blocks, n_real, SlimParams{l1, l2, tol, sweeps, flags}, w, sweeps_used, failed, space, device);
+    });
+}
+int mfx_slim_create_from_lists(mfx_slim_t* out, int64_t cols, int32_t K, const uint32_t* support, const float* w, mfx_memspace space,
+                               int device) {
+    return guarded("mfx_slim_create_from_lists", [&]() -> int {
+        MFX_REQUIRE(out, "mfx_slim_create_from_lists: out is NULL");
+        *out = nullptr;
+        Slim* h = nullptr;
+        MFX_TRY(Slim::from_lists(&h, cols, K, support, w, space, device));
+        *out = new mfx_slim_s{h};
+        return MFX_OK;
+    });
+}
+int mfx_slim_weights(mfx_slim_t h, uint32_t* support, float* w, int32_t* sweeps_used, mfx_memspace space) {
+    return guarded("mfx_slim_weights", [&]() -> int {
+        MFX_REQUIRE(h && h->impl, "mfx_slim_weights: null handle");
+        return h->impl->weights(support, w, sweeps_used, space);
+    });
+}
+int mfx_slim_recommend(mfx_slim_t h, int64_t nusers, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val, int32_t n_top,
+                       int flags, int32_t tile_items, uint32_t* items, float* scores, int64_t* bad_rows, mfx_memspace space) {
+    return guarded("mfx_slim_recommend", [&]() -> int {
+        MFX_REQUIRE(h && h->impl, "mfx_slim_recommend: null handle");
+        return h->impl->recommend(nusers, nnz, ptr, idx, val, n_top, flags, tile_items, items, scores, bad_rows, space);
+    });
+}
+int mfx_slim_times(mfx_slim_t h, double seconds[5]) {
+    return guarded("mfx_slim_times", [&]() -> int {
+        MFX_REQUIRE(h && h->impl && seconds, "mfx_slim_times: null handle or seconds");
+        h->impl->times(seconds);
+        return MFX_OK;
+    });
+}
+int mfx_slim_destroy(mfx_slim_t h) {
+    return guarded("mfx_slim_destroy", [&]() -> int {
         if (!h) return MFX_OK;
         delete h->impl;
         delete h;

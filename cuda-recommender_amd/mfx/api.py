@@ -815,6 +815,41 @@ def knn_weights(R: RatingData, scheme: Optional[str], k1: float = 1.2, b: float 
     return out
 
 
+def _rows_recommend(call, handle, device: int, rows, n_top: int, keep_seen: bool, on_device: bool, tile_items: int):
+    """The recommendation call shared by ItemKnn and Slim (mfx_knn_recommend / mfx_slim_recommend: one argument list) ->
+    (items, scores, bad_rows)."""
+    ptr, idx, val = (rows.csr_row_ptr, rows.csr_col_idx, rows.csr_val) if hasattr(rows, "csr_row_ptr") else rows
+    if len(ptr.shape) != 1 or ptr.shape[0] < 1 or tuple(idx.shape) != tuple(val.shape) or len(idx.shape) != 1:
+        raise ValueError("rows: ptr [U + 1], idx [nnz], val [nnz]")
+    n, nnz, n_top = int(ptr.shape[0]) - 1, int(idx.shape[0]), int(n_top)
+    flags = L.MFX_KNN_KEEP_SEEN if keep_seen else 0
+    bad = C.c_int64(0)
+    if any(_is_dev(a) for a in (ptr, idx, val)) or on_device:
+        import torch
+        dev = torch.device("cuda", device)
+
+        def put(a, dt):
+            if not _is_dev(a):
+                a = np.ascontiguousarray(a, dt)
+                a = torch.from_numpy(a.view(np.int32) if dt == np.uint32 else a).to(dev)
+            assert a.is_contiguous() and a.element_size() == 4, "query tensors: contiguous 32-bit"
+            return a
+        keep = [put(ptr, np.uint32), put(idx, np.uint32), put(val, np.float32)]
+        items = torch.empty((n, n_top), dtype=torch.int32, device=dev)
+        scores = torch.empty((n, n_top), dtype=torch.float32, device=dev)
+        p = lambda t: C.c_void_p(int(t.data_ptr())) if t.numel() else None
+        L.check(call(handle, n, nnz, p(keep[0]), p(keep[1]), p(keep[2]), n_top, flags, int(tile_items), p(items), p(scores), C.byref(bad),
+                     L.MFX_DEVICE))
+    else:
+        ptr, idx = np.ascontiguousarray(ptr, np.uint32), np.ascontiguousarray(idx, np.uint32)
+        val = np.ascontiguousarray(val, np.float32)
+        items = np.empty((n, n_top), np.uint32)
+        scores = np.empty((n, n_top), np.float32)
+        L.check(call(handle, n, nnz, _vp(ptr), _vp(idx), _vp(val), n_top, flags, int(tile_items), _vp(items), _vp(scores), C.byref(bad),
+                     L.MFX_HOST))
+    return items, scores, int(bad.value)
+
+
 class ItemKnn:
     """Item-kNN on the interaction matrix (mfx_knn_*, include/mfx.h): the K nearest items of every item by the exact
     fixed-point X^T X of the weighted matrix, and recommendations as sums over the user's own items -- every bit fixed by
@@ -893,36 +928,8 @@ class ItemKnn:
         (ptr, idx, val) triple of numpy arrays or GPU tensors, as for Recommender.fold_in.  The number of bad rows (all
         pads: a term that is not finite or of magnitude >= 64) is left in self.bad_rows.  Tensors in, or on_device=True:
         the results are tensors on the device (items as int32 holding the uint32 ids)."""
-        ptr, idx, val = (rows.csr_row_ptr, rows.csr_col_idx, rows.csr_val) if hasattr(rows, "csr_row_ptr") else rows
-        if len(ptr.shape) != 1 or ptr.shape[0] < 1 or tuple(idx.shape) != tuple(val.shape) or len(idx.shape) != 1:
-            raise ValueError("rows: ptr [U + 1], idx [nnz], val [nnz]")
-        n, nnz, n_top = int(ptr.shape[0]) - 1, int(idx.shape[0]), int(n_top)
-        flags = L.MFX_KNN_KEEP_SEEN if keep_seen else 0
-        bad = C.c_int64(0)
-        if any(_is_dev(a) for a in (ptr, idx, val)) or on_device:
-            import torch
-            dev = torch.device("cuda", self.device)
-
-            def put(a, dt):
-                if not _is_dev(a):
-                    a = np.ascontiguousarray(a, dt)
-                    a = torch.from_numpy(a.view(np.int32) if dt == np.uint32 else a).to(dev)
-                assert a.is_contiguous() and a.element_size() == 4, "query tensors: contiguous 32-bit"
-                return a
-            keep = [put(ptr, np.uint32), put(idx, np.uint32), put(val, np.float32)]
-            items = torch.empty((n, n_top), dtype=torch.int32, device=dev)
-            scores = torch.empty((n, n_top), dtype=torch.float32, device=dev)
-            p = lambda t: C.c_void_p(int(t.data_ptr())) if t.numel() else None
-            L.check(L.lib().mfx_knn_recommend(self.handle, n, nnz, p(keep[0]), p(keep[1]), p(keep[2]), n_top, flags, int(tile_items),
-                                              p(items), p(scores), C.byref(bad), L.MFX_DEVICE))
-        else:
-            ptr, idx = np.ascontiguousarray(ptr, np.uint32), np.ascontiguousarray(idx, np.uint32)
-            val = np.ascontiguousarray(val, np.float32)
-            items = np.empty((n, n_top), np.uint32)
-            scores = np.empty((n, n_top), np.float32)
-            L.check(L.lib().mfx_knn_recommend(self.handle, n, nnz, _vp(ptr), _vp(idx), _vp(val), n_top, flags, int(tile_items),
-                                              _vp(items), _vp(scores), C.byref(bad), L.MFX_HOST))
-        self.bad_rows = int(bad.value)
+        items, scores, self.bad_rows = _rows_recommend(L.lib().mfx_knn_recommend, self.handle, self.device, rows, n_top, keep_seen,
+                                                       on_device, tile_items)
         return items, scores
 
     def times(self) -> dict:
@@ -934,6 +941,174 @@ class ItemKnn:
     def close(self):
         if self.handle:
             L.lib().mfx_knn_destroy(self.handle)
+            self.handle = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+# ---------------------------------------------------------------------------------------------
+# SLIM: sparse linear item models on given supports (mfx_slim_*)
+# ---------------------------------------------------------------------------------------------
+def _slim_support(support, cols: int, K: int, on_dev: bool, device: int):
+    """The support [cols][K] of a SLIM call as (pointer, keep-alive): an ItemKnn's ids, a numpy array or a GPU tensor, brought
+    to the side (host / device) where the matrix of the call lives."""
+    if isinstance(support, ItemKnn):
+        if (support.cols, support.K) != (cols, K):
+            raise ValueError(f"support: an ItemKnn of {support.cols} items and K = {support.K}, need {cols} and {K}")
+        if on_dev:
+            import torch
+            t = torch.empty((cols, K), dtype=torch.int32, device=torch.device("cuda", device))
+            L.check(L.lib().mfx_knn_lists(support.handle, C.c_void_p(int(t.data_ptr())), None, L.MFX_DEVICE))
+            return C.c_void_p(int(t.data_ptr())), t
+        support = support.lists()[0]
+    if tuple(support.shape) != (cols, K):
+        raise ValueError(f"support must be [cols = {cols}][K = {K}], got {tuple(support.shape)}")
+    if on_dev:
+        t = _to_dev32(support.reshape(-1), __import__("torch").device("cuda", device))
+        return C.c_void_p(int(t.data_ptr())), t
+    a = support.cpu().numpy().view(np.uint32) if _is_dev(support) else support
+    a = np.ascontiguousarray(a, np.uint32)
+    return _vp(a), a
+
+
+def _slim_matrix(R, weighting, device_arrays):
+    """(mfx_csx, memory space, cols, keep-alive) of the matrix of a SLIM call."""
+    if device_arrays is not None:
+        if weighting is not None:
+            raise ValueError("device_arrays are taken as they are: pass weighting=None")
+        return _device_csx_coo(device_arrays)[0], L.MFX_DEVICE, int(device_arrays["cols"]), device_arrays
+    X = knn_weights(R, weighting)
+    return _csx(X), L.MFX_HOST, X.cols, X
+
+
+def slim_gram(R: Optional[RatingData], K: int, support, weighting: Optional[str] = None, device: int = 0,
+              device_arrays: Optional[dict] = None, tile_items: int = 0):
+    """The Gram blocks [cols][K + 1][K] of mfx_slim_gram (include/mfx.h): for every item j the fixed-point X^T X over its
+    support S_j (rows 0 .. K - 1, d on the diagonal) and against j itself (row K).  A numpy array, or with device_arrays a
+    float32 tensor on the device."""
+    csx, space, cols, keep = _slim_matrix(R, weighting, device_arrays)
+    ps, keep_s = _slim_support(support, cols, int(K), space == L.MFX_DEVICE, device)
+    if space == L.MFX_DEVICE:
+        import torch
+        out = torch.empty((cols, int(K) + 1, int(K)), dtype=torch.float32, device=torch.device("cuda", device))
+        po = C.c_void_p(int(out.data_ptr()))
+    else:
+        out = np.empty((cols, int(K) + 1, int(K)), np.float32)
+        po = _vp(out)
+    L.check(L.lib().mfx_slim_gram(C.byref(csx), int(K), ps, int(tile_items), po, space, device))
+    return out
+
+
+def slim_solve(blocks, n_real=None, l1: float = 1.0, l2: float = 10.0, sweeps: int = 10, tol: float = 0.0, signed: bool = False,
+               device: int = 0):
+    """mfx_slim_solve (include/mfx.h) on blocks [n][K + 1][K] (float32 numpy) with n_real [n] real slots each (None: K) ->
+    (w float32 [n][K], sweeps_used int32 [n], failed)."""
+    blocks = np.ascontiguousarray(blocks, np.float32)
+    if blocks.ndim != 3 or blocks.shape[1] != blocks.shape[2] + 1:
+        raise ValueError("blocks must be [n][K + 1][K]")
+    n, K = int(blocks.shape[0]), int(blocks.shape[2])
+    nr = None
+    if n_real is not None:
+        nr = np.ascontiguousarray(n_real, np.uint32)
+        if nr.shape != (n,):
+            raise ValueError("n_real must be [n]")
+    w = np.empty((n, K), np.float32)
+    used = np.empty(n, np.int32)
+    failed = C.c_int64(0)
+    L.check(L.lib().mfx_slim_solve(n, K, _vp(blocks), _vp(nr), float(l1), float(l2), int(sweeps), float(tol),
+                                   L.MFX_SLIM_SIGNED if signed else 0, _vp(w), _vp(used), C.byref(failed), L.MFX_HOST, device))
+    return w, used, int(failed.value)
+
+
+class Slim:
+    """SLIM on given supports (mfx_slim_*, include/mfx.h): for every item the elastic-net regression of its column on the K
+    columns of its support, trained on the GPU by coordinate descent on the exact fixed-point Gram matrix, and
+    recommendations as sums over the user's own items -- every bit fixed by the data.  R: a RatingData, its values taken
+    under `weighting` (knn_weights; None: as they are).  support: [cols][K] ids (PAD_ITEM at the tail only), an ItemKnn, or
+    None: the ids of ItemKnn(R, K, "cosine").  l1, l2: the penalties; at most `sweeps` sweeps per item, an item stops after
+    the first sweep whose largest change is <= tol; signed: weights of either sign (default: non-negative).
+    device_arrays: the matrix as a dict of device tensors (mfx.synth_torch) instead of R; weighting must then be None and a
+    support be given.  tile_items: the test hook of mfx_slim_train."""
+
+    def __init__(self, R: Optional[RatingData], K: int, l1: float = 1.0, l2: float = 10.0, sweeps: int = 10, tol: float = 0.0,
+                 signed: bool = False, weighting: Optional[str] = None, support=None, device: int = 0,
+                 device_arrays: Optional[dict] = None, tile_items: int = 0):
+        self.handle = C.c_void_p()
+        self.device, self.K, self.bad_rows, self.failed = int(device), int(K), 0, 0
+        if support is None and device_arrays is not None and weighting is None:
+            raise ValueError("device_arrays need a support (an ItemKnn or [cols][K] ids)")
+        csx, space, self.cols, keep = _slim_matrix(R, weighting, device_arrays)
+        if support is None:
+            with ItemKnn(R, self.K, "cosine", device=self.device) as nn:
+                support = nn.lists()[0]
+        ps, keep_s = _slim_support(support, self.cols, self.K, space == L.MFX_DEVICE, self.device)
+        failed = C.c_int64(0)
+        L.check(L.lib().mfx_slim_train(C.byref(self.handle), C.byref(csx), self.K, ps, float(l1), float(l2), int(sweeps), float(tol),
+                                       L.MFX_SLIM_SIGNED if signed else 0, int(tile_items), C.byref(failed), space, self.device))
+        self.failed = int(failed.value)
+
+    @classmethod
+    def from_lists(cls, support, w, device: int = 0) -> "Slim":
+        """A model from a support [cols][K] (uint32, PAD_ITEM at the tail only) and weights w [cols][K] (float32): numpy
+        arrays, or GPU tensors (the ids as int32 bits)."""
+        if tuple(support.shape) != tuple(w.shape) or len(support.shape) != 2:
+            raise ValueError("support and w must both be [cols][K]")
+        if _is_dev(support) != _is_dev(w):
+            raise ValueError("support and w must both be host arrays or both device tensors")
+        self = cls.__new__(cls)
+        self.handle = C.c_void_p()
+        self.device, self.bad_rows, self.failed = int(device), 0, 0
+        self.cols, self.K = int(support.shape[0]), int(support.shape[1])
+        if _is_dev(support):
+            assert support.is_contiguous() and support.element_size() == 4 and w.is_contiguous() and w.element_size() == 4
+            ps, pw, space = C.c_void_p(int(support.data_ptr())), C.c_void_p(int(w.data_ptr())), L.MFX_DEVICE
+        else:
+            support = np.ascontiguousarray(support, np.uint32)
+            w = np.ascontiguousarray(w, np.float32)
+            ps, pw, space = _vp(support), _vp(w), L.MFX_HOST
+        L.check(L.lib().mfx_slim_create_from_lists(C.byref(self.handle), self.cols, self.K, ps, pw, space, self.device))
+        return self
+
+    def weights(self):
+        """(support uint32 [cols][K], w float32 [cols][K]): unused slots hold PAD_ITEM and 0."""
+        sup = np.empty((self.cols, self.K), np.uint32)
+        w = np.empty((self.cols, self.K), np.float32)
+        L.check(L.lib().mfx_slim_weights(self.handle, _vp(sup), _vp(w), None, L.MFX_HOST))
+        return sup, w
+
+    @property
+    def sweeps_used(self) -> np.ndarray:
+        """int32 [cols]: the sweeps every item ran (0 for a model from lists)."""
+        used = np.empty(self.cols, np.int32)
+        L.check(L.lib().mfx_slim_weights(self.handle, None, None, _vp(used), L.MFX_HOST))
+        return used
+
+    def recommend(self, rows, n_top: int, keep_seen: bool = False, on_device: bool = False, tile_items: int = 0):
+        """Top-n_top items of the users given by their interactions, as ItemKnn.recommend: the score of j is the sum of
+        x_i * w_ij over the row's items i whose weight for j is stored.  The number of bad rows is left in self.bad_rows."""
+        items, scores, self.bad_rows = _rows_recommend(L.lib().mfx_slim_recommend, self.handle, self.device, rows, n_top, keep_seen,
+                                                       on_device, tile_items)
+        return items, scores
+
+    def times(self) -> dict:
+        """Seconds of the training (checks and inverse lists, Gram pass, solve) and of recommend summed over the calls."""
+        out = (C.c_double * 5)()
+        L.check(L.lib().mfx_slim_times(self.handle, out))
+        return dict(zip(("train_checks", "gram_pass", "solve", "recommend_checks", "recommend_pass"), (float(x) for x in out)))
+
+    def close(self):
+        if self.handle:
+            L.lib().mfx_slim_destroy(self.handle)
             self.handle = C.c_void_p()
 
     def __enter__(self):

@@ -540,6 +540,74 @@ int mfx_knn_times(mfx_knn_t h, double seconds[4]);
 int mfx_knn_destroy(mfx_knn_t h);
 
 /* ------------------------------------------------------------------------------------
+ * SLIM on given supports (Ning & Karypis 2011, the feature-selected form "fsSLIM"): the learned item-item model.  For every
+ * item j the column x_.j is regressed on the K columns of its support S_j with an elastic-net penalty,
+ *   minimise over w:  1/2 ||x_.j - X_S w||^2 + l2 / 2 ||w||^2 + l1 ||w||_1   (w >= 0 unless MFX_SLIM_SIGNED),
+ * by covariance-update coordinate descent on the Gram matrix of the support.  Every bit of the Gram entries, of the weights
+ * and of the scores is fixed by the data and this text: no bit depends on lanes per item, the workgroup shape, the tile
+ * width or the batch.
+ *
+ * Input.  X as for item-kNN (both orientations, values as given, the same structure checks, rows, cols, nnz < 2^32 - 1).
+ * support [cols][K], 1 <= K <= 128, cols * K < 2^32 - 1: the ids of list j are distinct, below cols and never j itself; unused slots hold
+ * 0xFFFFFFFF, at the tail only.  Checked on the device, MFX_ERR_INVALID naming the smallest bad item.  n_j is the number of
+ * real slots of list j.
+ *
+ * Gram.  For items a != b, G_ab is the item-kNN similarity s_ab above: the fp32 terms fp32(x_ua * x_ub), truncated to the
+ * 2^-36 grid, added as 64-bit integers, and the fp32 nearest to the sum.  d_a is the same sum over the terms
+ * fp32(x_ua * x_ua).  A term (of a pair or of a diagonal) that is not finite or of magnitude >= 64, or a column of more
+ * than 2^21 entries, is MFX_ERR_INVALID naming the smallest such item, as for item-kNN; every item's row is formed, whether
+ * a list names the item or not.  The block of item j is [K + 1][K] fp32: entry (p, t) for p, t < n_j is G of the pair
+ * (S_j[p], S_j[t]), with d on the diagonal; row K holds g_t = G of the pair (j, S_j[t]); everything else is +0.  G is
+ * symmetric in bits, and with S the lists of an item-kNN build of the same X, row K equals that build's nbr_sim.
+ *
+ * Solve of one block with n real slots: w = 0 and c = g, then sweeps; a sweep visits a = 0 .. n - 1 in order:
+ *   den = fp32(d_a + l2); unless den > 0 the coordinate is skipped;
+ *   z = fma(d_a, w_a, c_a);
+ *   r = fp32(z - l1), t = r if r > 0 else +0;  MFX_SLIM_SIGNED: r = fp32(|z| - l1), t = copysign(r if r > 0 else +0, z);
+ *   v = fp32(t / den) (correctly rounded), delta = fp32(v - w_a);
+ *   a delta that is not finite ends the item: its weights are stored as zeros, its sweep count as 0, and it is counted in
+ *   *failed (a block formed from X has finite entries; this concerns blocks handed to the stand-alone solve);
+ *   if delta != 0: c_b = fma(-delta, G_ab, c_b) for every b < n (b = a included), then w_a = v.
+ * m is the largest |delta| of the sweep.  The item stops after the first sweep with m <= tol, or after `sweeps` sweeps; the
+ * number of sweeps it ran is kept per item.  Slots n .. K - 1 of w hold +0.
+ *
+ * Model: support, w [cols][K], the sweep counts, and the transpose by source item: for every i the pairs (j, w_ij) with i
+ * in S_j.  Recommendation is that of item-kNN over the transpose: for every entry (i, x) of a query row and every stored
+ * (j, w) of source i the term fp32(x * w) goes on the 2^-36 grid into the 64-bit integer of j; eligible are the j whose sum
+ * is not 0 and that are not in the row (MFX_KNN_KEEP_SEEN: the row's own items stay in); order, padding, bad rows
+ * (*bad_rows), the checks of the rows, n_top <= 1024 and tile_items as for the item-kNN recommendation.
+ *
+ * The calls.  train: checks, Gram blocks of every item in a workspace of cols * (K + 1) * K * 4 bytes (MFX_ERR_ALLOC stating
+ * the size when it cannot be had), solve, transpose.  *failed (host memory, may be NULL) receives the count of failed items.
+ * tile_items: the test hook of the item-kNN build, for a selection of K.  gram: the blocks alone, [cols][K + 1][K].
+ * solve: n blocks [n][K + 1][K] and their real-slot counts n_real [n] (NULL: K each; a count above K is taken as K) ->
+ * w [n][K], sweeps_used [n], *failed; it reads no X, so any matrices may be handed in.
+ * create_from_lists: a model from a support and weights (copied; the support checked as above, weights of real slots must
+ * be finite; sweep counts 0).  weights: copies support, w and the sweep counts out (any may be NULL).
+ * times: seconds of train's checks and inverse lists, of its Gram pass and of its solve (host clock), and stream seconds of
+ * the checks and of the pass of the recommendation summed over the calls.  destroy of NULL is 0.
+ * Parameters: l1, l2, tol finite and >= 0, sweeps >= 1, flags 0 or MFX_SLIM_SIGNED.  MFX_ERR_INVALID without touching the
+ * device: a null argument, K, n_top or a parameter out of range, nnz = 0 or cols < 2, an unknown memory space or flag, a bad
+ * tile_items.  A failed train or create_from_lists leaves *out NULL.
+ * ---------------------------------------------------------------------------------- */
+typedef struct mfx_slim_s* mfx_slim_t;
+#define MFX_SLIM_SIGNED 1 /* flags of mfx_slim_train and mfx_slim_solve */
+int mfx_slim_train(mfx_slim_t* out, const mfx_csx* X, int32_t K, const uint32_t* support, float l1, float l2, int32_t sweeps,
+                   float tol, int flags, int32_t tile_items, int64_t* failed, mfx_memspace space, int device);
+int mfx_slim_gram(const mfx_csx* X, int32_t K, const uint32_t* support, int32_t tile_items, float* blocks, mfx_memspace space,
+                  int device);
+int mfx_slim_solve(int64_t n, int32_t K, const float* blocks, const uint32_t* n_real, float l1, float l2, int32_t sweeps,
+                   float tol, int flags, float* w, int32_t* sweeps_used, int64_t* failed, mfx_memspace space, int device);
+int mfx_slim_create_from_lists(mfx_slim_t* out, int64_t cols, int32_t K, const uint32_t* support, const float* w,
+                               mfx_memspace space, int device);
+int mfx_slim_weights(mfx_slim_t h, uint32_t* support, float* w, int32_t* sweeps_used, mfx_memspace space);
+int mfx_slim_recommend(mfx_slim_t h, int64_t nusers, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val,
+                       int32_t n_top, int flags, int32_t tile_items, uint32_t* items, float* scores, int64_t* bad_rows,
+                       mfx_memspace space);
+int mfx_slim_times(mfx_slim_t h, double seconds[5]);
+int mfx_slim_destroy(mfx_slim_t h);
+
+/* ------------------------------------------------------------------------------------
  * Top-N recommendation: a resident handle over trained factors that returns, for each
  * requested user, the n_top highest-scoring items the user must not be excluded from.
  * Score of (u, i) = the fp32 fused multiply-add chain in ascending t: acc = +0, then
