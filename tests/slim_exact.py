@@ -3,7 +3,9 @@
 The Gram entries are the item-kNN similarities of knn_exact (fp32 terms cut to the 2^-36 grid, int64 sums, the fp32 nearest to
 the sum) plus the same sum over the squares on the diagonal; the solve is the covariance-update coordinate descent in fp32,
 one rounding per operation in the order the contract gives (fused multiply-adds by rec_exact.fmaf32); the recommendation
-adds fp32 terms as int64 over the transposed weights and ranks with knn_exact.top_lists.  Nothing here calls the library."""
+adds fp32 terms as int64 over the transposed weights and ranks with knn_exact.top_lists.  gram_blocks_sparse gives the blocks
+of gram_blocks from the pairs the support names alone (pair_sums), for catalogues whose dense cols x cols sums do not fit.
+Nothing here calls the library."""
 import numpy as np
 
 import knn_exact as kx
@@ -31,15 +33,16 @@ def check_support(S, cols, w=None):
     """Raises BadSupport with the smallest item whose list has an id >= cols, its own item, a duplicate, a pad before a real
     slot or (given weights) a weight of a real slot that is not finite."""
     S = np.asarray(S, np.uint32)
-    for j in range(S.shape[0]):
-        real = S[j] != PAD
-        n = int(real.sum())
-        ids = S[j][real].astype(np.int64)
-        bad = real[:n].sum() != n or np.any(ids >= cols) or np.any(ids == j) or len(np.unique(ids)) != n
-        if w is not None and not bad:
-            bad = not np.all(np.isfinite(np.asarray(w, _F)[j][real]))
-        if bad:
-            raise BadSupport(j)
+    K = S.shape[1]
+    real = S != PAD
+    ids = np.where(real, S.astype(np.int64), -1 - np.arange(K, dtype=np.int64)[None, :])  # (pads: distinct, equal to no id)
+    bad = (real != (np.arange(K)[None, :] < real.sum(axis=1)[:, None])).any(axis=1)        # a pad before a real slot
+    bad |= (ids >= cols).any(axis=1) | (ids == np.arange(S.shape[0])[:, None]).any(axis=1)
+    bad |= (np.diff(np.sort(ids, axis=1), axis=1) == 0).any(axis=1)
+    if w is not None:
+        bad |= (real & ~np.isfinite(np.asarray(w, _F))).any(axis=1)
+    if bad.any():
+        raise BadSupport(int(np.argmax(bad)))
 
 
 def diagonal(X):
@@ -86,6 +89,82 @@ def gram_blocks(X, S, sums=None):
         ids = S[j, :n[j]].astype(np.int64)
         B[j, :n[j], :n[j]] = kx.from_fixed(G[np.ix_(ids, ids)])
         B[j, K, :n[j]] = kx.from_fixed(G[j, ids])
+    return B
+
+
+def pair_sums(X, a, b, chunk=1 << 22):
+    """int64 [len(a)]: for every pair (a[n], b[n]) the sum of to_fixed(fp32(x_ua * x_ub)) over the users u that hold both
+    items -- the entries of gram_sums(X) at (a, b) without the dense matrix.  The users of column a come from the CSC side;
+    (u, b) is looked up in the sorted CSR keys u * cols + col.  Raises kx.BadTerm with the smallest item of a pair that has a
+    term which is not finite or of magnitude >= 64.  chunk: entries of the columns a handled at a time."""
+    a = np.asarray(a, np.int64).reshape(-1)
+    b = np.asarray(b, np.int64).reshape(-1)
+    assert a.shape == b.shape
+    cols = np.int64(X.cols)
+    cptr = X.csc_col_ptr.astype(np.int64)
+    keys = np.repeat(np.arange(X.rows, dtype=np.int64), np.diff(X.csr_row_ptr.astype(np.int64))) * cols + X.csr_col_idx.astype(np.int64)
+    assert np.all(np.diff(keys) > 0)
+    out = np.zeros(len(a), np.int64)
+    ends = np.cumsum(cptr[a + 1] - cptr[a])
+    bad_item = None
+    lo = 0
+    while lo < len(a):
+        hi = max(lo + 1, int(np.searchsorted(ends, (ends[lo - 1] if lo else 0) + chunk, side="right")))
+        lens = cptr[a[lo:hi] + 1] - cptr[a[lo:hi]]
+        at = np.repeat(cptr[a[lo:hi]] - (np.cumsum(lens) - lens), lens) + np.arange(lens.sum())  # every entry of the columns a
+        pair = np.repeat(np.arange(lo, hi), lens)
+        want = X.csc_row_idx[at].astype(np.int64) * cols + b[pair]
+        pos = np.minimum(np.searchsorted(keys, want), len(keys) - 1)
+        hit = keys[pos] == want
+        with np.errstate(all="ignore"):
+            t = X.csc_val[at][hit].astype(_F) * X.csr_val[pos[hit]].astype(_F)
+            bad = ~(np.abs(t) < kx.TERM_LIMIT)
+        assert t.dtype == _F
+        pair = pair[hit]
+        if bad.any():
+            m = int(min(a[pair[bad]].min(), b[pair[bad]].min()))
+            bad_item = m if bad_item is None else min(bad_item, m)
+        with np.errstate(all="ignore"):
+            np.add.at(out, pair[~bad], kx.to_fixed(t[~bad]))
+        lo = hi
+    if bad_item is not None:
+        raise kx.BadTerm(bad_item)
+    return out
+
+
+def gram_blocks_sparse(X, S):
+    """gram_blocks(X, S) without gram_sums: only the pairs that S names are summed (pair_sums, every unordered pair once:
+    the terms commute), the diagonal comes from diagonal().  For catalogues whose cols x cols matrix does not fit.  A bad
+    term is looked for only where S looks (and on every diagonal), an over-long column everywhere."""
+    S = np.asarray(S, np.uint32)
+    cols, K = S.shape
+    assert cols == X.cols and 1 <= K <= MAX_K
+    check_support(S, cols)
+    bad = []
+    counts = np.diff(X.csc_col_ptr.astype(np.int64))
+    if np.any(counts > kx.MAX_ENTRIES):
+        bad.append(int(np.nonzero(counts > kx.MAX_ENTRIES)[0][0]))
+    d, bad_d = diagonal(X)
+    if bad_d is not None:
+        bad.append(bad_d)
+    real = S != PAD
+    ids = np.where(real, S, 0).astype(np.int64)
+    j, p, t = np.nonzero(real[:, :, None] & real[:, None, :] & ~np.eye(K, dtype=bool)[None])  # the off-diagonal cells of the blocks
+    gj, gp = np.nonzero(real)                                                                  # the cells of row K
+    one = np.concatenate([ids[j, p], gj])
+    two = np.concatenate([ids[j, t], ids[gj, gp]])
+    key, inv = np.unique(np.minimum(one, two) * np.int64(cols) + np.maximum(one, two), return_inverse=True)
+    try:
+        sums = pair_sums(X, key // cols, key % cols)
+    except kx.BadTerm as e:
+        bad.append(e.item)
+    if bad:
+        raise kx.BadTerm(min(bad))
+    v = kx.from_fixed(sums)[inv.reshape(-1)]
+    B = np.zeros((cols, K + 1, K), _F)
+    B[j, p, t] = v[:len(j)]
+    B[gj, gp, gp] = kx.from_fixed(d[ids[gj, gp]])
+    B[gj, K, gp] = v[len(j):]
     return B
 
 

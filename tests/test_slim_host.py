@@ -98,6 +98,59 @@ def test_reference_gram_is_symmetric_in_bits_and_its_last_row_is_the_knn_similar
     assert np.all(np.abs(d - 1.0) < 1e-5)  # unit columns
 
 
+def without_column(mfx, X, c):
+    r = np.repeat(np.arange(X.rows), np.diff(X.csr_row_ptr.astype(np.int64)))
+    keep = X.csr_col_idx != c
+    return mfx.dataset.from_coo(X.rows, X.cols, r[keep], X.csr_col_idx[keep], X.csr_val[keep])
+
+
+def test_sparse_reference_gram_equals_the_dense_one_in_bits(mfx):
+    """gram_blocks_sparse (pair by pair, for catalogues too wide for gram_sums) against gram_blocks: ratings, small integers
+    of both signs that cancel (and explicit zeros), an empty column; lists with pads, one all pads, full lists at K = 1, 6
+    and 28; and the 50 x 700 matrix of the GPU suite with its hub item, unused item and empty column."""
+    from test_gpu_slim import _hub_matrix, _hub_support
+    cases = []
+    for values, seed in (("ratings", 6), ("small_int", 5)):
+        X = random_matrix(mfx, 37, 29, 400, seed, values)
+        for K in (1, 6, 28):
+            S = random_support(29, K, 30 + K)
+            S[7, :] = PAD
+            cases += [(X, S), (X, random_support(29, K, 40 + K, pads=False))]
+        E = without_column(mfx, X, 5)
+        assert E.csc_col_ptr[5] == E.csc_col_ptr[6]
+        S = random_support(29, 6, 50, pads=False)
+        assert np.any(S == 5)
+        cases.append((E, S))
+    small_int = sx.gram_sums(cases[-1][0])
+    assert (small_int[~np.eye(29, dtype=bool)] == 0).sum() > 0  # pairs that meet and cancel, or never meet
+    H = _hub_matrix(mfx)
+    assert H.cols == 700 and H.csc_col_ptr[5] == H.csc_col_ptr[6]
+    cases.append((H, _hub_support()))
+    for X, S in cases:
+        want = sx.gram_blocks(X, S)
+        got = sx.gram_blocks_sparse(X, S)
+        assert got.shape == want.shape and got.dtype == want.dtype == F and np.array_equal(bits(got), bits(want))
+        assert want.any()
+    X, S = cases[0]
+    a, b = np.divmod(np.arange(29 * 29), 29)
+    assert np.array_equal(sx.pair_sums(X, a, b, chunk=100).reshape(29, 29), sx.gram_sums(X))  # every pair, in many chunks
+    c = X.copy()
+    e = int(c.csc_col_ptr[4])
+    u = int(c.csc_row_idx[e])
+    c.csc_val[e] = 9.0  # 81 on the diagonal of item 4 alone
+    r0, r1 = int(c.csr_row_ptr[u]), int(c.csr_row_ptr[u + 1])
+    c.csr_val[r0 + int(np.nonzero(c.csr_col_idx[r0:r1] == 4)[0][0])] = 9.0
+    with pytest.raises(kx.BadTerm) as err:
+        sx.gram_blocks_sparse(c, S)
+    assert err.value.item == 4
+    c.csc_val[e] = c.csr_val[r0 + int(np.nonzero(c.csr_col_idx[r0:r1] == 4)[0][0])] = 70.0  # and 70 * rating >= 64 with every pair
+    with pytest.raises(kx.BadTerm) as err:
+        sx.pair_sums(c, a, b)
+    with pytest.raises(kx.BadTerm) as dense:
+        sx.gram_sums(c)
+    assert err.value.item == dense.value.item
+
+
 def psd_blocks(N, K, seed, rows=40):
     """N random blocks: G = A^T A of a rows x K matrix of small entries, g = A^T y."""
     rng = np.random.default_rng(seed)
