@@ -11,6 +11,7 @@
 #include "knn.hpp"
 #include "recommend.hpp"
 #include "slim.hpp"
+#include "ease.hpp"
 
 namespace mfx {
 
@@ -591,6 +592,65 @@ int mfx_slim_times(mfx_slim_t h, double seconds[5]) {
 }
 int mfx_slim_destroy(mfx_slim_t h) {
     return guarded("mfx_slim_destroy", [&]() -> int {
+        if (!h) return MFX_OK;
+        delete h->impl;
+        delete h;
+        return MFX_OK;
+    });
+}
+
+/* ------------------------------------------------------------------ EASE: closed-form dense item-item models */
+int mfx_ease_gram(const mfx_csx* X, float lambda, int32_t tile_items, float* G, mfx_memspace space, int device) {
+    return guarded("mfx_ease_gram", [&]() -> int { return Ease::gram(X, lambda, tile_items, G, space, device); });
+}
+int mfx_ease_inverse(int64_t n, const float* A, float* Ainv, int flags, mfx_memspace space, int device) {
+    return guarded("mfx_ease_inverse", [&]() -> int { return Ease::inverse(n, A, Ainv, flags, space, device); });
+}
+int mfx_ease_weights_from_inverse(int64_t n, const float* P, float* B, mfx_memspace space, int device) {
+    return guarded("mfx_ease_weights_from_inverse", [&]() -> int { return Ease::weights_from_inverse(n, P, B, space, device); });
+}
+int mfx_ease_train(mfx_ease_t* out, const mfx_csx* X, float lambda, int flags, int32_t tile_items, mfx_memspace space, int device) {
+    return guarded("mfx_ease_train", [&]() -> int {
+        MFX_REQUIRE(out, "mfx_ease_train: out is NULL");
+        *out = nullptr;
+        Ease* h = nullptr;
+        MFX_TRY(Ease::train(&h, X, lambda, flags, tile_items, space, device));
+        *out = new mfx_ease_s{h};
+        return MFX_OK;
+    });
+}
+int mfx_ease_create_from_weights(mfx_ease_t* out, int64_t cols, const float* B, mfx_memspace space, int device) {
+    return guarded("mfx_ease_create_from_weights", [&]() -> int {
+        MFX_REQUIRE(out, "mfx_ease_create_from_weights: out is NULL");
+        *out = nullptr;
+        Ease* h = nullptr;
+        MFX_TRY(Ease::from_weights(&h, cols, B, space, device));
+        *out = new mfx_ease_s{h};
+        return MFX_OK;
+    });
+}
+int mfx_ease_weights(mfx_ease_t h, int64_t first, int64_t count, float* B_rows, mfx_memspace space) {
+    return guarded("mfx_ease_weights", [&]() -> int {
+        MFX_REQUIRE(h && h->impl, "mfx_ease_weights: null handle");
+        return h->impl->weights(first, count, B_rows, space);
+    });
+}
+int mfx_ease_recommend(mfx_ease_t h, int64_t nusers, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val, int32_t n_top,
+                       int flags, int32_t tile_items, uint32_t* items, float* scores, int64_t* bad_rows, mfx_memspace space) {
+    return guarded("mfx_ease_recommend", [&]() -> int {
+        MFX_REQUIRE(h && h->impl, "mfx_ease_recommend: null handle");
+        return h->impl->recommend(nusers, nnz, ptr, idx, val, n_top, flags, tile_items, items, scores, bad_rows, space);
+    });
+}
+int mfx_ease_times(mfx_ease_t h, double seconds[6]) {
+    return guarded("mfx_ease_times", [&]() -> int {
+        MFX_REQUIRE(h && h->impl && seconds, "mfx_ease_times: null handle or seconds");
+        h->impl->times(seconds);
+        return MFX_OK;
+    });
+}
+int mfx_ease_destroy(mfx_ease_t h) {
+    return guarded("mfx_ease_destroy", [&]() -> int {
         if (!h) return MFX_OK;
         delete h->impl;
         delete h;

@@ -1,6 +1,6 @@
 // knn_device.hpp -- the device skeleton and the host helpers that the units on the interaction matrix share: knn.hip
-// (mfx_knn_*) and slim.hip (mfx_slim_*).  Everything here sits in an anonymous namespace: each unit compiles its own copy,
-// as knn.hip did while this text was part of it.
+// (mfx_knn_*), slim.hip (mfx_slim_*) and ease.hip (mfx_ease_*).  Everything here sits in an anonymous namespace: each unit
+// compiles its own copy, as knn.hip did while this text was part of it.
 //
 // A workgroup owns one output row (the neighbours of an item, the scores of a query user, a row of X^T X) and walks the item
 // axis in tiles of T accumulators:
@@ -12,12 +12,15 @@
 //            the LDS candidate area behind the list; one that finds the area full stays in its accumulator, list and
 //            candidates are sorted together (bitonic, the total order beats()), the best `keep` stay, and the tile is
 //            scanned again for what is left.
-// knn_row is scan and select over a term source; slim.hip's Gram pass keeps `add` and gathers from the tile instead.
+// knn_row is scan and select over a term source; slim.hip's Gram pass keeps `add` and gathers from the tile instead, ease.hip's
+// writes the tile out densely; ease.hip's recommendation fills the tile with fp32 scores and selects with knn_dense_scan.
 #pragma once
 
 #include <algorithm>
 #include <chrono>
 #include <cmath>
+#include <numeric>
+#include <vector>
 
 #include "common.hpp"
 #include "rec_tiles.hpp"
@@ -155,6 +158,46 @@ __device__ int knn_row(const KnnLds& s, const Src& src, uint32_t cols, uint32_t 
     }
     if (bad) s.ctl[3] = 1;
     return knn_sort_keep(s, keep);  // (its barriers publish ctl[3])
+}
+
+// The sibling of knn_row's scan for scores that are not sums on the grid (ease.hip): every ELIGIBLE slot of the tile is a
+// candidate, zero and negative keys included.  A slot holds kKnnLive | the bits of its fp32 key, or 0 when it is not eligible
+// (an item of the row, a NaN score) or already taken.  Same threshold, area and merge as above; the tile is all zeros on
+// return.  knn_dense_begin resets the selection at the start of a row; the caller ends the row with knn_sort_keep.
+constexpr unsigned long long kKnnLive = 1ull << 32;
+
+__device__ inline void knn_dense_begin(const KnnLds& s) {
+    if (threadIdx.x == 0) {
+        s.ctl[0] = 0;
+        s.ctl[1] = kPad;
+        s.ctl[2] = __float_as_uint(-INFINITY);
+        s.ctl[3] = 0;
+    }
+    __syncthreads();
+}
+
+__device__ inline void knn_dense_scan(const KnnLds& s, uint32_t base, uint32_t len, int keep) {
+    const int tid = threadIdx.x;
+    for (;;) {
+        const float thr_key = __uint_as_float(s.ctl[2]);
+        const uint32_t thr_id = s.ctl[1];
+        for (uint32_t slot = tid; slot < len; slot += kKnnThreads) {
+            const unsigned long long v = s.acc[slot];
+            if (v == 0ull) continue;
+            const float key = __uint_as_float((uint32_t) v);
+            const uint32_t item = base + slot;
+            if (beats(key, item, thr_key, thr_id)) {
+                const uint32_t pos = atomicAdd(&s.ctl[0], 1u);
+                if (pos >= (uint32_t) s.NC) continue;
+                s.key[pos] = key;
+                s.id[pos] = item;
+            }
+            s.acc[slot] = 0ull;
+        }
+        __syncthreads();
+        if (s.ctl[0] <= (uint32_t) s.NC) break;  // (nobody touches ctl[0] again before the next barrier)
+        knn_sort_keep(s, keep);
+    }
 }
 
 // ---------------------------------------------------------------------------------------------- the build's term source
@@ -334,6 +377,79 @@ int allow_lds(Kern kern, size_t bytes) {
 }
 
 double since(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); }
+
+// ---------------------------------------------------------------------------------------------- the matrix of slim.hip and ease.hip
+int check_x(const char* fn, const mfx_csx* X) {
+    MFX_REQUIRE(X->nnz >= 1, "%s: the matrix has no entries", fn);
+    MFX_REQUIRE(X->cols >= 2, "%s: cols must be at least 2 (got %lld)", fn, (long long) X->cols);
+    MFX_REQUIRE(X->rows >= 1 && X->rows < 0xFFFFFFFFll && X->cols < 0xFFFFFFFFll && X->nnz < 0xFFFFFFFFll,
+                "%s: rows, cols and nnz must be below 2^32 - 1", fn);
+    MFX_REQUIRE(X->csr_row_ptr && X->csr_col_idx && X->csr_val && X->csc_col_ptr && X->csc_row_idx && X->csc_val,
+                "%s: X needs both orientations (a null array)", fn);
+    return MFX_OK;
+}
+
+struct StagedX {
+    Staged<uint32_t> ptr, idx, cptr, ridx;
+    Staged<float> val, cval;
+    uint32_t rows = 0, cols = 0, nnz = 0;
+
+    // The six arrays on the device, their structure checked as by mfx_knn_build.
+    int set(const char* fn, const mfx_csx* X, mfx_memspace space, hipStream_t st) {
+        rows = (uint32_t) X->rows; cols = (uint32_t) X->cols; nnz = (uint32_t) X->nnz;
+        MFX_TRY(ptr.set(X->csr_row_ptr, (size_t) rows + 1, space, st));
+        MFX_TRY(idx.set(X->csr_col_idx, nnz, space, st));
+        MFX_TRY(val.set(X->csr_val, nnz, space, st));
+        MFX_TRY(cptr.set(X->csc_col_ptr, (size_t) cols + 1, space, st));
+        MFX_TRY(ridx.set(X->csc_row_idx, nnz, space, st));
+        MFX_TRY(cval.set(X->csc_val, nnz, space, st));
+        FirstBad bad_row, bad_col;
+        MFX_TRY(bad_row.init(st));
+        MFX_TRY(bad_col.init(st));
+        hipLaunchKernelGGL(k_knn_check, dim3(grid_256(rows)), dim3(256), 0, st, ptr.p, idx.p, rows, cols, nnz, bad_row.w.get());
+        MFX_LAUNCH_CHECK();
+        hipLaunchKernelGGL(k_knn_check, dim3(grid_256(cols)), dim3(256), 0, st, cptr.p, ridx.p, cols, rows, nnz, bad_col.w.get());
+        MFX_LAUNCH_CHECK();
+        uint32_t first = kNone;
+        MFX_TRY(bad_row.read(st, &first));
+        MFX_REQUIRE(first == kNone, "%s: row %u of the CSR side: its pointers must ascend from 0 to nnz and its ids be strictly ascending and below cols",
+                    fn, first);
+        MFX_TRY(bad_col.read(st, &first));
+        MFX_REQUIRE(first == kNone,
+                    "%s: column %u of the CSC side: its pointers must ascend from 0 to nnz and its ids be strictly ascending and below rows", fn, first);
+        return MFX_OK;
+    }
+};
+
+// The work order of the queue (heaviest item first, ties by item), on the device.  Refuses an over-long column.
+int work_order(const char* fn, const StagedX& x, hipStream_t st, DevBuf<uint32_t>* order) {
+    const uint32_t cols = x.cols;
+    FirstBad long_col;
+    MFX_TRY(long_col.init(st));
+    DevBuf<unsigned long long> work;
+    MFX_TRY(work.alloc(cols));
+    hipLaunchKernelGGL(k_knn_work, dim3(grid_256((uint64_t) cols * 64)), dim3(256), 0, st, x.ptr.p, x.cptr.p, x.ridx.p, cols, work.get(),
+                       long_col.w.get());
+    MFX_LAUNCH_CHECK();
+    std::vector<unsigned long long> hwork(cols);
+    MFX_HIP(hipMemcpyAsync(hwork.data(), work.get(), sizeof(unsigned long long) * cols, hipMemcpyDeviceToHost, st));
+    uint32_t first = kNone;
+    MFX_TRY(long_col.read(st, &first));
+    MFX_REQUIRE(first == kNone, "%s: item %u: a column of more than 2^21 entries", fn, first);
+    std::vector<uint32_t> horder(cols);
+    std::iota(horder.begin(), horder.end(), 0u);
+    std::sort(horder.begin(), horder.end(), [&](uint32_t a, uint32_t b) { return hwork[a] > hwork[b] || (hwork[a] == hwork[b] && a < b); });
+    MFX_TRY(order->alloc(cols));
+    MFX_TRY(order->upload(horder.data(), cols, MFX_HOST, st));
+    MFX_HIP(hipStreamSynchronize(st));
+    return MFX_OK;
+}
+
+int device_cus(int device, int* cus) {
+    MFX_HIP(hipDeviceGetAttribute(cus, hipDeviceAttributeMultiprocessorCount, device));
+    *cus = std::max(*cus, 1);
+    return MFX_OK;
+}
 
 }  // namespace
 

@@ -343,16 +343,6 @@ int check_params(const char* fn, int32_t K, const SlimParams& p) {
     return MFX_OK;
 }
 
-int check_x(const char* fn, const mfx_csx* X) {
-    MFX_REQUIRE(X->nnz >= 1, "%s: the matrix has no entries", fn);
-    MFX_REQUIRE(X->cols >= 2, "%s: cols must be at least 2 (got %lld)", fn, (long long) X->cols);
-    MFX_REQUIRE(X->rows >= 1 && X->rows < 0xFFFFFFFFll && X->cols < 0xFFFFFFFFll && X->nnz < 0xFFFFFFFFll,
-                "%s: rows, cols and nnz must be below 2^32 - 1", fn);
-    MFX_REQUIRE(X->csr_row_ptr && X->csr_col_idx && X->csr_val && X->csc_col_ptr && X->csc_row_idx && X->csc_val,
-                "%s: X needs both orientations (a null array)", fn);
-    return MFX_OK;
-}
-
 // A checked support on the device and its inverse lists.
 struct Support {
     DevBuf<uint32_t> S, nreal, iptr, tj, tp;
@@ -408,62 +398,6 @@ struct Support {
         return MFX_OK;
     }
 };
-
-struct StagedX {
-    Staged<uint32_t> ptr, idx, cptr, ridx;
-    Staged<float> val, cval;
-    uint32_t rows = 0, cols = 0, nnz = 0;
-
-    // The six arrays on the device, their structure checked as by mfx_knn_build.
-    int set(const char* fn, const mfx_csx* X, mfx_memspace space, hipStream_t st) {
-        rows = (uint32_t) X->rows; cols = (uint32_t) X->cols; nnz = (uint32_t) X->nnz;
-        MFX_TRY(ptr.set(X->csr_row_ptr, (size_t) rows + 1, space, st));
-        MFX_TRY(idx.set(X->csr_col_idx, nnz, space, st));
-        MFX_TRY(val.set(X->csr_val, nnz, space, st));
-        MFX_TRY(cptr.set(X->csc_col_ptr, (size_t) cols + 1, space, st));
-        MFX_TRY(ridx.set(X->csc_row_idx, nnz, space, st));
-        MFX_TRY(cval.set(X->csc_val, nnz, space, st));
-        FirstBad bad_row, bad_col;
-        MFX_TRY(bad_row.init(st));
-        MFX_TRY(bad_col.init(st));
-        hipLaunchKernelGGL(k_knn_check, dim3(grid_256(rows)), dim3(256), 0, st, ptr.p, idx.p, rows, cols, nnz, bad_row.w.get());
-        MFX_LAUNCH_CHECK();
-        hipLaunchKernelGGL(k_knn_check, dim3(grid_256(cols)), dim3(256), 0, st, cptr.p, ridx.p, cols, rows, nnz, bad_col.w.get());
-        MFX_LAUNCH_CHECK();
-        uint32_t first = kNone;
-        MFX_TRY(bad_row.read(st, &first));
-        MFX_REQUIRE(first == kNone, "%s: row %u of the CSR side: its pointers must ascend from 0 to nnz and its ids be strictly ascending and below cols",
-                    fn, first);
-        MFX_TRY(bad_col.read(st, &first));
-        MFX_REQUIRE(first == kNone,
-                    "%s: column %u of the CSC side: its pointers must ascend from 0 to nnz and its ids be strictly ascending and below rows", fn, first);
-        return MFX_OK;
-    }
-};
-
-// The work order of the queue (heaviest item first, ties by item), on the device.  Refuses an over-long column.
-int work_order(const char* fn, const StagedX& x, hipStream_t st, DevBuf<uint32_t>* order) {
-    const uint32_t cols = x.cols;
-    FirstBad long_col;
-    MFX_TRY(long_col.init(st));
-    DevBuf<unsigned long long> work;
-    MFX_TRY(work.alloc(cols));
-    hipLaunchKernelGGL(k_knn_work, dim3(grid_256((uint64_t) cols * 64)), dim3(256), 0, st, x.ptr.p, x.cptr.p, x.ridx.p, cols, work.get(),
-                       long_col.w.get());
-    MFX_LAUNCH_CHECK();
-    std::vector<unsigned long long> hwork(cols);
-    MFX_HIP(hipMemcpyAsync(hwork.data(), work.get(), sizeof(unsigned long long) * cols, hipMemcpyDeviceToHost, st));
-    uint32_t first = kNone;
-    MFX_TRY(long_col.read(st, &first));
-    MFX_REQUIRE(first == kNone, "%s: item %u: a column of more than 2^21 entries", fn, first);
-    std::vector<uint32_t> horder(cols);
-    std::iota(horder.begin(), horder.end(), 0u);
-    std::sort(horder.begin(), horder.end(), [&](uint32_t a, uint32_t b) { return hwork[a] > hwork[b] || (hwork[a] == hwork[b] && a < b); });
-    MFX_TRY(order->alloc(cols));
-    MFX_TRY(order->upload(horder.data(), cols, MFX_HOST, st));
-    MFX_HIP(hipStreamSynchronize(st));
-    return MFX_OK;
-}
 
 // The Gram pass: the blocks [cols][K + 1][K] of the checked support into `blocks` (device memory).
 int gram_pass(const char* fn, const StagedX& x, const DevBuf<uint32_t>& order, const uint32_t* S, const uint32_t* iptr, const uint32_t* tj,
@@ -525,12 +459,6 @@ int solve_pass(int64_t n, int K, const float* blocks, const uint32_t* nreal, con
     MFX_HIP(hipMemcpyAsync(&h, nfailed.get(), sizeof(h), hipMemcpyDeviceToHost, st));
     MFX_HIP(hipStreamSynchronize(st));
     if (failed) *failed = (int64_t) h;
-    return MFX_OK;
-}
-
-int device_cus(int device, int* cus) {
-    MFX_HIP(hipDeviceGetAttribute(cus, hipDeviceAttributeMultiprocessorCount, device));
-    *cus = std::max(*cus, 1);
     return MFX_OK;
 }
 

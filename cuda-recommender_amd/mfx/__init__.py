@@ -11,9 +11,11 @@ from .api import BprSolver, bpr_apply, bpr_triples  # noqa: F401
 from .api import bpr_apply_neg, bpr_rank_weights, bpr_trials  # noqa: F401
 from .api import ItemKnn, knn_weights  # noqa: F401
 from .api import Slim, slim_gram, slim_solve  # noqa: F401
+from .api import Ease, ease_gram, ease_inverse, ease_weights_from_inverse  # noqa: F401
 from ._lib import LIB_PATH, MfxError, lib  # noqa: F401
 from ._lib import MFX_KNN_KEEP_SEEN  # noqa: F401
 from ._lib import MFX_SLIM_SIGNED  # noqa: F401
+from ._lib import MFX_EASE_INV_SIMPLE  # noqa: F401
 from ._lib import MFX_FOLD_ALS, MFX_FOLD_ALS_EXACT, MFX_FOLD_CCD, MFX_FOLD_IMPLICIT  # noqa: F401
 from ._lib import MFX_SIM_DOT, MFX_SIM_COSINE  # noqa: F401
 from ._lib import MFX_CAND_NO_EXCLUDE, MFX_DIV_NO_EXCLUDE  # noqa: F401

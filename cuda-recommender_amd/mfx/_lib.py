@@ -18,6 +18,7 @@ MFX_CAND_NO_EXCLUDE = 1  # include/mfx.h, flags of mfx_rec_query_candidates
 MFX_DIV_NO_EXCLUDE = 1  # include/mfx.h, flags of mfx_rec_diversify
 MFX_KNN_KEEP_SEEN = 1  # include/mfx.h, flags of mfx_knn_recommend
 MFX_SLIM_SIGNED = 1  # include/mfx.h, flags of mfx_slim_train and mfx_slim_solve
+MFX_EASE_INV_SIMPLE = 1  # include/mfx.h, flags of mfx_ease_inverse and mfx_ease_train
 
 u32p = C.POINTER(C.c_uint32)
 f32p = C.POINTER(C.c_float)
@@ -166,6 +167,16 @@ SIGNATURES = {
                                      C.c_void_p, C.c_void_p, i64p, C.c_int]),
     "mfx_slim_times": (C.c_int, [C.c_void_p, f64p]),
     "mfx_slim_destroy": (C.c_int, [C.c_void_p]),
+    "mfx_ease_gram": (C.c_int, [C.POINTER(mfx_csx), C.c_float, C.c_int32, C.c_void_p, C.c_int, C.c_int]),
+    "mfx_ease_inverse": (C.c_int, [C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "mfx_ease_weights_from_inverse": (C.c_int, [C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
+    "mfx_ease_train": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(mfx_csx), C.c_float, C.c_int, C.c_int32, C.c_int, C.c_int]),
+    "mfx_ease_create_from_weights": (C.c_int, [C.POINTER(C.c_void_p), C.c_int64, C.c_void_p, C.c_int, C.c_int]),
+    "mfx_ease_weights": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int]),
+    "mfx_ease_recommend": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int, C.c_int32,
+                                     C.c_void_p, C.c_void_p, i64p, C.c_int]),
+    "mfx_ease_times": (C.c_int, [C.c_void_p, f64p]),
+    "mfx_ease_destroy": (C.c_int, [C.c_void_p]),
     "mfx_comm_unique_id": (C.c_int, [C.c_void_p]),
     "mfx_comm_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "mfx_comm_create_local": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int]),

@@ -1125,6 +1125,138 @@ class Slim:
 
 
 # ---------------------------------------------------------------------------------------------
+# EASE: closed-form dense item-item models (mfx_ease_*)
+# ---------------------------------------------------------------------------------------------
+def _ease_matrix(R, weighting, k1, b, device_arrays):
+    """(mfx_csx, memory space, cols, keep-alive) of the matrix of an EASE call."""
+    if device_arrays is not None:
+        if weighting is not None:
+            raise ValueError("device_arrays are taken as they are: pass weighting=None")
+        return _device_csx_coo(device_arrays)[0], L.MFX_DEVICE, int(device_arrays["cols"]), device_arrays
+    X = knn_weights(R, weighting, k1, b)
+    return _csx(X), L.MFX_HOST, X.cols, X
+
+
+def _ease_square(a, what: str):
+    """A square float32 matrix of an EASE call as (pointer, memory space, n, keep-alive): numpy or a GPU tensor."""
+    if len(a.shape) != 2 or a.shape[0] != a.shape[1]:
+        raise ValueError(f"{what} must be a square matrix")
+    if _is_dev(a):
+        import torch
+        if a.dtype != torch.float32:
+            raise ValueError(f"{what}: a device tensor must be float32")
+        a = a.contiguous()
+        return C.c_void_p(int(a.data_ptr())), L.MFX_DEVICE, int(a.shape[0]), a
+    a = np.ascontiguousarray(a, np.float32)
+    return _vp(a), L.MFX_HOST, int(a.shape[0]), a
+
+
+def _ease_out(like_dev: bool, shape, device: int):
+    """An uninitialised float32 result on the side of the input -> (array, pointer)."""
+    if like_dev:
+        import torch
+        out = torch.empty(shape, dtype=torch.float32, device=torch.device("cuda", device))
+        return out, C.c_void_p(int(out.data_ptr()))
+    out = np.empty(shape, np.float32)
+    return out, _vp(out)
+
+
+def ease_gram(R: Optional[RatingData], lam: float, weighting: Optional[str] = None, k1: float = 1.2, b: float = 0.75, device: int = 0,
+              device_arrays: Optional[dict] = None, tile_items: int = 0):
+    """G = X^T X + lam I [cols][cols] of mfx_ease_gram (include/mfx.h): the fixed-point item-kNN similarities off the diagonal,
+    fp32(d_i + lam) on it.  A numpy array, or with device_arrays a float32 tensor on the device."""
+    csx, space, cols, keep = _ease_matrix(R, weighting, k1, b, device_arrays)
+    out, po = _ease_out(space == L.MFX_DEVICE, (cols, cols), device)
+    L.check(L.lib().mfx_ease_gram(C.byref(csx), float(lam), int(tile_items), po, space, device))
+    return out
+
+
+def ease_inverse(A, simple: bool = False, device: int = 0):
+    """The inverse of one symmetric positive definite matrix, n <= 32768, on the device (mfx_ease_inverse): the blocked
+    Cholesky inverse of spd_inverse, by grouped LDS-staged kernels or, simple=True, one wavefront per block -- the same
+    bits either way.  numpy in, numpy out; a GPU tensor in, a tensor out."""
+    pa, space, n, keep = _ease_square(A, "A")
+    out, po = _ease_out(space == L.MFX_DEVICE, (n, n), device)
+    L.check(L.lib().mfx_ease_inverse(n, pa, po, L.MFX_EASE_INV_SIMPLE if simple else 0, space, device))
+    return out
+
+
+def ease_weights_from_inverse(P, device: int = 0):
+    """B_ij = float32(-P_ij / P_jj) with a zero diagonal (mfx_ease_weights_from_inverse).  numpy or a GPU tensor."""
+    pp, space, n, keep = _ease_square(P, "P")
+    out, po = _ease_out(space == L.MFX_DEVICE, (n, n), device)
+    L.check(L.lib().mfx_ease_weights_from_inverse(n, pp, po, space, device))
+    return out
+
+
+class Ease:
+    """EASE (mfx_ease_*, include/mfx.h): the closed-form dense item-item model B = I - P diag(P)^-1 with a zero diagonal,
+    P = (X^T X + lam I)^-1, trained on the GPU -- exact fixed-point Gram matrix, blocked Cholesky inverse, one division per
+    weight -- and recommendations as fma chains over the user's own items; every bit fixed by the data.  R: a RatingData,
+    its values taken under `weighting` (knn_weights; k1, b: BM25; None: as they are).  lam: the ridge penalty, > 0.
+    device_arrays: the matrix as a dict of device tensors (mfx.synth_torch) instead of R; weighting must then be None.
+    tile_items: the test hook of mfx_ease_train.  simple_inverse: the one-wavefront-per-block schedule of the inverse."""
+
+    def __init__(self, R: Optional[RatingData], lam: float, weighting: Optional[str] = None, k1: float = 1.2, b: float = 0.75,
+                 device: int = 0, device_arrays: Optional[dict] = None, tile_items: int = 0, simple_inverse: bool = False):
+        self.handle = C.c_void_p()
+        self.device, self.bad_rows = int(device), 0
+        csx, space, self.cols, keep = _ease_matrix(R, weighting, k1, b, device_arrays)
+        L.check(L.lib().mfx_ease_train(C.byref(self.handle), C.byref(csx), float(lam), L.MFX_EASE_INV_SIMPLE if simple_inverse else 0,
+                                       int(tile_items), space, self.device))
+
+    @classmethod
+    def from_weights(cls, B, device: int = 0) -> "Ease":
+        """A model from given weights B [cols][cols] (float32, finite, zero diagonal): a numpy array or a GPU tensor."""
+        pb, space, n, keep = _ease_square(B, "B")
+        self = cls.__new__(cls)
+        self.handle = C.c_void_p()
+        self.device, self.bad_rows, self.cols = int(device), 0, n
+        L.check(L.lib().mfx_ease_create_from_weights(C.byref(self.handle), n, pb, space, self.device))
+        return self
+
+    def weights(self, first: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """Rows first .. first + count - 1 of B (count None: to the end) as float32 [count][cols]; row i holds the weights
+        from source item i to every target."""
+        first = int(first)
+        count = self.cols - first if count is None else int(count)
+        out = np.empty((max(count, 0), self.cols), np.float32)
+        L.check(L.lib().mfx_ease_weights(self.handle, first, count, _vp(out), L.MFX_HOST))
+        return out
+
+    def recommend(self, rows, n_top: int, keep_seen: bool = False, on_device: bool = False, tile_items: int = 0):
+        """Top-n_top items of the users given by their interactions, as ItemKnn.recommend: the score of j is the fma chain of
+        x_i * B[i][j] over the row's items i in stored order; every item not in the row is eligible, whatever its score's
+        sign.  The number of bad rows (a value that is not finite) is left in self.bad_rows."""
+        items, scores, self.bad_rows = _rows_recommend(L.lib().mfx_ease_recommend, self.handle, self.device, rows, n_top, keep_seen,
+                                                       on_device, tile_items)
+        return items, scores
+
+    def times(self) -> dict:
+        """Seconds of the training (checks, Gram pass, inverse, weights) and of recommend summed over the calls."""
+        out = (C.c_double * 6)()
+        L.check(L.lib().mfx_ease_times(self.handle, out))
+        return dict(zip(("train_checks", "gram_pass", "inverse", "weights", "recommend_checks", "recommend_pass"), (float(x) for x in out)))
+
+    def close(self):
+        if self.handle:
+            L.lib().mfx_ease_destroy(self.handle)
+            self.handle = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+# ---------------------------------------------------------------------------------------------
 # single operators (one per reference function on the path)
 # ---------------------------------------------------------------------------------------------
 def _u32(a):

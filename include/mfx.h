@@ -608,6 +608,65 @@ int mfx_slim_times(mfx_slim_t h, double seconds[5]);
 int mfx_slim_destroy(mfx_slim_t h);
 
 /* ------------------------------------------------------------------------------------
+ * EASE (Steck 2019, "Embarrassingly Shallow Autoencoders for Sparse Data"): the closed-form dense item-item model, the
+ * full-catalogue ridge form of SLIM.  With G = X^T X + lambda I and P = G^-1 the model is B = I - P diag(P)^-1 with a zero
+ * diagonal.  Every bit of G, P, B and of the scores is fixed by the data and this text: no bit depends on the workgroup
+ * shape, the tile width, the batch or the schedule of the inverse.
+ *
+ * Input.  X as for item-kNN (both orientations, values as given, the same structure checks), 2 <= cols <= 32768; lambda
+ * finite and > 0.  Every dense matrix here is [cols][cols] fp32, row-major.
+ *
+ * Gram.  For i != j, G_ij is the item-kNN similarity s_ij above (terms fp32(x_ui * x_uj) on the 2^-36 grid, added as 64-bit
+ * integers, the fp32 nearest to the sum).  G_ii = fp32(d_i + lambda) with d_i SLIM's diagonal, the fp32 of the same sum over
+ * fp32(x_ui * x_ui).  G is symmetric in bits.  A term that is not finite or of magnitude >= 64, or a column of more than
+ * 2^21 entries, is MFX_ERR_INVALID naming the smallest such item; unsorted or out-of-range ids are refused as at the item-kNN
+ * build.
+ *
+ * Inverse.  mfx_ease_inverse is the algorithm of mfx_spd_inverse (csrc/spd_inverse.hip: blocked Cholesky on a copy padded to
+ * a multiple of 32, T = L^-1, P = T^T T; diagonal blocks in fp64, every block product one chain of v_mfma_f32_32x32x2_f32
+ * over the summed index, ascending) for 1 <= n <= 32768.  flags = 0 runs it with workgroups of four waves that own 4 x 4
+ * blocks and stage operands in LDS, MFX_EASE_INV_SIMPLE with one wavefront per block; both return the same bits for every
+ * n, and for n <= 1024 the bits of mfx_spd_inverse.  P is symmetric in bits.  A pivot that is <= 0 or not finite is
+ * MFX_ERR_INVALID ("not positive definite"); the output is then unspecified.  The workspace is three padded copies.
+ *
+ * Weights.  B_ij = fp32((-P_ij) / P_jj) for i != j, one correctly rounded division; B_ii = +0.  Row i of B holds the weights
+ * from source item i to every target j.  A P_jj that is not finite or not > 0 is MFX_ERR_INVALID naming the item.
+ *
+ * Recommendation for users given by CSR rows of (item i, value x), checked as mfx_knn_recommend checks them.  For every
+ * item j the score starts at +0 and takes the row's entries e in stored order: s_j = fma(x_e, B[i_e][j], s_j).  Eligible:
+ * every item not in the row (MFX_KNN_KEEP_SEEN: every item); zero and negative scores are candidates, NaN scores are
+ * dropped.  Order and padding are those of mfx_rec_query, 1 <= n_top <= 1024.  An empty row returns pads and is not bad.
+ * A row with a value that is not finite, or with more than 2^21 entries, is BAD: it returns all pads and is counted in
+ * *bad_rows (host memory, may be NULL); the other rows are unaffected.  tile_items: the test hook of mfx_knn_recommend.
+ *
+ * The calls.  gram, inverse, weights_from_inverse: the three steps alone, arrays in `space`.  train: exactly gram ->
+ * inverse -> weights_from_inverse on the device; G and the inverse's workspace are freed once P stands, the weights are
+ * formed in place over P.  The peak is G + 3 padded copies + P: about 21 GB at cols = 32768; an allocation that fails is
+ * MFX_ERR_ALLOC stating the size.  tile_items of gram and train: the test hook of the item-kNN build.
+ * create_from_weights: a model from a given B (copied), checked on the device: every entry finite, the diagonal zero, else
+ * MFX_ERR_INVALID naming the first bad row.  weights: rows first .. first + count - 1 of B, [count][cols].
+ * times: seconds of train's checks and work order, Gram pass, inverse and weights step (host clock), and stream seconds of
+ * the checks and of the pass of the recommendation summed over the calls.  destroy of NULL is 0.
+ * MFX_ERR_INVALID without touching the device: a null argument, cols < 2 or > 32768, n < 1 or > 32768, nnz = 0, lambda not
+ * finite or <= 0, n_top out of range, an unknown memory space or flag, a bad tile_items.  A failed train or
+ * create_from_weights leaves *out NULL.
+ * ---------------------------------------------------------------------------------- */
+typedef struct mfx_ease_s* mfx_ease_t;
+#define MFX_EASE_INV_SIMPLE 1 /* flags of mfx_ease_inverse and mfx_ease_train: one wavefront per 32 x 32 block */
+int mfx_ease_gram(const mfx_csx* X, float lambda, int32_t tile_items, float* G, mfx_memspace space, int device);
+int mfx_ease_inverse(int64_t n, const float* A, float* Ainv, int flags, mfx_memspace space, int device);
+int mfx_ease_weights_from_inverse(int64_t n, const float* P, float* B, mfx_memspace space, int device);
+int mfx_ease_train(mfx_ease_t* out, const mfx_csx* X, float lambda, int flags, int32_t tile_items, mfx_memspace space,
+                   int device);
+int mfx_ease_create_from_weights(mfx_ease_t* out, int64_t cols, const float* B, mfx_memspace space, int device);
+int mfx_ease_weights(mfx_ease_t h, int64_t first, int64_t count, float* B_rows, mfx_memspace space);
+int mfx_ease_recommend(mfx_ease_t h, int64_t nusers, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val,
+                       int32_t n_top, int flags, int32_t tile_items, uint32_t* items, float* scores, int64_t* bad_rows,
+                       mfx_memspace space);
+int mfx_ease_times(mfx_ease_t h, double seconds[6]);
+int mfx_ease_destroy(mfx_ease_t h);
+
+/* ------------------------------------------------------------------------------------
  * Top-N recommendation: a resident handle over trained factors that returns, for each
  * requested user, the n_top highest-scoring items the user must not be excluded from.
  * Score of (u, i) = the fp32 fused multiply-add chain in ascending t: acc = +0, then
