@@ -65,6 +65,25 @@ static int guarded(const char* what, F&& body) noexcept {
     }
 }
 
+// A create entry point: `out` checked under the entry point's own name and cleared, the object made by `make`, the handle
+// S around it; and the end of a handle.
+template <class S, class Make>
+static int make_handle(const char* fn, S** out, Make&& make) {
+    MFX_REQUIRE(out, "%s: out is NULL", fn);
+    *out = nullptr;
+    decltype(S::impl) impl = nullptr;
+    MFX_TRY(make(&impl));
+    *out = new S{impl};
+    return MFX_OK;
+}
+template <class S>
+static int destroy_handle(S* h) {
+    if (!h) return MFX_OK;
+    delete h->impl;
+    delete h;
+    return MFX_OK;
+}
+
 extern "C" {
 
 const char* mfx_last_error(void) { return last_error().c_str(); }
@@ -93,12 +112,7 @@ void mfx_params_default(mfx_params* p) {
 int mfx_ccd_create(mfx_ccd_t* out, const mfx_csx* R, const mfx_coo* T, const mfx_params* p,
                    mfx_memspace space, const mfx_shard* shard) {
     return guarded("mfx_ccd_create", [&]() -> int {
-        MFX_REQUIRE(out, "mfx_ccd_create: out is NULL");
-        *out = nullptr;
-        CcdSolver* s = nullptr;
-        MFX_TRY(CcdSolver::create(&s, R, T, p, space, shard));
-        *out = new mfx_ccd_s{s};
-        return MFX_OK;
+        return make_handle("mfx_ccd_create", out, [&](CcdSolver** s) { return CcdSolver::create(s, R, T, p, space, shard); });
     });
 }
 int mfx_ccd_set_factors(mfx_ccd_t s, const float* W, const float* H, mfx_memspace space) {
@@ -167,10 +181,7 @@ int mfx_ccd_layout_info(mfx_ccd_t s, int side, int32_t out[4]) {
 }
 int mfx_ccd_destroy(mfx_ccd_t s) {
     return guarded("mfx_ccd_destroy", [&]() -> int {
-        if (!s) return MFX_OK;
-        delete s->impl;
-        delete s;
-        return MFX_OK;
+        return destroy_handle(s);
     });
 }
 
@@ -198,12 +209,8 @@ using AlsO = AlsPlan::Objective;
 
 static int als_create(mfx_als_t* out, const mfx_csx* R, const mfx_coo* T, const mfx_params* p, mfx_memspace space, const mfx_als_shard* shard,
                       const AlsSpec& spec) {
-    MFX_REQUIRE(out, "%s: out is NULL", spec.fn);
-    *out = nullptr;
-    AlsSolver* s = nullptr;
-    MFX_TRY(AlsSolver::create(&s, R, T, p, space, shard, spec));  // (argument checks before the device is touched)
-    *out = new mfx_als_s{s};
-    return MFX_OK;
+    // (argument checks before the device is touched)
+    return make_handle(spec.fn, out, [&](AlsSolver** s) { return AlsSolver::create(s, R, T, p, space, shard, spec); });
 }
 // The checks of a half's arrays, then of its spec, then the half itself.  k_positive: mfx_als_half counts k <= 0 as a bad argument
 static int als_half(AlsSpec spec, const HalfSegs& g, const float* X, const float* Y_in, float* Y_out, int64_t k, float lambda, int32_t* counts,
@@ -253,10 +260,7 @@ int mfx_als_kernel_times(mfx_als_t s, int cap, const char** names, double* secon
 }
 int mfx_als_destroy(mfx_als_t s) {
     return guarded("mfx_als_destroy", [&]() -> int {
-        if (!s) return MFX_OK;
-        delete s->impl;
-        delete s;
-        return MFX_OK;
+        return destroy_handle(s);
     });
 }
 /* ------------------------------------------------------------------ implicit-feedback ALS */
@@ -355,8 +359,8 @@ int mfx_ials_create_reg(mfx_als_t* out, const mfx_csx* R, const mfx_params* p, f
 int mfx_ials_block_create_reg(mfx_als_t* out, const mfx_csx* R, const mfx_params* p, float alpha, float alpha0, float nu, int32_t block,
                               mfx_memspace space) {
     return guarded("mfx_ials_block_create_reg", [&]() -> int {
-        MFX_REQUIRE(out, "mfx_ials_block_create_reg: out is NULL");
-        *out = nullptr;
+        MFX_REQUIRE(out, "mfx_ials_block_create_reg: out is NULL");  // (als_create repeats these two: they come before the
+        *out = nullptr;                                              // block check here, and there for every other create)
         // (this entry point alone refuses a negative block before it looks at anything else)
         MFX_REQUIRE(block >= 0, "implicit ALS by block sweeps: block = %d (0 = chosen from k, else 1 <= block <= %u)", block, kIalsBlockMaxBlock);
         AlsSpec s{AlsM::Blocks, AlsO::ImplicitReg, "mfx_ials_block_create_reg"};
@@ -385,12 +389,7 @@ int mfx_ials_block_half_reg(int64_t nseg, int64_t nnz, const uint32_t* ptr, cons
 /* ------------------------------------------------------------------ BPR: deterministic mini-batch pairwise ranking */
 int mfx_bpr_create(mfx_bpr_t* out, const mfx_csx* R, const mfx_params* p, float lr, int64_t batch, uint64_t seed, mfx_memspace space) {
     return guarded("mfx_bpr_create", [&]() -> int {
-        MFX_REQUIRE(out, "mfx_bpr_create: out is NULL");
-        *out = nullptr;
-        BprSolver* s = nullptr;
-        MFX_TRY(BprSolver::create(&s, R, p, lr, batch, seed, space));
-        *out = new mfx_bpr_s{s};
-        return MFX_OK;
+        return make_handle("mfx_bpr_create", out, [&](BprSolver** s) { return BprSolver::create(s, R, p, lr, batch, seed, space); });
     });
 }
 int mfx_bpr_set_factors(mfx_bpr_t s, const float* W, const float* H, mfx_memspace space) {
@@ -433,10 +432,7 @@ int mfx_bpr_kernel_times(mfx_bpr_t s, double seconds[4]) {
 }
 int mfx_bpr_destroy(mfx_bpr_t s) {
     return guarded("mfx_bpr_destroy", [&]() -> int {
-        if (!s) return MFX_OK;
-        delete s->impl;
-        delete s;
-        return MFX_OK;
+        return destroy_handle(s);
     });
 }
 int mfx_bpr_triples(uint64_t seed, int64_t first_slot, int64_t count, const mfx_csx* R, uint32_t* u, uint32_t* i, uint32_t* j,
@@ -450,12 +446,9 @@ int mfx_bpr_apply(int64_t rows, int64_t cols, int64_t k, float* W, float* H, int
 int mfx_bpr_create_neg(mfx_bpr_t* out, const mfx_csx* R, const mfx_params* p, float lr, int64_t batch, uint64_t seed, int32_t mode,
                        int64_t negatives, const float* rank_weight, mfx_memspace space) {
     return guarded("mfx_bpr_create_neg", [&]() -> int {
-        MFX_REQUIRE(out, "mfx_bpr_create_neg: out is NULL");
-        *out = nullptr;
-        BprSolver* s = nullptr;
-        MFX_TRY(BprSolver::create(&s, R, p, lr, batch, seed, space, "mfx_bpr_create_neg", mode, negatives, rank_weight));
-        *out = new mfx_bpr_s{s};
-        return MFX_OK;
+        return make_handle("mfx_bpr_create_neg", out, [&](BprSolver** s) {
+            return BprSolver::create(s, R, p, lr, batch, seed, space, "mfx_bpr_create_neg", mode, negatives, rank_weight);
+        });
     });
 }
 int mfx_bpr_trials(uint64_t seed, int64_t first_slot, int64_t count, int64_t negatives, const mfx_csx* R, uint32_t* u, uint32_t* i,
@@ -483,23 +476,14 @@ int mfx_bpr_trial_stats(mfx_bpr_t s, int64_t out[2]) {
 /* ------------------------------------------------------------------ item-kNN: neighbour lists on the interaction matrix */
 int mfx_knn_build(mfx_knn_t* out, const mfx_csx* X, int32_t K, int32_t tile_items, mfx_memspace space, int device) {
     return guarded("mfx_knn_build", [&]() -> int {
-        MFX_REQUIRE(out, "mfx_knn_build: out is NULL");
-        *out = nullptr;
-        Knn* h = nullptr;
-        MFX_TRY(Knn::build(&h, X, K, tile_items, space, device));
-        *out = new mfx_knn_s{h};
-        return MFX_OK;
+        return make_handle("mfx_knn_build", out, [&](Knn** h) { return Knn::build(h, X, K, tile_items, space, device); });
     });
 }
 int mfx_knn_create_from_lists(mfx_knn_t* out, int64_t cols, int32_t K, const uint32_t* nbr_idx, const float* nbr_sim, mfx_memspace space,
                               int device) {
     return guarded("mfx_knn_create_from_lists", [&]() -> int {
-        MFX_REQUIRE(out, "mfx_knn_create_from_lists: out is NULL");
-        *out = nullptr;
-        Knn* h = nullptr;
-        MFX_TRY(Knn::from_lists(&h, cols, K, nbr_idx, nbr_sim, space, device));
-        *out = new mfx_knn_s{h};
-        return MFX_OK;
+        return make_handle("mfx_knn_create_from_lists", out,
+                           [&](Knn** h) { return Knn::from_lists(h, cols, K, nbr_idx, nbr_sim, space, device); });
     });
 }
 int mfx_knn_lists(mfx_knn_t h, uint32_t* nbr_idx, float* nbr_sim, mfx_memspace space) {
@@ -531,10 +515,7 @@ int mfx_knn_times(mfx_knn_t h, double seconds[4]) {
 }
 int mfx_knn_destroy(mfx_knn_t h) {
     return guarded("mfx_knn_destroy", [&]() -> int {
-        if (!h) return MFX_OK;
-        delete h->impl;
-        delete h;
-        return MFX_OK;
+        return destroy_handle(h);
     });
 }
 
@@ -542,12 +523,9 @@ int mfx_knn_destroy(mfx_knn_t h) {
 int mfx_slim_train(mfx_slim_t* out, const mfx_csx* X, int32_t K, const uint32_t* support, float l1, float l2, int32_t sweeps, float tol, int flags,
                    int32_t tile_items, int64_t* failed, mfx_memspace space, int device) {
     return guarded("mfx_slim_train", [&]() -> int {
-        MFX_REQUIRE(out, "mfx_slim_train: out is NULL");
-        *out = nullptr;
-        Slim* h = nullptr;
-        MFX_TRY(Slim::train(&h, X, K, support, SlimParams{l1, l2, tol, sweeps, flags}, tile_items, failed, space, device));
-        *out = new mfx_slim_s{h};
-        return MFX_OK;
+        return make_handle("mfx_slim_train", out, [&](Slim** h) {
+            return Slim::train(h, X, K, support, SlimParams{l1, l2, tol, sweeps, flags}, tile_items, failed, space, device);
+        });
     });
 }
 int mfx_slim_gram(const mfx_csx* X, int32_t K, const uint32_t* support, int32_t tile_items, float* blocks, mfx_memspace space, int device) {
@@ -562,12 +540,7 @@ int mfx_slim_solve(int64_t n, int32_t K, const float* blocks, const uint32_t* n_
 int mfx_slim_create_from_lists(mfx_slim_t* out, int64_t cols, int32_t K, const uint32_t* support, const float* w, mfx_memspace space,
                                int device) {
     return guarded("mfx_slim_create_from_lists", [&]() -> int {
-        MFX_REQUIRE(out, "mfx_slim_create_from_lists: out is NULL");
-        *out = nullptr;
-        Slim* h = nullptr;
-        MFX_TRY(Slim::from_lists(&h, cols, K, support, w, space, device));
-        *out = new mfx_slim_s{h};
-        return MFX_OK;
+        return make_handle("mfx_slim_create_from_lists", out, [&](Slim** h) { return Slim::from_lists(h, cols, K, support, w, space, device); });
     });
 }
 int mfx_slim_weights(mfx_slim_t h, uint32_t* support, float* w, int32_t* sweeps_used, mfx_memspace space) {
@@ -592,10 +565,7 @@ int mfx_slim_times(mfx_slim_t h, double seconds[5]) {
 }
 int mfx_slim_destroy(mfx_slim_t h) {
     return guarded("mfx_slim_destroy", [&]() -> int {
-        if (!h) return MFX_OK;
-        delete h->impl;
-        delete h;
-        return MFX_OK;
+        return destroy_handle(h);
     });
 }
 
@@ -611,22 +581,12 @@ int mfx_ease_weights_from_inverse(int64_t n, const float* P, float* B, mfx_memsp
 }
 int mfx_ease_train(mfx_ease_t* out, const mfx_csx* X, float lambda, int flags, int32_t tile_items, mfx_memspace space, int device) {
     return guarded("mfx_ease_train", [&]() -> int {
-        MFX_REQUIRE(out, "mfx_ease_train: out is NULL");
-        *out = nullptr;
-        Ease* h = nullptr;
-        MFX_TRY(Ease::train(&h, X, lambda, flags, tile_items, space, device));
-        *out = new mfx_ease_s{h};
-        return MFX_OK;
+        return make_handle("mfx_ease_train", out, [&](Ease** h) { return Ease::train(h, X, lambda, flags, tile_items, space, device); });
     });
 }
 int mfx_ease_create_from_weights(mfx_ease_t* out, int64_t cols, const float* B, mfx_memspace space, int device) {
     return guarded("mfx_ease_create_from_weights", [&]() -> int {
-        MFX_REQUIRE(out, "mfx_ease_create_from_weights: out is NULL");
-        *out = nullptr;
-        Ease* h = nullptr;
-        MFX_TRY(Ease::from_weights(&h, cols, B, space, device));
-        *out = new mfx_ease_s{h};
-        return MFX_OK;
+        return make_handle("mfx_ease_create_from_weights", out, [&](Ease** h) { return Ease::from_weights(h, cols, B, space, device); });
     });
 }
 int mfx_ease_weights(mfx_ease_t h, int64_t first, int64_t count, float* B_rows, mfx_memspace space) {
@@ -651,10 +611,7 @@ int mfx_ease_times(mfx_ease_t h, double seconds[6]) {
 }
 int mfx_ease_destroy(mfx_ease_t h) {
     return guarded("mfx_ease_destroy", [&]() -> int {
-        if (!h) return MFX_OK;
-        delete h->impl;
-        delete h;
-        return MFX_OK;
+        return destroy_handle(h);
     });
 }
 
@@ -837,12 +794,9 @@ int mfx_als_half(int64_t nseg, int64_t nnz, const uint32_t* ptr, const uint32_t*
 int mfx_rec_create(mfx_rec_t* out, const float* W, const float* H, int64_t rows, int64_t cols, int64_t k, int layout,
                    const mfx_csx* exclude, mfx_memspace space, int device) {
     return guarded("mfx_rec_create", [&]() -> int {
-        MFX_REQUIRE(out, "mfx_rec_create: out is NULL");
-        *out = nullptr;
-        Recommender* r = nullptr;
-        MFX_TRY(Recommender::create(&r, W, H, rows, cols, k, layout, exclude, space, device));
-        *out = new mfx_rec_s{r};
-        return MFX_OK;
+        return make_handle("mfx_rec_create", out, [&](Recommender** r) {
+            return Recommender::create(r, W, H, rows, cols, k, layout, exclude, space, device);
+        });
     });
 }
 int mfx_rec_query(mfx_rec_t r, int64_t nusers, const uint32_t* users, int32_t n_top, uint32_t* items, float* scores,
@@ -1064,10 +1018,7 @@ int mfx_rec_diversify_times(mfx_rec_t r, double seconds[3]) {
 }
 int mfx_rec_destroy(mfx_rec_t r) {
     return guarded("mfx_rec_destroy", [&]() -> int {
-        if (!r) return MFX_OK;
-        delete r->impl;
-        delete r;
-        return MFX_OK;
+        return destroy_handle(r);
     });
 }
 int mfx_topn_metrics(int64_t nusers, const uint32_t* users, int32_t n_top, const uint32_t* items, const mfx_coo* T,

@@ -4,17 +4,17 @@
 // the kernels and the sizing.  The inverse is ease_inverse.hip.
 //
 // Kernels:
-//   k_ease_diag       a wave per item: G_ii = fp32(d_i + lambda), d_i the integer sum of x_ui^2 over column i (k_slim_diag's);
-//   k_ease_gram       the build pass of item-kNN (knn_device.hpp: the work queue, BuildSrc::add_terms, the tile walk) with the
-//                     selection replaced by a dense write: with row i of X^T X in the LDS tile, the workgroup writes
+//   k_ease_diag       knn_diag: a wave per item, G_ii = fp32(d_i + lambda), d_i the integer sum of x_ui^2 over column i;
+//   k_ease_gram       the build pass of item-kNN (knn_device.hpp: knn_build_items, BuildSrc::add_terms, knn_build_tiles) with
+//                     the selection replaced by a dense write: with row i of X^T X in the LDS tile, the workgroup writes
 //                     from_fixed(acc[t]) to G[i][base + t] (coalesced) and clears the tile;
 //   k_ease_pdiag      P_jj into a vector, a P_jj that is not finite or not > 0 named;
 //   k_ease_weights    elementwise, in place over P;
 //   k_ease_check      a given B: finite, zero diagonal;
 //   k_ease_recommend  a workgroup per query row walks the item axis in tiles of T; a thread owns the items tid + 512 q of the
 //                     tile in registers, every wave walks the row's entries (64 at a time, broadcast), kKnnBatch entries'
-//                     loads of B[i_e][base ...] in flight; the scores go to the LDS tile and the dense scan of knn_device.hpp
-//                     selects.
+//                     loads of B[i_e][base ...] in flight; the scores go to the LDS tile and knn_scan over KeyOfBits
+//                     selects (knn_begin, knn_drop_seen and the host side, rows_recommend, are knn_device.hpp's too).
 #include <memory>
 
 #include "ease.hpp"
@@ -31,65 +31,28 @@ __device__ __forceinline__ float add_rn(float a, float b) {
     return a + b;
 }
 
+// G_ii = fp32(d_i + lambda), d_i the fp32 of the integer sum of fp32(x * x) over column i.
 __global__ __launch_bounds__(256) void k_ease_diag(const uint32_t* __restrict__ cptr, const float* __restrict__ cval, uint32_t cols, float lambda,
                                                    float* __restrict__ G, uint32_t* first_bad) {
-    const int lane = threadIdx.x & 63;
-    const uint64_t nw = (uint64_t) gridDim.x * (blockDim.x >> 6);
-    for (uint64_t i = (uint64_t) blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); i < cols; i += nw) {
-        const uint32_t c0 = cptr[i], c1 = cptr[i + 1];
-        unsigned long long sum = 0;
-        bool bad = false;
-        for (uint64_t e = (uint64_t) c0 + lane; e < c1; e += 64) {
-            const float x = cval[e];
-            const float t = mul_rn(x, x);
-            if (!(t < 64.f)) bad = true;  // (NaN compares false)
-            else sum += to_fixed(t);
-        }
-        for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off);
-        if (bad) atomicMin(first_bad, (uint32_t) i);
-        if (lane == 0) G[(size_t) i * cols + i] = add_rn(from_fixed(sum), lambda);
-    }
+    knn_diag(cptr, cval, cols, first_bad, [&](uint64_t i, float di) { G[(size_t) i * cols + i] = add_rn(di, lambda); });
 }
 
-struct EaseGramArgs {
-    const uint32_t* ptr;
-    const uint32_t* idx;
-    const float* val;
-    const uint32_t* cptr;
-    const uint32_t* ridx;
-    const float* cval;
-    const uint32_t* order;  // [cols] the items, heaviest first
-    uint32_t* queue;        // the next position of `order`
-    uint32_t* first_bad;    // the smallest item with a bad term
-    float* G;               // [cols][cols]; the diagonal is k_ease_diag's
-    uint32_t cols, T;
+struct EaseGramArgs : BuildArgs {
+    float* G;  // [cols][cols]; the diagonal is k_ease_diag's
 };
 
 __global__ __launch_bounds__(kKnnThreads) void k_ease_gram(EaseGramArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char ease_raw[];
     const KnnLds s = knn_lds(ease_raw, (int) a.T, 0);  // the tile and ctl: no candidate area
-    knn_zero_tile(s, a.T);
-    for (;;) {
-        if (threadIdx.x == 0) s.ctl[4] = atomicAdd(a.queue, 1u);
-        __syncthreads();
-        const uint32_t pos = s.ctl[4];
-        if (pos >= a.cols) break;
-        const uint32_t i = a.order[pos];
-        const BuildSrc src{a.ptr, a.idx, a.val, a.ridx, a.cval, a.cptr[i], a.cptr[i + 1], i};
-        float* row = a.G + (size_t) i * a.cols;
-        bool bad = false;
-        for (uint32_t base = 0; base < a.cols; base += min(a.T, a.cols - base)) {
-            const uint32_t len = min(a.T, a.cols - base);
-            bad |= src.add_terms(s.acc, base, len);
-            __syncthreads();
+    knn_build_items(s, a, [&](const BuildSrc& src) {
+        float* row = a.G + (size_t) src.item * a.cols;
+        return knn_build_tiles(s, src, a.cols, a.T, [&](uint32_t base, uint32_t len) {
             for (uint32_t t = threadIdx.x; t < len; t += kKnnThreads) {
-                if (base + t != i) row[base + t] = from_fixed(s.acc[t]);
+                if (base + t != src.item) row[base + t] = from_fixed(s.acc[t]);
                 s.acc[t] = 0ull;
             }
-            __syncthreads();
-        }
-        if (bad) atomicMin(a.first_bad, i);
-    }
+        });
+    });
 }
 
 // d[j] = P_jj; the smallest j whose P_jj is not finite or not > 0 goes to first_bad.
@@ -120,17 +83,8 @@ __global__ __launch_bounds__(256) void k_ease_check(const float* __restrict__ B,
     }
 }
 
-struct EaseRecArgs {
-    const uint32_t* ptr;   // [nusers + 1]
-    const uint32_t* idx;
-    const float* val;
-    const float* B;        // [cols][cols]
-    uint32_t* items;       // [nusers][n_top]
-    float* scores;         // or NULL
-    unsigned long long* bad_rows;
-    uint32_t nusers, cols, T;
-    int n_top, NC;
-    bool keep_seen;
+struct EaseRecArgs : RowsArgs {
+    const float* B;  // [cols][cols]
 };
 
 __global__ __launch_bounds__(kKnnThreads) void k_ease_recommend(EaseRecArgs a) {
@@ -148,7 +102,7 @@ __global__ __launch_bounds__(kKnnThreads) void k_ease_recommend(EaseRecArgs a) {
         bad = __syncthreads_or(bad);
         int count = 0;
         if (!bad && n > 0) {  // (an empty row: pads, and not bad)
-            knn_dense_begin(s);
+            knn_begin(s);
             for (uint32_t base = 0; base < a.cols; base += min(a.T, a.cols - base)) {
                 const uint32_t len = min(a.T, a.cols - base);
                 const int nq = (int) ((len + kKnnThreads - 1) / kKnnThreads);  // (the same for every thread)
@@ -187,13 +141,10 @@ __global__ __launch_bounds__(kKnnThreads) void k_ease_recommend(EaseRecArgs a) {
                 }
                 __syncthreads();
                 if (!a.keep_seen) {
-                    for (uint32_t e = tid; e < n; e += kKnnThreads) {
-                        const uint32_t off = idx[e] - base;
-                        if (off < len) s.acc[off] = 0ull;
-                    }
+                    knn_drop_seen(s.acc, idx, n, base, len);
                     __syncthreads();
                 }
-                knn_dense_scan(s, base, len, a.n_top);
+                knn_scan(s, base, len, a.n_top, KeyOfBits());
             }
             count = knn_sort_keep(s, a.n_top);
         }
@@ -219,36 +170,19 @@ int check_inv_flags(const char* fn, int flags) {
     return MFX_OK;
 }
 
-int alloc_named(const char* fn, const char* what, DevBuf<float>* buf, size_t count) {
-    if (buf->alloc(count) != MFX_OK) return fail(MFX_ERR_ALLOC, "%s: %s, %zu bytes, could not be allocated", fn, what, count * sizeof(float));
-    return MFX_OK;
-}
-
 uint32_t grid_stride(size_t total, int cus) { return (uint32_t) std::min<size_t>((total + 255) / 256, (size_t) cus * 32); }
 
 // The Gram pass: G [cols][cols] on the device from the checked matrix.
 int gram_pass(const char* fn, const StagedX& x, const DevBuf<uint32_t>& order, float lambda, uint32_t T, int cus, hipStream_t st, float* G) {
-    const uint32_t cols = x.cols;
-    FirstBad bad_term;
-    MFX_TRY(bad_term.init(st));
-    DevBuf<uint32_t> queue;
-    MFX_TRY(queue.alloc_zero(1, st));
-    hipLaunchKernelGGL(k_ease_diag, dim3(grid_256((uint64_t) cols * 64)), dim3(256), 0, st, x.cptr.p, x.cval.p, cols, lambda, G, bad_term.w.get());
+    BuildPass pass;
+    MFX_TRY(pass.begin(st));
+    hipLaunchKernelGGL(k_ease_diag, dim3(grid_256((uint64_t) x.cols * 64)), dim3(256), 0, st, x.cptr.p, x.cval.p, x.cols, lambda, G,
+                       pass.bad_term.w.get());
     MFX_LAUNCH_CHECK();
     EaseGramArgs a{};
-    a.ptr = x.ptr.p; a.idx = x.idx.p; a.val = x.val.p;
-    a.cptr = x.cptr.p; a.ridx = x.ridx.p; a.cval = x.cval.p;
-    a.order = order.get(); a.queue = queue.get(); a.first_bad = bad_term.w.get();
-    a.G = G; a.cols = cols; a.T = T;
-    const size_t lds = (size_t) T * 8 + 4 * kKnnCtlWords;
-    MFX_TRY(allow_lds(k_ease_gram, lds));
-    const uint32_t grid = (uint32_t) std::min<uint64_t>(cols, (uint64_t) cus * 2);
-    hipLaunchKernelGGL(k_ease_gram, dim3(grid), dim3(kKnnThreads), lds, st, a);
-    MFX_LAUNCH_CHECK();
-    uint32_t first = kNone;
-    MFX_TRY(bad_term.read(st, &first));
-    MFX_REQUIRE(first == kNone, "%s: item %u: a term x_ui * x_uj that is not finite or of magnitude >= 64", fn, first);
-    return MFX_OK;
+    pass.fill(&a, x, order, T);
+    a.G = G;
+    return pass.run(k_ease_gram, fn, a, knn_tile_bytes(T), cus, st);
 }
 
 // P ~ G^-1 on the device (both [n][n]); the workspace lives for the call.  Synchronises.
@@ -283,24 +217,12 @@ int weights_pass(const char* fn, uint32_t n, const float* P, float* B, int cus, 
     return MFX_OK;
 }
 
-// An [n][n] result of a stand-alone call: the caller's own device array, or a device buffer copied out at the end.
-struct Result {
-    DevBuf<float> own;
-    float* p = nullptr;
-    int set(const char* fn, const char* what, float* out, size_t count, mfx_memspace space) {
-        p = out;
-        if (space == MFX_HOST) {
-            MFX_TRY(alloc_named(fn, what, &own, count));
-            p = own.get();
-        }
-        return MFX_OK;
-    }
-    int finish(float* out, size_t count, mfx_memspace space, hipStream_t st) {
-        if (space == MFX_HOST) MFX_HIP(hipMemcpyAsync(out, p, sizeof(float) * count, hipMemcpyDeviceToHost, st));
-        MFX_HIP(hipStreamSynchronize(st));
-        return MFX_OK;
-    }
-};
+// The end of a stand-alone call with an [n][n] result.  Synchronises.
+int finish(Out<float>& r, float* out, size_t count, mfx_memspace space, hipStream_t st) {
+    MFX_TRY(r.copy_out(out, count, space, st));
+    MFX_HIP(hipStreamSynchronize(st));
+    return MFX_OK;
+}
 
 }  // namespace
 
@@ -330,10 +252,10 @@ int Ease::gram(const mfx_csx* X, float lambda, int32_t tile_items, float* G, mfx
     DevBuf<uint32_t> order;
     MFX_TRY(work_order(fn, x, st, &order));
     const size_t nn = (size_t) X->cols * X->cols;
-    Result g;
-    MFX_TRY(g.set(fn, "the Gram matrix [cols][cols]", G, nn, space));
+    Out<float> g;
+    MFX_TRY(g.set(G, nn, space, fn, "the Gram matrix [cols][cols]"));
     MFX_TRY(gram_pass(fn, x, order, lambda, T, cus, st, g.p));
-    return g.finish(G, nn, space, st);
+    return finish(g, G, nn, space, st);
 }
 
 int Ease::inverse(int64_t n, const float* A, float* Ainv, int flags, mfx_memspace space, int device) {
@@ -347,10 +269,10 @@ int Ease::inverse(int64_t n, const float* A, float* Ainv, int flags, mfx_memspac
     const size_t nn = (size_t) n * n;
     Staged<float> a;
     MFX_TRY(a.set(A, nn, space, st));
-    Result p;
-    MFX_TRY(p.set(fn, "the inverse [n][n]", Ainv, nn, space));
+    Out<float> p;
+    MFX_TRY(p.set(Ainv, nn, space, fn, "the inverse [n][n]"));
     MFX_TRY(inverse_pass(fn, (uint32_t) n, a.p, p.p, flags, st));
-    return p.finish(Ainv, nn, space, st);
+    return finish(p, Ainv, nn, space, st);
 }
 
 int Ease::weights_from_inverse(int64_t n, const float* P, float* B, mfx_memspace space, int device) {
@@ -365,10 +287,10 @@ int Ease::weights_from_inverse(int64_t n, const float* P, float* B, mfx_memspace
     const size_t nn = (size_t) n * n;
     Staged<float> p;
     MFX_TRY(p.set(P, nn, space, st));
-    Result b;
-    MFX_TRY(b.set(fn, "the weights [n][n]", B, nn, space));
+    Out<float> b;
+    MFX_TRY(b.set(B, nn, space, fn, "the weights [n][n]"));
     MFX_TRY(weights_pass(fn, (uint32_t) n, p.p, b.p, cus, st));
-    return b.finish(B, nn, space, st);
+    return finish(b, B, nn, space, st);
 }
 
 int Ease::train(Ease** out, const mfx_csx* X, float lambda, int flags, int32_t tile_items, mfx_memspace space, int device) {
@@ -453,85 +375,9 @@ int Ease::weights(int64_t first, int64_t count, float* B_rows, mfx_memspace spac
 
 int Ease::recommend(int64_t nusers, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val, int32_t n_top, int flags,
                     int32_t tile_items, uint32_t* items, float* scores, int64_t* bad_rows, mfx_memspace space) {
-    const char* fn = "mfx_ease_recommend";
-    MFX_TRY(check_space(fn, space));
-    MFX_REQUIRE(n_top >= 1 && n_top <= 1024, "%s: n_top must be in [1, 1024] (got %d)", fn, n_top);
-    MFX_REQUIRE((flags & ~MFX_KNN_KEEP_SEEN) == 0, "%s: unknown flag bits 0x%x", fn, (unsigned) flags);
-    MFX_REQUIRE(nusers >= 0 && nusers < 0xFFFFFFFFll && nnz >= 0 && nnz < 0xFFFFFFFFll, "%s: nusers and nnz must be in [0, 2^32 - 1)", fn);
-    uint32_t T = 0;
-    MFX_TRY(pick_tile(fn, tile_items, cols_, n_top, &T));
-    if (bad_rows) *bad_rows = 0;
-    if (nusers == 0) return MFX_OK;
-    MFX_REQUIRE(ptr && items, "%s: ptr or items is NULL", fn);
-    MFX_REQUIRE(nnz == 0 || (idx && val), "%s: idx or val is NULL", fn);
-    MFX_TRY(use_device(device_));
-    hipStream_t st = st_;
-    hipEvent_t ev[3] = {};
-    struct EvGuard {
-        hipEvent_t* e;
-        ~EvGuard() {
-            for (int i = 0; i < 3; ++i)
-                if (e[i]) (void) hipEventDestroy(e[i]);
-        }
-    } guard{ev};
-    for (auto& e : ev) MFX_HIP(hipEventCreate(&e));
-    Staged<uint32_t> sp, si;
-    Staged<float> sv;
-    MFX_TRY(sp.set(ptr, (size_t) nusers + 1, space, st));
-    MFX_TRY(si.set(idx, (size_t) nnz, space, st));
-    MFX_TRY(sv.set(val, (size_t) nnz, space, st));
-    const size_t total = (size_t) nusers * n_top;
-    DevBuf<uint32_t> oi;
-    DevBuf<float> os;
-    uint32_t* di = items;
-    float* dsc = scores;
-    if (space == MFX_HOST) {
-        MFX_TRY(oi.alloc(total));
-        di = oi.get();
-        if (scores) {
-            MFX_TRY(os.alloc(total));
-            dsc = os.get();
-        }
-    }
-    DevBuf<unsigned long long> nbad;
-    MFX_TRY(nbad.alloc_zero(1, st));
-    FirstBad bad;
-    MFX_TRY(bad.init(st));
-    MFX_HIP(hipEventRecord(ev[0], st));
-    hipLaunchKernelGGL(k_knn_check, dim3(grid_256((uint64_t) nusers)), dim3(256), 0, st, sp.p, si.p, (uint32_t) nusers, (uint32_t) cols_, (uint32_t) nnz,
-                       bad.w.get());
-    MFX_LAUNCH_CHECK();
-    MFX_HIP(hipEventRecord(ev[1], st));
-    uint32_t first = kNone;
-    MFX_TRY(bad.read(st, &first));
-    MFX_REQUIRE(first == kNone, "%s: row %u: its pointers must ascend from 0 to nnz and its ids be strictly ascending and below cols", fn, first);
-
-    EaseRecArgs a{};
-    a.ptr = sp.p; a.idx = si.p; a.val = sv.p; a.B = B_.get();
-    a.items = di; a.scores = dsc; a.bad_rows = nbad.get();
-    a.nusers = (uint32_t) nusers; a.cols = (uint32_t) cols_; a.T = T;
-    a.n_top = n_top; a.NC = knn_area(n_top);
-    a.keep_seen = (flags & MFX_KNN_KEEP_SEEN) != 0;
-    const size_t lds = knn_lds_bytes((int) T, n_top);
-    MFX_TRY(allow_lds(k_ease_recommend, lds));
-    const uint32_t grid = (uint32_t) std::min<uint64_t>((uint64_t) nusers, (uint64_t) cus_ * 8);
-    hipLaunchKernelGGL(k_ease_recommend, dim3(grid), dim3(kKnnThreads), lds, st, a);
-    MFX_LAUNCH_CHECK();
-    MFX_HIP(hipEventRecord(ev[2], st));
-    unsigned long long hbad = 0;
-    MFX_HIP(hipMemcpyAsync(&hbad, nbad.get(), sizeof(hbad), hipMemcpyDeviceToHost, st));
-    if (space == MFX_HOST) {
-        MFX_HIP(hipMemcpyAsync(items, di, sizeof(uint32_t) * total, hipMemcpyDeviceToHost, st));
-        if (scores) MFX_HIP(hipMemcpyAsync(scores, dsc, sizeof(float) * total, hipMemcpyDeviceToHost, st));
-    }
-    MFX_HIP(hipStreamSynchronize(st));
-    float ms = 0.f;
-    MFX_HIP(hipEventElapsedTime(&ms, ev[0], ev[1]));
-    t_[4] += 1e-3 * ms;
-    MFX_HIP(hipEventElapsedTime(&ms, ev[1], ev[2]));
-    t_[5] += 1e-3 * ms;
-    if (bad_rows) *bad_rows = (int64_t) hbad;
-    return MFX_OK;
+    return rows_recommend(k_ease_recommend, "mfx_ease_recommend", cols_, cus_, device_, st_, &t_[4], &t_[5],
+                          RowsQuery{nusers, nnz, ptr, idx, val, n_top, flags, tile_items, items, scores, bad_rows, space},
+                          [&](EaseRecArgs* a) { a->B = B_.get(); });
 }
 
 }  // namespace mfx

@@ -1,6 +1,6 @@
-// knn_device.hpp -- the device skeleton and the host helpers that the units on the interaction matrix share: knn.hip
-// (mfx_knn_*), slim.hip (mfx_slim_*) and ease.hip (mfx_ease_*).  Everything here sits in an anonymous namespace: each unit
-// compiles its own copy, as knn.hip did while this text was part of it.
+// knn_device.hpp -- the shared layer of the item models on the interaction matrix: knn.hip (mfx_knn_*), slim.hip (mfx_slim_*)
+// and ease.hip (mfx_ease_*).  Everything here sits in an anonymous namespace: each unit compiles its own copy, as knn.hip did
+// while this text was part of it.  DESIGN 5.20 lists which kernel is an instance of what.
 //
 // A workgroup owns one output row (the neighbours of an item, the scores of a query user, a row of X^T X) and walks the item
 // axis in tiles of T accumulators:
@@ -12,8 +12,11 @@
 //            the LDS candidate area behind the list; one that finds the area full stays in its accumulator, list and
 //            candidates are sorted together (bitonic, the total order beats()), the best `keep` stay, and the tile is
 //            scanned again for what is left.
-// knn_row is scan and select over a term source; slim.hip's Gram pass keeps `add` and gathers from the tile instead, ease.hip's
-// writes the tile out densely; ease.hip's recommendation fills the tile with fp32 scores and selects with knn_dense_scan.
+// Device side: knn_begin / knn_scan / knn_sort_keep are the selection (knn_scan over KeyOfSum for sums, over KeyOfBits for
+// ease.hip's fp32 scores), knn_row is add, scan and select over a term source, BuildSrc the term source of the three build
+// kernels and knn_build_items / knn_build_tiles their work queue and tile walk, knn_diag the diagonal of X^T X, k_knn_rows the recommend kernel of item-kNN and SLIM.
+// Host side: the checks of the matrix (check_x, StagedX, work_order), Staged / Out for arrays in either memory space,
+// BuildPass for the launch of a build kernel and rows_recommend, the one body of the three mfx_*_recommend.
 #pragma once
 
 #include <algorithm>
@@ -47,7 +50,7 @@ __device__ __forceinline__ unsigned long long to_fixed(float x) {
     return (unsigned long long) (long long) ((double) x * 68719476736.0);
 }
 
-// The fp32 of an integer sum: one rounding int64 -> fp32, then the exact 2^-36 (what knn_row's scan does in line).
+// The fp32 of an integer sum: one rounding int64 -> fp32, then the exact 2^-36 (KeyOfSum: the key of knn_row's scan).
 __device__ __forceinline__ float from_fixed(unsigned long long v) {
     return mul_rn((float) (long long) v, 1.4551915228366852e-11f);
 }
@@ -114,59 +117,8 @@ __device__ int knn_sort_keep(const KnnLds& s, int keep) {
     return kept;
 }
 
-// One output row: the tiles of the item axis, the terms of `src`, the best `keep` candidates.  On return key / id [0 .. count)
-// hold them in order and ctl[3] says whether a thread met a bad term.  The accumulators are all zero on entry and on return.
-template <class Src>
-__device__ int knn_row(const KnnLds& s, const Src& src, uint32_t cols, uint32_t T, int keep) {
-    const int tid = threadIdx.x;
-    if (tid == 0) {
-        s.ctl[0] = 0;
-        s.ctl[1] = kPad;
-        s.ctl[2] = __float_as_uint(-INFINITY);
-        s.ctl[3] = 0;
-    }
-    __syncthreads();
-    bool bad = false;
-    for (uint32_t base = 0; base < cols; base += min(T, cols - base)) {
-        const uint32_t len = min(T, cols - base);
-        bad |= src.add_terms(s.acc, base, len);
-        __syncthreads();
-        if (src.drop_seen(s.acc, base, len)) __syncthreads();
-        // The scan runs over the whole tile without a barrier.  A candidate that finds the area full stays in its
-        // accumulator; then list and area are merged, which raises the threshold, and the tile is scanned again for what
-        // is left.  Every pass places at least NC - keep candidates or ends the tile.
-        for (;;) {
-            const float thr_key = __uint_as_float(s.ctl[2]);
-            const uint32_t thr_id = s.ctl[1];
-            for (uint32_t slot = tid; slot < len; slot += kKnnThreads) {
-                const unsigned long long v = s.acc[slot];
-                if (v == 0ull) continue;
-                const float key = mul_rn((float) (long long) v, 1.4551915228366852e-11f);  // one rounding int64 -> fp32, then the exact 2^-36
-                const uint32_t item = base + slot;
-                if (beats(key, item, thr_key, thr_id)) {
-                    const uint32_t pos = atomicAdd(&s.ctl[0], 1u);
-                    if (pos >= (uint32_t) s.NC) continue;
-                    s.key[pos] = key;
-                    s.id[pos] = item;
-                }
-                s.acc[slot] = 0ull;
-            }
-            __syncthreads();
-            if (s.ctl[0] <= (uint32_t) s.NC) break;  // (nobody touches ctl[0] again before the next barrier)
-            knn_sort_keep(s, keep);
-        }
-    }
-    if (bad) s.ctl[3] = 1;
-    return knn_sort_keep(s, keep);  // (its barriers publish ctl[3])
-}
-
-// The sibling of knn_row's scan for scores that are not sums on the grid (ease.hip): every ELIGIBLE slot of the tile is a
-// candidate, zero and negative keys included.  A slot holds kKnnLive | the bits of its fp32 key, or 0 when it is not eligible
-// (an item of the row, a NaN score) or already taken.  Same threshold, area and merge as above; the tile is all zeros on
-// return.  knn_dense_begin resets the selection at the start of a row; the caller ends the row with knn_sort_keep.
-constexpr unsigned long long kKnnLive = 1ull << 32;
-
-__device__ inline void knn_dense_begin(const KnnLds& s) {
+// The start of a row's selection: an empty list, no threshold, no bad term.
+__device__ inline void knn_begin(const KnnLds& s) {
     if (threadIdx.x == 0) {
         s.ctl[0] = 0;
         s.ctl[1] = kPad;
@@ -176,7 +128,22 @@ __device__ inline void knn_dense_begin(const KnnLds& s) {
     __syncthreads();
 }
 
-__device__ inline void knn_dense_scan(const KnnLds& s, uint32_t base, uint32_t len, int keep) {
+// How a slot's 64 bits become a key.  KeyOfSum: the slot is an integer sum on the 2^-36 grid.  KeyOfBits: scores that are not
+// sums on the grid (ease.hip) -- a slot holds kKnnLive | the bits of its fp32 key, or 0 when it is not eligible (an item of
+// the row, a NaN score) or already taken, so that zero and negative keys are candidates too.
+constexpr unsigned long long kKnnLive = 1ull << 32;
+struct KeyOfSum {
+    __device__ float operator()(unsigned long long v) const { return from_fixed(v); }
+};
+struct KeyOfBits {
+    __device__ float operator()(unsigned long long v) const { return __uint_as_float((uint32_t) v); }
+};
+
+// Scan and select over one tile, without a barrier before the end of a pass.  A candidate that finds the area full stays in
+// its slot; then list and area are merged, which raises the threshold, and the tile is scanned again for what is left.
+// Every pass places at least NC - keep candidates or ends the tile.  The tile is all zeros on return.
+template <class Key>
+__device__ void knn_scan(const KnnLds& s, uint32_t base, uint32_t len, int keep, Key key_of) {
     const int tid = threadIdx.x;
     for (;;) {
         const float thr_key = __uint_as_float(s.ctl[2]);
@@ -184,7 +151,7 @@ __device__ inline void knn_dense_scan(const KnnLds& s, uint32_t base, uint32_t l
         for (uint32_t slot = tid; slot < len; slot += kKnnThreads) {
             const unsigned long long v = s.acc[slot];
             if (v == 0ull) continue;
-            const float key = __uint_as_float((uint32_t) v);
+            const float key = key_of(v);
             const uint32_t item = base + slot;
             if (beats(key, item, thr_key, thr_id)) {
                 const uint32_t pos = atomicAdd(&s.ctl[0], 1u);
@@ -197,6 +164,31 @@ __device__ inline void knn_dense_scan(const KnnLds& s, uint32_t base, uint32_t l
         __syncthreads();
         if (s.ctl[0] <= (uint32_t) s.NC) break;  // (nobody touches ctl[0] again before the next barrier)
         knn_sort_keep(s, keep);
+    }
+}
+
+// One output row: the tiles of the item axis, the terms of `src`, the best `keep` candidates.  On return key / id [0 .. count)
+// hold them in order and ctl[3] says whether a thread met a bad term.  The accumulators are all zero on entry and on return.
+template <class Src>
+__device__ int knn_row(const KnnLds& s, const Src& src, uint32_t cols, uint32_t T, int keep) {
+    knn_begin(s);
+    bool bad = false;
+    for (uint32_t base = 0; base < cols; base += min(T, cols - base)) {
+        const uint32_t len = min(T, cols - base);
+        bad |= src.add_terms(s.acc, base, len);
+        __syncthreads();
+        if (src.drop_seen(s.acc, base, len)) __syncthreads();
+        knn_scan(s, base, len, keep, KeyOfSum());
+    }
+    if (bad) s.ctl[3] = 1;
+    return knn_sort_keep(s, keep);  // (its barriers publish ctl[3])
+}
+
+// The items of a query row are no candidates: their slots of the tile are cleared.
+__device__ inline void knn_drop_seen(unsigned long long* acc, const uint32_t* idx, uint32_t n, uint32_t base, uint32_t len) {
+    for (uint32_t e = threadIdx.x; e < n; e += kKnnThreads) {
+        const uint32_t off = idx[e] - base;
+        if (off < len) acc[off] = 0ull;
     }
 }
 
@@ -281,6 +273,121 @@ __device__ inline void knn_store(const KnnLds& s, int count, int width, bool ok,
     }
 }
 
+// ---------------------------------------------------------------------------------------------- the build kernels' queue
+// What k_knn_build, k_slim_gram and k_ease_gram take alike: the matrix in both orientations and the work queue.
+struct BuildArgs {
+    const uint32_t* ptr;
+    const uint32_t* idx;
+    const float* val;
+    const uint32_t* cptr;
+    const uint32_t* ridx;
+    const float* cval;
+    const uint32_t* order;  // [cols] the items, heaviest first
+    uint32_t* queue;        // the next position of `order`
+    uint32_t* first_bad;    // the smallest item with a bad term
+    uint32_t cols, T;
+};
+
+// The workgroup's loop over the queue: zero the tile, then item by item -- the next position of `order` through ctl[4] --
+// row(src) with the term source of the item.  row leaves the tile zero and returns whether this thread names the item for
+// a bad term.
+template <class Row>
+__device__ void knn_build_items(const KnnLds& s, const BuildArgs& a, Row row) {
+    knn_zero_tile(s, a.T);
+    for (;;) {
+        if (threadIdx.x == 0) s.ctl[4] = atomicAdd(a.queue, 1u);
+        __syncthreads();
+        const uint32_t pos = s.ctl[4];
+        if (pos >= a.cols) break;
+        const uint32_t i = a.order[pos];
+        const BuildSrc src{a.ptr, a.idx, a.val, a.ridx, a.cval, a.cptr[i], a.cptr[i + 1], i};
+        if (row(src)) atomicMin(a.first_bad, i);
+    }
+}
+
+// The tiles of one item's row of X^T X for a kernel that does not select: add the terms, then tile(base, len) reads the
+// sums and clears them (the barrier between the two is here, the one after the clearing too).  Returns the thread's bad flag.
+template <class Tile>
+__device__ bool knn_build_tiles(const KnnLds& s, const BuildSrc& src, uint32_t cols, uint32_t T, Tile tile) {
+    bool bad = false;
+    for (uint32_t base = 0; base < cols; base += min(T, cols - base)) {
+        const uint32_t len = min(T, cols - base);
+        bad |= src.add_terms(s.acc, base, len);
+        __syncthreads();
+        tile(base, len);
+        __syncthreads();
+    }
+    return bad;
+}
+
+// The diagonal of X^T X, a wave per item (blocks of 256 threads): done(i, d_i) on lane 0 with d_i the fp32 of the integer sum
+// of fp32(x * x) over column i; a bad term names the item.  The body of k_slim_diag and k_ease_diag.
+template <class Done>
+__device__ void knn_diag(const uint32_t* __restrict__ cptr, const float* __restrict__ cval, uint32_t cols, uint32_t* first_bad, Done done) {
+    const int lane = threadIdx.x & 63;
+    const uint64_t nw = (uint64_t) gridDim.x * (blockDim.x >> 6);
+    for (uint64_t i = (uint64_t) blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); i < cols; i += nw) {
+        const uint32_t c0 = cptr[i], c1 = cptr[i + 1];
+        unsigned long long sum = 0;
+        bool bad = false;
+        for (uint64_t e = (uint64_t) c0 + lane; e < c1; e += 64) {
+            const float x = cval[e];
+            const float t = mul_rn(x, x);
+            if (!(t < 64.f)) bad = true;  // (NaN compares false)
+            else sum += to_fixed(t);
+        }
+        for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off);
+        if (bad) atomicMin(first_bad, (uint32_t) i);
+        if (lane == 0) done(i, from_fixed(sum));
+    }
+}
+
+// ---------------------------------------------------------------------------------------------- the recommend kernels' rows
+// What the three recommend kernels take alike: the query rows and the outputs.
+struct RowsArgs {
+    const uint32_t* ptr;   // [nusers + 1]
+    const uint32_t* idx;
+    const float* val;
+    uint32_t* items;       // [nusers][n_top]
+    float* scores;         // or NULL
+    unsigned long long* bad_rows;
+    uint32_t nusers, cols, T;
+    int n_top, NC;
+    bool keep_seen;
+};
+
+// The query row of a term source: its entries, and their slots cleared after the terms unless keep_seen.
+struct RowSrc {
+    const uint32_t* idx;
+    const float* val;
+    uint32_t n;
+    bool keep_seen;
+    __device__ bool drop_seen(unsigned long long* acc, uint32_t base, uint32_t len) const {
+        if (keep_seen) return false;
+        knn_drop_seen(acc, idx, n, base, len);
+        return true;
+    }
+};
+
+// A workgroup per query row: knn_row over the model's term source, Args::source(row).  A row of more than 2^21 entries or
+// with a bad term is all pads and counted in bad_rows.
+template <class Args>
+__global__ __launch_bounds__(kKnnThreads) void k_knn_rows(Args a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char knn_raw[];
+    const KnnLds s = knn_lds(knn_raw, (int) a.T, a.NC);
+    knn_zero_tile(s, a.T);
+    for (uint32_t r = blockIdx.x; r < a.nusers; r += gridDim.x) {
+        const uint32_t r0 = a.ptr[r], n = a.ptr[r + 1] - r0;
+        const bool too_long = n > kKnnMaxEntries;
+        const auto src = a.source(RowSrc{a.idx + r0, a.val + r0, too_long ? 0u : n, a.keep_seen});
+        const int count = knn_row(s, src, a.cols, a.T, a.n_top);
+        const bool ok = !too_long && !s.ctl[3];
+        knn_store(s, count, a.n_top, ok, a.items + (size_t) r * a.n_top, a.scores ? a.scores + (size_t) r * a.n_top : nullptr);
+        if (threadIdx.x == 0 && !ok) atomicAdd(a.bad_rows, 1ull);
+        __syncthreads();
+    }
+}
+
 // ---------------------------------------------------------------------------------------------- the kernels of the checks
 // Segment r of a compressed matrix: its pointers inside [0, nnz] and in order, its ids strictly ascending and below `bound`.
 __global__ void k_knn_check(const uint32_t* ptr, const uint32_t* idx, uint32_t nseg, uint32_t bound, uint32_t nnz, uint32_t* first_bad) {
@@ -353,6 +460,33 @@ struct Staged {
     }
 };
 
+// An allocation whose failure names what it was for.
+template <typename T>
+int alloc_named(const char* fn, const char* what, DevBuf<T>* buf, size_t count) {
+    if (buf->alloc(count) != MFX_OK) return fail(MFX_ERR_ALLOC, "%s: %s, %zu bytes, could not be allocated", fn, what, count * sizeof(T));
+    return MFX_OK;
+}
+
+// An output array on the device: the caller's own (MFX_DEVICE, or NULL for an output that is not asked for), or a device
+// buffer that copy_out copies to the host's at the end of the call.  `what` names the buffer in its allocation failure.
+template <typename T>
+struct Out {
+    DevBuf<T> own;
+    T* p = nullptr;
+    int set(T* out, size_t count, mfx_memspace space, const char* fn = nullptr, const char* what = nullptr) {
+        p = out;
+        if (space == MFX_HOST && out) {
+            MFX_TRY(what ? alloc_named(fn, what, &own, count) : own.alloc(count));
+            p = own.get();
+        }
+        return MFX_OK;
+    }
+    int copy_out(T* out, size_t count, mfx_memspace space, hipStream_t st) {  // (asynchronous)
+        if (space == MFX_HOST && out) MFX_HIP(hipMemcpyAsync(out, p, sizeof(T) * count, hipMemcpyDeviceToHost, st));
+        return MFX_OK;
+    }
+};
+
 // One word on the device that kernels lower with atomicMin: kNone while nothing was found.
 struct FirstBad {
     DevBuf<uint32_t> w;
@@ -378,7 +512,7 @@ int allow_lds(Kern kern, size_t bytes) {
 
 double since(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); }
 
-// ---------------------------------------------------------------------------------------------- the matrix of slim.hip and ease.hip
+// ---------------------------------------------------------------------------------------------- the matrix of the three builds
 int check_x(const char* fn, const mfx_csx* X) {
     MFX_REQUIRE(X->nnz >= 1, "%s: the matrix has no entries", fn);
     MFX_REQUIRE(X->cols >= 2, "%s: cols must be at least 2 (got %lld)", fn, (long long) X->cols);
@@ -394,7 +528,7 @@ struct StagedX {
     Staged<float> val, cval;
     uint32_t rows = 0, cols = 0, nnz = 0;
 
-    // The six arrays on the device, their structure checked as by mfx_knn_build.
+    // The six arrays on the device, their structure checked: the row side first, then the column side.
     int set(const char* fn, const mfx_csx* X, mfx_memspace space, hipStream_t st) {
         rows = (uint32_t) X->rows; cols = (uint32_t) X->cols; nnz = (uint32_t) X->nnz;
         MFX_TRY(ptr.set(X->csr_row_ptr, (size_t) rows + 1, space, st));
@@ -448,6 +582,130 @@ int work_order(const char* fn, const StagedX& x, hipStream_t st, DevBuf<uint32_t
 int device_cus(int device, int* cus) {
     MFX_HIP(hipDeviceGetAttribute(cus, hipDeviceAttributeMultiprocessorCount, device));
     *cus = std::max(*cus, 1);
+    return MFX_OK;
+}
+
+// The launch of a build kernel (k_knn_build, k_slim_gram, k_ease_gram): begin() makes the word that names a bad term and
+// the zeroed queue word, fill() the shared fields of the kernel's arguments, run() launches min(cols, 2 * cus) workgroups
+// and reports the term.  Between begin() and run() the caller launches what shares the word (the diagonal kernels).
+struct BuildPass {
+    FirstBad bad_term;
+    DevBuf<uint32_t> queue;
+    int begin(hipStream_t st) {
+        MFX_TRY(bad_term.init(st));
+        MFX_TRY(queue.alloc_zero(1, st));
+        return MFX_OK;
+    }
+    void fill(BuildArgs* a, const StagedX& x, const DevBuf<uint32_t>& order, uint32_t T) const {
+        a->ptr = x.ptr.p; a->idx = x.idx.p; a->val = x.val.p;
+        a->cptr = x.cptr.p; a->ridx = x.ridx.p; a->cval = x.cval.p;
+        a->order = order.get(); a->queue = queue.get(); a->first_bad = bad_term.w.get();
+        a->cols = x.cols; a->T = T;
+    }
+    template <class Args>
+    int run(void (*kern)(Args), const char* fn, const Args& a, size_t lds, int cus, hipStream_t st) {  // synchronises
+        MFX_TRY(allow_lds(kern, lds));
+        const uint32_t grid = (uint32_t) std::min<uint64_t>(a.cols, (uint64_t) cus * 2);
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(kKnnThreads), lds, st, a);
+        MFX_LAUNCH_CHECK();
+        uint32_t first = kNone;
+        MFX_TRY(bad_term.read(st, &first));
+        MFX_REQUIRE(first == kNone, "%s: item %u: a term x_ui * x_uj that is not finite or of magnitude >= 64", fn, first);
+        return MFX_OK;
+    }
+};
+// The LDS of a build kernel that does not select: the tile and ctl.
+inline size_t knn_tile_bytes(uint32_t T) { return (size_t) T * 8 + 4 * kKnnCtlWords; }
+
+// ---------------------------------------------------------------------------------------------- the host side of recommend
+// The arguments of mfx_knn_recommend, mfx_slim_recommend and mfx_ease_recommend behind the handle.
+struct RowsQuery {
+    int64_t nusers, nnz;
+    const uint32_t* ptr;
+    const uint32_t* idx;
+    const float* val;
+    int32_t n_top;
+    int flags;
+    int32_t tile_items;
+    uint32_t* items;
+    float* scores;
+    int64_t* bad_rows;
+    mfx_memspace space;
+};
+
+// One recommend call of a model of `cols` items: the checks of the arguments, the rows on the device and their structure
+// check (its time goes to *t_check), `kern` with min(nusers, 8 * cus) workgroups (*t_pass), the results.  Args derives from
+// RowsArgs; fill(&args) sets the model's own fields.  One synchronisation at the end, after everything is queued.
+template <class Args, class Fill>
+int rows_recommend(void (*kern)(Args), const char* fn, int64_t cols, int cus, int device, hipStream_t st, double* t_check, double* t_pass,
+                   const RowsQuery& q, Fill fill) {
+    MFX_TRY(check_space(fn, q.space));
+    MFX_REQUIRE(q.n_top >= 1 && q.n_top <= 1024, "%s: n_top must be in [1, 1024] (got %d)", fn, q.n_top);
+    MFX_REQUIRE((q.flags & ~MFX_KNN_KEEP_SEEN) == 0, "%s: unknown flag bits 0x%x", fn, (unsigned) q.flags);
+    MFX_REQUIRE(q.nusers >= 0 && q.nusers < 0xFFFFFFFFll && q.nnz >= 0 && q.nnz < 0xFFFFFFFFll, "%s: nusers and nnz must be in [0, 2^32 - 1)", fn);
+    uint32_t T = 0;
+    MFX_TRY(pick_tile(fn, q.tile_items, cols, q.n_top, &T));
+    if (q.bad_rows) *q.bad_rows = 0;
+    if (q.nusers == 0) return MFX_OK;
+    MFX_REQUIRE(q.ptr && q.items, "%s: ptr or items is NULL", fn);
+    MFX_REQUIRE(q.nnz == 0 || (q.idx && q.val), "%s: idx or val is NULL", fn);
+    MFX_TRY(use_device(device));
+    hipEvent_t ev[3] = {};
+    struct EvGuard {
+        hipEvent_t* e;
+        ~EvGuard() {
+            for (int i = 0; i < 3; ++i)
+                if (e[i]) (void) hipEventDestroy(e[i]);
+        }
+    } guard{ev};
+    for (auto& e : ev) MFX_HIP(hipEventCreate(&e));
+    Staged<uint32_t> sp, si;
+    Staged<float> sv;
+    MFX_TRY(sp.set(q.ptr, (size_t) q.nusers + 1, q.space, st));
+    MFX_TRY(si.set(q.idx, (size_t) q.nnz, q.space, st));
+    MFX_TRY(sv.set(q.val, (size_t) q.nnz, q.space, st));
+    const size_t total = (size_t) q.nusers * q.n_top;
+    Out<uint32_t> oi;
+    Out<float> os;
+    MFX_TRY(oi.set(q.items, total, q.space));
+    MFX_TRY(os.set(q.scores, total, q.space));
+    DevBuf<unsigned long long> nbad;
+    MFX_TRY(nbad.alloc_zero(1, st));
+    FirstBad bad;
+    MFX_TRY(bad.init(st));
+    MFX_HIP(hipEventRecord(ev[0], st));
+    hipLaunchKernelGGL(k_knn_check, dim3(grid_256((uint64_t) q.nusers)), dim3(256), 0, st, sp.p, si.p, (uint32_t) q.nusers, (uint32_t) cols,
+                       (uint32_t) q.nnz, bad.w.get());
+    MFX_LAUNCH_CHECK();
+    MFX_HIP(hipEventRecord(ev[1], st));
+    uint32_t first = kNone;
+    MFX_TRY(bad.read(st, &first));
+    MFX_REQUIRE(first == kNone, "%s: row %u: its pointers must ascend from 0 to nnz and its ids be strictly ascending and below cols", fn, first);
+
+    Args a{};
+    a.ptr = sp.p; a.idx = si.p; a.val = sv.p;
+    a.items = oi.p; a.scores = os.p; a.bad_rows = nbad.get();
+    a.nusers = (uint32_t) q.nusers; a.cols = (uint32_t) cols; a.T = T;
+    a.n_top = q.n_top; a.NC = knn_area(q.n_top);
+    a.keep_seen = (q.flags & MFX_KNN_KEEP_SEEN) != 0;
+    fill(&a);
+    const size_t lds = knn_lds_bytes((int) T, q.n_top);
+    MFX_TRY(allow_lds(kern, lds));
+    const uint32_t grid = (uint32_t) std::min<uint64_t>((uint64_t) q.nusers, (uint64_t) cus * 8);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(kKnnThreads), lds, st, a);
+    MFX_LAUNCH_CHECK();
+    MFX_HIP(hipEventRecord(ev[2], st));
+    unsigned long long hbad = 0;
+    MFX_HIP(hipMemcpyAsync(&hbad, nbad.get(), sizeof(hbad), hipMemcpyDeviceToHost, st));
+    MFX_TRY(oi.copy_out(q.items, total, q.space, st));
+    MFX_TRY(os.copy_out(q.scores, total, q.space, st));
+    MFX_HIP(hipStreamSynchronize(st));
+    float ms = 0.f;
+    MFX_HIP(hipEventElapsedTime(&ms, ev[0], ev[1]));
+    *t_check += 1e-3 * ms;
+    MFX_HIP(hipEventElapsedTime(&ms, ev[1], ev[2]));
+    *t_pass += 1e-3 * ms;
+    if (q.bad_rows) *q.bad_rows = (int64_t) hbad;
     return MFX_OK;
 }
 

@@ -3,15 +3,16 @@
 // recommendation from the trained weights.  The contract -- the Gram entries (item-kNN's similarities plus a diagonal), each
 // fp32 operation of the solve in its order, the limits -- is in include/mfx.h; DESIGN 5.18 has the kernels and the sizing.
 //
-// Four kernels:
-//   k_slim_diag       a wave per item: d_a, the integer sum of x_ua^2 over column a;
-//   k_slim_gram       the build pass of item-kNN (knn_device.hpp: the work queue, BuildSrc::add_terms, the tile walk) with the
-//                     selection replaced by a gather.  With row a of X^T X in the LDS tile, the workgroup writes row K of block
-//                     a (a's own list) and, for every (j, p) of a's inverse list -- the lists S_j that hold a at slot p -- row p
-//                     of block j, for the slots whose ids lie in the tile; then it clears the tile;
+// Four kernels of its own and an instance of k_knn_rows (knn_device.hpp holds the layer shared with knn.hip and ease.hip):
+//   k_slim_diag       knn_diag: a wave per item, d_a the integer sum of x_ua^2 over column a;
+//   k_slim_gram       the build pass of item-kNN (knn_build_items, BuildSrc::add_terms, knn_build_tiles) with the selection
+//                     replaced by a gather.  With row a of X^T X in the LDS tile, the workgroup writes row K of block a (a's
+//                     own list) and, for every (j, p) of a's inverse list -- the lists S_j that hold a at slot p -- row p of
+//                     block j, for the slots whose ids lie in the tile; then it clears the tile;
 //   k_slim_solve      a wave per item: the block's Gram rows in LDS, lane b holds c_b and w_b (two per lane above K = 64), the
 //                     scalar chain of coordinate a is computed by every lane alike, the K updates read row a of G from LDS;
-//   k_slim_recommend  knn_row over the transpose: a wave takes 64 entries of the query row, then its lanes run across each list.
+//   k_knn_rows<SlimRecArgs>  knn_row over the transpose: a wave takes 64 entries of the query row, then its lanes run across
+//                     each list (behind rows_recommend on the host).
 // The inverse lists and the model's transpose are one structure (a counting sort on the host, targets ascending).
 #include <algorithm>
 #include <chrono>
@@ -58,68 +59,33 @@ __global__ void k_slim_check_support(const uint32_t* S, const float* w, uint32_t
     }
 }
 
-// d_a = the fp32 of the integer sum of fp32(x * x) over column a, a wave per item; a bad term names the item.
+// d_a = the fp32 of the integer sum of fp32(x * x) over column a.
 __global__ __launch_bounds__(256) void k_slim_diag(const uint32_t* __restrict__ cptr, const float* __restrict__ cval, uint32_t cols,
                                                    float* __restrict__ d, uint32_t* first_bad) {
-    const int lane = threadIdx.x & 63;
-    const uint64_t nw = (uint64_t) gridDim.x * (blockDim.x >> 6);
-    for (uint64_t i = (uint64_t) blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); i < cols; i += nw) {
-        const uint32_t c0 = cptr[i], c1 = cptr[i + 1];
-        unsigned long long sum = 0;
-        bool bad = false;
-        for (uint64_t e = (uint64_t) c0 + lane; e < c1; e += 64) {
-            const float x = cval[e];
-            const float t = mul_rn(x, x);
-            if (!(t < 64.f)) bad = true;  // (NaN compares false)
-            else sum += to_fixed(t);
-        }
-        for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off);
-        if (bad) atomicMin(first_bad, (uint32_t) i);
-        if (lane == 0) d[i] = from_fixed(sum);
-    }
+    knn_diag(cptr, cval, cols, first_bad, [&](uint64_t i, float di) { d[i] = di; });
 }
 
-struct SlimGramArgs {
-    const uint32_t* ptr;
-    const uint32_t* idx;
-    const float* val;
-    const uint32_t* cptr;
-    const uint32_t* ridx;
-    const float* cval;
-    const uint32_t* order;  // [cols] the items, heaviest first
-    uint32_t* queue;        // the next position of `order`
-    uint32_t* first_bad;    // the smallest item with a bad term
+struct SlimGramArgs : BuildArgs {
     const uint32_t* S;      // [cols][K]
     const uint32_t* iptr;   // [cols + 1] the inverse lists: item a -> the (j, p) with S[j][p] == a
     const uint32_t* tj;
     const uint32_t* tp;
     const float* d;         // [cols]
     float* blocks;          // [cols][K + 1][K], zero on entry
-    uint32_t cols, T;
     int K;
 };
 
 __global__ __launch_bounds__(kKnnThreads) void k_slim_gram(SlimGramArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char slim_raw[];
     const KnnLds s = knn_lds(slim_raw, (int) a.T, 0);  // the tile and ctl: no candidate area
-    knn_zero_tile(s, a.T);
     const uint32_t K = (uint32_t) a.K;
     const size_t blk = (size_t) (K + 1) * K;
-    for (;;) {
-        if (threadIdx.x == 0) s.ctl[4] = atomicAdd(a.queue, 1u);
-        __syncthreads();
-        const uint32_t pos = s.ctl[4];
-        if (pos >= a.cols) break;
-        const uint32_t i = a.order[pos];
-        const BuildSrc src{a.ptr, a.idx, a.val, a.ridx, a.cval, a.cptr[i], a.cptr[i + 1], i};
+    knn_build_items(s, a, [&](const BuildSrc& src) {
+        const uint32_t i = src.item;
         const uint32_t e0 = a.iptr[i];
         const uint64_t npairs = (uint64_t) (a.iptr[i + 1] - e0) * K;
         const float di = a.d[i];
-        bool bad = false;
-        for (uint32_t base = 0; base < a.cols; base += min(a.T, a.cols - base)) {
-            const uint32_t len = min(a.T, a.cols - base);
-            bad |= src.add_terms(s.acc, base, len);
-            __syncthreads();
+        return knn_build_tiles(s, src, a.cols, a.T, [&](uint32_t base, uint32_t len) {
             for (uint32_t t = threadIdx.x; t < K; t += kKnnThreads) {  // g of item i: row K of its own block
                 const uint32_t id = a.S[(size_t) i * K + t], off = id - base;
                 if (id != kPad && off < len) a.blocks[(size_t) i * blk + (size_t) K * K + t] = from_fixed(s.acc[off]);
@@ -134,10 +100,8 @@ __global__ __launch_bounds__(kKnnThreads) void k_slim_gram(SlimGramArgs a) {
             }
             __syncthreads();
             for (uint32_t t = threadIdx.x; t < len; t += kKnnThreads) s.acc[t] = 0ull;
-            __syncthreads();
-        }
-        if (bad) atomicMin(a.first_bad, i);
-    }
+        });
+    });
 }
 
 struct SlimSolveArgs {
@@ -231,14 +195,10 @@ __global__ void k_slim_transpose_weights(const float* w, const uint32_t* tj, con
 // time, a lane each for the two list pointers and, past the first tile, for the lower-bound search of the tile's start in
 // the ascending list; then list by list the lanes run across the targets, kKnnBatch loads in flight, and stop at the
 // tile's end.  The lists of popular sources are long (an item that many lists name), and they carry most of the work.
-struct SlimRecSrc {
-    const uint32_t* idx;   // the row's entries
-    const float* val;
-    uint32_t n;
+struct SlimRecSrc : RowSrc {
     const uint32_t* iptr;  // [cols + 1]
     const uint32_t* tj;
     const float* tw;
-    bool keep_seen;
 
     __device__ bool add_terms(unsigned long long* acc, uint32_t base, uint32_t len) const {
         const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -292,46 +252,14 @@ struct SlimRecSrc {
         }
         return bad;
     }
-    __device__ bool drop_seen(unsigned long long* acc, uint32_t base, uint32_t len) const {
-        if (keep_seen) return false;
-        for (uint32_t e = threadIdx.x; e < n; e += kKnnThreads) {
-            const uint32_t off = idx[e] - base;
-            if (off < len) acc[off] = 0ull;
-        }
-        return true;
-    }
 };
 
-struct SlimRecArgs {
-    const uint32_t* ptr;   // [nusers + 1]
-    const uint32_t* idx;
-    const float* val;
+struct SlimRecArgs : RowsArgs {
     const uint32_t* iptr;
     const uint32_t* tj;
     const float* tw;
-    uint32_t* items;       // [nusers][n_top]
-    float* scores;         // or NULL
-    unsigned long long* bad_rows;
-    uint32_t nusers, cols, T;
-    int n_top, NC;
-    bool keep_seen;
+    __device__ SlimRecSrc source(const RowSrc& row) const { return SlimRecSrc{row, iptr, tj, tw}; }
 };
-
-__global__ __launch_bounds__(kKnnThreads) void k_slim_recommend(SlimRecArgs a) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char slim_raw[];
-    const KnnLds s = knn_lds(slim_raw, (int) a.T, a.NC);
-    knn_zero_tile(s, a.T);
-    for (uint32_t r = blockIdx.x; r < a.nusers; r += gridDim.x) {
-        const uint32_t r0 = a.ptr[r], n = a.ptr[r + 1] - r0;
-        const bool too_long = n > kKnnMaxEntries;
-        const SlimRecSrc src{a.idx + r0, a.val + r0, too_long ? 0u : n, a.iptr, a.tj, a.tw, a.keep_seen};
-        const int count = knn_row(s, src, a.cols, a.T, a.n_top);
-        const bool ok = !too_long && !s.ctl[3];
-        knn_store(s, count, a.n_top, ok, a.items + (size_t) r * a.n_top, a.scores ? a.scores + (size_t) r * a.n_top : nullptr);
-        if (threadIdx.x == 0 && !ok) atomicAdd(a.bad_rows, 1ull);
-        __syncthreads();
-    }
-}
 
 // ---------------------------------------------------------------------------------------------- host helpers
 int check_params(const char* fn, int32_t K, const SlimParams& p) {
@@ -403,39 +331,25 @@ struct Support {
 int gram_pass(const char* fn, const StagedX& x, const DevBuf<uint32_t>& order, const uint32_t* S, const uint32_t* iptr, const uint32_t* tj,
               const uint32_t* tp, int K, uint32_t T, int cus, hipStream_t st, float* blocks) {
     const uint32_t cols = x.cols;
-    FirstBad bad_term;
-    MFX_TRY(bad_term.init(st));
+    BuildPass pass;
     DevBuf<float> d;
     MFX_TRY(d.alloc(cols));
-    DevBuf<uint32_t> queue;
-    MFX_TRY(queue.alloc_zero(1, st));
-    hipLaunchKernelGGL(k_slim_diag, dim3(grid_256((uint64_t) cols * 64)), dim3(256), 0, st, x.cptr.p, x.cval.p, cols, d.get(), bad_term.w.get());
+    MFX_TRY(pass.begin(st));
+    hipLaunchKernelGGL(k_slim_diag, dim3(grid_256((uint64_t) cols * 64)), dim3(256), 0, st, x.cptr.p, x.cval.p, cols, d.get(), pass.bad_term.w.get());
     MFX_LAUNCH_CHECK();
     MFX_HIP(hipMemsetAsync(blocks, 0, sizeof(float) * (size_t) cols * (K + 1) * K, st));
     SlimGramArgs a{};
-    a.ptr = x.ptr.p; a.idx = x.idx.p; a.val = x.val.p;
-    a.cptr = x.cptr.p; a.ridx = x.ridx.p; a.cval = x.cval.p;
-    a.order = order.get(); a.queue = queue.get(); a.first_bad = bad_term.w.get();
+    pass.fill(&a, x, order, T);
     a.S = S; a.iptr = iptr; a.tj = tj; a.tp = tp;
-    a.d = d.get(); a.blocks = blocks;
-    a.cols = cols; a.T = T; a.K = K;
-    const size_t lds = (size_t) T * 8 + 4 * kKnnCtlWords;
-    MFX_TRY(allow_lds(k_slim_gram, lds));
-    const uint32_t grid = (uint32_t) std::min<uint64_t>(cols, (uint64_t) cus * 2);
-    hipLaunchKernelGGL(k_slim_gram, dim3(grid), dim3(kKnnThreads), lds, st, a);
-    MFX_LAUNCH_CHECK();
-    uint32_t first = kNone;
-    MFX_TRY(bad_term.read(st, &first));
-    MFX_REQUIRE(first == kNone, "%s: item %u: a term x_ui * x_uj that is not finite or of magnitude >= 64", fn, first);
-    return MFX_OK;
+    a.d = d.get(); a.blocks = blocks; a.K = K;
+    return pass.run(k_slim_gram, fn, a, knn_tile_bytes(T), cus, st);
 }
 
+// The name of the Gram workspace in its allocation failure.
+std::string blocks_name(int64_t n) { return "the workspace of " + std::to_string(n) + " blocks [K + 1][K]"; }
+
 int alloc_blocks(const char* fn, DevBuf<float>* blocks, int64_t n, int K) {
-    const size_t count = (size_t) n * (K + 1) * K;
-    if (blocks->alloc(count) != MFX_OK)
-        return fail(MFX_ERR_ALLOC, "%s: the workspace of %lld blocks [K + 1][K], %zu bytes, could not be allocated", fn, (long long) n,
-                    count * sizeof(float));
-    return MFX_OK;
+    return alloc_named(fn, blocks_name(n).c_str(), blocks, (size_t) n * (K + 1) * K);
 }
 
 // The solve of n blocks on the device: w [n][K], sweeps_used [n], *failed.  Synchronises.
@@ -548,17 +462,12 @@ int Slim::gram(const mfx_csx* X, int32_t K, const uint32_t* support, int32_t til
     MFX_TRY(sup.set(fn, X->cols, K, support, nullptr, space, st));
     DevBuf<uint32_t> order;
     MFX_TRY(work_order(fn, x, st, &order));
-    DevBuf<float> own;
-    float* db = blocks;
-    if (space == MFX_HOST) {
-        MFX_TRY(alloc_blocks(fn, &own, X->cols, K));
-        db = own.get();
-    }
-    MFX_TRY(gram_pass(fn, x, order, sup.S.get(), sup.iptr.get(), sup.tj.get(), sup.tp.get(), K, T, cus, st, db));
-    if (space == MFX_HOST) {
-        MFX_HIP(hipMemcpyAsync(blocks, db, sizeof(float) * (size_t) X->cols * (K + 1) * K, hipMemcpyDeviceToHost, st));
-        MFX_HIP(hipStreamSynchronize(st));
-    }
+    const size_t count = (size_t) X->cols * (K + 1) * K;
+    Out<float> b;
+    MFX_TRY(b.set(blocks, count, space, fn, blocks_name(X->cols).c_str()));
+    MFX_TRY(gram_pass(fn, x, order, sup.S.get(), sup.iptr.get(), sup.tj.get(), sup.tp.get(), K, T, cus, st, b.p));
+    MFX_TRY(b.copy_out(blocks, count, space, st));
+    if (space == MFX_HOST) MFX_HIP(hipStreamSynchronize(st));
     return MFX_OK;
 }
 
@@ -579,22 +488,14 @@ int Slim::solve(int64_t n, int32_t K, const float* blocks, const uint32_t* n_rea
     Staged<uint32_t> sn;
     MFX_TRY(sb.set(blocks, (size_t) n * (K + 1) * K, space, st));
     if (n_real) MFX_TRY(sn.set(n_real, (size_t) n, space, st));
-    DevBuf<float> ow;
-    DevBuf<int32_t> os;
-    float* dw = w;
-    int32_t* ds = sweeps_used;
-    if (space == MFX_HOST) {
-        MFX_TRY(ow.alloc((size_t) n * K));
-        MFX_TRY(os.alloc((size_t) n));
-        dw = ow.get();
-        ds = os.get();
-    }
-    MFX_TRY(solve_pass(n, K, sb.p, sn.p, p, cus, st, dw, ds, failed));
-    if (space == MFX_HOST) {
-        MFX_HIP(hipMemcpyAsync(w, dw, sizeof(float) * (size_t) n * K, hipMemcpyDeviceToHost, st));
-        MFX_HIP(hipMemcpyAsync(sweeps_used, ds, sizeof(int32_t) * (size_t) n, hipMemcpyDeviceToHost, st));
-        MFX_HIP(hipStreamSynchronize(st));
-    }
+    Out<float> ow;
+    Out<int32_t> os;
+    MFX_TRY(ow.set(w, (size_t) n * K, space));
+    MFX_TRY(os.set(sweeps_used, (size_t) n, space));
+    MFX_TRY(solve_pass(n, K, sb.p, sn.p, p, cus, st, ow.p, os.p, failed));
+    MFX_TRY(ow.copy_out(w, (size_t) n * K, space, st));
+    MFX_TRY(os.copy_out(sweeps_used, (size_t) n, space, st));
+    if (space == MFX_HOST) MFX_HIP(hipStreamSynchronize(st));
     return MFX_OK;
 }
 
@@ -630,86 +531,10 @@ int Slim::weights(uint32_t* support, float* w, int32_t* sweeps_used, mfx_memspac
 
 int Slim::recommend(int64_t nusers, int64_t nnz, const uint32_t* ptr, const uint32_t* idx, const float* val, int32_t n_top, int flags,
                     int32_t tile_items, uint32_t* items, float* scores, int64_t* bad_rows, mfx_memspace space) {
-    const char* fn = "mfx_slim_recommend";
-    MFX_TRY(check_space(fn, space));
-    MFX_REQUIRE(n_top >= 1 && n_top <= 1024, "%s: n_top must be in [1, 1024] (got %d)", fn, n_top);
-    MFX_REQUIRE((flags & ~MFX_KNN_KEEP_SEEN) == 0, "%s: unknown flag bits 0x%x", fn, (unsigned) flags);
-    MFX_REQUIRE(nusers >= 0 && nusers < 0xFFFFFFFFll && nnz >= 0 && nnz < 0xFFFFFFFFll, "%s: nusers and nnz must be in [0, 2^32 - 1)", fn);
-    uint32_t T = 0;
-    MFX_TRY(pick_tile(fn, tile_items, cols_, n_top, &T));
-    if (bad_rows) *bad_rows = 0;
-    if (nusers == 0) return MFX_OK;
-    MFX_REQUIRE(ptr && items, "%s: ptr or items is NULL", fn);
-    MFX_REQUIRE(nnz == 0 || (idx && val), "%s: idx or val is NULL", fn);
-    MFX_TRY(use_device(device_));
-    hipStream_t st = st_;
-    hipEvent_t ev[3] = {};
-    struct EvGuard {
-        hipEvent_t* e;
-        ~EvGuard() {
-            for (int i = 0; i < 3; ++i)
-                if (e[i]) (void) hipEventDestroy(e[i]);
-        }
-    } guard{ev};
-    for (auto& e : ev) MFX_HIP(hipEventCreate(&e));
-    Staged<uint32_t> sp, si;
-    Staged<float> sv;
-    MFX_TRY(sp.set(ptr, (size_t) nusers + 1, space, st));
-    MFX_TRY(si.set(idx, (size_t) nnz, space, st));
-    MFX_TRY(sv.set(val, (size_t) nnz, space, st));
-    const size_t total = (size_t) nusers * n_top;
-    DevBuf<uint32_t> oi;
-    DevBuf<float> os;
-    uint32_t* di = items;
-    float* dsc = scores;
-    if (space == MFX_HOST) {
-        MFX_TRY(oi.alloc(total));
-        di = oi.get();
-        if (scores) {
-            MFX_TRY(os.alloc(total));
-            dsc = os.get();
-        }
-    }
-    DevBuf<unsigned long long> nbad;
-    MFX_TRY(nbad.alloc_zero(1, st));
-    FirstBad bad;
-    MFX_TRY(bad.init(st));
-    MFX_HIP(hipEventRecord(ev[0], st));
-    hipLaunchKernelGGL(k_knn_check, dim3(grid_256((uint64_t) nusers)), dim3(256), 0, st, sp.p, si.p, (uint32_t) nusers, (uint32_t) cols_, (uint32_t) nnz,
-                       bad.w.get());
-    MFX_LAUNCH_CHECK();
-    MFX_HIP(hipEventRecord(ev[1], st));
-    uint32_t first = kNone;
-    MFX_TRY(bad.read(st, &first));
-    MFX_REQUIRE(first == kNone, "%s: row %u: its pointers must ascend from 0 to nnz and its ids be strictly ascending and below cols", fn, first);
-
-    SlimRecArgs a{};
-    a.ptr = sp.p; a.idx = si.p; a.val = sv.p;
-    a.iptr = iptr_.get(); a.tj = tj_.get(); a.tw = tw_.get();
-    a.items = di; a.scores = dsc; a.bad_rows = nbad.get();
-    a.nusers = (uint32_t) nusers; a.cols = (uint32_t) cols_; a.T = T;
-    a.n_top = n_top; a.NC = knn_area(n_top);
-    a.keep_seen = (flags & MFX_KNN_KEEP_SEEN) != 0;
-    const size_t lds = knn_lds_bytes((int) T, n_top);
-    MFX_TRY(allow_lds(k_slim_recommend, lds));
-    const uint32_t grid = (uint32_t) std::min<uint64_t>((uint64_t) nusers, (uint64_t) cus_ * 8);
-    hipLaunchKernelGGL(k_slim_recommend, dim3(grid), dim3(kKnnThreads), lds, st, a);
-    MFX_LAUNCH_CHECK();
-    MFX_HIP(hipEventRecord(ev[2], st));
-    unsigned long long hbad = 0;
-    MFX_HIP(hipMemcpyAsync(&hbad, nbad.get(), sizeof(hbad), hipMemcpyDeviceToHost, st));
-    if (space == MFX_HOST) {
-        MFX_HIP(hipMemcpyAsync(items, di, sizeof(uint32_t) * total, hipMemcpyDeviceToHost, st));
-        if (scores) MFX_HIP(hipMemcpyAsync(scores, dsc, sizeof(float) * total, hipMemcpyDeviceToHost, st));
-    }
-    MFX_HIP(hipStreamSynchronize(st));
-    float ms = 0.f;
-    MFX_HIP(hipEventElapsedTime(&ms, ev[0], ev[1]));
-    t_[3] += 1e-3 * ms;
-    MFX_HIP(hipEventElapsedTime(&ms, ev[1], ev[2]));
-    t_[4] += 1e-3 * ms;
-    if (bad_rows) *bad_rows = (int64_t) hbad;
-    return MFX_OK;
+    return rows_recommend(k_knn_rows<SlimRecArgs>, "mfx_slim_recommend", cols_, cus_, device_, st_, &t_[3], &t_[4],
+                          RowsQuery{nusers, nnz, ptr, idx, val, n_top, flags, tile_items, items, scores, bad_rows, space}, [&](SlimRecArgs* a) {
+                              a->iptr = iptr_.get(); a->tj = tj_.get(); a->tw = tw_.get();
+                          });
 }
 
 }  // namespace mfx

@@ -816,7 +816,7 @@ def knn_weights(R: RatingData, scheme: Optional[str], k1: float = 1.2, b: float 
 
 
 def _rows_recommend(call, handle, device: int, rows, n_top: int, keep_seen: bool, on_device: bool, tile_items: int):
-    """The recommendation call shared by ItemKnn and Slim (mfx_knn_recommend / mfx_slim_recommend: one argument list) ->
+    """The recommendation call shared by ItemKnn, Slim and Ease (mfx_*_recommend: one argument list) ->
     (items, scores, bad_rows)."""
     ptr, idx, val = (rows.csr_row_ptr, rows.csr_col_idx, rows.csr_val) if hasattr(rows, "csr_row_ptr") else rows
     if len(ptr.shape) != 1 or ptr.shape[0] < 1 or tuple(idx.shape) != tuple(val.shape) or len(idx.shape) != 1:
@@ -850,17 +850,49 @@ def _rows_recommend(call, handle, device: int, rows, n_top: int, keep_seen: bool
     return items, scores, int(bad.value)
 
 
-class ItemKnn:
+class _ItemModel:
+    """What ItemKnn, Slim and Ease share: the handle of a model of `cols` items on `device`, the recommendation for rows of
+    interactions (bad_rows: the bad rows of the last call) and the end of the handle.  _destroy: the model's mfx_*_destroy."""
+    _destroy = ""
+
+    def _start(self, device: int):
+        self.handle = C.c_void_p()
+        self.device, self.cols, self.bad_rows = int(device), 0, 0
+
+    def _recommend(self, call, rows, n_top: int, keep_seen: bool, on_device: bool, tile_items: int):
+        items, scores, self.bad_rows = _rows_recommend(call, self.handle, self.device, rows, n_top, keep_seen, on_device, tile_items)
+        return items, scores
+
+    def close(self):
+        if self.handle:
+            getattr(L.lib(), self._destroy)(self.handle)
+            self.handle = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class ItemKnn(_ItemModel):
     """Item-kNN on the interaction matrix (mfx_knn_*, include/mfx.h): the K nearest items of every item by the exact
     fixed-point X^T X of the weighted matrix, and recommendations as sums over the user's own items -- every bit fixed by
     the data.  R: a RatingData; weighting "cosine" / "tfidf" / "bm25" / None as in knn_weights (k1, b: BM25).
     device_arrays: the already weighted matrix as a dict of device tensors (mfx.synth_torch) instead of R; weighting must
     then be None.  tile_items: the test hook of mfx_knn_build."""
+    _destroy = "mfx_knn_destroy"
 
     def __init__(self, R: Optional[RatingData], K: int, weighting: Optional[str] = "cosine", k1: float = 1.2, b: float = 0.75,
                  device: int = 0, device_arrays: Optional[dict] = None, tile_items: int = 0):
-        self.handle = C.c_void_p()
-        self.device, self.K, self.bad_rows = int(device), int(K), 0
+        self._start(device)
+        self.K = int(K)
         if device_arrays is not None:
             if weighting is not None:
                 raise ValueError("device_arrays are taken as they are: pass weighting=None")
@@ -879,8 +911,7 @@ class ItemKnn:
         if tuple(nbr_idx.shape) != tuple(nbr_sim.shape) or len(nbr_idx.shape) != 2:
             raise ValueError("nbr_idx and nbr_sim must both be [cols][K]")
         self = cls.__new__(cls)
-        self.handle = C.c_void_p()
-        self.device, self.bad_rows = int(device), 0
+        self._start(device)
         self.cols, self.K = int(nbr_idx.shape[0]), int(nbr_idx.shape[1])
         if _is_dev(nbr_idx) != _is_dev(nbr_sim):
             raise ValueError("nbr_idx and nbr_sim must both be host arrays or both device tensors")
@@ -928,32 +959,13 @@ class ItemKnn:
         (ptr, idx, val) triple of numpy arrays or GPU tensors, as for Recommender.fold_in.  The number of bad rows (all
         pads: a term that is not finite or of magnitude >= 64) is left in self.bad_rows.  Tensors in, or on_device=True:
         the results are tensors on the device (items as int32 holding the uint32 ids)."""
-        items, scores, self.bad_rows = _rows_recommend(L.lib().mfx_knn_recommend, self.handle, self.device, rows, n_top, keep_seen,
-                                                       on_device, tile_items)
-        return items, scores
+        return self._recommend(L.lib().mfx_knn_recommend, rows, n_top, keep_seen, on_device, tile_items)
 
     def times(self) -> dict:
         """Seconds of the build (checks and work order, similarity pass) and of recommend summed over the calls (checks, pass)."""
         out = (C.c_double * 4)()
         L.check(L.lib().mfx_knn_times(self.handle, out))
         return dict(zip(("build_checks", "build_pass", "recommend_checks", "recommend_pass"), (float(x) for x in out)))
-
-    def close(self):
-        if self.handle:
-            L.lib().mfx_knn_destroy(self.handle)
-            self.handle = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 # ---------------------------------------------------------------------------------------------
@@ -1030,7 +1042,7 @@ def slim_solve(blocks, n_real=None, l1: float = 1.0, l2: float = 10.0, sweeps: i
     return w, used, int(failed.value)
 
 
-class Slim:
+class Slim(_ItemModel):
     """SLIM on given supports (mfx_slim_*, include/mfx.h): for every item the elastic-net regression of its column on the K
     columns of its support, trained on the GPU by coordinate descent on the exact fixed-point Gram matrix, and
     recommendations as sums over the user's own items -- every bit fixed by the data.  R: a RatingData, its values taken
@@ -1039,12 +1051,13 @@ class Slim:
     the first sweep whose largest change is <= tol; signed: weights of either sign (default: non-negative).
     device_arrays: the matrix as a dict of device tensors (mfx.synth_torch) instead of R; weighting must then be None and a
     support be given.  tile_items: the test hook of mfx_slim_train."""
+    _destroy = "mfx_slim_destroy"
 
     def __init__(self, R: Optional[RatingData], K: int, l1: float = 1.0, l2: float = 10.0, sweeps: int = 10, tol: float = 0.0,
                  signed: bool = False, weighting: Optional[str] = None, support=None, device: int = 0,
                  device_arrays: Optional[dict] = None, tile_items: int = 0):
-        self.handle = C.c_void_p()
-        self.device, self.K, self.bad_rows, self.failed = int(device), int(K), 0, 0
+        self._start(device)
+        self.K, self.failed = int(K), 0
         if support is None and device_arrays is not None and weighting is None:
             raise ValueError("device_arrays need a support (an ItemKnn or [cols][K] ids)")
         csx, space, self.cols, keep = _slim_matrix(R, weighting, device_arrays)
@@ -1066,8 +1079,8 @@ class Slim:
         if _is_dev(support) != _is_dev(w):
             raise ValueError("support and w must both be host arrays or both device tensors")
         self = cls.__new__(cls)
-        self.handle = C.c_void_p()
-        self.device, self.bad_rows, self.failed = int(device), 0, 0
+        self._start(device)
+        self.failed = 0
         self.cols, self.K = int(support.shape[0]), int(support.shape[1])
         if _is_dev(support):
             assert support.is_contiguous() and support.element_size() == 4 and w.is_contiguous() and w.element_size() == 4
@@ -1096,32 +1109,13 @@ class Slim:
     def recommend(self, rows, n_top: int, keep_seen: bool = False, on_device: bool = False, tile_items: int = 0):
         """Top-n_top items of the users given by their interactions, as ItemKnn.recommend: the score of j is the sum of
         x_i * w_ij over the row's items i whose weight for j is stored.  The number of bad rows is left in self.bad_rows."""
-        items, scores, self.bad_rows = _rows_recommend(L.lib().mfx_slim_recommend, self.handle, self.device, rows, n_top, keep_seen,
-                                                       on_device, tile_items)
-        return items, scores
+        return self._recommend(L.lib().mfx_slim_recommend, rows, n_top, keep_seen, on_device, tile_items)
 
     def times(self) -> dict:
         """Seconds of the training (checks and inverse lists, Gram pass, solve) and of recommend summed over the calls."""
         out = (C.c_double * 5)()
         L.check(L.lib().mfx_slim_times(self.handle, out))
         return dict(zip(("train_checks", "gram_pass", "solve", "recommend_checks", "recommend_pass"), (float(x) for x in out)))
-
-    def close(self):
-        if self.handle:
-            L.lib().mfx_slim_destroy(self.handle)
-            self.handle = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 # ---------------------------------------------------------------------------------------------
@@ -1189,18 +1183,18 @@ def ease_weights_from_inverse(P, device: int = 0):
     return out
 
 
-class Ease:
+class Ease(_ItemModel):
     """EASE (mfx_ease_*, include/mfx.h): the closed-form dense item-item model B = I - P diag(P)^-1 with a zero diagonal,
     P = (X^T X + lam I)^-1, trained on the GPU -- exact fixed-point Gram matrix, blocked Cholesky inverse, one division per
     weight -- and recommendations as fma chains over the user's own items; every bit fixed by the data.  R: a RatingData,
     its values taken under `weighting` (knn_weights; k1, b: BM25; None: as they are).  lam: the ridge penalty, > 0.
     device_arrays: the matrix as a dict of device tensors (mfx.synth_torch) instead of R; weighting must then be None.
     tile_items: the test hook of mfx_ease_train.  simple_inverse: the one-wavefront-per-block schedule of the inverse."""
+    _destroy = "mfx_ease_destroy"
 
     def __init__(self, R: Optional[RatingData], lam: float, weighting: Optional[str] = None, k1: float = 1.2, b: float = 0.75,
                  device: int = 0, device_arrays: Optional[dict] = None, tile_items: int = 0, simple_inverse: bool = False):
-        self.handle = C.c_void_p()
-        self.device, self.bad_rows = int(device), 0
+        self._start(device)
         csx, space, self.cols, keep = _ease_matrix(R, weighting, k1, b, device_arrays)
         L.check(L.lib().mfx_ease_train(C.byref(self.handle), C.byref(csx), float(lam), L.MFX_EASE_INV_SIMPLE if simple_inverse else 0,
                                        int(tile_items), space, self.device))
@@ -1210,8 +1204,8 @@ class Ease:
         """A model from given weights B [cols][cols] (float32, finite, zero diagonal): a numpy array or a GPU tensor."""
         pb, space, n, keep = _ease_square(B, "B")
         self = cls.__new__(cls)
-        self.handle = C.c_void_p()
-        self.device, self.bad_rows, self.cols = int(device), 0, n
+        self._start(device)
+        self.cols = n
         L.check(L.lib().mfx_ease_create_from_weights(C.byref(self.handle), n, pb, space, self.device))
         return self
 
@@ -1228,32 +1222,13 @@ class Ease:
         """Top-n_top items of the users given by their interactions, as ItemKnn.recommend: the score of j is the fma chain of
         x_i * B[i][j] over the row's items i in stored order; every item not in the row is eligible, whatever its score's
         sign.  The number of bad rows (a value that is not finite) is left in self.bad_rows."""
-        items, scores, self.bad_rows = _rows_recommend(L.lib().mfx_ease_recommend, self.handle, self.device, rows, n_top, keep_seen,
-                                                       on_device, tile_items)
-        return items, scores
+        return self._recommend(L.lib().mfx_ease_recommend, rows, n_top, keep_seen, on_device, tile_items)
 
     def times(self) -> dict:
         """Seconds of the training (checks, Gram pass, inverse, weights) and of recommend summed over the calls."""
         out = (C.c_double * 6)()
         L.check(L.lib().mfx_ease_times(self.handle, out))
         return dict(zip(("train_checks", "gram_pass", "inverse", "weights", "recommend_checks", "recommend_pass"), (float(x) for x in out)))
-
-    def close(self):
-        if self.handle:
-            L.lib().mfx_ease_destroy(self.handle)
-            self.handle = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 # ---------------------------------------------------------------------------------------------
