@@ -4,20 +4,22 @@
 //     explicit:  A p = rho p + sum_e <h_e, p> h_e,     b = sum_e r_e h_e,             rho = lambda or fp32(lambda n),  M^-1 = I
 // and CG preconditioned by G^-1 ends, in exact arithmetic, after n + 1 steps on a row of n entries.  The method is
 // step-synchronous over the query batch; y (the caller's rows), r, z, p, q are [rows][k] fp32, |b|^2, gamma, the step count
-// and the frozen flag live per row.  The kernels, in the order of a step:
-//   k_foldcg_gather<C, MODE>  one wavefront per work item of AlsHalf (a whole row, or a chunk of 2048 entries into a partial
-//                             slot): lane l holds coordinates l + 64 i of p and of the sum; an entry's row of H is loaded once,
-//                             t = <h_e, p> by a butterfly over the lanes, then (c_e t) h_e from the registers that still hold
-//                             the row.  Four rows of H are in flight before their reductions.  The first pass forms b the
-//                             same way (and the sum over <h_e, y0> when warm).
-//   k_foldcg_reduce           the partial slots of a split row summed in slot order
-//   k_foldcg_dense<ND>        (implicit) out = V M (+ add) for a symmetric M [k][k]: 32 rows x 128 columns per wavefront on
-//                             v_mfma_f32_32x32x2_f32; an output row depends on its own input row and the k order alone
+// and the frozen flag live per row.
+// This unit also holds what the method shares with the target solves of rec_explain_cg.hip (rec_foldin_cg.hpp):
+// there a system is a (row, target) pair, T per row; here T = 1.  The kernels, in the order of a step:
+//   k_cg_gather<C, 1, MODE>   (rec_foldin_cg.hpp) one wavefront per work item of AlsHalf (a whole row, or a chunk of 2048
+//                             entries into a partial slot): lane l holds coordinates l + 64 i of p and of the sum; an entry's
+//                             row of H is loaded once, t = <h_e, p> by a butterfly over the lanes, then (c_e t) h_e from the
+//                             registers that still hold the row.  Four rows of H are in flight before their reductions.  The
+//                             first pass forms b the same way (and the sum over <h_e, y0> when warm).
+//   k_cg_reduce               (shared) the partial slots of a split row summed in slot order, per target
+//   k_foldcg_dense<ND>        (implicit; shared) out = V M (+ add) for a symmetric M [k][k]: 32 rows x 128 columns per wavefront
+//                             on v_mfma_f32_32x32x2_f32; an output row depends on its own input row and the k order alone
 //   k_foldcg_start            r = b - A y0, |b|^2, the rows without a right-hand side zeroed and frozen, the stop test on y0
-//   k_foldcg_step             <p, q>, a, y += a p, r -= a q, the count, the stop test |r| <= tol |b|
-//   k_foldcg_dir              gamma' = <r, z>, p = z + (gamma' / gamma) p; the rows still active counted for the host
-// A frozen row is skipped by every kernel: its bits never change again.  No float atomics; every sum has a fixed order that
-// depends on the row alone, so a row's bits and count do not depend on the batch around it.
+//   k_cg_step                 (shared) <p, q>, a, y += a p, r -= a q, the count, the stop test |r| <= tol |b|
+//   k_cg_dir                  (shared) gamma' = <r, z>, p = z + (gamma' / gamma) p; the systems still active counted for the host
+// cg_iterate is the step loop of both.  A frozen system is skipped by every kernel: its bits never change again.  No float
+// atomics; every sum has a fixed order that depends on the system alone, so its bits and count do not depend on the batch.
 #include <algorithm>
 #include <cmath>
 
@@ -31,90 +33,24 @@ using f32x4 = __attribute__((ext_vector_type(4))) float;
 
 // (kGatherRows, wave_sum, row_rho: rec_foldin_cg.hpp)
 
-// MODE bit 0: S = sum_e c_e <h_e, v> h_e with v = V[seg]; bit 1: B = sum_e d_e h_e.  implicit: an entry counts when r_e > 0,
-// c_e = w_e = fp32(alpha r_e), d_e = fp32(1 + w_e); explicit: every entry counts, c_e = 1, d_e = r_e.  C = columns per lane.
-// A whole row (slot < 0) writes S / B [seg][k]; a chunk writes its slot of ws: S at (2 slot) k, B at (2 slot + 1) k.
-template <int C, int MODE>
-__global__ __launch_bounds__(64) void k_foldcg_gather(const AlsItem* __restrict__ items, uint32_t nitems, const uint32_t* __restrict__ idx,
-                                                      const float* __restrict__ val, const float* __restrict__ X, uint32_t x_rows, uint32_t k,
-                                                      int32_t implicit, float alpha, const float* __restrict__ V,
-                                                      const uint32_t* __restrict__ frozen, float* __restrict__ S, float* __restrict__ B,
-                                                      float* __restrict__ ws) {
-    constexpr int U = kGatherRows;
-    const uint32_t lane = threadIdx.x & 63;
-    if (blockIdx.x >= nitems) return;
-    const AlsItem it = items[blockIdx.x];
-    if (it.hi == it.lo) return;                    // (k_foldcg_start zeroes the empty rows)
-    if (frozen && frozen[it.seg]) return;          // wave-uniform
-    float pv[C], acc[C], accb[C];
-#pragma unroll
-    for (int i = 0; i < C; ++i) {
-        pv[i] = (MODE & 1) && 64 * i + lane < k ? V[(size_t) it.seg * k + 64 * i + lane] : 0.f;
-        acc[i] = 0.f;
-        accb[i] = 0.f;
-    }
-    for (uint32_t q0 = it.lo; q0 < it.hi; q0 += U) {
-        float hv[U][C], cw[U], cb[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const uint32_t q = q0 + u;
-            const bool ok = q < it.hi;  // wave-uniform; past the end: the zero row of X, weight 0
-            const float r = ok ? val[q] : 0.f;
-            const float* x = X + (size_t) (ok ? idx[q] : x_rows) * k;
-            if (implicit) {
-                const float w = alpha * r;
-                cw[u] = r > 0.f ? w : 0.f;
-                cb[u] = r > 0.f ? 1.f + w : 0.f;
-            } else {
-                cw[u] = ok ? 1.f : 0.f;
-                cb[u] = r;
-            }
-#pragma unroll
-            for (int i = 0; i < C; ++i) hv[u][i] = 64 * i + lane < k ? x[64 * i + lane] : 0.f;
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            if (q0 + u < it.hi) {  // wave-uniform
-                if (MODE & 1) {
-                    float t = 0.f;
-#pragma unroll
-                    for (int i = 0; i < C; ++i) t = __builtin_fmaf(hv[u][i], pv[i], t);
-                    const float ct = cw[u] * wave_sum(t);
-#pragma unroll
-                    for (int i = 0; i < C; ++i) acc[i] = __builtin_fmaf(ct, hv[u][i], acc[i]);
-                }
-                if (MODE & 2) {
-#pragma unroll
-                    for (int i = 0; i < C; ++i) accb[i] = __builtin_fmaf(cb[u], hv[u][i], accb[i]);
-                }
-            }
-        }
-    }
-    float* s = it.slot < 0 ? S + (size_t) it.seg * k : ws + (size_t) (2 * it.slot) * k;
-    float* b = it.slot < 0 ? B + (size_t) it.seg * k : ws + (size_t) (2 * it.slot + 1) * k;
-#pragma unroll
-    for (int i = 0; i < C; ++i)
-        if (64 * i + lane < k) {
-            if (MODE & 1) s[64 * i + lane] = acc[i];
-            if (MODE & 2) b[64 * i + lane] = accb[i];
-        }
-}
-
-// the partial slots of a split row into S / B [seg][k], in slot order; one wavefront per split row
-__global__ __launch_bounds__(64) void k_foldcg_reduce(const AlsReduce* __restrict__ reduces, uint32_t nreduces, uint32_t k, int32_t mode,
-                                                      const uint32_t* __restrict__ frozen, const float* __restrict__ ws, float* __restrict__ S,
-                                                      float* __restrict__ B) {
+// the partial slots of a split row into S / B [seg T + t][k], in slot order; one wavefront per (split row, target)
+__global__ __launch_bounds__(64) void k_cg_reduce(const AlsReduce* __restrict__ reduces, uint32_t nreduces, uint32_t k, uint32_t T, int32_t mode,
+                                                  const uint32_t* __restrict__ frozen, const float* __restrict__ ws, float* __restrict__ S,
+                                                  float* __restrict__ B) {
     if (blockIdx.x >= nreduces) return;
     const AlsReduce rd = reduces[blockIdx.x];
-    if (frozen && frozen[rd.seg]) return;
+    const uint32_t t = blockIdx.y, stride = cg_ws_stride(T, mode);
+    const size_t sys = (size_t) rd.seg * T + t;
+    if (frozen && frozen[sys]) return;
     for (uint32_t c = threadIdx.x & 63; c < k; c += 64) {
         float s = 0.f, b = 0.f;
         for (uint32_t p = 0; p < rd.nslots; ++p) {
-            if (mode & 1) s += ws[(size_t) (2 * (rd.slot0 + p)) * k + c];
-            if (mode & 2) b += ws[(size_t) (2 * (rd.slot0 + p) + 1) * k + c];
+            const size_t row = (size_t) (rd.slot0 + p) * stride;
+            if (mode & 1) s += ws[(row + t) * k + c];
+            if (mode & 2) b += ws[(row + 1) * k + c];
         }
-        if (mode & 1) S[(size_t) rd.seg * k + c] = s;
-        if (mode & 2) B[(size_t) rd.seg * k + c] = b;
+        if (mode & 1) S[sys * k + c] = s;
+        if (mode & 2) B[sys * k + c] = b;
     }
 }
 
@@ -181,9 +117,8 @@ __global__ __launch_bounds__(256) void k_foldcg_dense(const float* __restrict__ 
 }
 
 // After the first gather (R = b; warm: Q = the gathered part of A y0, for the implicit model with G y0 added already), one
-// wavefront per row, lane l the columns l + 64 i.  A row without entries or with |b| = 0: y = 0, frozen, 0 steps, whatever
-// the start held.  Any other row: r = b - A y0 (cold: r = b, Y is zero), |b|^2 kept, frozen at once if tol > 0 and
-// |r| <= tol |b|.  r, z and p of a frozen row are zeroed so that nothing unwritten is ever read.
+// wavefront per row, lane l the columns l + 64 i.  A row with entries and b != 0: r = b - A y0 (cold: r = b, Y is zero); then
+// cg_start_tail (a row without entries has b2 = 0 there).
 __global__ __launch_bounds__(256) void k_foldcg_start(const uint32_t* __restrict__ ptr, uint32_t nseg, uint32_t k, float* __restrict__ Y,
                                                       float* R, float* Z, float* __restrict__ P,  // (explicit: Z is R)
                                                       const float* __restrict__ Q, int32_t warm, int32_t reg, float lambda, float tol,
@@ -197,13 +132,8 @@ __global__ __launch_bounds__(256) void k_foldcg_start(const uint32_t* __restrict
         for (uint32_t c = lane; c < k; c += 64) b2 = __builtin_fmaf(R[o + c], R[o + c], b2);
         b2 = wave_sum(b2);
     }
-    if (empty || b2 == 0.f) {
-        for (uint32_t c = lane; c < k; c += 64) Y[o + c] = R[o + c] = Z[o + c] = P[o + c] = 0.f;
-        if (lane == 0) { frozen[seg] = 1; counts[seg] = 0; bb[seg] = 0.f; }
-        return;
-    }
     float r2 = b2;
-    if (warm) {
+    if (warm && b2 != 0.f) {
         const float rho = row_rho(reg, lambda, ptr, seg);
         r2 = 0.f;
         for (uint32_t c = lane; c < k; c += 64) {
@@ -214,25 +144,23 @@ __global__ __launch_bounds__(256) void k_foldcg_start(const uint32_t* __restrict
         }
         r2 = wave_sum(r2);
     }
-    const bool stop = tol > 0.f && sqrtf(r2) <= tol * sqrtf(b2);
-    if (stop)
-        for (uint32_t c = lane; c < k; c += 64) Z[o + c] = P[o + c] = 0.f;
-    if (lane == 0) { frozen[seg] = stop; counts[seg] = 0; bb[seg] = b2; }
+    cg_start_tail(seg, o, k, lane, b2, r2, tol, Y, R, Z, P, bb, frozen, counts);
 }
 
 // One step's first half, after q = A p (explicit: Q holds the gathered part, rho p is added here): a = gamma / <p, q>,
-// y += a p, r -= a q, the step counted, the row frozen once |r| <= tol |b| (tol > 0).  <p, q> < 0 or not finite (the inputs
-// were not finite): the row becomes NaN, is frozen and counted into *fail.  <p, q> exactly 0 is a direction that underflowed
-// on a row long converged (tol = 0 and more steps than the row needs): frozen as it is, the step not counted.
-__global__ __launch_bounds__(256) void k_foldcg_step(const uint32_t* __restrict__ ptr, uint32_t nseg, uint32_t k, float* __restrict__ Y,
-                                                     float* __restrict__ R, const float* __restrict__ P, const float* __restrict__ Q,
-                                                     int32_t reg, float lambda, float tol, const float* __restrict__ gamma,
-                                                     const float* __restrict__ bb, uint32_t* __restrict__ frozen, int32_t* __restrict__ counts,
-                                                     uint32_t* __restrict__ fail) {
-    const uint32_t lane = threadIdx.x & 63, seg = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (seg >= nseg || frozen[seg]) return;  // wave-uniform
-    const size_t o = (size_t) seg * k;
-    const float rho = reg ? row_rho(reg, lambda, ptr, seg) : 0.f;
+// y += a p, r -= a q, the step counted, the system frozen once |r| <= tol |b| (tol > 0).  One wavefront per system; rho is
+// that of the system's row.  <p, q> < 0 or not finite (the inputs were not finite): the system becomes NaN, is frozen and
+// counted into *fail (NULL: no count).  <p, q> exactly 0 is a direction that underflowed on a system long converged (tol = 0
+// and more steps than it needs): frozen as it is, the step not counted.
+__global__ __launch_bounds__(256) void k_cg_step(const uint32_t* __restrict__ ptr, size_t nsys, uint32_t T, uint32_t k, float* __restrict__ Y,
+                                                 float* __restrict__ R, const float* __restrict__ P, const float* __restrict__ Q, int32_t reg,
+                                                 float lambda, float tol, const float* __restrict__ gamma, const float* __restrict__ bb,
+                                                 uint32_t* __restrict__ frozen, int32_t* __restrict__ counts, uint32_t* __restrict__ fail) {
+    const uint32_t lane = threadIdx.x & 63;
+    const size_t seg = (size_t) blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (seg >= nsys || frozen[seg]) return;  // wave-uniform
+    const size_t o = seg * k;
+    const float rho = reg ? row_rho(reg, lambda, ptr, (uint32_t) (seg / T)) : 0.f;
     float pq = 0.f;
     for (uint32_t c = lane; c < k; c += 64) {
         const float q = reg ? __builtin_fmaf(rho, P[o + c], Q[o + c]) : Q[o + c];
@@ -241,7 +169,11 @@ __global__ __launch_bounds__(256) void k_foldcg_step(const uint32_t* __restrict_
     pq = wave_sum(pq);
     if (!(pq >= 0.f) || !(pq <= 3.402823466e38f)) {
         for (uint32_t c = lane; c < k; c += 64) Y[o + c] = __builtin_nanf("");
-        if (lane == 0) { frozen[seg] = 1; counts[seg] += 1; atomicAdd(fail, 1u); }
+        if (lane == 0) {
+            frozen[seg] = 1;
+            counts[seg] += 1;
+            if (fail) atomicAdd(fail, 1u);
+        }
         return;
     }
     if (pq == 0.f) {
@@ -266,14 +198,15 @@ __global__ __launch_bounds__(256) void k_foldcg_step(const uint32_t* __restrict_
 }
 
 // After z = M^-1 r (explicit: Z is R): gamma' = <r, z>; first: p = z, else p = z + (gamma' / gamma) p; gamma = gamma'.
-// gamma' exactly 0 freezes the row (nothing is left to do).  The rows still active are counted into *active (NULL: no count;
-// one vector atomic per row, an integer: the sum has no order).
-__global__ __launch_bounds__(256) void k_foldcg_dir(uint32_t nseg, uint32_t k, const float* __restrict__ R, const float* __restrict__ Z,
-                                                    float* __restrict__ P, int32_t first, float* __restrict__ gamma,
-                                                    uint32_t* __restrict__ frozen, uint32_t* __restrict__ active) {
-    const uint32_t lane = threadIdx.x & 63, seg = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (seg >= nseg || frozen[seg]) return;  // wave-uniform
-    const size_t o = (size_t) seg * k;
+// gamma' exactly 0 freezes the system (nothing is left to do).  The systems still active are counted into *active (NULL: no
+// count; one vector atomic per system, an integer: the sum has no order).
+__global__ __launch_bounds__(256) void k_cg_dir(size_t nsys, uint32_t k, const float* __restrict__ R, const float* __restrict__ Z,
+                                                float* __restrict__ P, int32_t first, float* __restrict__ gamma, uint32_t* __restrict__ frozen,
+                                                uint32_t* __restrict__ active) {
+    const uint32_t lane = threadIdx.x & 63;
+    const size_t seg = (size_t) blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (seg >= nsys || frozen[seg]) return;  // wave-uniform
+    const size_t o = seg * k;
     float g = 0.f;
     for (uint32_t c = lane; c < k; c += 64) g = __builtin_fmaf(R[o + c], Z[o + c], g);
     g = wave_sum(g);
@@ -299,16 +232,16 @@ void launch_gather_c(int mode, const AlsHalf& h, const float* X, uint32_t x_rows
     const dim3 grid(h.nitems), block(64);
     switch (mode) {
         case 1:
-            hipLaunchKernelGGL((k_foldcg_gather<C, 1>), grid, block, 0, st, h.items.get(), h.nitems, h.idx.get(), h.val.get(), X, x_rows, k, implicit,
-                               alpha, V, frozen, S, B, ws);
+            hipLaunchKernelGGL((k_cg_gather<C, 1, 1>), grid, block, 0, st, h.items.get(), h.nitems, h.idx.get(), h.val.get(), X, x_rows, k, implicit,
+                               alpha, 1u, V, frozen, S, B, ws);
             break;
         case 2:
-            hipLaunchKernelGGL((k_foldcg_gather<C, 2>), grid, block, 0, st, h.items.get(), h.nitems, h.idx.get(), h.val.get(), X, x_rows, k, implicit,
-                               alpha, V, frozen, S, B, ws);
+            hipLaunchKernelGGL((k_cg_gather<C, 1, 2>), grid, block, 0, st, h.items.get(), h.nitems, h.idx.get(), h.val.get(), X, x_rows, k, implicit,
+                               alpha, 1u, V, frozen, S, B, ws);
             break;
         default:
-            hipLaunchKernelGGL((k_foldcg_gather<C, 3>), grid, block, 0, st, h.items.get(), h.nitems, h.idx.get(), h.val.get(), X, x_rows, k, implicit,
-                               alpha, V, frozen, S, B, ws);
+            hipLaunchKernelGGL((k_cg_gather<C, 1, 3>), grid, block, 0, st, h.items.get(), h.nitems, h.idx.get(), h.val.get(), X, x_rows, k, implicit,
+                               alpha, 1u, V, frozen, S, B, ws);
             break;
     }
 }
@@ -323,11 +256,7 @@ int gather(int mode, const AlsHalf& h, const float* X, uint32_t x_rows, uint32_t
     else if (c <= 8) launch_gather_c<8>(mode, h, X, x_rows, k, implicit, alpha, V, frozen, S, B, ws, st);
     else launch_gather_c<16>(mode, h, X, x_rows, k, implicit, alpha, V, frozen, S, B, ws, st);
     MFX_HIP(hipGetLastError());
-    if (h.nreduces) {
-        hipLaunchKernelGGL(k_foldcg_reduce, dim3(h.nreduces), dim3(64), 0, st, h.reduces.get(), h.nreduces, k, mode, frozen, ws, S, B);
-        MFX_HIP(hipGetLastError());
-    }
-    return MFX_OK;
+    return cg_reduce(h, k, 1, mode, frozen, ws, S, B, st);
 }
 
 // fp64 dot of two contiguous rows over [0, n): four partial sums in a fixed order
@@ -355,6 +284,53 @@ int foldcg_dense(const float* V, uint32_t nseg, uint32_t k, const float* M, cons
         default: hipLaunchKernelGGL(k_foldcg_dense<4>, grid, block, 0, st, V, nseg, k, M, frozen, add, out); break;
     }
     MFX_HIP(hipGetLastError());
+    return MFX_OK;
+}
+
+int cg_reduce(const AlsHalf& h, uint32_t k, uint32_t T, int mode, const uint32_t* frozen, const float* ws, float* S, float* B, hipStream_t st) {
+    if (h.nreduces) {
+        hipLaunchKernelGGL(k_cg_reduce, dim3(h.nreduces, T), dim3(64), 0, st, h.reduces.get(), h.nreduces, k, T, mode, frozen, ws, S, B);
+        MFX_HIP(hipGetLastError());
+    }
+    return MFX_OK;
+}
+
+int cg_iterate(const AlsHalf& h, uint32_t T, uint32_t k, const FoldCg& m, float* Y, FoldCgWs& w, int32_t* counts, uint32_t* fail,
+               uint32_t* first_active, const std::function<int()>& gather, hipStream_t st) {
+    const bool implicit = m.reg == 0, stop = m.tol > 0.f;
+    const size_t nsys = (size_t) h.nseg * T;
+    const uint32_t n32 = (uint32_t) nsys;
+    float *R = w.R.get(), *P = w.P.get(), *Q = w.Q.get();
+    float* Z = implicit ? w.Z.get() : R;  // the explicit models' preconditioner is the identity
+    uint32_t *frozen = w.frozen.get(), *active = w.active.get();  // active [1 + steps]: the systems still active after the start and after each step
+    const dim3 grid((n32 + 3) / 4), block(256);
+    // whether every system is frozen, read from the counter that k_cg_dir filled (tol > 0 only)
+    auto all_frozen = [&](uint32_t slot, bool& done) -> int {
+        uint32_t left = 0;
+        MFX_HIP(hipMemcpyAsync(&left, active + slot, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        MFX_HIP(hipStreamSynchronize(st));
+        done = left == 0;
+        return MFX_OK;
+    };
+
+    if (implicit) MFX_TRY(foldcg_dense(R, n32, k, m.Minv, frozen, nullptr, Z, st));
+    hipLaunchKernelGGL(k_cg_dir, grid, block, 0, st, nsys, k, R, Z, P, 1, w.gamma.get(), frozen, first_active);
+    MFX_HIP(hipGetLastError());
+    bool done = false;
+    if (stop) MFX_TRY(all_frozen(0, done));
+    for (int32_t s = 0; s < m.steps && !done; ++s) {
+        MFX_TRY(gather());
+        if (implicit) MFX_TRY(foldcg_dense(P, n32, k, m.G, frozen, Q, Q, st));
+        hipLaunchKernelGGL(k_cg_step, grid, block, 0, st, h.ptr.get(), nsys, T, k, Y, R, P, Q, m.reg, m.lambda, m.tol, w.gamma.get(), w.bb.get(),
+                           frozen, counts, fail);
+        MFX_HIP(hipGetLastError());
+        if (s + 1 == m.steps) break;  // (the direction of a step that never comes)
+        if (implicit) MFX_TRY(foldcg_dense(R, n32, k, m.Minv, frozen, nullptr, Z, st));
+        hipLaunchKernelGGL(k_cg_dir, grid, block, 0, st, nsys, k, R, Z, P, 0, w.gamma.get(), frozen, stop ? active + s + 1 : nullptr);
+        MFX_HIP(hipGetLastError());
+        if (stop) MFX_TRY(all_frozen((uint32_t) s + 1, done));
+    }
+    MFX_HIP(hipStreamSynchronize(st));  // (the workspace goes with this call)
     return MFX_OK;
 }
 
@@ -425,50 +401,20 @@ int foldcg_launch(const AlsHalf& h, const float* X, uint32_t x_rows, uint32_t k,
         MFX_TRY(own.frozen.alloc(nseg));
         if (stop) MFX_TRY(own.active.alloc_zero((size_t) m.steps + 1, st));  // [1 + steps]: the rows still active after the start and after each step
     }
-    DevBuf<float>&R = cw->R, &Zb = cw->Z, &P = cw->P, &Q = cw->Q, &ws = cw->part, &bb = cw->bb, &gamma = cw->gamma;
-    DevBuf<uint32_t>&frozen = cw->frozen, &active = cw->active;
     if (!counts) {
         MFX_TRY(own_counts.alloc(nseg));
         counts = own_counts.get();
     }
-    float* Z = implicit ? Zb.get() : R.get();  // the explicit models' preconditioner is the identity
-    const dim3 grid((nseg + 3) / 4), block(256);
-    // whether every row is frozen, read from the counter that k_foldcg_dir filled (tol > 0 only)
-    auto all_frozen = [&](uint32_t slot, bool& done) -> int {
-        uint32_t left = 0;
-        MFX_HIP(hipMemcpyAsync(&left, active.get() + slot, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        MFX_HIP(hipStreamSynchronize(st));
-        done = left == 0;
-        return MFX_OK;
-    };
-
+    float *R = cw->R.get(), *Q = cw->Q.get(), *part = cw->part.get();
+    float* Z = implicit ? cw->Z.get() : R;  // the explicit models' preconditioner is the identity
     // b into R; warm: the gathered part of A y0 into Q, then G y0 on top (implicit)
-    MFX_TRY(gather(warm ? 3 : 2, h, X, x_rows, k, implicit, m.alpha, Y, nullptr, Q.get(), R.get(), ws.get(), st));
-    if (warm && implicit) MFX_TRY(foldcg_dense(Y, nseg, k, m.G, nullptr, Q.get(), Q.get(), st));
-    hipLaunchKernelGGL(k_foldcg_start, grid, block, 0, st, h.ptr.get(), nseg, k, Y, R.get(), Z, P.get(), Q.get(), (int32_t) warm, m.reg, m.lambda,
-                       m.tol, bb.get(), frozen.get(), counts);
+    MFX_TRY(gather(warm ? 3 : 2, h, X, x_rows, k, implicit, m.alpha, Y, nullptr, Q, R, part, st));
+    if (warm && implicit) MFX_TRY(foldcg_dense(Y, nseg, k, m.G, nullptr, Q, Q, st));
+    hipLaunchKernelGGL(k_foldcg_start, dim3((nseg + 3) / 4), dim3(256), 0, st, h.ptr.get(), nseg, k, Y, R, Z, cw->P.get(), Q, (int32_t) warm, m.reg,
+                       m.lambda, m.tol, cw->bb.get(), cw->frozen.get(), counts);
     MFX_HIP(hipGetLastError());
-    if (implicit) MFX_TRY(foldcg_dense(R.get(), nseg, k, m.Minv, frozen.get(), nullptr, Z, st));
-    hipLaunchKernelGGL(k_foldcg_dir, grid, block, 0, st, nseg, k, R.get(), Z, P.get(), 1, gamma.get(), frozen.get(),
-                       stop ? active.get() : nullptr);
-    MFX_HIP(hipGetLastError());
-    bool done = false;
-    if (stop) MFX_TRY(all_frozen(0, done));
-    for (int32_t s = 0; s < m.steps && !done; ++s) {
-        MFX_TRY(gather(1, h, X, x_rows, k, implicit, m.alpha, P.get(), frozen.get(), Q.get(), nullptr, ws.get(), st));
-        if (implicit) MFX_TRY(foldcg_dense(P.get(), nseg, k, m.G, frozen.get(), Q.get(), Q.get(), st));
-        hipLaunchKernelGGL(k_foldcg_step, grid, block, 0, st, h.ptr.get(), nseg, k, Y, R.get(), P.get(), Q.get(), m.reg, m.lambda, m.tol,
-                           gamma.get(), bb.get(), frozen.get(), counts, fail);
-        MFX_HIP(hipGetLastError());
-        if (s + 1 == m.steps) break;  // (the direction of a step that never comes)
-        if (implicit) MFX_TRY(foldcg_dense(R.get(), nseg, k, m.Minv, frozen.get(), nullptr, Z, st));
-        hipLaunchKernelGGL(k_foldcg_dir, grid, block, 0, st, nseg, k, R.get(), Z, P.get(), 0, gamma.get(), frozen.get(),
-                           stop ? active.get() + s + 1 : nullptr);
-        MFX_HIP(hipGetLastError());
-        if (stop) MFX_TRY(all_frozen((uint32_t) s + 1, done));
-    }
-    MFX_HIP(hipStreamSynchronize(st));  // (the workspace goes with this call)
-    return MFX_OK;
+    return cg_iterate(h, 1, k, m, Y, *cw, counts, fail, stop ? cw->active.get() : nullptr,
+                      [&] { return gather(1, h, X, x_rows, k, implicit, m.alpha, cw->P.get(), cw->frozen.get(), Q, nullptr, part, st); }, st);
 }
 
 }  // namespace mfx

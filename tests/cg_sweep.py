@@ -5,7 +5,7 @@ Inputs, for a rank k: foldin_cg_ref.inputs(k, 4200, sizes), so the seeds and dra
 (H = standard_normal((4200, k), seed k) / sqrt(k) as fp32, rows of distinct sorted items with values 1..5 and 15 % explicit
 zeros, seed 100 + k, the warm start W0 = 0.1 N(0, 1), seed 1000 + k), lambda = 0.1.  Two size sets:
     S: 12 rows (0, 1, 2, 3, 4, 5, 17, 130, 2048, 2049, 4097, 1): an empty row, the tails of kGatherRows = 4, a row that is
-       exactly one chunk, one split in two and one split in three (k_foldcg_reduce, k_explcg_reduce)
+       exactly one chunk, one split in two and one split in three (k_cg_reduce)
     M: 140 rows, sizes cycling through 0..40 with rows 32..63 empty: two blocks of k_foldcg_dense and of the per-row kernels,
        the second with one ragged wavefront and idle ones, and one wavefront (rows 32..63) frozen from the start
 Models on S: up to rank 136 the implicit model at alpha = 1 and 40, ALS and CCD on foldin_cg_ref.explicit_values; above,
@@ -73,12 +73,13 @@ def dispatch_constants():
     f_ladder = [tuple(map(int, m)) for m in re.findall(r"if\s*\(c\s*<=\s*(\d+)\)\s*launch_gather_c<(\d+)>\(mode,", fold)]
     f_last = re.findall(r"else\s+launch_gather_c<(\d+)>\(mode,", fold)
     assert f_ladder == [(1, 1), (2, 2), (4, 4), (8, 8)] and f_last == ["16"], (f_ladder, f_last)
-    assert re.findall(r"k_foldcg_gather<C,\s*(\d)>\)", fold) == ["1", "2", "3"]
+    assert re.findall(r"k_cg_gather<C,\s*1,\s*(\d)>\)", fold) == ["1", "2", "3"]  # one system per wavefront (TG = 1), MODE 1 .. 3
     # the first pass forms b (MODE 2) and, warm, the sum over y0 as well (MODE 3); a step is MODE 1
     assert len(re.findall(r"gather\(warm\s*\?\s*3\s*:\s*2,", fold)) == 1 and len(re.findall(r"gather\(1,", fold)) == 1
     e_ladder = [tuple(map(int, m)) for m in re.findall(r"if\s*\(c\s*<=\s*(\d+)\)\s*launch_gather<(\d+),\s*(\d+)>\(h,", expl)]
     e_last = re.findall(r"else\s+launch_gather<(\d+),\s*(\d+)>\(h,", expl)
     assert e_ladder == [(1, 1, 16), (2, 2, 16), (4, 4, 8), (8, 8, 4)] and e_last == [("16", "1")], (e_ladder, e_last)
+    assert len(re.findall(r"k_cg_gather<C,\s*TG,\s*1>\)", expl)) == 1  # the same kernel, TG targets per wavefront, MODE 1
     dense = re.findall(r"switch\s*\(k\s*>\s*(\d+)\s*\?\s*(\d+)\s*:\s*\(k\s*\+\s*31\)\s*/\s*32\)", fold)
     cases = re.findall(r"case\s+(\d+):\s*hipLaunchKernelGGL\(k_foldcg_dense<(\d+)>", fold)
     default = re.findall(r"default:\s*hipLaunchKernelGGL\(k_foldcg_dense<(\d+)>", fold)
@@ -99,7 +100,7 @@ def dispatch_constants():
 
 def dispatch(k):
     """(C, TG, ND, last width, nb) of rank k: the columns per lane of both gathers, the targets per wavefront of
-    k_explcg_gather, the 32-column tiles of k_foldcg_dense, the width of its last column block and the blocks of the device
+    explanation's k_cg_gather, the 32-column tiles of k_foldcg_dense, the width of its last column block and the blocks of the device
     inverse."""
     assert 1 <= k <= 1024, k
     d = dispatch_constants()

@@ -53,9 +53,9 @@ def test_the_rank_lists_reach_every_instance():
     d = cs.dispatch_constants()
     assert cs.ALL_RANKS == sorted(set(cs.ALL_RANKS)) and cs.ALL_RANKS[:136] == list(range(1, 137)) and cs.RANGES[0] == (1, 17) and cs.RANGES[-1] == (120, 136)
     disp = {k: cs.dispatch(k) for k in cs.ALL_RANKS}
-    # k_foldcg_gather<C, MODE>: every rank runs MODE 2 (cold start), MODE 3 (warm start) and MODE 1 (a step), so every C is enough
+    # k_cg_gather<C, 1, MODE>: every rank runs MODE 2 (cold start), MODE 3 (warm start) and MODE 1 (a step), so every C is enough
     assert {v[0] for v in disp.values()} == set(d["fold"])
-    assert {(v[0], v[1]) for v in disp.values()} == set(d["explain"])                      # k_explcg_gather<C, TG>
+    assert {(v[0], v[1]) for v in disp.values()} == set(d["explain"])                      # k_cg_gather<C, TG, 1>
     assert {v[2] for v in disp.values()} == {1, 2, 3, 4}                                   # k_foldcg_dense<ND>
     for C in d["fold"]:                                                                    # both settings of vec in every class
         assert {cs.vec(k) for k, v in disp.items() if v[0] == C} == {True, False}, C

@@ -6,8 +6,8 @@ sources).  Coverage of a launch whose result is compared with a reference that i
 every CG test.  BEFORE this module (ranks 37, 64, 130, 160, 256, 1024 only):
 
     kernel                    chosen by                               run                                  never run
-    k_foldcg_gather<C, MODE>  C from ceil(k / 64) on 1, 2, 4, 8, 16   C = 1, 4, 16                         C = 2 (65..128), C = 8 (257..512)
-    k_explcg_gather<C, TG>    the same ladder, TG = 16, 16, 8, 4, 1   <1,16>, <4,8>, <16,1>                <2,16>, <8,4>
+    k_cg_gather<C, 1, MODE>   C from ceil(k / 64) on 1, 2, 4, 8, 16   C = 1, 4, 16                         C = 2 (65..128), C = 8 (257..512)
+    k_cg_gather<C, TG, 1>     the same ladder, TG = 16, 16, 8, 4, 1   <1,16>, <4,8>, <16,1>                <2,16>, <8,4>
     k_foldcg_dense<ND>        k > 128 ? 4 : ceil(k / 32)              ND = 2, 4                            ND = 1 (k <= 32), ND = 3 (65..96)
     load4 of k_foldcg_dense   k % 4, tail k % 8                       k = 37, 130 not vectorised           k = 1, 2, 3, most residues of k % 8
     target groups             T = 5 < TG = 8, 16                      a second, ragged group at C = 16     at every other C
@@ -72,7 +72,7 @@ scalar load4 below rank 4, every ragged last column block, the frozen wavefront,
 with the margin of the six ranks tested before, and no figure grows towards a class edge.  That the checks would have seen one
 was tried once with two deliberate defects in a build that was not kept: the last column of k_foldcg_dense<3> not stored at
 k % 8 = 5 (refused by checks 1 to 4 under the implicit model at k = 69, 77 and 85, at no other rank of 69..85), and the last
-target of a ragged group of k_explcg_gather<8, 4> not gathered (refused by check 4 at k = 257, the first rank of that class; the
+target of a ragged group of k_cg_gather<8, 4, 1> not gathered (refused by check 4 at k = 257, the first rank of that class; the
 run was stopped there).
 """
 import numpy as np

@@ -197,6 +197,30 @@ def test_a_pair_does_not_depend_on_its_batch(mfx, k):
             print(f"explcg-measured independence k={k} tol={tol} steps={sorted(set(full['target_steps'][live].tolist()))} bitwise=equal")
 
 
+@pytest.mark.parametrize("k,T", [(64, 17), (256, 9)])
+def test_a_pair_of_a_split_row_does_not_depend_on_its_gather_group(mfx, k, T):
+    """A row of ten chunks (ten partial slots, summed per target) with a slot of T targets that spans two gather groups, the
+    second holding one target (k = 64: 16 + 1; k = 256: 8 + 1): every pair bit for bit the pair in a slot of its own."""
+    alpha, model, steps = 40.0, ref.IMPLICIT, 4
+    cols, sizes = TEN_CHUNKS
+    ptr, idx, val, H = data(model, k, cols, sizes)
+    rng = np.random.default_rng(11 + k)
+    tg = rng.integers(0, cols, (len(sizes), T)).astype(np.uint32)
+    tg[:, 0] = idx[0]   # an item of the long row
+    tg[:, 3] = PAD
+    with rec(mfx, H) as r:
+        r.fold_in_cg_setup(model, LAM, alpha, steps=steps, tol=0.0)
+        full = call(r, (ptr, idx, val), tg)
+        live = xr.live_pairs(model, k, alpha, tg, cols, sizes)
+        assert live[0].sum() == T - 1 and (full["target_steps"][live] == steps).all() and not full["target_steps"][~live].any()
+        assert np.isfinite(full["Z"]).all() and full["Z"][live].any(axis=1).all()
+        for t in range(T):
+            one = call(r, (ptr, idx, val), tg[:, [t]])
+            assert all(same(one[key][:, 0], full[key][:, t]) for key in ("Z", "target_steps")), (k, T, t)
+            assert all(same(one[key], full[key]) for key in ROW_KEYS), (k, T, t)
+    print(f"explcg-measured gather-groups k={k} T={T} chunks=10 pairs={int(live.sum())} bitwise=equal")
+
+
 # ------------------------------------------------------------------------------------------------ 6. stop rule, counts
 def test_pairs_stop_on_their_own(mfx):
     k, alpha, tol, model = 160, 40.0, 1e-4, ref.IMPLICIT
