@@ -9,6 +9,7 @@
 #include "bpr.hpp"
 #include "ccd_solver.hpp"
 #include "knn.hpp"
+#include "lgcn.hpp"
 #include "recommend.hpp"
 #include "slim.hpp"
 #include "ease.hpp"
@@ -471,6 +472,70 @@ int mfx_bpr_trial_stats(mfx_bpr_t s, int64_t out[2]) {
         s->impl->trial_stats(out);
         return MFX_OK;
     });
+}
+
+/* ------------------------------------------------------------------ LightGCN: BPR on graph-propagated embeddings */
+int mfx_lgcn_create(mfx_lgcn_t* out, const mfx_csx* R, const mfx_params* p, float lr, int64_t batch, int32_t layers, uint64_t seed,
+                    mfx_memspace space) {
+    return guarded("mfx_lgcn_create", [&]() -> int {
+        return make_handle("mfx_lgcn_create", out, [&](LgcnSolver** s) { return LgcnSolver::create(s, R, p, lr, batch, layers, seed, space); });
+    });
+}
+int mfx_lgcn_set_base(mfx_lgcn_t s, const float* W0, const float* H0, mfx_memspace space) {
+    return guarded("mfx_lgcn_set_base", [&]() -> int {
+        MFX_REQUIRE(s && s->impl, "null solver");
+        return s->impl->set_base(W0, H0, space);
+    });
+}
+int mfx_lgcn_get_base(mfx_lgcn_t s, float* W0, float* H0, mfx_memspace space) {
+    return guarded("mfx_lgcn_get_base", [&]() -> int {
+        MFX_REQUIRE(s && s->impl, "null solver");
+        return s->impl->get_base(W0, H0, space);
+    });
+}
+int mfx_lgcn_get_factors(mfx_lgcn_t s, float* W, float* H, mfx_memspace space) {
+    return guarded("mfx_lgcn_get_factors", [&]() -> int {
+        MFX_REQUIRE(s && s->impl, "null solver");
+        return s->impl->get_factors(W, H, space);
+    });
+}
+int mfx_lgcn_steps(mfx_lgcn_t s, int64_t n_steps, int64_t stats[4], double* seconds) {
+    return guarded("mfx_lgcn_steps", [&]() -> int {
+        MFX_REQUIRE(s && s->impl, "null solver");
+        return s->impl->steps(n_steps, stats, seconds);
+    });
+}
+int mfx_lgcn_epochs(mfx_lgcn_t s, int32_t n_epochs, int64_t* stats, double* seconds) {
+    return guarded("mfx_lgcn_epochs", [&]() -> int {
+        MFX_REQUIRE(s && s->impl, "null solver");
+        return s->impl->epochs(n_epochs, stats, seconds);
+    });
+}
+int mfx_lgcn_position(mfx_lgcn_t s, int64_t* next_slot) {
+    return guarded("mfx_lgcn_position", [&]() -> int {
+        MFX_REQUIRE(s && s->impl && next_slot, "null solver or next_slot");
+        *next_slot = s->impl->position();
+        return MFX_OK;
+    });
+}
+int mfx_lgcn_kernel_times(mfx_lgcn_t s, double seconds[6]) {
+    return guarded("mfx_lgcn_kernel_times", [&]() -> int {
+        MFX_REQUIRE(s && s->impl && seconds, "null solver or seconds");
+        s->impl->times(seconds);
+        return MFX_OK;
+    });
+}
+int mfx_lgcn_destroy(mfx_lgcn_t s) {
+    return guarded("mfx_lgcn_destroy", [&]() -> int {
+        return destroy_handle(s);
+    });
+}
+int mfx_lgcn_propagate(const mfx_csx* R, const float* W0, const float* H0, int64_t k, int32_t layers, float* W, float* H, int device) {
+    return guarded("mfx_lgcn_propagate", [&]() -> int { return lgcn_propagate(R, W0, H0, k, layers, W, H, device); });
+}
+int mfx_lgcn_apply(const mfx_csx* R, int64_t k, float* W0, float* H0, int64_t n, const uint32_t* u, const uint32_t* i, const uint32_t* j,
+                   const uint8_t* skipped, int32_t layers, float lr, float lambda, int64_t stats[4], int device) {
+    return guarded("mfx_lgcn_apply", [&]() -> int { return lgcn_apply(R, k, W0, H0, n, u, i, j, skipped, layers, lr, lambda, stats, device); });
 }
 
 /* ------------------------------------------------------------------ item-kNN: neighbour lists on the interaction matrix */

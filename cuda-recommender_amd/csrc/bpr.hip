@@ -291,19 +291,26 @@ int BprCore::download(float* W, float* H, mfx_memspace space) {
     return MFX_OK;
 }
 
-int BprCore::step(uint32_t n, float lr, float lambda) {
+namespace {
+BprArgs args_of(const BprCore& c, uint32_t n, float lr, float lambda) {
+    BprArgs a{};
+    a.W = c.W_.get(); a.H = c.H_.get();
+    a.accW = c.accW_.get(); a.accH = c.accH_.get();
+    a.cntW = c.cntW_.get(); a.cntH = c.cntH_.get();
+    a.claimW = c.claimW_.get(); a.claimH = c.claimH_.get();
+    a.u = c.u_.get(); a.i = c.i_.get(); a.j = c.j_.get();
+    a.skipped = c.skip_.get(); a.g = c.g_.get(); a.state = c.state_.get();
+    a.stats = c.stats_.get();
+    a.n = n; a.k = (int) c.k_; a.gs = c.gs_; a.gsh = __builtin_ctz((unsigned) c.gs_);
+    a.lr = lr; a.lambda = lambda;
+    return a;
+}
+}  // namespace
+
+int BprCore::grad_scatter(uint32_t n) {
     if (n == 0) return MFX_OK;
     MFX_REQUIRE((int64_t) n <= batch_, "bpr: a step of %u slots on a handle made for %lld", n, (long long) batch_);
-    BprArgs a{};
-    a.W = W_.get(); a.H = H_.get();
-    a.accW = accW_.get(); a.accH = accH_.get();
-    a.cntW = cntW_.get(); a.cntH = cntH_.get();
-    a.claimW = claimW_.get(); a.claimH = claimH_.get();
-    a.u = u_.get(); a.i = i_.get(); a.j = j_.get();
-    a.skipped = skip_.get(); a.g = g_.get(); a.state = state_.get();
-    a.stats = stats_.get();
-    a.n = n; a.k = (int) k_; a.gs = gs_; a.gsh = __builtin_ctz((unsigned) gs_);
-    a.lr = lr; a.lambda = lambda;
+    const BprArgs a = args_of(*this, n, 0.f, 0.f);
     if (profile_) MFX_HIP(hipEventRecord(ev_[1], st_));
     if (neg_mode_ != MFX_BPR_NEG_WARP) {  // (WARP: k_bpr_trials has written g and the state, its weight is no sigmoid)
         hipLaunchKernelGGL(k_bpr_grad, dim3(grid_of(n)), dim3(kBprThreads), 0, st_, a);
@@ -313,6 +320,12 @@ int BprCore::step(uint32_t n, float lr, float lambda) {
     hipLaunchKernelGGL(k_bpr_scatter, dim3(grid_of((uint64_t) n * gs_)), dim3(kBprThreads), 0, st_, a);
     MFX_LAUNCH_CHECK();
     if (profile_) MFX_HIP(hipEventRecord(ev_[3], st_));
+    return MFX_OK;
+}
+
+int BprCore::apply(uint32_t n, float lr, float lambda) {
+    if (n == 0) return MFX_OK;
+    const BprArgs a = args_of(*this, n, lr, lambda);
     hipLaunchKernelGGL(k_bpr_apply, dim3(grid_of((uint64_t) n * 3 * gs_)), dim3(kBprThreads), 0, st_, a);
     MFX_LAUNCH_CHECK();
     if (profile_) {
@@ -324,6 +337,49 @@ int BprCore::step(uint32_t n, float lr, float lambda) {
             phase_s_[p] += 1e-3 * ms;
         }
     }
+    return MFX_OK;
+}
+
+int BprCore::step(uint32_t n, float lr, float lambda) {
+    MFX_TRY(grad_scatter(n));
+    return apply(n, lr, lambda);
+}
+
+int BprCore::sample(uint64_t s0, uint64_t base, uint32_t n, const uint32_t* ptr, const uint32_t* idx, uint32_t nnz) {
+    hipLaunchKernelGGL(k_bpr_sample, dim3(grid_of(n)), dim3(kBprThreads), 0, st_, s0, base, n, ptr, idx, (uint32_t) rows_, (uint32_t) cols_, nnz,
+                       u_.get(), i_.get(), j_.get(), skip_.get());
+    MFX_LAUNCH_CHECK();
+    return MFX_OK;
+}
+
+int BprCore::set_slots(const char* fn, int64_t n, const uint32_t* u, const uint32_t* i, const uint32_t* j, const uint8_t* skipped) {
+    MFX_TRY(u_.upload(u, (size_t) n, MFX_HOST, st_));
+    MFX_TRY(i_.upload(i, (size_t) n, MFX_HOST, st_));
+    MFX_TRY(j_.upload(j, (size_t) n, MFX_HOST, st_));
+    if (skipped) MFX_TRY(skip_.upload(skipped, (size_t) n, MFX_HOST, st_));
+    else MFX_HIP(hipMemsetAsync(skip_.get(), 0, (size_t) n, st_));
+    DevBuf<uint32_t> bad;
+    MFX_TRY(bad.alloc(1));
+    MFX_HIP(hipMemsetAsync(bad.get(), 0xFF, sizeof(uint32_t), st_));
+    hipLaunchKernelGGL(k_bpr_check_ids, dim3(grid_of((uint64_t) n)), dim3(kBprThreads), 0, st_, u_.get(), i_.get(), j_.get(), (uint32_t) n,
+                       (uint32_t) rows_, (uint32_t) cols_, bad.get());
+    MFX_LAUNCH_CHECK();
+    uint32_t first_bad = kNoClaim;
+    MFX_HIP(hipMemcpyAsync(&first_bad, bad.get(), sizeof(uint32_t), hipMemcpyDeviceToHost, st_));
+    MFX_HIP(hipStreamSynchronize(st_));
+    MFX_REQUIRE(first_bad == kNoClaim, "%s: slot %u names a user >= rows or an item >= cols", fn, first_bad);
+    return MFX_OK;
+}
+
+// The rows of one side of a matrix on the device (k_bpr_check): *first_bad = the first row that breaks the rules, or 2^32 - 1.
+int bpr_check_rows(const uint32_t* ptr, const uint32_t* idx, uint32_t rows, uint32_t cols, uint32_t nnz, hipStream_t st, uint32_t* first_bad) {
+    DevBuf<uint32_t> bad;
+    MFX_TRY(bad.alloc(1));
+    MFX_HIP(hipMemsetAsync(bad.get(), 0xFF, sizeof(uint32_t), st));
+    hipLaunchKernelGGL(k_bpr_check, dim3(std::min<uint32_t>(grid_of(rows), 65536u)), dim3(kBprThreads), 0, st, ptr, idx, rows, cols, nnz, bad.get());
+    MFX_LAUNCH_CHECK();
+    MFX_HIP(hipMemcpyAsync(first_bad, bad.get(), sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    MFX_HIP(hipStreamSynchronize(st));
     return MFX_OK;
 }
 
@@ -355,15 +411,8 @@ int BprSolver::create(BprSolver** out, const mfx_csx* R, const mfx_params* p, fl
     MFX_TRY(s->idx_.alloc((size_t) R->nnz));
     MFX_TRY(s->ptr_.upload(R->csr_row_ptr, (size_t) rows + 1, space, st));
     MFX_TRY(s->idx_.upload(R->csr_col_idx, (size_t) R->nnz, space, st));
-    DevBuf<uint32_t> bad;
-    MFX_TRY(bad.alloc(1));
-    MFX_HIP(hipMemsetAsync(bad.get(), 0xFF, sizeof(uint32_t), st));
-    hipLaunchKernelGGL(k_bpr_check, dim3(std::min<uint32_t>(grid_of(rows), 65536u)), dim3(kBprThreads), 0, st, s->ptr_.get(), s->idx_.get(), rows,
-                       (uint32_t) R->cols, (uint32_t) R->nnz, bad.get());
-    MFX_LAUNCH_CHECK();
     uint32_t first_bad = kNoClaim;
-    MFX_HIP(hipMemcpyAsync(&first_bad, bad.get(), sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    MFX_HIP(hipStreamSynchronize(st));
+    MFX_TRY(bpr_check_rows(s->ptr_.get(), s->idx_.get(), rows, (uint32_t) R->cols, (uint32_t) R->nnz, st, &first_bad));
     MFX_REQUIRE(first_bad == kNoClaim,
                 "%s: row %u of the CSR side: its pointers must ascend from 0 to nnz and its ids be strictly ascending and below cols", fn,
                 first_bad);
@@ -403,9 +452,7 @@ int BprSolver::run(int64_t n_steps, bool to_epoch_end, int64_t stats[4], double*
     for (int64_t s = 0; to_epoch_end || s < n_steps; ++s) {
         const uint32_t n = (uint32_t) std::min<uint64_t>((uint64_t) core_.batch_, nnz - pos_ % nnz);
         if (core_.profile_) MFX_HIP(hipEventRecord(core_.ev_[0], st));
-        hipLaunchKernelGGL(k_bpr_sample, dim3(grid_of(n)), dim3(kBprThreads), 0, st, s0, pos_, n, ptr_.get(), idx_.get(), (uint32_t) core_.rows_,
-                           (uint32_t) core_.cols_, (uint32_t) nnz_, core_.u_.get(), core_.i_.get(), core_.j_.get(), core_.skip_.get());
-        MFX_LAUNCH_CHECK();
+        MFX_TRY(core_.sample(s0, pos_, n, ptr_.get(), idx_.get(), (uint32_t) nnz_));
         if (neg) MFX_TRY(core_.trials(n, nullptr, nullptr, s1, pos_, ptr_.get(), idx_.get()));
         MFX_TRY(core_.step(n, lr_, lambda_));
         pos_ += n;
@@ -478,21 +525,7 @@ int bpr_apply(int64_t rows, int64_t cols, int64_t k, float* W, float* H, int64_t
     BprCore core;
     MFX_TRY(core.init(rows, cols, k, n, device));
     hipStream_t st = core.st_;
-    MFX_TRY(core.u_.upload(u, (size_t) n, MFX_HOST, st));
-    MFX_TRY(core.i_.upload(i, (size_t) n, MFX_HOST, st));
-    MFX_TRY(core.j_.upload(j, (size_t) n, MFX_HOST, st));
-    if (skipped) MFX_TRY(core.skip_.upload(skipped, (size_t) n, MFX_HOST, st));
-    else MFX_HIP(hipMemsetAsync(core.skip_.get(), 0, (size_t) n, st));
-    DevBuf<uint32_t> bad;
-    MFX_TRY(bad.alloc(1));
-    MFX_HIP(hipMemsetAsync(bad.get(), 0xFF, sizeof(uint32_t), st));
-    hipLaunchKernelGGL(k_bpr_check_ids, dim3(grid_of((uint64_t) n)), dim3(kBprThreads), 0, st, core.u_.get(), core.i_.get(), core.j_.get(),
-                       (uint32_t) n, (uint32_t) rows, (uint32_t) cols, bad.get());
-    MFX_LAUNCH_CHECK();
-    uint32_t first_bad = kNoClaim;
-    MFX_HIP(hipMemcpyAsync(&first_bad, bad.get(), sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    MFX_HIP(hipStreamSynchronize(st));
-    MFX_REQUIRE(first_bad == kNoClaim, "%s: slot %u names a user >= rows or an item >= cols", fn, first_bad);
+    MFX_TRY(core.set_slots(fn, n, u, i, j, skipped));
     MFX_TRY(core.upload(W, H, MFX_HOST));
     MFX_TRY(core.step((uint32_t) n, lr, lambda));
     unsigned long long h[4] = {0, 0, 0, 0};

@@ -18,6 +18,14 @@ public:
     // One step over the n slots that sit in u_, i_, j_, skip_ (device); the four counts are ADDED to stats_ (device).
     // With neg_mode_ = MFX_BPR_NEG_WARP the gradient kernel is left out: trials() has written g_ and state_ already.
     int step(uint32_t n, float lr, float lambda);
+    // The two halves of step: k_bpr_grad and k_bpr_scatter on the factors in W_ and H_, then k_bpr_apply.  lgcn.hip runs the
+    // first half on its final embeddings and applies the sums itself.
+    int grad_scatter(uint32_t n);
+    int apply(uint32_t n, float lr, float lambda);
+    // k_bpr_sample: the slots base .. base + n - 1 of the stream s0 over the matrix (ptr, idx) into u_, i_, j_, skip_.
+    int sample(uint64_t s0, uint64_t base, uint32_t n, const uint32_t* ptr, const uint32_t* idx, uint32_t nnz);
+    // The caller's n host slots into u_, i_, j_, skip_ (skipped = NULL: none), ids checked on the device under the name fn.
+    int set_slots(const char* fn, int64_t n, const uint32_t* u, const uint32_t* i, const uint32_t* j, const uint8_t* skipped);
     // bpr_neg.hip.  init_neg after init: the mode, the number of trials M, the rank weights (WARP; NULL = the default table).
     // trials: k_bpr_trials over the n slots whose u_ and i_ are set.  Trial items from `items` [n][M] with `member` [n][M]
     // (NULL: none), or, with items = NULL, from the stream s1 at the slot numbers base + t over the matrix (ptr, idx) with
@@ -66,6 +74,7 @@ private:
     bool have_factors_ = false;
 };
 
+int bpr_check_rows(const uint32_t* ptr, const uint32_t* idx, uint32_t rows, uint32_t cols, uint32_t nnz, hipStream_t st, uint32_t* first_bad);
 int bpr_triples(uint64_t seed, int64_t first_slot, int64_t count, const mfx_csx* R, uint32_t* u, uint32_t* i, uint32_t* j, uint8_t* skipped);
 int bpr_apply(int64_t rows, int64_t cols, int64_t k, float* W, float* H, int64_t n, const uint32_t* u, const uint32_t* i, const uint32_t* j,
               const uint8_t* skipped, float lr, float lambda, int64_t stats[4], int device);

@@ -1,6 +1,7 @@
 // bpr_device.hpp -- what the two device units of BPR training share (bpr.hip: the step; bpr_neg.hip: the trials): the
 // stateless sampler, one function for kernel and host each, the states of a slot and the single fp32 operations.  The
-// contract is in include/mfx.h ("BPR training").  Included by those two units only.
+// contract is in include/mfx.h ("BPR training").  Included by those two units and by lgcn.hip, which runs the same step on
+// propagated embeddings.
 #pragma once
 
 #include <cstdint>

@@ -148,6 +148,19 @@ SIGNATURES = {
     "mfx_bpr_apply_neg": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, f32p, f32p, C.c_int64, u32p, u32p, C.c_int64, u32p, C.c_void_p,
                                     C.c_int32, C.c_void_p, C.c_float, C.c_float, i64p, C.c_void_p, C.c_void_p, C.c_int]),
     "mfx_bpr_trial_stats": (C.c_int, [C.c_void_p, i64p]),
+    "mfx_lgcn_create": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(mfx_csx), C.POINTER(mfx_params), C.c_float, C.c_int64, C.c_int32,
+                                  C.c_uint64, C.c_int]),
+    "mfx_lgcn_set_base": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    "mfx_lgcn_get_base": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    "mfx_lgcn_get_factors": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    "mfx_lgcn_steps": (C.c_int, [C.c_void_p, C.c_int64, i64p, f64p]),
+    "mfx_lgcn_epochs": (C.c_int, [C.c_void_p, C.c_int32, i64p, f64p]),
+    "mfx_lgcn_position": (C.c_int, [C.c_void_p, i64p]),
+    "mfx_lgcn_kernel_times": (C.c_int, [C.c_void_p, f64p]),
+    "mfx_lgcn_destroy": (C.c_int, [C.c_void_p]),
+    "mfx_lgcn_propagate": (C.c_int, [C.POINTER(mfx_csx), f32p, f32p, C.c_int64, C.c_int32, f32p, f32p, C.c_int]),
+    "mfx_lgcn_apply": (C.c_int, [C.POINTER(mfx_csx), C.c_int64, f32p, f32p, C.c_int64, u32p, u32p, u32p, C.c_void_p, C.c_int32,
+                                 C.c_float, C.c_float, i64p, C.c_int]),
     "mfx_knn_build": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(mfx_csx), C.c_int32, C.c_int32, C.c_int, C.c_int]),
     "mfx_knn_create_from_lists": (C.c_int, [C.POINTER(C.c_void_p), C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
     "mfx_knn_lists": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),

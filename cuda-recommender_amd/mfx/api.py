@@ -773,6 +773,124 @@ def bpr_apply_neg(W, H, u, i, items, lr: float, lam: float, loss: str = "bpr", m
 
 
 # ---------------------------------------------------------------------------------------------
+# LightGCN: BPR on graph-propagated embeddings (mfx_lgcn_*)
+# ---------------------------------------------------------------------------------------------
+class LightGcnSolver:
+    """Resident LightGCN training (mfx_lgcn_*, include/mfx.h): BprSolver's deterministic mini-batch steps, with the vectors
+    that enter the pairwise loss being the mean of the base embeddings and their `layers` propagated copies under the
+    symmetrically normalised interaction graph; layers = 0 is BprSolver bit for bit.  Reads k, lambda_, device and profile of
+    `parameters`; both sides of R's pattern are read, values ignored.  The base embeddings use the ALS layout, W0 [rows][k]
+    and H0 [cols][k]; without set_base the first step draws BprSolver's defaults, 0.1 * N(0, 1) from
+    numpy.random.default_rng(init_seed).  get_factors() returns the final embeddings (W, H), which serve Recommender, query,
+    evaluate, IVF and MMR as any factors do.  Every step propagates the whole graph: its cost grows with nnz * k * layers."""
+
+    def __init__(self, R: Optional[RatingData], parameters: parameter, lr: float, batch: int, layers: int, seed: int = 0,
+                 device_arrays: Optional[dict] = None, init_seed: Optional[int] = None):
+        self.handle = C.c_void_p()
+        cp = parameters.to_c()
+        if device_arrays is not None:
+            self.rows, self.cols, self.k = int(device_arrays["rows"]), int(device_arrays["cols"]), int(parameters.k)
+            csx, space = _device_csx_coo(device_arrays)[0], L.MFX_DEVICE
+        else:
+            self.rows, self.cols, self.k = R.rows, R.cols, int(parameters.k)
+            csx, space = _csx(R), L.MFX_HOST
+        self.layers = int(layers)
+        self._init_seed, self._have_base = init_seed, False
+        L.check(L.lib().mfx_lgcn_create(C.byref(self.handle), C.byref(csx), C.byref(cp), float(lr), int(batch), self.layers, int(seed), space))
+
+    def set_base(self, W0, H0):
+        _f32c(W0, (self.rows, self.k))
+        _f32c(H0, (self.cols, self.k))
+        L.check(L.lib().mfx_lgcn_set_base(self.handle, _vp(W0), _vp(H0), L.MFX_HOST))
+        self._have_base = True
+
+    def _default_base(self):
+        if not self._have_base:
+            rng = np.random.default_rng(self._init_seed)
+            W0 = (0.1 * rng.standard_normal((self.rows, self.k))).astype(np.float32)
+            H0 = (0.1 * rng.standard_normal((self.cols, self.k))).astype(np.float32)
+            self.set_base(W0, H0)
+
+    def _pair(self, fn):
+        W = np.empty((self.rows, self.k), np.float32)
+        H = np.empty((self.cols, self.k), np.float32)
+        L.check(fn(self.handle, _vp(W), _vp(H), L.MFX_HOST))
+        return W, H
+
+    def get_base(self):
+        """The base embeddings (W0, H0): what the steps update."""
+        return self._pair(L.lib().mfx_lgcn_get_base)
+
+    def get_factors(self):
+        """The final embeddings (W, H) of the current base: lgcn_propagate(R, *get_base(), layers)."""
+        return self._pair(L.lib().mfx_lgcn_get_factors)
+
+    def steps(self, n: int) -> dict:
+        """n steps from the current slot: {"slots", "skipped", "bad", "correct", "auc", "seconds"} of the call."""
+        self._default_base()
+        stats, sec = (C.c_int64 * 4)(), C.c_double(0.0)
+        L.check(L.lib().mfx_lgcn_steps(self.handle, int(n), stats, C.byref(sec)))
+        return _bpr_report(stats, sec.value)
+
+    def iterate(self, n_epochs: int) -> List[dict]:
+        """n_epochs epochs (the first finishes a started one): one report per epoch."""
+        self._default_base()
+        n = int(n_epochs)
+        stats, sec = (C.c_int64 * (4 * max(1, n)))(), (C.c_double * max(1, n))()
+        L.check(L.lib().mfx_lgcn_epochs(self.handle, n, stats, sec))
+        return [_bpr_report(stats[4 * e:4 * e + 4], sec[e]) for e in range(n)]
+
+    def position(self) -> int:
+        out = C.c_int64(0)
+        L.check(L.lib().mfx_lgcn_position(self.handle, C.byref(out)))
+        return int(out.value)
+
+    def kernel_times(self) -> dict:
+        """Stream seconds since create by phase, collected with parameters.profile = 1 only."""
+        out = (C.c_double * 6)()
+        L.check(L.lib().mfx_lgcn_kernel_times(self.handle, out))
+        return dict(zip(("sample", "forward", "gradient", "scatter", "backward", "update"), (float(x) for x in out)))
+
+    def close(self):
+        if self.handle:
+            L.lib().mfx_lgcn_destroy(self.handle)
+            self.handle = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def lgcn_propagate(R: RatingData, W0, H0, layers: int, device: int = 0):
+    """The final embeddings (W, H) of the base embeddings W0 [rows][k], H0 [cols][k] over R's pattern (mfx_lgcn_propagate):
+    the mean of the base and its `layers` propagated copies."""
+    W0, H0 = _f32c(W0), _f32c(H0)
+    assert W0.ndim == 2 and H0.ndim == 2 and W0.shape[1] == H0.shape[1] and W0.shape[0] == R.rows and H0.shape[0] == R.cols
+    W, H = np.empty_like(W0), np.empty_like(H0)
+    csx = _csx(R)
+    L.check(L.lib().mfx_lgcn_propagate(C.byref(csx), _f32(W0), _f32(H0), W0.shape[1], int(layers), _f32(W), _f32(H), device))
+    return W, H
+
+
+def lgcn_apply(R: RatingData, W0, H0, u, i, j, layers: int, lr: float, lam: float, skipped=None, device: int = 0):
+    """One LightGCN step on the given triples at the base embeddings W0, H0 (mfx_lgcn_apply): returns (W0', H0', stats); a
+    slot is skipped only where `skipped` says so."""
+    W0, H0 = np.array(_f32c(W0)), np.array(_f32c(H0))
+    assert W0.ndim == 2 and H0.ndim == 2 and W0.shape[1] == H0.shape[1] and W0.shape[0] == R.rows and H0.shape[0] == R.cols
+    u, i, j = (np.ascontiguousarray(a, np.uint32) for a in (u, i, j))
+    assert u.shape == i.shape == j.shape and u.ndim == 1
+    s = None if skipped is None else np.ascontiguousarray(skipped, np.uint8)
+    assert s is None or s.shape == u.shape
+    stats = (C.c_int64 * 4)()
+    csx = _csx(R)
+    L.check(L.lib().mfx_lgcn_apply(C.byref(csx), W0.shape[1], _f32(W0), _f32(H0), u.shape[0], _u32(u), _u32(i), _u32(j), _vp(s),
+                                   int(layers), float(lr), float(lam), stats, device))
+    return W0, H0, _bpr_report(stats, 0.0)
+
+
+# ---------------------------------------------------------------------------------------------
 # item-kNN: the neighbourhood model on the interaction matrix (mfx_knn_*)
 # ---------------------------------------------------------------------------------------------
 def knn_weights(R: RatingData, scheme: Optional[str], k1: float = 1.2, b: float = 0.75) -> RatingData:

@@ -397,7 +397,8 @@ int mfx_als_block_half(int64_t nseg, int64_t nnz, const uint32_t* ptr, const uin
  * mfx_bpr_create reads k, lambda, device and profile of *p.  MFX_ERR_INVALID without touching the device: k outside
  * 1..1024, batch outside 1..2^20, lr or lambda negative or not finite, nnz = 0, cols < 2, a null argument.  Memory on the
  * device: the factors, 8 bytes beside every factor element (the accumulators), 8 bytes per row and column, the CSR
- * pointers and ids, 18 bytes per slot of a step.  After create no step's cost grows with rows + cols.
+ * pointers and ids, 18 bytes per slot of a step.  After create no step's cost grows with rows + cols (this does not hold
+ * for mfx_lgcn_* below, which propagates the whole graph every step: nnz * k * layers by construction).
  * mfx_bpr_set_factors copies W and H (both required); stepping or mfx_bpr_get_factors before it is MFX_ERR_INVALID and
  * leaves the handle usable.  mfx_bpr_steps runs n_steps steps from the current slot; mfx_bpr_epochs runs n_epochs
  * epochs, the first of them being the remaining steps of a started epoch; stats [4] (per epoch: [n_epochs][4]) = slots,
@@ -479,6 +480,75 @@ int mfx_bpr_apply_neg(int64_t rows, int64_t cols, int64_t k, float* W, float* H,
                       int64_t stats[4], uint32_t* j_out /* [n] or NULL */, uint32_t* t_out /* [n] or NULL, 0 = none chosen */,
                       int device);
 int mfx_bpr_trial_stats(mfx_bpr_t s, int64_t out[2]);
+
+/* ------------------------------------------------------------------------------------
+ * LightGCN (He et al., SIGIR 2020): BPR training on graph-propagated embeddings.  The user and item vectors that enter
+ * the pairwise loss are the mean of the base embeddings and their L propagated copies under the symmetrically normalised
+ * interaction graph; sampler, score chain, sigmoid, bad rule, fixed-point sums and counts are those of "BPR training"
+ * above.  Every bit of the base embeddings is fixed by (data, seed, parameters, batch, layers): no bit depends on launch
+ * geometry, lanes per row, tile width or batch of loads.
+ *
+ * Data.  Only the pattern of R is read, BOTH sides: the CSR side gives a user's items, the CSC side an item's users; values
+ * are ignored.  Each side must satisfy the row rules of BPR (pointers from 0 to nnz, ids strictly ascending and in range),
+ * and the CSC side must be the transpose pattern of the CSR side; all three are checked on the device at create
+ * (MFX_ERR_INVALID naming the first row or column).  d_x = the degree of a user or item, s_x = fp32(1 / sqrt((double) d_x)),
+ * s_x = 0 where d_x = 0; L = `layers`, 0 <= L <= 8; c_L = fp32(1 / fp32(L + 1)), one correctly rounded division.
+ *
+ * One propagation half-pass produces the rows of one side from the rows X of the other side.  Destination row r has the
+ * entries e_0 .. e_{n-1} in stored order (CSR order for a user, CSC order for an item).  For coordinate c:
+ *   the entries are cut into segments of 1024 consecutive entries;
+ *   a segment's sum is the fp32 FMA chain acc = fmaf(s[src_e], X[src_e][c], acc) over its entries from +0;
+ *   the segment sums are added left to right in fp32, starting from the first segment's sum;
+ *   the result is fp32(s_r * total).
+ * A row of at most 1024 entries is one chain, an empty row gives +0.  The constant 1024 is part of the contract.
+ * Layers.  E^0 = (W0, H0), the base embeddings.  E^{l+1}: its user rows by a half-pass from the item rows of E^l, its item
+ * rows by a half-pass from the user rows of E^l.  The final embeddings are fp32(c_L * (((E^0 + E^1) + ...) + E^L)), the sum
+ * left to right in fp32; for L = 0 they are the base embeddings bit for bit.
+ *
+ * One step on n <= batch slots (u, i, j, skipped):
+ *   1. (W, H) = the final embeddings of the current base;
+ *   2. the step of "BPR training" on (W, H) up to its sums: g, the states and counts, the 2^-36 fixed-point sums a row, m_r
+ *      = the counted slots of row r;
+ *   3. G[r][c] = the fp32 nearest to the sum (one rounding, int64 -> fp32, then the exact scale) for the rows with
+ *      m_r > 0, +0 elsewhere;
+ *   4. D = the propagation and mean of step 1 applied to G (G's own layers, the same c_L): the normalised adjacency is
+ *      symmetric, so this is the gradient with respect to the base;
+ *   5. every row r with m_r > 0, or with L >= 1 and d_r > 0:
+ *        new = fp32(old + fp32(lr * fp32(D[r][c] - fp32(fp32(lambda * fp32(m_r)) * old))));  other rows keep their bits.
+ * With L = 0 this is the step of mfx_bpr_apply bit for bit.  Every step propagates the whole graph twice: its cost grows
+ * with nnz * k * L, unlike a BPR step.
+ *
+ * mfx_lgcn_create reads k, lambda, device and profile of *p.  MFX_ERR_INVALID without touching the device: k outside
+ * 1..1024, batch outside 1..2^20, layers outside 0..8, lr or lambda negative or not finite, nnz = 0, cols < 2, a null
+ * argument or side.  Memory on the device: 32 bytes per element of the embeddings (base, final, accumulators, G, D and up
+ * to two layers), both sides of the pattern, 20 bytes per row and column, 16 bytes per work item (a row or a 1024-entry
+ * segment), 4 k bytes per segment of the rows above 1024 entries, 18 bytes per slot.
+ * mfx_lgcn_set_base copies the base embeddings W0 [rows][k], H0 [cols][k] (both required); stepping or reading before it
+ * is MFX_ERR_INVALID and leaves the handle usable.  mfx_lgcn_get_base returns the base, mfx_lgcn_get_factors the final
+ * embeddings of the current base (a forward pass), which serve mfx_rec_* as any (W, H).  mfx_lgcn_steps, _epochs and
+ * _position are those of mfx_bpr_*.  mfx_lgcn_kernel_times: stream seconds since create of the sampler, the forward pass,
+ * the gradient kernel, the scatter, the backward pass (with the collection of G) and the update, p->profile != 0 only.
+ * mfx_lgcn_propagate is the single operator of step 1 on host arrays: (W, H) from (W0, H0) over the host matrix R.
+ * mfx_lgcn_apply is the single operator of one step: the caller's n <= 2^20 triples, host base embeddings in place, a slot
+ * skipped only where skipped[t] != 0 (NULL: none), ids checked as mfx_bpr_apply does.  The solver's step is the sampler
+ * (mfx_bpr_triples) followed by exactly this code path.
+ * ---------------------------------------------------------------------------------- */
+typedef struct mfx_lgcn_s* mfx_lgcn_t;
+int mfx_lgcn_create(mfx_lgcn_t* out, const mfx_csx* R, const mfx_params* p, float lr, int64_t batch, int32_t layers,
+                    uint64_t seed, mfx_memspace space);
+int mfx_lgcn_set_base(mfx_lgcn_t s, const float* W0, const float* H0, mfx_memspace space);
+int mfx_lgcn_get_base(mfx_lgcn_t s, float* W0, float* H0, mfx_memspace space);
+int mfx_lgcn_get_factors(mfx_lgcn_t s, float* W, float* H, mfx_memspace space);
+int mfx_lgcn_steps(mfx_lgcn_t s, int64_t n_steps, int64_t stats[4], double* seconds);
+int mfx_lgcn_epochs(mfx_lgcn_t s, int32_t n_epochs, int64_t* stats /* [n_epochs][4] */, double* seconds /* [n_epochs] */);
+int mfx_lgcn_position(mfx_lgcn_t s, int64_t* next_slot);
+int mfx_lgcn_kernel_times(mfx_lgcn_t s, double seconds[6]);
+int mfx_lgcn_destroy(mfx_lgcn_t s);
+int mfx_lgcn_propagate(const mfx_csx* R, const float* W0, const float* H0, int64_t k, int32_t layers, float* W, float* H,
+                       int device);
+int mfx_lgcn_apply(const mfx_csx* R, int64_t k, float* W0, float* H0, int64_t n, const uint32_t* u, const uint32_t* i,
+                   const uint32_t* j, const uint8_t* skipped /* may be NULL */, int32_t layers, float lr, float lambda,
+                   int64_t stats[4], int device);
 
 /* ------------------------------------------------------------------------------------
  * Item-kNN: the neighbourhood model on the interaction matrix itself (Sarwar et al. 2001; cosine, TF-IDF and BM25
