@@ -9,6 +9,7 @@
 #include "bpr.hpp"
 #include "ccd_solver.hpp"
 #include "knn.hpp"
+#include "hybrid.hpp"
 #include "lgcn.hpp"
 #include "recommend.hpp"
 #include "slim.hpp"
@@ -536,6 +537,71 @@ int mfx_lgcn_propagate(const mfx_csx* R, const float* W0, const float* H0, int64
 int mfx_lgcn_apply(const mfx_csx* R, int64_t k, float* W0, float* H0, int64_t n, const uint32_t* u, const uint32_t* i, const uint32_t* j,
                    const uint8_t* skipped, int32_t layers, float lr, float lambda, int64_t stats[4], int device) {
     return guarded("mfx_lgcn_apply", [&]() -> int { return lgcn_apply(R, k, W0, H0, n, u, i, j, skipped, layers, lr, lambda, stats, device); });
+}
+
+/* ------------------------------------------------------------------ hybrid BPR: rows embedded through their features */
+int mfx_hyb_create(mfx_hyb_t* out, const mfx_csx* R, const mfx_features* Fu, const mfx_features* Fi, const mfx_params* p, float lr,
+                   int64_t batch, uint64_t seed, mfx_memspace space) {
+    return guarded("mfx_hyb_create", [&]() -> int {
+        return make_handle("mfx_hyb_create", out, [&](HybSolver** s) { return HybSolver::create(s, R, Fu, Fi, p, lr, batch, seed, space); });
+    });
+}
+int mfx_hyb_set_embeddings(mfx_hyb_t s, const float* Eu, const float* Ei, mfx_memspace space) {
+    return guarded("mfx_hyb_set_embeddings", [&]() -> int {
+        MFX_REQUIRE(s && s->impl, "null solver");
+        return s->impl->set_embeddings(Eu, Ei, space);
+    });
+}
+int mfx_hyb_get_embeddings(mfx_hyb_t s, float* Eu, float* Ei, mfx_memspace space) {
+    return guarded("mfx_hyb_get_embeddings", [&]() -> int {
+        MFX_REQUIRE(s && s->impl, "null solver");
+        return s->impl->get_embeddings(Eu, Ei, space);
+    });
+}
+int mfx_hyb_get_factors(mfx_hyb_t s, float* W, float* H, mfx_memspace space) {
+    return guarded("mfx_hyb_get_factors", [&]() -> int {
+        MFX_REQUIRE(s && s->impl, "null solver");
+        return s->impl->get_factors(W, H, space);
+    });
+}
+int mfx_hyb_steps(mfx_hyb_t s, int64_t n_steps, int64_t stats[4], double* seconds) {
+    return guarded("mfx_hyb_steps", [&]() -> int {
+        MFX_REQUIRE(s && s->impl, "null solver");
+        return s->impl->steps(n_steps, stats, seconds);
+    });
+}
+int mfx_hyb_epochs(mfx_hyb_t s, int32_t n_epochs, int64_t* stats, double* seconds) {
+    return guarded("mfx_hyb_epochs", [&]() -> int {
+        MFX_REQUIRE(s && s->impl, "null solver");
+        return s->impl->epochs(n_epochs, stats, seconds);
+    });
+}
+int mfx_hyb_position(mfx_hyb_t s, int64_t* next_slot) {
+    return guarded("mfx_hyb_position", [&]() -> int {
+        MFX_REQUIRE(s && s->impl && next_slot, "null solver or next_slot");
+        *next_slot = s->impl->position();
+        return MFX_OK;
+    });
+}
+int mfx_hyb_kernel_times(mfx_hyb_t s, double seconds[6]) {
+    return guarded("mfx_hyb_kernel_times", [&]() -> int {
+        MFX_REQUIRE(s && s->impl && seconds, "null solver or seconds");
+        s->impl->times(seconds);
+        return MFX_OK;
+    });
+}
+int mfx_hyb_destroy(mfx_hyb_t s) {
+    return guarded("mfx_hyb_destroy", [&]() -> int {
+        return destroy_handle(s);
+    });
+}
+int mfx_hyb_embed(const mfx_features* F, const float* E, int64_t k, float* out, int device) {
+    return guarded("mfx_hyb_embed", [&]() -> int { return hyb_embed(F, E, k, out, device); });
+}
+int mfx_hyb_apply(int64_t rows, int64_t cols, int64_t k, const mfx_features* Fu, const mfx_features* Fi, float* Eu, float* Ei, int64_t n,
+                  const uint32_t* u, const uint32_t* i, const uint32_t* j, const uint8_t* skipped, float lr, float lambda, int64_t stats[4],
+                  int device) {
+    return guarded("mfx_hyb_apply", [&]() -> int { return hyb_apply(rows, cols, k, Fu, Fi, Eu, Ei, n, u, i, j, skipped, lr, lambda, stats, device); });
 }
 
 /* ------------------------------------------------------------------ item-kNN: neighbour lists on the interaction matrix */

@@ -10,6 +10,7 @@ from .api import als_block_half  # noqa: F401
 from .api import BprSolver, bpr_apply, bpr_triples  # noqa: F401
 from .api import bpr_apply_neg, bpr_rank_weights, bpr_trials  # noqa: F401
 from .api import LightGcnSolver, lgcn_apply, lgcn_propagate  # noqa: F401
+from .api import HybFeatures, HybridSolver, hyb_apply, hyb_embed, hyb_features  # noqa: F401
 from .api import ItemKnn, knn_weights  # noqa: F401
 from .api import Slim, slim_gram, slim_solve  # noqa: F401
 from .api import Ease, ease_gram, ease_inverse, ease_weights_from_inverse  # noqa: F401

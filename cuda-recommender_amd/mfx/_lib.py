@@ -36,6 +36,10 @@ class mfx_coo(C.Structure):
     _fields_ = [("nnz", C.c_int64), ("row", C.c_void_p), ("col", C.c_void_p), ("val", C.c_void_p)]
 
 
+class mfx_features(C.Structure):
+    _fields_ = [("n", C.c_int64), ("nf", C.c_int64), ("ptr", C.c_void_p), ("idx", C.c_void_p), ("val", C.c_void_p)]
+
+
 class mfx_params(C.Structure):
     _fields_ = [("k", C.c_uint32), ("lambda_", C.c_float), ("maxiter", C.c_int32), ("maxinneriter", C.c_int32),
                 ("nBlocks", C.c_uint32), ("nThreadsPerBlock", C.c_uint32), ("verbose", C.c_int32),
@@ -161,6 +165,19 @@ SIGNATURES = {
     "mfx_lgcn_propagate": (C.c_int, [C.POINTER(mfx_csx), f32p, f32p, C.c_int64, C.c_int32, f32p, f32p, C.c_int]),
     "mfx_lgcn_apply": (C.c_int, [C.POINTER(mfx_csx), C.c_int64, f32p, f32p, C.c_int64, u32p, u32p, u32p, C.c_void_p, C.c_int32,
                                  C.c_float, C.c_float, i64p, C.c_int]),
+    "mfx_hyb_create": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(mfx_csx), C.POINTER(mfx_features), C.POINTER(mfx_features),
+                                 C.POINTER(mfx_params), C.c_float, C.c_int64, C.c_uint64, C.c_int]),
+    "mfx_hyb_set_embeddings": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    "mfx_hyb_get_embeddings": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    "mfx_hyb_get_factors": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    "mfx_hyb_steps": (C.c_int, [C.c_void_p, C.c_int64, i64p, f64p]),
+    "mfx_hyb_epochs": (C.c_int, [C.c_void_p, C.c_int32, i64p, f64p]),
+    "mfx_hyb_position": (C.c_int, [C.c_void_p, i64p]),
+    "mfx_hyb_kernel_times": (C.c_int, [C.c_void_p, f64p]),
+    "mfx_hyb_destroy": (C.c_int, [C.c_void_p]),
+    "mfx_hyb_embed": (C.c_int, [C.POINTER(mfx_features), C.c_void_p, C.c_int64, C.c_void_p, C.c_int]),
+    "mfx_hyb_apply": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.POINTER(mfx_features), C.POINTER(mfx_features), C.c_void_p, C.c_void_p,
+                                C.c_int64, u32p, u32p, u32p, C.c_void_p, C.c_float, C.c_float, i64p, C.c_int]),
     "mfx_knn_build": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(mfx_csx), C.c_int32, C.c_int32, C.c_int, C.c_int]),
     "mfx_knn_create_from_lists": (C.c_int, [C.POINTER(C.c_void_p), C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
     "mfx_knn_lists": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),

@@ -891,6 +891,203 @@ def lgcn_apply(R: RatingData, W0, H0, u, i, j, layers: int, lr: float, lam: floa
 
 
 # ---------------------------------------------------------------------------------------------
+# hybrid BPR: rows embedded through their features (mfx_hyb_*)
+# ---------------------------------------------------------------------------------------------
+@dataclass
+class HybFeatures:
+    """A feature matrix in CSR with values (mfx_features, include/mfx.h "Hybrid BPR"): n rows over nf features, ptr [n + 1]
+    uint32, idx [nnz] uint32 strictly ascending inside a row, val [nnz] float32 with |v| <= 1, at most 1024 entries a row."""
+    n: int
+    nf: int
+    ptr: np.ndarray
+    idx: np.ndarray
+    val: np.ndarray
+
+    def to_c(self) -> L.mfx_features:
+        for a, dt in ((self.ptr, np.uint32), (self.idx, np.uint32), (self.val, np.float32)):
+            assert isinstance(a, np.ndarray) and a.dtype == dt and a.flags["C_CONTIGUOUS"], "need C-contiguous uint32 / float32 arrays"
+        assert self.ptr.shape == (self.n + 1,) and self.idx.shape == self.val.shape and self.idx.ndim == 1
+        return L.mfx_features(int(self.n), int(self.nf), _vp(self.ptr), _vp(self.idx), _vp(self.val))
+
+
+def hyb_features(n: int, tag_rows=None, tag_ids=None, n_tags: int = 0, identity: bool = True, normalize: bool = True) -> HybFeatures:
+    """LightFM's default feature matrix [I | tags] of n rows: feature r for row r itself (identity=True), then feature n + t
+    (identity=False: t) for every pair (tag_rows[e], tag_ids[e]) = (row, t), a pair named twice counting once.  Every entry
+    is 1, or with normalize=True float32(1 / entries of the row), so that a row sums to 1: this keeps |v| <= 1."""
+    n, n_tags = int(n), int(n_tags)
+    r = np.zeros(0, np.int64) if tag_rows is None else np.asarray(tag_rows, np.int64).ravel()
+    t = np.zeros(0, np.int64) if tag_ids is None else np.asarray(tag_ids, np.int64).ravel()
+    assert r.shape == t.shape, "tag_rows and tag_ids must pair up"
+    assert r.size == 0 or (r.min() >= 0 and r.max() < n and t.min() >= 0 and t.max() < n_tags), "a tag pair is out of range"
+    base = n if identity else 0
+    nf = base + n_tags
+    assert nf >= 1, "no features: identity=False needs n_tags >= 1"
+    cells = np.unique(r * nf + base + t)  # row * nf + feature: ascending by row, then by feature
+    if identity:
+        cells = np.sort(np.concatenate([np.arange(n, dtype=np.int64) * (nf + 1), cells]))
+    rows, idx = cells // nf, cells % nf
+    counts = np.bincount(rows, minlength=n)
+    ptr = np.concatenate([[0], np.cumsum(counts)])
+    assert ptr[-1] < 2 ** 32 and (counts.max() if n else 0) <= 1024, "a row may hold at most 1024 features"
+    val = np.ones(rows.size, np.float32)
+    if normalize:
+        val = (1.0 / counts[rows]).astype(np.float32)
+    return HybFeatures(n, nf, ptr.astype(np.uint32), idx.astype(np.uint32), val)
+
+
+def _features_c(F: Optional[HybFeatures], n: int, what: str):
+    if F is None:
+        return None, n
+    assert isinstance(F, HybFeatures), f"{what} must be a HybFeatures (mfx.hyb_features) or None"
+    return C.byref(F.to_c()), int(F.nf)
+
+
+class HybridSolver:
+    """Resident hybrid BPR training (mfx_hyb_*, include/mfx.h "Hybrid BPR"): BprSolver's deterministic mini-batch steps on
+    rows whose vectors are the weighted sums of the embeddings of their features, so that a row without interactions still
+    has a vector.  user_features / item_features are HybFeatures (mfx.hyb_features builds LightFM's [I | tags]); None is the
+    identity, and with None on both sides the solver is BprSolver bit for bit.  Reads k, lambda_, device and profile of
+    `parameters`; R's CSR pattern is read, values ignored; uniform negatives only.  The tables are Eu [nfu][k] and Ei
+    [nfi][k]; without set_embeddings the first step draws 0.1 * N(0, 1) from numpy.random.default_rng(init_seed), Eu then
+    Ei -- BprSolver's draw when both sides are identities.  get_factors() returns the embeddings (W, H) of all rows, which
+    serve Recommender, query, evaluate, IVF and MMR as any factors do; embed(side, F) gives the rows of any other feature
+    matrix over the same features: the cold start."""
+
+    def __init__(self, R: Optional[RatingData], parameters: parameter, lr: float, batch: int, user_features: Optional[HybFeatures] = None,
+                 item_features: Optional[HybFeatures] = None, seed: int = 0, device_arrays: Optional[dict] = None,
+                 init_seed: Optional[int] = None):
+        self.handle = C.c_void_p()
+        cp = parameters.to_c()
+        self.device = int(parameters.device)
+        if device_arrays is not None:
+            self.rows, self.cols, self.k = int(device_arrays["rows"]), int(device_arrays["cols"]), int(parameters.k)
+            csx, space = _device_csx_coo(device_arrays)[0], L.MFX_DEVICE
+        else:
+            self.rows, self.cols, self.k = R.rows, R.cols, int(parameters.k)
+            csx, space = _csx(R), L.MFX_HOST
+        keep = []  # the device copies of the feature arrays live until create returns
+
+        def side(F, n, what):
+            if F is None:
+                return None, n
+            assert isinstance(F, HybFeatures), f"{what} must be a HybFeatures (mfx.hyb_features) or None"
+            c = F.to_c()
+            if space == L.MFX_DEVICE:
+                import torch
+                dev = device_arrays["csr_row_ptr"].device
+                t = [torch.from_numpy(a.view(np.int32) if a.dtype == np.uint32 else a).to(dev) for a in (F.ptr, F.idx, F.val)]
+                keep.extend(t)
+                c = L.mfx_features(int(F.n), int(F.nf), *(C.c_void_p(int(x.data_ptr())) if x.numel() else None for x in t))
+            keep.append(c)
+            return C.byref(c), int(F.nf)
+
+        fu, self.nfu = side(user_features, self.rows, "user_features")
+        fi, self.nfi = side(item_features, self.cols, "item_features")
+        self._init_seed, self._have_tables = init_seed, False
+        L.check(L.lib().mfx_hyb_create(C.byref(self.handle), C.byref(csx), fu, fi, C.byref(cp), float(lr), int(batch), int(seed), space))
+
+    def set_embeddings(self, Eu, Ei):
+        _f32c(Eu, (self.nfu, self.k))
+        _f32c(Ei, (self.nfi, self.k))
+        L.check(L.lib().mfx_hyb_set_embeddings(self.handle, _vp(Eu), _vp(Ei), L.MFX_HOST))
+        self._have_tables = True
+
+    def _default_tables(self):
+        if not self._have_tables:
+            rng = np.random.default_rng(self._init_seed)
+            Eu = (0.1 * rng.standard_normal((self.nfu, self.k))).astype(np.float32)
+            Ei = (0.1 * rng.standard_normal((self.nfi, self.k))).astype(np.float32)
+            self.set_embeddings(Eu, Ei)
+
+    def get_embeddings(self):
+        """The embedding tables (Eu, Ei): what the steps update."""
+        Eu = np.empty((self.nfu, self.k), np.float32)
+        Ei = np.empty((self.nfi, self.k), np.float32)
+        L.check(L.lib().mfx_hyb_get_embeddings(self.handle, _vp(Eu), _vp(Ei), L.MFX_HOST))
+        return Eu, Ei
+
+    def get_factors(self):
+        """The embeddings (W, H) of all rows at the current tables: hyb_embed of either feature matrix."""
+        W = np.empty((self.rows, self.k), np.float32)
+        H = np.empty((self.cols, self.k), np.float32)
+        L.check(L.lib().mfx_hyb_get_factors(self.handle, _vp(W), _vp(H), L.MFX_HOST))
+        return W, H
+
+    def embed(self, side: str, F: HybFeatures) -> np.ndarray:
+        """The rows of F over the current table of `side` ("user" or "item"): rows that were not in R included."""
+        if side not in ("user", "item"):
+            raise ValueError('side must be "user" or "item"')
+        E = self.get_embeddings()[side == "item"]
+        return hyb_embed(F, E, device=self.device)
+
+    def steps(self, n: int) -> dict:
+        """n steps from the current slot: {"slots", "skipped", "bad", "correct", "auc", "seconds"} of the call."""
+        self._default_tables()
+        stats, sec = (C.c_int64 * 4)(), C.c_double(0.0)
+        L.check(L.lib().mfx_hyb_steps(self.handle, int(n), stats, C.byref(sec)))
+        return _bpr_report(stats, sec.value)
+
+    def iterate(self, n_epochs: int) -> List[dict]:
+        """n_epochs epochs (the first finishes a started one): one report per epoch."""
+        self._default_tables()
+        n = int(n_epochs)
+        stats, sec = (C.c_int64 * (4 * max(1, n)))(), (C.c_double * max(1, n))()
+        L.check(L.lib().mfx_hyb_epochs(self.handle, n, stats, sec))
+        return [_bpr_report(stats[4 * e:4 * e + 4], sec[e]) for e in range(n)]
+
+    def position(self) -> int:
+        out = C.c_int64(0)
+        L.check(L.lib().mfx_hyb_position(self.handle, C.byref(out)))
+        return int(out.value)
+
+    def kernel_times(self) -> dict:
+        """Stream seconds since create by phase, collected with parameters.profile = 1 only."""
+        out = (C.c_double * 6)()
+        L.check(L.lib().mfx_hyb_kernel_times(self.handle, out))
+        return dict(zip(("sample", "embed", "gradient", "scatter", "spread", "apply"), (float(x) for x in out)))
+
+    def close(self):
+        if self.handle:
+            L.lib().mfx_hyb_destroy(self.handle)
+            self.handle = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def hyb_embed(F: HybFeatures, E, device: int = 0) -> np.ndarray:
+    """The embeddings [F.n][k] of the rows of F over the table E [F.nf][k] (mfx_hyb_embed): per coordinate the FMA chain of
+    the row's entries in stored order, started from the first product; an empty row gives +0."""
+    E = _f32c(E)
+    assert isinstance(F, HybFeatures) and E.ndim == 2 and E.shape[0] == F.nf, "E must hold one row per feature of F"
+    out = np.empty((F.n, E.shape[1]), np.float32)
+    c = F.to_c()
+    L.check(L.lib().mfx_hyb_embed(C.byref(c), _vp(E), E.shape[1], _vp(out), device))
+    return out
+
+
+def hyb_apply(rows: int, cols: int, Eu, Ei, u, i, j, lr: float, lam: float, user_features: Optional[HybFeatures] = None,
+              item_features: Optional[HybFeatures] = None, skipped=None, device: int = 0):
+    """One hybrid step on the given triples at the tables Eu [nfu][k], Ei [nfi][k] (mfx_hyb_apply): returns (Eu', Ei',
+    stats); None features are the identity; a slot is skipped only where `skipped` says so."""
+    Eu, Ei = np.array(_f32c(Eu)), np.array(_f32c(Ei))
+    fu, nfu = _features_c(user_features, int(rows), "user_features")
+    fi, nfi = _features_c(item_features, int(cols), "item_features")
+    assert Eu.ndim == 2 and Ei.ndim == 2 and Eu.shape[1] == Ei.shape[1] and Eu.shape[0] == nfu and Ei.shape[0] == nfi
+    u, i, j = (np.ascontiguousarray(a, np.uint32) for a in (u, i, j))
+    assert u.shape == i.shape == j.shape and u.ndim == 1
+    s = None if skipped is None else np.ascontiguousarray(skipped, np.uint8)
+    assert s is None or s.shape == u.shape
+    stats = (C.c_int64 * 4)()
+    L.check(L.lib().mfx_hyb_apply(int(rows), int(cols), Eu.shape[1], fu, fi, _vp(Eu), _vp(Ei), u.shape[0], _u32(u), _u32(i), _u32(j), _vp(s),
+                                  float(lr), float(lam), stats, device))
+    return Eu, Ei, _bpr_report(stats, 0.0)
+
+
+# ---------------------------------------------------------------------------------------------
 # item-kNN: the neighbourhood model on the interaction matrix (mfx_knn_*)
 # ---------------------------------------------------------------------------------------------
 def knn_weights(R: RatingData, scheme: Optional[str], k1: float = 1.2, b: float = 0.75) -> RatingData:

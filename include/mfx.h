@@ -551,6 +551,83 @@ int mfx_lgcn_apply(const mfx_csx* R, int64_t k, float* W0, float* H0, int64_t n,
                    int64_t stats[4], int device);
 
 /* ------------------------------------------------------------------------------------
+ * Hybrid BPR: BPR training on rows whose vectors are the weighted sums of the embeddings of their features (the model of
+ * LightFM, Kula 2015, without biases).  A row that has no interaction still has a vector, so an item that was never rated
+ * can be scored: the cold start.  Sampler, score chain, sigmoid, bad rule, fixed-point sums and counts are those of "BPR
+ * training" above.  Every bit of the embedding tables is fixed by (data, features, seed, parameters, batch): no bit
+ * depends on lanes per row, launch geometry, batch of loads or order of arrival.
+ *
+ * Data.  R is read as in "BPR training": the CSR side, values ignored.  Two feature matrices in CSR with values, Fu
+ * [rows] x nfu and Fi [cols] x nfi (mfx_features: n rows, nf features, ptr [n + 1], idx and val [ptr[n]]), and two
+ * embedding tables Eu [nfu][k], Ei [nfi][k], 1 <= k <= 1024.  Rules of a feature matrix: the pointers run from 0 to the
+ * number of entries, the ids are strictly ascending inside a row and below nf, every value is finite with |v| <= 1, a row
+ * holds at most 1024 entries; empty rows are allowed.  All of it is checked on the device at create (MFX_ERR_INVALID
+ * naming the first offending row).  A NULL feature matrix is the identity (nf = n, the entry (r, 1) in row r); it gives the
+ * bits of the identity passed explicitly.
+ * The embedding of row r, coordinate c, with the entries (f_0, v_0) .. (f_{n-1}, v_{n-1}) in stored order:
+ *   acc = fp32(v_0 * E[f_0][c]);  acc = fmaf(v_e, E[f_e][c], acc) for e = 1 .. n-1;  an empty row gives +0.
+ * The chain starts from the first product and not from +0, so a row of the identity returns E's bits, -0 included.
+ *
+ * One step on n <= batch slots (u, i, j, skipped):
+ *   1. W[u], H[i], H[j] = the embeddings of the slots' rows at the tables of before the step;
+ *   2. the step of "BPR training" on those rows up to its sums, unchanged: g, the states, the bad rule, the counts, the
+ *      2^-36 fixed-point sums of a row and m_r = the counted slots of row r;
+ *   3. for every row with m_r > 0: G[r][c] = the fp32 nearest to the row's sum (one rounding int64 -> fp32, then the exact
+ *      scale), as in step 3 of "LightGCN";
+ *   4. for every such row and every entry (f, v) of it: the term fp32(v * G[r][c]), truncated toward zero to a multiple of
+ *      2^-36, is added exactly (64-bit integers) into the accumulator of feature f, and m_r is added to m_f;
+ *   5. every feature with m_f > 0: a_c = the fp32 nearest to its sum, and
+ *        new = fp32(old + fp32(lr * fp32(a_c - fp32(fp32(lambda * fp32(m_f)) * old))));  other features keep their bits.
+ * Limits.  |term| <= |G| < 64 m_r, so the conversion of a term is valid up to 2^27 (not only below 64 as for the terms of a
+ * slot).  With |v| <= 1 the sum of a feature is at most 64 times the sum of m_r over the rows that carry it, at most
+ * 64 * 2^21 = 2^27: the limit of a row in "BPR training", so no new bad rule is needed.
+ * With the identity on both sides the step is that of mfx_bpr_apply bit for bit: G is a multiple of 2^-36, so fp32(1 * G)
+ * = G truncates to itself, the feature's sum is the row's sum rounded once, rounding it again returns G, and m_f = m_r.
+ * As in BPR a batch is the sum of its slots' steps at frozen parameters: lr * lambda * m_f of a feature that every row
+ * carries grows with the batch and can be large; choose lr and lambda for the batch.
+ *
+ * mfx_hyb_create reads k, lambda, device and profile of *p; Fu and Fi live in `space` as R does.  MFX_ERR_INVALID without
+ * touching the device: what mfx_bpr_create refuses, a feature matrix whose n is not rows (cols), nf = 0 or nf >= 2^32 - 1,
+ * a NULL ptr.  Memory on the device: what mfx_bpr_create takes (its factors are scratch for the embedded rows), the
+ * feature matrices (12 bytes per row of an identity), and per feature 12 k + 8 bytes (the table, its accumulators, count
+ * and claim).  After create no step's cost grows with rows + cols or with nfu + nfi: only the rows of the slots are
+ * embedded and only their features are updated.
+ * mfx_hyb_set_embeddings copies Eu and Ei (both required); stepping or reading before it is MFX_ERR_INVALID and leaves the
+ * handle usable.  mfx_hyb_get_embeddings returns the tables (either may be NULL), mfx_hyb_get_factors the embeddings of
+ * all rows W [rows][k], H [cols][k] (a NULL side is not computed), which serve mfx_rec_* as any (W, H).  mfx_hyb_steps, _epochs and _position are those of
+ * mfx_bpr_*; only uniform negatives.  mfx_hyb_kernel_times: stream seconds since create of the sampler, the embedding, the
+ * gradient kernel, the scatter, the spread to the features and the apply, p->profile != 0 only.
+ * mfx_hyb_embed is the single operator of the embedding on host arrays: out [F->n][k] from E [F->nf][k], any number of
+ * rows.  It is also the cold start: the rows of items that were not in R, which the caller appends to H.
+ * mfx_hyb_apply is the single operator of one step: the caller's n <= 2^20 triples, host feature matrices (NULL: the
+ * identity) and host tables in place, a slot skipped only where skipped[t] != 0 (NULL: none), ids checked as mfx_bpr_apply
+ * does (the tables are left as they were).  The solver's step is the sampler (mfx_bpr_triples) followed by exactly this
+ * code path.
+ * Left out: biases, trials (hardest of M and WARP would need the trial items embedded first), AdaGrad, several GPUs.
+ * ---------------------------------------------------------------------------------- */
+typedef struct mfx_features {
+    int64_t n, nf;       /* rows, features */
+    const uint32_t* ptr; /* [n + 1] */
+    const uint32_t* idx; /* [ptr[n]] */
+    const float* val;    /* [ptr[n]] */
+} mfx_features;
+typedef struct mfx_hyb_s* mfx_hyb_t;
+int mfx_hyb_create(mfx_hyb_t* out, const mfx_csx* R, const mfx_features* Fu /* or NULL */, const mfx_features* Fi /* or NULL */,
+                   const mfx_params* p, float lr, int64_t batch, uint64_t seed, mfx_memspace space);
+int mfx_hyb_set_embeddings(mfx_hyb_t s, const float* Eu, const float* Ei, mfx_memspace space);
+int mfx_hyb_get_embeddings(mfx_hyb_t s, float* Eu, float* Ei, mfx_memspace space);
+int mfx_hyb_get_factors(mfx_hyb_t s, float* W, float* H, mfx_memspace space);
+int mfx_hyb_steps(mfx_hyb_t s, int64_t n_steps, int64_t stats[4], double* seconds);
+int mfx_hyb_epochs(mfx_hyb_t s, int32_t n_epochs, int64_t* stats /* [n_epochs][4] */, double* seconds /* [n_epochs] */);
+int mfx_hyb_position(mfx_hyb_t s, int64_t* next_slot);
+int mfx_hyb_kernel_times(mfx_hyb_t s, double seconds[6]);
+int mfx_hyb_destroy(mfx_hyb_t s);
+int mfx_hyb_embed(const mfx_features* F, const float* E, int64_t k, float* out, int device);
+int mfx_hyb_apply(int64_t rows, int64_t cols, int64_t k, const mfx_features* Fu /* or NULL */, const mfx_features* Fi /* or NULL */,
+                  float* Eu, float* Ei, int64_t n, const uint32_t* u, const uint32_t* i, const uint32_t* j,
+                  const uint8_t* skipped /* may be NULL */, float lr, float lambda, int64_t stats[4], int device);
+
+/* ------------------------------------------------------------------------------------
  * Item-kNN: the neighbourhood model on the interaction matrix itself (Sarwar et al. 2001; cosine, TF-IDF and BM25
  * weightings as in the usual libraries).  Every bit of the lists and of the scores is fixed by the data: the sums are
  * exact integer sums, so no order of summation, batch or tile width plays a part.
